@@ -19,6 +19,16 @@ by the CPU oracle on this very config): it prices BVH-node, triangle and attribu
 L2 serve them, so it can exceed the peak and bounds nothing on small scenes. `traffic` (PMC FETCH_SIZE / WRITE_SIZE) and
 `valu` (instruction-issue counters) come from committed rocprofv3 passes of this command and name their source file.
 cpu_baseline: the oracle (a port; the reference has no CPU path) timed on all host cores of the box.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config). Everything above that takes runs of its own -- one_frame_in_flight, roofline (the HRPT_FRAME_PROFILE pass),
+per_rank / rank_balance, cpu_baseline -- is measured only with --full.
+
+--dump-outputs DIR writes what the last timed step computed, after the timed region, as float32 / float64 .npy files:
+output.npy (the resolved RGBA32F Output image), accumulation.npy (N = 1: the RGBA32F Accumulation image), rays_per_step.npy (float64
+[closest, shadow] rays of one step). An image above its byte budget is replaced by a fixed sample of its pixels (rows of RGBA, pixel
+indices k * 2654435761 mod (W * H) for k = 0.., sorted; a prime multiplier, so distinct), and the file name says `_sample`: the dump
+stays below 64 MB at any size. The inputs of a run are fully determined by its arguments.
 """
 import argparse
 import json
@@ -79,6 +89,34 @@ def _baseline_metric():
         return "Mrays/s at 1920\u00d71080, 8 spp, 4 bounces; 1/2/4/8 GPU scaling"
 
 
+_SAMPLE_STRIDE = 2654435761          # prime: k * stride mod (W * H) visits distinct pixels for k < W * H
+
+
+def _pixels(image, max_bytes):
+    """(name suffix, array): the RGBA image as it is when it fits in max_bytes, else a fixed sample of its pixels as rows of RGBA."""
+    if image.nbytes <= max_bytes:
+        return "", image
+    flat = image.reshape(-1, image.shape[-1])
+    n = max_bytes // flat[0].nbytes
+    idx = np.sort((np.arange(n, dtype=np.uint64) * np.uint64(_SAMPLE_STRIDE)) % np.uint64(len(flat)))
+    return "_sample", flat[idx.astype(np.int64)]
+
+
+def _dump_outputs(out_dir, output, accumulation, rays_per_step):
+    """--dump-outputs: the last timed step's images and ray counts as .npy; 40 + 16 MB at most (< 64 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"rays_per_step": rays_per_step}
+    suffix, a = _pixels(output, 40_000_000)
+    arrays["output" + suffix] = a
+    if accumulation is not None:
+        suffix, a = _pixels(accumulation, 16_000_000)
+        arrays["accumulation" + suffix] = a
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    print(f"bench: wrote {', '.join(n + '.npy' for n in arrays)} to {out_dir}", file=sys.stderr)
+
+
 def _launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher (WORLD_SIZE unset): start the N ranks as FRESH child processes through
     torch.distributed.run -- one per GPU, rendezvous on 127.0.0.1 at a free port -- relay their output (rank 0 prints the JSON line) and
@@ -108,7 +146,11 @@ def main(argv=None):
     ap.add_argument("--bounces", type=int, default=None, help="default: BASELINE.json's value for the config (4 / 8 / 12)")
     ap.add_argument("--cpu-cores", type=int, default=0, help="threads of the cpu_baseline leg (default: every core this process may run on)")
     ap.add_argument("--mode", choices=["default", "megakernel", "wavefront"], default="default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: one_frame_in_flight, roofline (a profiled pass), per_rank, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="rehearsal only: all ranks share GPU 0 and the all-gather runs over gloo through host memory; the printed value is NOT a result")
     ap.add_argument("--serial-gather", action="store_true", help="N>1: all-gather in stream order after each render instead of overlapping it with the next frame")
@@ -126,6 +168,8 @@ def main(argv=None):
     ap.add_argument("--config", type=int, default=2, choices=[2, 4, 5],
                     help="BASELINE.json config: 2 = headline (Cornell-class), 4 = Sponza-class stand-in, 5 = glass stress stand-in")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher (it has touched neither torch nor HIP) and exits with the ranks' status
@@ -244,13 +288,14 @@ def main(argv=None):
                                  resolve_columns=lambda sh, acc, out, stream: ctx.resolve_columns_device(sh.data_ptr(), acc.data_ptr() if acc is not None else 0, out.data_ptr(), W, H, world, stream),
                                  keep_accumulation=False)
     step_no = [0]
+    last_slot = [0]                                             # pipelined: the slot of frames.output that holds the last step's image
 
     def step():
         if not sharded:
             lanes[step_no[0] % len(lanes)].render(cb, accum_count=spp, flags=flags)   # step k on lane k % L: L frames in flight
             step_no[0] += 1
         elif pipelined:
-            frames.submit()
+            last_slot[0] = frames.submit()
         else:
             render_sharded(render_band, full, rank, world, all_gather)                   # the single collective
             if not same_stream:
@@ -291,11 +336,33 @@ def main(argv=None):
         shadowRays = sum(int(c.stats().shadowRays) for c in lanes)
         lastRenderMs = float(ctx.stats().lastRenderMs)
     st = _Sum
+    red_dev = torch.device("cpu") if rehearse else dev
+    my_elapsed = elapsed
+    tm = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
+    rays = torch.tensor([float(st.closestRays + st.shadowRays), float(st.closestRays), float(st.shadowRays)], dtype=torch.float64, device=red_dev)
+    if sharded:
+        dist.all_reduce(tm, op=dist.ReduceOp.MAX)
+        dist.all_reduce(rays, op=dist.ReduceOp.SUM)
+    elapsed = float(tm.item())
+    total_rays, closest_total, shadow_total = (float(x) for x in rays.tolist())
+
+    if args.dump_outputs and rank == 0:
+        # before anything else renders: the images of the last timed step are still where that step left them
+        if not sharded:
+            last = lanes[(step_no[0] - 1) % len(lanes)]
+            output, accumulation = last.read_output(), last.read_accumulation()
+        elif pipelined:
+            output, accumulation = frames.output[last_slot[0]].cpu().numpy(), None
+        else:
+            output, accumulation = ctx.read_output(), None
+        _dump_outputs(args.dump_outputs, output, accumulation, np.array([closest_total, shadow_total], np.float64) / args.steps)
+
     if lane_streams is not None:
         ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    # reference point outside the timed region: the same steps one frame at a time (lane 0 only, frames back to back on one stream)
+    # --full only from here on: measurements that take runs of their own, all outside the timed region
+    # reference point: the same steps one frame at a time (lane 0 only, frames back to back on one stream)
     one_at_a_time_ms = None
-    if not sharded and len(lanes) > 1:
+    if args.full and not sharded and len(lanes) > 1:
         n1 = max(2, min(args.steps, 10))
         ctx.synchronize()
         ctx.set_shadow_overlap(True)                         # what a one-frame-at-a-time host would use
@@ -307,9 +374,9 @@ def main(argv=None):
         ctx.synchronize()
         one_at_a_time_ms = (time.perf_counter() - t1) / n1 * 1e3
         ctx.set_shadow_overlap(False)
-    # per-kernel-class device times: a few extra steps with HRPT_FRAME_PROFILE (events around every launch), outside the timed region
+    # per-kernel-class device times: a few extra steps with HRPT_FRAME_PROFILE (events around every launch)
     prof_steps = 0
-    if args.mode != "megakernel":
+    if args.full and args.mode != "megakernel":
         prof_steps = 3
         ctx.reset_stats()
         for _ in range(prof_steps):
@@ -317,20 +384,10 @@ def main(argv=None):
         ctx.synchronize()
         pst = ctx.stats()
 
-    red_dev = torch.device("cpu") if rehearse else dev
-    my_elapsed = elapsed
-    tm = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
-    rays = torch.tensor([float(st.closestRays + st.shadowRays), float(st.closestRays), float(st.shadowRays)], dtype=torch.float64, device=red_dev)
-    if sharded:
-        dist.all_reduce(tm, op=dist.ReduceOp.MAX)
-        dist.all_reduce(rays, op=dist.ReduceOp.SUM)
-    elapsed = float(tm.item())
-    total_rays, closest_total, shadow_total = (float(x) for x in rays.tolist())
-
     # per-rank breakdown for the sharded runs (the first hardware SCALE run should explain itself): render time of this rank's share
     # alone (HRPT_FRAME_PROFILE pass above, lastRenderMs = device time of one hrpt_render) and what the gather pipeline adds per step
     per_rank = None
-    if sharded:
+    if args.full and sharded:
         mine = torch.tensor([float(pst.lastRenderMs) if prof_steps else 0.0, my_elapsed / args.steps * 1e3,
                              frames.gather_ms() if frames is not None else 0.0, comm_wait_ms], dtype=torch.float64, device=red_dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -365,7 +422,7 @@ def main(argv=None):
                                       "slowest_over_mean_render_alone": (max(r["render_ms_alone"] for r in per_rank) / max(1e-9, sum(r["render_ms_alone"] for r in per_rank) / len(per_rank)))}
         # ---- cpu_baseline + n/t counters: the oracle on a bounded sample of THIS config (N = 1 only)
         model = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle.binding import Oracle, OrStats
             o = Oracle(sc)
             ost = OrStats()
@@ -459,7 +516,7 @@ def main(argv=None):
                         + "On config 2 wf_extend and wf_shade take the same time to within 2 %, so which of the two is named here can change from run to "
                           "run: 'kernels' has time, bytes and frac_of_hbm_peak of every class, 'whole_step' the figure for all classes of a frame together.",
             }
-        else:
+        elif args.full:
             # megakernel: one launch per accumulation index does the whole dispatch; its HBM traffic is the 48 B per pixel of the image streams
             avg_ms = st.lastRenderMs / spp
             per_launch_bytes = W * H * 48.0 / world

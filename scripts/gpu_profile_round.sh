@@ -5,9 +5,9 @@ export TMPDIR=/tmp
 make -C oracle >/dev/null
 OUT=gpurun_out/round
 rm -rf $OUT; mkdir -p $OUT
-python3 bench.py --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 # one frame in flight under the profiler: with two, every kernel shares the GPU with the other lane's kernels and its begin-to-end span is not its cost
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --frames-in-flight 1 > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --frames-in-flight 1 > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --frames-in-flight 1 > /dev/null 2> $OUT/pmc_fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --frames-in-flight 1 > /dev/null 2> $OUT/pmc_write.err

@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -2 $OUT/gpu_tests.log
 fi
 for cfg in ${CONFIGS:-2 4 5}; do
-  timeout -k 10 400 python3 bench.py --config $cfg --steps ${STEPS:-10} --warmup 3 ${BENCH_EXTRA:-} > $OUT/bench_config$cfg.json 2> $OUT/bench_config$cfg.err || { tail -20 $OUT/bench_config$cfg.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --config $cfg --steps ${STEPS:-10} --warmup 3 ${BENCH_EXTRA:-} > $OUT/bench_config$cfg.json 2> $OUT/bench_config$cfg.err || { tail -20 $OUT/bench_config$cfg.err; exit 1; }
   python3 - $OUT/bench_config$cfg.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

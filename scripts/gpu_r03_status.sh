@@ -2,7 +2,7 @@
 set -e
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r03/status; mkdir -p $OUT
-for cfg in 2 4 5; do python3 bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_config$cfg.json 2> $OUT/bench_config$cfg.err; done
+for cfg in 2 4 5; do python3 bench.py --full --config $cfg --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_config$cfg.json 2> $OUT/bench_config$cfg.err; done
 python3 - <<'PY'
 import json
 for c in (2, 4, 5):

@@ -10,6 +10,6 @@ import json,sys
 d=json.loads([l for l in sys.stdin.read().strip().splitlines() if l.startswith('{')][-1])
 print(sys.argv[1], 'ms_per_step %.3f Mrays/s %.0f kernel %s frac %.2f'%(d['ms_per_step'],d['value'],d['roofline']['kernel'],d['roofline']['frac']), d['config']['sharding'])
 " "$1"; }
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | show "plain N=1     "
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --force-sharded 2>/dev/null | show "sharded pipelined"
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --force-sharded --serial-gather 2>/dev/null | show "sharded serial "
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | show "plain N=1     "
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --force-sharded 2>/dev/null | show "sharded pipelined"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --force-sharded --serial-gather 2>/dev/null | show "sharded serial "

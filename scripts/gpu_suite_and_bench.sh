@@ -7,7 +7,7 @@ timeout -k 10 900 python -m pytest tests -x -q -m gpu > gpurun_out/parity.log 2>
 tail -2 gpurun_out/parity.log
 rm -f gpurun_out/bench_cfgs.log
 for cfg in 2 4 5; do
-  timeout -k 10 300 python bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  timeout -k 10 300 python bench.py --full --config $cfg --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['roofline']['kernels']

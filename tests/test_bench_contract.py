@@ -1,5 +1,6 @@
 """The bench line's contract (the driver parses it): checked on the committed lines of rounds 2 and 3 (profiles/r0N_bench_*.json, written by
-`python bench.py [--config N]` on an MI355X) and on bench.py's command line. No GPU needed."""
+`python bench.py [--config N]` on an MI355X, what `python bench.py --full [--config N]` writes now) and on bench.py's command line. No GPU
+needed, except for the last test (a plain run and its --dump-outputs)."""
 import json
 import os
 import subprocess
@@ -53,8 +54,31 @@ def test_committed_bench_lines_keep_the_contract(name, config):
 def test_bench_command_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--config", "--serial-kernels", "--frames-in-flight"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--serial-kernels", "--frames-in-flight", "--full", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_dump_outputs_are_float_bounded_and_fixed(tmp_path):
+    """--dump-outputs at the headline size: Output in full, Accumulation as a fixed sample of distinct pixels, float32 / float64, < 64 MB."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    H, W = 1080, 1920
+    out = np.arange(H * W * 4, dtype=np.float32).reshape(H, W, 4)
+    acc = out * 2
+    bench._dump_outputs(str(tmp_path), out, acc, np.array([3.0, 4.0]))
+    names = sorted(os.listdir(tmp_path))
+    assert names == ["accumulation_sample.npy", "output.npy", "rays_per_step.npy"]
+    assert sum(os.path.getsize(tmp_path / n) for n in names) < 64e6
+    a = np.load(tmp_path / "output.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, out)
+    s = np.load(tmp_path / "accumulation_sample.npy")
+    assert s.dtype == np.float32 and s.shape[1] == 4 and s.shape[0] == 16_000_000 // 16
+    px = s[:, 0] / 8                                    # pixel index of every sampled row (acc = 2 * out, out[p, 0] = 4 p)
+    assert np.all(np.diff(px) > 0) and np.array_equal(s, acc.reshape(-1, 4)[px.astype(np.int64)])
+    bench._dump_outputs(str(tmp_path / "again"), out, acc, np.array([3.0, 4.0]))
+    assert np.array_equal(np.load(tmp_path / "again" / "accumulation_sample.npy"), s)
+    assert np.load(tmp_path / "rays_per_step.npy").dtype == np.float64
 
 
 def test_gpus_n_without_launcher_starts_fresh_ranks():
@@ -105,3 +129,34 @@ def test_gpus_n_under_a_launcher_does_not_relaunch():
                           "try:\n    bench.main(['--gpus', '2', '--help'])\nexcept SystemExit as e:\n    print('exit', e.code)\n" % ROOT],
                          capture_output=True, text=True, timeout=120, env=env)
     assert out.returncode == 0 and "exit 0" in out.stdout, out.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_and_dump_outputs(tmp_path):
+    """A plain run prints the headline line only (no --full measurements) and dumps the images of its last timed step: the Output of that step equals
+    a render of the same frame through the C ABI, and two runs with the same arguments dump the same bits."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "64", "--height", "36"]
+    lines = []
+    for k in range(2):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / str(k))], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads(out.stdout.strip().splitlines()[-1]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["value"] == pytest.approx(d["config"]["rays_per_step"] / d["ms_per_step"] / 1e3, rel=1e-6)
+    assert not {"roofline", "cpu_baseline", "one_frame_in_flight", "per_rank"} & set(d)
+    for name in ("output.npy", "accumulation.npy", "rays_per_step.npy"):
+        assert np.array_equal(np.load(tmp_path / "0" / name), np.load(tmp_path / "1" / name)), name
+    from hobbyrenderer_amd import native, scenes
+    luts = native.precompute_atmosphere()
+    sc, view, pos, _ = scenes.config_cornell(luts, 64, 36)
+    ctx = native.PathTracerContext(0)
+    ctx.upload_scene(sc)
+    ctx.resize(64, 36)
+    ctx.render(scenes.fill_constants(view, pos, sc, 0, 4), accum_count=8)
+    want_out, want_acc = ctx.read_output(), ctx.read_accumulation()
+    st = ctx.stats()
+    ctx.close()
+    assert np.array_equal(np.load(tmp_path / "0" / "output.npy").view(np.uint32), want_out.view(np.uint32))
+    assert np.array_equal(np.load(tmp_path / "0" / "accumulation.npy").view(np.uint32), want_acc.view(np.uint32))
+    assert np.load(tmp_path / "0" / "rays_per_step.npy").tolist() == [float(st.closestRays), float(st.shadowRays)]

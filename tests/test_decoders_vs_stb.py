@@ -2,9 +2,17 @@
 the reference's own decoder: external/stb_image.h compiled where it lies in /root/reference into oracle/_ref/libstb_ref.so (oracle/Makefile,
 oracle/stb_ref.c -- test infrastructure) and called the way the reference calls it, stbi_load_from_memory(bytes, size, &w, &h, &n, 4)
 (src/TextureLoader.cpp:225-257). No GPU needed. The input files are synthetic (no asset ships with the reference): the PNG matrix is written
-by tests/gltf_helpers.write_png, baseline JPEGs by its write_jpeg, progressive / optimised-Huffman JPEGs by Pillow where it is installed."""
+by tests/gltf_helpers.write_png, baseline JPEGs by its write_jpeg, progressive / optimised-Huffman JPEGs and zlib PNGs by Pillow (those bytes are
+stored in tests/golden/stb_pillow_inputs.npz, so the inputs do not depend on the Pillow at hand).
+
+Where the reference decoder is not built (its source tree is not part of this repository), every case is checked against stb_image's decode
+as stored in tests/golden/stb_decodes.json: shape and SHA-256 of the RGBA bytes per case, or null where stb_image refuses the file. Where it
+is built, the live decoder is the expectation and must also agree with the stored record. python tests/golden/make_stb_golden.py
+regenerates both files from the live decoder."""
 import ctypes as C
+import hashlib
 import io
+import json
 import os
 
 import numpy as np
@@ -17,10 +25,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.path.join(ROOT, "oracle", "_ref", "libstb_ref.so")
 
 
-@pytest.fixture(scope="module")
-def stb():
-    if not os.path.exists(_LIB):
-        pytest.skip("oracle/_ref/libstb_ref.so not built (make -C oracle needs /root/reference/external/stb_image.h)")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "stb_decodes.json")
+PILLOW_INPUTS = os.path.join(ROOT, "tests", "golden", "stb_pillow_inputs.npz")
+
+
+def _live_loader():
+    """stbi_load_from_memory(bytes, ..., 4) of oracle/_ref/libstb_ref.so -> RGBA uint8 array, or None when stb_image refuses the file."""
     lib = C.CDLL(_LIB)
     lib.stbi_load_from_memory.restype = C.POINTER(C.c_ubyte)
     lib.stbi_load_from_memory.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
@@ -39,11 +49,61 @@ def stb():
     return load
 
 
+def _record(img):
+    return None if img is None else {"shape": list(img.shape), "sha256": hashlib.sha256(np.ascontiguousarray(img).tobytes()).hexdigest()}
+
+
+class _Stored:
+    """stb_image's decode of one case as stored: shape + SHA-256 of the RGBA bytes."""
+
+    def __init__(self, rec):
+        self.shape, self.sha256 = tuple(rec["shape"]), rec["sha256"]
+
+
+class _Missing:
+    """No stored decode for this case label."""
+
+
+class _Expect:
+    """stb(data, what): stb_image's decode of `data` (case label `what`) -- the live array where the reference decoder is built, else the stored
+    record (_Stored), None where stb_image refuses the file, _Missing where the case is not in tests/golden/stb_decodes.json."""
+
+    def __init__(self, live, golden):
+        self.live, self.golden = live, golden
+
+    def __call__(self, data, what):
+        rec = self.golden.get(what, _Missing) if self.golden is not None else _Missing
+        if self.live is None:
+            return _Stored(rec) if isinstance(rec, dict) else rec
+        want = self.live(data)
+        if self.golden is not None:
+            assert rec is not _Missing and rec == _record(want), f"{what}: tests/golden/stb_decodes.json is stale (python tests/golden/make_stb_golden.py)"
+        return want
+
+
+@pytest.fixture(scope="module")
+def stb():
+    with open(GOLDEN) as f:
+        golden = json.load(f)["decodes"]
+    return _Expect(_live_loader() if os.path.exists(_LIB) else None, golden)
+
+
+def _pillow_inputs(prefix):
+    """(label, bytes) of the stored Pillow-written files whose label starts with `prefix`, in the order they were written."""
+    with np.load(PILLOW_INPUTS) as z:
+        order = [str(k) for k in z["order"]]
+        return [(k, z[k].tobytes()) for k in order if k.startswith(prefix)]
+
+
 def _same(stb, data, what):
-    want = stb(data)
+    want = stb(data, what)
+    assert want is not _Missing, f"{what}: no stb_image decode stored in tests/golden/stb_decodes.json (python tests/golden/make_stb_golden.py)"
     assert want is not None, f"stb_image refused {what}"
     got = scene_io.decode_image(data)
     assert got.shape == want.shape, (what, got.shape, want.shape)
+    if isinstance(want, _Stored):
+        assert hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() == want.sha256, f"{what}: bytes differ from stb_image's stored decode"
+        return got
     if not np.array_equal(got, want):
         bad = np.argwhere(got != want)
         y, x, c = bad[0]
@@ -121,12 +181,10 @@ def test_baseline_jpeg_equals_stb_image(tmp_path, stb):
         _same(stb, open(p, "rb").read(), f"saturated {sub}")
 
 
-def test_pillow_written_jpeg_equals_stb_image(stb):
-    """libjpeg-written files: optimised Huffman tables, progressive (spectral selection + successive approximation), all subsamplings Pillow
-    offers, greyscale, several qualities."""
-    Image = pytest.importorskip("PIL.Image")
+def pillow_jpeg_files(Image):
+    """(label, bytes): libjpeg-written files -- optimised Huffman tables, progressive (spectral selection + successive approximation), all
+    subsamplings Pillow offers, greyscale, several qualities (tests/golden/make_stb_golden.py stores them)."""
     rng = np.random.default_rng(21)
-    n = 0
     for (w, h) in ((70, 45), (16, 16), (33, 7)):
         img = _photo(rng, w, h).astype(np.uint8)
         for mode, subs in (("RGB", (0, 1, 2)), ("L", (0,))):
@@ -136,16 +194,21 @@ def test_pillow_written_jpeg_equals_stb_image(stb):
                     for quality in (35, 88, 100):
                         buf = io.BytesIO()
                         pil.save(buf, "JPEG", quality=quality, subsampling=sub, progressive=prog, optimize=True)
-                        data = buf.getvalue()
-                        assert (b"\xff\xc2" in data) == prog
-                        _same(stb, data, f"pillow {mode} {w}x{h} sub={sub} progressive={prog} q={quality}")
-                        n += 1
+                        yield f"pillow jpeg {mode} {w}x{h} sub={sub} progressive={prog} q={quality}", buf.getvalue()
+
+
+def test_pillow_written_jpeg_equals_stb_image(stb):
+    """libjpeg-written files (pillow_jpeg_files, stored): optimised Huffman tables, progressive, all subsamplings, greyscale, several qualities."""
+    n = 0
+    for what, data in _pillow_inputs("pillow jpeg "):
+        assert (b"\xff\xc2" in data) == ("progressive=True" in what)
+        _same(stb, data, what)
+        n += 1
     assert n == 72
 
 
-def test_pillow_written_png_equals_stb_image(stb):
-    """zlib-compressed (dynamic Huffman blocks) PNGs from an independent writer, incl. palette + tRNS and 16-bit."""
-    Image = pytest.importorskip("PIL.Image")
+def pillow_png_files(Image):
+    """(label, bytes): zlib-compressed (dynamic Huffman blocks) PNGs from an independent writer, incl. palette + tRNS and 16-bit."""
     rng = np.random.default_rng(4)
     rgba = rng.integers(0, 256, (40, 61, 4), dtype=np.uint8)
     rgba[..., :3] = (rgba[..., :3] // 64) * 64           # compressible
@@ -155,10 +218,18 @@ def test_pillow_written_png_equals_stb_image(stb):
         for opt in (False, True):
             buf = io.BytesIO()
             im.save(buf, "PNG", optimize=opt)
-            _same(stb, buf.getvalue(), f"pillow png {mode} optimize={opt}")
+            yield f"pillow png {mode} optimize={opt}", buf.getvalue()
     g16 = Image.fromarray(rng.integers(0, 65536, (9, 14), dtype=np.uint16))
     buf = io.BytesIO(); g16.save(buf, "PNG")
-    _same(stb, buf.getvalue(), "pillow png I;16")
+    yield "pillow png I;16", buf.getvalue()
+
+
+def test_pillow_written_png_equals_stb_image(stb):
+    """zlib-compressed (dynamic Huffman blocks) PNGs from an independent writer (pillow_png_files, stored), incl. palette + tRNS and 16-bit."""
+    files = _pillow_inputs("pillow png ")
+    assert len(files) == 11
+    for what, data in files:
+        _same(stb, data, what)
 
 
 def test_both_refuse_the_same_broken_files(tmp_path, stb):
@@ -166,8 +237,8 @@ def test_both_refuse_the_same_broken_files(tmp_path, stb):
     p = str(tmp_path / "a.jpg")
     write_jpeg(p, _photo(rng, 24, 24), "420")
     good = open(p, "rb").read()
-    for bad in (good[:100], b"\xff\xd8\xff\xd9", b"\x89PNG\r\n\x1a\n" + b"\0" * 40):
-        assert stb(bad) is None
+    for k, bad in enumerate((good[:100], b"\xff\xd8\xff\xd9", b"\x89PNG\r\n\x1a\n" + b"\0" * 40)):
+        assert stb(bad, f"broken {k}") is None
         with pytest.raises(scene_io.SceneFormatError):
             scene_io.decode_image(bad)
 
