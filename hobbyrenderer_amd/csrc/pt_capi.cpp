@@ -47,6 +47,8 @@ struct HrptContext {
     uint32_t width = 0, height = 0;
     float4* dAccum = nullptr; float4* dOutput = nullptr; float4* dDisplay = nullptr;
     uint32_t* dHistogram = nullptr; float* dExposure = nullptr;   // persistent exposure buffer (HDRRenderer m_RG_ExposureBuffer)
+    uint32_t* dBloomDown = nullptr; uint32_t* dBloomUp = nullptr; size_t bloomWords = 0;   // bloom pyramids (packed R11G11B10_FLOAT), sized by the last bloom call
+    uint32_t bloomTailTexels = 0;            // HRPT_BLOOM_FUSED_TAIL: levels of at most this many texels run in one workgroup's LDS (0 = one kernel per pass, the measured-faster default)
     DeviceCounters* dCounters = nullptr;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
@@ -169,6 +171,7 @@ int hrpt_create(const HrptDeviceDesc* desc, HrptContext** out)
     if (const char* e = getenv("HRPT_WF_SLIM_SHADOW")) c->wf.noSlimShadow = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_FUSED_PRIMARY")) c->wf.noFusedPrimary = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_NODE_LOOP_MIN")) c->wf.nodeLoopMin = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_BLOOM_FUSED_TAIL")) { const int v = atoi(e); c->bloomTailTexels = v == 1 ? 8192u : (v > 0 ? (uint32_t)v : 0u); }
     *out = c;
     return HRPT_OK;
 }
@@ -185,6 +188,8 @@ void hrpt_destroy(HrptContext* c)
     if (c->dDisplay) (void)hipFree(c->dDisplay);
     if (c->dHistogram) (void)hipFree(c->dHistogram);
     if (c->dExposure) (void)hipFree(c->dExposure);
+    if (c->dBloomDown) (void)hipFree(c->dBloomDown);
+    if (c->dBloomUp) (void)hipFree(c->dBloomUp);
     if (c->dCounters) (void)hipFree(c->dCounters);
     if (c->evStart) (void)hipEventDestroy(c->evStart);
     if (c->evStop) (void)hipEventDestroy(c->evStop);
@@ -1021,6 +1026,66 @@ int hrpt_post_process(HrptContext* c, const HrptPostParams* p)
     }
     if (!c->dDisplay) HIP_TRY(c, hipMalloc((void**)&c->dDisplay, (size_t)c->width * c->height * sizeof(float4)));
     HIP_TRY(c, launch_post_chain(c->dOutput, c->dDisplay, c->width * c->height, *p, c->dHistogram, c->dExposure, c->stream));
+    return HRPT_OK;
+}
+
+// Pyramids for a width x height image: kept while the size stays, re-allocated when it changes (hipFree waits for work in flight).
+static int bloom_run(HrptContext* c, float4* image, uint32_t width, uint32_t height, const HrptBloomParams& p, hipStream_t stream)
+{
+    const size_t words = bloom_pyramid_words(width, height);
+    if (words == 0) return HRPT_OK;
+    if (words != c->bloomWords) {
+        if (c->dBloomDown) { (void)hipFree(c->dBloomDown); c->dBloomDown = nullptr; }
+        if (c->dBloomUp) { (void)hipFree(c->dBloomUp); c->dBloomUp = nullptr; }
+        c->bloomWords = 0;
+        HIP_TRY(c, hipMalloc((void**)&c->dBloomDown, words * sizeof(uint32_t)));
+        HIP_TRY(c, hipMalloc((void**)&c->dBloomUp, words * sizeof(uint32_t)));
+        c->bloomWords = words;
+    }
+    HIP_TRY(c, launch_bloom(image, width, height, p, c->dBloomDown, c->dBloomUp, c->bloomTailTexels, stream));
+    return HRPT_OK;
+}
+
+int hrpt_bloom(HrptContext* c, const HrptBloomParams* p)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom: null params");
+    if (!bloom_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom: knee, intensity and upsampleRadius must be finite and >= 0");
+    if (!c->dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom: hrpt_resize not called");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return bloom_run(c, c->dOutput, c->width, c->height, *p, c->stream);
+}
+
+int hrpt_bloom_device(HrptContext* c, float* hdrDevice, uint32_t width, uint32_t height, const HrptBloomParams* p, void* stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: null params");
+    if (!hdrDevice) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: null image");
+    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: size must be 1..65535");
+    if (!bloom_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: knee, intensity and upsampleRadius must be finite and >= 0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return bloom_run(c, reinterpret_cast<float4*>(hdrDevice), width, height, *p, static_cast<hipStream_t>(stream));
+}
+
+int hrpt_bloom_host(const float* hdrIn, float* hdrOut, uint32_t width, uint32_t height, const HrptBloomParams* p, int nthreads)
+{
+    if (!p) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: null params");
+    if (!hdrIn || !hdrOut) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: null image");
+    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: size must be 1..65535");
+    if (!bloom_params_valid(*p)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: knee, intensity and upsampleRadius must be finite and >= 0");
+    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    try { bloom_host(hdrIn, hdrOut, width, height, *p, nthreads); }
+    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_bloom_host: out of memory"); }
+    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_bloom_host: ") + e.what()); }
+    return HRPT_OK;
+}
+
+int hrpt_bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, float* unpackedRgb)
+{
+    if (!rgb && count) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_pack_probe: null input");
+    bloom_pack_probe(rgb, count, packed, unpackedRgb);
     return HRPT_OK;
 }
 

@@ -40,6 +40,16 @@ hipError_t launch_megakernel(const SceneView& scene, const HrptPathTracerConstan
 hipError_t launch_post_chain(const float4* hdr, float4* display, uint32_t pixelCount, const HrptPostParams& params, uint32_t* histogram,
                              float* exposure, hipStream_t stream);
 
+// Bloom (pt_bloom.hip; arithmetic in pt_bloom.h): composites into `hdr` (W x H float4) in place. downPyramid / upPyramid hold
+// bloom_pyramid_words(W, H) packed R11G11B10_FLOAT words each. tailTexels: 0 = one kernel per pass, otherwise the levels from the first one
+// with at most that many texels on run in one workgroup's LDS (same bits). bloom_host: the same arithmetic on host threads.
+size_t bloom_pyramid_words(uint32_t width, uint32_t height);
+bool bloom_params_valid(const HrptBloomParams& params);
+hipError_t launch_bloom(float4* hdr, uint32_t width, uint32_t height, const HrptBloomParams& params, uint32_t* downPyramid, uint32_t* upPyramid,
+                        uint32_t tailTexels, hipStream_t stream);
+void bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, float* unpacked);   // test hook: the format conversion alone
+void bloom_host(const float* hdrIn, float* hdrOut, uint32_t width, uint32_t height, const HrptBloomParams& params, int nthreads);
+
 // Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
 hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
 

@@ -30,6 +30,7 @@ EXPORTS = [
     "hrpt_create", "hrpt_destroy", "hrpt_last_error", "hrpt_upload_scene", "hrpt_resize", "hrpt_render",
     "hrpt_synchronize", "hrpt_set_stream", "hrpt_get_device_images", "hrpt_read_accumulation", "hrpt_read_output",
     "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_bvh", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
+    "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
 ]
 
@@ -69,6 +70,10 @@ lib.hrpt_post_process.argtypes = [C.c_void_p, C.POINTER(S.PostParams)]
 lib.hrpt_read_display.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.hrpt_get_exposure.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
 lib.hrpt_set_exposure.argtypes = [C.c_void_p, C.c_float]
+lib.hrpt_bloom.argtypes = [C.c_void_p, C.POINTER(S.BloomParams)]
+lib.hrpt_bloom_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.BloomParams), C.c_void_p]
+lib.hrpt_bloom_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.BloomParams), C.c_int]
+lib.hrpt_bloom_pack_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
 lib.hrpt_halton.argtypes = [C.c_uint32, C.c_uint32]
 lib.hrpt_halton.restype = C.c_float
 lib.hrpt_precompute_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -125,6 +130,31 @@ def precompute_atmosphere(nthreads=0, orders=ATMOSPHERE_ORDERS, device=-2, cache
         except OSError:
             pass
     return t, s, i
+
+
+def bloom_host(img, params=None, nthreads=0):
+    """hrpt_bloom_host: the bloom stage (csrc/pt_bloom.h) on host threads over a float32 [H, W, 4] image; returns the composited image.
+    Needs no GPU; bit-identical to PathTracerContext.bloom."""
+    img = np.ascontiguousarray(img, np.float32)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("bloom_host: float32 [H, W, 4] image expected")
+    params = params if params is not None else S.BloomParams()
+    out = np.empty_like(img)
+    rc = lib.hrpt_bloom_host(img.ctypes.data, out.ctypes.data, img.shape[1], img.shape[0], C.byref(params), int(nthreads))
+    if rc != 0:
+        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    return out
+
+
+def bloom_pack_probe(rgb):
+    """Test hook: (packed R11G11B10_FLOAT words, the values read back from them) for float32 [..., 3] colours."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    packed = np.empty(rgb.shape[:-1], np.uint32)
+    unpacked = np.empty_like(rgb)
+    rc = lib.hrpt_bloom_pack_probe(rgb.ctypes.data, packed.size, packed.ctypes.data, unpacked.ctypes.data)
+    if rc != 0:
+        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    return packed, unpacked
 
 
 def allgather(contexts):
@@ -283,6 +313,16 @@ class PathTracerContext:
 
     def post_process(self, params):
         self._check(lib.hrpt_post_process(self._h, C.byref(params)))
+
+    def bloom(self, params=None):
+        """Bloom composited into Output in place (hrpt_bloom): call between render and post_process, once per frame."""
+        params = params if params is not None else S.BloomParams()
+        self._check(lib.hrpt_bloom(self._h, C.byref(params)))
+
+    def bloom_device(self, image_ptr, width, height, params=None, hip_stream=0):
+        """The same over a caller-owned device image (width * height float4), asynchronously on `hip_stream` (integer handle)."""
+        params = params if params is not None else S.BloomParams()
+        self._check(lib.hrpt_bloom_device(self._h, C.c_void_p(int(image_ptr)), int(width), int(height), C.byref(params), C.c_void_p(int(hip_stream))))
 
     def read_display(self):
         out = np.empty((self.height, self.width, 4), np.float32)

@@ -116,6 +116,14 @@ class PostParams(C.Structure):
                 ("hdrDisplay", C.c_uint32), ("maxDisplayNits", C.c_float)]
 
 
+class BloomParams(C.Structure):
+    """HrptBloomParams; the defaults are the reference's (Renderer::m_BloomKnee, m_BloomIntensity, m_UpsampleRadius)."""
+    _fields_ = [("knee", C.c_float), ("intensity", C.c_float), ("upsampleRadius", C.c_float), ("reserved", C.c_uint32)]
+
+    def __init__(self, knee=0.1, intensity=0.005, upsampleRadius=0.85, reserved=0):
+        super().__init__(knee, intensity, upsampleRadius, reserved)
+
+
 class Stats(C.Structure):
     _fields_ = [("closestRays", C.c_uint64), ("shadowRays", C.c_uint64), ("paths", C.c_uint64),
                 ("lastRenderMs", C.c_float), ("traceKernelMs", C.c_float), ("traceKernelLaunches", C.c_uint32),

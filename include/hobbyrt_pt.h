@@ -447,6 +447,36 @@ int  hrpt_read_display(HrptContext* ctx, float* rgba, size_t bytes);           /
 int  hrpt_get_exposure(HrptContext* ctx, float* exposure, uint32_t histogram256[256]);   /* histogram may be NULL */
 int  hrpt_set_exposure(HrptContext* ctx, float exposure);                      /* the persistent exposure buffer, initially 1 */
 
+/* ---- Bloom: the stage in front of the post chain ---------------------------------------------------------------
+ * BloomRenderer::Render (src/BloomRenderer.cpp:48-175) + src/shaders/Bloom.hlsl over the HDR colour image: soft-knee prefilter into a
+ * half-resolution pyramid of up to six R11G11B10_FLOAT levels, Jimenez 13-tap downsamples, 9-tap tent upsamples, additive composite
+ * hdr.rgb += bloom * intensity (alpha untouched). The reference schedules it in its raster modes only and off by default
+ * (Renderer::m_EnableBloom); here it is an opt-in call and nothing calls it implicitly. Call order of a frame:
+ * hrpt_render -> hrpt_bloom -> hrpt_post_process. Pixel uv, the bilinear filter, the packed format's rounding and the schedule for
+ * images with fewer than six levels are defined in hobbyrenderer_amd/csrc/pt_bloom.h (an image narrower or lower than 2 pixels has no
+ * level and is left unchanged). knee, intensity and upsampleRadius must be finite and >= 0. */
+typedef struct HrptBloomParams {
+    float knee;            /* Renderer::m_BloomKnee,      src/Renderer.h:378, default 0.1   */
+    float intensity;       /* Renderer::m_BloomIntensity, src/Renderer.h:307, default 0.005 */
+    float upsampleRadius;  /* Renderer::m_UpsampleRadius, src/Renderer.h:379, default 0.85  */
+    uint32_t reserved;     /* 0 */
+} HrptBloomParams;
+/* Composites into the context's Output image in place, asynchronously on the context stream like hrpt_post_process: a following
+ * hrpt_post_process / hrpt_read_output sees the bloomed image. Every render re-resolves Output from the accumulation, so bloom never
+ * feeds back into it; two calls without a render in between bloom twice (one call per frame, like the reference). The pyramids are
+ * context-owned, allocated at the first call and after a resize. */
+int  hrpt_bloom(HrptContext* ctx, const HrptBloomParams* params);
+/* The same over a caller-owned DEVICE image (width * height float4, e.g. the assembled multi-GPU frame), asynchronous on the caller's
+ * stream (a hipStream_t; NULL = the default stream). It uses the context's pyramids as scratch: do not overlap it with another bloom
+ * call of the same context on a different stream. */
+int  hrpt_bloom_device(HrptContext* ctx, float* hdrDevice, uint32_t width, uint32_t height, const HrptBloomParams* params, void* stream);
+/* The same arithmetic on host threads over host images (no GPU needed; nthreads <= 0: one per hardware thread, at most 16). hdrOut may
+ * be hdrIn. Bit-identical to the device calls. */
+int  hrpt_bloom_host(const float* hdrIn, float* hdrOut, uint32_t width, uint32_t height, const HrptBloomParams* params, int nthreads);
+/* Test hook (host only): packed[i] = the R11G11B10_FLOAT word the pyramids store for rgb[3i .. 3i + 2], unpackedRgb[3i ..] = what a
+ * sample reads back from it. Either output may be NULL. */
+int  hrpt_bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, float* unpackedRgb);
+
 /* Intra-frame overlap: by default the shadow stage of bounce b runs on a second, library-owned stream next to the traversal of bounce
  * b + 1 (they share no buffer). That fills the tails of a context that renders one frame at a time (-3 % per frame). A host that keeps
  * two frames in flight on two contexts already fills those tails with the other frame; there the fork / join events only cost
