@@ -156,21 +156,21 @@ int hrpt_create(const HrptDeviceDesc* desc, HrptContext** out)
         return r;
     }
     c->ownStream = c->stream;
-    if (const char* e = getenv("HRPT_WF_SEGMENT_SHIFT")) c->wf.segmentShift = (uint32_t)atoi(e);
-    if (const char* e = getenv("HRPT_WF_SEGMENT_SIZE")) c->wf.segmentSize = (uint32_t)atoi(e);
-    if (const char* e = getenv("HRPT_WF_BLOCKS_PER_CU")) c->wf.blocksPerCu = (uint32_t)atoi(e);
-    if (const char* e = getenv("HRPT_WF_EXTEND_BLOCKS_PER_CU")) c->wf.extendBlocksPerCu = (uint32_t)atoi(e);
-    if (const char* e = getenv("HRPT_WF_REFILL_MIN")) c->wf.refillMin = (uint32_t)atoi(e);
-    if (const char* e = getenv("HRPT_WF_BVH_WIDTH")) c->wf.bvhWidth = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_WF_SEGMENT_SHIFT")) c->wf.knobs.segmentShift = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_WF_SEGMENT_SIZE")) c->wf.knobs.segmentSize = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_WF_BLOCKS_PER_CU")) c->wf.knobs.blocksPerCu = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_WF_EXTEND_BLOCKS_PER_CU")) c->wf.knobs.extendBlocksPerCu = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_WF_REFILL_MIN")) c->wf.knobs.refillMin = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_WF_BVH_WIDTH")) c->wf.knobs.bvhWidth = (uint32_t)atoi(e);
     if (const char* e = getenv("HRPT_BVH_BUILDER")) c->bvhBuilder = (strcmp(e, "ploc") == 0 || strcmp(e, "2") == 0) ? HRPT_BVH_BUILDER_GPU_PLOC : ((strcmp(e, "gpu") == 0 || strcmp(e, "lbvh") == 0 || strcmp(e, "1") == 0) ? HRPT_BVH_BUILDER_GPU_LBVH : ((strcmp(e, "auto") == 0 || strcmp(e, "3") == 0) ? HRPT_BVH_BUILDER_AUTO : HRPT_BVH_BUILDER_HOST_SAH));
-    if (const char* e = getenv("HRPT_WF_PAD_LDS")) c->wf.padLdsBytes = (uint32_t)atoi(e);
-    if (const char* e = getenv("HRPT_WF_DRAIN_SEGMENTS")) c->wf.drainSegments = atoi(e) != 0;
-    if (const char* e = getenv("HRPT_WF_SERIAL_SHADOW")) c->wf.serialShadow = atoi(e) != 0;
-    if (const char* e = getenv("HRPT_WF_SHADOW_PATH")) c->wf.shadowPath = atoi(e);
-    if (const char* e = getenv("HRPT_WF_SHADE_SORT")) c->wf.shadeSort = atoi(e) != 0 ? 1 : 0;
-    if (const char* e = getenv("HRPT_WF_SLIM_SHADOW")) c->wf.noSlimShadow = atoi(e) == 0;
-    if (const char* e = getenv("HRPT_WF_FUSED_PRIMARY")) c->wf.noFusedPrimary = atoi(e) == 0;
-    if (const char* e = getenv("HRPT_WF_NODE_LOOP_MIN")) c->wf.nodeLoopMin = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_WF_PAD_LDS")) c->wf.knobs.padLdsBytes = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_WF_DRAIN_SEGMENTS")) c->wf.knobs.drainSegments = atoi(e) != 0;
+    if (const char* e = getenv("HRPT_WF_SERIAL_SHADOW")) c->wf.knobs.serialShadow = atoi(e) != 0;
+    if (const char* e = getenv("HRPT_WF_SHADOW_PATH")) c->wf.knobs.shadowPath = atoi(e);
+    if (const char* e = getenv("HRPT_WF_SHADE_SORT")) c->wf.knobs.shadeSort = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("HRPT_WF_SLIM_SHADOW")) c->wf.knobs.noSlimShadow = atoi(e) == 0;
+    if (const char* e = getenv("HRPT_WF_FUSED_PRIMARY")) c->wf.knobs.noFusedPrimary = atoi(e) == 0;
+    if (const char* e = getenv("HRPT_WF_NODE_LOOP_MIN")) c->wf.knobs.nodeLoopMin = (uint32_t)atoi(e);
     if (const char* e = getenv("HRPT_BLOOM_FUSED_TAIL")) { const int v = atoi(e); c->bloomTailTexels = v == 1 ? 8192u : (v > 0 ? (uint32_t)v : 0u); }
     *out = c;
     return HRPT_OK;
@@ -951,7 +951,7 @@ int hrpt_resolve_columns_device(HrptContext* c, const float* shardsDevice, float
 int hrpt_set_shadow_overlap(HrptContext* c, int enabled)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    c->wf.serialShadow = enabled == 0;
+    c->wf.knobs.serialShadow = enabled == 0;
     return HRPT_OK;
 }
 

@@ -24,6 +24,7 @@
 #include "pt_wavefront.h"
 
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -41,11 +42,7 @@ namespace hrt {
 
 namespace {
 
-constexpr uint32_t kMaxSegment = 1024;       // largest wave-owned segment (samples); the size is chosen per batch, 64..1024
-constexpr uint32_t kBlock = 256;             // 4 waves
-constexpr uint32_t kMaxLights = 8;
 constexpr uint32_t kMaxSppPerBatch = 64;
-constexpr size_t kLdsBudget = 64 * 1024;     // dynamic LDS per block: traversal stacks + BVH copy
 
 struct WfBuffers {
     float4 *rayO[2], *rayD[2], *thr[2], *med0[2], *med1[2];
@@ -137,12 +134,6 @@ HRT_DEV uint32_t path_count(const WfArgs& a, uint32_t in, uint32_t seg)
 
 // per-lane traversal stack in LDS: element (sp, lane-in-block) at base[sp * kBlock]
 // DEPTH 64 = "deeper than 32": the first 32 entries stay in LDS, the (rarely reached) rest lives in a per-lane column of global memory.
-// A 64-entry LDS stack is 64 KB per block, i.e. two blocks per CU: it cost 40 % on the scenes that needed it, although the worst case
-// 3 * depth4 + 2 that forces the size is never approached by real rays.
-// Measured (MI355X): a 64-entry LDS stack -> 32 + spill: -33 % frame time on the 1.17 M-triangle scene; closest-hit kernel 32 -> 16 LDS
-// entries + spill: another -3 % there and on config 4 (occupancy); the shadow kernel is faster with 32 (+4 % with 16 on configs 4, 5).
-constexpr int kExtendLdsStack = 16, kShadowLdsStack = 32;
-constexpr uint32_t kMaxStackNeed = 128;        // deepest supported 4-wide stack need (3 * depth4 + 2)
 template <int DEPTH, int LDSMAX>
 struct LdsStack {
     static constexpr int kLdsStackMax = LDSMAX;
@@ -162,7 +153,6 @@ struct LdsStack {
 };
 // per-lane buffer of the K closest non-opaque shadow candidates: (t, triangle) of entry k at base[(k*2 + {0,1}) * kBlock];
 // the barycentrics are recomputed from the triangle when the candidate is processed (same test => same bits)
-constexpr int kShadowCandidates = 8;
 struct LdsCandidates {
     int32_t* base;
     HRT_DEV void key(int k, float& t, uint32_t& tri) const { t = __int_as_float(base[(k * 2 + 0) * kBlock]); tri = (uint32_t)base[(k * 2 + 1) * kBlock]; }
@@ -170,7 +160,6 @@ struct LdsCandidates {
     HRT_DEV void move(int dst, int src) { base[(dst * 2 + 0) * kBlock] = base[(src * 2 + 0) * kBlock]; base[(dst * 2 + 1) * kBlock] = base[(src * 2 + 1) * kBlock]; }
 };
 // ... with the instance next to the triangle (two-level structure: the triangle index is per mesh): entry k at base[(k*3 + {0,1,2}) * kBlock]
-constexpr int kTwoLevelCandidates = 4;
 struct LdsCandidates3 {
     int32_t* base;
     HRT_DEV void key(int k, float& t, uint32_t& tri, uint32_t& inst) const { t = __int_as_float(base[(k * 3 + 0) * kBlock]); tri = (uint32_t)base[(k * 3 + 1) * kBlock]; inst = (uint32_t)base[(k * 3 + 2) * kBlock]; }
@@ -183,13 +172,6 @@ struct GlobalCandidates {
     HRT_DEV void key(int k, float& t, uint32_t& tri) const { uint2 v = base[k]; t = __uint_as_float(v.x); tri = v.y; }
 };
 // BVH copy in LDS; W = node width (2: GpuNode, 4: GpuNode4)
-// Stride of a 4-wide node in the LDS copy. At 128 bytes the rows of all even nodes start in the same four banks (and those of the odd nodes in four
-// others): lanes at different nodes conflict 8-fold at worst. A multiple of 32 keeps the near ^ 16 = far addressing of inner_step.
-#ifndef HRPT_LDS_NODE4_STRIDE
-#define HRPT_LDS_NODE4_STRIDE 128
-#endif
-constexpr uint32_t kLdsNode4Stride = HRPT_LDS_NODE4_STRIDE;
-static_assert(kLdsNode4Stride >= 128 && kLdsNode4Stride % 32 == 0, "LDS node stride: 128 bytes of node, near / far rows 32-byte aligned");
 template <int W>
 struct LdsBvh {
     static constexpr int kWidth = W == 5 ? 4 : W; static constexpr bool kTwoLevel = false; static constexpr bool kLds = true;
@@ -359,7 +341,6 @@ constexpr int kWavesExtendLds = 6, kWavesExtendGlobal = 6, kWavesExtendTwoLevel 
 #define HRPT_WAVES_EXTEND_LDS_OPAQUE 6
 #endif
 constexpr int kWavesExtendLdsOpaque = HRPT_WAVES_EXTEND_LDS_OPAQUE;
-constexpr uint32_t kRefillMinDefault = 12;
 constexpr uint32_t kShadeRing = 64;        // entries of wf_shade<SIMPLE>'s per-wave ring of parked specular-lobe paths
 constexpr uint32_t kNoPathRecord = 0xFFFFFFFEu;     // hit-record code of a slot without a path (wf_extend<PRIMARY>; 0xFFFFFFFF = miss)
 
@@ -1076,12 +1057,7 @@ __global__ __launch_bounds__(kBlock) void wf_shadow_rays(WfArgs a, HrptPathTrace
 }
 
 // ------------------------------------------------------------------ shadow (NEE visibility + accumulation)
-// MODE kShadowOpaque: no ForceNonOpaque instance in the scene: plain any-hit query per light sample.
-// MODE kShadowBuffered: non-opaque geometry, the kernel traverses itself: per-lane candidate buffer in LDS (after the stack) and the buffered query.
-// MODE kShadowResolve: non-opaque geometry, visibility traversal already done by wf_shadow_rays + wf_extend<ANYHIT>: this kernel only walks
-//   the recorded candidate lists (its stack serves the rare re-trace behind an overflowing list) and evaluates the contributions.
-// MODE kShadowSlim: kShadowOpaque with directional lights only and the 32-byte entries of wf_shade<1, SIMPLE> (see there).
-enum : int { kShadowOpaque = 0, kShadowBuffered = 1, kShadowResolve = 2, kShadowSlim = 3 };
+// MODE: kShadowOpaque / kShadowBuffered / kShadowResolve / kShadowSlim (pt_wavefront_plan.h)
 // Waves per SIMD (built without the SLP vectoriser, csrc/Makefile): the buffered variant is held at 3 -- the gradient-sampled alpha test of
 // mip-mapped MASK textures, a rare path, would otherwise cost every scene with alpha-tested geometry a wave (145-152 VGPRs; at 4 waves config 4's
 // shadow stage is 6 % SLOWER: it traverses, and spills hurt its loops); the resolve variant runs at 4 (146-150 VGPRs wanted, 128 given: it waits
@@ -1283,6 +1259,7 @@ __global__ __launch_bounds__(kBlock) void wf_resolve(WfArgs a, float4* __restric
 }
 
 // ------------------------------------------------------------------ host side
+// What is launched, on which grid and with how much LDS is decided in pt_wavefront_plan.h; here the plan meets the kernels.
 // The persistent kernels divide their segments evenly among the waves of the grid (seg = wave, wave + waves, ...), so a grid that is not a
 // whole number of ROUNDS of what a CU holds of that kernel finishes late: with six resident blocks per CU a grid of 16 per CU takes three
 // rounds of 1/16 of the work each, 12 takes two of 1/12 (measured: LDS-tree wf_extend +8 % at 16, global-tree wf_extend +20 % at 7 against 6).
@@ -1290,7 +1267,6 @@ __global__ __launch_bounds__(kBlock) void wf_resolve(WfArgs a, float4* __restric
 // registers, its LDS bytes), asked once per kernel and LDS size. Used for the closest-hit traversal kernels (wf_extend, wf_trace_rays), where
 // the effect is large and consistent; the other kernels launch the grid asked for: trimmed, the any-hit pass of the glass config lost 12 %
 // (one round of its five resident blocks instead of eight blocks per CU) and the buffered shadow kernel 3 %, the rest did not move.
-static thread_local uint32_t tlCus = 0;        // compute units of the device the calling thread launches on (wavefront_render / wavefront_trace_rays set it)
 static int resident_blocks_per_cu(const void* kernel, size_t ldsBytes)
 {
     static std::mutex mu; static std::unordered_map<uint64_t, int> cache;
@@ -1303,119 +1279,89 @@ static int resident_blocks_per_cu(const void* kernel, size_t ldsBytes)
     cache.emplace(key, n);
     return n;
 }
-template <class K, class... Args> static void launch_rounds(K kernel, dim3 g, size_t ldsBytes, hipStream_t st, Args... args)
+template <class K, class... Args> static void launch_rounds(uint32_t cus, K kernel, dim3 g, size_t ldsBytes, hipStream_t st, Args... args)
 {
-    const int resident = tlCus ? resident_blocks_per_cu(reinterpret_cast<const void*>(kernel), ldsBytes) : 0;
-    const uint32_t perRound = tlCus * (uint32_t)(resident > 0 ? resident : 0);
+    const int resident = cus ? resident_blocks_per_cu(reinterpret_cast<const void*>(kernel), ldsBytes) : 0;
+    const uint32_t perRound = cus * (uint32_t)(resident > 0 ? resident : 0);
     if (perRound && g.x > perRound) g.x = (g.x / perRound) * perRound;
     hipLaunchKernelGGL(kernel, g, dim3(kBlock), ldsBytes, st, args...);
 }
-struct Variant { bool lds; int depth; int width; size_t ldsBytes; bool twoLevel = false; bool twoLevelCandidates = false; bool quantised = false; };
 
-template <bool L, int D, int W> void launch_extend_t(dim3 g, size_t sh, hipStream_t st, const WfArgs& a, uint32_t parity, bool anyHit)
+// The template arguments <LDS_BVH, DEPTH, W, TL> of the traversal kernel a Variant stands for, as compile-time constants: calls
+// f(bool_constant<L>, integral_constant<int, D>, integral_constant<int, W>, integral_constant<int, TL>) with one of
+//   flat 2-wide tree       L in { false, true }   D in { 8, 16, 32, 64 }   W = 2                     TL = 0
+//   flat 4-wide tree       L in { false, true }   D in { 16, 32, 64 }      W = 4                     TL = 0
+//   ... quantised nodes    L = false              D in { 16, 32, 64 }      W = kQuantisedTree        TL = 0
+//   two-level structure    L = false              D in { 16, 32, 64 }      W = 4                     TL = 1 (every instance opaque), 2
+// and no other combination, so a kernel is instantiated only where f names it for one of these.
+template <int N> using int_c = std::integral_constant<int, N>;
+template <class F> void dispatch_variant(const Variant& v, F&& f)
 {
-    if constexpr (W >= 4) if (a.primary && !anyHit) {
-        if (a.allOpaque) launch_rounds((wf_extend<L, D, W, false, 0, true, true>), g, sh, st, a, parity);
-        else launch_rounds((wf_extend<L, D, W, false, 0, true>), g, sh, st, a, parity);
-        return;
-    }
-    if (anyHit) hipLaunchKernelGGL((wf_extend<L, D, W, true>), g, dim3(kBlock), sh + (size_t)kShadowCandidates * 2 * kBlock * 4, st, a, parity);
-    else if constexpr (W >= 4) { if (a.allOpaque) launch_rounds((wf_extend<L, D, W, false, 0, false, true>), g, sh, st, a, parity); else launch_rounds((wf_extend<L, D, W, false>), g, sh, st, a, parity); }
-    else launch_rounds((wf_extend<L, D, W, false>), g, sh, st, a, parity);
+    auto depth = [&](auto L, auto W, auto TL) {
+        if constexpr (W() == 2) if (v.depth <= 8) return f(L, int_c<8>(), W, TL);
+        if (v.depth <= 16) return f(L, int_c<16>(), W, TL);
+        if (v.depth <= 32) return f(L, int_c<32>(), W, TL);
+        return f(L, int_c<64>(), W, TL);
+    };
+    if (v.twoLevel) { if (v.twoLevelCandidates) depth(std::false_type(), int_c<4>(), int_c<2>()); else depth(std::false_type(), int_c<4>(), int_c<1>()); }
+    else if (v.width == 2) { if (v.lds) depth(std::true_type(), int_c<2>(), int_c<0>()); else depth(std::false_type(), int_c<2>(), int_c<0>()); }
+    else if (v.lds) depth(std::true_type(), int_c<4>(), int_c<0>());
+    else if (v.quantised) depth(std::false_type(), int_c<kQuantisedTree>(), int_c<0>());
+    else depth(std::false_type(), int_c<4>(), int_c<0>());
 }
-// nonOpaque: 0 = opaque scene, 1 = buffered query inside wf_shadow, 2 = resolve only (after the any-hit pass)
-template <bool L, int D, int W> void launch_shadow_t(dim3 g, size_t sh, hipStream_t st, const WfArgs& a, const HrptPathTracerConstants& cb, int bounce, bool dirOnly, int nonOpaque)
+
+// wf_extend: closest hits (trimmed to whole rounds) or, anyHit, the visibility pass of the resolve schedule over the shadow-ray queue
+void launch_extend(const Variant& v, uint32_t cus, dim3 g, hipStream_t st, const WfArgs& a, uint32_t parity, bool anyHit = false)
 {
-    if (nonOpaque == kShadowResolve) hipLaunchKernelGGL((wf_shadow<L, D, W, false, kShadowResolve>), g, dim3(kBlock), sh, st, a, cb, bounce);
-    else if (nonOpaque == kShadowBuffered) {   // general variant (all light types) + candidate buffer
+    dispatch_variant(v, [&](auto L, auto D, auto W, auto TL) {
+        constexpr bool l = L(); constexpr int d = D(), w = W(), tl = TL();
+        auto closest = [&](auto kernel) { launch_rounds(cus, kernel, g, v.ldsBytes, st, a, parity); };
+        if constexpr (tl != 0) {       // closest hits only (plan_render keeps the any-hit pass off for two-level scenes)
+            if (a.primary) closest(wf_extend<false, d, 4, false, tl, true>);
+            else closest(wf_extend<false, d, 4, false, tl, false>);
+        } else if (anyHit) hipLaunchKernelGGL((wf_extend<l, d, w, true>), g, dim3(kBlock), v.ldsBytes + kCandidateLdsBytes, st, a, parity);
+        else if constexpr (w == 2) closest(wf_extend<l, d, w, false>);
+        else if (a.primary) { if (a.allOpaque) closest(wf_extend<l, d, w, false, 0, true, true>); else closest(wf_extend<l, d, w, false, 0, true>); }
+        else { if (a.allOpaque) closest(wf_extend<l, d, w, false, 0, false, true>); else closest(wf_extend<l, d, w, false>); }
+    });
+}
+// wf_shadow in one of the kShadow* modes; two-level scenes: kShadowOpaque or kShadowSlim, candidates by Variant::twoLevelCandidates
+void launch_shadow(const Variant& v, dim3 g, hipStream_t st, const WfArgs& a, const HrptPathTracerConstants& cb, int bounce, bool dirOnly, int mode)
+{
+    dispatch_variant(v, [&](auto L, auto D, auto W, auto TL) {
+        constexpr bool l = L(); constexpr int d = D(), w = W(), tl = TL();
+        auto launch = [&](auto kernel, size_t extraLds) { hipLaunchKernelGGL(kernel, g, dim3(kBlock), v.ldsBytes + extraLds, st, a, cb, bounce); };
+        if constexpr (tl != 0) {
+            const size_t cand = tl == 2 ? (size_t)kTwoLevelCandidates * 3 * kBlock * 4 : 0;      // candidate columns of the buffered two-level shadow query
+            if (mode == kShadowSlim) launch(wf_shadow<false, d, 4, true, kShadowSlim, tl>, cand);
+            else if (dirOnly) launch(wf_shadow<false, d, 4, true, kShadowOpaque, tl>, cand);
+            else launch(wf_shadow<false, d, 4, false, kShadowOpaque, tl>, cand);
+        } else if (mode == kShadowResolve) launch(wf_shadow<l, d, w, false, kShadowResolve>, 0);
+        // general variant (all light types) + candidate buffer
         // (not trimmed to whole rounds: measured, the buffered variant -- three resident blocks per CU, long uneven entries -- is 3 % slower
         // with 15 or 6 blocks per CU than with the 16 or 8 asked for)
-        hipLaunchKernelGGL((wf_shadow<L, D, W, false, kShadowBuffered>), g, dim3(kBlock), sh + (size_t)kShadowCandidates * 2 * kBlock * 4, st, a, cb, bounce);
-    } else if (nonOpaque == kShadowSlim) hipLaunchKernelGGL((wf_shadow<L, D, W, true, kShadowSlim>), g, dim3(kBlock), sh, st, a, cb, bounce);
-    else if (dirOnly) hipLaunchKernelGGL((wf_shadow<L, D, W, true, kShadowOpaque>), g, dim3(kBlock), sh, st, a, cb, bounce);
-    else hipLaunchKernelGGL((wf_shadow<L, D, W, false, kShadowOpaque>), g, dim3(kBlock), sh, st, a, cb, bounce);
+        else if (mode == kShadowBuffered) launch(wf_shadow<l, d, w, false, kShadowBuffered>, kCandidateLdsBytes);
+        else if (mode == kShadowSlim) launch(wf_shadow<l, d, w, true, kShadowSlim>, 0);
+        else if (dirOnly) launch(wf_shadow<l, d, w, true, kShadowOpaque>, 0);
+        else launch(wf_shadow<l, d, w, false, kShadowOpaque>, 0);
+    });
+}
+// wf_trace_rays: visibility (shadow) or closest hits over a caller's rays
+void launch_wf_trace_rays(const Variant& v, uint32_t cus, dim3 g, hipStream_t st, const WfTraceArgs& a, bool shadow)
+{
+    dispatch_variant(v, [&](auto L, auto D, auto W, auto TL) {
+        constexpr bool l = L(), tl = TL() != 0; constexpr int d = D(), w = W();
+        if constexpr (w != 2) {        // (4-wide trees only: plan_trace_rays)
+            // (two-level: no candidate columns: visibility queries over non-opaque instances re-trace behind every candidate)
+            if (shadow) launch_rounds(cus, wf_trace_rays<l, d, w, true, tl>, g, v.ldsBytes + (tl ? 0 : kCandidateLdsBytes), st, a);
+            else launch_rounds(cus, wf_trace_rays<l, d, w, false, tl>, g, v.ldsBytes, st, a);
+        }
+    });
 }
 
-// stack need classes: BVH2 8/16/32/64 (maxDepth + 2), BVH4 16/32/64 (3 * maxDepth4 + 2); class 64 = "deeper than the LDS part": the kernel keeps
-// kExtendLdsStack / kShadowLdsStack entries in LDS and the rest in the overflow columns (LdsStack)
-template <bool L> void launch_extend_l(Variant v, dim3 g, size_t sh, hipStream_t st, const WfArgs& a, uint32_t parity, bool anyHit)
-{
-    if (v.width == 2) {
-        if (v.depth <= 8) launch_extend_t<L, 8, 2>(g, sh, st, a, parity, anyHit); else if (v.depth <= 16) launch_extend_t<L, 16, 2>(g, sh, st, a, parity, anyHit); else if (v.depth <= 32) launch_extend_t<L, 32, 2>(g, sh, st, a, parity, anyHit); else launch_extend_t<L, 64, 2>(g, sh, st, a, parity, anyHit);
-    } else {
-        if constexpr (!L) if (v.quantised) {
-            if (v.depth <= 16) launch_extend_t<L, 16, kQuantisedTree>(g, sh, st, a, parity, anyHit); else if (v.depth <= 32) launch_extend_t<L, 32, kQuantisedTree>(g, sh, st, a, parity, anyHit); else launch_extend_t<L, 64, kQuantisedTree>(g, sh, st, a, parity, anyHit);
-            return;
-        }
-        if (v.depth <= 16) launch_extend_t<L, 16, 4>(g, sh, st, a, parity, anyHit); else if (v.depth <= 32) launch_extend_t<L, 32, 4>(g, sh, st, a, parity, anyHit); else launch_extend_t<L, 64, 4>(g, sh, st, a, parity, anyHit);
-    }
-}
-template <bool L> void launch_shadow_l(Variant v, dim3 g, size_t sh, hipStream_t st, const WfArgs& a, const HrptPathTracerConstants& cb, int bounce, bool dirOnly, int nonOpaque)
-{
-    if (v.width == 2) {
-        if (v.depth <= 8) launch_shadow_t<L, 8, 2>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else if (v.depth <= 16) launch_shadow_t<L, 16, 2>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else if (v.depth <= 32) launch_shadow_t<L, 32, 2>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else launch_shadow_t<L, 64, 2>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque);
-    } else {
-        if constexpr (!L) if (v.quantised) {
-            if (v.depth <= 16) launch_shadow_t<L, 16, kQuantisedTree>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else if (v.depth <= 32) launch_shadow_t<L, 32, kQuantisedTree>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else launch_shadow_t<L, 64, kQuantisedTree>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque);
-            return;
-        }
-        if (v.depth <= 16) launch_shadow_t<L, 16, 4>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else if (v.depth <= 32) launch_shadow_t<L, 32, 4>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else launch_shadow_t<L, 64, 4>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque);
-    }
-}
-template <int D, int TL> void launch_shadow_two_level(dim3 g, size_t sh, hipStream_t st, const WfArgs& a, const HrptPathTracerConstants& cb, int bounce, bool dirOnly, int mode)
-{
-    if (TL == 2) sh += (size_t)kTwoLevelCandidates * 3 * kBlock * 4;      // candidate columns of the buffered two-level shadow query
-    if (mode == kShadowSlim) hipLaunchKernelGGL((wf_shadow<false, D, 4, true, kShadowSlim, TL>), g, dim3(kBlock), sh, st, a, cb, bounce);
-    else if (dirOnly) hipLaunchKernelGGL((wf_shadow<false, D, 4, true, kShadowOpaque, TL>), g, dim3(kBlock), sh, st, a, cb, bounce);
-    else hipLaunchKernelGGL((wf_shadow<false, D, 4, false, kShadowOpaque, TL>), g, dim3(kBlock), sh, st, a, cb, bounce);
-}
-template <int D, int TL> void launch_extend_two_level(dim3 g, size_t sh, hipStream_t st, const WfArgs& a, uint32_t parity)
-{
-    if (a.primary) launch_rounds((wf_extend<false, D, 4, false, TL, true>), g, sh, st, a, parity);
-    else launch_rounds((wf_extend<false, D, 4, false, TL, false>), g, sh, st, a, parity);
-}
-void launch_extend(Variant v, dim3 g, size_t sh, hipStream_t st, const WfArgs& a, uint32_t parity, bool anyHit = false)
-{
-    if (v.twoLevel) {       // closest hits only (wavefront_render keeps the any-hit pass off for two-level scenes)
-        if (v.twoLevelCandidates) {
-            if (v.depth <= 16) launch_extend_two_level<16, 2>(g, sh, st, a, parity); else if (v.depth <= 32) launch_extend_two_level<32, 2>(g, sh, st, a, parity); else launch_extend_two_level<64, 2>(g, sh, st, a, parity);
-        } else {
-            if (v.depth <= 16) launch_extend_two_level<16, 1>(g, sh, st, a, parity); else if (v.depth <= 32) launch_extend_two_level<32, 1>(g, sh, st, a, parity); else launch_extend_two_level<64, 1>(g, sh, st, a, parity);
-        }
-        return;
-    }
-    if (v.lds) launch_extend_l<true>(v, g, sh, st, a, parity, anyHit); else launch_extend_l<false>(v, g, sh, st, a, parity, anyHit);
-}
-void launch_shadow(Variant v, dim3 g, size_t sh, hipStream_t st, const WfArgs& a, const HrptPathTracerConstants& cb, int bounce, bool dirOnly, int nonOpaque)
-{
-    if (v.twoLevel) {
-        if (v.twoLevelCandidates) {
-            if (v.depth <= 16) launch_shadow_two_level<16, 2>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else if (v.depth <= 32) launch_shadow_two_level<32, 2>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else launch_shadow_two_level<64, 2>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque);
-        } else {
-            if (v.depth <= 16) launch_shadow_two_level<16, 1>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else if (v.depth <= 32) launch_shadow_two_level<32, 1>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else launch_shadow_two_level<64, 1>(g, sh, st, a, cb, bounce, dirOnly, nonOpaque);
-        }
-        return;
-    }
-    if (v.lds) launch_shadow_l<true>(v, g, sh, st, a, cb, bounce, dirOnly, nonOpaque); else launch_shadow_l<false>(v, g, sh, st, a, cb, bounce, dirOnly, nonOpaque);
-}
+TreeCounts tree_counts(const SceneView& scene) { return { scene.nodeCount, scene.node4Count, scene.triCount, scene.nodesQ != nullptr, scene.instances != nullptr }; }
 
 } // namespace
-
-namespace {
-template <bool L, int D, bool SH> void launch_trace_rays_t(dim3 g, size_t lds, hipStream_t st, const WfTraceArgs& a)
-{
-    if constexpr (!L) if (a.quantised) { launch_rounds((wf_trace_rays<L, D, kQuantisedTree, SH>), g, lds + (SH ? (size_t)kShadowCandidates * 2 * kBlock * 4 : 0), st, a); return; }
-    launch_rounds((wf_trace_rays<L, D, 4, SH>), g, lds + (SH ? (size_t)kShadowCandidates * 2 * kBlock * 4 : 0), st, a);
-}
-template <bool L, bool SH> void launch_trace_rays_d(int depth, dim3 g, size_t lds, hipStream_t st, const WfTraceArgs& a)
-{
-    if (depth <= 16) launch_trace_rays_t<L, 16, SH>(g, lds, st, a); else if (depth <= 32) launch_trace_rays_t<L, 32, SH>(g, lds, st, a); else launch_trace_rays_t<L, 64, SH>(g, lds, st, a);
-}
-}
-
-
-
-bool wavefront_trace_rays_supported(const SceneTraits& traits) { return (traits.twoLevelStackNeed ? traits.twoLevelStackNeed : 3 * traits.bvh4MaxDepth + 2) <= kMaxStackNeed; }
 
 hipError_t wavefront_trace_rays(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptRay* rays, HrptRayHit* hits, uint64_t count,
                                 bool shadow, hipStream_t stream, std::string& error)
@@ -1424,26 +1370,13 @@ hipError_t wavefront_trace_rays(WavefrontState& st, const SceneView& scene, cons
     hipError_t e; int dev = 0; hipDeviceProp_t prop;
     if ((e = hipGetDevice(&dev)) != hipSuccess || (e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) { error = "hipGetDeviceProperties"; return e; }
     const uint32_t cus = (uint32_t)prop.multiProcessorCount;
-    tlCus = cus;
-    const bool twoLevel = traits.twoLevelStackNeed != 0;
-    const uint32_t need = twoLevel ? traits.twoLevelStackNeed : 3 * traits.bvh4MaxDepth + 2;
-    const int depth = need <= 16 ? 16 : (need <= 32 ? 32 : 64);
-    const size_t candBytes = shadow ? (size_t)kShadowCandidates * 2 * kBlock * 4 : 0;
-    const size_t stackBytes = (size_t)(depth > kExtendLdsStack ? kExtendLdsStack : depth) * kBlock * 4;
-    const size_t bvhBytes = (size_t)scene.node4Count * kLdsNode4Stride + (size_t)scene.triCount * 48;
-    const bool lds = !twoLevel && bvhBytes > 0 && stackBytes + candBytes + bvhBytes <= kLdsBudget && !st.forceGlobalBvh;
-    const uint32_t blocksPerCu = st.blocksPerCu ? st.blocksPerCu : 16;
-    const uint64_t chunks = (count + 255) / 256, blocksNeeded = (chunks + 3) / 4;
-    uint32_t grid = cus * blocksPerCu; if (grid > blocksNeeded) grid = (uint32_t)blocksNeeded;
+    const TraceRaysPlan p = plan_trace_rays(traits, tree_counts(scene), count, shadow, cus, st.knobs);
     WfTraceArgs a{};
     a.scene = scene; a.rays = rays; a.hits = hits; a.count = count;
-    a.refillMin = st.refillMin ? st.refillMin : kRefillMinDefault;
-    a.nodeLoopMin = st.nodeLoopMin != ~0u ? st.nodeLoopMin : (lds ? 16u : 24u);
-    a.quantised = !twoLevel && !lds && traits.quantisedNodes && scene.nodesQ != nullptr;
-    if (depth > kExtendLdsStack) {
+    a.refillMin = p.refillMin; a.nodeLoopMin = p.nodeLoopMin; a.quantised = p.v.quantised;
+    if (p.spillEntries) {
         // own overflow columns (a render may be in flight on the context's buffers only in stream order, but sizes differ)
-        const uint32_t entries = need > (uint32_t)kExtendLdsStack ? need - kExtendLdsStack : 1u;
-        const size_t bytes = (size_t)cus * blocksPerCu * kBlock * entries * 4;
+        const size_t bytes = p.spillThreads * p.spillEntries * 4;
         if (bytes > st.traceSpillBytes) {
             if (st.traceSpill) { (void)hipStreamSynchronize(stream); (void)hipFree(st.traceSpill); st.traceSpill = nullptr; st.traceSpillBytes = 0; }
             if ((e = hipMalloc(&st.traceSpill, bytes)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
@@ -1451,14 +1384,7 @@ hipError_t wavefront_trace_rays(WavefrontState& st, const SceneView& scene, cons
         }
         a.spill = static_cast<int32_t*>(st.traceSpill);
     }
-    const size_t ldsBytes = stackBytes + (lds ? bvhBytes : 0);
-    if (twoLevel) {
-        const dim3 g(grid); const size_t sl = ldsBytes;     // (no candidate columns: visibility queries over non-opaque instances re-trace behind every candidate)
-        if (shadow) { if (depth <= 16) launch_rounds((wf_trace_rays<false, 16, 4, true, true>), g, sl, stream, a); else if (depth <= 32) launch_rounds((wf_trace_rays<false, 32, 4, true, true>), g, sl, stream, a); else launch_rounds((wf_trace_rays<false, 64, 4, true, true>), g, sl, stream, a); }
-        else { if (depth <= 16) launch_rounds((wf_trace_rays<false, 16, 4, false, true>), g, sl, stream, a); else if (depth <= 32) launch_rounds((wf_trace_rays<false, 32, 4, false, true>), g, sl, stream, a); else launch_rounds((wf_trace_rays<false, 64, 4, false, true>), g, sl, stream, a); }
-    } else
-    if (lds) { if (shadow) launch_trace_rays_d<true, true>(depth, dim3(grid), ldsBytes, stream, a); else launch_trace_rays_d<true, false>(depth, dim3(grid), ldsBytes, stream, a); }
-    else { if (shadow) launch_trace_rays_d<false, true>(depth, dim3(grid), ldsBytes, stream, a); else launch_trace_rays_d<false, false>(depth, dim3(grid), ldsBytes, stream, a); }
+    launch_wf_trace_rays(p.v, cus, dim3(p.grid), stream, a, shadow);
     if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }
     return hipSuccess;
 }
@@ -1523,16 +1449,16 @@ void wavefront_reset_timing(WavefrontState& st)
 // Any-hit schedule (kShadowResolve): per shadow ray sqO + sqD + sqId written and read (2 x 36 B), shVis written and read per light slot.
 void wavefront_queue_bytes(const WavefrontState& st, const DeviceCounters& c, uint64_t& trace, uint64_t& shade, uint64_t& shadow)
 {
-    const uint64_t path = st.layout.pathRecordBytes, survivors = c.closestRays > c.paths ? c.closestRays - c.paths : 0;
+    const uint64_t path = st.plan.pathRecordBytes, survivors = c.closestRays > c.paths ? c.closestRays - c.paths : 0;
     trace = c.closestRays * (32 + 16);
     shade = c.closestRays * (path + 16) + survivors * path + c.neeEntries * 80 + c.neeSamples * 16 + c.radianceShade * 32;
     shadow = c.neeEntries * 48 + c.neeSamples * 16 + c.radianceShadow * (32 + 32);
-    if (st.layout.shadowMode == kShadowSlim) {     // 32-byte entries; wf_shadow re-reads rayD (always) and thr (unoccluded samples) of the path's input record
+    if (st.plan.shadowMode == kShadowSlim) {     // 32-byte entries; wf_shadow re-reads rayD (always) and thr (unoccluded samples) of the path's input record
         shade = c.closestRays * (path + 16) + survivors * path + c.neeEntries * 32 + c.radianceShade * 32;
         shadow = c.neeEntries * (32 + 16) + c.radianceShadow * (16 + 32);
     }
-    if (st.layout.shadowMode == kShadowResolve) shadow += c.neeEntries * 32 + c.neeSamples * 16 + c.shadowRays * 72 + c.neeEntries * st.layout.maxLights * 8;
-    if (st.layout.fusedPrimary) {      // bounce 0 reads no path records: wf_extend only writes hits, wf_shade reads them and stores the first radiance term
+    if (st.plan.shadowMode == kShadowResolve) shadow += c.neeEntries * 32 + c.neeSamples * 16 + c.shadowRays * 72 + c.neeEntries * st.plan.maxLights * 8;
+    if (st.plan.fusedPrimary) {      // bounce 0 reads no path records: wf_extend only writes hits, wf_shade reads them and stores the first radiance term
         trace -= c.paths * 16;                               // no record read, {direction, seed} written
         shade = shade - c.paths * (path - 16) + c.paths * 16;     // 16 of the 48 record bytes read; first radiance term stored
         shadow -= c.skipped16 * 16;
@@ -1554,6 +1480,34 @@ bool timing_mark(WavefrontState& st, hipStream_t stream, int kind, bool begin)
     st.eventsUsed++;
     return true;
 }
+
+// Queue pool layout: every stream of WfBuffers (and the PrimaryArgs copy) at a 256-byte aligned offset from `base`, in this order; returns the
+// bytes used. Run against a null base for the size, then against the allocation. A stream the scene does not have points at the base (hitInst: null).
+size_t carve_pool(char* base, WfArgs& a, uint64_t capacity, uint32_t segs, uint32_t maxLights, const SceneTraits& traits, bool hasInstances)
+{
+    const bool hasMedium = traits.hasMedium, hasShadowRayQueue = traits.hasNonOpaque || maxLights > 1;
+    size_t off = 0;
+    auto carve = [&](auto*& stream, size_t bytes, bool present = true) {
+        stream = reinterpret_cast<std::remove_reference_t<decltype(stream)>>(reinterpret_cast<uintptr_t>(base) + (present ? off : 0));
+        if (present) off += (bytes + 255) & ~(size_t)255;
+    };
+    WfBuffers& b = a.b;
+    for (int p = 0; p < 2; ++p) {
+        carve(b.rayO[p], capacity * 16); carve(b.rayD[p], capacity * 16); carve(b.thr[p], capacity * 16);
+        carve(b.med0[p], capacity * 16, hasMedium); carve(b.med1[p], capacity * 16, hasMedium);
+        carve(b.pathCnt[p], (size_t)segs * 4);
+    }
+    carve(b.hit, capacity * 16);
+    carve(b.hitInst, capacity * 4, hasInstances); if (!hasInstances) b.hitInst = nullptr;
+    carve(a.primaryArgs, sizeof(PrimaryArgs));
+    carve(b.sh0, capacity * 16); carve(b.sh1, capacity * 16); carve(b.sh2, capacity * 16); carve(b.sh3, capacity * 16); carve(b.sh4, capacity * 16);
+    carve(b.shL, capacity * 16 * maxLights);
+    carve(b.shadowCnt, (size_t)segs * 4); carve(b.radiance, capacity * 16);
+    // (the shadow mode is the plan's; the arrays are small next to the path queues)
+    carve(b.sqO, capacity * 16 * maxLights, hasShadowRayQueue); carve(b.sqD, capacity * 16 * maxLights, hasShadowRayQueue); carve(b.sqId, capacity * 4 * maxLights, hasShadowRayQueue);
+    carve(b.sqCnt, (size_t)segs * 4, hasShadowRayQueue); carve(b.shVis, capacity * 4 * maxLights, hasShadowRayQueue); carve(b.sqCand, capacity * 8 * kShadowCandidates * maxLights, hasShadowRayQueue);
+    return off;
+}
 }
 
 hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
@@ -1563,193 +1517,69 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
     (void)height;
     if (rect.x1 <= rect.x0 || rect.y1 <= rect.y0 || rect.columns() == 0) return hipSuccess;
     hipError_t e;
+    int dev = 0; hipDeviceProp_t prop;
+    if ((e = hipGetDevice(&dev)) != hipSuccess || (e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) { error = "hipGetDeviceProperties"; return e; }
+    const uint32_t cus = (uint32_t)prop.multiProcessorCount;
+    const RenderPlan& plan = st.plan = plan_render(traits, tree_counts(scene), constants.m_LightCount, cus, st.knobs);
+    const uint32_t maxLights = plan.maxLights;
     const uint32_t tilesX = rect.columns(), tilesY = (rect.y1 - rect.y0 + 7) / 8;
     const uint64_t pixelsPadded = (uint64_t)tilesX * tilesY * 64;
-    // batch the accumulation indices so that one batch stays below maxSamples AND its queue pool below a byte budget: the pool takes
-    // 240 B per sample with one light and no medium, but ~1.2 KB with 8 lights and non-opaque geometry (shadow-ray queue + candidate lists)
-    const uint32_t maxLights = constants.m_LightCount ? constants.m_LightCount : 1;
-    const uint64_t bytesPerSample = 16ull * (2 * (3 + (traits.hasMedium ? 2 : 0)) + 1 + 5 + maxLights + 1) + (scene.instances ? 4 : 0) +
-                                    ((traits.hasNonOpaque || maxLights > 1) ? (16ull + 16 + 4 + 4 + 8 * kShadowCandidates) * maxLights : 0);
+    // batch the accumulation indices so that one batch stays below maxSamples AND its queue pool below a byte budget
     uint32_t sppPerBatch = accumCount < kMaxSppPerBatch ? accumCount : kMaxSppPerBatch;
-    uint64_t maxSamples = st.maxSamplesPerBatch ? st.maxSamplesPerBatch : (64ull << 20);
-    if (!st.maxSamplesPerBatch && pixelsPadded * sppPerBatch * bytesPerSample > st.poolBytes) {
+    uint64_t maxSamples = 64ull << 20;
+    if (pixelsPadded * sppPerBatch * plan.bytesPerSample > st.poolBytes) {
         // the pool has to grow: keep it within half of what the device has free (other contexts -- a second frame in flight -- need theirs)
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
             const uint64_t budget = (uint64_t)(freeB + st.poolBytes) / 2;
-            if (budget / bytesPerSample < maxSamples) maxSamples = budget / bytesPerSample;
+            if (budget / plan.bytesPerSample < maxSamples) maxSamples = budget / plan.bytesPerSample;
         }
     }
     if (maxSamples * maxLights > 0xFFFFFFFFull) maxSamples = 0xFFFFFFFFull / maxLights;      // (entry, light) slot ids are 32-bit
     while (sppPerBatch > 1 && pixelsPadded * sppPerBatch > maxSamples) --sppPerBatch;
-    // ---- pool layout (again with half the accumulation indices per batch when the device refuses the allocation)
-    uint64_t capacity = 0; uint32_t segs = 0;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    size_t oRayO[2], oRayD[2], oThr[2], oMed0[2] = { 0, 0 }, oMed1[2] = { 0, 0 }, oCnt[2];
-    size_t oHit = 0, oHitInst = 0, oPrimary = 0, oSh0 = 0, oSh1 = 0, oSh2 = 0, oSh3 = 0, oSh4 = 0, oShL = 0, oShCnt = 0, oRad = 0;
-    size_t oSqO = 0, oSqD = 0, oSqId = 0, oSqCnt = 0, oShVis = 0, oSqCand = 0;
-    for (;;) {
-    capacity = ((pixelsPadded * sppPerBatch + kMaxSegment - 1) / kMaxSegment) * kMaxSegment;
-    if (capacity >= (1ull << 31)) { error = "tile too large for one batch"; return hipErrorInvalidValue; }
-    segs = (uint32_t)(capacity / 64);   // counter arrays sized for the smallest segment
-    off = 0;
-    for (int p = 0; p < 2; ++p) {
-        oRayO[p] = carve(capacity * 16); oRayD[p] = carve(capacity * 16); oThr[p] = carve(capacity * 16);
-        if (traits.hasMedium) { oMed0[p] = carve(capacity * 16); oMed1[p] = carve(capacity * 16); }
-        oCnt[p] = carve((size_t)segs * 4);
-    }
-    oHit = carve(capacity * 16);
-    oHitInst = scene.instances ? carve(capacity * 4) : 0;
-    oPrimary = carve(sizeof(PrimaryArgs));
-    oSh0 = carve(capacity * 16); oSh1 = carve(capacity * 16); oSh2 = carve(capacity * 16); oSh3 = carve(capacity * 16); oSh4 = carve(capacity * 16);
-    oShL = carve(capacity * 16 * maxLights);
-    oShCnt = carve((size_t)segs * 4); oRad = carve(capacity * 16);
-    if (traits.hasNonOpaque || maxLights > 1) {     // (the mode is picked below; the arrays are small next to the path queues)
-        oSqO = carve(capacity * 16 * maxLights); oSqD = carve(capacity * 16 * maxLights); oSqId = carve(capacity * 4 * maxLights);
-        oSqCnt = carve((size_t)segs * 4); oShVis = carve(capacity * 4 * maxLights); oSqCand = carve(capacity * 8 * kShadowCandidates * maxLights);
-    }
-    if (off <= st.poolBytes) break;
-    if (st.pool) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); (void)hipFree(st.pool); st.pool = nullptr; st.poolBytes = 0; }
-    e = hipMalloc(&st.pool, off);
-    if (e == hipSuccess) { st.poolBytes = off; break; }
-    (void)hipGetLastError();
-    if (sppPerBatch == 1 || st.maxSamplesPerBatch) {       // nothing left to halve (or the caller fixed the batch size)
-        error = "hipMalloc(queue pool, " + std::to_string(off >> 20) + " MiB for " + std::to_string(capacity) + " samples; render a smaller tile)";
-        return e;
-    }
-    sppPerBatch = (sppPerBatch + 1) / 2;
-    }
-    char* base = static_cast<char*>(st.pool);
+    // ---- queue pool (again with half the accumulation indices per batch when the device refuses the allocation)
     WfArgs a{};
-    a.scene = scene;
-    for (int p = 0; p < 2; ++p) {
-        a.b.rayO[p] = (float4*)(base + oRayO[p]); a.b.rayD[p] = (float4*)(base + oRayD[p]); a.b.thr[p] = (float4*)(base + oThr[p]);
-        a.b.med0[p] = (float4*)(base + oMed0[p]); a.b.med1[p] = (float4*)(base + oMed1[p]); a.b.pathCnt[p] = (uint32_t*)(base + oCnt[p]);
-    }
-    a.primaryArgs = (const PrimaryArgs*)(base + oPrimary);
-    a.b.hit = (float4*)(base + oHit); a.b.hitInst = scene.instances ? (uint32_t*)(base + oHitInst) : nullptr;
-    a.b.sh0 = (float4*)(base + oSh0); a.b.sh1 = (float4*)(base + oSh1); a.b.sh2 = (float4*)(base + oSh2); a.b.sh3 = (float4*)(base + oSh3);
-    a.b.sh4 = (float4*)(base + oSh4); a.b.shL = (float4*)(base + oShL);
-    a.b.shadowCnt = (uint32_t*)(base + oShCnt); a.b.radiance = (float4*)(base + oRad);
-    a.b.sqO = (float4*)(base + oSqO); a.b.sqD = (float4*)(base + oSqD); a.b.sqId = (uint32_t*)(base + oSqId); a.b.sqCnt = (uint32_t*)(base + oSqCnt); a.b.shVis = (uint32_t*)(base + oShVis); a.b.sqCand = (uint2*)(base + oSqCand);
-    a.tilesX = tilesX; a.tilesY = tilesY; a.rect = rect; a.imageWidth = width; a.pixelsPadded = (uint32_t)pixelsPadded;
-    a.maxLights = maxLights; a.hasMedium = traits.hasMedium ? 1u : 0u; a.hasStochasticAlpha = traits.hasStochasticAlpha ? 1u : 0u; a.allOpaque = traits.hasNonOpaque ? 0u : 1u;
-    st.layout.pathRecordBytes = traits.hasMedium ? 80u : 48u; st.layout.maxLights = maxLights;
-    a.counters = counters;
-    a.refillMin = st.refillMin ? st.refillMin : kRefillMinDefault;
-    a.streamSegments = st.drainSegments ? 0u : 1u;
-    // default: on for scenes that sample textures (the longest branch of shade_surface_a; Sponza-class config: same shade time, -15 % VALU
-    // instructions), off otherwise (glass config: the sort costs 3.5 % of wf_shade, its classes are too few per segment to fill iterations)
-    a.sortShade = st.shadeSort < 0 ? (traits.hasTextures ? 1u : 0u) : (uint32_t)st.shadeSort;
-    a.nodeLoopMin = 0;      // set below, once the traversal variant is known
-
-    // ---- kernel variants and grids
-    int dev = 0; hipDeviceProp_t prop;
-    if ((e = hipGetDevice(&dev)) != hipSuccess || (e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) { error = "hipGetDeviceProperties"; return e; }
-    const uint32_t cus = (uint32_t)prop.multiProcessorCount;
-    tlCus = cus;
-    // Node width per kernel class (measured, scripts/gpu_bvh4_ab.sh): the 4-wide tree wins for closest-hit queries everywhere
-    // (fewer, fuller steps: -9..-11% extend time on configs 2/4/5) and for shadow queries that buffer non-opaque candidates or
-    // read the BVH from global memory (-9..-14%); the small opaque any-hit kernel over an LDS-resident BVH is faster 2-wide
-    // (the 4-wide step costs it 12 VGPRs = one wave of occupancy).
-    const size_t candBytes = traits.hasNonOpaque ? (size_t)kShadowCandidates * 2 * kBlock * 4 : 0;
-    auto pick = [&](int width, size_t extraBytes, int ldsStackMax) {
-        Variant v; v.width = width;
-        if (traits.twoLevelStackNeed) {      // two-level structure: 4-wide trees in global memory, its own kernels
-            v.width = 4; v.twoLevel = true; v.lds = false; v.twoLevelCandidates = traits.hasNonOpaque;
-            v.depth = traits.twoLevelStackNeed <= 16 ? 16 : (traits.twoLevelStackNeed <= 32 ? 32 : 64);
-            v.ldsBytes = (size_t)(v.depth > ldsStackMax ? ldsStackMax : v.depth) * kBlock * 4 + st.padLdsBytes;
-            return v;
+    uint64_t capacity = 0; uint32_t segs = 0;
+    for (;;) {
+        capacity = ((pixelsPadded * sppPerBatch + kMaxSegment - 1) / kMaxSegment) * kMaxSegment;
+        if (capacity >= (1ull << 31)) { error = "tile too large for one batch"; return hipErrorInvalidValue; }
+        segs = (uint32_t)(capacity / 64);   // counter arrays sized for the smallest segment
+        const size_t bytes = carve_pool(nullptr, a, capacity, segs, maxLights, traits, scene.instances != nullptr);
+        if (bytes <= st.poolBytes) break;
+        if (st.pool) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); (void)hipFree(st.pool); st.pool = nullptr; st.poolBytes = 0; }
+        e = hipMalloc(&st.pool, bytes);
+        if (e == hipSuccess) { st.poolBytes = bytes; break; }
+        (void)hipGetLastError();
+        if (sppPerBatch == 1) {       // nothing left to halve
+            error = "hipMalloc(queue pool, " + std::to_string(bytes >> 20) + " MiB for " + std::to_string(capacity) + " samples; render a smaller tile)";
+            return e;
         }
-        if (v.width == 4 && 3 * traits.bvh4MaxDepth + 2 > kMaxStackNeed) v.width = 2;
-        if (v.width == 2) v.depth = traits.bvhMaxDepth + 2 <= 8 ? 8 : (traits.bvhMaxDepth + 2 <= 16 ? 16 : (traits.bvhMaxDepth + 2 <= 32 ? 32 : 64));
-        else v.depth = 3 * traits.bvh4MaxDepth + 2 <= 16 ? 16 : (3 * traits.bvh4MaxDepth + 2 <= 32 ? 32 : 64);
-        const size_t bvhBytes = (v.width == 2 ? (size_t)scene.nodeCount * 64 : (size_t)scene.node4Count * kLdsNode4Stride) + (size_t)scene.triCount * 48;
-        const size_t stackBytes = (size_t)(v.depth > ldsStackMax ? ldsStackMax : v.depth) * kBlock * 4;
-        v.lds = bvhBytes > 0 && stackBytes + extraBytes + bvhBytes <= kLdsBudget && !st.forceGlobalBvh;
-        v.ldsBytes = stackBytes + (v.lds ? bvhBytes : 0) + st.padLdsBytes;
-        v.quantised = v.width == 4 && !v.lds && traits.quantisedNodes && scene.nodesQ != nullptr;
-        return v;
-    };
-    const int forced = st.bvhWidth == 2 ? 2 : (st.bvhWidth == 4 ? 4 : 0);
-    const Variant vE = pick(forced ? forced : 4, 0, kExtendLdsStack);
-    Variant vS = pick(forced ? forced : 4, candBytes, kShadowLdsStack);
-    if (!forced && vS.lds && !traits.hasNonOpaque) vS = pick(2, candBytes, kShadowLdsStack);
-    // Shadow-ray schedule. Several lights per vertex, or glass (rays that cross many non-opaque triangles), make the per-ray cost very
-    // uneven; when the tree is in global memory their visibility traversal runs in the refilling traversal kernel (wf_shadow_rays +
-    // wf_extend<ANYHIT>, which also records the crossed non-opaque triangles) and wf_shadow only resolves: glass config 4.7 -> 4.2 ms per
-    // bounce, an opaque 101 k-triangle scene with three lights 20.3 -> 18.4 ms per frame. With an LDS-resident tree the traversal is too
-    // cheap to pay for the extra passes (Cornell box with three lights 11.3 vs 13.1 ms), and a single sun over alpha-tested foliage
-    // (config 4) is faster with wf_shadow's own buffered query (0.96 vs 1.07 ms per bounce). HRPT_WF_SHADOW_PATH = 1 / 2 forces either.
-    const bool unevenRays = maxLights > 1 || (traits.hasNonOpaque && traits.hasTransmissiveOrBlend);
-    const int selfMode = traits.hasNonOpaque ? kShadowBuffered : kShadowOpaque;
-    int shadowMode = (!vS.lds && unevenRays) ? kShadowResolve : selfMode;
-    if (st.shadowPath == 1) shadowMode = selfMode;
-    if (st.shadowPath == 2 && (traits.hasNonOpaque || maxLights > 1)) shadowMode = kShadowResolve;
-    // two-level scenes: wf_shadow traverses itself (no any-hit pass over that structure); TL = 1 instantiations when every instance is opaque, TL = 2
-    // (buffered candidates of non-opaque instances, shadow_query_two_level_buffered) otherwise -- launch_shadow picks by Variant::twoLevelCandidates
-    if (traits.twoLevelStackNeed) shadowMode = kShadowOpaque;
-    // any-hit pass over the shadow rays (same kernel family as vE). wf_extend<ANYHIT> always carves its candidate columns out of LDS
-    // (launch_extend_t adds them to the launch), opaque scene or not, so the budget check must count them too.
-    const Variant vA = pick(forced ? forced : 4, (size_t)kShadowCandidates * 2 * kBlock * 4, kExtendLdsStack);
-    if (shadowMode == kShadowResolve) vS = pick(forced ? forced : 4, 0, kExtendLdsStack);
-    const bool manyLightsEarly = maxLights > 1;
-    const bool simpleEarly = !traits.hasTextures && !traits.hasTransmissiveOrBlend && traits.directionalLightsOnly && !st.forceGeneralShade;
-    // slim shadow-queue entries: the SIMPLE single-light shade variant feeding the plain opaque any-hit query (HRPT_WF_SLIM_SHADOW=0 keeps the 96-byte entries)
-    const bool slim = simpleEarly && !manyLightsEarly && shadowMode == kShadowOpaque && !st.noSlimShadow;
-    if (slim) shadowMode = kShadowSlim;
-    a.slimShadow = slim ? 1u : 0u;
-    st.layout.shadowMode = shadowMode;
-    // Thresholded while-while (measured, scripts/env_sweep.sh HRPT_WF_NODE_LOOP_MIN): 16 lanes for an LDS-resident tree (config 2 extend -3 %),
-    // 24 for a tree in global memory (config 4 extend -11 %, glass config extend -24 % and its any-hit pass -14 %)
-    a.nodeLoopMin = st.nodeLoopMin != ~0u ? st.nodeLoopMin : (vE.lds ? 16u : 24u);
-    // more blocks than fit: the dispatcher back-fills CUs as blocks retire (scripts/knob_sweep.py). A context that is one lane of a
-    // two-frames-in-flight loop (hrpt_set_shadow_overlap(ctx, 0)) and traverses a tree in global memory does better with half the grid:
-    // its latency-bound kernels leave room for the other lane's (config 4 14.4 -> 14.0 ms, config 5 22.6 -> 21.9 ms per frame).
-    const uint32_t blocksPerCu = st.blocksPerCu ? st.blocksPerCu : ((st.serialShadow && !vE.lds) ? 8 : 16);
-    // wf_extend gets a grid of its own: a whole number of rounds of the six blocks a CU holds of it. Measured (scripts/env_sweep.sh
-    // HRPT_WF_EXTEND_BLOCKS_PER_CU): tree in LDS 12 per CU (two rounds; 16 = 2.67 rounds: +8 % on config 2, the last round runs with four of six
-    // slots filled), tree in global memory 6 (one persistent round: its waves are latency-bound and every further round re-pays the ramp:
-    // config 4 extend -6 %, glass config -20 %; the two-level kernels hold five blocks per CU and launch_rounds trims the six to that: -6 / -10 %
-    // on instanced scenes of opaque / non-opaque materials).
-    const uint32_t extendBlocksPerCu = st.extendBlocksPerCu ? st.extendBlocksPerCu : (st.blocksPerCu ? st.blocksPerCu : (vE.lds ? 12u : 6u));
-    const uint32_t maxBlocksPerCu = blocksPerCu > extendBlocksPerCu ? blocksPerCu : extendBlocksPerCu;
-    if (vE.depth > kExtendLdsStack || vS.depth > kShadowLdsStack) {
-        // stack overflow columns for trees whose worst-case stack need exceeds the LDS entries (see LdsStack); sized for the smaller LDS part
-        const uint32_t worst = traits.twoLevelStackNeed ? traits.twoLevelStackNeed : (vE.width == 4 || vS.width == 4 ? 3 * traits.bvh4MaxDepth + 2 : traits.bvhMaxDepth + 2);
-        const uint32_t entries = worst > (uint32_t)kExtendLdsStack ? worst - kExtendLdsStack : 1u;
-        const size_t threads = (size_t)cus * maxBlocksPerCu * kBlock, bytes = 2 * threads * entries * 4;
+        sppPerBatch = (sppPerBatch + 1) / 2;
+    }
+    carve_pool(static_cast<char*>(st.pool), a, capacity, segs, maxLights, traits, scene.instances != nullptr);
+    if (plan.spillEntries) {
+        const size_t bytes = 2 * plan.spillThreads * plan.spillEntries * 4;
         if (bytes > st.spillBytes) {
             if (st.spill) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); (void)hipFree(st.spill); st.spill = nullptr; st.spillBytes = 0; }
             if ((e = hipMalloc(&st.spill, bytes)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
             st.spillBytes = bytes;
         }
-        a.spill[0] = static_cast<int32_t*>(st.spill); a.spill[1] = a.spill[0] + threads * entries;
+        a.spill[0] = static_cast<int32_t*>(st.spill); a.spill[1] = a.spill[0] + plan.spillThreads * plan.spillEntries;
     }
+    a.scene = scene;
+    a.tilesX = tilesX; a.tilesY = tilesY; a.rect = rect; a.imageWidth = width; a.pixelsPadded = (uint32_t)pixelsPadded;
+    a.maxLights = maxLights; a.hasMedium = traits.hasMedium ? 1u : 0u; a.hasStochasticAlpha = traits.hasStochasticAlpha ? 1u : 0u; a.allOpaque = traits.hasNonOpaque ? 0u : 1u;
+    a.counters = counters;
+    a.refillMin = st.knobs.refillMin ? st.knobs.refillMin : kRefillMinDefault; a.streamSegments = st.knobs.drainSegments ? 0u : 1u; a.sortShade = plan.sortShade; a.nodeLoopMin = plan.nodeLoopMin;
+    a.slimShadow = plan.slim ? 1u : 0u;
+    const bool fusedPrimary = plan.fusedPrimary;
 
-    const bool manyLights = maxLights > 1;
-    const bool simpleScene = !traits.hasTextures && !traits.hasTransmissiveOrBlend && traits.directionalLightsOnly && !st.forceGeneralShade;
     for (uint32_t first = 0; first < accumCount; first += sppPerBatch) {
         const uint32_t spp = (accumCount - first) < sppPerBatch ? (accumCount - first) : sppPerBatch;
         a.spp = spp; a.numSamples = (uint32_t)(pixelsPadded * spp);
-        // segment size: large segments amortise the partially filled last 64-lane iteration of every segment (after compaction a
-        // segment holds ~80 % / 65 % / 53 % of its slots at bounces 1 / 2 / 3), small ones give every SIMD several waves when the batch is
-        // small (tile-sharded multi-GPU runs) and balance uneven per-entry work (several lights per shadow entry). Measured on MI355X
-        // (scripts/sweep_env.sh, scripts/seg_sweep.py): 512 wins for full-frame single-light batches (-3 % config 2, -4 % config 4),
-        // 256 for a 135-row band (0.76 vs 0.89 ms) and for the three-light glass scene.
-        // (512 only with an LDS-resident tree: rays through a big tree in global memory differ too much in length -- 256 is 2..4 % faster
-        // there: config 4 14.4 -> 14.2 ms, 1.17 M triangles 20.1 -> 19.4 ms)
-        const bool largeBatch = a.numSamples >= (8u << 20) && maxLights == 1 && vE.lds;
-        uint32_t shift = st.segmentShift ? st.segmentShift : (largeBatch ? 9u : 8u);
-        if (shift < 6) shift = 6;
-        if (shift > 10) shift = 10;
-        a.segSize = 1u << shift;
-        if (st.segmentSize >= 64u && st.segmentSize <= kMaxSegment) a.segSize = st.segmentSize;       // HRPT_WF_SEGMENT_SIZE: any size (experiments)
-        a.numSegments = (a.numSamples + a.segSize - 1) / a.segSize;
-        const uint32_t wavesNeeded = a.numSegments, blocksNeeded = (wavesNeeded + 3) / 4;
-        uint32_t grid = cus * blocksPerCu; if (grid > blocksNeeded) grid = blocksNeeded; if (grid == 0) grid = 1;
-        uint32_t gridExtend = cus * extendBlocksPerCu; if (gridExtend > blocksNeeded) gridExtend = blocksNeeded; if (gridExtend == 0) gridExtend = 1;
+        const BatchPlan batch = plan_batch(plan, st.knobs, a.numSamples);
+        a.segSize = batch.segSize; a.numSegments = batch.numSegments;
+        const dim3 grid(batch.grid);
 
         HrptPathTracerConstants cb = constants;
         cb.m_AccumulationIndex = constants.m_AccumulationIndex + first;
@@ -1758,32 +1588,24 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
             jt.j[k].x = hrpt_halton(cb.m_AccumulationIndex + k + 1, 2) - 0.5f;
             jt.j[k].y = hrpt_halton(cb.m_AccumulationIndex + k + 1, 3) - 0.5f;
         }
-        // SIMPLE scenes: no raygen pass. wf_extend<PRIMARY> (the bounce-0 launch) derives the primary ray and the RNG seed of a slot (= sample index) from
-        // PrimaryArgs in its refill and leaves {direction, seed} in rayD for wf_shade<PRIMARY> / wf_shadow, which take the camera position as origin and
-        // (1, 1, 1) as throughput; wf_shade(0) stores the first radiance term instead of adding to a zeroed array; padding pixels of the 8 x 8 tiles get
-        // a kNoPathRecord hit record. 96 B per sample less queue traffic and one launch less: config 2 -3 % one frame at a time, -4 % two in flight
-        // (HRPT_WF_FUSED_PRIMARY=0 keeps wf_raygen). As run-time branches inside the ordinary kernels the same code cost every bounce 6 % (extend) and
-        // 16 % (shade): the extra live values; and regenerating the ray in wf_shade instead of reading 16 bytes gave the saving back in instructions.
-        const bool fusedPrimary = simpleScene && !manyLights && maxLights <= kMaxLights && vE.width == 4 && !traits.hasMedium && !traits.hasStochasticAlpha && !st.noFusedPrimary;
         PrimaryArgs pr{};
         if (fusedPrimary) {
             for (int i = 0; i < 16; ++i) pr.clipToWorld[i] = cb.m_View.m_MatClipToWorldNoOffset[i];
             for (int i = 0; i < 3; ++i) pr.cam[i] = cb.m_CameraPos[i];
             pr.invW = cb.m_View.m_ViewportSizeInv[0]; pr.invH = cb.m_View.m_ViewportSizeInv[1]; pr.accumIndex = cb.m_AccumulationIndex;
             for (uint32_t k = 0; k < spp; ++k) pr.j[k] = jt.j[k];
+            hipLaunchKernelGGL(wf_store_primary, dim3(1), dim3(64), 0, stream, pr, const_cast<PrimaryArgs*>(a.primaryArgs));
         }
-        if (fusedPrimary) hipLaunchKernelGGL(wf_store_primary, dim3(1), dim3(64), 0, stream, pr, const_cast<PrimaryArgs*>(a.primaryArgs));
-        st.layout.fusedPrimary = fusedPrimary;
         const bool timedEnds = st.profile && st.eventsUsed + 4 <= 4096;
         if (!fusedPrimary) {
             if (timedEnds) timing_mark(st, stream, 3, true);
-            hipLaunchKernelGGL(wf_raygen, dim3(grid), dim3(kBlock), 0, stream, a, cb, jt);
+            hipLaunchKernelGGL(wf_raygen, grid, dim3(kBlock), 0, stream, a, cb, jt);
             if (timedEnds) timing_mark(st, stream, 3, false);
         }
         {   // raygen: sampleRadiance zeroed + one path record per pixel of the rectangle and index; resolve: sampleRadiance read, Accumulation
             // read (when resuming) and written, Output written
             const uint64_t w = (uint64_t)rect.columns() * 8u, px = (w < rect.x1 - rect.x0 ? w : (uint64_t)rect.x1 - rect.x0) * (rect.y1 - rect.y0);
-            if (!fusedPrimary) st.raygenBytes += (uint64_t)a.numSamples * 16 + px * spp * st.layout.pathRecordBytes;
+            if (!fusedPrimary) st.raygenBytes += (uint64_t)a.numSamples * 16 + px * spp * st.plan.pathRecordBytes;
             st.resolveBytes += px * ((uint64_t)spp * 16 + 32 + (cb.m_AccumulationIndex > 0 ? 16 : 0));
         }
         const int maxBounces = (int)cb.m_MaxBounces;
@@ -1791,7 +1613,7 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
         // writes hit records: no shared buffer, so the two run concurrently (fork after shade(b), join before shade(b+1), which both
         // rewrites the shadow queue and adds the next radiance term -- the per-sample order of additions is unchanged).
         // Per-launch timing (HRPT_FRAME_PROFILE) needs stream order, so profiling renders serially.
-        bool overlap = !st.profile && !st.serialShadow && maxBounces > 1;
+        bool overlap = !st.profile && !st.knobs.serialShadow && maxBounces > 1;
         if (overlap) {
             if (!st.auxStream && hipStreamCreateWithFlags(&st.auxStream, hipStreamNonBlocking) != hipSuccess) { st.auxStream = nullptr; overlap = false; }
             while (overlap && st.forkEvents.size() < (size_t)maxBounces) {
@@ -1805,12 +1627,12 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
         // traversal kernel, then wf_shadow for the contributions and the (few) rays that crossed non-opaque triangles.
         auto shadow_stage = [&](hipStream_t sst, int bounce) {
             a.shadowParity = (uint32_t)bounce & 1u;
-            if (shadowMode == kShadowResolve) {
-                if (traits.directionalLightsOnly) hipLaunchKernelGGL((wf_shadow_rays<true>), dim3(grid), dim3(kBlock), 0, sst, a, cb);
-                else hipLaunchKernelGGL((wf_shadow_rays<false>), dim3(grid), dim3(kBlock), 0, sst, a, cb);
-                launch_extend(vA, dim3(grid), vA.ldsBytes, sst, a, 0u, true);
+            if (plan.shadowMode == kShadowResolve) {
+                if (traits.directionalLightsOnly) hipLaunchKernelGGL((wf_shadow_rays<true>), grid, dim3(kBlock), 0, sst, a, cb);
+                else hipLaunchKernelGGL((wf_shadow_rays<false>), grid, dim3(kBlock), 0, sst, a, cb);
+                launch_extend(plan.vA, cus, grid, sst, a, 0u, true);
             }
-            launch_shadow(vS, dim3(grid), vS.ldsBytes, sst, a, cb, bounce, traits.directionalLightsOnly, shadowMode);
+            launch_shadow(plan.vS, grid, sst, a, cb, bounce, traits.directionalLightsOnly, plan.shadowMode);
         };
         bool pendingJoin = false;
         for (int bounce = 0; bounce < maxBounces; ++bounce) {
@@ -1818,19 +1640,20 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
             const bool timed = st.profile && st.eventsUsed + 8 <= 4096;
             if (timed) timing_mark(st, stream, 0, true);
             a.primary = (fusedPrimary && bounce == 0) ? 1u : 0u;
-            launch_extend(vE, dim3(gridExtend), vE.ldsBytes, stream, a, parity);
+            launch_extend(plan.vE, cus, dim3(batch.gridExtend), stream, a, parity);
             if (timed) { timing_mark(st, stream, 0, false); timing_mark(st, stream, 1, true); }
             if (pendingJoin) { if ((e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)bounce - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; } pendingJoin = false; }
             const int last = bounce + 1 == maxBounces ? 1 : 0;
             const size_t sortLds = (size_t)(kBlock / 64) * ((size_t)5 * a.segSize);      // per wave: two uint16 permutations (segments A, B) + uint8 class keys
-            if (maxLights > kMaxLights) hipLaunchKernelGGL((wf_shade<0, false>), dim3(grid), dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
-            else if (manyLights) hipLaunchKernelGGL((wf_shade<(int)kMaxLights, false>), dim3(grid), dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
-            else if (simpleScene && a.primary) hipLaunchKernelGGL((wf_shade<1, true, true>), dim3(grid), dim3(kBlock), (kBlock / 64) * kShadeRing * 23 * 4, stream, a, cb, parity, bounce, last);
-            else if (simpleScene) hipLaunchKernelGGL((wf_shade<1, true>), dim3(grid), dim3(kBlock), (kBlock / 64) * kShadeRing * 23 * 4, stream, a, cb, parity, bounce, last);
-            else hipLaunchKernelGGL((wf_shade<1, false>), dim3(grid), dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
+            if (maxLights > kMaxLights) hipLaunchKernelGGL((wf_shade<0, false>), grid, dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
+            else if (maxLights > 1) hipLaunchKernelGGL((wf_shade<(int)kMaxLights, false>), grid, dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
+            else if (plan.simpleScene && a.primary) hipLaunchKernelGGL((wf_shade<1, true, true>), grid, dim3(kBlock), (kBlock / 64) * kShadeRing * 23 * 4, stream, a, cb, parity, bounce, last);
+            else if (plan.simpleScene) hipLaunchKernelGGL((wf_shade<1, true>), grid, dim3(kBlock), (kBlock / 64) * kShadeRing * 23 * 4, stream, a, cb, parity, bounce, last);
+            else hipLaunchKernelGGL((wf_shade<1, false>), grid, dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
             if (timed) { timing_mark(st, stream, 1, false); timing_mark(st, stream, 2, true); }
             if (overlap) {
-                if ((e = hipEventRecord(st.forkEvents[(size_t)bounce], stream)) != hipSuccess || (e = hipStreamWaitEvent(st.auxStream, st.forkEvents[(size_t)bounce], 0)) != hipSuccess) { error = "fork to the shadow stream"; return e; }
+                if ((e = hipEventRecord(st.forkEvents[(size_t)bounce], stream)) != hipSuccess ||
+                    (e = hipStreamWaitEvent(st.auxStream, st.forkEvents[(size_t)bounce], 0)) != hipSuccess) { error = "fork to the shadow stream"; return e; }
                 shadow_stage(st.auxStream, bounce);
                 if ((e = hipEventRecord(st.joinEvents[(size_t)bounce], st.auxStream)) != hipSuccess) { error = "hipEventRecord(join)"; return e; }
                 pendingJoin = true;
