@@ -322,7 +322,8 @@ bool build_scene_bvh(const HrptSceneDesc& s, BuiltBvh& out, std::string& error)
         const float extPad = 1e-6f * triangle_extent(t);
         for (int k = 0; k < 3; ++k) {
             float mn = std::min(t.p0[k], std::min(t.p1[k], t.p2[k])), mx = std::max(t.p0[k], std::max(t.p1[k], t.p2[k]));
-            if (!(mn == mn) || !(mx == mx) || std::isinf(mn) || std::isinf(mx)) { error = "non-finite vertex position"; return false; }
+            // (every vertex is looked at: std::min / std::max drop a NaN in their second argument, so mn / mx of a triangle with a NaN in p1 or p2 are finite)
+            if (!std::isfinite(t.p0[k]) || !std::isfinite(t.p1[k]) || !std::isfinite(t.p2[k])) { error = "non-finite vertex position"; return false; }
             // conservative padding: the fp32 watertight test can accept points a few ulp outside the triangle (see triangle_extent)
             float pad = 1e-5f * std::max(std::fabs(mn), std::fabs(mx)) + 1e-6f + extPad;
             p.bmin[k] = mn - pad; p.bmax[k] = mx + pad; p.c[k] = 0.5f * mn + 0.5f * mx;
@@ -410,7 +411,7 @@ bool build_mesh_trees(const HrptSceneDesc& s, BuiltTwoLevel& out, std::vector<in
             const float extPad = 1e-6f * triangle_extent(t);
             for (int k = 0; k < 3; ++k) {
                 float mn = std::min(t.p0[k], std::min(t.p1[k], t.p2[k])), mx = std::max(t.p0[k], std::max(t.p1[k], t.p2[k]));
-                if (!(mn == mn) || !(mx == mx) || std::isinf(mn) || std::isinf(mx)) { error = "non-finite vertex position"; return false; }
+                if (!std::isfinite(t.p0[k]) || !std::isfinite(t.p1[k]) || !std::isfinite(t.p2[k])) { error = "non-finite vertex position"; return false; }
                 float pad = 1e-5f * std::max(std::fabs(mn), std::fabs(mx)) + 1e-6f + extPad;
                 pr.bmin[k] = mn - pad; pr.bmax[k] = mx + pad; pr.c[k] = 0.5f * mn + 0.5f * mx;
             }

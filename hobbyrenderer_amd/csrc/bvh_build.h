@@ -72,7 +72,7 @@ static_assert(sizeof(HostNode) == 64 && sizeof(HostTri) == 48 && sizeof(HostTriA
 struct BuiltBvh {
     std::vector<HostNode> nodes;    // empty when the scene fits one leaf
     std::vector<HostNode4> nodes4;  // the same tree collapsed to 4-wide nodes (root = 0); empty when nodes is empty
-    uint32_t maxDepth4 = 0;         // depth of the 4-wide tree; a traversal stack needs at most 3 * maxDepth4 + 1 entries
+    uint32_t maxDepth4 = 0;         // depth of the deepest inner node of the 4-wide tree (root 0); a traversal stack holds up to 3 * (maxDepth4 + 1) entries
     std::vector<HostTri> tris;      // leaf order
     std::vector<HostTriAttr> attrs; // parallel to tris
     std::vector<HostTriTangent> tangents; // parallel to tris, empty unless some material samples a normal map

@@ -12,7 +12,7 @@ namespace hrt {
 
 struct GpuBuiltBvh {            // device pointers owned by the GpuBvhBuilder that produced them (valid until its next build() / destruction)
     GpuNode* nodes = nullptr; uint32_t nodeCount = 0;
-    GpuNode4* nodes4 = nullptr; uint32_t node4Count = 0;
+    GpuNode4* nodes4 = nullptr; uint32_t node4Count = 0; uint32_t nodes4Capacity = 0;   // capacity: records the nodes4 buffer holds (>= node4Count, checked before the emission)
     GpuTri* tris = nullptr; GpuTriAttr* attrs = nullptr; GpuTriTangent* tangents = nullptr; uint32_t triCount = 0;
     uint32_t maxDepth = 0, maxDepth4 = 0;
     bool ploc = false;          // hierarchy by PLOC (nearest-neighbour clustering) rather than the Morton radix tree

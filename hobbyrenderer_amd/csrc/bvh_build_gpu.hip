@@ -579,6 +579,15 @@ struct Arena {          // one temporary allocation carved into aligned pieces
 
 } // namespace
 
+// leaf size in force: box mode fixes it (Impl::maxLeaf = 1), else HRPT_GPU_BVH_MAX_LEAF (1..4), else 2 -- measured with the greedy collapse:
+// 2 beats 4 on all three test scenes for both hierarchies (-2..-6 % frame time)
+static uint32_t effective_max_leaf(uint32_t fixedLeaf)
+{
+    if (fixedLeaf >= 1 && fixedLeaf <= 4) return fixedLeaf;
+    if (const char* e = getenv("HRPT_GPU_BVH_MAX_LEAF")) { int v = atoi(e); if (v >= 1 && v <= 4) return (uint32_t)v; }
+    return 2;
+}
+
 struct GpuBvhBuilder::Impl {
     BuildBuffers b0{};                 // pointers as carved at prepare(); build() works on a copy (the PLOC path swaps order buffers)
     void* scratch = nullptr; void* prim = nullptr;
@@ -588,6 +597,7 @@ struct GpuBvhBuilder::Impl {
     uint32_t n = 0;
     bool boxes = false;                // prepare_boxes(): the primitives are boxes (one per leaf), no triangle / attribute outputs
     uint32_t maxLeaf = 0;              // 0: the default leaf size (2, HRPT_GPU_BVH_MAX_LEAF); 1 in box mode
+    uint32_t nodes4Capacity = 0;       // records of BuildBuffers::nodes4 (allocate)
     int lastBudget = -1; bool lastUsePloc = false;   // hierarchy attempt that fitted the stacks at the previous build(): a rebuild starts there
     // what refit() needs of the last successful build: the buffer set as the back end saw it (final leaf order in valB), node count, 2-wide depth
     BuildBuffers last{}; bool haveTree = false; uint32_t lastNodeCount = 0, lastMaxDepth = 0, lastBits = 0; bool lastPloc = false;
@@ -662,7 +672,13 @@ hipError_t GpuBvhBuilder::allocate(uint32_t n, const HrptSceneDesc* s, bool need
         b.clusterA = A.take<uint32_t>(n); b.clusterB = A.take<uint32_t>(n); b.nn = A.take<uint32_t>(n); b.mergeFlag = A.take<uint32_t>(n); b.validFlag = A.take<uint32_t>(n);
         b.mergeIdx = A.take<uint32_t>(n); b.validIdx = A.take<uint32_t>(n);
         b.nodes = A.take<GpuNode>(n);            // the traversal kernels read the trees in place: a rebuild may change the node counts
-        b.nodes4 = A.take<GpuNode4>(m.maxLeaf == 1 ? n : n / 2 + 1);      // (single-primitive leaves: up to n - 1 inner nodes survive the collapse of a degenerate tree)
+        // 4-wide nodes of a tree over n primitives with leaves of up to L primitives. A node whose children are all leaves ("terminal") roots a kept
+        // 2-wide node, i.e. more than L primitives; every other node has four children under the greedy collapse (it stops early only when no inner
+        // child is left) and at least three under the fixed one. With T terminal nodes and l leaf children elsewhere: n >= (L + 1) T + l, and the node
+        // count is at most T + (T + l - 1) / 2. For L >= 2 that is at most (n - 1) / 2 (greedy: 4 n / 9); for L = 1 up to 3 n / 4, and never more than the
+        // n - 1 two-wide nodes. build_any still checks the count against this capacity before k_emit4 writes.
+        m.nodes4Capacity = effective_max_leaf(m.maxLeaf) == 1 ? n : n / 2 + 1;
+        b.nodes4 = A.take<GpuNode4>(m.nodes4Capacity);
         m.prim = A.take<char>(std::max(m.sortBytes, m.scanBytes));
         char* vtx = A.take<char>(s ? (size_t)s->vertexCount * sizeof(HrptVertexQuantized) : 0);
         char* idx = A.take<char>(s ? (size_t)s->indexCount * 4 : 0);
@@ -729,9 +745,7 @@ hipError_t GpuBvhBuilder::build_any(const HrptPerInstanceData* instances, const 
     // Hierarchy attempts, best tree first: PLOC (when asked for), then the radix tree over the full 63-bit codes, then radix trees over
     // fewer Morton bits (no re-sort: the order stays the full-code order) until the depth fits the traversal stacks.
     uint32_t nodeCount = 0, maxDepthSeen = 0; int usedBits = 0; bool usedPloc = false;
-    uint32_t maxLeafTris = 2;          // measured with the greedy collapse: 2 beats 4 on all three test scenes for both hierarchies (-2..-6 % frame time)
-    if (const char* e = getenv("HRPT_GPU_BVH_MAX_LEAF")) { int v = atoi(e); if (v >= 1 && v <= 4) maxLeafTris = (uint32_t)v; }
-    if (m.maxLeaf >= 1 && m.maxLeaf <= 4) maxLeafTris = m.maxLeaf;
+    const uint32_t maxLeafTris = effective_max_leaf(m.maxLeaf);
     int plocRadius = kPlocRadius;
     if (const char* e = getenv("HRPT_GPU_PLOC_RADIUS")) { int v = atoi(e); if (v >= 1 && v <= 256) plocRadius = v; }
     const int attempts[] = { 64, 63, 48, 39, 30, 21, 12, 0 };          // 64 = PLOC
@@ -806,23 +820,28 @@ hipError_t GpuBvhBuilder::build_any(const HrptPerInstanceData* instances, const 
     hipLaunchKernelGGL(k_mark4_init, dim3(1), dim3(1), 0, stream, b);
     for (uint32_t d = 0; d <= maxDepthSeen; ++d) hipLaunchKernelGGL(k_mark4, gN, blk, 0, stream, b, nodeCount, d, greedy);
     if ((e = rocprim::exclusive_scan(prim, scanBytes, b.even, b.index4, 0u, nodeCount, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return fail(e, "rocprim::exclusive_scan(even)");
+    // k_emit4 writes nodes4[index4[k]] unchecked: the 4-wide node count is read first and a tree that does not fit the buffer is refused (the caller
+    // builds on the host instead). allocate() argues why that cannot happen while the leaf size is the one the buffer was sized for.
+    uint32_t tail4[2] = { 0, 0 };
+    if ((e = hipMemcpyAsync(&tail4[0], b.index4 + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(&tail4[1], b.even + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH build (collapse)");
+    const uint32_t node4Count = tail4[0] + tail4[1];
+    if (node4Count > m.nodes4Capacity) return fail(hipErrorInvalidValue, "GPU BVH build: the 4-wide tree does not fit its buffer");
     hipLaunchKernelGGL(k_emit4, gN, blk, 0, stream, b, nodeCount, greedy);
     float* sahDev = reinterpret_cast<float*>(b.flags + 4);
     (void)hipMemsetAsync(sahDev, 0, 4, stream);
     hipLaunchKernelGGL(k_sah, gN, blk, 0, stream, b, nodeCount, sahDev);
     if (!m.boxes) hipLaunchKernelGGL(k_attrs, gT, blk, 0, stream, b);
     (void)hipEventRecord(ev1, stream);
-    uint32_t flags[4] = { 0, 0, 0, 0 }, tail4[2] = { 0, 0 }; float sahSum = 0.0f; GpuNode rootNode;
+    uint32_t flags[4] = { 0, 0, 0, 0 }; float sahSum = 0.0f; GpuNode rootNode;
     if ((e = hipMemcpyAsync(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
         (e = hipMemcpyAsync(&sahSum, sahDev, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
         (e = hipMemcpyAsync(&rootNode, b.nodes, sizeof rootNode, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&tail4[0], b.index4 + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&tail4[1], b.even + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
         (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH build (emit)");
     if (flags[0]) return fail(hipErrorInvalidValue, "non-finite vertex position");
-    const uint32_t node4Count = tail4[0] + tail4[1];
     float ms = 0.0f; (void)hipEventElapsedTime(&ms, ev0, ev1);
-    out.nodes = b.nodes; out.nodeCount = nodeCount; out.nodes4 = b.nodes4; out.node4Count = node4Count;
+    out.nodes = b.nodes; out.nodeCount = nodeCount; out.nodes4 = b.nodes4; out.node4Count = node4Count; out.nodes4Capacity = m.nodes4Capacity;
     out.tris = b.tris; out.attrs = b.attrs; out.tangents = b.tangents; out.triCount = n; out.leafOrder = b.valB;
     {   // root box = union of the root's two child boxes
         float dx = std::max(rootNode.lmax[0], rootNode.rmax[0]) - std::min(rootNode.lmin[0], rootNode.rmin[0]);
@@ -880,22 +899,25 @@ hipError_t GpuBvhBuilder::refit_any(const HrptPerInstanceData* instances, const 
     hipLaunchKernelGGL(k_mark4_init, dim3(1), dim3(1), 0, stream, b);
     for (uint32_t d = 0; d <= m.lastMaxDepth; ++d) hipLaunchKernelGGL(k_mark4, gN, blk, 0, stream, b, nodeCount, d, greedy);
     if ((e = rocprim::exclusive_scan(prim, scanBytes, b.even, b.index4, 0u, nodeCount, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return fail(e, "rocprim::exclusive_scan(even)");
+    uint32_t tail4[2] = { 0, 0 };                                      // as in build_any: the count is checked before k_emit4 writes
+    if ((e = hipMemcpyAsync(&tail4[0], b.index4 + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(&tail4[1], b.even + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH refit (collapse)");
+    if (tail4[0] + tail4[1] > m.nodes4Capacity) return fail(hipErrorInvalidValue, "GPU BVH refit: the 4-wide tree does not fit its buffer");
     hipLaunchKernelGGL(k_emit4, gN, blk, 0, stream, b, nodeCount, greedy);
     float* sahDev = reinterpret_cast<float*>(b.flags + 4);
     (void)hipMemsetAsync(sahDev, 0, 4, stream);
     hipLaunchKernelGGL(k_sah, gN, blk, 0, stream, b, nodeCount, sahDev);
     if (!m.boxes) hipLaunchKernelGGL(k_attrs, gT, blk, 0, stream, b);
     (void)hipEventRecord(m.ev1, stream);
-    uint32_t flags[4] = { 0, 0, 0, 0 }, tail4[2] = { 0, 0 }; float sahSum = 0.0f; GpuNode rootNode;
+    uint32_t flags[4] = { 0, 0, 0, 0 }; float sahSum = 0.0f; GpuNode rootNode;
     if ((e = hipMemcpyAsync(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
         (e = hipMemcpyAsync(&sahSum, sahDev, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
         (e = hipMemcpyAsync(&rootNode, b.nodes, sizeof rootNode, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&tail4[0], b.index4 + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&tail4[1], b.even + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
         (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH refit");
     if (flags[0]) return fail(hipErrorInvalidValue, "non-finite vertex position");
     float ms = 0.0f; (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
-    out.nodes = b.nodes; out.nodeCount = nodeCount; out.nodes4 = b.nodes4; out.node4Count = tail4[0] + tail4[1];
+    out.nodes = b.nodes; out.nodeCount = nodeCount; out.nodes4 = b.nodes4; out.node4Count = tail4[0] + tail4[1]; out.nodes4Capacity = m.nodes4Capacity;
     out.tris = b.tris; out.attrs = b.attrs; out.tangents = b.tangents; out.triCount = n; out.leafOrder = b.valB;
     {
         float dx = std::max(rootNode.lmax[0], rootNode.rmax[0]) - std::min(rootNode.lmin[0], rootNode.rmin[0]);

@@ -34,6 +34,7 @@ struct HrptContext {
     std::vector<void*> allocations;          // scene-lifetime device allocations
     std::vector<void*> bvhAllocations;       // acceleration structure of the host builder + per-instance records: replaced by hrpt_update_instances
     GpuNodeQ* nodesQ = nullptr; size_t nodesQCapacity = 0;    // quantised copy of the flat 4-wide tree (pt_device.h GpuNodeQ), kept across rebuilds
+    uint32_t nodes4Capacity = 0;             // records behind view.nodes4 when it is the GPU builder's buffer (0: allocated to size), for hrpt_selftest_read_bvh
     GpuBvhBuilder* gpuBuilder = nullptr;     // GPU builders: geometry + build buffers stay on the device for rebuilds
     GpuBvhBuilder* tlasBuilder = nullptr; uint32_t tlasBuilderInstances = 0;   // two-level structure: the tree over the instances, built on the GPU (build_two_level)
     // host copy of what a rebuild needs (the reference's Scene keeps the same vectors: m_InstanceData, m_Vertices, m_Indices, m_MeshData)
@@ -339,7 +340,7 @@ static int build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t s
     int r;
     c->buildInfo = HrptBuildInfo{};
     c->buildInfo.requestedBuilder = (uint32_t)c->bvhBuilder;
-    c->buildInfo.structure = HRPT_ACCEL_FLAT;
+    c->buildInfo.structure = HRPT_ACCEL_FLAT; c->nodes4Capacity = 0;
     const bool keepMeshTrees = !firstBuild && c->twoLevel != nullptr;       // hrpt_update_instances on a two-level scene
     free_acceleration(c, !firstBuild);
     if (keepMeshTrees || (firstBuild && two_level_wanted(c, s, sceneTris))) {
@@ -372,7 +373,7 @@ static int build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t s
         if (ge == hipSuccess && g.maxDepth + 2 <= kTraversalStackDepth) {
             v.nodes = g.nodes; v.nodeCount = g.nodeCount; v.nodes4 = g.nodes4; v.node4Count = g.node4Count; v.tris = g.tris; v.triCount = g.triCount;
             v.rootLeaf = 0; v.attrs = g.attrs; v.tangents = g.tangents;
-            maxDepth = g.maxDepth; maxDepth4 = g.maxDepth4; built = true;
+            maxDepth = g.maxDepth; maxDepth4 = g.maxDepth4; built = true; c->nodes4Capacity = g.nodes4Capacity;
             if (getenv("HRPT_GPU_BVH_HOST_COLLAPSE")) {     // experiment: the GPU-built 2-wide tree with the host's area-greedy, depth-first 4-wide collapse
                 std::vector<HostNode> n2(g.nodeCount); std::vector<HostNode4> n4; uint32_t d4 = 0;
                 HIP_TRY(c, hipMemcpy(n2.data(), g.nodes, n2.size() * sizeof(HostNode), hipMemcpyDeviceToHost));
@@ -380,7 +381,7 @@ static int build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t s
                 const HostNode4* dn4;
                 if ((r = upload(c, n4.data(), n4.size(), &dn4, &c->bvhAllocations)) != HRPT_OK) return r;
                 HIP_TRY(c, hipStreamSynchronize(c->stream));
-                v.nodes4 = reinterpret_cast<const GpuNode4*>(dn4); v.node4Count = (uint32_t)n4.size(); maxDepth4 = d4;
+                v.nodes4 = reinterpret_cast<const GpuNode4*>(dn4); v.node4Count = (uint32_t)n4.size(); maxDepth4 = d4; c->nodes4Capacity = 0;
             }
             c->buildInfo.usedBuilder = g.ploc ? HRPT_BVH_BUILDER_GPU_PLOC : HRPT_BVH_BUILDER_GPU_LBVH; c->buildInfo.deviceBuildMs = g.deviceMs; c->buildInfo.mortonBits = g.mortonBits; c->buildInfo.sahCost = g.sahCost;
             if (g.refitted) c->buildInfo.usedBuilder |= HRPT_BVH_BUILDER_REFITTED;
@@ -430,7 +431,7 @@ static int build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t s
     // the 64-byte quantised form of the 4-wide tree, whichever builder made it (what the wavefront kernels may read when the tree is not in LDS)
     v.nodesQ = nullptr; bool quantisedNodes = false;
     if (v.node4Count) {
-        if (c->nodesQCapacity < v.node4Count) {
+        if (c->nodesQCapacity <= v.node4Count) {                   // (<=: record nodesQCapacity - 1 is the accumulator below, never a node)
             if (c->nodesQ) (void)hipFree(c->nodesQ);
             c->nodesQ = nullptr; c->nodesQCapacity = 0;
             const size_t cap = (size_t)v.node4Count + v.node4Count / 8 + 64;
@@ -1147,6 +1148,65 @@ int hrpt_selftest_bvh(HrptContext* c, uint64_t* violations)
     (void)hipFree(d);
     if (e != hipSuccess) return fail(c, HRPT_ERR_HIP, std::string("hrpt_selftest_bvh: ") + hipGetErrorString(e));
     *violations = h;
+    return HRPT_OK;
+}
+
+int hrpt_selftest_read_bvh(HrptContext* c, HrptBvhDump* d)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!d) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_selftest_read_bvh: null dump");
+    if (!c->haveScene) return fail(c, HRPT_ERR_NO_SCENE, "hrpt_selftest_read_bvh: no scene uploaded");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const SceneView& v = c->view;
+    const bool twoLevel = v.instances != nullptr;
+    d->structure = twoLevel ? HRPT_ACCEL_TWO_LEVEL : HRPT_ACCEL_FLAT;
+    d->nodeCount = twoLevel ? 0u : v.nodeCount; d->node4Count = v.node4Count; d->triangleCount = v.triCount;
+    d->instanceCount = twoLevel ? v.instanceCount : 0u; d->instanceNodeCount = twoLevel ? v.nodeCount : 0u;
+    d->rootLeaf = v.rootLeaf; d->hasNodesQ = v.nodesQ ? 1u : 0u; d->hasTangents = v.tangents ? 1u : 0u;
+    d->maxDepth = c->buildInfo.maxDepth; d->maxDepth4 = c->buildInfo.maxDepth4;
+    d->maxDepth4Tlas = twoLevel && c->twoLevel ? c->twoLevel->maxDepth4Tlas : 0u; d->maxDepth4Blas = twoLevel && c->twoLevel ? c->twoLevel->maxDepth4Blas : 0u;
+    d->sahCost = c->buildInfo.sahCost;
+    d->nodes4Capacity = twoLevel ? 0u : c->nodes4Capacity; d->nodesQCapacity = v.nodesQ ? (uint32_t)c->nodesQCapacity : 0u;
+    auto fetch = [&](void* dst, const void* src, size_t bytes) { return (dst && src && bytes) ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+    HIP_TRY(c, fetch(d->nodes, twoLevel ? nullptr : v.nodes, (size_t)d->nodeCount * sizeof(GpuNode)));
+    HIP_TRY(c, fetch(d->nodes4, v.nodes4, (size_t)v.node4Count * sizeof(GpuNode4)));
+    HIP_TRY(c, fetch(d->nodesQ, v.nodesQ, (size_t)v.node4Count * sizeof(GpuNodeQ)));
+    HIP_TRY(c, fetch(d->triangles, v.tris, (size_t)v.triCount * sizeof(GpuTri)));
+    HIP_TRY(c, fetch(d->attributes, v.attrs, (size_t)v.triCount * sizeof(GpuTriAttr)));
+    HIP_TRY(c, fetch(d->tangents, v.tangents, (size_t)v.triCount * sizeof(GpuTriTangent)));
+    HIP_TRY(c, fetch(d->instances, v.instances, (size_t)d->instanceCount * sizeof(GpuInstance)));
+    return HRPT_OK;
+}
+
+int hrpt_selftest_host_build(const HrptSceneDesc* scene, uint32_t structure, uint32_t flags, HrptBvhDump* d)
+{
+    if (!scene || !d) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_selftest_host_build: null argument");
+    if ((structure != HRPT_ACCEL_FLAT && structure != HRPT_ACCEL_TWO_LEVEL) || (flags & ~HRPT_HOST_BUILD_SEPARATE_COLLAPSE) ||
+        (flags && structure != HRPT_ACCEL_FLAT)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_selftest_host_build: structure / flags");
+    std::string berr;
+    auto put = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) memcpy(dst, src, bytes); };
+    d->structure = structure; d->hasNodesQ = 0; d->nodes4Capacity = 0; d->nodesQCapacity = 0;
+    if (structure == HRPT_ACCEL_FLAT) {
+        BuiltBvh b;
+        if (!build_scene_bvh(*scene, b, berr)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + berr);
+        if ((flags & HRPT_HOST_BUILD_SEPARATE_COLLAPSE) && !b.nodes.empty()) collapse_bvh2_on_host(b.nodes, b.nodes4, b.maxDepth4);
+        d->nodeCount = (uint32_t)b.nodes.size(); d->node4Count = (uint32_t)b.nodes4.size(); d->triangleCount = (uint32_t)b.tris.size();
+        d->instanceCount = 0; d->instanceNodeCount = 0; d->rootLeaf = b.rootLeaf; d->hasTangents = b.tangents.empty() ? 0u : 1u;
+        d->maxDepth = b.maxDepth; d->maxDepth4 = b.maxDepth4; d->maxDepth4Tlas = 0; d->maxDepth4Blas = 0; d->sahCost = b.sahCost;
+        put(d->nodes, b.nodes.data(), b.nodes.size() * sizeof(HostNode)); put(d->nodes4, b.nodes4.data(), b.nodes4.size() * sizeof(HostNode4));
+        put(d->triangles, b.tris.data(), b.tris.size() * sizeof(HostTri)); put(d->attributes, b.attrs.data(), b.attrs.size() * sizeof(HostTriAttr));
+        put(d->tangents, b.tangents.data(), b.tangents.size() * sizeof(HostTriTangent));
+        return HRPT_OK;
+    }
+    BuiltTwoLevel b;
+    if (!build_scene_two_level(*scene, b, berr)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + berr);
+    d->nodeCount = 0; d->node4Count = (uint32_t)b.nodes4.size(); d->triangleCount = (uint32_t)b.tris.size();
+    d->instanceCount = (uint32_t)b.instances.size(); d->instanceNodeCount = b.tlasNodeCount; d->rootLeaf = b.tlasRootLeaf; d->hasTangents = b.tangents.empty() ? 0u : 1u;
+    d->maxDepth = 0; d->maxDepth4 = b.maxDepth4Tlas + b.maxDepth4Blas; d->maxDepth4Tlas = b.maxDepth4Tlas; d->maxDepth4Blas = b.maxDepth4Blas; d->sahCost = 0.0f;
+    put(d->nodes4, b.nodes4.data(), b.nodes4.size() * sizeof(HostNode4));
+    put(d->triangles, b.tris.data(), b.tris.size() * sizeof(HostTri)); put(d->attributes, b.attrs.data(), b.attrs.size() * sizeof(HostTriAttr));
+    put(d->tangents, b.tangents.data(), b.tangents.size() * sizeof(HostTriTangent)); put(d->instances, b.instances.data(), b.instances.size() * sizeof(HostInstance));
     return HRPT_OK;
 }
 

@@ -51,11 +51,11 @@ constexpr uint32_t kBlock = 256;             // 4 waves
 constexpr uint32_t kMaxLights = 8;
 constexpr size_t kLdsBudget = 64 * 1024;     // dynamic LDS per block: traversal stacks + BVH copy
 // A 64-entry LDS stack is 64 KB per block, i.e. two blocks per CU: it cost 40 % on the scenes that needed it, although the worst case
-// 3 * depth4 + 2 that forces the size is never approached by real rays.
+// 3 * (depth4 + 1) that forces the size is never approached by real rays.
 // Measured (MI355X): a 64-entry LDS stack -> 32 + spill: -33 % frame time on the 1.17 M-triangle scene; closest-hit kernel 32 -> 16 LDS
 // entries + spill: another -3 % there and on config 4 (occupancy); the shadow kernel is faster with 32 (+4 % with 16 on configs 4, 5).
 constexpr int kExtendLdsStack = 16, kShadowLdsStack = 32;
-constexpr uint32_t kMaxStackNeed = 128;        // deepest supported 4-wide stack need (3 * depth4 + 2)
+constexpr uint32_t kMaxStackNeed = 128;        // deepest supported 4-wide stack need (stack_entries4)
 constexpr int kShadowCandidates = 8;           // non-opaque candidates a shadow ray buffers (LdsCandidates: two LDS columns each)
 constexpr int kTwoLevelCandidates = 4;         // the same over the two-level structure (LdsCandidates3: three columns each)
 constexpr size_t kCandidateLdsBytes = (size_t)kShadowCandidates * 2 * kBlock * 4;     // LdsCandidates of one block
@@ -77,11 +77,15 @@ enum : int { kShadowOpaque = 0, kShadowBuffered = 1, kShadowResolve = 2, kShadow
 
 // One instantiation of a traversal kernel family and the dynamic LDS it is launched with (without the candidate columns some modes add: see the
 // launch_* functions of pt_wavefront.hip).
-// stack need classes: BVH2 8/16/32/64 (maxDepth + 2), BVH4 16/32/64 (3 * maxDepth4 + 2); class 64 = "deeper than the LDS part": the kernel keeps
+// stack need classes: BVH2 8/16/32/64 (maxDepth + 2), BVH4 16/32/64 (stack_entries4); class 64 = "deeper than the LDS part": the kernel keeps
 // kExtendLdsStack / kShadowLdsStack entries in LDS and the rest in the overflow columns (LdsStack)
 struct Variant { bool lds = false; int depth = 0, width = 0; size_t ldsBytes = 0; bool twoLevel = false; bool twoLevelCandidates = false; bool quantised = false; };
 
-inline uint32_t stack_need4(const SceneTraits& traits) { return traits.twoLevelStackNeed ? traits.twoLevelStackNeed : 3 * traits.bvh4MaxDepth + 2; }
+// Entries the 4-wide traversal can hold at once: inner_step (pt_device.h) pushes up to three siblings at every inner node it visits, and the path to
+// the deepest inner node (depth4, the root being 0) visits depth4 + 1 of them. (3 * depth4 + 2 stood here before: one entry short on a ray that
+// finds all four children of every node on the deepest path, where the LDS stack wraps and the overflow column is written one row past its end.)
+inline uint32_t stack_entries4(uint32_t depth4) { return 3 * depth4 + 3; }
+inline uint32_t stack_need4(const SceneTraits& traits) { return traits.twoLevelStackNeed ? traits.twoLevelStackNeed : stack_entries4(traits.bvh4MaxDepth); }
 
 // The variant of one kernel class: `width` asked for, `extraBytes` of LDS the kernel takes besides stack and tree (they count against the
 // budget, the launch adds them), `ldsStackMax` stack entries that kernel class keeps in LDS, `padBytes` added to the launch only.
@@ -91,8 +95,8 @@ inline Variant pick_variant(const SceneTraits& traits, const TreeCounts& tree, i
     uint32_t need = traits.twoLevelStackNeed;
     if (need) { v.width = 4; v.twoLevel = true; v.twoLevelCandidates = traits.hasNonOpaque; }     // two-level structure: 4-wide trees in global memory, its own kernels
     else {
-        if (v.width == 4 && 3 * traits.bvh4MaxDepth + 2 > kMaxStackNeed) v.width = 2;
-        need = v.width == 2 ? traits.bvhMaxDepth + 2 : 3 * traits.bvh4MaxDepth + 2;
+        if (v.width == 4 && stack_entries4(traits.bvh4MaxDepth) > kMaxStackNeed) v.width = 2;
+        need = v.width == 2 ? traits.bvhMaxDepth + 2 : stack_entries4(traits.bvh4MaxDepth);
     }
     v.depth = (v.width == 2 && need <= 8) ? 8 : (need <= 16 ? 16 : (need <= 32 ? 32 : 64));
     const size_t bvhBytes = v.twoLevel ? 0 : (v.width == 2 ? (size_t)tree.nodeCount * 64 : (size_t)tree.node4Count * kLdsNode4Stride) + (size_t)tree.triCount * 48;
@@ -177,7 +181,7 @@ inline RenderPlan plan_render(const SceneTraits& traits, const TreeCounts& tree,
     p.extendBlocksPerCu = k.extendBlocksPerCu ? k.extendBlocksPerCu : (k.blocksPerCu ? k.blocksPerCu : (p.vE.lds ? 12u : 6u));
     if (p.vE.depth > kExtendLdsStack || p.vS.depth > kShadowLdsStack) {
         // stack overflow columns for trees whose worst-case stack need exceeds the LDS entries (see LdsStack); sized for the smaller LDS part
-        const uint32_t worst = traits.twoLevelStackNeed ? traits.twoLevelStackNeed : (p.vE.width == 4 || p.vS.width == 4 ? 3 * traits.bvh4MaxDepth + 2 : traits.bvhMaxDepth + 2);
+        const uint32_t worst = traits.twoLevelStackNeed ? traits.twoLevelStackNeed : (p.vE.width == 4 || p.vS.width == 4 ? stack_entries4(traits.bvh4MaxDepth) : traits.bvhMaxDepth + 2);
         p.spillEntries = worst > (uint32_t)kExtendLdsStack ? worst - kExtendLdsStack : 1u;
         p.spillThreads = (size_t)cus * (p.blocksPerCu > p.extendBlocksPerCu ? p.blocksPerCu : p.extendBlocksPerCu) * kBlock;
     }

@@ -29,7 +29,7 @@ lib = C.CDLL(LIB_PATH)
 EXPORTS = [
     "hrpt_create", "hrpt_destroy", "hrpt_last_error", "hrpt_upload_scene", "hrpt_resize", "hrpt_render",
     "hrpt_synchronize", "hrpt_set_stream", "hrpt_get_device_images", "hrpt_read_accumulation", "hrpt_read_output",
-    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_bvh", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
+    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
 ]
@@ -66,6 +66,8 @@ lib.hrpt_reset_stats.argtypes = [C.c_void_p]
 lib.hrpt_selftest_f16_decode.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_selftest_unorm8.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_selftest_bvh.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+lib.hrpt_selftest_read_bvh.argtypes = [C.c_void_p, C.POINTER(S.BvhDump)]
+lib.hrpt_selftest_host_build.argtypes = [C.POINTER(S.SceneDesc), C.c_uint32, C.c_uint32, C.POINTER(S.BvhDump)]
 lib.hrpt_post_process.argtypes = [C.c_void_p, C.POINTER(S.PostParams)]
 lib.hrpt_read_display.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.hrpt_get_exposure.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
@@ -155,6 +157,45 @@ def bloom_pack_probe(rgb):
     if rc != 0:
         raise HrptError(rc, lib.hrpt_last_error(None).decode())
     return packed, unpacked
+
+
+_BVH_DUMP_ARRAYS = (("nodes", S.GpuNode, "nodeCount"), ("nodes4", S.GpuNode4, "node4Count"), ("nodesQ", S.GpuNodeQ, "node4Count"),
+                    ("triangles", S.GpuTri, "triangleCount"), ("attributes", S.GpuTriAttr, "triangleCount"),
+                    ("tangents", S.GpuTriTangent, "triangleCount"), ("instances", S.GpuInstance, "instanceCount"))
+
+
+def _read_bvh_dump(call):
+    """Size query, then fill (HrptBvhDump): returns a dict of the header fields and one structured numpy array per record array
+    (None where the structure has none)."""
+    d = S.BvhDump()
+    call(d)
+    present = {"nodesQ": d.hasNodesQ, "tangents": d.hasTangents}
+    arrays = {}
+    for name, dtype, count in _BVH_DUMP_ARRAYS:
+        if present.get(name, 1):
+            arrays[name] = np.zeros(getattr(d, count), dtype)
+            setattr(d, name, arrays[name].ctypes.data if arrays[name].size else None)
+        else:
+            arrays[name] = None
+    counts = [getattr(d, c) for _, _, c in _BVH_DUMP_ARRAYS]
+    call(d)
+    assert counts == [getattr(d, c) for _, _, c in _BVH_DUMP_ARRAYS], "the structure changed between the size query and the fill"
+    out = {f: getattr(d, f) for f, _ in S.BvhDump._fields_ if f not in arrays}
+    out.update(arrays)
+    return out
+
+
+def host_build_bvh(scene, structure=S.ACCEL_FLAT, separate_collapse=False):
+    """hrpt_selftest_host_build: the host builder's structure for a SceneArrays, without a context or a device (see _read_bvh_dump)."""
+    desc, keep = scene.desc()
+
+    def call(d):
+        rc = lib.hrpt_selftest_host_build(C.byref(desc), int(structure), S.HOST_BUILD_SEPARATE_COLLAPSE if separate_collapse else 0, C.byref(d))
+        if rc != 0:
+            raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    out = _read_bvh_dump(call)
+    del keep
+    return out
 
 
 def allgather(contexts):
@@ -347,6 +388,10 @@ class PathTracerContext:
         v = C.c_uint64()
         self._check(lib.hrpt_selftest_bvh(self._h, C.byref(v)))
         return int(v.value)
+
+    def read_bvh(self):
+        """hrpt_selftest_read_bvh: the structure the kernels currently walk, as host arrays (see _read_bvh_dump)."""
+        return _read_bvh_dump(lambda d: self._check(lib.hrpt_selftest_read_bvh(self._h, C.byref(d))))
 
     def selftest_unorm8(self):
         out = np.empty(512, np.float32)

@@ -149,6 +149,33 @@ class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B
                 ("instanceNodeCount", C.c_uint32), ("distinctMeshes", C.c_uint32), ("leafAreaPermille", C.c_uint32), ("nodeFormat", C.c_uint32)]
 
 
+# Records of the acceleration structure as the kernels read them (csrc/pt_device.h), for hrpt_selftest_read_bvh / hrpt_selftest_host_build.
+i32 = np.int32
+GpuNode = np.dtype([("lmin", f32, 3), ("left", i32), ("lmax", f32, 3), ("right", i32), ("rmin", f32, 3), ("pad0", u32), ("rmax", f32, 3), ("pad1", u32)])
+GpuNode4 = np.dtype([("minx", f32, 4), ("maxx", f32, 4), ("miny", f32, 4), ("maxy", f32, 4), ("minz", f32, 4), ("maxz", f32, 4), ("child", i32, 4), ("pad", u32, 4)])
+GpuNodeQ = np.dtype([("o", f32, 3), ("sx", f32), ("lox", u32), ("hix", u32), ("loy", u32), ("hiy", u32), ("loz", u32), ("hiz", u32), ("sy", f32), ("sz", f32),
+                     ("child", i32, 4)])
+GpuTri = np.dtype([("p0", f32, 3), ("inst", u32), ("p1", f32, 3), ("prim", u32), ("p2", f32, 3), ("flags", u32)])
+GpuTriAttr = np.dtype([("n0", f32, 3), ("n1", f32, 3), ("n2", f32, 3), ("uv0", f32, 2), ("uv1", f32, 2), ("uv2", f32, 2), ("material", u32), ("inst", u32),
+                       ("prim", u32), ("pad", u32, 2)])
+GpuTriTangent = np.dtype([("t0", f32, 4), ("t1", f32, 4), ("t2", f32, 4)])
+GpuInstance = np.dtype([("world", f32, (4, 3)), ("inv", f32, (4, 3)), ("blasRoot", i32), ("flags", u32), ("material", u32), ("boxEps", f32), ("mesh", u32),
+                        ("objMaxAbs", f32), ("invNorm", f32), ("pad", u32)])
+assert (GpuNode.itemsize, GpuNode4.itemsize, GpuNodeQ.itemsize, GpuTri.itemsize, GpuTriAttr.itemsize, GpuTriTangent.itemsize, GpuInstance.itemsize) == \
+    (64, 128, 64, 48, 80, 48, 128)
+BVH_EMPTY_CHILD = 0x7fffffff       # unused slot of a 4-wide node
+HOST_BUILD_SEPARATE_COLLAPSE = 1   # HRPT_HOST_BUILD_SEPARATE_COLLAPSE
+
+
+class BvhDump(C.Structure):        # HrptBvhDump
+    _fields_ = [("structure", C.c_uint32), ("nodeCount", C.c_uint32), ("node4Count", C.c_uint32), ("triangleCount", C.c_uint32),
+                ("instanceCount", C.c_uint32), ("instanceNodeCount", C.c_uint32), ("rootLeaf", C.c_int32), ("hasNodesQ", C.c_uint32),
+                ("hasTangents", C.c_uint32), ("maxDepth", C.c_uint32), ("maxDepth4", C.c_uint32), ("maxDepth4Tlas", C.c_uint32),
+                ("maxDepth4Blas", C.c_uint32), ("sahCost", C.c_float), ("nodes4Capacity", C.c_uint32), ("nodesQCapacity", C.c_uint32),
+                ("nodes", C.c_void_p), ("nodes4", C.c_void_p), ("nodesQ", C.c_void_p), ("triangles", C.c_void_p), ("attributes", C.c_void_p),
+                ("tangents", C.c_void_p), ("instances", C.c_void_p)]
+
+
 ABI_VERSION = 3                    # HRPT_ABI_VERSION (include/hobbyrt_pt.h)
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_GPU_LBVH, BVH_BUILDER_GPU_PLOC, BVH_BUILDER_AUTO = 0, 1, 2, 3
 BVH_BUILDER_REFITTED = 0x100     # ORed into BuildInfo.usedBuilder after a refit (hrpt_refit_instances)

@@ -488,6 +488,31 @@ int  hrpt_reset_stats(HrptContext* ctx);
 /* Device self-test of the acceleration structure: *violations = number of child boxes (2-wide tree and its 4-wide collapse) that do
  * not contain the boxes / triangle vertices below them. 0 for a sound tree; anything else means missed hits. Synchronises. */
 int  hrpt_selftest_bvh(HrptContext* ctx, uint64_t* violations);
+/* Read-back of an acceleration structure for host-side validation (tests/bvh_reference.py): the records exactly as the kernels read them
+ * (layouts: hobbyrenderer_amd/csrc/pt_device.h GpuNode 64 B, GpuNode4 128 B, GpuNodeQ 64 B, GpuTri 48 B, GpuTriAttr 80 B, GpuTriTangent 48 B,
+ * GpuInstance 128 B). Size query, then fill: every call writes the counts; an array pointer that is not NULL receives that array and must
+ * have room for the count the query reported (nodes: nodeCount, nodes4 / nodesQ: node4Count, triangles / attributes / tangents:
+ * triangleCount, instances: instanceCount). Flat structure: the 2-wide tree, its 4-wide collapse, the quantised nodes (hasNodesQ).
+ * Two-level structure: nodeCount = 0, nodes4 = the instance tree ([0, instanceNodeCount), root 0 or rootLeaf) followed by the mesh trees,
+ * triangles in object space (inst = mesh index). */
+typedef struct HrptBvhDump {
+    uint32_t structure;                     /* HRPT_ACCEL_FLAT or HRPT_ACCEL_TWO_LEVEL */
+    uint32_t nodeCount, node4Count, triangleCount, instanceCount, instanceNodeCount;
+    int32_t  rootLeaf;                      /* encoded leaf when the tree (two-level: the instance tree) has no node, else 0 */
+    uint32_t hasNodesQ, hasTangents;
+    uint32_t maxDepth, maxDepth4;           /* as reported by the builder (two-level: maxDepth4 = maxDepth4Tlas + maxDepth4Blas) */
+    uint32_t maxDepth4Tlas, maxDepth4Blas;  /* two-level: LEVELS of the instance tree / of the deepest mesh tree (depth + 1; 0 = no node) */
+    float    sahCost;
+    uint32_t nodes4Capacity, nodesQCapacity;/* records the device allocations behind nodes4 / nodesQ hold (0: allocated to size / absent) */
+    void*    nodes; void* nodes4; void* nodesQ; void* triangles; void* attributes; void* tangents; void* instances;
+} HrptBvhDump;                              /* 64 B + 7 pointers */
+/* The structure the kernels of `ctx` currently walk. Waits for frames in flight; changes nothing. */
+int  hrpt_selftest_read_bvh(HrptContext* ctx, HrptBvhDump* dump);
+/* The host builder alone, without a context or a device: builds `scene` (structure: HRPT_ACCEL_FLAT or HRPT_ACCEL_TWO_LEVEL) and
+ * returns it in the same form (size query, then fill: the tree is built by every call, and is deterministic). A scene that the builder
+ * refuses answers HRPT_ERR_INVALID_ARGUMENT with the reason in hrpt_last_error(NULL). */
+#define HRPT_HOST_BUILD_SEPARATE_COLLAPSE 1u   /* flat only: nodes4 by collapse_bvh2_on_host over the finished 2-wide tree instead of the builder's own collapse */
+int  hrpt_selftest_host_build(const HrptSceneDesc* scene, uint32_t structure, uint32_t flags, HrptBvhDump* dump);
 /* Device self-test: out65536[i] = the kernels' decode of the binary16 bit pattern i (RGBA16F LUT texels). */
 int  hrpt_selftest_f16_decode(HrptContext* ctx, float* out65536);
 /* out512[i] = the kernels' RGBA8_UNORM channel decode of byte i (i < 256); out512[256 + i] = (float)i / 255.0f computed on the device. */
