@@ -171,6 +171,7 @@ int hrpt_create(const HrptDeviceDesc* desc, HrptContext** out)
     if (const char* e = getenv("HRPT_WF_SHADE_SORT")) c->wf.knobs.shadeSort = atoi(e) != 0 ? 1 : 0;
     if (const char* e = getenv("HRPT_WF_SLIM_SHADOW")) c->wf.knobs.noSlimShadow = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_FUSED_PRIMARY")) c->wf.knobs.noFusedPrimary = atoi(e) == 0;
+    if (const char* e = getenv("HRPT_WF_SHADE_LDS_TABLES")) c->wf.knobs.noShadeLdsTables = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_NODE_LOOP_MIN")) c->wf.knobs.nodeLoopMin = (uint32_t)atoi(e);
     if (const char* e = getenv("HRPT_BLOOM_FUSED_TAIL")) { const int v = atoi(e); c->bloomTailTexels = v == 1 ? 8192u : (v > 0 ? (uint32_t)v : 0u); }
     *out = c;
@@ -725,6 +726,7 @@ static int render_impl(HrptContext* c, const HrptFrameParams* p)
     if (wavefront) {
         std::string werr;
         c->wf.profile = (p->flags & HRPT_FRAME_PROFILE) != 0;
+        c->wf.shadeInstances = (uint32_t)c->keptInstances.size(); c->wf.shadeMaterials = (uint32_t)c->keptMaterials.size();    // as uploaded / last updated
         hipError_t e = wavefront_render(c->wf, c->view, c->traits, p->constants, p->accumCount, c->dAccum, c->dOutput, c->width, c->height, rect,
                                         c->dCounters, c->stream, werr);
         if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? HRPT_ERR_OUT_OF_MEMORY : HRPT_ERR_HIP, "wavefront_render: " + werr + ": " + hipGetErrorString(e));

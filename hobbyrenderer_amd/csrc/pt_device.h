@@ -613,9 +613,8 @@ HRT_DEV Hit closest_two_level(const GlobalBvhTl& bvh, int32_t rootLeaf, uint32_t
 // What GetTriangleVertices + UnpackVertex (RaytracingCommon.hlsli:33-50, MeshCommon.hlsli:9-22) yield for a hit,
 // read from the per-triangle record built at upload (the quantised vertex / index buffers are consumed there).
 struct TriVerts { f3 n0, n1, n2; f2 uv0, uv1, uv2; uint32_t material, inst; };
-HRT_DEV TriVerts load_tri_attr(const SceneView& s, uint32_t tri)
+HRT_DEV TriVerts unpack_tri_attr(const float4* p)      // one GpuTriAttr record
 {
-    const float4* p = reinterpret_cast<const float4*>(s.attrs + tri);
     float4 a = p[0], b = p[1], c = p[2], d = p[3], e = p[4];
     TriVerts t;
     t.n0 = mk3(a.x, a.y, a.z); t.n1 = mk3(a.w, b.x, b.y); t.n2 = mk3(b.z, b.w, c.x);
@@ -623,6 +622,7 @@ HRT_DEV TriVerts load_tri_attr(const SceneView& s, uint32_t tri)
     t.material = __float_as_uint(d.w); t.inst = __float_as_uint(e.x);
     return t;
 }
+HRT_DEV TriVerts load_tri_attr(const SceneView& s, uint32_t tri) { return unpack_tri_attr(reinterpret_cast<const float4*>(s.attrs + tri)); }
 // ... for a committed hit: with the two-level structure the record is per MESH triangle and the instance (hence the material) comes
 // from the hit
 HRT_DEV TriVerts load_hit_attr(const SceneView& s, const Hit& hit)
@@ -649,6 +649,29 @@ HRT_DEV f3 transform_normal(f3 n, const GpuInstShade& is)
                (n.x * a0.z + n.y * a1.z) + n.z * a2.z);
     return normalize(o);
 }
+
+// ------------------------------------------------------------------ where the shading path reads its three small tables
+// shade_surface_a (pt_path.h) gathers, per lane, the hit triangle's GpuTriAttr, its instance's GpuInstShade and its material's
+// HrptMaterialConstants. It takes one of these accessors, the way traversal takes LdsBvh / GlobalBvh4:
+//   GlobalShadeTables  the arrays of the SceneView (every kernel but wf_shade_lt)
+//   LdsShadeTables     a block's copy of the three arrays in LDS, whole records in their global layout (pt_wavefront.hip copy_shade_tables).
+//                      Records are addressed by 32-bit LDS byte addresses through address_space(3) pointers so that the reads are ds_read_*:
+//                      a generic pointer into LDS would become flat_load, which takes the vector-memory path the copy exists to avoid.
+struct GlobalShadeTables {
+    const SceneView& s;
+    HRT_DEV TriVerts hit_attr(const Hit& hit) const { return load_hit_attr(s, hit); }
+    HRT_DEV const GpuInstShade& inst_shade(uint32_t inst) const { return s.instShade[inst]; }
+    HRT_DEV const HrptMaterialConstants& material(uint32_t material) const { return s.materials[material]; }
+};
+struct LdsShadeTables {
+    typedef __attribute__((address_space(3))) const char* LdsPtr;
+    uint32_t attrs, instShade, materials;      // LDS byte address of each table (16-byte aligned)
+    template <class T> HRT_DEV const T& at(uint32_t address) const { return *reinterpret_cast<const T*>((const char*)(LdsPtr)(uintptr_t)address); }
+    // (flat structure only: the record holds the instance and the material, load_hit_attr's two-level branch does not apply)
+    HRT_DEV TriVerts hit_attr(const Hit& hit) const { return unpack_tri_attr(&at<float4>(attrs + hit.tri * (uint32_t)sizeof(GpuTriAttr))); }
+    HRT_DEV const GpuInstShade& inst_shade(uint32_t inst) const { return at<GpuInstShade>(instShade + inst * (uint32_t)sizeof(GpuInstShade)); }
+    HRT_DEV const HrptMaterialConstants& material(uint32_t material) const { return at<HrptMaterialConstants>(materials + material * (uint32_t)sizeof(HrptMaterialConstants)); }
+};
 
 // ------------------------------------------------------------------ textures / LUTs
 HRT_DEV int wrap_i(int i, int n, bool wrap)

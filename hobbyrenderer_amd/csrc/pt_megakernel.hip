@@ -53,7 +53,7 @@ __global__ __launch_bounds__(64) void pt_megakernel(SceneView s, HrptPathTracerC
                 f3 neeThroughput;
                 const f3 sunDir = mk3(cb.m_SunDirection[0], cb.m_SunDirection[1], cb.m_SunDirection[2]);
                 const float sunIntensity = s.lights[0].m_Intensity;                  // g_Lights[0], PathTracer.hlsl:137 (quirk kept)
-                SurfaceOutcome oc = shade_surface_a<true, true, false>(s, cb, ps, hit, carry, [&](uint32_t li, float ux, float uy) {
+                SurfaceOutcome oc = shade_surface_a<true, true, false>(s, GlobalShadeTables{ s }, cb, ps, hit, carry, [&](uint32_t li, float ux, float uy) {
                     HrptGPULight l = load_light(s, li);
                     f3 L; float maxDist;
                     if (!nee_direction<false>(l, carry.N, carry.worldPos, sunDir, cb.m_CosSunAngularRadius, ux, uy, L, maxDist)) return;

@@ -494,13 +494,14 @@ enum SurfaceOutcome { SURFACE_TRANSMITTED = 0, SURFACE_SCATTER = 1 };
 //   TEX     some material samples a texture          (false: every m_TextureFlags is 0 -> sampling code compiled out)
 //   TRANS   some material is transmissive or BLEND   (false: the transmission branch :149-255 is compiled out)
 //   DIRONLY every light is directional               (true: point / spot code compiled out)
-template <bool TEX, bool TRANS, bool DIRONLY, class EMIT>
-HRT_DEV SurfaceOutcome shade_surface_a(const SceneView& s, const HrptPathTracerConstants& cb, PathState& ps, const Hit& hit,
+// TABLES: where the triangle, instance and material records are read from (pt_device.h GlobalShadeTables / LdsShadeTables)
+template <bool TEX, bool TRANS, bool DIRONLY, class TABLES, class EMIT>
+HRT_DEV SurfaceOutcome shade_surface_a(const SceneView& s, const TABLES& tables, const HrptPathTracerConstants& cb, PathState& ps, const Hit& hit,
                                        SurfaceCarry& carry, EMIT&& emit)
 {
-    TriVerts tv = load_hit_attr(s, hit);                                          // inst/mesh/vertex fetch :92-94,:104 (LOD 0, :103)
-    GpuInstShade is = s.instShade[tv.inst];
-    const HrptMaterialConstants& mat = s.materials[tv.material];
+    TriVerts tv = tables.hit_attr(hit);                                           // inst/mesh/vertex fetch :92-94,:104 (LOD 0, :103)
+    GpuInstShade is = tables.inst_shade(tv.inst);
+    const HrptMaterialConstants& mat = tables.material(tv.material);
     uint32_t texFlags = TEX ? mat.m_TextureFlags : 0u;
 
     if (TRANS && ps.inVolume) {                                                            // Beer-Lambert :97-100

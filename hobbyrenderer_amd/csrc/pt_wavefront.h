@@ -32,6 +32,7 @@ struct WavefrontState {
     // counters and the record layout of the last render (its plan)
     uint64_t raygenBytes = 0, resolveBytes = 0;
     RenderPlan plan;
+    uint32_t shadeInstances = 0, shadeMaterials = 0;   // records of SceneView::instShade / materials (set by the owner of the scene; 0 = unknown: no LDS tables)
     WavefrontKnobs knobs;
     bool profile = false;              // record HIP events around every extend / shade / shadow launch (HRPT_FRAME_PROFILE)
     // second stream + fork/join events: wf_shadow(b) overlaps wf_extend(b+1) (they share no buffer)

@@ -26,6 +26,7 @@ struct SceneTraits {
 struct TreeCounts {
     uint32_t nodeCount = 0, node4Count = 0, triCount = 0;
     bool hasNodesQ = false, hasInstances = false;      // SceneView::nodesQ / instances != nullptr
+    uint32_t instanceCount = 0, materialCount = 0;     // records of SceneView::instShade / materials (0 = unknown: wf_shade reads its tables from global memory)
 };
 
 // Tuning knobs (0 = default): hrpt_create reads them from the environment, two have setters in the ABI.
@@ -43,6 +44,7 @@ struct WavefrontKnobs {
     bool noFusedPrimary = false;       // HRPT_WF_FUSED_PRIMARY=0: SIMPLE scenes keep the wf_raygen pass (A/B knob)
     bool noSlimShadow = false;         // HRPT_WF_SLIM_SHADOW=0: the SIMPLE shade variant writes full 96-byte shadow-queue entries (A/B knob)
     int shadeSort = -1;                // HRPT_WF_SHADE_SORT = 0 / 1: general wf_shade variants shade in queue order / grouped by shading class (-1: automatic)
+    bool noShadeLdsTables = false;     // HRPT_WF_SHADE_LDS_TABLES=0: wf_shade gathers triangle / instance / material records from global memory even when they fit LDS (A/B knob)
     int shadowPath = 0;                // scenes with non-opaque geometry: 0 = automatic, 1 = wf_shadow traverses itself (buffered query), 2 = any-hit pass + resolve
 };
 
@@ -67,6 +69,23 @@ constexpr size_t kCandidateLdsBytes = (size_t)kShadowCandidates * 2 * kBlock * 4
 constexpr uint32_t kLdsNode4Stride = HRPT_LDS_NODE4_STRIDE;
 static_assert(kLdsNode4Stride >= 128 && kLdsNode4Stride % 32 == 0, "LDS node stride: 128 bytes of node, near / far rows 32-byte aligned");
 constexpr uint32_t kRefillMinDefault = 12;
+// wf_shade
+// The SIMPLE variant parks specular-lobe paths in a per-wave LDS ring of kShadeRing entries x kShadeRingFields floats.
+constexpr uint32_t kShadeRing = 64, kShadeRingFields = 23;
+constexpr size_t kShadeRingBytes = (size_t)(kBlock / 64) * kShadeRing * kShadeRingFields * 4;
+// Every variant is compiled for kWavesShade = 4 waves per SIMD, i.e. four blocks per CU: of the CU's 160 KiB of LDS a block may take 40 KiB,
+// static LDS (the statistics partials, 32 B) and the allocation granularity included -- 1 KiB is kept back for both.
+constexpr uint32_t kShadeBlocksPerCu = 4;
+constexpr size_t kCuLdsBytes = 160 * 1024, kShadeLdsMargin = 1024;
+constexpr size_t kShadeLdsPerBlock = kCuLdsBytes / kShadeBlocksPerCu - kShadeLdsMargin;     // dynamic LDS a wf_shade block may ask for
+// Records of the three tables the shading path gathers from (pt_device.h GpuTriAttr, GpuInstShade; hobbyrt_pt.h HrptMaterialConstants;
+// pt_wavefront.hip asserts the sizes). wf_shade_lt copies them whole, in their global layout, behind the ring.
+constexpr size_t kTriAttrBytes = 80, kInstShadeBytes = 48, kMaterialBytes = 180;
+inline size_t shade_table_bytes(uint32_t triCount, uint32_t instanceCount, uint32_t materialCount)
+{
+    const size_t b = (size_t)triCount * kTriAttrBytes + (size_t)instanceCount * kInstShadeBytes + (size_t)materialCount * kMaterialBytes;
+    return (b + 15) & ~(size_t)15;
+}
 // wf_shadow
 // MODE kShadowOpaque: no ForceNonOpaque instance in the scene: plain any-hit query per light sample.
 // MODE kShadowBuffered: non-opaque geometry, the kernel traverses itself: per-lane candidate buffer in LDS (after the stack) and the buffered query.
@@ -118,6 +137,9 @@ struct RenderPlan {
     uint32_t maxLights = 1, cus = 0, blocksPerCu = 0, extendBlocksPerCu = 0;
     uint32_t spillEntries = 0; size_t spillThreads = 0;    // stack-overflow entries per thread (0 = none) in two columns (wf_extend, wf_shadow) of so many threads each
     uint32_t pathRecordBytes = 48; uint64_t bytesPerSample = 0;    // of the queue pool
+    bool shadeLdsTables = false;       // wf_shade_lt: triangle, instance and material records are served from a per-block LDS copy
+    size_t shadeTableBytes = 0;        // ... which takes so many bytes (0 when the tables stay in global memory)
+    size_t shadeLdsBytes = 0;          // dynamic LDS of the SIMPLE shade launches: the ring + shadeTableBytes (the general variants size their sort tables per batch)
 };
 struct BatchPlan { uint32_t segSize, numSegments, grid, gridExtend; };
 
@@ -191,6 +213,17 @@ inline RenderPlan plan_render(const SceneTraits& traits, const TreeCounts& tree,
     // a kNoPathRecord hit record. 96 B per sample less queue traffic and one launch less: config 2 -3 % one frame at a time, -4 % two in flight
     // (HRPT_WF_FUSED_PRIMARY=0 keeps wf_raygen). As run-time branches inside the ordinary kernels the same code cost every bounce 6 % (extend) and
     // 16 % (shade): the extra live values; and regenerating the ray in wf_shade instead of reading 16 bytes gave the saving back in instructions.
+    // wf_shade's table gathers. Per 64-lane iteration the kernel issues 13 per-lane reads into three read-only tables of a few KB, and a CU's
+    // L1 serves about one lane-request per cycle whatever the width (profiles/r03_gather_nodes_microbench.txt): copied to LDS at block start (every
+    // launch, so hrpt_update_materials / hrpt_update_instances need no bookkeeping) they are ds_reads. Only where the copy still lets a CU hold its
+    // four blocks; only the SIMPLE single-light variants have the LDS instantiation; two-level scenes (per-mesh records, instance from the hit)
+    // and scenes whose counts are unknown keep the global tables. HRPT_WF_SHADE_LDS_TABLES=0 forces the global tables.
+    p.shadeLdsBytes = kShadeRingBytes;
+    if (p.simpleScene && !manyLights && !k.noShadeLdsTables && !tree.hasInstances && !traits.twoLevelStackNeed &&
+        tree.triCount && tree.instanceCount && tree.materialCount) {
+        const size_t tables = shade_table_bytes(tree.triCount, tree.instanceCount, tree.materialCount);
+        if (kShadeRingBytes + tables <= kShadeLdsPerBlock) { p.shadeLdsTables = true; p.shadeTableBytes = tables; p.shadeLdsBytes = kShadeRingBytes + tables; }
+    }
     p.fusedPrimary = p.simpleScene && !manyLights && maxLights <= kMaxLights && p.vE.width == 4 && !traits.hasMedium && !traits.hasStochasticAlpha && !k.noFusedPrimary;
     return p;
 }

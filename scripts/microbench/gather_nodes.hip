@@ -11,6 +11,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
@@ -85,13 +86,78 @@ __global__ __launch_bounds__(256) void walk_coop(const uint4* __restrict__ nodes
     out[blockIdx.x * 256u + threadIdx.x] = acc + idx;
 }
 
+// The gather pattern of wf_shade (pt_wavefront.hip): every lane reads ROWS 16-byte rows of one 80-byte record of a 3 KB table (38 records, config 2's
+// GpuTriAttr table), and RUN consecutive lanes address the SAME record (lanes of a wave that hit the same triangle). LDS = false: global_load_dwordx4
+// from the L1-resident table; LDS = true: the block copies the table to LDS first and reads it with ds_read_b128 (address_space(3) pointers).
+// Run with: ./gather_nodes shade
+constexpr uint32_t kShadeRecords = 38, kShadeRecordRows = 5;
+template <int ROWS, bool LDS>
+__global__ __launch_bounds__(256) void shade_tables(const uint4* __restrict__ table, uint32_t run, int steps, unsigned long long, uint32_t* out)
+{
+    __shared__ uint4 copy[kShadeRecords * kShadeRecordRows];
+    if (LDS) { for (uint32_t i = threadIdx.x; i < kShadeRecords * kShadeRecordRows; i += 256u) copy[i] = table[i]; __syncthreads(); }
+    typedef __attribute__((address_space(3))) const char* LdsPtr;        // 32-bit LDS addresses, as LdsShadeTables (pt_device.h)
+    const uint32_t copyAddress = (uint32_t)(uintptr_t)(LdsPtr) reinterpret_cast<const char*>(copy);
+    const uint32_t group = (blockIdx.x * 256u + threadIdx.x) / run;
+    uint32_t idx = group * 2654435761u, acc = 0;
+    for (int s = 0; s < steps; ++s) {
+        const uint32_t rec = (idx >> 8) % kShadeRecords;
+        uint32_t v = 0;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            uint4 q;
+            if (LDS) q = *reinterpret_cast<const uint4*>((const char*)(LdsPtr)(uintptr_t)(copyAddress + (rec * kShadeRecordRows + r) * 16u)); else q = table[rec * kShadeRecordRows + r];
+            v ^= q.x + q.y + q.z + q.w;
+        }
+        acc += v;
+        idx = idx * 1664525u + 1013904223u + (v & 1u);      // depends on the data; the lanes of a run stay together (same table words, same v)
+    }
+    out[blockIdx.x * 256u + threadIdx.x] = acc + idx;
+}
+
 typedef void (*Kernel)(const uint4*, uint32_t, int, unsigned long long, uint32_t*);
 struct Case { const char* name; Kernel k; int rows, width; };
 
-int main()
+// the wf_shade pattern: global_load against ds_read, for runs of 1 .. 64 lanes per record
+static int shade_cases(int cus)
+{
+    const int blocks = cus * 4;                             // wf_shade's four blocks per CU (4 waves per SIMD)
+    uint4* dTable; CHECK(hipMalloc(&dTable, kShadeRecords * kShadeRecordRows * 16));
+    {
+        std::vector<uint32_t> h(kShadeRecords * kShadeRecordRows * 4);
+        uint32_t x = 12345u; for (auto& w : h) { x = x * 1664525u + 1013904223u; w = x >> 3; }
+        CHECK(hipMemcpy(dTable, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    }
+    uint32_t* dOut; CHECK(hipMalloc(&dOut, (size_t)blocks * 256 * 4));
+    hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    const struct { const char* name; Kernel k; } cases[] = {
+        { "2 x global_load_dwordx4", shade_tables<2, false> }, { "2 x ds_read_b128", shade_tables<2, true> },
+        { "5 x global_load_dwordx4", shade_tables<5, false> }, { "5 x ds_read_b128", shade_tables<5, true> },
+    };
+    printf("wf_shade table gathers: %u records of 80 B (3 KB table), 64 lanes, runs of lanes share a record; %d blocks of 256 per CU\n", kShadeRecords, blocks / cus);
+    printf("%-26s %-14s | %10s %18s %26s\n", "loads / step", "lanes / record", "ms", "wave-steps/us/CU", "CU cyc / wave-instruction");
+    for (const auto& c : cases)
+        for (uint32_t run : { 1u, 4u, 16u, 64u }) {
+            int steps = 2000; float ms = 0.0f;
+            for (int pass = 0; pass < 3; ++pass) {
+                CHECK(hipEventRecord(e0));
+                hipLaunchKernelGGL(c.k, dim3(blocks), dim3(256), 0, 0, dTable, run, steps, 0ull, dOut);
+                CHECK(hipEventRecord(e1)); CHECK(hipEventSynchronize(e1)); CHECK(hipEventElapsedTime(&ms, e0, e1));
+                if (pass == 0) steps = (int)(steps * 20.0f / (ms > 0.01f ? ms : 0.01f));
+                if (steps < 2000) steps = 2000;
+            }
+            const double waveSteps = (double)blocks * 4.0 * steps, clock = 2.2e9, rows = c.name[0] - '0';
+            printf("%-26s %-14u | %10.3f %18.2f %26.1f\n", c.name, run, ms, waveSteps / (ms * 1e3) / cus, ms * 1e-3 * clock / (waveSteps / cus) / rows);
+            fflush(stdout);
+        }
+    return 0;
+}
+
+int main(int argc, char** argv)
 {
     hipDeviceProp_t prop; CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
+    if (argc > 1 && std::string(argv[1]) == "shade") return shade_cases(cus);
     const size_t maxNodes = 1u << 21;                       // 256 MB
     uint4* dNodes; CHECK(hipMalloc(&dNodes, maxNodes * 128));
     {

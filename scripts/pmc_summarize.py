@@ -12,7 +12,7 @@ agg = collections.defaultdict(lambda: collections.defaultdict(list))
 dur = collections.defaultdict(list)
 for f in glob.glob(out + "/p*/**/*counter_collection.csv", recursive=True):
     for row in csv.DictReader(open(f)):
-        m = re.search(r"(wf_shadow_rays|wf_store_primary|wf_[a-z]+|pt_megakernel)(<[^>]*>)?", row["Kernel_Name"])
+        m = re.search(r"(wf_shadow_rays|wf_store_primary|wf_shade_lt|wf_[a-z]+|pt_megakernel)(<[^>]*>)?", row["Kernel_Name"])
         if not m:
             continue
         name = m.group(1)
@@ -22,12 +22,12 @@ for f in glob.glob(out + "/p*/**/*counter_collection.csv", recursive=True):
             name = "wf_extend_anyhit"
         elif name == "wf_extend" and len(targs) > 5 and targs[5] in ("true", "1"):
             name = "wf_extend_primary"
-        elif name == "wf_shade" and len(targs) > 2 and targs[2] in ("true", "1"):
-            name = "wf_shade_primary"
+        elif name in ("wf_shade", "wf_shade_lt") and len(targs) > 2 and targs[2] in ("true", "1"):       # wf_shade_lt: the same kernels over tables in LDS
+            name += "_primary"
         agg[name][row["Counter_Name"]].append(float(row["Counter_Value"]))
 for f in glob.glob(out + "/p1/**/*kernel_trace.csv", recursive=True):
     for row in csv.DictReader(open(f)):
-        m = re.search(r"(wf_shadow_rays|wf_store_primary|wf_[a-z]+|pt_megakernel)", row["Kernel_Name"])
+        m = re.search(r"(wf_shadow_rays|wf_store_primary|wf_shade_lt|wf_[a-z]+|pt_megakernel)", row["Kernel_Name"])
         if m:
             dur[m.group(1)].append((float(row["End_Timestamp"]) - float(row["Start_Timestamp"])) * 1e-6)
 CUS, SIMDS = 256, 1024
