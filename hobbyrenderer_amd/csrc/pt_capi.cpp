@@ -1227,6 +1227,30 @@ int hrpt_selftest_unorm8(HrptContext* c, float* out512)
     return HRPT_OK;
 }
 
+int hrpt_selftest_sample_textures(HrptContext* c, const HrptTextureProbe* probes, HrptTextureProbeResult* results, uint64_t count)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->haveScene) return fail(c, HRPT_ERR_NO_SCENE, "hrpt_selftest_sample_textures: no scene uploaded");
+    if (count == 0) return HRPT_OK;
+    if (!probes || !results) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_selftest_sample_textures: null array");
+    if (count > (1ull << 24)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_selftest_sample_textures: too many probes in one call");
+    const uint32_t materialCount = (uint32_t)c->keptMaterials.size();
+    for (uint64_t i = 0; i < count; ++i)
+        if (probes[i].material >= materialCount) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_selftest_sample_textures: material index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HrptTextureProbe* dProbes = nullptr; HrptTextureProbeResult* dResults = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dProbes), count * sizeof(HrptTextureProbe));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dResults), count * sizeof(HrptTextureProbeResult));
+    if (e == hipSuccess) e = hipMemcpyAsync(dProbes, probes, count * sizeof(HrptTextureProbe), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_sample_textures(c->view, materialCount, dProbes, dResults, (uint32_t)count, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, dResults, count * sizeof(HrptTextureProbeResult), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (dProbes) (void)hipFree(dProbes);
+    if (dResults) (void)hipFree(dResults);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? HRPT_ERR_OUT_OF_MEMORY : HRPT_ERR_HIP, std::string("hrpt_selftest_sample_textures: ") + hipGetErrorString(e));
+    return HRPT_OK;
+}
+
 int hrpt_reset_stats(HrptContext* c)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;

@@ -61,6 +61,9 @@ hipError_t launch_bvh_check(const SceneView& scene, unsigned long long* violatio
 // Self-test: out[i] = device decode of the binary16 pattern i, i in [0, 65536).
 hipError_t launch_unorm8_table(float* out512, hipStream_t stream);
 hipError_t launch_f16_table(float* out, hipStream_t stream);
+// Self-test: results[i] = the shader's texture sampling functions on probes[i] (hrpt_selftest_sample_textures); device arrays.
+hipError_t launch_sample_textures(const SceneView& scene, uint32_t materialCount, const HrptTextureProbe* probes, HrptTextureProbeResult* results,
+                                  uint32_t count, hipStream_t stream);
 
 // Output[xy] = accum.rgb / accum.a (PathTracer.hlsl:339) over the whole image.
 hipError_t launch_resolve(const float4* accumulation, float4* output, uint32_t pixelCount, hipStream_t stream);

@@ -161,6 +161,48 @@ hipError_t launch_f16_table(float* out, hipStream_t stream)
     return hipGetLastError();
 }
 
+// Self-test of texture sampling (hrpt_selftest_sample_textures): one thread per probe calls sample_texture, pbr_textures_batched and
+// sample_texture_grad of pt_device.h as the shade and any-hit code does, over the scene's own texture and material tables.
+__device__ __forceinline__ void store4(float* dst, const f4& v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w; }
+__global__ void pt_sample_textures_kernel(SceneView s, uint32_t materialCount, const HrptTextureProbe* __restrict__ probes,
+                                          HrptTextureProbeResult* __restrict__ results, uint32_t count)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const HrptTextureProbe p = probes[i];
+    HrptTextureProbeResult& r = results[i];
+    f4 zero; zero.x = zero.y = zero.z = zero.w = 0.0f;
+    f4 single[4] = { zero, zero, zero, zero }, batched[4] = { zero, zero, zero, zero }, grad = zero;
+    uint32_t accepted = 0u;
+    if (p.material < materialCount) {
+        const HrptMaterialConstants& m = s.materials[p.material];
+        f2 uv, ddx, ddy; uv.x = p.uv[0]; uv.y = p.uv[1]; ddx.x = p.ddx[0]; ddx.y = p.ddx[1]; ddy.x = p.ddy[0]; ddy.y = p.ddy[1];
+        if (p.texFlags & HRPT_TEXFLAG_ALBEDO) single[0] = sample_texture(s, m.m_AlbedoTextureIndex, m.m_AlbedoSamplerIndex, uv);
+        if (p.texFlags & HRPT_TEXFLAG_ROUGHNESS_METALLIC) single[1] = sample_texture(s, m.m_RoughnessMetallicTextureIndex, m.m_RoughnessSamplerIndex, uv);
+        if (p.texFlags & HRPT_TEXFLAG_EMISSIVE) single[2] = sample_texture(s, m.m_EmissiveTextureIndex, m.m_EmissiveSamplerIndex, uv);
+        if (p.texFlags & HRPT_TEXFLAG_NORMAL) single[3] = sample_texture(s, m.m_NormalTextureIndex, m.m_NormalSamplerIndex, uv);
+#ifndef HRPT_NO_BATCHED_TEXTURES
+        f4 tex[4];
+        if (pbr_textures_batched(s, uv, m, p.texFlags, tex)) {
+            accepted = 1u;
+            for (int k = 0; k < 4; ++k) batched[k] = tex[k];
+        }
+#endif
+        if (m.m_AlbedoTextureIndex < s.textureCount && s.textures[m.m_AlbedoTextureIndex].texels)      // candidate_alpha_grad's guards
+            grad = sample_texture_grad(s.textures[m.m_AlbedoTextureIndex], m.m_AlbedoSamplerIndex, uv, ddx, ddy);
+    }
+    for (int k = 0; k < 4; ++k) { store4(r.single[k], single[k]); store4(r.batched[k], batched[k]); }
+    r.batchedAccepted = accepted; r.pad[0] = r.pad[1] = r.pad[2] = 0u;
+    store4(r.grad, grad);
+}
+hipError_t launch_sample_textures(const SceneView& scene, uint32_t materialCount, const HrptTextureProbe* probes, HrptTextureProbeResult* results,
+                                  uint32_t count, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(pt_sample_textures_kernel, dim3((count + 63u) / 64u), dim3(64), 0, stream, scene, materialCount, probes, results, count);
+    return hipGetLastError();
+}
+
 // Self-test of the acceleration structure (hrpt_selftest_bvh): every child box stored in a node must contain what hangs below it -- the
 // child's own child boxes when it is an inner node, the vertices of its triangles when it is a leaf. The GPU builder fits boxes bottom-up
 // with relaxed agent-scope atomics and write-through stores (bvh_build_gpu.hip k_fit); a stale read there would give a parent box that is

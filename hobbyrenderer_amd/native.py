@@ -29,7 +29,7 @@ lib = C.CDLL(LIB_PATH)
 EXPORTS = [
     "hrpt_create", "hrpt_destroy", "hrpt_last_error", "hrpt_upload_scene", "hrpt_resize", "hrpt_render",
     "hrpt_synchronize", "hrpt_set_stream", "hrpt_get_device_images", "hrpt_read_accumulation", "hrpt_read_output",
-    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
+    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
 ]
@@ -65,6 +65,7 @@ lib.hrpt_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_ui
 lib.hrpt_reset_stats.argtypes = [C.c_void_p]
 lib.hrpt_selftest_f16_decode.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_selftest_unorm8.argtypes = [C.c_void_p, C.c_void_p]
+lib.hrpt_selftest_sample_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
 lib.hrpt_selftest_bvh.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 lib.hrpt_selftest_read_bvh.argtypes = [C.c_void_p, C.POINTER(S.BvhDump)]
 lib.hrpt_selftest_host_build.argtypes = [C.POINTER(S.SceneDesc), C.c_uint32, C.c_uint32, C.POINTER(S.BvhDump)]
@@ -397,6 +398,15 @@ class PathTracerContext:
         out = np.empty(512, np.float32)
         self._check(lib.hrpt_selftest_unorm8(self._h, out.ctypes.data))
         return out[:256], out[256:]
+
+    def selftest_sample_textures(self, probes):
+        """hrpt_selftest_sample_textures: probes = structured array of S.TextureProbe over the uploaded scene's materials; returns a
+        structured array of S.TextureProbeResult (the shader's one-by-one, batched and gradient sampling of every probe)."""
+        probes = np.ascontiguousarray(probes, S.TextureProbe)
+        results = np.zeros(len(probes), S.TextureProbeResult)
+        self._check(lib.hrpt_selftest_sample_textures(self._h, probes.ctypes.data if len(probes) else None, results.ctypes.data if len(probes) else None,
+                                                      len(probes)))
+        return results
 
     def reset_stats(self):
         self._check(lib.hrpt_reset_stats(self._h))

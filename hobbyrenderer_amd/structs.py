@@ -52,6 +52,7 @@ assert PathTracerConstants.fields["m_SunDirection"][1] == 752 and PathTracerCons
 
 TEXFLAG_ALBEDO, TEXFLAG_NORMAL, TEXFLAG_ROUGHNESS_METALLIC, TEXFLAG_EMISSIVE = 1, 2, 4, 8
 ALPHA_MODE_OPAQUE, ALPHA_MODE_MASK, ALPHA_MODE_BLEND = 0, 1, 2
+TEXTURE_PROBE_SLOT_FLAGS = (TEXFLAG_ALBEDO, TEXFLAG_ROUGHNESS_METALLIC, TEXFLAG_EMISSIVE, TEXFLAG_NORMAL)
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2
 FRAME_DEFAULT, FRAME_MEGAKERNEL, FRAME_WAVEFRONT, FRAME_PROFILE = 0, 1, 2, 4
 
@@ -140,6 +141,10 @@ class Stats(C.Structure):
 Ray = np.dtype([("origin", f32, 3), ("tmin", f32), ("direction", f32, 3), ("tmax", f32), ("rng", u32), ("pad", u32, 3)])       # HrptRay, 48 B
 RayHit = np.dtype([("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32), ("hit", u32), ("rng", u32), ("pad", u32)])   # HrptRayHit, 32 B
 RAYS_CLOSEST, RAYS_SHADOW, RAYS_DEVICE_POINTERS, RAYS_THREAD_PER_RAY = 0, 1, 0x100, 0x200
+# hrpt_selftest_sample_textures; slots of single / batched: albedo, roughness-metallic, emissive, normal (TEXTURE_PROBE_SLOT_FLAGS)
+TextureProbe = np.dtype([("material", u32), ("uv", f32, 2), ("ddx", f32, 2), ("ddy", f32, 2), ("texFlags", u32)])                       # HrptTextureProbe, 32 B
+TextureProbeResult = np.dtype([("single", f32, (4, 4)), ("batched", f32, (4, 4)), ("batchedAccepted", u32), ("pad", u32, 3), ("grad", f32, 4)])   # HrptTextureProbeResult, 160 B
+assert TextureProbe.itemsize == 32 and TextureProbeResult.itemsize == 160
 
 
 class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B

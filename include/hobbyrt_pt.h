@@ -517,6 +517,16 @@ int  hrpt_selftest_host_build(const HrptSceneDesc* scene, uint32_t structure, ui
 int  hrpt_selftest_f16_decode(HrptContext* ctx, float* out65536);
 /* out512[i] = the kernels' RGBA8_UNORM channel decode of byte i (i < 256); out512[256 + i] = (float)i / 255.0f computed on the device. */
 int  hrpt_selftest_unorm8(HrptContext* ctx, float* out512);
+/* Device self-test of texture sampling over the uploaded scene's own texture and material tables (tests/texture_reference.py states the
+ * same filtering in float64): one thread per probe calls the shader's sampling functions as they are. A probe names a material of the
+ * scene, a uv, the gradients of a SampleGrad and the texture-flag mask the shader would pass. Slots are ordered albedo, roughness-metallic,
+ * emissive, normal. single[k]: the slot's texture through the one-by-one path (SampleLevel at level 0) when its flag is in texFlags, else
+ * zeros; batched[k]: the same four through the batched fetch of the shade kernels, batchedAccepted saying whether it took the material
+ * (8-bit formats only; when 0, batched holds zeros); grad: the albedo texture through SampleGrad with ddx / ddy, whatever texFlags says
+ * (zeros when the material's albedo index names no texture). probes / results are host arrays; count == 0 does nothing. Synchronises. */
+typedef struct HrptTextureProbe { uint32_t material; float uv[2], ddx[2], ddy[2]; uint32_t texFlags; } HrptTextureProbe;                /* 32 B */
+typedef struct HrptTextureProbeResult { float single[4][4]; float batched[4][4]; uint32_t batchedAccepted, pad[3]; float grad[4]; } HrptTextureProbeResult;   /* 160 B */
+int  hrpt_selftest_sample_textures(HrptContext* ctx, const HrptTextureProbe* probes, HrptTextureProbeResult* results, uint64_t count);
 
 /* Host-side helpers of PathTracerRenderer::Render, exported so that callers in other languages
  * produce the same constants: Halton (src/Utilities.cpp:67-79) and the CB fill (:58-75). */

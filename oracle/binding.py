@@ -74,6 +74,10 @@ def lib():
         L.or_sky_radiance.restype = None
         L.or_sun_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         L.or_sun_radiance.restype = None
+        L.or_sample_texture.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.or_sample_texture.restype = None
+        L.or_sample_texture_grad.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.or_sample_texture_grad.restype = None
         L.or_post_process.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
         L.or_post_process.restype = None
         for n in ("or_log2", "or_exp2"):
@@ -158,6 +162,25 @@ class Oracle:
         out = np.zeros(3, np.float32)
         a, b = (np.ascontiguousarray(x, np.float32) for x in (world_pos, sun_dir))
         lib().or_sun_radiance(self._h, a.ctypes.data, b.ctypes.data, sun_intensity, out.ctypes.data)
+        return out
+
+    def sample_texture(self, tex, sampler, uv):
+        """or_sample_texture for every row of uv (n, 2): the oracle's SampleLevel at level 0 of texture `tex`, float32 (n, 4)."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 4), np.float32)
+        f, h, pu, po = lib().or_sample_texture, self._h, uv.ctypes.data, out.ctypes.data
+        for i in range(len(uv)):
+            f(h, tex, sampler, pu + 8 * i, po + 16 * i)
+        return out
+
+    def sample_texture_grad(self, tex, sampler, uv, ddx, ddy):
+        """or_sample_texture_grad for every row of uv / ddx / ddy (n, 2): the oracle's SampleGrad of texture `tex`, float32 (n, 4)."""
+        uv, ddx, ddy = (np.ascontiguousarray(a, np.float32).reshape(-1, 2) for a in (uv, ddx, ddy))
+        assert len(uv) == len(ddx) == len(ddy)
+        out = np.zeros((len(uv), 4), np.float32)
+        f, h, pu, px, py, po = lib().or_sample_texture_grad, self._h, uv.ctypes.data, ddx.ctypes.data, ddy.ctypes.data, out.ctypes.data
+        for i in range(len(uv)):
+            f(h, tex, sampler, pu + 8 * i, px + 8 * i, py + 8 * i, po + 16 * i)
         return out
 
 

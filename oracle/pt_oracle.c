@@ -1429,6 +1429,20 @@ float or_shadow_query(OrContext* c, const float worldPos[3], const float L[3], f
     return calculate_rt_shadow(&tl, V3(worldPos[0], worldPos[1], worldPos[2]), V3(L[0], L[1], L[2]), maxDist);
 }
 
+/* The oracle's own sampler (SampleLevel at level 0 / SampleGrad) as stand-alone queries: checkers for hrpt_selftest_sample_textures. */
+void or_sample_texture(const OrContext* c, uint32_t tex, uint32_t sampler, const float uv[2], float out4[4])
+{
+    v2 p = { uv[0], uv[1] };
+    v4 r = sample_texture(c, tex, sampler, p);
+    out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = r.w;
+}
+void or_sample_texture_grad(const OrContext* c, uint32_t tex, uint32_t sampler, const float uv[2], const float ddx[2], const float ddy[2], float out4[4])
+{
+    v2 p = { uv[0], uv[1] }, gx = { ddx[0], ddx[1] }, gy = { ddy[0], ddy[1] };
+    v4 r = sample_texture_grad(c, tex, sampler, p, gx, gy);
+    out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = r.w;
+}
+
 /* ------------------------------------------------------------------ HDR post chain */
 float or_log2(float x) { return hrt_log2(x); }
 float or_exp2(float x) { return hrt_exp2(x); }

@@ -81,7 +81,12 @@ int      or_trace_closest(OrContext* ctx, const float origin[3], const float dir
 int      or_trace_standard(OrContext* ctx, const float origin[3], const float dir[3], float tmin, float tmax, uint32_t* rng,
                            uint32_t* inst, uint32_t* prim, float bary[2], float* t);
 float    or_shadow_query(OrContext* ctx, const float worldPos[3], const float L[3], float maxDist);
-/* GetAtmosphereSkyRadiance / GetAtmosphereSunRadiance (Atmosphere.hlsli:569-601) */
+/* SampleBindlessTextureLevel(lod 0) / SampleBindlessTextureGrad of texture `tex` of the scene (Bindless.hlsli:118-132) as stand-alone
+ * queries (checkers for hrpt_selftest_sample_textures); a texture index that names no texture samples as zero */
+void     or_sample_texture(const OrContext* ctx, uint32_t tex, uint32_t sampler, const float uv[2], float out4[4]);
+void     or_sample_texture_grad(const OrContext* ctx, uint32_t tex, uint32_t sampler, const float uv[2], const float ddx[2], const float ddy[2],
+                                float out4[4]);
+/* GetAtmosphereSkyRadiance /GetAtmosphereSunRadiance (Atmosphere.hlsli:569-601) */
 void     or_sky_radiance(OrContext* ctx, const float cameraPos[3], const float viewRay[3], const float sunDir[3],
                          float sunIntensity, int addSunDisk, float out[3]);
 void     or_sun_radiance(OrContext* ctx, const float worldPos[3], const float sunDir[3], float sunIntensity, float out[3]);
