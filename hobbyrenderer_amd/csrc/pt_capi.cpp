@@ -50,6 +50,7 @@ struct HrptContext {
     uint32_t* dHistogram = nullptr; float* dExposure = nullptr;   // persistent exposure buffer (HDRRenderer m_RG_ExposureBuffer)
     uint32_t* dBloomDown = nullptr; uint32_t* dBloomUp = nullptr; size_t bloomWords = 0;   // bloom pyramids (packed R11G11B10_FLOAT), sized by the last bloom call
     uint32_t bloomTailTexels = 0;            // HRPT_BLOOM_FUSED_TAIL: levels of at most this many texels run in one workgroup's LDS (0 = one kernel per pass, the measured-faster default)
+    float4* dGBuffer[HRPT_GB_PLANES] = {};   // first-hit G-buffer planes (hrpt_render_gbuffer): allocated by the first call that requests one, re-allocated by hrpt_resize
     DeviceCounters* dCounters = nullptr;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
@@ -188,6 +189,7 @@ void hrpt_destroy(HrptContext* c)
     if (c->dAccum) (void)hipFree(c->dAccum);
     if (c->dOutput) (void)hipFree(c->dOutput);
     if (c->dDisplay) (void)hipFree(c->dDisplay);
+    for (float4* plane : c->dGBuffer) if (plane) (void)hipFree(plane);
     if (c->dHistogram) (void)hipFree(c->dHistogram);
     if (c->dExposure) (void)hipFree(c->dExposure);
     if (c->dBloomDown) (void)hipFree(c->dBloomDown);
@@ -682,6 +684,12 @@ int hrpt_resize(HrptContext* c, uint32_t width, uint32_t height)
     HIP_TRY(c, hipMalloc((void**)&c->dOutput, bytes));
     HIP_TRY(c, hipMemsetAsync(c->dAccum, 0, bytes, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->dOutput, 0, bytes, c->stream));
+    for (float4*& plane : c->dGBuffer) {       // the G-buffer planes a caller has asked for follow the image size (zeroed, like a first request)
+        if (!plane) continue;
+        (void)hipFree(plane); plane = nullptr;
+        HIP_TRY(c, hipMalloc((void**)&plane, bytes));
+        HIP_TRY(c, hipMemsetAsync(plane, 0, bytes, c->stream));
+    }
     c->width = width; c->height = height;
     return HRPT_OK;
 }
@@ -819,6 +827,62 @@ static int read_image(HrptContext* c, const float4* src, float* dst, size_t byte
 }
 int hrpt_read_accumulation(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->dAccum : nullptr, rgba, bytes, "hrpt_read_accumulation"); }
 int hrpt_read_output(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->dOutput : nullptr, rgba, bytes, "hrpt_read_output"); }
+
+// First-hit G-buffer: the checks of render_impl that apply (no bounces, no lights), then one of the two kernel paths. No events, no counters, no
+// fallback count: HrptStats keeps describing renders.
+static int render_gbuffer_impl(HrptContext* c, const HrptFrameParams* p, uint32_t planeMask)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: null params");
+    if (planeMask == 0 || (planeMask >> HRPT_GB_PLANES) != 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: planeMask must name at least one of the HRPT_GB_PLANES planes and no other bit");
+    if (!c->haveScene) return fail(c, HRPT_ERR_NO_SCENE, "hrpt_render_gbuffer: no scene uploaded");
+    if (!c->dAccum) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: hrpt_resize not called");
+    if (p->accumCount != 1) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: accumCount must be 1 (the planes describe path vertex 0 of ONE accumulation index)");
+    uint32_t vw = (uint32_t)p->constants.m_View.m_ViewportSize[0], vh = (uint32_t)p->constants.m_View.m_ViewportSize[1];
+    if (vw != c->width || vh != c->height) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: m_ViewportSize does not match hrpt_resize");
+    TileRect rect; rect.x0 = p->tileX0; rect.y0 = p->tileY0; rect.x1 = p->tileX1; rect.y1 = p->tileY1;
+    rect.stripeCount = p->stripeCount ? p->stripeCount : 1u; rect.stripeIndex = p->stripeIndex;
+    if (rect.stripeIndex >= rect.stripeCount) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: stripeIndex must be below stripeCount");
+    if (rect.x0 == 0 && rect.y0 == 0 && rect.x1 == 0 && rect.y1 == 0) { rect.x1 = c->width; rect.y1 = c->height; }
+    if (rect.x1 > c->width || rect.y1 > c->height || rect.x0 > rect.x1 || rect.y0 > rect.y1)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: tile rectangle outside the image");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool wavefront = (p->flags & HRPT_FRAME_MEGAKERNEL) == 0;
+    if (!wavefront && c->view.instances && c->traits.twoLevelStackNeed > 64u)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: this two-level structure is deeper than the validation kernel's 64-entry stack");
+    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+    for (uint32_t k = 0; k < HRPT_GB_PLANES; ++k) {
+        if (!(planeMask & (1u << k)) || c->dGBuffer[k]) continue;
+        HIP_TRY(c, hipMalloc((void**)&c->dGBuffer[k], bytes));
+        HIP_TRY(c, hipMemsetAsync(c->dGBuffer[k], 0, bytes, c->stream));
+    }
+    if (wavefront) {
+        std::string werr;
+        hipError_t e = wavefront_gbuffer(c->wf, c->view, c->traits, p->constants, c->dGBuffer, planeMask, c->width, rect, c->stream, werr);
+        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? HRPT_ERR_OUT_OF_MEMORY : HRPT_ERR_HIP, "wavefront_gbuffer: " + werr + ": " + hipGetErrorString(e));
+    } else HIP_TRY(c, launch_gbuffer_megakernel(c->view, p->constants, c->dGBuffer, planeMask, c->width, rect, c->stream));
+    return HRPT_OK;
+}
+int hrpt_render_gbuffer(HrptContext* c, const HrptFrameParams* p, uint32_t planeMask)
+{
+    try { return render_gbuffer_impl(c, p, planeMask); }
+    catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_render_gbuffer: host allocation failed"); }
+    catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_render_gbuffer: ") + e.what()); }
+}
+int hrpt_read_gbuffer(HrptContext* c, uint32_t plane, void* dst, size_t bytes)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (plane >= HRPT_GB_PLANES) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_gbuffer: unknown plane");
+    if (!c->dGBuffer[plane]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_gbuffer: plane " + std::to_string(plane) + " was never requested from hrpt_render_gbuffer");
+    return read_image(c, c->dGBuffer[plane], static_cast<float*>(dst), bytes, "hrpt_read_gbuffer");
+}
+int hrpt_get_gbuffer_device(HrptContext* c, uint32_t plane, void** devicePtr)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (plane >= HRPT_GB_PLANES || !devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_gbuffer_device: unknown plane or null out");
+    *devicePtr = c->dGBuffer[plane];
+    return HRPT_OK;
+}
 
 int hrpt_write_accumulation(HrptContext* c, const float* rgba, size_t bytes)
 {

@@ -36,6 +36,11 @@ struct TileRect {
 hipError_t launch_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* accumulation,
                              float4* output, uint32_t imageWidth, TileRect rect, DeviceCounters* counters, hipStream_t stream);
 
+// First-hit G-buffer through the validation path (pt_gbuffer.h): planes[HRPT_GB_PLANES] device images of imageWidth x H float4, of which those in
+// planeMask are written inside `rect`; constants.m_Jitter / m_AccumulationIndex are used as given.
+hipError_t launch_gbuffer_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* const* planes, uint32_t planeMask,
+                                     uint32_t imageWidth, TileRect rect, hipStream_t stream);
+
 // HDR post chain over `hdr` (W*H float4): histogram[256] + exposure[1] are context-owned device buffers.
 hipError_t launch_post_chain(const float4* hdr, float4* display, uint32_t pixelCount, const HrptPostParams& params, uint32_t* histogram,
                              float* exposure, hipStream_t stream);

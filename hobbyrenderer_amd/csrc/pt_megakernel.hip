@@ -5,6 +5,7 @@
 // oracle; the wavefront pipeline (pt_wavefront.hip) is the production path and reuses the same stages.
 #include <type_traits>
 
+#include "pt_gbuffer.h"
 #include "pt_kernels.h"
 #include "pt_path.h"
 
@@ -94,6 +95,37 @@ __global__ __launch_bounds__(64) void pt_megakernel(SceneView s, HrptPathTracerC
         atomicAdd(&shard->shadowRays, sh);
         atomicAdd(&shard->paths, pa);
     }
+}
+
+// First-hit G-buffer, validation path (hrpt_render_gbuffer with HRPT_FRAME_MEGAKERNEL): one thread per pixel, 8x8 pixel tile per wave like
+// pt_megakernel: init_path -> trace_standard -> gbuffer_texels (pt_gbuffer.h) -> one 16-byte store per requested plane. No counters: HrptStats
+// describes renders.
+template <bool TL>
+__global__ __launch_bounds__(64) void pt_gbuffer_kernel(SceneView s, HrptPathTracerConstants cb, GBufferPlanes planes, uint32_t planeMask,
+                                                        uint32_t imageWidth, TileRect rect)
+{
+    const uint32_t lx = threadIdx.x & 7u, ly = threadIdx.x >> 3;
+    const uint32_t px = rect.column_x(blockIdx.x) + lx, py = rect.y0 + blockIdx.y * 8u + ly;
+    if (!(px < rect.x1 && py < rect.y1)) return;
+    typename std::conditional<TL, GlobalBvhTl, GlobalBvh>::type bvh;
+    if constexpr (TL) { bvh.nodes = s.nodes4; bvh.tris = s.tris; bvh.instances = s.instances; } else { bvh.nodes = s.nodes; bvh.tris = s.tris; }
+    PrivateStack stack;
+    PathState ps; init_path(ps, cb, px, py);
+    float4 texel[kGbPlanes];
+    Hit hit;
+    if (trace_standard(s, bvh, ps.ray, ps.rng, stack, hit)) gbuffer_texels(s, cb, ps.ray, hit, texel);
+    else gbuffer_miss(texel);
+    gbuffer_store(planes, planeMask, (size_t)py * imageWidth + px, texel);
+}
+hipError_t launch_gbuffer_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* const* planes, uint32_t planeMask,
+                                     uint32_t imageWidth, TileRect rect, hipStream_t stream)
+{
+    if (rect.x1 <= rect.x0 || rect.y1 <= rect.y0 || rect.columns() == 0) return hipSuccess;
+    GBufferPlanes g; for (uint32_t k = 0; k < kGbPlanes; ++k) g.plane[k] = planes[k];
+    dim3 grid(rect.columns(), (rect.y1 - rect.y0 + 7) / 8, 1);
+    if (scene.instances) hipLaunchKernelGGL(pt_gbuffer_kernel<true>, grid, dim3(64, 1, 1), 0, stream, scene, constants, g, planeMask, imageWidth, rect);
+    else hipLaunchKernelGGL(pt_gbuffer_kernel<false>, grid, dim3(64, 1, 1), 0, stream, scene, constants, g, planeMask, imageWidth, rect);
+    return hipGetLastError();
 }
 
 __global__ void pt_resolve_kernel(const float4* __restrict__ accumulation, float4* __restrict__ output, uint32_t n)

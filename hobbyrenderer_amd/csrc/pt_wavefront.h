@@ -21,6 +21,8 @@ struct WavefrontState {
     size_t spillBytes = 0;
     void* traceSpill = nullptr;        // the same for hrpt_trace_rays batches
     size_t traceSpillBytes = 0;
+    void* gbPool = nullptr;            // queue pool of hrpt_render_gbuffer calls the render's pool is too small for (never rendered, or a smaller tile)
+    size_t gbPoolBytes = 0;
     // start/stop event pairs around every extend / shade / shadow launch; kind[i] = 0,1,2
     std::vector<hipEvent_t> events;
     std::vector<uint8_t> kind;
@@ -47,6 +49,10 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
 // hrpt_trace_rays over device arrays (where wavefront_trace_rays_supported, pt_wavefront_plan.h)
 hipError_t wavefront_trace_rays(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptRay* rays, HrptRayHit* hits, uint64_t count,
                                 bool shadow, hipStream_t stream, std::string& error);
+// hrpt_render_gbuffer: the render's bounce-0 front end over one sample per pixel of `rect`, then wf_gbuffer into the planes of planeMask
+// (planes[HRPT_GB_PLANES], width x H float4 each). Leaves the statistics, the plan and the timing state of renders alone.
+hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
+                             float4* const* planes, uint32_t planeMask, uint32_t width, TileRect rect, hipStream_t stream, std::string& error);
 void wavefront_release(WavefrontState& st);
 void wavefront_collect_timing(WavefrontState& st);   // call after the stream is synchronised; folds pending events into kernelMs
 void wavefront_reset_timing(WavefrontState& st);

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "pt_gbuffer.h"
 #include "pt_path.h"
 
 #ifdef HRPT_PHASE_PROFILE
@@ -1300,6 +1301,45 @@ __global__ __launch_bounds__(kBlock) void wf_resolve(WfArgs a, float4* __restric
     }
 }
 
+// ------------------------------------------------------------------ first-hit G-buffer (hrpt_render_gbuffer)
+// Runs after wf_raygen + wf_extend(0) of a one-sample-per-pixel batch: persistent waves over the segments of path queue 0, like wf_shade. A lane
+// takes one path, reads its ray, sample index and hit record (+ instance on two-level scenes), gathers the triangle / instance / material records
+// from global memory, evaluates gbuffer_texels (pt_gbuffer.h: full_hit_attributes + pbr_attributes, the code wf_shade runs) and stores one float4
+// per requested plane at the sample's pixel. wf_raygen enumerates samples in 8 x 8 pixel tiles and compacts only the padding away, so eight
+// consecutive lanes hold eight consecutive pixels of a row: each plane store of a wave covers whole 128-byte row pieces. planeMask is a kernel
+// argument: the stores are the only code it guards. No shading-class sort and no LDS tables (wf_shade's answers to its long divergent branches and
+// its thirteen gathers per path): this kernel's divergent part is pbr_attributes alone, see DESIGN.md section 15.
+__global__ __launch_bounds__(kBlock) void wf_gbuffer(WfArgs a, HrptPathTracerConstants cb, GBufferPlanes g, uint32_t planeMask)
+{
+    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
+    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
+    const SceneView& s = a.scene;
+    for (uint32_t seg = gw; seg < a.numSegments; seg += totalWaves) {
+        const uint32_t cnt = uniform(a.b.pathCnt[0][seg]), segBase = seg * a.segSize;
+        for (uint32_t base = 0; base < cnt; base += 64) {
+            if (base + lane >= cnt) continue;
+            const uint32_t slot = segBase + base + lane;
+            const float4 o = a.b.rayO[0][slot], d = a.b.rayD[0][slot], ha = a.b.hit[slot];
+            const uint32_t smp = reinterpret_cast<const uint32_t*>(a.b.thr[0] + slot)[3];       // one accumulation index: sample == padded pixel
+            const uint32_t tile = smp >> 6, within = smp & 63u;
+            // tile_position with selects instead of two arms (as two arms the compiler parked the quotient / remainder pair in scratch here)
+            const bool columnMajor = a.rect.stripeCount > 1u;
+            const uint32_t den = columnMajor ? a.tilesY : a.tilesX, quo = tile / den, rem = tile - quo * den;
+            const uint32_t tcol = columnMajor ? quo : rem, trow = columnMajor ? rem : quo;
+            const uint32_t px = a.rect.column_x(tcol) + (within & 7u), py = a.rect.y0 + trow * 8u + (within >> 3);
+            uint32_t tri = __float_as_uint(ha.w);
+            float4 texel[kGbPlanes];
+            if (tri != 0xFFFFFFFFu) {
+                tri &= 0x1FFFFFFFu;                                  // bits 29-31: shading class (wf_extend)
+                Ray ray; ray.o = mk3(o.x, o.y, o.z); ray.d = mk3(d.x, d.y, d.z); ray.tmin = o.w; ray.tmax = 1e10f;
+                Hit h; h.valid = true; h.t = ha.x; h.u = ha.y; h.v = ha.z; h.tri = tri; h.prim = 0; h.inst = s.instances ? a.b.hitInst[slot] : 0u; h.opaque = 1;
+                gbuffer_texels(s, cb, ray, h, texel);
+            } else gbuffer_miss(texel);
+            gbuffer_store(g, planeMask, (size_t)py * a.imageWidth + px, texel);
+        }
+    }
+}
+
 // ------------------------------------------------------------------ host side
 // What is launched, on which grid and with how much LDS is decided in pt_wavefront_plan.h; here the plan meets the kernels.
 // The persistent kernels divide their segments evenly among the waves of the grid (seg = wave, wave + waves, ...), so a grid that is not a
@@ -1445,6 +1485,8 @@ void wavefront_release(WavefrontState& st)
     st.spill = nullptr; st.spillBytes = 0;
     if (st.traceSpill) (void)hipFree(st.traceSpill);
     st.traceSpill = nullptr; st.traceSpillBytes = 0;
+    if (st.gbPool) (void)hipFree(st.gbPool);
+    st.gbPool = nullptr; st.gbPoolBytes = 0;
     for (hipEvent_t e : st.events) (void)hipEventDestroy(e);
     st.events.clear(); st.eventsUsed = 0;
     for (hipEvent_t e : st.forkEvents) (void)hipEventDestroy(e);
@@ -1716,6 +1758,83 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
         if (timedEnds) timing_mark(st, stream, 4, false);
         if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }
     }
+    return hipSuccess;
+}
+
+namespace {
+// Queue pool of a G-buffer call: path queue 0, hit records, the radiance slots wf_raygen zeroes and a scratch counter block (the front end counts
+// rays and paths; HrptStats describes renders, so these counts go nowhere). Same conventions as carve_pool.
+size_t carve_gbuffer_pool(char* base, WfArgs& a, uint64_t capacity, uint32_t segs, bool hasMedium, bool hasInstances)
+{
+    size_t off = 0;
+    auto carve = [&](auto*& stream, size_t bytes, bool present = true) {
+        stream = reinterpret_cast<std::remove_reference_t<decltype(stream)>>(reinterpret_cast<uintptr_t>(base) + (present ? off : 0));
+        if (present) off += (bytes + 255) & ~(size_t)255;
+    };
+    WfBuffers& b = a.b;
+    carve(b.rayO[0], capacity * 16); carve(b.rayD[0], capacity * 16); carve(b.thr[0], capacity * 16);
+    carve(b.med0[0], capacity * 16, hasMedium); carve(b.med1[0], capacity * 16, hasMedium);
+    carve(b.pathCnt[0], (size_t)segs * 4);
+    carve(b.hit, capacity * 16);
+    carve(b.hitInst, capacity * 4, hasInstances); if (!hasInstances) b.hitInst = nullptr;
+    carve(b.radiance, capacity * 16);
+    carve(a.counters, sizeof(DeviceCounters) * kCounterShards);
+    return off;
+}
+}
+
+// hrpt_render_gbuffer, wavefront path: wf_raygen + the render's closest-hit kernel over one sample per pixel of `rect` (plan_gbuffer), then
+// wf_gbuffer. Touches neither st.plan nor the byte / timing accounting of renders; works in the render's queue pool when that is large enough,
+// otherwise in a pool of its own (HrptStats::queuePoolBytes keeps describing renders).
+hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
+                             float4* const* planes, uint32_t planeMask, uint32_t width, TileRect rect, hipStream_t stream, std::string& error)
+{
+    if (rect.x1 <= rect.x0 || rect.y1 <= rect.y0 || rect.columns() == 0) return hipSuccess;
+    hipError_t e;
+    int dev = 0; hipDeviceProp_t prop;
+    if ((e = hipGetDevice(&dev)) != hipSuccess || (e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) { error = "hipGetDeviceProperties"; return e; }
+    const uint32_t cus = (uint32_t)prop.multiProcessorCount;
+    const uint32_t tilesX = rect.columns(), tilesY = (rect.y1 - rect.y0 + 7) / 8;
+    const uint64_t pixelsPadded = (uint64_t)tilesX * tilesY * 64;
+    const uint64_t capacity = ((pixelsPadded + kMaxSegment - 1) / kMaxSegment) * kMaxSegment;
+    if (capacity >= (1ull << 31)) { error = "tile too large for one batch"; return hipErrorInvalidValue; }
+    const GBufferPlan plan = plan_gbuffer(traits, tree_counts(scene), cus, st.knobs, (uint32_t)pixelsPadded);
+    WfArgs a{};
+    const uint32_t segs = (uint32_t)(capacity / 64);
+    const size_t bytes = carve_gbuffer_pool(nullptr, a, capacity, segs, traits.hasMedium, scene.instances != nullptr);
+    char* pool = static_cast<char*>(st.pool);
+    if (bytes > st.poolBytes) {
+        if (bytes > st.gbPoolBytes) {
+            if (st.gbPool) { (void)hipStreamSynchronize(stream); (void)hipFree(st.gbPool); st.gbPool = nullptr; st.gbPoolBytes = 0; }
+            if ((e = hipMalloc(&st.gbPool, bytes)) != hipSuccess) { error = "hipMalloc(G-buffer queue pool, " + std::to_string(bytes >> 20) + " MiB)"; return e; }
+            st.gbPoolBytes = bytes;
+        }
+        pool = static_cast<char*>(st.gbPool);
+    }
+    carve_gbuffer_pool(pool, a, capacity, segs, traits.hasMedium, scene.instances != nullptr);
+    if (plan.spillEntries) {
+        const size_t spillBytes = 2 * plan.spillThreads * plan.spillEntries * 4;      // sized as a render sizes it: the next render keeps the buffer
+        if (spillBytes > st.spillBytes) {
+            if (st.spill) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); (void)hipFree(st.spill); st.spill = nullptr; st.spillBytes = 0; }
+            if ((e = hipMalloc(&st.spill, spillBytes)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
+            st.spillBytes = spillBytes;
+        }
+        a.spill[0] = static_cast<int32_t*>(st.spill); a.spill[1] = a.spill[0] + plan.spillThreads * plan.spillEntries;
+    }
+    a.scene = scene;
+    a.tilesX = tilesX; a.tilesY = tilesY; a.rect = rect; a.imageWidth = width; a.pixelsPadded = (uint32_t)pixelsPadded;
+    a.spp = 1; a.numSamples = (uint32_t)pixelsPadded; a.segSize = plan.batch.segSize; a.numSegments = plan.batch.numSegments;
+    a.maxLights = 1; a.hasMedium = traits.hasMedium ? 1u : 0u; a.hasStochasticAlpha = traits.hasStochasticAlpha ? 1u : 0u; a.allOpaque = traits.hasNonOpaque ? 0u : 1u;
+    a.refillMin = st.knobs.refillMin ? st.knobs.refillMin : kRefillMinDefault; a.streamSegments = st.knobs.drainSegments ? 0u : 1u; a.nodeLoopMin = plan.nodeLoopMin;
+    a.primary = 0u;
+    JitterTable jt{};
+    jt.j[0].x = constants.m_Jitter[0]; jt.j[0].y = constants.m_Jitter[1];      // the caller's jitter, not the Halton point of the index (pass 0 for pixel centres)
+    GBufferPlanes g; for (uint32_t k = 0; k < kGbPlanes; ++k) g.plane[k] = planes[k];
+    const dim3 grid(plan.batch.grid);
+    hipLaunchKernelGGL(wf_raygen, grid, dim3(kBlock), 0, stream, a, constants, jt);
+    launch_extend(plan.vE, cus, dim3(plan.batch.gridExtend), stream, a, 0u);
+    hipLaunchKernelGGL(wf_gbuffer, grid, dim3(kBlock), 0, stream, a, constants, g, planeMask);
+    if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }
     return hipSuccess;
 }
 

@@ -252,6 +252,26 @@ inline BatchPlan plan_batch(const RenderPlan& p, const WavefrontKnobs& k, uint32
     return b;
 }
 
+// hrpt_render_gbuffer (wavefront path): bounce 0 of a one-sample-per-pixel batch through the render's own front end -- wf_raygen and the
+// closest-hit kernel plan_render / plan_batch pick for this scene (a single light slot: the lights are not read) -- followed by wf_gbuffer on
+// the shade grid. Nothing is chosen here that a render does not choose: same variant, same LDS bytes, same segments, same grids.
+struct GBufferPlan {
+    Variant vE; BatchPlan batch;
+    uint32_t nodeLoopMin = 0, pathRecordBytes = 48;
+    uint32_t spillEntries = 0; size_t spillThreads = 0;
+    uint64_t bytesPerSample = 0;       // of the queue pool: path record + hit record (+ instance) + the radiance slot wf_raygen zeroes
+};
+inline GBufferPlan plan_gbuffer(const SceneTraits& traits, const TreeCounts& tree, uint32_t cus, const WavefrontKnobs& k, uint32_t numSamples)
+{
+    const RenderPlan p = plan_render(traits, tree, 1, cus, k);
+    GBufferPlan g;
+    g.vE = p.vE; g.batch = plan_batch(p, k, numSamples);
+    g.nodeLoopMin = p.nodeLoopMin; g.pathRecordBytes = p.pathRecordBytes;
+    g.spillEntries = p.spillEntries; g.spillThreads = p.spillThreads;
+    g.bytesPerSample = p.pathRecordBytes + 16u + (tree.hasInstances ? 4u : 0u) + 16u;
+    return g;
+}
+
 // hrpt_trace_rays over device arrays through the persistent refilling traversal kernel (wf_trace_rays): the closest-hit kernel class of the
 // render path (4-wide, kExtendLdsStack), with these differences: HRPT_WF_BVH_WIDTH and HRPT_WF_PAD_LDS do not apply, and there is no 2-wide
 // kernel to fall back to: wavefront_trace_rays_supported is false when the tree is too deep for it, and the caller asks before it plans.

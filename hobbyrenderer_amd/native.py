@@ -31,6 +31,7 @@ EXPORTS = [
     "hrpt_synchronize", "hrpt_set_stream", "hrpt_get_device_images", "hrpt_read_accumulation", "hrpt_read_output",
     "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
+    "hrpt_render_gbuffer", "hrpt_read_gbuffer", "hrpt_get_gbuffer_device",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
 ]
 
@@ -77,6 +78,9 @@ lib.hrpt_bloom.argtypes = [C.c_void_p, C.POINTER(S.BloomParams)]
 lib.hrpt_bloom_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.BloomParams), C.c_void_p]
 lib.hrpt_bloom_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.BloomParams), C.c_int]
 lib.hrpt_bloom_pack_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.hrpt_render_gbuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+lib.hrpt_read_gbuffer.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+lib.hrpt_get_gbuffer_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
 lib.hrpt_halton.argtypes = [C.c_uint32, C.c_uint32]
 lib.hrpt_halton.restype = C.c_float
 lib.hrpt_precompute_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -251,6 +255,29 @@ class PathTracerContext:
         p["tileX0"], p["tileY0"], p["tileX1"], p["tileY1"] = tile
         p["flags"] = flags
         self._check(lib.hrpt_render(self._h, p.ctypes.data))
+
+    def render_gbuffer(self, constants, planes=S.GB_ALL_PLANES, tile=(0, 0, 0, 0), flags=S.FRAME_DEFAULT, stripes=(1, 0)):
+        """hrpt_render_gbuffer: what the primary rays of one accumulation index saw (path vertex 0), into the planes of the bit mask `planes`
+        (1 << S.GB_ALBEDO ...). constants.m_Jitter is used as given; tile / flags / stripes as in render. Asynchronous."""
+        p = np.zeros((), S.FrameParams)
+        p["stripeCount"], p["stripeIndex"] = stripes
+        p["constants"] = constants
+        p["accumCount"] = 1
+        p["tileX0"], p["tileY0"], p["tileX1"], p["tileY1"] = tile
+        p["flags"] = flags
+        self._check(lib.hrpt_render_gbuffer(self._h, p.ctypes.data, int(planes)))
+
+    def read_gbuffer(self, plane):
+        """One G-buffer plane: float32 [H, W, 4], or uint32 [H, W, 4] for S.GB_IDS (synchronises)."""
+        out = np.empty((self.height, self.width, 4), np.uint32 if plane == S.GB_IDS else np.float32)
+        self._check(lib.hrpt_read_gbuffer(self._h, int(plane), out.ctypes.data, out.nbytes))
+        return out
+
+    def gbuffer_device(self, plane):
+        """Device pointer of one G-buffer plane (None when it was never requested)."""
+        ptr = C.c_void_p()
+        self._check(lib.hrpt_get_gbuffer_device(self._h, int(plane), C.byref(ptr)))
+        return ptr.value
 
     def set_stream(self, hip_stream):
         """hip_stream: integer handle (e.g. torch.cuda.current_stream().cuda_stream; 0 = the default stream), or None to go

@@ -408,6 +408,36 @@ typedef struct HrptRayHit { float t, u, v; uint32_t instance, primitive, hit, rn
 #define HRPT_RAYS_THREAD_PER_RAY  0x200u   /* testing: the one-thread-per-ray kernel instead of the persistent refilling traversal kernel (same results) */
 int  hrpt_trace_rays(HrptContext* ctx, const HrptRay* rays, HrptRayHit* hits, uint64_t count, uint32_t flags);
 
+/* ---- first-hit G-buffer ------------------------------------------------------------------------------------------
+ * What the primary ray of every pixel saw: path vertex 0 of ONE accumulation index, with the contents of the reference's GBufferOut
+ * (src/shaders/BasePass.hlsl:184-192, 485-493) computed by the path tracer's own stages. For pixel (px, py) and params->constants:
+ * the ray and the RNG seed are those of PathTracer.hlsl:61-72 with constants.m_Jitter AS GIVEN (pass 0, 0 for pixel-centre guides;
+ * hrpt_render recomputes the jitter from the index, this call does not) and constants.m_AccumulationIndex; the hit is TraceRayStandard's,
+ * MASK / stochastic BLEND candidates drawing from that RNG state -- for the constants hrpt_render uses for an index this is the surface it
+ * shades at bounce 0. m_MaxBounces, the lights and the sun are not read. accumCount must be 1.
+ * Six planes of width x height texels, 16 bytes each, owned by the library; a plane is allocated (zeroed) by the first call that requests
+ * it and re-allocated (zeroed) by hrpt_resize. Normals are unit vectors in binary32 (no octahedral packing, no render-target formats).
+ *   plane                 type     hit                                                                          miss
+ *   HRPT_GB_ALBEDO        float4   pbr.baseColor, pbr.alpha                                                     0, 0, 0, 0
+ *   HRPT_GB_NORMAL        float4   shading normal N, negated when dot(N, -d) < 0 (PathTracer.hlsl:111-117); w = roughness (>= 0.04)   0, 0, 0, 0
+ *   HRPT_GB_GEO_NORMAL    float4   Ng = normalize(interpolated vertex normal in world space), not flipped; w = metallic     0, 0, 0, 0
+ *   HRPT_GB_EMISSIVE      float4   pbr.emissive, 1                                                              0, 0, 0, 0
+ *   HRPT_GB_DEPTH         float4   t, viewDepth = (float4(o + d t, 1) * m_MatWorldToClipNoOffset).w, u, v (weights of v1, v2)   1e10, 1e10, 0, 0
+ *   HRPT_GB_IDS           uint4    instance, primitive, material index, flags (HRPT_GB_FLAG_*)                  0xFFFFFFFF x 3, 0
+ * hrpt_render_gbuffer honours the tile rectangle, the stripes and HRPT_FRAME_MEGAKERNEL / _WAVEFRONT of params exactly as hrpt_render does,
+ * writes only the planes in planeMask and only the pixels of the tile, is asynchronous on the context stream (ordered with renders) and
+ * leaves Accumulation, Output, the exposure buffer and every HrptStats field as they were. planeMask == 0 or a bit >= HRPT_GB_PLANES:
+ * HRPT_ERR_INVALID_ARGUMENT; no scene: HRPT_ERR_NO_SCENE. Motion vectors are not provided. */
+enum { HRPT_GB_ALBEDO = 0, HRPT_GB_NORMAL = 1, HRPT_GB_GEO_NORMAL = 2, HRPT_GB_EMISSIVE = 3, HRPT_GB_DEPTH = 4, HRPT_GB_IDS = 5, HRPT_GB_PLANES = 6 };
+#define HRPT_GB_ALL_PLANES 0x3Fu
+#define HRPT_GB_FLAG_HIT 1u          /* the primary ray committed a hit */
+#define HRPT_GB_FLAG_FRONT_FACE 2u   /* dot(Ng, d) < 0 (isFrontFace, PathTracer.hlsl:113) */
+int  hrpt_render_gbuffer(HrptContext* ctx, const HrptFrameParams* params, uint32_t planeMask);
+/* Host read-back of one plane (synchronises); bytes must be width*height*16. A plane that was never requested: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_read_gbuffer(HrptContext* ctx, uint32_t plane, void* dst, size_t bytes);
+/* Device pointer of one plane (valid until hrpt_resize / hrpt_destroy); NULL when the plane was never requested. */
+int  hrpt_get_gbuffer_device(HrptContext* ctx, uint32_t plane, void** devicePtr);
+
 /* Host read-back (synchronises). bytes must be width*height*16. */
 int  hrpt_read_accumulation(HrptContext* ctx, float* rgba, size_t bytes);
 int  hrpt_read_output(HrptContext* ctx, float* rgba, size_t bytes);

@@ -1,0 +1,202 @@
+"""NumPy restatement of the first-hit G-buffer (hrpt_render_gbuffer) -- TEST INFRASTRUCTURE.
+
+Shares no code with hobbyrenderer_amd/csrc/pt_device.h: the primary rays are built here in binary32 step by step as init_path does
+(PathTracer.hlsl:61-72), the hits come from the oracle's TraceRayStandard (Oracle.trace_standard, with the seeded RNG), vertices through
+or_unpack_vertex and texels through Oracle.sample_texture; interpolation, the normal transform by the adjugate rows, TransformNormalWithTBN,
+the flips, viewDepth and the plane packing are NumPy float32 with one rounding per operation, in the order DESIGN.md section 2 fixes
+(sums left to right, dot = (x*x + y*y) + z*z, normalize = v * (1 / sqrt(dot)), no contraction)."""
+import ctypes as C
+
+import numpy as np
+
+from hobbyrenderer_amd import structs as S
+from oracle import binding
+
+f32 = np.float32
+MISS_T = f32(1e10)          # the primary ray's tmax
+
+
+def cube_case(luts, width=61, height=37, index=3, jitter=(0.25, -0.125)):
+    """The cube scene of the G-buffer tests: three faces in view from an off-axis camera, a size that is no multiple of the 8 x 8 tile,
+    a jitter that is no Halton point. Returns (scene, constants)."""
+    import math
+    from hobbyrenderer_amd import scenes
+    sc = scenes.cube_scene(luts)
+    view, pos = scenes.planar_view(width, height, position=(2.0, 1.5, -3.0), yaw=math.atan2(-2.0, 3.0), pitch=math.asin(1.5 / math.sqrt(15.25)))
+    cb = scenes.fill_constants(view, pos, sc, index, 1)
+    cb["m_Jitter"] = jitter
+    return sc, cb
+
+
+def _dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1],
+                     a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
+
+
+def _normalize(a):
+    inv = f32(1.0) / np.sqrt(_dot(a, a))
+    return a * inv[..., None]
+
+
+def _saturate(x):
+    return np.where(x > f32(0.0), np.where(x < f32(1.0), x, f32(1.0)), f32(0.0)).astype(f32)
+
+
+def _max(a, b):          # hrt_max: (a >= b || b != b) ? a : b
+    return np.where((a >= b) | (b != b), a, b).astype(f32)
+
+
+def primary_rays(cb, width, height):
+    """(origin float32[3], direction float32[H, W, 3], seed uint32[H, W]) of every pixel for the constants `cb` (jitter as given)."""
+    view = cb["m_View"]
+    M = np.asarray(view["m_MatClipToWorldNoOffset"], f32)          # row-major, row-vector convention: M[r, c]
+    inv_w, inv_h = f32(view["m_ViewportSizeInv"][0]), f32(view["m_ViewportSizeInv"][1])
+    jx, jy = f32(cb["m_Jitter"][0]), f32(cb["m_Jitter"][1])
+    px = np.broadcast_to(np.arange(width, dtype=np.uint32)[None, :], (height, width))
+    py = np.broadcast_to(np.arange(height, dtype=np.uint32)[:, None], (height, width))
+    u = ((px.astype(f32) + f32(0.5)) + jx) * inv_w
+    v = ((py.astype(f32) + f32(0.5)) + jy) * inv_h
+    cx = u * f32(2.0) + f32(-1.0)
+    cy = v * f32(-2.0) + f32(1.0)
+    e = [((cx * M[0, k] + cy * M[1, k]) + f32(0.9) * M[2, k]) + f32(1.0) * M[3, k] for k in range(4)]
+    end = np.stack([e[0] / e[3], e[1] / e[3], e[2] / e[3]], -1)
+    o = np.asarray(cb["m_CameraPos"], f32)[:3].copy()
+    d = _normalize(end - o)
+    lib = binding.lib()
+    index = int(cb["m_AccumulationIndex"])
+    seed = np.array([[lib.or_init_rng(x, y, index) for x in range(width)] for y in range(height)], np.uint32)
+    return o, d.astype(f32), seed
+
+
+def unpacked_vertices(scene):
+    """or_unpack_vertex of every vertex: float32 [n, 12] = pos3 normal3 uv2 tangent4."""
+    out = np.zeros((len(scene.vertices), 12), f32)
+    lib, pv, po = binding.lib(), scene.vertices.ctypes.data, out.ctypes.data
+    for i in range(len(out)):
+        lib.or_unpack_vertex(pv + 24 * i, po + 48 * i)
+    return out
+
+
+def _transform_normal(n, world):
+    """TransformNormal (Common.hlsli:33-47): normalize(n * adjugate(world3x3)); world float32 [m, 4, 4]."""
+    r0, r1, r2 = world[:, 0, :3], world[:, 1, :3], world[:, 2, :3]
+    a0, a1, a2 = _cross(r1, r2), _cross(r2, r0), _cross(r0, r1)
+    o = np.stack([(n[:, 0] * a0[:, k] + n[:, 1] * a1[:, k]) + n[:, 2] * a2[:, k] for k in range(3)], -1)
+    return _normalize(o)
+
+
+def _normal_with_tbn(nx, ny, normal, tangent, sign):
+    """TransformNormalWithTBN, Common.hlsli:183-200."""
+    x = f32(2.0) * nx - f32(1.0)
+    y = f32(2.0) * ny - f32(1.0)
+    z = np.sqrt(_saturate(f32(1.0) - (x * x + y * y)))
+    n_w = _normalize(normal)
+    t_w = _normalize(tangent)
+    t_w = _normalize(t_w - n_w * _dot(t_w, n_w)[:, None])
+    b_w = _normalize(_cross(n_w, t_w) * sign[:, None])
+    o = np.stack([(x * t_w[:, k] + y * b_w[:, k]) + z * n_w[:, k] for k in range(3)], -1)
+    return _normalize(o)
+
+
+def trace(scene, oracle, cb, width, height):
+    """The primary rays and what TraceRayStandard commits for each: dict of o, d, seed, hit (bool), t, u, v, inst, prim, rng (state after)."""
+    o, d, seed = primary_rays(cb, width, height)
+    r = dict(o=o, d=d, seed=seed, hit=np.zeros((height, width), bool), t=np.zeros((height, width), f32), u=np.zeros((height, width), f32),
+             v=np.zeros((height, width), f32), inst=np.zeros((height, width), np.uint32), prim=np.zeros((height, width), np.uint32),
+             rng=np.zeros((height, width), np.uint32))
+    for y in range(height):
+        for x in range(width):
+            ok, inst, prim, u, v, t, rng = oracle.trace_standard(o, d[y, x], 0.0, float(MISS_T), int(seed[y, x]))
+            r["hit"][y, x] = ok; r["rng"][y, x] = rng
+            if ok:
+                r["t"][y, x], r["u"][y, x], r["v"][y, x], r["inst"][y, x], r["prim"][y, x] = t, u, v, inst, prim
+    return r
+
+
+def gbuffer(scene, oracle, cb, width, height, verts=None, traced=None):
+    """The six planes for the constants `cb`: list indexed by S.GB_*, float32 [H, W, 4] (uint32 for S.GB_IDS). `verts`: unpacked_vertices(scene)
+    when the caller has them; `traced`: trace(...) likewise."""
+    verts = unpacked_vertices(scene) if verts is None else verts
+    tr = trace(scene, oracle, cb, width, height) if traced is None else traced
+    planes = [np.zeros((height, width, 4), f32) for _ in range(S.GB_PLANES)]
+    planes[S.GB_DEPTH][..., 0] = MISS_T; planes[S.GB_DEPTH][..., 1] = MISS_T
+    ids = np.zeros((height, width, 4), np.uint32); ids[..., :3] = 0xFFFFFFFF
+    planes[S.GB_IDS] = ids
+    ys, xs = np.nonzero(tr["hit"])
+    if len(ys) == 0:
+        return planes
+    d = tr["d"][ys, xs]; t = tr["t"][ys, xs]; u = tr["u"][ys, xs]; v = tr["v"][ys, xs]
+    inst = tr["inst"][ys, xs]; prim = tr["prim"][ys, xs]
+    rec = scene.instances[inst]
+    world = np.asarray(rec["m_World"], f32)
+    mesh = scene.mesh_data[rec["m_MeshDataIndex"]]
+    mat_index = rec["m_MaterialIndex"].astype(np.uint32)
+    base = mesh["m_IndexOffsets"][:, 0].astype(np.int64) + 3 * prim.astype(np.int64)          # LOD 0 (PathTracer.hlsl:103)
+    tv = [verts[scene.indices[base + k]] for k in range(3)]
+    # GetFullHitAttributes, RaytracingCommon.hlsli:52-77
+    bx = (f32(1.0) - u) - v; by = u; bz = v
+    world_pos = tr["o"] + d * t[:, None]
+    ln = (tv[0][:, 3:6] * bx[:, None] + tv[1][:, 3:6] * by[:, None]) + tv[2][:, 3:6] * bz[:, None]
+    world_normal = _transform_normal(ln, world)
+    lt = (tv[0][:, 8:11] * bx[:, None] + tv[1][:, 8:11] * by[:, None]) + tv[2][:, 8:11] * bz[:, None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        world_tangent = _transform_normal(lt, world)
+    tangent_sign = (tv[0][:, 11] * bx + tv[1][:, 11] * by) + tv[2][:, 11] * bz
+    uv = np.stack([(tv[0][:, 6 + k] * bx + tv[1][:, 6 + k] * by) + tv[2][:, 6 + k] * bz for k in range(2)], -1).astype(f32)
+    # GetPBRAttributes, RaytracingCommon.hlsli:252-296, material by material
+    n = len(ys)
+    base_color = np.zeros((n, 3), f32); alpha = np.zeros(n, f32); rough = np.zeros(n, f32); metal = np.zeros(n, f32)
+    emissive = np.zeros((n, 3), f32); normal = _normalize(world_normal)
+    for m in np.unique(mat_index):
+        sel = np.nonzero(mat_index == m)[0]
+        mc = scene.materials[m]
+        flags = int(mc["m_TextureFlags"])
+        bc = np.broadcast_to(np.asarray(mc["m_BaseColor"], f32), (len(sel), 4)).copy()
+        if flags & S.TEXFLAG_ALBEDO:
+            s = oracle.sample_texture(int(mc["m_AlbedoTextureIndex"]), int(mc["m_AlbedoSamplerIndex"]), uv[sel])
+            bc = bc * s
+        base_color[sel] = bc[:, :3]; alpha[sel] = bc[:, 3]
+        r = np.full(len(sel), mc["m_RoughnessMetallic"][0], f32); me = np.full(len(sel), mc["m_RoughnessMetallic"][1], f32)
+        if flags & S.TEXFLAG_ROUGHNESS_METALLIC:
+            s = oracle.sample_texture(int(mc["m_RoughnessMetallicTextureIndex"]), int(mc["m_RoughnessSamplerIndex"]), uv[sel])
+            r, me = s[:, 1], s[:, 2]
+        rough[sel] = _max(r, f32(0.04)); metal[sel] = me
+        em = np.broadcast_to(np.asarray(mc["m_EmissiveFactor"], f32)[:3], (len(sel), 3)).copy()
+        if flags & S.TEXFLAG_EMISSIVE:
+            s = oracle.sample_texture(int(mc["m_EmissiveTextureIndex"]), int(mc["m_EmissiveSamplerIndex"]), uv[sel])
+            em = em * s[:, :3]
+        emissive[sel] = em
+        if flags & S.TEXFLAG_NORMAL:
+            s = oracle.sample_texture(int(mc["m_NormalTextureIndex"]), int(mc["m_NormalSamplerIndex"]), uv[sel])
+            normal[sel] = _normal_with_tbn(s[:, 0], s[:, 1], world_normal[sel], world_tangent[sel], tangent_sign[sel])
+    # PathTracer.hlsl:110-117
+    ng = _normalize(world_normal)
+    front = _dot(ng, d) < f32(0.0)
+    flip = _dot(normal, -d) < f32(0.0)
+    shading = np.where(flip[:, None], -normal, normal)
+    # linear view-space depth (CommonLighting.hlsli:249-250): w of float4(worldPos, 1) * m_MatWorldToClipNoOffset
+    W2C = np.asarray(cb["m_View"]["m_MatWorldToClipNoOffset"], f32)
+    view_depth = ((world_pos[:, 0] * W2C[0, 3] + world_pos[:, 1] * W2C[1, 3]) + world_pos[:, 2] * W2C[2, 3]) + f32(1.0) * W2C[3, 3]
+    planes[S.GB_ALBEDO][ys, xs] = np.concatenate([base_color, alpha[:, None]], 1)
+    planes[S.GB_NORMAL][ys, xs] = np.concatenate([shading, rough[:, None]], 1)
+    planes[S.GB_GEO_NORMAL][ys, xs] = np.concatenate([ng, metal[:, None]], 1)
+    planes[S.GB_EMISSIVE][ys, xs] = np.concatenate([emissive, np.ones((n, 1), f32)], 1)
+    planes[S.GB_DEPTH][ys, xs] = np.stack([t, view_depth, u, v], 1)
+    ids[ys, xs] = np.stack([inst, prim, mat_index, (S.GB_FLAG_HIT | np.where(front, S.GB_FLAG_FRONT_FACE, 0)).astype(np.uint32)], 1)
+    for p in planes:
+        assert p.dtype in (np.float32, np.uint32)
+    return planes
+
+
+def world_triangle(scene, verts, inst, prim):
+    """float64 [3, 3] world-space vertex positions of primitive `prim` of instance `inst` (p * m_World, row-vector convention)."""
+    rec = scene.instances[inst]
+    base = int(scene.mesh_data[rec["m_MeshDataIndex"]]["m_IndexOffsets"][0]) + 3 * int(prim)
+    p = verts[scene.indices[base:base + 3], 0:3].astype(np.float64)
+    w = np.asarray(rec["m_World"], np.float64)
+    return p @ w[:3, :3] + w[3, :3]
