@@ -21,6 +21,7 @@
 #include "bvh_build_gpu.h"
 #include "pt_device.h"
 #include "pt_kernels.h"
+#include "pt_motion.h"
 #include "pt_wavefront.h"
 
 using namespace hrt;
@@ -51,6 +52,11 @@ struct HrptContext {
     uint32_t* dBloomDown = nullptr; uint32_t* dBloomUp = nullptr; size_t bloomWords = 0;   // bloom pyramids (packed R11G11B10_FLOAT), sized by the last bloom call
     uint32_t bloomTailTexels = 0;            // HRPT_BLOOM_FUSED_TAIL: levels of at most this many texels run in one workgroup's LDS (0 = one kernel per pass, the measured-faster default)
     float4* dGBuffer[HRPT_GB_PLANES] = {};   // first-hit G-buffer planes (hrpt_render_gbuffer): allocated by the first call that requests one, re-allocated by hrpt_resize
+    // first-hit motion vectors (hrpt_render_motion_vectors): the plane, and the device tables the first motion call builds from the kept copies
+    float4* dMotion = nullptr;
+    MotionInst* dMotionInst = nullptr; size_t motionInstCapacity = 0;          // one record per instance: m_PrevWorld + the mesh's LOD-0 index offset
+    float* dMotionPositions = nullptr; uint32_t* dMotionIndices = nullptr;     // object-space positions (12 B per vertex) and the index buffer
+    bool motionInstStale = true, motionGeometryStale = true;                   // set by uploads / instance updates / rebuilds, cleared by the next motion call
     DeviceCounters* dCounters = nullptr;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
@@ -112,9 +118,19 @@ static void free_acceleration(HrptContext* c, bool keepGpuBuilder)
     }
 }
 
+static void free_motion_tables(HrptContext* c)
+{
+    if (c->dMotionInst) (void)hipFree(c->dMotionInst);
+    if (c->dMotionPositions) (void)hipFree(c->dMotionPositions);
+    if (c->dMotionIndices) (void)hipFree(c->dMotionIndices);
+    c->dMotionInst = nullptr; c->motionInstCapacity = 0; c->dMotionPositions = nullptr; c->dMotionIndices = nullptr;
+    c->motionInstStale = c->motionGeometryStale = true;
+}
+
 static void free_scene(HrptContext* c)
 {
     free_acceleration(c, false);
+    free_motion_tables(c);
     for (void* p : c->allocations) (void)hipFree(p);
     c->allocations.clear();
     if (c->nodesQ) { (void)hipFree(c->nodesQ); c->nodesQ = nullptr; c->nodesQCapacity = 0; }
@@ -190,6 +206,7 @@ void hrpt_destroy(HrptContext* c)
     if (c->dOutput) (void)hipFree(c->dOutput);
     if (c->dDisplay) (void)hipFree(c->dDisplay);
     for (float4* plane : c->dGBuffer) if (plane) (void)hipFree(plane);
+    if (c->dMotion) (void)hipFree(c->dMotion);
     if (c->dHistogram) (void)hipFree(c->dHistogram);
     if (c->dExposure) (void)hipFree(c->dExposure);
     if (c->dBloomDown) (void)hipFree(c->dBloomDown);
@@ -640,6 +657,7 @@ static int update_materials_impl(HrptContext* c, const HrptMaterialConstants* ma
         int r = build_acceleration(c, s, kept_triangle_count(c), v, true);     // from scratch: the GPU builder's resident instance table holds the opacity flags
         if (r != HRPT_OK) { c->haveScene = false; return r; }
         c->view = v;
+        c->motionInstStale = true;
     }
     refresh_traits(c);
     return HRPT_OK;
@@ -660,6 +678,7 @@ static int update_instances_impl(HrptContext* c, const HrptPerInstanceData* inst
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));        // frames in flight still traverse the old tree
     std::memcpy(c->keptInstances.data() + firstInstance, instances, (size_t)count * sizeof(HrptPerInstanceData));
+    c->motionInstStale = true;                          // m_PrevWorld travels in these records (hrpt_render_motion_vectors)
     HrptSceneDesc s = kept_scene_desc(c);
     const uint64_t sceneTris = kept_triangle_count(c);
     SceneView v = c->view;
@@ -689,6 +708,11 @@ int hrpt_resize(HrptContext* c, uint32_t width, uint32_t height)
         (void)hipFree(plane); plane = nullptr;
         HIP_TRY(c, hipMalloc((void**)&plane, bytes));
         HIP_TRY(c, hipMemsetAsync(plane, 0, bytes, c->stream));
+    }
+    if (c->dMotion) {                           // ... and so does the motion plane
+        (void)hipFree(c->dMotion); c->dMotion = nullptr;
+        HIP_TRY(c, hipMalloc((void**)&c->dMotion, bytes));
+        HIP_TRY(c, hipMemsetAsync(c->dMotion, 0, bytes, c->stream));
     }
     c->width = width; c->height = height;
     return HRPT_OK;
@@ -828,46 +852,120 @@ static int read_image(HrptContext* c, const float4* src, float* dst, size_t byte
 int hrpt_read_accumulation(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->dAccum : nullptr, rgba, bytes, "hrpt_read_accumulation"); }
 int hrpt_read_output(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->dOutput : nullptr, rgba, bytes, "hrpt_read_output"); }
 
+// The device tables of hrpt_render_motion_vectors, (re)built from the kept copies where a flag says they are stale: the instance records after
+// every upload / instance update / rebuild, positions and indices after an upload only. A context that never asks for motion never gets here.
+static int refresh_motion_tables(HrptContext* c)
+{
+    if (!c->motionInstStale && !c->motionGeometryStale) return HRPT_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // motion calls in flight still read the old tables
+    std::vector<float> positions;
+    if (c->motionGeometryStale) {
+        if (c->dMotionPositions) { (void)hipFree(c->dMotionPositions); c->dMotionPositions = nullptr; }
+        if (c->dMotionIndices) { (void)hipFree(c->dMotionIndices); c->dMotionIndices = nullptr; }
+        positions.resize(c->keptVertices.size() * 3);
+        for (size_t i = 0; i < c->keptVertices.size(); ++i) std::memcpy(&positions[3 * i], c->keptVertices[i].m_Pos, 12);
+        const size_t pb = positions.size() * sizeof(float), ib = c->keptIndices.size() * sizeof(uint32_t);
+        HIP_TRY(c, hipMalloc((void**)&c->dMotionPositions, pb ? pb : 16));
+        HIP_TRY(c, hipMalloc((void**)&c->dMotionIndices, ib ? ib : 16));
+        if (pb) HIP_TRY(c, hipMemcpyAsync(c->dMotionPositions, positions.data(), pb, hipMemcpyHostToDevice, c->stream));
+        if (ib) HIP_TRY(c, hipMemcpyAsync(c->dMotionIndices, c->keptIndices.data(), ib, hipMemcpyHostToDevice, c->stream));
+    }
+    std::vector<MotionInst> records(c->keptInstances.size());
+    for (size_t i = 0; i < records.size(); ++i) {
+        const HrptPerInstanceData& in = c->keptInstances[i];
+        MotionInst& r = records[i];
+        for (int row = 0; row < 4; ++row) for (int k = 0; k < 3; ++k) r.prevWorld[row * 3 + k] = in.m_PrevWorld[row * 4 + k];
+        r.firstIndex = c->keptMeshData[in.m_MeshDataIndex].m_IndexOffsets[0];         // LOD 0 (PathTracer.hlsl:102-103)
+        r.pad[0] = r.pad[1] = r.pad[2] = 0;
+    }
+    if (records.size() > c->motionInstCapacity || !c->dMotionInst) {
+        if (c->dMotionInst) { (void)hipFree(c->dMotionInst); c->dMotionInst = nullptr; c->motionInstCapacity = 0; }
+        HIP_TRY(c, hipMalloc((void**)&c->dMotionInst, records.empty() ? 64 : records.size() * sizeof(MotionInst)));
+        c->motionInstCapacity = records.size();
+    }
+    if (!records.empty()) HIP_TRY(c, hipMemcpyAsync(c->dMotionInst, records.data(), records.size() * sizeof(MotionInst), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // the staging vectors die at scope exit
+    c->motionInstStale = c->motionGeometryStale = false;
+    return HRPT_OK;
+}
+
 // First-hit G-buffer: the checks of render_impl that apply (no bounces, no lights), then one of the two kernel paths. No events, no counters, no
-// fallback count: HrptStats keeps describing renders.
-static int render_gbuffer_impl(HrptContext* c, const HrptFrameParams* p, uint32_t planeMask)
+// fallback count: HrptStats keeps describing renders. hrpt_render_motion_vectors (`motion`) is the same pass with the motion plane written too
+// and a planeMask that may be 0.
+static int render_gbuffer_impl(HrptContext* c, const HrptFrameParams* p, uint32_t planeMask, bool motion, const HrptPlanarViewConstants* prevView)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: null params");
-    if (planeMask == 0 || (planeMask >> HRPT_GB_PLANES) != 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: planeMask must name at least one of the HRPT_GB_PLANES planes and no other bit");
-    if (!c->haveScene) return fail(c, HRPT_ERR_NO_SCENE, "hrpt_render_gbuffer: no scene uploaded");
-    if (!c->dAccum) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: hrpt_resize not called");
-    if (p->accumCount != 1) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: accumCount must be 1 (the planes describe path vertex 0 of ONE accumulation index)");
+    const std::string what = motion ? "hrpt_render_motion_vectors" : "hrpt_render_gbuffer";
+    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": null params");
+    if (motion && !prevView) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": null prevView (pass the current view for a camera that did not move)");
+    if ((planeMask == 0 && !motion) || (planeMask >> HRPT_GB_PLANES) != 0)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + (motion ? ": planeMask names G-buffer planes (bits 0..5) only" : ": planeMask must name at least one of the HRPT_GB_PLANES planes and no other bit"));
+    if (!c->haveScene) return fail(c, HRPT_ERR_NO_SCENE, what + ": no scene uploaded");
+    if (!c->dAccum) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": hrpt_resize not called");
+    if (p->accumCount != 1) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": accumCount must be 1 (the planes describe path vertex 0 of ONE accumulation index)");
     uint32_t vw = (uint32_t)p->constants.m_View.m_ViewportSize[0], vh = (uint32_t)p->constants.m_View.m_ViewportSize[1];
-    if (vw != c->width || vh != c->height) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: m_ViewportSize does not match hrpt_resize");
+    if (vw != c->width || vh != c->height) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": m_ViewportSize does not match hrpt_resize");
     TileRect rect; rect.x0 = p->tileX0; rect.y0 = p->tileY0; rect.x1 = p->tileX1; rect.y1 = p->tileY1;
     rect.stripeCount = p->stripeCount ? p->stripeCount : 1u; rect.stripeIndex = p->stripeIndex;
-    if (rect.stripeIndex >= rect.stripeCount) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: stripeIndex must be below stripeCount");
+    if (rect.stripeIndex >= rect.stripeCount) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": stripeIndex must be below stripeCount");
     if (rect.x0 == 0 && rect.y0 == 0 && rect.x1 == 0 && rect.y1 == 0) { rect.x1 = c->width; rect.y1 = c->height; }
     if (rect.x1 > c->width || rect.y1 > c->height || rect.x0 > rect.x1 || rect.y0 > rect.y1)
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: tile rectangle outside the image");
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": tile rectangle outside the image");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = (p->flags & HRPT_FRAME_MEGAKERNEL) == 0;
     if (!wavefront && c->view.instances && c->traits.twoLevelStackNeed > 64u)
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render_gbuffer: this two-level structure is deeper than the validation kernel's 64-entry stack");
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": this two-level structure is deeper than the validation kernel's 64-entry stack");
     const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
     for (uint32_t k = 0; k < HRPT_GB_PLANES; ++k) {
         if (!(planeMask & (1u << k)) || c->dGBuffer[k]) continue;
         HIP_TRY(c, hipMalloc((void**)&c->dGBuffer[k], bytes));
         HIP_TRY(c, hipMemsetAsync(c->dGBuffer[k], 0, bytes, c->stream));
     }
+    MotionArgs m{};
+    if (motion) {
+        if (!c->dMotion) {
+            HIP_TRY(c, hipMalloc((void**)&c->dMotion, bytes));
+            HIP_TRY(c, hipMemsetAsync(c->dMotion, 0, bytes, c->stream));
+        }
+        int r = refresh_motion_tables(c);
+        if (r != HRPT_OK) return r;
+        m.inst = c->dMotionInst; m.positions = c->dMotionPositions; m.indices = c->dMotionIndices; m.plane = c->dMotion;
+        std::memcpy(m.prevWorldToClip, prevView->m_MatWorldToClip, sizeof m.prevWorldToClip);
+        m.prevScale[0] = prevView->m_ClipToWindowScale[0]; m.prevScale[1] = prevView->m_ClipToWindowScale[1];
+        m.prevBias[0] = prevView->m_ClipToWindowBias[0]; m.prevBias[1] = prevView->m_ClipToWindowBias[1];
+    }
     if (wavefront) {
         std::string werr;
-        hipError_t e = wavefront_gbuffer(c->wf, c->view, c->traits, p->constants, c->dGBuffer, planeMask, c->width, rect, c->stream, werr);
+        hipError_t e = wavefront_gbuffer(c->wf, c->view, c->traits, p->constants, c->dGBuffer, planeMask, c->width, rect, c->stream, werr, motion ? &m : nullptr);
         if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? HRPT_ERR_OUT_OF_MEMORY : HRPT_ERR_HIP, "wavefront_gbuffer: " + werr + ": " + hipGetErrorString(e));
-    } else HIP_TRY(c, launch_gbuffer_megakernel(c->view, p->constants, c->dGBuffer, planeMask, c->width, rect, c->stream));
+    } else if (motion) HIP_TRY(c, launch_motion_megakernel(c->view, p->constants, c->dGBuffer, planeMask, m, c->width, rect, c->stream));
+    else HIP_TRY(c, launch_gbuffer_megakernel(c->view, p->constants, c->dGBuffer, planeMask, c->width, rect, c->stream));
     return HRPT_OK;
 }
 int hrpt_render_gbuffer(HrptContext* c, const HrptFrameParams* p, uint32_t planeMask)
 {
-    try { return render_gbuffer_impl(c, p, planeMask); }
+    try { return render_gbuffer_impl(c, p, planeMask, false, nullptr); }
     catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_render_gbuffer: host allocation failed"); }
     catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_render_gbuffer: ") + e.what()); }
+}
+int hrpt_render_motion_vectors(HrptContext* c, const HrptFrameParams* p, const HrptPlanarViewConstants* prevView, uint32_t planeMask)
+{
+    try { return render_gbuffer_impl(c, p, planeMask, true, prevView); }
+    catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_render_motion_vectors: host allocation failed"); }
+    catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_render_motion_vectors: ") + e.what()); }
+}
+int hrpt_read_motion_vectors(HrptContext* c, float* dst, size_t bytes)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->dMotion) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_motion_vectors: the motion plane was never requested from hrpt_render_motion_vectors");
+    return read_image(c, c->dMotion, dst, bytes, "hrpt_read_motion_vectors");
+}
+int hrpt_get_motion_vectors_device(HrptContext* c, void** devicePtr)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_motion_vectors_device: null out");
+    *devicePtr = c->dMotion;
+    return HRPT_OK;
 }
 int hrpt_read_gbuffer(HrptContext* c, uint32_t plane, void* dst, size_t bytes)
 {

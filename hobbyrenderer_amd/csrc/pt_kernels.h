@@ -9,6 +9,7 @@
 namespace hrt {
 
 struct SceneView;   // pt_device.h
+struct MotionArgs;  // pt_motion.h
 struct GpuNode4; struct GpuNodeQ;
 
 constexpr int kCounterShards = 32;   // DeviceCounters[kCounterShards] per context; a block adds to shard blockIdx % kCounterShards
@@ -40,6 +41,10 @@ hipError_t launch_megakernel(const SceneView& scene, const HrptPathTracerConstan
 // planeMask are written inside `rect`; constants.m_Jitter / m_AccumulationIndex are used as given.
 hipError_t launch_gbuffer_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* const* planes, uint32_t planeMask,
                                      uint32_t imageWidth, TileRect rect, hipStream_t stream);
+
+// First-hit motion vectors through the validation path (pt_motion.h): launch_gbuffer_megakernel's pass plus motion.plane; planeMask may be 0.
+hipError_t launch_motion_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* const* planes, uint32_t planeMask,
+                                    const MotionArgs& motion, uint32_t imageWidth, TileRect rect, hipStream_t stream);
 
 // HDR post chain over `hdr` (W*H float4): histogram[256] + exposure[1] are context-owned device buffers.
 hipError_t launch_post_chain(const float4* hdr, float4* display, uint32_t pixelCount, const HrptPostParams& params, uint32_t* histogram,

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "pt_gbuffer.h"
+#include "pt_motion.h"
 #include "pt_kernels.h"
 #include "pt_path.h"
 
@@ -125,6 +126,42 @@ hipError_t launch_gbuffer_megakernel(const SceneView& scene, const HrptPathTrace
     dim3 grid(rect.columns(), (rect.y1 - rect.y0 + 7) / 8, 1);
     if (scene.instances) hipLaunchKernelGGL(pt_gbuffer_kernel<true>, grid, dim3(64, 1, 1), 0, stream, scene, constants, g, planeMask, imageWidth, rect);
     else hipLaunchKernelGGL(pt_gbuffer_kernel<false>, grid, dim3(64, 1, 1), 0, stream, scene, constants, g, planeMask, imageWidth, rect);
+    return hipGetLastError();
+}
+
+// First-hit motion vectors, validation path (hrpt_render_motion_vectors with HRPT_FRAME_MEGAKERNEL): pt_gbuffer_kernel plus the motion texel of
+// pt_motion.h; the G-buffer texels are evaluated and stored only when the call names G-buffer planes (planeMask != 0).
+template <bool TL>
+__global__ __launch_bounds__(64) void pt_motion_kernel(SceneView s, HrptPathTracerConstants cb, GBufferPlanes planes, uint32_t planeMask,
+                                                       MotionArgs m, uint32_t imageWidth, TileRect rect)
+{
+    const uint32_t lx = threadIdx.x & 7u, ly = threadIdx.x >> 3;
+    const uint32_t px = rect.column_x(blockIdx.x) + lx, py = rect.y0 + blockIdx.y * 8u + ly;
+    if (!(px < rect.x1 && py < rect.y1)) return;
+    typename std::conditional<TL, GlobalBvhTl, GlobalBvh>::type bvh;
+    if constexpr (TL) { bvh.nodes = s.nodes4; bvh.tris = s.tris; bvh.instances = s.instances; } else { bvh.nodes = s.nodes; bvh.tris = s.tris; }
+    PrivateStack stack;
+    PathState ps; init_path(ps, cb, px, py);
+    float4 texel[kGbPlanes];
+    float4 motion = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const size_t idx = (size_t)py * imageWidth + px;
+    Hit hit;
+    if (trace_standard(s, bvh, ps.ray, ps.rng, stack, hit)) {
+        const MotionTri mt = motion_gather(s, m, hit);
+        if (planeMask != 0u) gbuffer_texels(s, cb, ps.ray, hit, texel);
+        motion = motion_texel(cb.m_View, m, mt, hit.u, hit.v);
+    } else if (planeMask != 0u) gbuffer_miss(texel);
+    if (planeMask != 0u) gbuffer_store(planes, planeMask, idx, texel);
+    m.plane[idx] = motion;
+}
+hipError_t launch_motion_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* const* planes, uint32_t planeMask,
+                                    const MotionArgs& motion, uint32_t imageWidth, TileRect rect, hipStream_t stream)
+{
+    if (rect.x1 <= rect.x0 || rect.y1 <= rect.y0 || rect.columns() == 0) return hipSuccess;
+    GBufferPlanes g; for (uint32_t k = 0; k < kGbPlanes; ++k) g.plane[k] = planes[k];
+    dim3 grid(rect.columns(), (rect.y1 - rect.y0 + 7) / 8, 1);
+    if (scene.instances) hipLaunchKernelGGL(pt_motion_kernel<true>, grid, dim3(64, 1, 1), 0, stream, scene, constants, g, planeMask, motion, imageWidth, rect);
+    else hipLaunchKernelGGL(pt_motion_kernel<false>, grid, dim3(64, 1, 1), 0, stream, scene, constants, g, planeMask, motion, imageWidth, rect);
     return hipGetLastError();
 }
 

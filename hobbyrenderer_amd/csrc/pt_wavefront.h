@@ -13,6 +13,7 @@
 namespace hrt {
 
 struct SceneView;
+struct MotionArgs;     // pt_motion.h
 
 struct WavefrontState {
     void* pool = nullptr;              // one device allocation carved into the SoA queues
@@ -51,8 +52,10 @@ hipError_t wavefront_trace_rays(WavefrontState& st, const SceneView& scene, cons
                                 bool shadow, hipStream_t stream, std::string& error);
 // hrpt_render_gbuffer: the render's bounce-0 front end over one sample per pixel of `rect`, then wf_gbuffer into the planes of planeMask
 // (planes[HRPT_GB_PLANES], width x H float4 each). Leaves the statistics, the plan and the timing state of renders alone.
+// hrpt_render_motion_vectors is the same call with `motion` (pt_motion.h): wf_gbuffer_motion then writes motion->plane as well, and planeMask may be 0.
 hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
-                             float4* const* planes, uint32_t planeMask, uint32_t width, TileRect rect, hipStream_t stream, std::string& error);
+                             float4* const* planes, uint32_t planeMask, uint32_t width, TileRect rect, hipStream_t stream, std::string& error,
+                             const MotionArgs* motion = nullptr);
 void wavefront_release(WavefrontState& st);
 void wavefront_collect_timing(WavefrontState& st);   // call after the stream is synchronised; folds pending events into kernelMs
 void wavefront_reset_timing(WavefrontState& st);

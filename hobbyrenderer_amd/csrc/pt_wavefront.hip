@@ -30,6 +30,7 @@
 
 #include "bvh_build.h"
 #include "pt_gbuffer.h"
+#include "pt_motion.h"
 #include "pt_path.h"
 
 #ifdef HRPT_PHASE_PROFILE
@@ -1340,6 +1341,50 @@ __global__ __launch_bounds__(kBlock) void wf_gbuffer(WfArgs a, HrptPathTracerCon
     }
 }
 
+// ------------------------------------------------------------------ first-hit motion vectors (hrpt_render_motion_vectors)
+// wf_gbuffer's loop with one more plane: the motion texel of pt_motion.h (16 bytes per pixel), and the G-buffer texels only when the call names
+// G-buffer planes too (PLANES = planeMask != 0: one traversal serves both; the motion-only instantiation carries none of gbuffer_texels'
+// registers). Held to four waves per SIMD (at most 128 VGPRs) like the shade kernels. The motion gather -- instance record, three indices, three positions, a
+// three-deep dependent chain -- is issued before gbuffer_texels so that it is in flight while pbr_attributes waits for its texels; lanes that
+// missed skip it and store zeros. The pixel lookup is wf_gbuffer's, restated here: that kernel stays the one hrpt_render_gbuffer has always run.
+template <bool PLANES>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void wf_gbuffer_motion(WfArgs a, HrptPathTracerConstants cb, GBufferPlanes g, uint32_t planeMask, MotionArgs m)
+{
+    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
+    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
+    const SceneView& s = a.scene;
+    for (uint32_t seg = gw; seg < a.numSegments; seg += totalWaves) {
+        const uint32_t cnt = uniform(a.b.pathCnt[0][seg]), segBase = seg * a.segSize;
+        for (uint32_t base = 0; base < cnt; base += 64) {
+            if (base + lane >= cnt) continue;
+            const uint32_t slot = segBase + base + lane;
+            const float4 o = a.b.rayO[0][slot], d = a.b.rayD[0][slot], ha = a.b.hit[slot];
+            const uint32_t smp = reinterpret_cast<const uint32_t*>(a.b.thr[0] + slot)[3];       // one accumulation index: sample == padded pixel
+            const uint32_t tile = smp >> 6, within = smp & 63u;
+            const bool columnMajor = a.rect.stripeCount > 1u;                                    // tile_position with selects, as in wf_gbuffer
+            const uint32_t den = columnMajor ? a.tilesY : a.tilesX, quo = tile / den, rem = tile - quo * den;
+            const uint32_t tcol = columnMajor ? quo : rem, trow = columnMajor ? rem : quo;
+            const uint32_t px = a.rect.column_x(tcol) + (within & 7u), py = a.rect.y0 + trow * 8u + (within >> 3);
+            const size_t idx = (size_t)py * a.imageWidth + px;
+            uint32_t tri = __float_as_uint(ha.w);
+            float4 texel[kGbPlanes];
+            float4 motion = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (tri != 0xFFFFFFFFu) {
+                tri &= 0x1FFFFFFFu;                                  // bits 29-31: shading class (wf_extend)
+                Hit h; h.valid = true; h.t = ha.x; h.u = ha.y; h.v = ha.z; h.tri = tri; h.prim = 0; h.inst = s.instances ? a.b.hitInst[slot] : 0u; h.opaque = 1;
+                const MotionTri mt = motion_gather(s, m, h);
+                if constexpr (PLANES) {
+                    Ray ray; ray.o = mk3(o.x, o.y, o.z); ray.d = mk3(d.x, d.y, d.z); ray.tmin = o.w; ray.tmax = 1e10f;
+                    gbuffer_texels(s, cb, ray, h, texel);
+                }
+                motion = motion_texel(cb.m_View, m, mt, h.u, h.v);
+            } else if constexpr (PLANES) gbuffer_miss(texel);
+            if constexpr (PLANES) gbuffer_store(g, planeMask, idx, texel);
+            m.plane[idx] = motion;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ host side
 // What is launched, on which grid and with how much LDS is decided in pt_wavefront_plan.h; here the plan meets the kernels.
 // The persistent kernels divide their segments evenly among the waves of the grid (seg = wave, wave + waves, ...), so a grid that is not a
@@ -1784,10 +1829,10 @@ size_t carve_gbuffer_pool(char* base, WfArgs& a, uint64_t capacity, uint32_t seg
 }
 
 // hrpt_render_gbuffer, wavefront path: wf_raygen + the render's closest-hit kernel over one sample per pixel of `rect` (plan_gbuffer), then
-// wf_gbuffer. Touches neither st.plan nor the byte / timing accounting of renders; works in the render's queue pool when that is large enough,
+// wf_gbuffer -- or, for hrpt_render_motion_vectors (`motion` given), wf_gbuffer_motion. Touches neither st.plan nor the byte / timing accounting of renders; works in the render's queue pool when that is large enough,
 // otherwise in a pool of its own (HrptStats::queuePoolBytes keeps describing renders).
 hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
-                             float4* const* planes, uint32_t planeMask, uint32_t width, TileRect rect, hipStream_t stream, std::string& error)
+                             float4* const* planes, uint32_t planeMask, uint32_t width, TileRect rect, hipStream_t stream, std::string& error, const MotionArgs* motion)
 {
     if (rect.x1 <= rect.x0 || rect.y1 <= rect.y0 || rect.columns() == 0) return hipSuccess;
     hipError_t e;
@@ -1833,7 +1878,9 @@ hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const S
     const dim3 grid(plan.batch.grid);
     hipLaunchKernelGGL(wf_raygen, grid, dim3(kBlock), 0, stream, a, constants, jt);
     launch_extend(plan.vE, cus, dim3(plan.batch.gridExtend), stream, a, 0u);
-    hipLaunchKernelGGL(wf_gbuffer, grid, dim3(kBlock), 0, stream, a, constants, g, planeMask);
+    if (motion && planeMask != 0u) hipLaunchKernelGGL(wf_gbuffer_motion<true>, grid, dim3(kBlock), 0, stream, a, constants, g, planeMask, *motion);
+    else if (motion) hipLaunchKernelGGL(wf_gbuffer_motion<false>, grid, dim3(kBlock), 0, stream, a, constants, g, planeMask, *motion);
+    else hipLaunchKernelGGL(wf_gbuffer, grid, dim3(kBlock), 0, stream, a, constants, g, planeMask);
     if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }
     return hipSuccess;
 }

@@ -32,6 +32,7 @@ EXPORTS = [
     "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_render_gbuffer", "hrpt_read_gbuffer", "hrpt_get_gbuffer_device",
+    "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
 ]
 
@@ -81,6 +82,9 @@ lib.hrpt_bloom_pack_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_vo
 lib.hrpt_render_gbuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
 lib.hrpt_read_gbuffer.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
 lib.hrpt_get_gbuffer_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+lib.hrpt_render_motion_vectors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+lib.hrpt_read_motion_vectors.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+lib.hrpt_get_motion_vectors_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
 lib.hrpt_halton.argtypes = [C.c_uint32, C.c_uint32]
 lib.hrpt_halton.restype = C.c_float
 lib.hrpt_precompute_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -277,6 +281,31 @@ class PathTracerContext:
         """Device pointer of one G-buffer plane (None when it was never requested)."""
         ptr = C.c_void_p()
         self._check(lib.hrpt_get_gbuffer_device(self._h, int(plane), C.byref(ptr)))
+        return ptr.value
+
+    def render_motion_vectors(self, constants, prev_view, planes=0, tile=(0, 0, 0, 0), flags=S.FRAME_DEFAULT, stripes=(1, 0)):
+        """hrpt_render_motion_vectors: screen-space motion of the first hit (previous minus current window position in pixels, change of view
+        depth, valid flag) for constants["m_View"] against last frame's `prev_view` (S.PlanarViewConstants) and the instances' m_PrevWorld.
+        `planes`: G-buffer planes to write in the same pass (0 = motion only). tile / flags / stripes as in render_gbuffer. Asynchronous."""
+        p = np.zeros((), S.FrameParams)
+        p["stripeCount"], p["stripeIndex"] = stripes
+        p["constants"] = constants
+        p["accumCount"] = 1
+        p["tileX0"], p["tileY0"], p["tileX1"], p["tileY1"] = tile
+        p["flags"] = flags
+        pv = np.ascontiguousarray(np.asarray(prev_view, S.PlanarViewConstants))
+        self._check(lib.hrpt_render_motion_vectors(self._h, p.ctypes.data, pv.ctypes.data, int(planes)))
+
+    def read_motion_vectors(self):
+        """The motion plane: float32 [H, W, 4] (synchronises)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(lib.hrpt_read_motion_vectors(self._h, out.ctypes.data, out.nbytes))
+        return out
+
+    def motion_vectors_device(self):
+        """Device pointer of the motion plane (None before the first render_motion_vectors)."""
+        ptr = C.c_void_p()
+        self._check(lib.hrpt_get_motion_vectors_device(self._h, C.byref(ptr)))
         return ptr.value
 
     def set_stream(self, hip_stream):

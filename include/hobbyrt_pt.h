@@ -355,7 +355,7 @@ int  hrpt_set_acceleration_structure(HrptContext* ctx, int structure);
 /* Moving objects: writes instances[0..count) over the scene's instances [firstInstance, firstInstance + count) -- the closed dirty range
  * Renderer::UploadDirtyInstanceTransforms copies into m_InstanceDataBuffer / m_RTInstanceDescBuffer (src/Renderer.cpp:924-967, fed by
  * Scene::Update, src/Scene.cpp:536-556) -- and rebuilds the acceleration structure, the job of TLASRenderer's per-frame
- * buildTopLevelAccelStructFromBuffer (src/CommonRenderers.cpp:234-246). Only m_World (and the unused m_PrevWorld / m_Center / m_Radius)
+ * buildTopLevelAccelStructFromBuffer (src/CommonRenderers.cpp:234-246). Only m_World, m_PrevWorld (read by hrpt_render_motion_vectors alone) and the unused m_Center / m_Radius
  * may differ from the uploaded instance; a changed mesh, material or LOD index is HRPT_ERR_INVALID_ARGUMENT. With a GPU builder selected
  * the geometry and all build buffers are already on the device: the call uploads count-independent O(instances) data and runs the build
  * kernels (hrpt_get_build_info reports the rebuild); with the host builder the tree is rebuilt on the host from the library's copy of
@@ -427,7 +427,7 @@ int  hrpt_trace_rays(HrptContext* ctx, const HrptRay* rays, HrptRayHit* hits, ui
  * hrpt_render_gbuffer honours the tile rectangle, the stripes and HRPT_FRAME_MEGAKERNEL / _WAVEFRONT of params exactly as hrpt_render does,
  * writes only the planes in planeMask and only the pixels of the tile, is asynchronous on the context stream (ordered with renders) and
  * leaves Accumulation, Output, the exposure buffer and every HrptStats field as they were. planeMask == 0 or a bit >= HRPT_GB_PLANES:
- * HRPT_ERR_INVALID_ARGUMENT; no scene: HRPT_ERR_NO_SCENE. Motion vectors are not provided. */
+ * HRPT_ERR_INVALID_ARGUMENT; no scene: HRPT_ERR_NO_SCENE. Motion vectors: hrpt_render_motion_vectors below (bit 6 stays an error here). */
 enum { HRPT_GB_ALBEDO = 0, HRPT_GB_NORMAL = 1, HRPT_GB_GEO_NORMAL = 2, HRPT_GB_EMISSIVE = 3, HRPT_GB_DEPTH = 4, HRPT_GB_IDS = 5, HRPT_GB_PLANES = 6 };
 #define HRPT_GB_ALL_PLANES 0x3Fu
 #define HRPT_GB_FLAG_HIT 1u          /* the primary ray committed a hit */
@@ -437,6 +437,32 @@ int  hrpt_render_gbuffer(HrptContext* ctx, const HrptFrameParams* params, uint32
 int  hrpt_read_gbuffer(HrptContext* ctx, uint32_t plane, void* dst, size_t bytes);
 /* Device pointer of one plane (valid until hrpt_resize / hrpt_destroy); NULL when the plane was never requested. */
 int  hrpt_get_gbuffer_device(HrptContext* ctx, uint32_t plane, void** devicePtr);
+
+/* ---- first-hit motion vectors -------------------------------------------------------------------------------------
+ * The sixth target of the reference's GBufferOut: screen-space motion of the surface the primary ray of every pixel saw, by
+ * ComputeMotionVectors (src/shaders/CommonLighting.hlsli:242-260) fed as the raster pass feeds it (src/shaders/BasePass.hlsl:53,492).
+ * The hit (instance i, primitive p, barycentrics u, v) is the one hrpt_render_gbuffer commits for the same params. With q_k the object-space
+ * positions of the primitive's LOD-0 vertices, cur_k = q_k * m_World_i, prev_k = q_k * m_PrevWorld_i (row-vector products, left to right),
+ * bx = (1 - u) - v:  worldPos = (cur_0 bx + cur_1 u) + cur_2 v  and prevWorldPos likewise -- the INTERPOLATED vertex position, not o + d t,
+ * so equal transforms and equal views give exactly (0, 0, 0). Then
+ *   clip = float4(worldPos, 1) * params->constants.m_View.m_MatWorldToClip,   prevClip = float4(prevWorldPos, 1) * prevView->m_MatWorldToClip
+ *   window = clip.xy / clip.w * m_ClipToWindowScale + m_ClipToWindowBias      (prevWindow with prevView's scale and bias)
+ *   texel  = (prevWindow.x - window.x, prevWindow.y - window.y, prevClip.w - clip.w, 1)        miss: (0, 0, 0, 0)
+ * in binary32, one rounding per operation. x, y are in pixels and point from this frame's position to last frame's;
+ * z is the change of linear view depth; w is the valid flag (the reference leaves it unused). The matrices are the jittered ones, as in the reference.
+ * The caller maintains m_PrevWorld as the reference's Scene::Update does (src/Scene.cpp:413-417): before moving anything, m_PrevWorld <- m_World
+ * for ALL instances, then hrpt_update_instances / hrpt_refit_instances over the full range; prevView is last frame's m_View.
+ * planeMask names G-buffer planes (bits 0..5) to write in the same pass from the same hits, 0 = motion only; planes not named keep their
+ * contents. Tile rectangle, stripes, frame flags, asynchrony and hrpt_set_stream as in hrpt_render_gbuffer; Accumulation, Output, exposure and
+ * HrptStats are not touched. The motion plane (width x height x 16 bytes) is owned by the library, allocated (zeroed) by the first call and
+ * re-allocated (zeroed) by hrpt_resize; the first call also uploads the tables it reads (positions, indices, one 64-byte record per instance),
+ * later calls refresh what an upload or an instance update made stale. NULL params or prevView, accumCount != 1, a mask bit >= 6:
+ * HRPT_ERR_INVALID_ARGUMENT; no scene: HRPT_ERR_NO_SCENE. prevClip.w == 0 or non-finite inputs give what IEEE 754 gives. */
+int  hrpt_render_motion_vectors(HrptContext* ctx, const HrptFrameParams* params, const HrptPlanarViewConstants* prevView, uint32_t planeMask);
+/* Host read-back of the motion plane (synchronises); bytes must be width*height*16. Before the first hrpt_render_motion_vectors: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_read_motion_vectors(HrptContext* ctx, float* dst, size_t bytes);
+/* Device pointer of the motion plane (valid until hrpt_resize / hrpt_destroy); NULL until the first hrpt_render_motion_vectors. */
+int  hrpt_get_motion_vectors_device(HrptContext* ctx, void** devicePtr);
 
 /* Host read-back (synchronises). bytes must be width*height*16. */
 int  hrpt_read_accumulation(HrptContext* ctx, float* rgba, size_t bytes);
