@@ -57,6 +57,8 @@ struct HrptContext {
     MotionInst* dMotionInst = nullptr; size_t motionInstCapacity = 0;          // one record per instance: m_PrevWorld + the mesh's LOD-0 index offset
     float* dMotionPositions = nullptr; uint32_t* dMotionIndices = nullptr;     // object-space positions (12 B per vertex) and the index buffer
     bool motionInstStale = true, motionGeometryStale = true;                   // set by uploads / instance updates / rebuilds, cleared by the next motion call
+    // temporal accumulation (hrpt_temporal_accumulate): ping-pong history pair, allocated by the first call; [temporalCur] is the image the last call wrote
+    float4* dTemporal[2] = {}; int temporalCur = 0; bool temporalValid = false;
     DeviceCounters* dCounters = nullptr;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
@@ -207,6 +209,7 @@ void hrpt_destroy(HrptContext* c)
     if (c->dDisplay) (void)hipFree(c->dDisplay);
     for (float4* plane : c->dGBuffer) if (plane) (void)hipFree(plane);
     if (c->dMotion) (void)hipFree(c->dMotion);
+    for (float4* image : c->dTemporal) if (image) (void)hipFree(image);
     if (c->dHistogram) (void)hipFree(c->dHistogram);
     if (c->dExposure) (void)hipFree(c->dExposure);
     if (c->dBloomDown) (void)hipFree(c->dBloomDown);
@@ -713,6 +716,13 @@ int hrpt_resize(HrptContext* c, uint32_t width, uint32_t height)
         (void)hipFree(c->dMotion); c->dMotion = nullptr;
         HIP_TRY(c, hipMalloc((void**)&c->dMotion, bytes));
         HIP_TRY(c, hipMemsetAsync(c->dMotion, 0, bytes, c->stream));
+    }
+    c->temporalValid = false; c->temporalCur = 0;     // the temporal history does not survive a resize
+    for (float4*& image : c->dTemporal) {
+        if (!image) continue;
+        (void)hipFree(image); image = nullptr;
+        HIP_TRY(c, hipMalloc((void**)&image, bytes));
+        HIP_TRY(c, hipMemsetAsync(image, 0, bytes, c->stream));
     }
     c->width = width; c->height = height;
     return HRPT_OK;
@@ -1251,6 +1261,105 @@ int hrpt_bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, fl
 {
     if (!rgb && count) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_pack_probe: null input");
     bloom_pack_probe(rgb, count, packed, unpackedRgb);
+    return HRPT_OK;
+}
+
+// ---- temporal accumulation (pt_temporal.h / pt_temporal.hip) ----
+static int temporal_check(HrptContext* c, const char* what, const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                          const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p)
+{
+    const std::string w(what);
+    if (!img || !view || !prevView || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->color || !img->motion || !img->depth || !img->normal || !img->historyOut || !img->colorOut)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only historyIn may be NULL)");
+    if (img->historyOut == img->historyIn) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": historyOut must differ from historyIn");
+    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
+    if (!(view->m_ViewportSize[0] == (float)width && view->m_ViewportSize[1] == (float)height))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
+    if (!temporal_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": blend must be finite and in [0, 1], flags HRPT_TEMPORAL_* only, reserved 0");
+    return HRPT_OK;
+}
+
+int hrpt_temporal_host(const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                       const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p, int nthreads)
+{
+    int r = temporal_check(nullptr, "hrpt_temporal_host", img, width, height, view, prevView, p);
+    if (r != HRPT_OK) return r;
+    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    try { temporal_host(*img, width, height, *view, *prevView, *p, nthreads); }
+    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_temporal_host: out of memory"); }
+    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_temporal_host: ") + e.what()); }
+    return HRPT_OK;
+}
+
+int hrpt_temporal_device(HrptContext* c, const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                         const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p, void* stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    int r = temporal_check(c, "hrpt_temporal_device", img, width, height, view, prevView, p);
+    if (r != HRPT_OK) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_temporal(*img, width, height, *view, *prevView, *p, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+}
+
+int hrpt_temporal_accumulate(HrptContext* c, const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!view || !prevView || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: null argument");
+    if (!c->dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: hrpt_resize not called");
+    if (!c->dMotion || !c->dGBuffer[HRPT_GB_DEPTH] || !c->dGBuffer[HRPT_GB_NORMAL])
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: the motion, depth or normal plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH | NORMAL fills them)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+    const bool fresh = !c->dTemporal[0];
+    const int next = fresh ? 0 : 1 - c->temporalCur;
+    HrptTemporalImages img{};
+    img.color = reinterpret_cast<const float*>(c->dOutput); img.colorOut = reinterpret_cast<float*>(c->dOutput);
+    img.motion = reinterpret_cast<const float*>(c->dMotion);
+    img.depth = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_DEPTH]); img.normal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_NORMAL]);
+    // validate before anything is allocated; the history pointers are placeholders for the check (the pair never aliases)
+    img.historyOut = reinterpret_cast<float*>(c->dOutput);
+    int r = temporal_check(c, "hrpt_temporal_accumulate", &img, c->width, c->height, view, prevView, p);
+    if (r != HRPT_OK) return r;
+    if (fresh) {
+        for (float4*& image : c->dTemporal) {
+            HIP_TRY(c, hipMalloc((void**)&image, bytes));
+            HIP_TRY(c, hipMemsetAsync(image, 0, bytes, c->stream));
+        }
+        c->temporalValid = false;
+    }
+    const bool useHistory = c->temporalValid && (p->flags & HRPT_TEMPORAL_RESET) == 0;
+    img.historyIn = useHistory ? reinterpret_cast<const float*>(c->dTemporal[1 - next]) : nullptr;
+    img.historyOut = reinterpret_cast<float*>(c->dTemporal[next]);
+    HIP_TRY(c, launch_temporal(img, c->width, c->height, *view, *prevView, *p, c->stream));
+    c->temporalCur = next; c->temporalValid = true;
+    return HRPT_OK;
+}
+
+int hrpt_read_temporal_history(HrptContext* c, float* dst, size_t bytes)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->dTemporal[0]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_temporal_history: the history was never requested from hrpt_temporal_accumulate");
+    return read_image(c, c->dTemporal[c->temporalCur], dst, bytes, "hrpt_read_temporal_history");
+}
+
+int hrpt_get_temporal_history_device(HrptContext* c, void** devicePtr)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_temporal_history_device: null out");
+    *devicePtr = c->dTemporal[0] ? c->dTemporal[c->temporalCur] : nullptr;
+    return HRPT_OK;
+}
+
+int hrpt_clear_accumulation(HrptContext* c)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->dAccum) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_clear_accumulation: hrpt_resize not called");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemsetAsync(c->dAccum, 0, (size_t)c->width * c->height * sizeof(float4), c->stream));
     return HRPT_OK;
 }
 

@@ -60,6 +60,14 @@ hipError_t launch_bloom(float4* hdr, uint32_t width, uint32_t height, const Hrpt
 void bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, float* unpacked);   // test hook: the format conversion alone
 void bloom_host(const float* hdrIn, float* hdrOut, uint32_t width, uint32_t height, const HrptBloomParams& params, int nthreads);
 
+// Temporal accumulation (pt_temporal.hip; arithmetic in pt_temporal.h): one kernel over width x height device images. temporal_host
+// (pt_temporal_host.cpp): the same arithmetic on host threads. colorOut may be color; historyOut must not be historyIn.
+bool temporal_params_valid(const HrptTemporalParams& params);
+hipError_t launch_temporal(const HrptTemporalImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+                           const HrptPlanarViewConstants& prevView, const HrptTemporalParams& params, hipStream_t stream);
+void temporal_host(const HrptTemporalImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+                   const HrptPlanarViewConstants& prevView, const HrptTemporalParams& params, int nthreads);
+
 // Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
 hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
 

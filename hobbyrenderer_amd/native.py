@@ -33,6 +33,8 @@ EXPORTS = [
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_render_gbuffer", "hrpt_read_gbuffer", "hrpt_get_gbuffer_device",
     "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
+    "hrpt_temporal_host", "hrpt_temporal_device", "hrpt_temporal_accumulate", "hrpt_read_temporal_history", "hrpt_get_temporal_history_device",
+    "hrpt_clear_accumulation",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
 ]
 
@@ -85,6 +87,12 @@ lib.hrpt_get_gbuffer_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_vo
 lib.hrpt_render_motion_vectors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
 lib.hrpt_read_motion_vectors.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.hrpt_get_motion_vectors_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+lib.hrpt_temporal_host.argtypes = [C.POINTER(S.TemporalImages), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(S.TemporalParams), C.c_int]
+lib.hrpt_temporal_device.argtypes = [C.c_void_p, C.POINTER(S.TemporalImages), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(S.TemporalParams), C.c_void_p]
+lib.hrpt_temporal_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(S.TemporalParams)]
+lib.hrpt_read_temporal_history.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+lib.hrpt_get_temporal_history_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+lib.hrpt_clear_accumulation.argtypes = [C.c_void_p]
 lib.hrpt_halton.argtypes = [C.c_uint32, C.c_uint32]
 lib.hrpt_halton.restype = C.c_float
 lib.hrpt_precompute_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -166,6 +174,34 @@ def bloom_pack_probe(rgb):
     if rc != 0:
         raise HrptError(rc, lib.hrpt_last_error(None).decode())
     return packed, unpacked
+
+
+def _view_record(view):
+    return np.ascontiguousarray(np.asarray(view, S.PlanarViewConstants))
+
+
+def temporal_host(color, motion, depth, normal, history, view, prev_view, params=None, nthreads=0):
+    """hrpt_temporal_host: the temporal stage (csrc/pt_temporal.h) on host threads over float32 [H, W, 4] images; needs no GPU and is
+    bit-identical to PathTracerContext.temporal_accumulate / temporal_device. color: Output of a render; motion: read_motion_vectors();
+    depth / normal: the planes S.GB_DEPTH / S.GB_NORMAL of the same frame; history: what the previous call returned, or None.
+    view / prev_view: S.PlanarViewConstants of this and of last frame. view["m_ViewportSize"] must be (W, H), and
+    view["m_CameraDirectionOrPosition"] must hold (camera position, 1): scenes.planar_view leaves it zero, the caller fills it.
+    Returns (colour out, history out): rgb = blended radiance in both, alpha = color's alpha / the age."""
+    imgs = [np.ascontiguousarray(a, np.float32) for a in (color, motion, depth, normal)]
+    shape = imgs[0].shape
+    if len(shape) != 3 or shape[2] != 4 or any(a.shape != shape for a in imgs):
+        raise ValueError("temporal_host: four float32 [H, W, 4] images of one size expected")
+    hist = None if history is None else np.ascontiguousarray(history, np.float32)
+    if hist is not None and hist.shape != shape:
+        raise ValueError("temporal_host: history must have the images' shape")
+    params = params if params is not None else S.TemporalParams()
+    out, hout = np.empty(shape, np.float32), np.empty(shape, np.float32)
+    im = S.TemporalImages(*[a.ctypes.data for a in imgs], None if hist is None else hist.ctypes.data, hout.ctypes.data, out.ctypes.data)
+    v, pv = _view_record(view), _view_record(prev_view)
+    rc = lib.hrpt_temporal_host(C.byref(im), shape[1], shape[0], v.ctypes.data, pv.ctypes.data, C.byref(params), int(nthreads))
+    if rc != 0:
+        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    return out, hout
 
 
 _BVH_DUMP_ARRAYS = (("nodes", S.GpuNode, "nodeCount"), ("nodes4", S.GpuNode4, "node4Count"), ("nodesQ", S.GpuNodeQ, "node4Count"),
@@ -421,6 +457,41 @@ class PathTracerContext:
         """The same over a caller-owned device image (width * height float4), asynchronously on `hip_stream` (integer handle)."""
         params = params if params is not None else S.BloomParams()
         self._check(lib.hrpt_bloom_device(self._h, C.c_void_p(int(image_ptr)), int(width), int(height), C.byref(params), C.c_void_p(int(hip_stream))))
+
+    def clear_accumulation(self):
+        """hrpt_clear_accumulation: zeroes the Accumulation image on the context stream, so that the next render may start a fresh frame at
+        a non-zero accumulation index (new RNG seeds every frame -- what a temporal accumulator needs)."""
+        self._check(lib.hrpt_clear_accumulation(self._h))
+
+    def temporal_accumulate(self, view, prev_view, params=None):
+        """hrpt_temporal_accumulate: reprojected accumulation of Output across frames, in place (csrc/pt_temporal.h).
+        Frame order: clear_accumulation -> render -> render_motion_vectors(planes = 1 << S.GB_DEPTH | 1 << S.GB_NORMAL) -> temporal_accumulate
+        -> bloom -> post_process. view / prev_view: S.PlanarViewConstants of this and of last frame; view["m_CameraDirectionOrPosition"]
+        must hold (camera position, 1) -- scenes.planar_view leaves it zero, the caller fills it. The history lives in the context; the
+        first call, the first call after resize and S.TEMPORAL_RESET run without it. Asynchronous."""
+        params = params if params is not None else S.TemporalParams()
+        v, pv = _view_record(view), _view_record(prev_view)
+        self._check(lib.hrpt_temporal_accumulate(self._h, v.ctypes.data, pv.ctypes.data, C.byref(params)))
+
+    def temporal_device(self, images, width, height, view, prev_view, params=None, hip_stream=0):
+        """The same over caller-owned device images (S.TemporalImages of device addresses, width * height float4 each), asynchronously on
+        `hip_stream` (integer handle). historyIn may be None (no history); historyOut must differ from it; colorOut may be color."""
+        params = params if params is not None else S.TemporalParams()
+        v, pv = _view_record(view), _view_record(prev_view)
+        self._check(lib.hrpt_temporal_device(self._h, C.byref(images), int(width), int(height), v.ctypes.data, pv.ctypes.data, C.byref(params),
+                                             C.c_void_p(int(hip_stream))))
+
+    def read_temporal_history(self):
+        """The history the last temporal_accumulate wrote: float32 [H, W, 4], rgb = accumulated radiance, a = age (synchronises)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(lib.hrpt_read_temporal_history(self._h, out.ctypes.data, out.nbytes))
+        return out
+
+    def temporal_history_device(self):
+        """Device pointer of that image (None before the first temporal_accumulate)."""
+        ptr = C.c_void_p()
+        self._check(lib.hrpt_get_temporal_history_device(self._h, C.byref(ptr)))
+        return ptr.value
 
     def read_display(self):
         out = np.empty((self.height, self.width, 4), np.float32)

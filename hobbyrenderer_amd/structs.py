@@ -125,6 +125,23 @@ class BloomParams(C.Structure):
         super().__init__(knee, intensity, upsampleRadius, reserved)
 
 
+TEMPORAL_LINEAR, TEMPORAL_RESET = 1, 2          # HrptTemporalParams::flags
+
+
+class TemporalParams(C.Structure):
+    """HrptTemporalParams; blend defaults to the reference's m_SSGI_TemporalBlend (Renderer.h:358). flags: TEMPORAL_LINEAR blends in linear
+    radiance (the unbiased running mean) instead of the reference's log(1 + x) space; TEMPORAL_RESET ignores the context's stored history."""
+    _fields_ = [("blend", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, blend=0.9, flags=0):
+        super().__init__(blend, flags, (C.c_uint32 * 2)(0, 0))
+
+
+class TemporalImages(C.Structure):
+    """HrptTemporalImages: host or device addresses of width x height float4 images."""
+    _fields_ = [(n, C.c_void_p) for n in ("color", "motion", "depth", "normal", "historyIn", "historyOut", "colorOut")]
+
+
 class Stats(C.Structure):
     _fields_ = [("closestRays", C.c_uint64), ("shadowRays", C.c_uint64), ("paths", C.c_uint64),
                 ("lastRenderMs", C.c_float), ("traceKernelMs", C.c_float), ("traceKernelLaunches", C.c_uint32),

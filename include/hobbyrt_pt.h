@@ -533,6 +533,60 @@ int  hrpt_bloom_host(const float* hdrIn, float* hdrOut, uint32_t width, uint32_t
  * sample reads back from it. Either output may be NULL. */
 int  hrpt_bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, float* unpackedRgb);
 
+/* ---- Temporal accumulation: reprojected accumulation across frames --------------------------------------------------
+ * The consumer of the G-buffer and the motion vectors: the reference's SSGI temporal pass (src/shaders/SSGITemporalReproject.hlsl, driven by
+ * src/SSGIRenderer.cpp:170-230, m_SSGI_TemporalBlend = 0.9) over the path tracer's own images. Per pixel: reproject through the motion
+ * vector, validate the reprojected position against this frame's depth, normal and velocity, resample last call's history with
+ * SampleTextureCatmullRom (nine bilinear taps + anti-ringing clamp), blend with an age kept in the history's alpha, cap the history weight
+ * at `blend` where the pixel moves more than a pixel. hobbyrenderer_amd/csrc/pt_temporal.h is the definition: what
+ * the samplers do, the depth convention, the miss rule, and the differences from the reference (no history = confidence 0; the linear mode).
+ * All images are width x height float4: color = Output of hrpt_render; motion = the plane of hrpt_render_motion_vectors; depth / normal =
+ * the planes HRPT_GB_DEPTH / HRPT_GB_NORMAL of the same frame; history: rgb = accumulated radiance, a = age (frames behind the estimate).
+ * Outputs: historyOut = (blended rgb, new age), colorOut = (blended rgb, color.a). view->m_ViewportSize must equal (width, height);
+ * view->m_CameraDirectionOrPosition.xyz must hold the camera position. Opt-in: nothing calls it implicitly. Not part of multi-GPU tiles:
+ * it works on whole images, run it after the gather. */
+#define HRPT_TEMPORAL_LINEAR 1u   /* blend in linear radiance instead of the reference's log(1 + x) space */
+#define HRPT_TEMPORAL_RESET  2u   /* context call: ignore the stored history this call */
+typedef struct HrptTemporalParams {
+    float blend;          /* SSGITemporalConstants::m_Blend, default 0.9 (src/Renderer.h:358); finite, in [0, 1] */
+    uint32_t flags;       /* HRPT_TEMPORAL_* */
+    uint32_t reserved[2]; /* 0 */
+} HrptTemporalParams;
+typedef struct HrptTemporalImages {
+    const float *color, *motion, *depth, *normal;
+    const float *historyIn;     /* NULL = no history */
+    float *historyOut;          /* must differ from historyIn */
+    float *colorOut;            /* may equal color */
+} HrptTemporalImages;
+/* The stage on host threads over host images (no GPU needed; nthreads <= 0: one per hardware thread, at most 16). Bit-identical to the
+ * device calls. NULL arguments or images (historyIn excepted), historyOut == historyIn, a size outside 1..65535, m_ViewportSize != the
+ * size, blend outside [0, 1] or not finite, unknown flag bits, non-zero reserved: HRPT_ERR_INVALID_ARGUMENT. HRPT_TEMPORAL_RESET is
+ * accepted and means nothing here (pass historyIn = NULL). */
+int  hrpt_temporal_host(const HrptTemporalImages* images, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                        const HrptPlanarViewConstants* prevView, const HrptTemporalParams* params, int nthreads);
+/* The same over caller-owned DEVICE images, asynchronous on the caller's stream (a hipStream_t; NULL = the default stream). */
+int  hrpt_temporal_device(HrptContext* ctx, const HrptTemporalImages* deviceImages, uint32_t width, uint32_t height,
+                          const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptTemporalParams* params, void* stream);
+/* The stage over the context's own images: color = colorOut = Output, the motion plane and the planes HRPT_GB_DEPTH and HRPT_GB_NORMAL as
+ * the caller filled them for this frame with hrpt_render_motion_vectors(..., planeMask = DEPTH | NORMAL), and a library-owned ping-pong
+ * pair of history images, allocated by the first call and re-allocated (history dropped) by hrpt_resize. The first call, the first call
+ * after a resize and a call with HRPT_TEMPORAL_RESET run without history. Asynchronous on the context stream, ordered with renders,
+ * honours hrpt_set_stream. Accumulation, the planes, exposure and HrptStats are not touched; every render re-resolves Output, so the
+ * stage never feeds back into the accumulation. Frame order:
+ *   hrpt_clear_accumulation -> hrpt_render -> hrpt_render_motion_vectors -> hrpt_temporal_accumulate -> hrpt_bloom -> hrpt_post_process
+ * A motion, depth or normal plane that was never requested, and the argument errors of hrpt_temporal_host: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_temporal_accumulate(HrptContext* ctx, const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptTemporalParams* params);
+/* Host read-back of the history the last hrpt_temporal_accumulate wrote (synchronises); bytes must be width*height*16. Before the first
+ * call: HRPT_ERR_INVALID_ARGUMENT; after a resize: the new size, zeroed (as hrpt_read_motion_vectors). */
+int  hrpt_read_temporal_history(HrptContext* ctx, float* dst, size_t bytes);
+/* Device pointer of that image (valid until the next hrpt_temporal_accumulate / hrpt_resize / hrpt_destroy); NULL before the first call. */
+int  hrpt_get_temporal_history_device(HrptContext* ctx, void** devicePtr);
+/* Zeroes the Accumulation image, asynchronously on the context stream: a fresh frame that starts at a non-zero accumulation index. A
+ * following hrpt_render with first index k > 0 and accumCount s leaves Accumulation.a == s and Output = rgb / s of exactly the indices
+ * k .. k + s - 1 (both kernel paths add onto the stored image whenever the index is > 0). A per-frame render at index 0 would instead
+ * reuse the same RNG seeds every frame, and a temporal accumulator fed by it converges to one fixed sample set. */
+int  hrpt_clear_accumulation(HrptContext* ctx);
+
 /* Intra-frame overlap: by default the shadow stage of bounce b runs on a second, library-owned stream next to the traversal of bounce
  * b + 1 (they share no buffer). That fills the tails of a context that renders one frame at a time (-3 % per frame). A host that keeps
  * two frames in flight on two contexts already fills those tails with the other frame; there the fork / join events only cost
