@@ -59,6 +59,8 @@ struct HrptContext {
     bool motionInstStale = true, motionGeometryStale = true;                   // set by uploads / instance updates / rebuilds, cleared by the next motion call
     // temporal accumulation (hrpt_temporal_accumulate): ping-pong history pair, allocated by the first call; [temporalCur] is the image the last call wrote
     float4* dTemporal[2] = {}; int temporalCur = 0; bool temporalValid = false;
+    // denoise (hrpt_denoise): the default noise tile (uploaded by the first denoise call of the context) and the scratch pair of HRPT_DENOISE_OUTPUT_ONLY
+    float* dDenoiseTile = nullptr; float4* dDenoiseScratch[2] = {};
     DeviceCounters* dCounters = nullptr;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
@@ -210,6 +212,8 @@ void hrpt_destroy(HrptContext* c)
     for (float4* plane : c->dGBuffer) if (plane) (void)hipFree(plane);
     if (c->dMotion) (void)hipFree(c->dMotion);
     for (float4* image : c->dTemporal) if (image) (void)hipFree(image);
+    for (float4* image : c->dDenoiseScratch) if (image) (void)hipFree(image);
+    if (c->dDenoiseTile) (void)hipFree(c->dDenoiseTile);
     if (c->dHistogram) (void)hipFree(c->dHistogram);
     if (c->dExposure) (void)hipFree(c->dExposure);
     if (c->dBloomDown) (void)hipFree(c->dBloomDown);
@@ -724,6 +728,7 @@ int hrpt_resize(HrptContext* c, uint32_t width, uint32_t height)
         HIP_TRY(c, hipMalloc((void**)&image, bytes));
         HIP_TRY(c, hipMemsetAsync(image, 0, bytes, c->stream));
     }
+    for (float4*& image : c->dDenoiseScratch) if (image) { (void)hipFree(image); image = nullptr; }     // allocated again by the call that needs it
     c->width = width; c->height = height;
     return HRPT_OK;
 }
@@ -1351,6 +1356,106 @@ int hrpt_get_temporal_history_device(HrptContext* c, void** devicePtr)
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_temporal_history_device: null out");
     *devicePtr = c->dTemporal[0] ? c->dTemporal[c->temporalCur] : nullptr;
+    return HRPT_OK;
+}
+
+// ---- denoise (pt_denoise.h / pt_denoise.hip) ----
+static int denoise_check(HrptContext* c, const char* what, const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                         const HrptDenoiseParams* p, bool singlePass)
+{
+    const std::string w(what);
+    if (!img || !view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->input || !img->depth || !img->normal || !img->geoNormal || !img->output)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only noise, and color with colorOut, may be NULL)");
+    if ((img->color == nullptr) != (img->colorOut == nullptr)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": color and colorOut must both be NULL or both be set");
+    if (img->output == img->input) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": output must differ from input");
+    if (img->color && (img->color == img->input || img->colorOut == img->input)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": color and colorOut must differ from input");
+    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
+    if (!(view->m_ViewportSize[0] == (float)width && view->m_ViewportSize[1] == (float)height))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
+    if (!denoise_params_valid(*p))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": radius and phi must be finite and > 0, the other phis finite and >= 0, iterations 1..5 with radius * 2^(iterations - 1) finite, flags HRPT_DENOISE_* only, reserved 0");
+    if (singlePass && p->iterations != 1u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": one pass per call, iterations must be 1 (hrpt_denoise iterates)");
+    return HRPT_OK;
+}
+
+static int denoise_tile(HrptContext* c)
+{
+    if (c->dDenoiseTile) return HRPT_OK;
+    std::vector<float> tile(denoise_noise_floats());
+    denoise_default_tile(tile.data());
+    float* d = nullptr;
+    HIP_TRY(c, hipMalloc((void**)&d, tile.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(d, tile.data(), tile.size() * sizeof(float), hipMemcpyHostToDevice);     // complete on return: ordered before every later launch
+    if (e != hipSuccess) { (void)hipFree(d); HIP_TRY(c, e); }
+    c->dDenoiseTile = d;
+    return HRPT_OK;
+}
+
+int hrpt_denoise_host(const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view, const HrptDenoiseParams* p, int nthreads)
+{
+    int r = denoise_check(nullptr, "hrpt_denoise_host", img, width, height, view, p, true);
+    if (r != HRPT_OK) return r;
+    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    try { denoise_host(*img, width, height, *view, *p, nthreads); }
+    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_denoise_host: out of memory"); }
+    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_denoise_host: ") + e.what()); }
+    return HRPT_OK;
+}
+
+int hrpt_denoise_device(HrptContext* c, const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                        const HrptDenoiseParams* p, void* stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    int r = denoise_check(c, "hrpt_denoise_device", img, width, height, view, p, true);
+    if (r != HRPT_OK) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HrptDenoiseImages im = *img;
+    if (!im.noise) { r = denoise_tile(c); if (r != HRPT_OK) return r; im.noise = c->dDenoiseTile; }
+    HIP_TRY(c, launch_denoise(im, width, height, *view, *p, p->radius, p->frame, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+}
+
+int hrpt_denoise(HrptContext* c, const HrptPlanarViewConstants* view, const HrptDenoiseParams* p)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: null argument");
+    if (!c->dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: hrpt_resize not called");
+    if (!c->dTemporal[0] || !c->temporalValid)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: no temporal history at the current size (hrpt_temporal_accumulate writes the image this stage filters)");
+    if (!c->dGBuffer[HRPT_GB_DEPTH] || !c->dGBuffer[HRPT_GB_NORMAL] || !c->dGBuffer[HRPT_GB_GEO_NORMAL])
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: the depth, normal or geo-normal plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH | NORMAL | GEO_NORMAL fills them)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HrptDenoiseImages img{};
+    img.input = reinterpret_cast<const float*>(c->dTemporal[c->temporalCur]);
+    img.depth = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_DEPTH]); img.normal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_NORMAL]);
+    img.geoNormal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_GEO_NORMAL]);
+    img.output = reinterpret_cast<float*>(c->dTemporal[1 - c->temporalCur]);       // a placeholder for the check where the scratch pair is used
+    int r = denoise_check(c, "hrpt_denoise", &img, c->width, c->height, view, p, false);
+    if (r != HRPT_OK) return r;
+    r = denoise_tile(c);
+    if (r != HRPT_OK) return r;
+    img.noise = c->dDenoiseTile;
+    const bool outputOnly = (p->flags & HRPT_DENOISE_OUTPUT_ONLY) != 0;
+    if (outputOnly) {
+        const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+        for (uint32_t k = 0; k < (p->iterations > 1u ? 2u : 1u); ++k)
+            if (!c->dDenoiseScratch[k]) HIP_TRY(c, hipMalloc((void**)&c->dDenoiseScratch[k], bytes));
+    }
+    int cur = c->temporalCur;
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        // default: the two history images are the ping-pong pair (the stale one is free after the temporal call); the image a pass wrote is the history
+        float4* dst = outputOnly ? c->dDenoiseScratch[i & 1u] : c->dTemporal[1 - cur];
+        img.output = reinterpret_cast<float*>(dst);
+        const bool last = i + 1u == p->iterations;
+        img.color = last ? reinterpret_cast<const float*>(c->dOutput) : nullptr;
+        img.colorOut = last ? reinterpret_cast<float*>(c->dOutput) : nullptr;
+        HIP_TRY(c, launch_denoise(img, c->width, c->height, *view, *p, p->radius * (float)(1u << i), p->frame * p->iterations + i, c->stream));
+        img.input = reinterpret_cast<const float*>(dst);
+        if (!outputOnly) { cur = 1 - cur; c->temporalCur = cur; }
+    }
     return HRPT_OK;
 }
 

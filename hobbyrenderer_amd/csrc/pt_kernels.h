@@ -68,6 +68,17 @@ hipError_t launch_temporal(const HrptTemporalImages& images, uint32_t width, uin
 void temporal_host(const HrptTemporalImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
                    const HrptPlanarViewConstants& prevView, const HrptTemporalParams& params, int nthreads);
 
+// Denoise (pt_denoise.hip; arithmetic in pt_denoise.h): ONE pass of the Poisson filter with the given radius and frame over width x height
+// device images; images.noise must be set (a device tile of denoise_noise_floats() floats). denoise_host (pt_denoise_host.cpp): the same
+// arithmetic on host threads; a NULL images.noise means the default tile there. colorOut may be color; output must not be input.
+bool denoise_params_valid(const HrptDenoiseParams& params);
+size_t denoise_noise_floats();
+void denoise_default_tile(float* tile);
+hipError_t launch_denoise(const HrptDenoiseImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+                          const HrptDenoiseParams& params, float radius, uint32_t frame, hipStream_t stream);
+void denoise_host(const HrptDenoiseImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+                  const HrptDenoiseParams& params, int nthreads);
+
 // Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
 hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
 

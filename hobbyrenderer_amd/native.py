@@ -35,6 +35,7 @@ EXPORTS = [
     "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
     "hrpt_temporal_host", "hrpt_temporal_device", "hrpt_temporal_accumulate", "hrpt_read_temporal_history", "hrpt_get_temporal_history_device",
     "hrpt_clear_accumulation",
+    "hrpt_denoise_host", "hrpt_denoise_device", "hrpt_denoise",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
 ]
 
@@ -93,6 +94,9 @@ lib.hrpt_temporal_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.P
 lib.hrpt_read_temporal_history.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.hrpt_get_temporal_history_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
 lib.hrpt_clear_accumulation.argtypes = [C.c_void_p]
+lib.hrpt_denoise_host.argtypes = [C.POINTER(S.DenoiseImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.DenoiseParams), C.c_int]
+lib.hrpt_denoise_device.argtypes = [C.c_void_p, C.POINTER(S.DenoiseImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.DenoiseParams), C.c_void_p]
+lib.hrpt_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(S.DenoiseParams)]
 lib.hrpt_halton.argtypes = [C.c_uint32, C.c_uint32]
 lib.hrpt_halton.restype = C.c_float
 lib.hrpt_precompute_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -202,6 +206,35 @@ def temporal_host(color, motion, depth, normal, history, view, prev_view, params
     if rc != 0:
         raise HrptError(rc, lib.hrpt_last_error(None).decode())
     return out, hout
+
+
+def denoise_host(input, depth, normal, geo_normal, view, params=None, noise=None, color=None, nthreads=0):
+    """hrpt_denoise_host: ONE pass of the denoise stage (csrc/pt_denoise.h) on host threads over float32 [H, W, 4] images; needs no GPU and
+    is bit-identical to PathTracerContext.denoise_device and to one pass of PathTracerContext.denoise. input: rgb = radiance, a = age (the
+    history of the temporal stage); depth / normal / geo_normal: the planes S.GB_DEPTH / S.GB_NORMAL / S.GB_GEO_NORMAL of the same frame;
+    noise: a float32 [64, 64, 2] tile, or None for the library's default tile (white noise); color: an image whose alpha the second
+    result keeps. view: as for temporal_host. params.iterations must be 1; params.radius and params.frame are used as given.
+    Returns output = (filtered rgb, age), or (output, colorOut) when color is given."""
+    imgs = [np.ascontiguousarray(a, np.float32) for a in (input, depth, normal, geo_normal)]
+    shape = imgs[0].shape
+    if len(shape) != 3 or shape[2] != 4 or any(a.shape != shape for a in imgs):
+        raise ValueError("denoise_host: four float32 [H, W, 4] images of one size expected")
+    tile = None if noise is None else np.ascontiguousarray(noise, np.float32)
+    if tile is not None and tile.shape != (64, 64, 2):
+        raise ValueError("denoise_host: noise must be a float32 [64, 64, 2] tile")
+    col = None if color is None else np.ascontiguousarray(color, np.float32)
+    if col is not None and col.shape != shape:
+        raise ValueError("denoise_host: color must have the images' shape")
+    params = params if params is not None else S.DenoiseParams()
+    out = np.empty(shape, np.float32)
+    cout = None if col is None else np.empty(shape, np.float32)
+    im = S.DenoiseImages(*[a.ctypes.data for a in imgs], None if tile is None else tile.ctypes.data, out.ctypes.data,
+                         None if col is None else col.ctypes.data, None if cout is None else cout.ctypes.data)
+    v = _view_record(view)
+    rc = lib.hrpt_denoise_host(C.byref(im), shape[1], shape[0], v.ctypes.data, C.byref(params), int(nthreads))
+    if rc != 0:
+        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    return out if cout is None else (out, cout)
 
 
 _BVH_DUMP_ARRAYS = (("nodes", S.GpuNode, "nodeCount"), ("nodes4", S.GpuNode4, "node4Count"), ("nodesQ", S.GpuNodeQ, "node4Count"),
@@ -492,6 +525,23 @@ class PathTracerContext:
         ptr = C.c_void_p()
         self._check(lib.hrpt_get_temporal_history_device(self._h, C.byref(ptr)))
         return ptr.value
+
+    def denoise(self, view, params=None):
+        """hrpt_denoise: the edge-stopping Poisson filter over the temporal history (csrc/pt_denoise.h), after
+        temporal_accumulate and before bloom; the planes S.GB_DEPTH, S.GB_NORMAL and S.GB_GEO_NORMAL must have been requested for this frame.
+        params.iterations passes with a doubling radius; the last one also writes Output. By default the filtered image becomes the history
+        the next temporal_accumulate reprojects (read_temporal_history returns it); with S.DENOISE_OUTPUT_ONLY the history is left alone and
+        only Output is filtered. Asynchronous."""
+        params = params if params is not None else S.DenoiseParams()
+        v = _view_record(view)
+        self._check(lib.hrpt_denoise(self._h, v.ctypes.data, C.byref(params)))
+
+    def denoise_device(self, images, width, height, view, params=None, hip_stream=0):
+        """One pass over caller-owned device images (S.DenoiseImages of device addresses; noise None = the default tile), asynchronously on
+        `hip_stream` (integer handle). output must differ from input; color / colorOut are both None or both set; colorOut may be color."""
+        params = params if params is not None else S.DenoiseParams()
+        v = _view_record(view)
+        self._check(lib.hrpt_denoise_device(self._h, C.byref(images), int(width), int(height), v.ctypes.data, C.byref(params), C.c_void_p(int(hip_stream))))
 
     def read_display(self):
         out = np.empty((self.height, self.width, 4), np.float32)

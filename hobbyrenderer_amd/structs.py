@@ -142,6 +142,26 @@ class TemporalImages(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("color", "motion", "depth", "normal", "historyIn", "historyOut", "colorOut")]
 
 
+DENOISE_OUTPUT_ONLY = 1                         # HrptDenoiseParams::flags
+
+
+class DenoiseParams(C.Structure):
+    """HrptDenoiseParams; the defaults are the reference's m_SSGI_Denoise* (Renderer.h:362-368). iterations: passes of the context call
+    (1..5; pass i uses radius * 2^i and frame * iterations + i), 1 for the single-pass calls. flags: DENOISE_OUTPUT_ONLY filters Output and
+    leaves the context's temporal history as the temporal stage wrote it."""
+    _fields_ = [("radius", C.c_float), ("phi", C.c_float), ("lumaPhi", C.c_float), ("depthPhi", C.c_float), ("normalPhi", C.c_float),
+                ("roughnessPhi", C.c_float), ("iterations", C.c_uint32), ("frame", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, radius=3.0, phi=0.5, lumaPhi=5.0, depthPhi=2.0, normalPhi=50.0, roughnessPhi=50.0, iterations=1, frame=0, flags=0, reserved=0):
+        super().__init__(radius, phi, lumaPhi, depthPhi, normalPhi, roughnessPhi, iterations, frame, flags, reserved)
+
+
+class DenoiseImages(C.Structure):
+    """HrptDenoiseImages: host or device addresses of width x height float4 images; noise: 64 * 64 * 2 floats or None (the default tile);
+    color / colorOut: both None or both set."""
+    _fields_ = [(n, C.c_void_p) for n in ("input", "depth", "normal", "geoNormal", "noise", "output", "color", "colorOut")]
+
+
 class Stats(C.Structure):
     _fields_ = [("closestRays", C.c_uint64), ("shadowRays", C.c_uint64), ("paths", C.c_uint64),
                 ("lastRenderMs", C.c_float), ("traceKernelMs", C.c_float), ("traceKernelLaunches", C.c_uint32),

@@ -581,6 +581,70 @@ int  hrpt_temporal_accumulate(HrptContext* ctx, const HrptPlanarViewConstants* v
 int  hrpt_read_temporal_history(HrptContext* ctx, float* dst, size_t bytes);
 /* Device pointer of that image (valid until the next hrpt_temporal_accumulate / hrpt_resize / hrpt_destroy); NULL before the first call. */
 int  hrpt_get_temporal_history_device(HrptContext* ctx, void** devicePtr);
+
+/* ---- Denoise: edge-stopping Poisson filter after the temporal accumulation ---------------------------------------------
+ * The spatial half of the real-time chain: the reference's SSGI denoise pass (src/shaders/SSGIDenoise.hlsl, iterated with a doubling radius
+ * by src/SSGIRenderer.cpp:217-276) over the path tracer's own images. An 8-tap Poisson disk, rotated per pixel by a 64 x 64 noise tile,
+ * gathers neighbours in log(1 + x) space; each tap is weighted by normal, plane distance, roughness and luminance against the centre, and
+ * the younger a pixel's history is (input.a, clamped at 64), the wider and the more permissive its filter. After a camera cut or a
+ * disocclusion hrpt_temporal_accumulate hands back raw samples with age 0: this is the stage that filters them.
+ * hobbyrenderer_amd/csrc/pt_denoise.h is the definition. All images are width x height float4:
+ *   input     rgb = radiance, a = age (the history of the temporal stage)
+ *   depth     HRPT_GB_DEPTH (view depth in .y, miss: .x == 1e10f)      normal  HRPT_GB_NORMAL (unit normal, roughness in .w)
+ *   geoNormal HRPT_GB_GEO_NORMAL (metallic in .w)                      noise   64 * 64 * 2 floats, noise[y][x][2], or NULL
+ *   output    (filtered rgb, input.a unclamped); must differ from input
+ *   color / colorOut   both NULL or both set: colorOut = (filtered rgb, color.a). colorOut may equal color; neither may equal input.
+ * Differences from the reference, on purpose: a miss passes its input texel through (the reference writes 0; here Output holds the sky
+ * there); one radiance image, so the separate specular signal (w2, m_SpecularPhi, specularFactor) is not restated, and the image plays both
+ * signals in the age falloff; the planes hold unit normals, so there is no DecodeNormal. The reference's blue-noise texture is not part of
+ * its tree: the tile is an input, and with noise == NULL the library uses its default tile, texel (x, y) = the first two numbers of
+ * hrt_rng_seed(x, y, 0) -- WHITE noise, not blue noise. A caller that has a blue-noise tile passes it.
+ * view->m_ViewportSize must equal (width, height); view->m_CameraDirectionOrPosition.xyz must hold the camera position. Opt-in: nothing
+ * calls it implicitly. Not part of multi-GPU tiles: it works on whole images, run it after the gather. */
+#define HRPT_DENOISE_OUTPUT_ONLY 1u   /* context call: filter Output only, leave the temporal history as the temporal stage wrote it */
+typedef struct HrptDenoiseParams {
+    float radius;         /* Renderer::m_SSGI_DenoiseRadius, default 3 (src/Renderer.h:362-368); finite, > 0 */
+    float phi;            /* m_SSGI_DenoisePhi, default 0.5; finite, > 0 */
+    float lumaPhi;        /* m_SSGI_DenoiseLumaPhi, default 5; finite, >= 0 */
+    float depthPhi;       /* m_SSGI_DenoiseDepthPhi, default 2; finite, >= 0 */
+    float normalPhi;      /* m_SSGI_DenoiseNormalPhi, default 50; finite, >= 0 */
+    float roughnessPhi;   /* m_SSGI_DenoiseRoughnessPhi, default 50; finite, >= 0 */
+    uint32_t iterations;  /* m_SSGI_DenoiseIterations, default 1; 1..5. Pass i uses radius * 2^i, which must stay finite */
+    uint32_t frame;       /* the frame number that seeds the disk rotation (Renderer::m_FrameNumber) */
+    uint32_t flags;       /* HRPT_DENOISE_* */
+    uint32_t reserved;    /* 0 */
+} HrptDenoiseParams;
+typedef struct HrptDenoiseImages {
+    const float *input, *depth, *normal, *geoNormal;
+    const float *noise;         /* 64 * 64 * 2 floats, or NULL = the default tile */
+    float *output;              /* must differ from input */
+    const float *color;         /* NULL, or the image whose alpha colorOut keeps */
+    float *colorOut;            /* NULL exactly when color is; may equal color */
+} HrptDenoiseImages;
+/* ONE pass on host threads over host images (no GPU needed; nthreads <= 0: one per hardware thread, at most 16), with params->radius and
+ * params->frame as given; params->iterations must be 1. Bit-identical to the device calls. NULL arguments or images (noise, and color with
+ * colorOut, excepted), output == input, color or colorOut == input, one of color / colorOut without the other, a size outside 1..65535,
+ * m_ViewportSize != the size, a parameter outside the ranges above, unknown flag bits, non-zero reserved: HRPT_ERR_INVALID_ARGUMENT.
+ * HRPT_DENOISE_OUTPUT_ONLY is accepted and means nothing here. */
+int  hrpt_denoise_host(const HrptDenoiseImages* images, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                       const HrptDenoiseParams* params, int nthreads);
+/* The same pass over caller-owned DEVICE images (noise, where given, is a device address too), asynchronous on the caller's stream (a
+ * hipStream_t; NULL = the default stream). The default tile is uploaded once per context. */
+int  hrpt_denoise_device(HrptContext* ctx, const HrptDenoiseImages* deviceImages, uint32_t width, uint32_t height,
+                         const HrptPlanarViewConstants* view, const HrptDenoiseParams* params, void* stream);
+/* The stage over the context's own images, after hrpt_temporal_accumulate: input = the temporal history, the planes HRPT_GB_DEPTH,
+ * HRPT_GB_NORMAL and HRPT_GB_GEO_NORMAL as the caller filled them for this frame, the default tile. It runs params->iterations passes;
+ * pass i uses radius * (float)(1u << i) and frame * iterations + i (uint32, wrapping), and the last pass also writes Output as
+ * (filtered rgb, Output.a). By default, as in the reference, the passes ping-pong between the two history images (the stale one is free
+ * after the temporal call) and the filtered image BECOMES the history: the next hrpt_temporal_accumulate reprojects it, and
+ * hrpt_read_temporal_history / hrpt_get_temporal_history_device return it. With HRPT_DENOISE_OUTPUT_ONLY the history stays bit for bit
+ * what the temporal stage wrote and only Output is filtered (this keeps the exact running mean of HRPT_TEMPORAL_LINEAR); the passes then
+ * use a library-owned scratch pair, allocated at first use and dropped by hrpt_resize. Asynchronous on the context stream, honours
+ * hrpt_set_stream; Accumulation, the planes, exposure and HrptStats are not touched. Frame order:
+ *   ... -> hrpt_temporal_accumulate -> hrpt_denoise -> hrpt_bloom -> hrpt_post_process
+ * No valid temporal history at the current size (hrpt_temporal_accumulate not called since hrpt_resize), a depth, normal or geo-normal
+ * plane that was never requested, and the argument errors of hrpt_denoise_host (iterations 1..5 here): HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_denoise(HrptContext* ctx, const HrptPlanarViewConstants* view, const HrptDenoiseParams* params);
 /* Zeroes the Accumulation image, asynchronously on the context stream: a fresh frame that starts at a non-zero accumulation index. A
  * following hrpt_render with first index k > 0 and accumCount s leaves Accumulation.a == s and Output = rgb / s of exactly the indices
  * k .. k + s - 1 (both kernel paths add onto the stored image whenever the index is > 0). A per-frame render at index 0 would instead
