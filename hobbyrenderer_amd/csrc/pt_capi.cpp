@@ -192,6 +192,7 @@ int hrpt_create(const HrptDeviceDesc* desc, HrptContext** out)
     if (const char* e = getenv("HRPT_WF_SHADE_SORT")) c->wf.knobs.shadeSort = atoi(e) != 0 ? 1 : 0;
     if (const char* e = getenv("HRPT_WF_SLIM_SHADOW")) c->wf.knobs.noSlimShadow = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_FUSED_PRIMARY")) c->wf.knobs.noFusedPrimary = atoi(e) == 0;
+    if (const char* e = getenv("HRPT_WF_FUSED_BOUNCE0")) c->wf.knobs.noFusedBounce0 = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_SHADE_LDS_TABLES")) c->wf.knobs.noShadeLdsTables = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_NODE_LOOP_MIN")) c->wf.knobs.nodeLoopMin = (uint32_t)atoi(e);
     if (const char* e = getenv("HRPT_BLOOM_FUSED_TAIL")) { const int v = atoi(e); c->bloomTailTexels = v == 1 ? 8192u : (v > 0 ? (uint32_t)v : 0u); }
@@ -1173,6 +1174,7 @@ int hrpt_get_stats(HrptContext* c, HrptStats* out)
     for (int i = 0; i < kCounterShards; ++i) {
         total.closestRays += h[i].closestRays; total.shadowRays += h[i].shadowRays; total.paths += h[i].paths; total.neeEntries += h[i].neeEntries;
         total.neeSamples += h[i].neeSamples; total.radianceShade += h[i].radianceShade; total.radianceShadow += h[i].radianceShadow; total.skipped16 += h[i].skipped16;
+        total.fusedPaths += h[i].fusedPaths; total.fusedEntries += h[i].fusedEntries;
     }
     out->closestRays = total.closestRays; out->shadowRays = total.shadowRays; out->paths = total.paths;
     out->neeEntries = total.neeEntries; out->neeSamples = total.neeSamples;

@@ -13,7 +13,7 @@ struct MotionArgs;  // pt_motion.h
 struct GpuNode4; struct GpuNodeQ;
 
 constexpr int kCounterShards = 32;   // DeviceCounters[kCounterShards] per context; a block adds to shard blockIdx % kCounterShards
-struct DeviceCounters {         // 64 B; summed over the shards by hrpt_get_stats. The wavefront kernels address the fields by word index.
+struct DeviceCounters {         // 80 B; summed over the shards by hrpt_get_stats. The wavefront kernels address the fields by word index.
     unsigned long long closestRays;       // 0
     unsigned long long shadowRays;        // 1
     unsigned long long paths;             // 2
@@ -22,6 +22,8 @@ struct DeviceCounters {         // 64 B; summed over the shards by hrpt_get_stat
     unsigned long long radianceShade;     // 5: sampleRadiance read-modify-writes of wf_shade (emissive / sky terms)
     unsigned long long radianceShadow;    // 6: sampleRadiance read-modify-writes of wf_shadow (NEE terms)
     unsigned long long skipped16;         // 7: 16-byte path-record reads wf_shadow's slim mode did not make at bounce 0 of a batch without raygen pass
+    unsigned long long fusedPaths;        // 8: primary paths wf_bounce0 traced and shaded (no hit record, no {direction, seed} record for all of them)
+    unsigned long long fusedEntries;      // 9: ... and the shadow-queue entries it emitted (a {direction, seed} record written for each)
 };
 
 struct TileRect {

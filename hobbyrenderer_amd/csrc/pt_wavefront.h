@@ -37,6 +37,7 @@ struct WavefrontState {
     RenderPlan plan;
     uint32_t shadeInstances = 0, shadeMaterials = 0;   // records of SceneView::instShade / materials (set by the owner of the scene; 0 = unknown: no LDS tables)
     WavefrontKnobs knobs;
+    uint32_t cus = 0;                  // compute units of the context's device (0: not asked yet)
     bool profile = false;              // record HIP events around every extend / shade / shadow launch (HRPT_FRAME_PROFILE)
     // second stream + fork/join events: wf_shadow(b) overlaps wf_extend(b+1) (they share no buffer)
     hipStream_t auxStream = nullptr;

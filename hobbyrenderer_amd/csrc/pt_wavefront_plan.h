@@ -44,6 +44,7 @@ struct WavefrontKnobs {
     bool noFusedPrimary = false;       // HRPT_WF_FUSED_PRIMARY=0: SIMPLE scenes keep the wf_raygen pass (A/B knob)
     bool noSlimShadow = false;         // HRPT_WF_SLIM_SHADOW=0: the SIMPLE shade variant writes full 96-byte shadow-queue entries (A/B knob)
     int shadeSort = -1;                // HRPT_WF_SHADE_SORT = 0 / 1: general wf_shade variants shade in queue order / grouped by shading class (-1: automatic)
+    bool noFusedBounce0 = false;       // HRPT_WF_FUSED_BOUNCE0=0: bounce 0 keeps the wf_extend<PRIMARY> + wf_shade<PRIMARY> pair where wf_bounce0 would run (A/B knob)
     bool noShadeLdsTables = false;     // HRPT_WF_SHADE_LDS_TABLES=0: wf_shade gathers triangle / instance / material records from global memory even when they fit LDS (A/B knob)
     int shadowPath = 0;                // scenes with non-opaque geometry: 0 = automatic, 1 = wf_shadow traverses itself (buffered query), 2 = any-hit pass + resolve
 };
@@ -81,11 +82,18 @@ constexpr size_t kShadeLdsPerBlock = kCuLdsBytes / kShadeBlocksPerCu - kShadeLds
 // Records of the three tables the shading path gathers from (pt_device.h GpuTriAttr, GpuInstShade; hobbyrt_pt.h HrptMaterialConstants;
 // pt_wavefront.hip asserts the sizes). wf_shade_lt copies them whole, in their global layout, behind the ring.
 constexpr size_t kTriAttrBytes = 80, kInstShadeBytes = 48, kMaterialBytes = 180;
-inline size_t shade_table_bytes(uint32_t triCount, uint32_t instanceCount, uint32_t materialCount)
+constexpr size_t shade_table_bytes(uint32_t triCount, uint32_t instanceCount, uint32_t materialCount)
 {
     const size_t b = (size_t)triCount * kTriAttrBytes + (size_t)instanceCount * kInstShadeBytes + (size_t)materialCount * kMaterialBytes;
     return (b + 15) & ~(size_t)15;
 }
+// wf_bounce0: trace and shade of bounce 0 in one kernel, at wf_shade's four blocks per CU. Its block holds what both halves hold -- traversal
+// stack, specular ring, shading tables, tree copy, in this order -- so the ring is halved to 32 entries per wave (with 64 the Cornell-class block
+// is 23.5 + 5.3 + 16 + 3.5 KB: too much). The tables are padded to 128 bytes: the tree copy behind them must start 128-byte aligned (setup_lds).
+constexpr uint32_t kBounce0Ring = 32;
+constexpr size_t kBounce0RingBytes = (size_t)(kBlock / 64) * kBounce0Ring * kShadeRingFields * 4;
+static_assert(kBounce0RingBytes % 128 == 0, "the tree copy behind ring and tables starts 128-byte aligned");
+constexpr size_t bounce0_shade_bytes(size_t tableBytes) { return kBounce0RingBytes + ((tableBytes + 127) & ~(size_t)127); }     // between stack and tree
 // wf_shadow
 // MODE kShadowOpaque: no ForceNonOpaque instance in the scene: plain any-hit query per light sample.
 // MODE kShadowBuffered: non-opaque geometry, the kernel traverses itself: per-lane candidate buffer in LDS (after the stack) and the buffered query.
@@ -140,6 +148,8 @@ struct RenderPlan {
     bool shadeLdsTables = false;       // wf_shade_lt: triangle, instance and material records are served from a per-block LDS copy
     size_t shadeTableBytes = 0;        // ... which takes so many bytes (0 when the tables stay in global memory)
     size_t shadeLdsBytes = 0;          // dynamic LDS of the SIMPLE shade launches: the ring + shadeTableBytes (the general variants size their sort tables per batch)
+    bool fusedBounce0 = false;         // bounce 0 runs wf_bounce0 instead of wf_extend<PRIMARY> + wf_shade_lt<PRIMARY>
+    size_t bounce0LdsBytes = 0;        // ... launched with so much dynamic LDS: vE's stack and tree + the 32-entry ring + the padded tables (0 when off)
 };
 struct BatchPlan { uint32_t segSize, numSegments, grid, gridExtend; };
 
@@ -225,6 +235,14 @@ inline RenderPlan plan_render(const SceneTraits& traits, const TreeCounts& tree,
         if (kShadeRingBytes + tables <= kShadeLdsPerBlock) { p.shadeLdsTables = true; p.shadeTableBytes = tables; p.shadeLdsBytes = kShadeRingBytes + tables; }
     }
     p.fusedPrimary = p.simpleScene && !manyLights && maxLights <= kMaxLights && p.vE.width == 4 && !traits.hasMedium && !traits.hasStochasticAlpha && !k.noFusedPrimary;
+    // Bounce 0 in one kernel (wf_bounce0). Primary rays are coherent (lane utilisation 0.91 / 0.92 in the two kernels against 0.60 / 0.74 at the
+    // other bounces), yet the pair hands every sample's hit and {direction, seed} record through HBM. Where the bounce-0 pair is
+    // wf_extend<LDS, OPQ, PRIMARY> + wf_shade_lt<1, SIMPLE, PRIMARY> -- tree and tables in LDS, every instance opaque, one light -- and one block
+    // can hold the LDS of both, a wave traces 64 primary rays to completion and shades them from registers. HRPT_WF_FUSED_BOUNCE0=0 keeps the pair.
+    if (p.fusedPrimary && p.shadeLdsTables && p.vE.lds && p.vE.width == 4 && !traits.hasNonOpaque && !manyLights && !k.noFusedBounce0) {
+        const size_t bytes = p.vE.ldsBytes + bounce0_shade_bytes(p.shadeTableBytes);
+        if (bytes <= kShadeLdsPerBlock) { p.fusedBounce0 = true; p.bounce0LdsBytes = bytes; }
+    }
     return p;
 }
 
