@@ -168,6 +168,13 @@ HRT_DEV RayShear make_shear(f3 d)
     s.Sx = comp(d, kx) / dz; s.Sy = comp(d, ky) / dz; s.Sz = 1.0f / dz;
     return s;
 }
+// Every component finite (x - x is 0 for a finite x and NaN for +-inf and NaN). A caller's ray that is not gives a miss: with an infinite direction
+// component traversal_rcp returns 0, every plane is at distance 0 and the far-away box of an unused 4-wide slot passes the slab test -- its child
+// reference is no node (hrpt_trace_rays checks its rays with this before it walks; oracle/pt_oracle.c closest_any has the same rule).
+HRT_DEV bool all_finite(f3 o, f3 d)
+{
+    return (o.x - o.x) == 0.0f && (o.y - o.y) == 0.0f && (o.z - o.z) == 0.0f && (d.x - d.x) == 0.0f && (d.y - d.y) == 0.0f && (d.z - d.z) == 0.0f;
+}
 HRT_DEV bool key_less(float t, uint32_t inst, uint32_t prim, float t2, uint32_t inst2, uint32_t prim2)
 {
     if (t < t2) return true;

@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256) void pt_trace_rays_kernel(SceneView s, const H
     if constexpr (TL) { bvh.nodes = s.nodes4; bvh.tris = s.tris; bvh.instances = s.instances; } else { bvh.nodes = s.nodes; bvh.tris = s.tris; }
     PrivateStack stack;
     f3 o = mk3(r.origin[0], r.origin[1], r.origin[2]), d = mk3(r.direction[0], r.direction[1], r.direction[2]);
-    const bool finite = d.x == d.x && d.y == d.y && d.z == d.z && o.x == o.x && o.y == o.y && o.z == o.z;
+    const bool finite = all_finite(o, d);
     if (SHADOW) {
         out.t = finite ? shadow_query(s, bvh, o, d, r.tmax, stack) : 1.0f;     // visibility in [0, 1]
         out.hit = out.t < 1.0f ? 1u : 0u;

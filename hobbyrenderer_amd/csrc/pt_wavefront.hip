@@ -608,7 +608,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHADOW ?
                 const float4* rp = reinterpret_cast<const float4*>(a.rays + slot);           // 48-byte records: three 16-byte loads
                 const float4 q0 = rp[0], q1 = rp[1]; const uint32_t rr = reinterpret_cast<const uint32_t*>(rp + 2)[0];
                 const f3 o = mk3(q0.x, q0.y, q0.z), d = mk3(q1.x, q1.y, q1.z);
-                finite = d.x == d.x && d.y == d.y && d.z == d.z && o.x == o.x && o.y == o.y && o.z == o.z;
+                finite = all_finite(o, d);
                 if (SHADOW) r = shadow_ray(o, d, q1.w);                                        // the query applies its own bias; tmax = distance to the light
                 else { r.o = o; r.d = d; r.tmin = q0.w; r.tmax = q1.w; }
                 rng = rr; blocked = false; candOverflow = false; candCount = 0; lower.have = false; best.valid = false; tlim = r.tmax; sp = 0;

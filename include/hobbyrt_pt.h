@@ -398,6 +398,8 @@ int  hrpt_allgather(HrptContext* const* ranks, int n);
  *   HRPT_RAYS_SHADOW   CalculateRTShadow<true> (src/shaders/CommonLighting.hlsli:380-496): origin = shaded point, direction = L,
  *                      tmax = distance to the light; the visibility in [0, 1] comes back in HrptRayHit::t (tmin is ignored:
  *                      the query applies its own 0.01 bias)
+ * A ray with a NaN or infinite origin or direction component is a miss (hit == 0, visibility 1) and is not traced. Finite rays are expected
+ * to keep direction components below about 1e20 and tmax * |direction| below 1e29 (what the far-away boxes of unused node slots allow).
  * rays / hits are host arrays unless HRPT_RAYS_DEVICE_POINTERS is set (then both are device pointers and the call is asynchronous
  * on the context stream). */
 typedef struct HrptRay    { float origin[3]; float tmin; float direction[3]; float tmax; uint32_t rng; uint32_t pad[3]; } HrptRay;       /* 48 B */

@@ -369,7 +369,9 @@ static Hit closest_any(const OrContext* c, const Ray* r, int haveLower, float lt
 {
     Hit best; memset(&best, 0, sizeof best);
     if (c->triCount == 0) return best;
-    if (!(r->d.x == r->d.x && r->d.y == r->d.y && r->d.z == r->d.z)) return best; /* NaN direction: no hits */
+    /* a ray with a NaN or infinite component has no hits (pt_device.h all_finite: the kernels do not walk with it) */
+    if (!((r->d.x - r->d.x) == 0.0f && (r->d.y - r->d.y) == 0.0f && (r->d.z - r->d.z) == 0.0f &&
+          (r->o.x - r->o.x) == 0.0f && (r->o.y - r->o.y) == 0.0f && (r->o.z - r->o.z) == 0.0f)) return best;
     RayShear s = make_shear(r->d);
     if (brute) {
         for (uint32_t i = 0; i < c->triCount; i++) { tc->tris++; consider(c, i, r, &s, haveLower, lt, linst, lprim, &best); }
