@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -61,6 +62,8 @@ struct HrptContext {
     float4* dTemporal[2] = {}; int temporalCur = 0; bool temporalValid = false;
     // denoise (hrpt_denoise): the default noise tile (uploaded by the first denoise call of the context) and the scratch pair of HRPT_DENOISE_OUTPUT_ONLY
     float* dDenoiseTile = nullptr; float4* dDenoiseScratch[2] = {};
+    // demodulate / compose (hrpt_demodulate): the stored factor, allocated by the first hrpt_demodulate, dropped by hrpt_resize
+    float4* dModulation = nullptr;
     DeviceCounters* dCounters = nullptr;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
@@ -215,6 +218,7 @@ void hrpt_destroy(HrptContext* c)
     for (float4* image : c->dTemporal) if (image) (void)hipFree(image);
     for (float4* image : c->dDenoiseScratch) if (image) (void)hipFree(image);
     if (c->dDenoiseTile) (void)hipFree(c->dDenoiseTile);
+    if (c->dModulation) (void)hipFree(c->dModulation);
     if (c->dHistogram) (void)hipFree(c->dHistogram);
     if (c->dExposure) (void)hipFree(c->dExposure);
     if (c->dBloomDown) (void)hipFree(c->dBloomDown);
@@ -730,6 +734,7 @@ int hrpt_resize(HrptContext* c, uint32_t width, uint32_t height)
         HIP_TRY(c, hipMemsetAsync(image, 0, bytes, c->stream));
     }
     for (float4*& image : c->dDenoiseScratch) if (image) { (void)hipFree(image); image = nullptr; }     // allocated again by the call that needs it
+    if (c->dModulation) { (void)hipFree(c->dModulation); c->dModulation = nullptr; }                     // written again by the next hrpt_demodulate
     c->width = width; c->height = height;
     return HRPT_OK;
 }
@@ -1394,6 +1399,26 @@ static int denoise_tile(HrptContext* c)
     return HRPT_OK;
 }
 
+int hrpt_set_denoise_noise(HrptContext* c, const float* hostTile)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    const size_t count = denoise_noise_floats();
+    std::vector<float> tile(count);
+    if (hostTile) {
+        for (size_t i = 0; i < count; ++i) {
+            if (!std::isfinite(hostTile[i])) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_set_denoise_noise: the tile holds a value that is not finite");
+            tile[i] = hostTile[i];
+        }
+    } else denoise_default_tile(tile.data());
+    HIP_TRY(c, hipSetDevice(c->device));
+    int r = denoise_tile(c);
+    if (r != HRPT_OK) return r;
+    // on the context stream: passes enqueued before this call still read the old tile. The source is pageable and local, so wait for the copy.
+    HIP_TRY(c, hipMemcpyAsync(c->dDenoiseTile, tile.data(), count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HRPT_OK;
+}
+
 int hrpt_denoise_host(const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view, const HrptDenoiseParams* p, int nthreads)
 {
     int r = denoise_check(nullptr, "hrpt_denoise_host", img, width, height, view, p, true);
@@ -1458,6 +1483,152 @@ int hrpt_denoise(HrptContext* c, const HrptPlanarViewConstants* view, const Hrpt
         img.input = reinterpret_cast<const float*>(dst);
         if (!outputOnly) { cur = 1 - cur; c->temporalCur = cur; }
     }
+    return HRPT_OK;
+}
+
+// ---- demodulate / compose (pt_modulation.h / pt_modulation.hip) ----
+static bool size_ok(uint32_t width, uint32_t height) { return !(width == 0 || height == 0 || width > 65535u || height > 65535u); }
+
+static int demodulate_check(HrptContext* c, const char* what, const HrptDemodulateImages* img, uint32_t width, uint32_t height,
+                            const HrptPlanarViewConstants* view, const HrptModulationParams* p)
+{
+    const std::string w(what);
+    if (!img || !view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->color || !img->albedo || !img->normal || !img->geoNormal || !img->depth || !img->colorOut || !img->modulationOut)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only emissive may be NULL)");
+    const float* inputs[6] = { img->color, img->albedo, img->normal, img->geoNormal, img->depth, img->emissive };
+    for (const float* in : inputs)
+        if (in && img->modulationOut == in) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": modulationOut must differ from every input");
+    if (img->modulationOut == img->colorOut) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": modulationOut must differ from colorOut");
+    for (int i = 1; i < 6; ++i)
+        if (inputs[i] && img->colorOut == inputs[i]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": colorOut may equal color, but no other input");
+    if (!size_ok(width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
+    if (!(view->m_ViewportSize[0] == (float)width && view->m_ViewportSize[1] == (float)height))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
+    if (!modulation_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": floor must be finite and > 0, flags 0, reserved 0");
+    return HRPT_OK;
+}
+
+static int compose_check(HrptContext* c, const char* what, const HrptComposeImages* img, uint32_t width, uint32_t height)
+{
+    const std::string w(what);
+    if (!img) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->color || !img->modulation || !img->colorOut) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only emissive may be NULL)");
+    if (img->colorOut == img->modulation || (img->emissive && img->colorOut == img->emissive))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": colorOut may equal color, but not modulation or emissive");
+    if (!size_ok(width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
+    return HRPT_OK;
+}
+
+static int host_threads(int nthreads)
+{
+    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
+    if (nthreads < 1) nthreads = 1;
+    return nthreads > 256 ? 256 : nthreads;
+}
+
+int hrpt_demodulate_host(const HrptDemodulateImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                         const HrptModulationParams* p, int nthreads)
+{
+    int r = demodulate_check(nullptr, "hrpt_demodulate_host", img, width, height, view, p);
+    if (r != HRPT_OK) return r;
+    try { demodulate_host(*img, width, height, *view, *p, host_threads(nthreads)); }
+    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_demodulate_host: out of memory"); }
+    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_demodulate_host: ") + e.what()); }
+    return HRPT_OK;
+}
+
+int hrpt_compose_host(const HrptComposeImages* img, uint32_t width, uint32_t height, int nthreads)
+{
+    int r = compose_check(nullptr, "hrpt_compose_host", img, width, height);
+    if (r != HRPT_OK) return r;
+    try { compose_host(*img, width, height, host_threads(nthreads)); }
+    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_compose_host: out of memory"); }
+    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_compose_host: ") + e.what()); }
+    return HRPT_OK;
+}
+
+int hrpt_demodulate_device(HrptContext* c, const HrptDemodulateImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                           const HrptModulationParams* p, void* stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    int r = demodulate_check(c, "hrpt_demodulate_device", img, width, height, view, p);
+    if (r != HRPT_OK) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_demodulate(*img, width, height, *view, *p, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+}
+
+int hrpt_compose_device(HrptContext* c, const HrptComposeImages* img, uint32_t width, uint32_t height, void* stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    int r = compose_check(c, "hrpt_compose_device", img, width, height);
+    if (r != HRPT_OK) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_compose(*img, width, height, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+}
+
+int hrpt_demodulate(HrptContext* c, const HrptPlanarViewConstants* view, const HrptModulationParams* p)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_demodulate: null argument");
+    if (!c->dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_demodulate: hrpt_resize not called");
+    static const struct { int plane; const char* name; } needed[5] = { { HRPT_GB_ALBEDO, "HRPT_GB_ALBEDO" }, { HRPT_GB_NORMAL, "HRPT_GB_NORMAL" },
+        { HRPT_GB_GEO_NORMAL, "HRPT_GB_GEO_NORMAL" }, { HRPT_GB_EMISSIVE, "HRPT_GB_EMISSIVE" }, { HRPT_GB_DEPTH, "HRPT_GB_DEPTH" } };
+    for (const auto& n : needed)
+        if (!c->dGBuffer[n.plane])
+            return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_demodulate: the plane ") + n.name + " was never requested (hrpt_render_motion_vectors or hrpt_render_gbuffer with planeMask = ALBEDO | NORMAL | GEO_NORMAL | EMISSIVE | DEPTH fills them)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HrptDemodulateImages img{};
+    img.color = reinterpret_cast<const float*>(c->dOutput); img.colorOut = reinterpret_cast<float*>(c->dOutput);
+    img.albedo = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_ALBEDO]); img.normal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_NORMAL]);
+    img.geoNormal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_GEO_NORMAL]); img.depth = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_DEPTH]);
+    img.emissive = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_EMISSIVE]);
+    // validate before anything is allocated; a placeholder stands for the modulation image (a context image that is none of the others)
+    img.modulationOut = reinterpret_cast<float*>(c->dModulation ? c->dModulation : c->dAccum);
+    int r = demodulate_check(c, "hrpt_demodulate", &img, c->width, c->height, view, p);
+    if (r != HRPT_OK) return r;
+    if (!c->dModulation) HIP_TRY(c, hipMalloc((void**)&c->dModulation, (size_t)c->width * c->height * sizeof(float4)));
+    img.modulationOut = reinterpret_cast<float*>(c->dModulation);
+    HIP_TRY(c, launch_demodulate(img, c->width, c->height, *view, *p, c->stream));
+    return HRPT_OK;
+}
+
+int hrpt_compose(HrptContext* c)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_compose: hrpt_resize not called");
+    if (!c->dModulation)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_compose: no modulation image at the current size (hrpt_demodulate writes the factor this stage multiplies back in)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HrptComposeImages img{};
+    img.color = reinterpret_cast<const float*>(c->dOutput); img.colorOut = reinterpret_cast<float*>(c->dOutput);
+    img.modulation = reinterpret_cast<const float*>(c->dModulation);
+    img.emissive = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_EMISSIVE]);      // set: hrpt_demodulate required it, and a resize drops the modulation image
+    HIP_TRY(c, launch_compose(img, c->width, c->height, c->stream));
+    return HRPT_OK;
+}
+
+int hrpt_read_modulation(HrptContext* c, float* dst, size_t bytes)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->dModulation) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_modulation: no modulation image at the current size (hrpt_demodulate writes it)");
+    return read_image(c, c->dModulation, dst, bytes, "hrpt_read_modulation");
+}
+
+int hrpt_get_modulation_device(HrptContext* c, void** devicePtr)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_modulation_device: null out");
+    *devicePtr = c->dModulation;
+    return HRPT_OK;
+}
+
+int hrpt_modulation_probe(const float* albedo3, const float* N3, const float* V3, float rough, float metal, float floor, float* outM3)
+{
+    if (!albedo3 || !N3 || !V3 || !outM3) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_modulation_probe: null argument");
+    modulation_probe(albedo3, N3, V3, rough, metal, floor, outM3);
     return HRPT_OK;
 }
 

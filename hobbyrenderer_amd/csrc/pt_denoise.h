@@ -16,8 +16,10 @@
 //
 // Differences from the reference pass, on purpose:
 //   * a miss (depth.x == 1e10f) passes its input texel through; the reference writes 0. Here Output holds the sky at a miss and keeps it.
-//   * the noise tile is an input. The reference reads a 64 x 64 blue-noise texture its tree does not ship; where the caller passes none,
-//     default_tile() below is used, which is WHITE noise (the path tracer's PCG stream per texel), not blue noise.
+//   * the noise tile is an input. The reference reads a 64 x 64 blue-noise texture that its tree ships as a data file
+//     (external/LDR_RG01_0.png, src/CommonResources.cpp:575); the library may not embed that file, so where the caller passes no tile (and
+//     has set none with hrpt_set_denoise_noise) default_tile_texel() below is used, which is WHITE noise (the path tracer's PCG stream per
+//     texel), not blue noise. The caller's own copy of the reference's tile gives the reference's behaviour.
 // Not restated: the separate specular image with w2, m_SpecularPhi and specularFactor (one radiance image; it plays both signals in the
 // age falloff's a + a2), and DecodeNormal (the plane already holds unit vectors).
 #pragma once

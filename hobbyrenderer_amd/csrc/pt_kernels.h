@@ -81,6 +81,18 @@ hipError_t launch_denoise(const HrptDenoiseImages& images, uint32_t width, uint3
 void denoise_host(const HrptDenoiseImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
                   const HrptDenoiseParams& params, int nthreads);
 
+// Demodulate / compose (pt_modulation.hip; arithmetic in pt_modulation.h): one kernel each over width x height device images; emissive may be
+// null. demodulate_host / compose_host (pt_modulation_host.cpp): the same arithmetic on host threads. colorOut may be color; modulationOut
+// aliases nothing. modulation_probe: the factor of one hit with the view vector given (test hook).
+bool modulation_params_valid(const HrptModulationParams& params);
+hipError_t launch_demodulate(const HrptDemodulateImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+                             const HrptModulationParams& params, hipStream_t stream);
+hipError_t launch_compose(const HrptComposeImages& images, uint32_t width, uint32_t height, hipStream_t stream);
+void demodulate_host(const HrptDemodulateImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+                     const HrptModulationParams& params, int nthreads);
+void compose_host(const HrptComposeImages& images, uint32_t width, uint32_t height, int nthreads);
+void modulation_probe(const float* albedo3, const float* N3, const float* V3, float rough, float metal, float floor, float* outM3);
+
 // Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
 hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
 

@@ -35,7 +35,9 @@ EXPORTS = [
     "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
     "hrpt_temporal_host", "hrpt_temporal_device", "hrpt_temporal_accumulate", "hrpt_read_temporal_history", "hrpt_get_temporal_history_device",
     "hrpt_clear_accumulation",
-    "hrpt_denoise_host", "hrpt_denoise_device", "hrpt_denoise",
+    "hrpt_denoise_host", "hrpt_denoise_device", "hrpt_denoise", "hrpt_set_denoise_noise",
+    "hrpt_demodulate_host", "hrpt_compose_host", "hrpt_demodulate_device", "hrpt_compose_device", "hrpt_demodulate", "hrpt_compose",
+    "hrpt_read_modulation", "hrpt_get_modulation_device", "hrpt_modulation_probe",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
 ]
 
@@ -97,6 +99,16 @@ lib.hrpt_clear_accumulation.argtypes = [C.c_void_p]
 lib.hrpt_denoise_host.argtypes = [C.POINTER(S.DenoiseImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.DenoiseParams), C.c_int]
 lib.hrpt_denoise_device.argtypes = [C.c_void_p, C.POINTER(S.DenoiseImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.DenoiseParams), C.c_void_p]
 lib.hrpt_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(S.DenoiseParams)]
+lib.hrpt_set_denoise_noise.argtypes = [C.c_void_p, C.c_void_p]
+lib.hrpt_demodulate_host.argtypes = [C.POINTER(S.DemodulateImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.ModulationParams), C.c_int]
+lib.hrpt_compose_host.argtypes = [C.POINTER(S.ComposeImages), C.c_uint32, C.c_uint32, C.c_int]
+lib.hrpt_demodulate_device.argtypes = [C.c_void_p, C.POINTER(S.DemodulateImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.ModulationParams), C.c_void_p]
+lib.hrpt_compose_device.argtypes = [C.c_void_p, C.POINTER(S.ComposeImages), C.c_uint32, C.c_uint32, C.c_void_p]
+lib.hrpt_demodulate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(S.ModulationParams)]
+lib.hrpt_compose.argtypes = [C.c_void_p]
+lib.hrpt_read_modulation.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+lib.hrpt_get_modulation_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+lib.hrpt_modulation_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]
 lib.hrpt_halton.argtypes = [C.c_uint32, C.c_uint32]
 lib.hrpt_halton.restype = C.c_float
 lib.hrpt_precompute_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -235,6 +247,70 @@ def denoise_host(input, depth, normal, geo_normal, view, params=None, noise=None
     if rc != 0:
         raise HrptError(rc, lib.hrpt_last_error(None).decode())
     return out if cout is None else (out, cout)
+
+
+def noise_tile_from_png(path):
+    """A float32 [64, 64, 2] noise tile for denoise_host / PathTracerContext.set_denoise_noise from a 64 x 64 PNG, decoded through the
+    library's own PNG decoder: tile[y][x] = (R / 255, G / 255), one correctly rounded binary32 division each. The reference's blue-noise
+    tile is its data file external/LDR_RG01_0.png (tests/golden/blue_noise_rg_64.png is a copy)."""
+    from . import scene_io
+    with open(path, "rb") as f:
+        rgba = scene_io.decode_image(f.read())
+    if rgba.shape != (64, 64, 4):
+        raise ValueError(f"noise_tile_from_png: a 64 x 64 image expected, got {rgba.shape[1]} x {rgba.shape[0]}")
+    return np.ascontiguousarray(rgba[..., :2].astype(np.float32) / np.float32(255.0))
+
+
+def demodulate_host(color, albedo, normal, geo_normal, depth, view, params=None, emissive=None, nthreads=0):
+    """hrpt_demodulate_host: the demodulate stage (csrc/pt_modulation.h) on host threads over float32 [H, W, 4]
+    images; needs no GPU and is bit-identical to PathTracerContext.demodulate / demodulate_device. color: Output of a render; albedo /
+    normal / geo_normal / depth / emissive: the planes S.GB_ALBEDO / S.GB_NORMAL / S.GB_GEO_NORMAL / S.GB_DEPTH / S.GB_EMISSIVE of the same
+    frame (emissive None = 0). view: as for temporal_host. Returns (colour out, modulation): colour out = (max(rgb - E, 0) / Mf, alpha),
+    modulation = (Mf, 1) at a hit and (1, 1, 1, 0) at a miss."""
+    imgs = [np.ascontiguousarray(a, np.float32) for a in (color, albedo, normal, geo_normal, depth)]
+    shape = imgs[0].shape
+    if len(shape) != 3 or shape[2] != 4 or any(a.shape != shape for a in imgs):
+        raise ValueError("demodulate_host: five float32 [H, W, 4] images of one size expected")
+    em = None if emissive is None else np.ascontiguousarray(emissive, np.float32)
+    if em is not None and em.shape != shape:
+        raise ValueError("demodulate_host: emissive must have the images' shape")
+    params = params if params is not None else S.ModulationParams()
+    out, mod = np.empty(shape, np.float32), np.empty(shape, np.float32)
+    im = S.DemodulateImages(*[a.ctypes.data for a in imgs], None if em is None else em.ctypes.data, out.ctypes.data, mod.ctypes.data)
+    v = _view_record(view)
+    rc = lib.hrpt_demodulate_host(C.byref(im), shape[1], shape[0], v.ctypes.data, C.byref(params), int(nthreads))
+    if rc != 0:
+        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    return out, mod
+
+
+def compose_host(color, modulation, emissive=None, nthreads=0):
+    """hrpt_compose_host: the compose stage on host threads: (rgb * Mf + E, alpha) with Mf from `modulation` (what demodulate_host
+    returned); a texel whose modulation alpha is 0 (a miss) passes through. Bit-identical to PathTracerContext.compose / compose_device."""
+    imgs = [np.ascontiguousarray(a, np.float32) for a in (color, modulation)]
+    shape = imgs[0].shape
+    if len(shape) != 3 or shape[2] != 4 or imgs[1].shape != shape:
+        raise ValueError("compose_host: two float32 [H, W, 4] images of one size expected")
+    em = None if emissive is None else np.ascontiguousarray(emissive, np.float32)
+    if em is not None and em.shape != shape:
+        raise ValueError("compose_host: emissive must have the images' shape")
+    out = np.empty(shape, np.float32)
+    im = S.ComposeImages(imgs[0].ctypes.data, imgs[1].ctypes.data, None if em is None else em.ctypes.data, out.ctypes.data)
+    rc = lib.hrpt_compose_host(C.byref(im), shape[1], shape[0], int(nthreads))
+    if rc != 0:
+        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    return out
+
+
+def modulation_probe(albedo, normal, view_dir, rough, metal, floor=0.04):
+    """Test hook (hrpt_modulation_probe): the factor Mf of one hit, float32 [3], for an albedo, a unit normal and a unit vector towards the
+    camera given directly instead of reconstructed from a depth."""
+    a, n, v = [np.ascontiguousarray(x, np.float32).reshape(3) for x in (albedo, normal, view_dir)]
+    out = np.empty(3, np.float32)
+    rc = lib.hrpt_modulation_probe(a.ctypes.data, n.ctypes.data, v.ctypes.data, float(rough), float(metal), float(floor), out.ctypes.data)
+    if rc != 0:
+        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    return out
 
 
 _BVH_DUMP_ARRAYS = (("nodes", S.GpuNode, "nodeCount"), ("nodes4", S.GpuNode4, "node4Count"), ("nodesQ", S.GpuNodeQ, "node4Count"),
@@ -542,6 +618,54 @@ class PathTracerContext:
         params = params if params is not None else S.DenoiseParams()
         v = _view_record(view)
         self._check(lib.hrpt_denoise_device(self._h, C.byref(images), int(width), int(height), v.ctypes.data, C.byref(params), C.c_void_p(int(hip_stream))))
+
+    def set_denoise_noise(self, tile):
+        """hrpt_set_denoise_noise: the float32 [64, 64, 2] noise tile that denoise, and denoise_device without a tile, use from now on (e.g.
+        native.noise_tile_from_png of the reference's blue-noise file); None restores the built-in default tile (white noise)."""
+        if tile is None:
+            self._check(lib.hrpt_set_denoise_noise(self._h, None))
+            return
+        t = np.ascontiguousarray(tile, np.float32)
+        if t.shape != (64, 64, 2):
+            raise ValueError("set_denoise_noise: a float32 [64, 64, 2] tile expected")
+        self._check(lib.hrpt_set_denoise_noise(self._h, t.ctypes.data))
+
+    def demodulate(self, view, params=None):
+        """hrpt_demodulate: divides the first-hit BRDF factor out of Output, in place, and keeps the factor in a context image
+        (csrc/pt_modulation.h). After render and render_motion_vectors / render_gbuffer with the planes S.GB_ALBEDO,
+        S.GB_NORMAL, S.GB_GEO_NORMAL, S.GB_EMISSIVE and S.GB_DEPTH of this frame, before temporal_accumulate. view: as for
+        temporal_accumulate. Asynchronous."""
+        params = params if params is not None else S.ModulationParams()
+        v = _view_record(view)
+        self._check(lib.hrpt_demodulate(self._h, v.ctypes.data, C.byref(params)))
+
+    def compose(self):
+        """hrpt_compose: multiplies the factor the last demodulate stored back into Output and adds the emissive plane, in place; after
+        denoise, before bloom. Asynchronous."""
+        self._check(lib.hrpt_compose(self._h))
+
+    def demodulate_device(self, images, width, height, view, params=None, hip_stream=0):
+        """The demodulate stage over caller-owned device images (S.DemodulateImages of device addresses; emissive None = 0), asynchronously
+        on `hip_stream` (integer handle). colorOut may be color; modulationOut must differ from every other image."""
+        params = params if params is not None else S.ModulationParams()
+        v = _view_record(view)
+        self._check(lib.hrpt_demodulate_device(self._h, C.byref(images), int(width), int(height), v.ctypes.data, C.byref(params), C.c_void_p(int(hip_stream))))
+
+    def compose_device(self, images, width, height, hip_stream=0):
+        """The compose stage over caller-owned device images (S.ComposeImages of device addresses), asynchronously on `hip_stream`."""
+        self._check(lib.hrpt_compose_device(self._h, C.byref(images), int(width), int(height), C.c_void_p(int(hip_stream))))
+
+    def read_modulation(self):
+        """The factor image the last demodulate wrote: float32 [H, W, 4], rgb = Mf, a = 1 at a hit, 0 at a miss (synchronises)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(lib.hrpt_read_modulation(self._h, out.ctypes.data, out.nbytes))
+        return out
+
+    def modulation_device(self):
+        """Device pointer of that image (None before the first demodulate and after a resize)."""
+        ptr = C.c_void_p()
+        self._check(lib.hrpt_get_modulation_device(self._h, C.byref(ptr)))
+        return ptr.value
 
     def read_display(self):
         out = np.empty((self.height, self.width, 4), np.float32)

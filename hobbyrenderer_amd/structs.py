@@ -162,6 +162,25 @@ class DenoiseImages(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("input", "depth", "normal", "geoNormal", "noise", "output", "color", "colorOut")]
 
 
+class ModulationParams(C.Structure):
+    """HrptModulationParams; floor is the lower bound of every channel of the factor the demodulate stage divides by (default 0.04: the
+    least value a non-metal's factor takes, so it only bites on dark metals)."""
+    _fields_ = [("floor", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, floor=0.04, flags=0):
+        super().__init__(floor, flags, (C.c_uint32 * 2)(0, 0))
+
+
+class DemodulateImages(C.Structure):
+    """HrptDemodulateImages: host or device addresses of width x height float4 images; emissive may be None (= 0); colorOut may be color."""
+    _fields_ = [(n, C.c_void_p) for n in ("color", "albedo", "normal", "geoNormal", "depth", "emissive", "colorOut", "modulationOut")]
+
+
+class ComposeImages(C.Structure):
+    """HrptComposeImages: host or device addresses of width x height float4 images; emissive may be None (= 0); colorOut may be color."""
+    _fields_ = [(n, C.c_void_p) for n in ("color", "modulation", "emissive", "colorOut")]
+
+
 class Stats(C.Structure):
     _fields_ = [("closestRays", C.c_uint64), ("shadowRays", C.c_uint64), ("paths", C.c_uint64),
                 ("lastRenderMs", C.c_float), ("traceKernelMs", C.c_float), ("traceKernelLaunches", C.c_uint32),

@@ -575,7 +575,8 @@ int  hrpt_temporal_device(HrptContext* ctx, const HrptTemporalImages* deviceImag
  * after a resize and a call with HRPT_TEMPORAL_RESET run without history. Asynchronous on the context stream, ordered with renders,
  * honours hrpt_set_stream. Accumulation, the planes, exposure and HrptStats are not touched; every render re-resolves Output, so the
  * stage never feeds back into the accumulation. Frame order:
- *   hrpt_clear_accumulation -> hrpt_render -> hrpt_render_motion_vectors -> hrpt_temporal_accumulate -> hrpt_bloom -> hrpt_post_process
+ *   hrpt_clear_accumulation -> hrpt_render -> hrpt_render_motion_vectors -> [hrpt_demodulate] -> hrpt_temporal_accumulate -> [hrpt_denoise]
+ *   -> [hrpt_compose] -> hrpt_bloom -> hrpt_post_process
  * A motion, depth or normal plane that was never requested, and the argument errors of hrpt_temporal_host: HRPT_ERR_INVALID_ARGUMENT. */
 int  hrpt_temporal_accumulate(HrptContext* ctx, const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptTemporalParams* params);
 /* Host read-back of the history the last hrpt_temporal_accumulate wrote (synchronises); bytes must be width*height*16. Before the first
@@ -598,9 +599,11 @@ int  hrpt_get_temporal_history_device(HrptContext* ctx, void** devicePtr);
  *   color / colorOut   both NULL or both set: colorOut = (filtered rgb, color.a). colorOut may equal color; neither may equal input.
  * Differences from the reference, on purpose: a miss passes its input texel through (the reference writes 0; here Output holds the sky
  * there); one radiance image, so the separate specular signal (w2, m_SpecularPhi, specularFactor) is not restated, and the image plays both
- * signals in the age falloff; the planes hold unit normals, so there is no DecodeNormal. The reference's blue-noise texture is not part of
- * its tree: the tile is an input, and with noise == NULL the library uses its default tile, texel (x, y) = the first two numbers of
- * hrt_rng_seed(x, y, 0) -- WHITE noise, not blue noise. A caller that has a blue-noise tile passes it.
+ * signals in the age falloff; the planes hold unit normals, so there is no DecodeNormal. The noise tile is an input. The reference ships its
+ * 64 x 64 blue-noise texture as a data file (external/LDR_RG01_0.png, loaded by src/CommonResources.cpp:575); the library may not embed that
+ * file, so with noise == NULL it uses its built-in default tile, texel (x, y) = the first two numbers of hrt_rng_seed(x, y, 0) -- WHITE
+ * noise, not blue noise. A caller that has the reference's tile (or any other) passes it here, or installs it on a context with
+ * hrpt_set_denoise_noise, and gets the reference's behaviour.
  * view->m_ViewportSize must equal (width, height); view->m_CameraDirectionOrPosition.xyz must hold the camera position. Opt-in: nothing
  * calls it implicitly. Not part of multi-GPU tiles: it works on whole images, run it after the gather. */
 #define HRPT_DENOISE_OUTPUT_ONLY 1u   /* context call: filter Output only, leave the temporal history as the temporal stage wrote it */
@@ -635,7 +638,8 @@ int  hrpt_denoise_host(const HrptDenoiseImages* images, uint32_t width, uint32_t
 int  hrpt_denoise_device(HrptContext* ctx, const HrptDenoiseImages* deviceImages, uint32_t width, uint32_t height,
                          const HrptPlanarViewConstants* view, const HrptDenoiseParams* params, void* stream);
 /* The stage over the context's own images, after hrpt_temporal_accumulate: input = the temporal history, the planes HRPT_GB_DEPTH,
- * HRPT_GB_NORMAL and HRPT_GB_GEO_NORMAL as the caller filled them for this frame, the default tile. It runs params->iterations passes;
+ * HRPT_GB_NORMAL and HRPT_GB_GEO_NORMAL as the caller filled them for this frame, the context's noise tile (hrpt_set_denoise_noise; the
+ * default tile until it is called). It runs params->iterations passes;
  * pass i uses radius * (float)(1u << i) and frame * iterations + i (uint32, wrapping), and the last pass also writes Output as
  * (filtered rgb, Output.a). By default, as in the reference, the passes ping-pong between the two history images (the stale one is free
  * after the temporal call) and the filtered image BECOMES the history: the next hrpt_temporal_accumulate reprojects it, and
@@ -643,10 +647,84 @@ int  hrpt_denoise_device(HrptContext* ctx, const HrptDenoiseImages* deviceImages
  * what the temporal stage wrote and only Output is filtered (this keeps the exact running mean of HRPT_TEMPORAL_LINEAR); the passes then
  * use a library-owned scratch pair, allocated at first use and dropped by hrpt_resize. Asynchronous on the context stream, honours
  * hrpt_set_stream; Accumulation, the planes, exposure and HrptStats are not touched. Frame order:
- *   ... -> hrpt_temporal_accumulate -> hrpt_denoise -> hrpt_bloom -> hrpt_post_process
+ *   ... -> [hrpt_demodulate] -> hrpt_temporal_accumulate -> hrpt_denoise -> [hrpt_compose] -> hrpt_bloom -> hrpt_post_process
  * No valid temporal history at the current size (hrpt_temporal_accumulate not called since hrpt_resize), a depth, normal or geo-normal
  * plane that was never requested, and the argument errors of hrpt_denoise_host (iterations 1..5 here): HRPT_ERR_INVALID_ARGUMENT. */
 int  hrpt_denoise(HrptContext* ctx, const HrptPlanarViewConstants* view, const HrptDenoiseParams* params);
+/* Replaces the noise tile that hrpt_denoise, and hrpt_denoise_device with noise == NULL, use for this context: hostTile holds 64 * 64 * 2
+ * floats, hostTile[y][x][2]; NULL restores the built-in default tile. The copy is ordered on the context stream (calls enqueued before it
+ * see the old tile, calls after it the new one) and hostTile may be reused on return. Until it is called the behaviour is that of the
+ * default tile. A value that is not finite: HRPT_ERR_INVALID_ARGUMENT, and the tile in use stays. */
+int  hrpt_set_denoise_noise(HrptContext* ctx, const float* hostTile);
+
+/* ---- Demodulate / compose: keep textures out of the temporal and spatial filters -----------------------------------------------
+ * The two stages around hrpt_temporal_accumulate and hrpt_denoise. The reference never filters radiance: its SSGI passes run on a signal
+ * with the first-hit BRDF factored out, and its compose pass (src/shaders/SSGICompose.hlsl:75-107) multiplies albedo * (1 - metalness) *
+ * (1 - F) and F back in, F being a Schlick Fresnel term at a deterministic GGX half vector. The denoiser's edge stops (normal, plane
+ * distance, roughness, luminance) do not see albedo, so filtering radiance itself averages a texture away. hrpt_demodulate divides the
+ * factor out of the colour image and stores it; hrpt_compose multiplies the stored factor back in. Per pixel (the definition is
+ * hobbyrenderer_amd/csrc/pt_modulation.h), with E = emissive.rgb (0 without an emissive image):
+ *   miss (depth.x == 1e10f)   modulation = (1, 1, 1, 0); both stages pass the colour texel through bit for bit
+ *   hit                       M = albedo * (1 - metallic) * (1 - F) + F per channel, Mf = max(M, floor), modulation = (Mf, 1)
+ *   demodulate                colorOut = (max(color.rgb - E, 0) / Mf, color.a)
+ *   compose                   colorOut = (color.rgb * Mf + E, color.a), Mf read from `modulation` (a == 0 marks a miss)
+ * floor (finite, > 0; default 0.04, the least value a channel of M takes on a non-metal, so that it only bites on dark metals) bounds the
+ * amplification of the division. Both stages use the same Mf: where nothing was filtered compose undoes demodulate up to rounding
+ * (|compose(demodulate(x)) - x| <= 5 * 2^-24 * x for normal numbers with x >= E >= 0, 3 * 2^-24 * x when E == 0).
+ * All images are width x height float4: color = Output of hrpt_render; albedo, normal (roughness in .w), geoNormal (metallic in .w),
+ * emissive, depth = the planes HRPT_GB_ALBEDO, HRPT_GB_NORMAL, HRPT_GB_GEO_NORMAL, HRPT_GB_EMISSIVE, HRPT_GB_DEPTH of the same frame.
+ * view->m_ViewportSize must equal (width, height); view->m_CameraDirectionOrPosition.xyz must hold the camera position. Opt-in: nothing
+ * calls them implicitly. Not part of multi-GPU tiles: they work on whole images, run them after the gather. */
+typedef struct HrptModulationParams {
+    float floor;          /* lower bound of every channel of the factor; finite, > 0; default 0.04 */
+    uint32_t flags;       /* 0 */
+    uint32_t reserved[2]; /* 0 */
+} HrptModulationParams;
+typedef struct HrptDemodulateImages {
+    const float *color, *albedo, *normal, *geoNormal, *depth;
+    const float *emissive;      /* NULL = 0 */
+    float *colorOut;            /* may equal color; must differ from every other image */
+    float *modulationOut;       /* required; must differ from every other image */
+} HrptDemodulateImages;
+typedef struct HrptComposeImages {
+    const float *color, *modulation;
+    const float *emissive;      /* NULL = 0 */
+    float *colorOut;            /* may equal color; must differ from modulation and emissive */
+} HrptComposeImages;
+/* The stages on host threads over host images (no GPU needed; nthreads <= 0: one per hardware thread, at most 16). Bit-identical to the
+ * device calls. NULL arguments or images (emissive excepted), an output that equals an image it must differ from, a size outside
+ * 1..65535, m_ViewportSize != the size, floor not finite or <= 0, flags != 0, non-zero reserved: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_demodulate_host(const HrptDemodulateImages* images, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                          const HrptModulationParams* params, int nthreads);
+int  hrpt_compose_host(const HrptComposeImages* images, uint32_t width, uint32_t height, int nthreads);
+/* The same over caller-owned DEVICE images, asynchronous on the caller's stream (a hipStream_t; NULL = the default stream). */
+int  hrpt_demodulate_device(HrptContext* ctx, const HrptDemodulateImages* deviceImages, uint32_t width, uint32_t height,
+                            const HrptPlanarViewConstants* view, const HrptModulationParams* params, void* stream);
+int  hrpt_compose_device(HrptContext* ctx, const HrptComposeImages* deviceImages, uint32_t width, uint32_t height, void* stream);
+/* The stages over the context's own images. hrpt_demodulate: color = colorOut = Output, the planes HRPT_GB_ALBEDO, HRPT_GB_NORMAL,
+ * HRPT_GB_GEO_NORMAL, HRPT_GB_EMISSIVE and HRPT_GB_DEPTH as the caller filled them for this frame (hrpt_render_motion_vectors or
+ * hrpt_render_gbuffer with those five in planeMask), and a library-owned modulation image, allocated at first use and dropped by
+ * hrpt_resize. hrpt_compose: Output in place, from that image and the emissive plane. Both are asynchronous on the context stream, honour
+ * hrpt_set_stream, and touch neither Accumulation, the planes, the temporal history, exposure nor HrptStats. They are stateless otherwise,
+ * like hrpt_bloom: every render re-resolves Output, two hrpt_demodulate calls without a render in between divide twice, two hrpt_compose
+ * calls multiply twice. Frame order:
+ *   hrpt_clear_accumulation -> hrpt_render -> hrpt_render_motion_vectors -> hrpt_demodulate -> hrpt_temporal_accumulate -> hrpt_denoise
+ *   -> hrpt_compose -> hrpt_bloom -> hrpt_post_process
+ * (the temporal history then holds the demodulated signal, as the reference's does). hrpt_demodulate with one of the five planes never
+ * requested: HRPT_ERR_INVALID_ARGUMENT, the message names the plane. hrpt_compose with no modulation image at the current size
+ * (hrpt_demodulate not called since hrpt_resize): HRPT_ERR_INVALID_ARGUMENT, the message names hrpt_demodulate. The argument errors of
+ * hrpt_demodulate_host apply. */
+int  hrpt_demodulate(HrptContext* ctx, const HrptPlanarViewConstants* view, const HrptModulationParams* params);
+int  hrpt_compose(HrptContext* ctx);
+/* Host read-back of the modulation image the last hrpt_demodulate wrote (synchronises); bytes must be width*height*16. With no such image
+ * at the current size (before the first call, after a resize): HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_read_modulation(HrptContext* ctx, float* dst, size_t bytes);
+/* Device pointer of that image (valid until hrpt_resize / hrpt_destroy); NULL where hrpt_read_modulation would fail. */
+int  hrpt_get_modulation_device(HrptContext* ctx, void** devicePtr);
+/* Test hook (host only): the factor of one hit with the view vector given instead of reconstructed -- outM3 = Mf for albedo3, the unit
+ * normal N3, the unit vector V3 towards the camera, roughness, metallic and floor (pt_modulation.h factor()). It reaches branches that no
+ * camera produces reliably (N == V exactly, both tangent-frame choices, grazing and back-facing V). NULL pointers: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_modulation_probe(const float* albedo3, const float* N3, const float* V3, float rough, float metal, float floor, float* outM3);
 /* Zeroes the Accumulation image, asynchronously on the context stream: a fresh frame that starts at a non-zero accumulation index. A
  * following hrpt_render with first index k > 0 and accumCount s leaves Accumulation.a == s and Output = rgb / s of exactly the indices
  * k .. k + s - 1 (both kernel paths add onto the stored image whenever the index is > 0). A per-frame render at index 0 would instead
