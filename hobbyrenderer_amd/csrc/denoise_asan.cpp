@@ -4,13 +4,7 @@
 // negative radiance and age) sprinkled in; with the default and a caller tile, with and without the colour pair, in place, three chained
 // passes with a doubling radius, nthreads 1-3. Any out-of-bounds read, undefined float -> int conversion or other report ends the program
 // with a non-zero status.   usage: denoise_asan [seed]
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <vector>
-
+#include "asan_common.h"
 #include "pt_denoise.h"
 
 namespace hrt {
@@ -18,29 +12,10 @@ void denoise_host(const HrptDenoiseImages& images, uint32_t width, uint32_t heig
                   const HrptDenoiseParams& params, int nthreads);
 }
 
-static uint32_t g_state = 1;
-static float rnd() { g_state = hrt_pcg_hash(g_state); return (float)(g_state >> 8) * (1.0f / 16777216.0f); }
-
-static HrptPlanarViewConstants make_view(int w, int h)
-{
-    HrptPlanarViewConstants v;
-    std::memset(&v, 0, sizeof v);
-    const float n = 0.1f, sx = 1.2f, sy = 1.2f * (float)w / (float)h;
-    float* P = v.m_MatViewToClip;                   // reversed-Z, infinite far plane
-    P[0] = sx; P[5] = sy; P[11] = 1.0f; P[14] = n;
-    float* M = v.m_MatClipToWorld;                  // its inverse (camera at the origin of the world)
-    M[0] = 1.0f / sx; M[5] = 1.0f / sy; M[11] = 1.0f / n; M[14] = 1.0f;
-    v.m_ViewportSize[0] = (float)w; v.m_ViewportSize[1] = (float)h;
-    v.m_ViewportSizeInv[0] = 1.0f / (float)w; v.m_ViewportSizeInv[1] = 1.0f / (float)h;
-    v.m_CameraDirectionOrPosition[3] = 1.0f;
-    return v;
-}
-
 static int run(int w, int h, bool hostile)
 {
     const size_t n = (size_t)w * h * 4;
     std::vector<float> input(n), depth(n), normal(n), geo(n), color(n), outA(n), outB(n), colorOut(n), tile(hrt::denoise::kNoiseFloats);
-    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
     for (float& t : tile) t = rnd();
     for (int y = 0; y < h; ++y)
         for (int x = 0; x < w; ++x) {
@@ -53,12 +28,11 @@ static int run(int w, int h, bool hostile)
             geo[i] = 0.0f; geo[i + 1] = 0.6f; geo[i + 2] = -0.8f; geo[i + 3] = rnd() < 0.5f ? 0.0f : 1.0f;
             color[i] = rnd(); color[i + 1] = rnd(); color[i + 2] = rnd(); color[i + 3] = rnd();
             if (hostile && rnd() < 0.1f) {
-                const float bad[] = { nan, inf, -inf, 3e38f, -3e38f, 0.0f, -1.0f, 1e-42f };
                 float* planes[] = { input.data(), depth.data(), normal.data(), geo.data() };
-                planes[(int)(rnd() * 3.999f)][i + (int)(rnd() * 3.999f)] = bad[(int)(rnd() * 7.999f)];
+                planes[(int)(rnd() * 3.999f)][i + (int)(rnd() * 3.999f)] = kBad[(int)(rnd() * 7.999f)];
             }
         }
-    if (hostile) for (size_t i = 0; i < tile.size(); i += 5) if (rnd() < 0.05f) tile[i] = rnd() < 0.5f ? nan : -3e38f;
+    if (hostile) for (size_t i = 0; i < tile.size(); i += 5) if (rnd() < 0.05f) tile[i] = rnd() < 0.5f ? kNan : -3e38f;
     const HrptPlanarViewConstants view = make_view(w, h);
     int calls = 0;
     for (int variant = 0; variant < 4; ++variant) {
@@ -87,10 +61,9 @@ static int run(int w, int h, bool hostile)
 
 int main(int argc, char** argv)
 {
-    g_state = argc > 1 ? (uint32_t)std::strtoul(argv[1], nullptr, 10) : 1u;
+    seed_from(argc, argv);
     int calls = 0;
-    const int sizes[][2] = { { 1, 1 }, { 2, 3 }, { 37, 23 }, { 64, 36 } };
-    for (const auto& s : sizes)
+    for (const auto& s : kSizes)
         for (int hostile = 0; hostile < 2; ++hostile)
             calls += run(s[0], s[1], hostile != 0);
     std::printf("denoise_asan: %d calls, no report\n", calls);

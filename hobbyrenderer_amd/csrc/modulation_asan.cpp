@@ -3,13 +3,7 @@
 // images with random planes and hostile values sprinkled in (NaN, inf, huge, negative albedo, zero normals, view depth 0, negative
 // radiance), with and without the emissive image, in place and not, with three floors, nthreads 1-3. Any out-of-bounds access or other
 // report ends the program with a non-zero status.   usage: modulation_asan [seed]
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <vector>
-
+#include "asan_common.h"
 #include "pt_modulation.h"
 
 namespace hrt {
@@ -19,30 +13,10 @@ void compose_host(const HrptComposeImages& images, uint32_t width, uint32_t heig
 void modulation_probe(const float* albedo3, const float* N3, const float* V3, float rough, float metal, float floor, float* outM3);
 }
 
-static uint32_t g_state = 1;
-static float rnd() { g_state = hrt_pcg_hash(g_state); return (float)(g_state >> 8) * (1.0f / 16777216.0f); }
-
-static HrptPlanarViewConstants make_view(int w, int h)
-{
-    HrptPlanarViewConstants v;
-    std::memset(&v, 0, sizeof v);
-    const float n = 0.1f, sx = 1.2f, sy = 1.2f * (float)w / (float)h;
-    float* P = v.m_MatViewToClip;                   // reversed-Z, infinite far plane
-    P[0] = sx; P[5] = sy; P[11] = 1.0f; P[14] = n;
-    float* M = v.m_MatClipToWorld;                  // its inverse (camera at the origin of the world)
-    M[0] = 1.0f / sx; M[5] = 1.0f / sy; M[11] = 1.0f / n; M[14] = 1.0f;
-    v.m_ViewportSize[0] = (float)w; v.m_ViewportSize[1] = (float)h;
-    v.m_ViewportSizeInv[0] = 1.0f / (float)w; v.m_ViewportSizeInv[1] = 1.0f / (float)h;
-    v.m_CameraDirectionOrPosition[3] = 1.0f;
-    return v;
-}
-
 static int run(int w, int h, bool hostile)
 {
     const size_t n = (size_t)w * h * 4;
     std::vector<float> color(n), albedo(n), normal(n), geo(n), depth(n), emissive(n), colorOut(n), modulation(n), composed(n);
-    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
-    const float bad[] = { nan, inf, -inf, 3e38f, -3e38f, 0.0f, -1.0f, 1e-42f };
     for (int y = 0; y < h; ++y)
         for (int x = 0; x < w; ++x) {
             const size_t i = ((size_t)y * w + x) * 4;
@@ -59,7 +33,7 @@ static int run(int w, int h, bool hostile)
             emissive[i + 3] = 1.0f;
             if (hostile && rnd() < 0.15f) {
                 float* planes[] = { color.data(), albedo.data(), normal.data(), geo.data(), depth.data(), emissive.data() };
-                planes[(int)(rnd() * 5.999f)][i + (int)(rnd() * 3.999f)] = bad[(int)(rnd() * 7.999f)];
+                planes[(int)(rnd() * 5.999f)][i + (int)(rnd() * 3.999f)] = kBad[(int)(rnd() * 7.999f)];
             }
             if (hostile && rnd() < 0.03f) { normal[i] = normal[i + 1] = normal[i + 2] = 0.0f; }      // zero normal
             if (hostile && rnd() < 0.03f) depth[i + 1] = 0.0f;                                        // view depth 0
@@ -97,8 +71,8 @@ static int run(int w, int h, bool hostile)
     for (int k = 0; k < 64; ++k) {                     // the probe, vectors of any kind
         float a[3], N[3], V[3], out[3];
         for (int j = 0; j < 3; ++j) { a[j] = rnd(); N[j] = 2.0f * rnd() - 1.0f; V[j] = 2.0f * rnd() - 1.0f; }
-        if (hostile && (k & 3) == 0) N[k % 3] = bad[k % 8];
-        if (hostile && (k & 3) == 1) V[k % 3] = bad[k % 8];
+        if (hostile && (k & 3) == 0) N[k % 3] = kBad[k % 8];
+        if (hostile && (k & 3) == 1) V[k % 3] = kBad[k % 8];
         if (hostile && (k & 7) == 2) N[0] = N[1] = N[2] = 0.0f;
         hrt::modulation_probe(a, N, V, rnd(), rnd(), floors[k % 3], out);
         ++calls;
@@ -108,10 +82,9 @@ static int run(int w, int h, bool hostile)
 
 int main(int argc, char** argv)
 {
-    g_state = argc > 1 ? (uint32_t)std::strtoul(argv[1], nullptr, 10) : 1u;
+    seed_from(argc, argv);
     int calls = 0;
-    const int sizes[][2] = { { 1, 1 }, { 2, 3 }, { 37, 23 }, { 64, 36 } };
-    for (const auto& s : sizes)
+    for (const auto& s : kSizes)
         for (int hostile = 0; hostile < 2; ++hostile) {
             const int r = run(s[0], s[1], hostile != 0);
             if (r < 0) return 1;

@@ -12,21 +12,24 @@
 // format decode and the correctly rounded divisions in software a downsampled texel is ~2000 dependent instructions, so the small levels
 // are bound by that instruction stream (5 us per pass however small), not by launches or bytes, and one workgroup that walks several
 // texels per lane serialises exactly that: 49 us for levels 4..5 against 15 us for the three launches it replaces.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <thread>
 #include <vector>
 
 #include "pt_bloom.h"
+#include "pt_host_rows.h"
+#include "pt_image_kernel.h"
 #include "pt_kernels.h"
 
 namespace hrt {
 
 namespace {
 using namespace bloom;
+using img::kTileX;
+using img::kTileY;
+using img::stage_grid;
+using img::stage_index;
+using img::stage_pixel;
 
-constexpr int kTileX = 32, kTileY = 8;
 constexpr int kTailThreads = 512;         // 256 VGPRs per lane: the 13-tap downsample keeps its 52 loads in flight without spilling (1024 threads spilled 320 B per lane)
 constexpr size_t kTailLdsLimit = 160u * 1024u;      // LDS of one gfx950 CU
 constexpr size_t kLdsNoOptIn = 64u * 1024u;         // dynamic LDS a launch may ask for without raising the kernel's limit
@@ -34,33 +37,34 @@ constexpr size_t kLdsNoOptIn = 64u * 1024u;         // dynamic LDS a launch may 
 __global__ __launch_bounds__(kTileX * kTileY) void bloom_prefilter(const float* __restrict__ hdr, int W, int H, uint32_t* __restrict__ down0,
                                                                    int w, int h, float knee)
 {
-    const int px = blockIdx.x * kTileX + threadIdx.x, py = blockIdx.y * kTileY + threadIdx.y;
-    if (px < w && py < h) down0[(size_t)py * w + px] = prefilter_texel(hdr, W, H, w, h, px, py, knee);
+    int px, py;
+    if (stage_pixel(w, h, &px, &py)) down0[stage_index(w, px, py)] = prefilter_texel(hdr, W, H, w, h, px, py, knee);
 }
 
 __global__ __launch_bounds__(kTileX * kTileY) void bloom_downsample(const uint32_t* __restrict__ src, int sw, int sh, uint32_t* __restrict__ dst,
                                                                     int w, int h)
 {
-    const int px = blockIdx.x * kTileX + threadIdx.x, py = blockIdx.y * kTileY + threadIdx.y;
-    if (px < w && py < h) dst[(size_t)py * w + px] = down_texel(src, sw, sh, w, h, px, py);
+    int px, py;
+    if (stage_pixel(w, h, &px, &py)) dst[stage_index(w, px, py)] = down_texel(src, sw, sh, w, h, px, py);
 }
 
 __global__ __launch_bounds__(kTileX * kTileY) void bloom_upsample(const uint32_t* __restrict__ upper, int uw, int uh, const uint32_t* __restrict__ down,
                                                                   uint32_t* __restrict__ dst, int w, int h, float radius)
 {
-    const int px = blockIdx.x * kTileX + threadIdx.x, py = blockIdx.y * kTileY + threadIdx.y;
-    if (px < w && py < h) dst[(size_t)py * w + px] = up_texel(upper, uw, uh, down, w, h, px, py, radius);
+    int px, py;
+    if (stage_pixel(w, h, &px, &py)) dst[stage_index(w, px, py)] = up_texel(upper, uw, uh, down, w, h, px, py, radius);
 }
 
 __global__ __launch_bounds__(kTileX * kTileY) void bloom_composite(float4* __restrict__ hdr, int W, int H, const uint32_t* __restrict__ up0, int w, int h,
                                                                    float intensity)
 {
-    const int px = blockIdx.x * kTileX + threadIdx.x, py = blockIdx.y * kTileY + threadIdx.y;
-    if (px >= W || py >= H) return;
+    int px, py;
+    if (!stage_pixel(W, H, &px, &py)) return;
     const B3 b = composite_texel(up0, w, h, W, H, px, py, intensity);
-    float4 c = hdr[(size_t)py * W + px];
+    const size_t idx = stage_index(W, px, py);
+    float4 c = hdr[idx];
     c.x = c.x + b.x; c.y = c.y + b.y; c.z = c.z + b.z;                              // BlendTargetAdditive; alpha stays
-    hdr[(size_t)py * W + px] = c;
+    hdr[idx] = c;
 }
 
 // Levels T..L-1 of the down pyramid and L-2..T of the up pyramid in one workgroup. LDS: Down[T], ..., Down[L-1], then Up[T+1], ..., Up[L-2]
@@ -128,17 +132,6 @@ struct Schedule {
     }
 };
 
-dim3 tiles(int w, int h) { return dim3((unsigned)((w + kTileX - 1) / kTileX), (unsigned)((h + kTileY - 1) / kTileY)); }
-
-template <class F> void parallel_rows(int nthreads, int rows, F f)
-{
-    if (nthreads > rows) nthreads = rows;
-    if (nthreads <= 1) { for (int y = 0; y < rows; ++y) f(y); return; }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; ++t)
-        th.emplace_back([=] { for (int y = t; y < rows; y += nthreads) f(y); });
-    for (auto& x : th) x.join();
-}
 } // namespace
 
 size_t bloom_pyramid_words(uint32_t width, uint32_t height) { Schedule s(width, height); return s.off[s.L]; }
@@ -164,12 +157,12 @@ hipError_t launch_bloom(float4* hdr, uint32_t width, uint32_t height, const Hrpt
     const Schedule s(width, height);
     if (s.L == 0) return hipSuccess;
     const int W = (int)width, H = (int)height;
-    const dim3 block(kTileX, kTileY);
+    const dim3 block = img::stage_block();
     size_t ldsBytes = 0;
     const int T = s.tail_start(tailTexels, &ldsBytes);
-    hipLaunchKernelGGL(bloom_prefilter, tiles(s.w[0], s.h[0]), block, 0, stream, reinterpret_cast<const float*>(hdr), W, H, downPyramid, s.w[0], s.h[0], p.knee);
+    hipLaunchKernelGGL(bloom_prefilter, stage_grid(s.w[0], s.h[0]), block, 0, stream, reinterpret_cast<const float*>(hdr), W, H, downPyramid, s.w[0], s.h[0], p.knee);
     for (int i = 1; i < s.L && i < T; ++i)
-        hipLaunchKernelGGL(bloom_downsample, tiles(s.w[i], s.h[i]), block, 0, stream, downPyramid + s.off[i - 1], s.w[i - 1], s.h[i - 1],
+        hipLaunchKernelGGL(bloom_downsample, stage_grid(s.w[i], s.h[i]), block, 0, stream, downPyramid + s.off[i - 1], s.w[i - 1], s.h[i - 1],
                            downPyramid + s.off[i], s.w[i], s.h[i]);
     int top = s.L - 1;                                         // the level the remaining upsamples start from
     const uint32_t* upper = downPyramid + s.off[top];          // Up[L - 1] = Down[L - 1] (the seed copy, not made)
@@ -183,11 +176,11 @@ hipError_t launch_bloom(float4* hdr, uint32_t width, uint32_t height, const Hrpt
         top = T; upper = upPyramid + s.off[T];
     }
     for (int i = top - 1; i >= 0; --i) {
-        hipLaunchKernelGGL(bloom_upsample, tiles(s.w[i], s.h[i]), block, 0, stream, upper, s.w[i + 1], s.h[i + 1], downPyramid + s.off[i],
+        hipLaunchKernelGGL(bloom_upsample, stage_grid(s.w[i], s.h[i]), block, 0, stream, upper, s.w[i + 1], s.h[i + 1], downPyramid + s.off[i],
                            upPyramid + s.off[i], s.w[i], s.h[i], p.upsampleRadius);
         upper = upPyramid + s.off[i];
     }
-    hipLaunchKernelGGL(bloom_composite, tiles(W, H), block, 0, stream, hdr, W, H, upper, s.w[0], s.h[0], p.intensity);
+    hipLaunchKernelGGL(bloom_composite, stage_grid(width, height), block, 0, stream, hdr, W, H, upper, s.w[0], s.h[0], p.intensity);
     return hipGetLastError();
 }
 
@@ -198,26 +191,25 @@ void bloom_host(const float* hdrIn, float* hdrOut, uint32_t width, uint32_t heig
     if (s.L > 0) {
         std::vector<uint32_t> down(s.off[s.L]), up(s.off[s.L]);
         uint32_t* d = down.data(); uint32_t* u = up.data();
-        parallel_rows(nthreads, s.h[0], [&](int y) { for (int x = 0; x < s.w[0]; ++x) d[(size_t)y * s.w[0] + x] = prefilter_texel(hdrIn, W, H, s.w[0], s.h[0], x, y, p.knee); });
+        over_rows(s.h[0], nthreads, [&](int y) { for (int x = 0; x < s.w[0]; ++x) d[(size_t)y * s.w[0] + x] = prefilter_texel(hdrIn, W, H, s.w[0], s.h[0], x, y, p.knee); });
         for (int i = 1; i < s.L; ++i)
-            parallel_rows(nthreads, s.h[i], [&](int y) {
+            over_rows(s.h[i], nthreads, [&](int y) {
                 for (int x = 0; x < s.w[i]; ++x) d[s.off[i] + (size_t)y * s.w[i] + x] = down_texel(d + s.off[i - 1], s.w[i - 1], s.h[i - 1], s.w[i], s.h[i], x, y);
             });
         const uint32_t* upper = d + s.off[s.L - 1];
         for (int i = s.L - 2; i >= 0; --i) {
-            parallel_rows(nthreads, s.h[i], [&](int y) {
+            over_rows(s.h[i], nthreads, [&](int y) {
                 for (int x = 0; x < s.w[i]; ++x)
                     u[s.off[i] + (size_t)y * s.w[i] + x] = up_texel(upper, s.w[i + 1], s.h[i + 1], d + s.off[i], s.w[i], s.h[i], x, y, p.upsampleRadius);
             });
             upper = u + s.off[i];
         }
         // hdrOut may be hdrIn: the composite reads and writes one pixel, the prefilter has finished with the image
-        parallel_rows(nthreads, H, [&](int y) {
+        over_rows(H, nthreads, [&](int y) {
             for (int x = 0; x < W; ++x) {
                 const B3 b = composite_texel(upper, s.w[0], s.h[0], W, H, x, y, p.intensity);
-                const float* in = hdrIn + ((size_t)y * W + x) * 4; float* out = hdrOut + ((size_t)y * W + x) * 4;
-                const float r = in[0] + b.x, g = in[1] + b.y, bl = in[2] + b.z, a = in[3];
-                out[0] = r; out[1] = g; out[2] = bl; out[3] = a;
+                const img::T4 in = img::load4(hdrIn, W, x, y);
+                store4(hdrOut + ((size_t)y * W + x) * 4, img::t4(in.x + b.x, in.y + b.y, in.z + b.z, in.w));
             }
         });
     } else if (hdrOut != hdrIn) {

@@ -92,6 +92,19 @@ static int fail(HrptContext* ctx, int code, const std::string& msg)
         if (e_ != hipSuccess) return fail(ctx, e_ == hipErrorOutOfMemory ? HRPT_ERR_OUT_OF_MEMORY : HRPT_ERR_HIP, \
                                           std::string(#expr) + ": " + hipGetErrorString(e_));      \
     } while (0)
+#define HRPT_TRY(expr) do { int r_ = (expr); if (r_ != HRPT_OK) return r_; } while (0)      // pass a failed status on (fail() has set the message)
+
+static bool size_ok(uint32_t width, uint32_t height) { return !(width == 0 || height == 0 || width > 65535u || height > 65535u); }
+
+// Per-context images of width * height float4. hipFree waits for work in flight.
+static void free_image(float4*& image) { if (image) { (void)hipFree(image); image = nullptr; } }
+static int realloc_image(HrptContext* c, float4*& image, size_t bytes)      // a fresh image, zeroed on the context stream
+{
+    free_image(image);
+    HIP_TRY(c, hipMalloc((void**)&image, bytes));
+    HIP_TRY(c, hipMemsetAsync(image, 0, bytes, c->stream));
+    return HRPT_OK;
+}
 
 // DirectX::PackedVector::XMConvertFloatToHalf (round to nearest even), src/CommonResources.cpp:553
 static uint16_t float_to_half(float f)
@@ -703,38 +716,22 @@ static int update_instances_impl(HrptContext* c, const HrptPerInstanceData* inst
 int hrpt_resize(HrptContext* c, uint32_t width, uint32_t height)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    if (width == 0 || height == 0 || width > 65535u || height > 65535u)
+    if (!size_ok(width, height))
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_resize: size must be 1..65535 (RNG seed packs y*65536+x, RNG.hlsli:24)");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->dAccum) { (void)hipFree(c->dAccum); c->dAccum = nullptr; }
-    if (c->dOutput) { (void)hipFree(c->dOutput); c->dOutput = nullptr; }
-    if (c->dDisplay) { (void)hipFree(c->dDisplay); c->dDisplay = nullptr; }
-    size_t bytes = (size_t)width * height * sizeof(float4);
-    HIP_TRY(c, hipMalloc((void**)&c->dAccum, bytes));
-    HIP_TRY(c, hipMalloc((void**)&c->dOutput, bytes));
-    HIP_TRY(c, hipMemsetAsync(c->dAccum, 0, bytes, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->dOutput, 0, bytes, c->stream));
-    for (float4*& plane : c->dGBuffer) {       // the G-buffer planes a caller has asked for follow the image size (zeroed, like a first request)
-        if (!plane) continue;
-        (void)hipFree(plane); plane = nullptr;
-        HIP_TRY(c, hipMalloc((void**)&plane, bytes));
-        HIP_TRY(c, hipMemsetAsync(plane, 0, bytes, c->stream));
-    }
-    if (c->dMotion) {                           // ... and so does the motion plane
-        (void)hipFree(c->dMotion); c->dMotion = nullptr;
-        HIP_TRY(c, hipMalloc((void**)&c->dMotion, bytes));
-        HIP_TRY(c, hipMemsetAsync(c->dMotion, 0, bytes, c->stream));
-    }
+    free_image(c->dAccum); free_image(c->dOutput); free_image(c->dDisplay);      // all three go before anything is allocated
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    HRPT_TRY(realloc_image(c, c->dAccum, bytes));
+    HRPT_TRY(realloc_image(c, c->dOutput, bytes));
+    for (float4*& plane : c->dGBuffer)         // the G-buffer planes a caller has asked for follow the image size (zeroed, like a first request)
+        if (plane) HRPT_TRY(realloc_image(c, plane, bytes));
+    if (c->dMotion) HRPT_TRY(realloc_image(c, c->dMotion, bytes));       // ... and so does the motion plane
     c->temporalValid = false; c->temporalCur = 0;     // the temporal history does not survive a resize
-    for (float4*& image : c->dTemporal) {
-        if (!image) continue;
-        (void)hipFree(image); image = nullptr;
-        HIP_TRY(c, hipMalloc((void**)&image, bytes));
-        HIP_TRY(c, hipMemsetAsync(image, 0, bytes, c->stream));
-    }
-    for (float4*& image : c->dDenoiseScratch) if (image) { (void)hipFree(image); image = nullptr; }     // allocated again by the call that needs it
-    if (c->dModulation) { (void)hipFree(c->dModulation); c->dModulation = nullptr; }                     // written again by the next hrpt_demodulate
+    for (float4*& image : c->dTemporal)
+        if (image) HRPT_TRY(realloc_image(c, image, bytes));
+    for (float4*& image : c->dDenoiseScratch) free_image(image);        // allocated again by the call that needs it
+    free_image(c->dModulation);                                         // written again by the next hrpt_demodulate
     c->width = width; c->height = height;
     return HRPT_OK;
 }
@@ -938,16 +935,11 @@ static int render_gbuffer_impl(HrptContext* c, const HrptFrameParams* p, uint32_
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": this two-level structure is deeper than the validation kernel's 64-entry stack");
     const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
     for (uint32_t k = 0; k < HRPT_GB_PLANES; ++k) {
-        if (!(planeMask & (1u << k)) || c->dGBuffer[k]) continue;
-        HIP_TRY(c, hipMalloc((void**)&c->dGBuffer[k], bytes));
-        HIP_TRY(c, hipMemsetAsync(c->dGBuffer[k], 0, bytes, c->stream));
+        if ((planeMask & (1u << k)) && !c->dGBuffer[k]) HRPT_TRY(realloc_image(c, c->dGBuffer[k], bytes));
     }
     MotionArgs m{};
     if (motion) {
-        if (!c->dMotion) {
-            HIP_TRY(c, hipMalloc((void**)&c->dMotion, bytes));
-            HIP_TRY(c, hipMemsetAsync(c->dMotion, 0, bytes, c->stream));
-        }
+        if (!c->dMotion) HRPT_TRY(realloc_image(c, c->dMotion, bytes));
         int r = refresh_motion_tables(c);
         if (r != HRPT_OK) return r;
         m.inst = c->dMotionInst; m.positions = c->dMotionPositions; m.indices = c->dMotionIndices; m.plane = c->dMotion;
@@ -1216,6 +1208,38 @@ int hrpt_post_process(HrptContext* c, const HrptPostParams* p)
     return HRPT_OK;
 }
 
+// ---- screen-space stages: bloom, temporal accumulation, denoise, demodulate / compose ----
+// What the _host, _device and context entry points of a stage with a view check alike, in this order, after their null checks and, for
+// caller-owned images, the image checks: the size, then the view against it. The stage's parameter rule follows.
+static bool view_matches(const HrptPlanarViewConstants& view, uint32_t width, uint32_t height)
+{
+    return view.m_ViewportSize[0] == (float)width && view.m_ViewportSize[1] == (float)height;
+}
+static int size_and_view_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view)
+{
+    if (!size_ok(width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
+    if (!view_matches(view, width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
+    return HRPT_OK;
+}
+
+// Threads of a host executor: 0 or less = one per hardware thread up to 16; at most 256.
+static int host_threads(int nthreads)
+{
+    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
+    if (nthreads < 1) nthreads = 1;
+    return nthreads > 256 ? 256 : nthreads;
+}
+
+// No C++ exception crosses the C boundary: what a host executor may throw (its buffers, its threads) becomes a status code. A template, so
+// that the call itself allocates nothing; templates need C++ linkage.
+extern "C++" template <class Fn> static int run_host(const char* what, Fn fn)
+{
+    try { fn(); }
+    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, std::string(what) + ": out of memory"); }
+    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string(what) + ": " + e.what()); }
+    return HRPT_OK;
+}
+
 // Pyramids for a width x height image: kept while the size stays, re-allocated when it changes (hipFree waits for work in flight).
 static int bloom_run(HrptContext* c, float4* image, uint32_t width, uint32_t height, const HrptBloomParams& p, hipStream_t stream)
 {
@@ -1248,7 +1272,7 @@ int hrpt_bloom_device(HrptContext* c, float* hdrDevice, uint32_t width, uint32_t
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: null params");
     if (!hdrDevice) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: null image");
-    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: size must be 1..65535");
+    if (!size_ok(width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: size must be 1..65535");
     if (!bloom_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: knee, intensity and upsampleRadius must be finite and >= 0");
     HIP_TRY(c, hipSetDevice(c->device));
     return bloom_run(c, reinterpret_cast<float4*>(hdrDevice), width, height, *p, static_cast<hipStream_t>(stream));
@@ -1258,15 +1282,9 @@ int hrpt_bloom_host(const float* hdrIn, float* hdrOut, uint32_t width, uint32_t 
 {
     if (!p) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: null params");
     if (!hdrIn || !hdrOut) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: null image");
-    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: size must be 1..65535");
+    if (!size_ok(width, height)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: size must be 1..65535");
     if (!bloom_params_valid(*p)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: knee, intensity and upsampleRadius must be finite and >= 0");
-    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
-    if (nthreads < 1) nthreads = 1;
-    if (nthreads > 256) nthreads = 256;
-    try { bloom_host(hdrIn, hdrOut, width, height, *p, nthreads); }
-    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_bloom_host: out of memory"); }
-    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_bloom_host: ") + e.what()); }
-    return HRPT_OK;
+    return run_host("hrpt_bloom_host", [&] { bloom_host(hdrIn, hdrOut, width, height, *p, host_threads(nthreads)); });
 }
 
 int hrpt_bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, float* unpackedRgb)
@@ -1277,6 +1295,14 @@ int hrpt_bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, fl
 }
 
 // ---- temporal accumulation (pt_temporal.h / pt_temporal.hip) ----
+// Size, view and parameters: all a context call has left to check once its arguments are not null (its images are the context's own).
+static int temporal_args_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view, const HrptTemporalParams& p)
+{
+    HRPT_TRY(size_and_view_check(c, w, width, height, view));
+    if (!temporal_params_valid(p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": blend must be finite and in [0, 1], flags HRPT_TEMPORAL_* only, reserved 0");
+    return HRPT_OK;
+}
+// Caller-owned images: the null checks and the aliasing rule first, then the above.
 static int temporal_check(HrptContext* c, const char* what, const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
                           const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p)
 {
@@ -1285,33 +1311,21 @@ static int temporal_check(HrptContext* c, const char* what, const HrptTemporalIm
     if (!img->color || !img->motion || !img->depth || !img->normal || !img->historyOut || !img->colorOut)
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only historyIn may be NULL)");
     if (img->historyOut == img->historyIn) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": historyOut must differ from historyIn");
-    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
-    if (!(view->m_ViewportSize[0] == (float)width && view->m_ViewportSize[1] == (float)height))
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
-    if (!temporal_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": blend must be finite and in [0, 1], flags HRPT_TEMPORAL_* only, reserved 0");
-    return HRPT_OK;
+    return temporal_args_check(c, w, width, height, *view, *p);
 }
 
 int hrpt_temporal_host(const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
                        const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p, int nthreads)
 {
-    int r = temporal_check(nullptr, "hrpt_temporal_host", img, width, height, view, prevView, p);
-    if (r != HRPT_OK) return r;
-    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
-    if (nthreads < 1) nthreads = 1;
-    if (nthreads > 256) nthreads = 256;
-    try { temporal_host(*img, width, height, *view, *prevView, *p, nthreads); }
-    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_temporal_host: out of memory"); }
-    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_temporal_host: ") + e.what()); }
-    return HRPT_OK;
+    HRPT_TRY(temporal_check(nullptr, "hrpt_temporal_host", img, width, height, view, prevView, p));
+    return run_host("hrpt_temporal_host", [&] { temporal_host(*img, width, height, *view, *prevView, *p, host_threads(nthreads)); });
 }
 
 int hrpt_temporal_device(HrptContext* c, const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
                          const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p, void* stream)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    int r = temporal_check(c, "hrpt_temporal_device", img, width, height, view, prevView, p);
-    if (r != HRPT_OK) return r;
+    HRPT_TRY(temporal_check(c, "hrpt_temporal_device", img, width, height, view, prevView, p));
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, launch_temporal(*img, width, height, *view, *prevView, *p, static_cast<hipStream_t>(stream)));
     return HRPT_OK;
@@ -1325,24 +1339,17 @@ int hrpt_temporal_accumulate(HrptContext* c, const HrptPlanarViewConstants* view
     if (!c->dMotion || !c->dGBuffer[HRPT_GB_DEPTH] || !c->dGBuffer[HRPT_GB_NORMAL])
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: the motion, depth or normal plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH | NORMAL fills them)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+    HRPT_TRY(temporal_args_check(c, "hrpt_temporal_accumulate", c->width, c->height, *view, *p));      // before anything is allocated
     const bool fresh = !c->dTemporal[0];
     const int next = fresh ? 0 : 1 - c->temporalCur;
+    if (fresh) {
+        for (float4*& image : c->dTemporal) HRPT_TRY(realloc_image(c, image, (size_t)c->width * c->height * sizeof(float4)));
+        c->temporalValid = false;
+    }
     HrptTemporalImages img{};
     img.color = reinterpret_cast<const float*>(c->dOutput); img.colorOut = reinterpret_cast<float*>(c->dOutput);
     img.motion = reinterpret_cast<const float*>(c->dMotion);
     img.depth = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_DEPTH]); img.normal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_NORMAL]);
-    // validate before anything is allocated; the history pointers are placeholders for the check (the pair never aliases)
-    img.historyOut = reinterpret_cast<float*>(c->dOutput);
-    int r = temporal_check(c, "hrpt_temporal_accumulate", &img, c->width, c->height, view, prevView, p);
-    if (r != HRPT_OK) return r;
-    if (fresh) {
-        for (float4*& image : c->dTemporal) {
-            HIP_TRY(c, hipMalloc((void**)&image, bytes));
-            HIP_TRY(c, hipMemsetAsync(image, 0, bytes, c->stream));
-        }
-        c->temporalValid = false;
-    }
     const bool useHistory = c->temporalValid && (p->flags & HRPT_TEMPORAL_RESET) == 0;
     img.historyIn = useHistory ? reinterpret_cast<const float*>(c->dTemporal[1 - next]) : nullptr;
     img.historyOut = reinterpret_cast<float*>(c->dTemporal[next]);
@@ -1367,8 +1374,19 @@ int hrpt_get_temporal_history_device(HrptContext* c, void** devicePtr)
 }
 
 // ---- denoise (pt_denoise.h / pt_denoise.hip) ----
+// Size, view and parameters: all a context call has left to check once its arguments are not null (its images are the context's own).
+static int denoise_args_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view, const HrptDenoiseParams& p,
+                              bool singlePass)
+{
+    HRPT_TRY(size_and_view_check(c, w, width, height, view));
+    if (!denoise_params_valid(p))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": radius and phi must be finite and > 0, the other phis finite and >= 0, iterations 1..5 with radius * 2^(iterations - 1) finite, flags HRPT_DENOISE_* only, reserved 0");
+    if (singlePass && p.iterations != 1u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": one pass per call, iterations must be 1 (hrpt_denoise iterates)");
+    return HRPT_OK;
+}
+// Caller-owned images, one pass: the null checks and the aliasing rules first, then the above.
 static int denoise_check(HrptContext* c, const char* what, const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
-                         const HrptDenoiseParams* p, bool singlePass)
+                         const HrptDenoiseParams* p)
 {
     const std::string w(what);
     if (!img || !view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
@@ -1377,13 +1395,7 @@ static int denoise_check(HrptContext* c, const char* what, const HrptDenoiseImag
     if ((img->color == nullptr) != (img->colorOut == nullptr)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": color and colorOut must both be NULL or both be set");
     if (img->output == img->input) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": output must differ from input");
     if (img->color && (img->color == img->input || img->colorOut == img->input)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": color and colorOut must differ from input");
-    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
-    if (!(view->m_ViewportSize[0] == (float)width && view->m_ViewportSize[1] == (float)height))
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
-    if (!denoise_params_valid(*p))
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": radius and phi must be finite and > 0, the other phis finite and >= 0, iterations 1..5 with radius * 2^(iterations - 1) finite, flags HRPT_DENOISE_* only, reserved 0");
-    if (singlePass && p->iterations != 1u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": one pass per call, iterations must be 1 (hrpt_denoise iterates)");
-    return HRPT_OK;
+    return denoise_args_check(c, w, width, height, *view, *p, true);
 }
 
 static int denoise_tile(HrptContext* c)
@@ -1411,8 +1423,7 @@ int hrpt_set_denoise_noise(HrptContext* c, const float* hostTile)
         }
     } else denoise_default_tile(tile.data());
     HIP_TRY(c, hipSetDevice(c->device));
-    int r = denoise_tile(c);
-    if (r != HRPT_OK) return r;
+    HRPT_TRY(denoise_tile(c));
     // on the context stream: passes enqueued before this call still read the old tile. The source is pageable and local, so wait for the copy.
     HIP_TRY(c, hipMemcpyAsync(c->dDenoiseTile, tile.data(), count * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1421,26 +1432,18 @@ int hrpt_set_denoise_noise(HrptContext* c, const float* hostTile)
 
 int hrpt_denoise_host(const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view, const HrptDenoiseParams* p, int nthreads)
 {
-    int r = denoise_check(nullptr, "hrpt_denoise_host", img, width, height, view, p, true);
-    if (r != HRPT_OK) return r;
-    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
-    if (nthreads < 1) nthreads = 1;
-    if (nthreads > 256) nthreads = 256;
-    try { denoise_host(*img, width, height, *view, *p, nthreads); }
-    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_denoise_host: out of memory"); }
-    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_denoise_host: ") + e.what()); }
-    return HRPT_OK;
+    HRPT_TRY(denoise_check(nullptr, "hrpt_denoise_host", img, width, height, view, p));
+    return run_host("hrpt_denoise_host", [&] { denoise_host(*img, width, height, *view, *p, host_threads(nthreads)); });
 }
 
 int hrpt_denoise_device(HrptContext* c, const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
                         const HrptDenoiseParams* p, void* stream)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    int r = denoise_check(c, "hrpt_denoise_device", img, width, height, view, p, true);
-    if (r != HRPT_OK) return r;
+    HRPT_TRY(denoise_check(c, "hrpt_denoise_device", img, width, height, view, p));
     HIP_TRY(c, hipSetDevice(c->device));
     HrptDenoiseImages im = *img;
-    if (!im.noise) { r = denoise_tile(c); if (r != HRPT_OK) return r; im.noise = c->dDenoiseTile; }
+    if (!im.noise) { HRPT_TRY(denoise_tile(c)); im.noise = c->dDenoiseTile; }
     HIP_TRY(c, launch_denoise(im, width, height, *view, *p, p->radius, p->frame, static_cast<hipStream_t>(stream)));
     return HRPT_OK;
 }
@@ -1455,15 +1458,12 @@ int hrpt_denoise(HrptContext* c, const HrptPlanarViewConstants* view, const Hrpt
     if (!c->dGBuffer[HRPT_GB_DEPTH] || !c->dGBuffer[HRPT_GB_NORMAL] || !c->dGBuffer[HRPT_GB_GEO_NORMAL])
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: the depth, normal or geo-normal plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH | NORMAL | GEO_NORMAL fills them)");
     HIP_TRY(c, hipSetDevice(c->device));
+    HRPT_TRY(denoise_args_check(c, "hrpt_denoise", c->width, c->height, *view, *p, false));
+    HRPT_TRY(denoise_tile(c));
     HrptDenoiseImages img{};
     img.input = reinterpret_cast<const float*>(c->dTemporal[c->temporalCur]);
     img.depth = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_DEPTH]); img.normal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_NORMAL]);
     img.geoNormal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_GEO_NORMAL]);
-    img.output = reinterpret_cast<float*>(c->dTemporal[1 - c->temporalCur]);       // a placeholder for the check where the scratch pair is used
-    int r = denoise_check(c, "hrpt_denoise", &img, c->width, c->height, view, p, false);
-    if (r != HRPT_OK) return r;
-    r = denoise_tile(c);
-    if (r != HRPT_OK) return r;
     img.noise = c->dDenoiseTile;
     const bool outputOnly = (p->flags & HRPT_DENOISE_OUTPUT_ONLY) != 0;
     if (outputOnly) {
@@ -1487,8 +1487,14 @@ int hrpt_denoise(HrptContext* c, const HrptPlanarViewConstants* view, const Hrpt
 }
 
 // ---- demodulate / compose (pt_modulation.h / pt_modulation.hip) ----
-static bool size_ok(uint32_t width, uint32_t height) { return !(width == 0 || height == 0 || width > 65535u || height > 65535u); }
-
+// Size, view and parameters: all a context call has left to check once its arguments are not null (its images are the context's own).
+static int demodulate_args_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view, const HrptModulationParams& p)
+{
+    HRPT_TRY(size_and_view_check(c, w, width, height, view));
+    if (!modulation_params_valid(p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": floor must be finite and > 0, flags 0, reserved 0");
+    return HRPT_OK;
+}
+// Caller-owned images: the null checks and the aliasing rules first, then the above.
 static int demodulate_check(HrptContext* c, const char* what, const HrptDemodulateImages* img, uint32_t width, uint32_t height,
                             const HrptPlanarViewConstants* view, const HrptModulationParams* p)
 {
@@ -1502,11 +1508,7 @@ static int demodulate_check(HrptContext* c, const char* what, const HrptDemodula
     if (img->modulationOut == img->colorOut) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": modulationOut must differ from colorOut");
     for (int i = 1; i < 6; ++i)
         if (inputs[i] && img->colorOut == inputs[i]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": colorOut may equal color, but no other input");
-    if (!size_ok(width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
-    if (!(view->m_ViewportSize[0] == (float)width && view->m_ViewportSize[1] == (float)height))
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
-    if (!modulation_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": floor must be finite and > 0, flags 0, reserved 0");
-    return HRPT_OK;
+    return demodulate_args_check(c, w, width, height, *view, *p);
 }
 
 static int compose_check(HrptContext* c, const char* what, const HrptComposeImages* img, uint32_t width, uint32_t height)
@@ -1520,40 +1522,24 @@ static int compose_check(HrptContext* c, const char* what, const HrptComposeImag
     return HRPT_OK;
 }
 
-static int host_threads(int nthreads)
-{
-    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
-    if (nthreads < 1) nthreads = 1;
-    return nthreads > 256 ? 256 : nthreads;
-}
-
 int hrpt_demodulate_host(const HrptDemodulateImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
                          const HrptModulationParams* p, int nthreads)
 {
-    int r = demodulate_check(nullptr, "hrpt_demodulate_host", img, width, height, view, p);
-    if (r != HRPT_OK) return r;
-    try { demodulate_host(*img, width, height, *view, *p, host_threads(nthreads)); }
-    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_demodulate_host: out of memory"); }
-    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_demodulate_host: ") + e.what()); }
-    return HRPT_OK;
+    HRPT_TRY(demodulate_check(nullptr, "hrpt_demodulate_host", img, width, height, view, p));
+    return run_host("hrpt_demodulate_host", [&] { demodulate_host(*img, width, height, *view, *p, host_threads(nthreads)); });
 }
 
 int hrpt_compose_host(const HrptComposeImages* img, uint32_t width, uint32_t height, int nthreads)
 {
-    int r = compose_check(nullptr, "hrpt_compose_host", img, width, height);
-    if (r != HRPT_OK) return r;
-    try { compose_host(*img, width, height, host_threads(nthreads)); }
-    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, "hrpt_compose_host: out of memory"); }
-    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string("hrpt_compose_host: ") + e.what()); }
-    return HRPT_OK;
+    HRPT_TRY(compose_check(nullptr, "hrpt_compose_host", img, width, height));
+    return run_host("hrpt_compose_host", [&] { compose_host(*img, width, height, host_threads(nthreads)); });
 }
 
 int hrpt_demodulate_device(HrptContext* c, const HrptDemodulateImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
                            const HrptModulationParams* p, void* stream)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    int r = demodulate_check(c, "hrpt_demodulate_device", img, width, height, view, p);
-    if (r != HRPT_OK) return r;
+    HRPT_TRY(demodulate_check(c, "hrpt_demodulate_device", img, width, height, view, p));
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, launch_demodulate(*img, width, height, *view, *p, static_cast<hipStream_t>(stream)));
     return HRPT_OK;
@@ -1562,8 +1548,7 @@ int hrpt_demodulate_device(HrptContext* c, const HrptDemodulateImages* img, uint
 int hrpt_compose_device(HrptContext* c, const HrptComposeImages* img, uint32_t width, uint32_t height, void* stream)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    int r = compose_check(c, "hrpt_compose_device", img, width, height);
-    if (r != HRPT_OK) return r;
+    HRPT_TRY(compose_check(c, "hrpt_compose_device", img, width, height));
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, launch_compose(*img, width, height, static_cast<hipStream_t>(stream)));
     return HRPT_OK;
@@ -1580,16 +1565,13 @@ int hrpt_demodulate(HrptContext* c, const HrptPlanarViewConstants* view, const H
         if (!c->dGBuffer[n.plane])
             return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_demodulate: the plane ") + n.name + " was never requested (hrpt_render_motion_vectors or hrpt_render_gbuffer with planeMask = ALBEDO | NORMAL | GEO_NORMAL | EMISSIVE | DEPTH fills them)");
     HIP_TRY(c, hipSetDevice(c->device));
+    HRPT_TRY(demodulate_args_check(c, "hrpt_demodulate", c->width, c->height, *view, *p));      // before anything is allocated
+    if (!c->dModulation) HIP_TRY(c, hipMalloc((void**)&c->dModulation, (size_t)c->width * c->height * sizeof(float4)));
     HrptDemodulateImages img{};
     img.color = reinterpret_cast<const float*>(c->dOutput); img.colorOut = reinterpret_cast<float*>(c->dOutput);
     img.albedo = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_ALBEDO]); img.normal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_NORMAL]);
     img.geoNormal = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_GEO_NORMAL]); img.depth = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_DEPTH]);
     img.emissive = reinterpret_cast<const float*>(c->dGBuffer[HRPT_GB_EMISSIVE]);
-    // validate before anything is allocated; a placeholder stands for the modulation image (a context image that is none of the others)
-    img.modulationOut = reinterpret_cast<float*>(c->dModulation ? c->dModulation : c->dAccum);
-    int r = demodulate_check(c, "hrpt_demodulate", &img, c->width, c->height, view, p);
-    if (r != HRPT_OK) return r;
-    if (!c->dModulation) HIP_TRY(c, hipMalloc((void**)&c->dModulation, (size_t)c->width * c->height * sizeof(float4)));
     img.modulationOut = reinterpret_cast<float*>(c->dModulation);
     HIP_TRY(c, launch_demodulate(img, c->width, c->height, *view, *p, c->stream));
     return HRPT_OK;

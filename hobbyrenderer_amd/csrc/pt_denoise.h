@@ -9,9 +9,9 @@
 // normal.w, metallic in geoNormal.w), `output` (rgb = filtered radiance, a = the input's age, unclamped). `noise` is a 64 x 64 tile of two
 // floats per texel, noise[y][x][2].
 //
-// What the HLSL leaves to the rasteriser and the samplers is DEFINED as in pt_temporal.h, whose functions are used: pixel uv
-// (bloom::pixel_u), the point sampler (temporal::point_index, clamped in fp32 before the conversion, so nothing indexes outside an image
-// whatever the inputs are), ReconstructWorldPos from the view depth (temporal::recon), log / exp / pow; sincos = hrt_sincos,
+// What the HLSL leaves to the rasteriser and the samplers is DEFINED in pt_image.h, whose functions are used: pixel uv
+// (bloom::pixel_u), the point sampler (img::point_index, clamped in fp32 before the conversion, so nothing indexes outside an image
+// whatever the inputs are), ReconstructWorldPos from the view depth (img::recon), log; exp = hrt_exp, pow = hrt_pow, sincos = hrt_sincos,
 // frac(x) = x - hrt_floor(x). dist == 0, NaN radiance and the like give what IEEE 754 and the select forms give.
 //
 // Differences from the reference pass, on purpose:
@@ -28,23 +28,19 @@
 #include <stdint.h>
 
 #include "../../include/hobbyrt_pt.h"
-#include "pt_temporal.h"
+#include "pt_image.h"
 
 namespace hrt {
 namespace denoise {
 
-using temporal::T2;
-using temporal::T3;
-using temporal::T4;
-using temporal::t3;
-using temporal::t4;
+using namespace img;
 
 constexpr int kNoiseSize = 64;                                     // srrhi::CommonConsts::kBlueNoiseSize
 constexpr size_t kNoiseFloats = (size_t)kNoiseSize * kNoiseSize * 2;
 constexpr float kMaxEffectiveAge = 64.0f, kMinAgeFalloff = 0.15f, kPerspectiveScale = 25.0f, kMinKernelTexels = 2.0f, kYoungNormalPhi = 10.0f;
 
 struct Args {
-    temporal::Args view;            // clipToWorld, p10 / p14, sizeInv, cam, w, h (the other members are not read)
+    ViewArgs view;
     float radius, phi, lumaPhi, depthPhi, normalPhi, roughnessPhi;
     uint32_t frame;
 };
@@ -52,7 +48,7 @@ struct Args {
 HRT_FN Args make_args(const HrptPlanarViewConstants& view, const HrptDenoiseParams& p, float radius, uint32_t frame, int w, int h)
 {
     Args a;
-    a.view = temporal::make_args(view, view, 0.0f, 0u, w, h);
+    a.view = make_view_args(view, w, h);
     a.radius = radius; a.phi = p.phi; a.lumaPhi = p.lumaPhi; a.depthPhi = p.depthPhi; a.normalPhi = p.normalPhi; a.roughnessPhi = p.roughnessPhi;
     a.frame = frame;
     return a;
@@ -68,7 +64,7 @@ HRT_FN void default_tile_texel(int x, int y, float* rg)
 
 HRT_FN float frac(float x) { return x - hrt_floor(x); }
 HRT_FN float luminance(T3 c) { return (c.x * 0.2126f + c.y * 0.7152f) + c.z * 0.0722f; }                  // CommonLighting.hlsli:14
-HRT_FN T3 to_denoise_space(T4 c) { return t3(temporal::ln(c.x + 1.0f), temporal::ln(c.y + 1.0f), temporal::ln(c.z + 1.0f)); }
+HRT_FN T3 to_denoise_space(T4 c) { return t3(ln(c.x + 1.0f), ln(c.y + 1.0f), ln(c.z + 1.0f)); }
 HRT_FN float denoise_luminance(T3 c) { return hrt_pow(luminance(c), 0.125f); }
 
 // SampleBlueNoise (Common.hlsli:92-107): .x and .w of the four numbers, the two the pass uses.
@@ -79,7 +75,7 @@ HRT_FN T2 sample_noise(const float* noise, uint32_t px, uint32_t py, uint32_t fr
     const uint32_t p1x = (px + frame * 5851u + 31u) & mask, p1y = (py + frame * 3917u + 17u) & mask;
     const float ar = noise[((size_t)p0y * kNoiseSize + p0x) * 2], bg = noise[((size_t)p1y * kNoiseSize + p1x) * 2 + 1];
     const float cycleIndex = (float)(frame & 4095u);
-    return temporal::t2(frac(ar + 0.618033988749895f * cycleIndex), frac(bg + 0.167303978261419f * cycleIndex));
+    return t2(frac(ar + 0.618033988749895f * cycleIndex), frac(bg + 0.167303978261419f * cycleIndex));
 }
 
 // ---- SSGIDenoise_PSMain for pixel (px, py): returns output[p]; colorOut[p] is (its rgb, color[p].a) -------------------------------------
@@ -88,8 +84,8 @@ HRT_FN T4 pixel(const Args& a, const float* input, const float* depth, const flo
     const float kPoissonDisk[8][2] = { { -1.0f, 0.0f }, { 0.0f, -1.0f }, { 1.0f, 0.0f }, { 0.0f, 1.0f },
                                        { -0.353553f, -0.353553f }, { 0.353553f, -0.353553f }, { 0.353553f, 0.353553f }, { -0.353553f, 0.353553f } };
     const int W = a.view.w, H = a.view.h;
-    const T4 C = temporal::load4(input, W, px, py), D = temporal::load4(depth, W, px, py);
-    if (D.x == temporal::kMissDepth) return C;
+    const T4 C = load4(input, W, px, py), D = load4(depth, W, px, py);
+    if (D.x == kMissDepth) return C;
 
     const float u = bloom::pixel_u(px, W), v = bloom::pixel_u(py, H);
     const float outputAge = C.w;
@@ -98,13 +94,13 @@ HRT_FN T4 pixel(const Args& a, const float* input, const float* depth, const flo
 
     const T3 Cd = to_denoise_space(C);
     const float centerLum = denoise_luminance(Cd);
-    const T4 N4 = temporal::load4(normal, W, px, py);
+    const T4 N4 = load4(normal, W, px, py);
     const T3 N = t3(N4.x, N4.y, N4.z);
-    const float rough = N4.w, metal = temporal::load4(geoNormal, W, px, py).w;
+    const float rough = N4.w, metal = load4(geoNormal, W, px, py).w;
 
-    const T3 centerWorldPos = temporal::recon(a.view, u, v, D.y);
-    const float dist = temporal::length3(temporal::sub(centerWorldPos, t3(a.view.cam[0], a.view.cam[1], a.view.cam[2])));
-    const float roughnessRadius = temporal::lerp(hrt_sqrt(rough), 1.0f, 0.5f * (1.0f - metal));
+    const T3 centerWorldPos = recon(a.view, u, v, D.y);
+    const float dist = length3(sub(centerWorldPos, t3(a.view.cam[0], a.view.cam[1], a.view.cam[2])));
+    const float roughnessRadius = lerp(hrt_sqrt(rough), 1.0f, 0.5f * (1.0f - metal));
 
     const T2 random = sample_noise(noise, (uint32_t)px, (uint32_t)py, a.frame);          // .x = random.r, .y = random.a
 
@@ -120,22 +116,22 @@ HRT_FN T4 pixel(const Args& a, const float* input, const float* depth, const flo
         const float dx = kPoissonDisk[i][0], dy = kPoissonDisk[i][1];
         const float rx = dx * c - dy * s, ry = dx * s + dy * c;
         const float nu = u + (rx * diskScale) * a.view.sizeInv[0], nv = v + (ry * diskScale) * a.view.sizeInv[1];
-        const int qx = temporal::point_index(nu, W), qy = temporal::point_index(nv, H);
-        const T4 nD = temporal::load4(depth, W, qx, qy);
-        if (nD.x == temporal::kMissDepth) continue;
+        const int qx = point_index(nu, W), qy = point_index(nv, H);
+        const T4 nD = load4(depth, W, qx, qy);
+        if (nD.x == kMissDepth) continue;
 
-        const T3 nC = to_denoise_space(temporal::load4(input, W, qx, qy));
+        const T3 nC = to_denoise_space(load4(input, W, qx, qy));
         const float nLum = denoise_luminance(nC);
-        const T4 nN = temporal::load4(normal, W, qx, qy);
-        const T3 nWorldPos = temporal::recon(a.view, nu, nv, nD.y);
+        const T4 nN = load4(normal, W, qx, qy);
+        const T3 nWorldPos = recon(a.view, nu, nv, nD.y);
 
-        const float normalDiff = 1.0f - hrt_max(temporal::dot3(N, t3(nN.x, nN.y, nN.z)), 0.0f);
-        const float depthDiff = 10.0f * hrt_abs(temporal::dot3(temporal::sub(centerWorldPos, nWorldPos), N));        // plane distance
+        const float normalDiff = 1.0f - hrt_max(dot3(N, t3(nN.x, nN.y, nN.z)), 0.0f);
+        const float depthDiff = 10.0f * hrt_abs(dot3(sub(centerWorldPos, nWorldPos), N));        // plane distance
         const float roughnessDiff = hrt_abs(rough - nN.w);
-        const float lumaDiff = temporal::lerp(hrt_abs(centerLum - nLum), 0.0f, w);
+        const float lumaDiff = lerp(hrt_abs(centerLum - nLum), 0.0f, w);
 
         const float wBasic = hrt_exp(((-normalDiff * a.normalPhi) - depthDiff * a.depthPhi) - roughnessDiff * a.roughnessPhi);
-        const float wBasicD = temporal::lerp(wBasic, hrt_exp(-normalDiff * kYoungNormalPhi), w);
+        const float wBasicD = lerp(wBasic, hrt_exp(-normalDiff * kYoungNormalPhi), w);
         const float wDiff = hrt_min(w * hrt_pow(wBasicD * hrt_exp(-lumaDiff * a.lumaPhi), a.phi / w), 1.0f);
 
         sum = t3(sum.x + wDiff * nC.x, sum.y + wDiff * nC.y, sum.z + wDiff * nC.z);

@@ -7,15 +7,15 @@
 // each: every lane has its own disk rotation, so a wave's taps fall anywhere within +-4 * radius texels of its pixels; they are served by
 // the caches. No LDS: with a per-lane rotation and a radius that doubles per iteration a tile has no fixed footprint worth staging. The
 // compiler unrolls the eight taps (35 KB of code, the disk offsets as immediates). DESIGN.md section 18 has the register counts.
-#include <hip/hip_runtime.h>
-
 #include "pt_denoise.h"
+#include "pt_image_kernel.h"
 #include "pt_kernels.h"
 
 namespace hrt {
 
 namespace {
-constexpr int kTileX = 32, kTileY = 8;
+using img::kTileX;
+using img::kTileY;
 
 // color and colorOut may be the same image (no __restrict__ on them): a thread reads its own colour texel before it writes it. Both are
 // null together. output aliases no input.
@@ -24,22 +24,22 @@ __global__ __launch_bounds__(kTileX * kTileY) void denoise_poisson(denoise::Args
                                                                    const float* __restrict__ noise, float4* __restrict__ output,
                                                                    const float4* color, float4* colorOut)
 {
-    const int px = blockIdx.x * kTileX + threadIdx.x, py = blockIdx.y * kTileY + threadIdx.y;
-    if (px >= a.view.w || py >= a.view.h) return;
-    const temporal::T4 out = denoise::pixel(a, input, depth, normal, geoNormal, noise, px, py);
-    const size_t idx = (size_t)py * (size_t)a.view.w + (size_t)px;
-    output[idx] = make_float4(out.x, out.y, out.z, out.w);
-    if (colorOut) colorOut[idx] = make_float4(out.x, out.y, out.z, color[idx].w);
+    int px, py;
+    if (!img::stage_pixel(a.view.w, a.view.h, &px, &py)) return;
+    const img::T4 out = denoise::pixel(a, input, depth, normal, geoNormal, noise, px, py);
+    const size_t idx = img::stage_index(a.view.w, px, py);
+    img::st4(output, idx, out);
+    if (colorOut) img::st4(colorOut, idx, img::t4(out.x, out.y, out.z, color[idx].w));
 }
 } // namespace
 
-hipError_t launch_denoise(const HrptDenoiseImages& img, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+hipError_t launch_denoise(const HrptDenoiseImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
                           const HrptDenoiseParams& params, float radius, uint32_t frame, hipStream_t stream)
 {
     const denoise::Args a = denoise::make_args(view, params, radius, frame, (int)width, (int)height);
-    const dim3 grid((width + kTileX - 1) / kTileX, (height + kTileY - 1) / kTileY), block(kTileX, kTileY);
-    hipLaunchKernelGGL(denoise_poisson, grid, block, 0, stream, a, img.input, img.depth, img.normal, img.geoNormal, img.noise,
-                       reinterpret_cast<float4*>(img.output), reinterpret_cast<const float4*>(img.color), reinterpret_cast<float4*>(img.colorOut));
+    hipLaunchKernelGGL(denoise_poisson, img::stage_grid(width, height), img::stage_block(), 0, stream, a, images.input, images.depth,
+                       images.normal, images.geoNormal, images.noise, reinterpret_cast<float4*>(images.output),
+                       reinterpret_cast<const float4*>(images.color), reinterpret_cast<float4*>(images.colorOut));
     return hipGetLastError();
 }
 

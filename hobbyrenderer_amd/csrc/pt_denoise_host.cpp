@@ -2,10 +2,9 @@
 // default noise tile and the parameter rules. Plain C++ with no HIP call, so that the sanitizer program (denoise_asan.cpp,
 // `make denoise_asan`) builds it with g++ as it is.
 #include <cmath>
-#include <thread>
-#include <vector>
 
 #include "pt_denoise.h"
+#include "pt_host_rows.h"
 
 namespace hrt {
 
@@ -30,29 +29,22 @@ bool denoise_params_valid(const HrptDenoiseParams& p)
 
 // One pass with params.radius and params.frame. colorOut may be color (a pixel reads only its own colour texel and reads it before
 // writing); output must not be input (the taps read input texels other rows write).
-void denoise_host(const HrptDenoiseImages& img, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+void denoise_host(const HrptDenoiseImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
                   const HrptDenoiseParams& params, int nthreads)
 {
     const denoise::Args a = denoise::make_args(view, params, params.radius, params.frame, (int)width, (int)height);
     std::vector<float> tile;
-    const float* noise = img.noise;
+    const float* noise = images.noise;
     if (!noise) { tile.resize(denoise::kNoiseFloats); denoise_default_tile(tile.data()); noise = tile.data(); }
     const int W = (int)width, H = (int)height;
-    auto row = [&, noise](int y) {
+    over_rows(H, nthreads, [&, noise](int y) {
         for (int x = 0; x < W; ++x) {
-            const temporal::T4 out = denoise::pixel(a, img.input, img.depth, img.normal, img.geoNormal, noise, x, y);
+            const img::T4 out = denoise::pixel(a, images.input, images.depth, images.normal, images.geoNormal, noise, x, y);
             const size_t i = ((size_t)y * W + x) * 4;
-            float* o = img.output + i;
-            o[0] = out.x; o[1] = out.y; o[2] = out.z; o[3] = out.w;
-            if (img.colorOut) { const float alpha = img.color[i + 3]; float* c = img.colorOut + i; c[0] = out.x; c[1] = out.y; c[2] = out.z; c[3] = alpha; }
+            store4(images.output + i, out);
+            if (images.colorOut) store4(images.colorOut + i, img::t4(out.x, out.y, out.z, images.color[i + 3]));     // alpha read before the write
         }
-    };
-    if (nthreads > H) nthreads = H;
-    if (nthreads <= 1) { for (int y = 0; y < H; ++y) row(y); return; }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; ++t)
-        th.emplace_back([=] { for (int y = t; y < H; y += nthreads) row(y); });
-    for (auto& x : th) x.join();
+    });
 }
 
 } // namespace hrt

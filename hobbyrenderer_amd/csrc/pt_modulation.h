@@ -15,8 +15,8 @@
 // HRPT_GB_ALBEDO, HRPT_GB_NORMAL with roughness in .w, HRPT_GB_GEO_NORMAL with metallic in .w, HRPT_GB_EMISSIVE, HRPT_GB_DEPTH with the
 // view depth in .y), `modulation` (rgb = Mf, a = 1 at a hit and 0 at a miss). E = emissive.rgb, 0 where no emissive image is given.
 //
-// What the HLSL leaves open is DEFINED here:
-//   * pixel uv (bloom::pixel_u), ReconstructWorldPos from the view depth (temporal::recon), lerp(a, b, t) = a + t * (b - a)
+// What the HLSL leaves open is DEFINED here (the functions of the first four items are pt_image.h's):
+//   * pixel uv (bloom::pixel_u), ReconstructWorldPos from the view depth (img::recon), lerp(a, b, t) = a + t * (b - a)
 //   * normalize(v) = (v.x / len, v.y / len, v.z / len) with len = sqrt((v.x * v.x + v.y * v.y) + v.z * v.z): one correctly rounded sqrt and
 //     three correctly rounded divisions. A zero vector gives 0 / 0 = NaN in every component; the NaN ends in max(kEpsilon, dot(V, h)),
 //     whose select form returns kEpsilon, so the factor of such a pixel is finite.
@@ -49,35 +49,26 @@
 #include <stdint.h>
 
 #include "../../include/hobbyrt_pt.h"
-#include "pt_temporal.h"
+#include "pt_image.h"
 
 namespace hrt {
 namespace modulation {
 
-using temporal::T3;
-using temporal::T4;
-using temporal::t3;
-using temporal::t4;
+using namespace img;
 
 constexpr float kDefaultFloor = 0.04f;
 
 struct Args {
-    temporal::Args view;            // clipToWorld, p10 / p14, cam, w, h (the other members are not read)
+    ViewArgs view;
     float floor;
 };
 HRT_FN Args make_args(const HrptPlanarViewConstants& view, const HrptModulationParams& p, int w, int h)
 {
     Args a;
-    a.view = temporal::make_args(view, view, 0.0f, 0u, w, h);
+    a.view = make_view_args(view, w, h);
     a.floor = p.floor;
     return a;
 }
-
-HRT_FN T3 add(T3 a, T3 b) { return t3(a.x + b.x, a.y + b.y, a.z + b.z); }
-HRT_FN T3 neg(T3 a) { return t3(-a.x, -a.y, -a.z); }
-HRT_FN T3 cross(T3 a, T3 b) { return t3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-HRT_FN T3 normalize(T3 v) { const float len = temporal::length3(v); return t3(v.x / len, v.y / len, v.z / len); }
-HRT_FN T3 reflect(T3 i, T3 n) { const float k = 2.0f * temporal::dot3(n, i); return t3(i.x - k * n.x, i.y - k * n.y, i.z - k * n.z); }
 
 // BuildTangentFrame (CommonLighting.hlsli:610-615)
 HRT_FN void tangent_frame(T3 N, T3* T, T3* B)
@@ -87,7 +78,7 @@ HRT_FN void tangent_frame(T3 N, T3* T, T3* B)
     *B = cross(N, *T);
 }
 // TangentToLocal / TangentToWorld (Common.hlsli:70-78)
-HRT_FN T3 to_local(T3 T, T3 B, T3 N, T3 V) { return t3(temporal::dot3(V, T), temporal::dot3(V, B), temporal::dot3(V, N)); }
+HRT_FN T3 to_local(T3 T, T3 B, T3 N, T3 V) { return t3(dot3(V, T), dot3(V, B), dot3(V, N)); }
 HRT_FN T3 to_world(T3 T, T3 B, T3 N, T3 V)
 {
     return t3((V.x * T.x + V.y * B.x) + V.z * N.x, (V.x * T.y + V.y * B.y) + V.z * N.y, (V.x * T.z + V.y * B.z) + V.z * N.z);
@@ -129,13 +120,13 @@ HRT_FN T3 factor(T3 albedo, T3 N, T3 V, float rough, float metal, float floor)
     const T3 lLocal = normalize(reflect(neg(Vlocal), H));
     const T3 l = to_world(T, B, N, lLocal);
     const T3 h = normalize(add(V, l));
-    const float VoH = hrt_max(HRT_K_EPSILON, temporal::dot3(V, h));
+    const float VoH = hrt_max(HRT_K_EPSILON, dot3(V, h));
     const float p = hrt_pow(hrt_max(1.0f - VoH, 0.0f), 5.0f);
     const float one = 1.0f - metal;
     const float a3[3] = { albedo.x, albedo.y, albedo.z };
     float m[3];
     for (int i = 0; i < 3; ++i) {
-        const float F = schlick(temporal::lerp(0.04f, a3[i], metal), p);
+        const float F = schlick(lerp(0.04f, a3[i], metal), p);
         m[i] = hrt_max(((a3[i] * one) * (1.0f - F)) + F, floor);
     }
     return t3(m[0], m[1], m[2]);
@@ -145,13 +136,13 @@ HRT_FN T3 factor(T3 albedo, T3 N, T3 V, float rough, float metal, float floor)
 HRT_FN T4 modulation_pixel(const Args& a, const float* albedo, const float* normal, const float* geoNormal, const float* depth, int px, int py)
 {
     const int W = a.view.w, H = a.view.h;
-    const T4 D = temporal::load4(depth, W, px, py);
-    if (D.x == temporal::kMissDepth) return t4(1.0f, 1.0f, 1.0f, 0.0f);
-    const T4 A = temporal::load4(albedo, W, px, py), N4 = temporal::load4(normal, W, px, py);
-    const float metal = temporal::load4(geoNormal, W, px, py).w;
+    const T4 D = load4(depth, W, px, py);
+    if (D.x == kMissDepth) return t4(1.0f, 1.0f, 1.0f, 0.0f);
+    const T4 A = load4(albedo, W, px, py), N4 = load4(normal, W, px, py);
+    const float metal = load4(geoNormal, W, px, py).w;
     const float u = bloom::pixel_u(px, W), v = bloom::pixel_u(py, H);
-    const T3 worldPos = temporal::recon(a.view, u, v, D.y);
-    const T3 V = normalize(temporal::sub(t3(a.view.cam[0], a.view.cam[1], a.view.cam[2]), worldPos));
+    const T3 worldPos = recon(a.view, u, v, D.y);
+    const T3 V = normalize(sub(t3(a.view.cam[0], a.view.cam[1], a.view.cam[2]), worldPos));
     const T3 m = factor(t3(A.x, A.y, A.z), t3(N4.x, N4.y, N4.z), V, N4.w, metal, a.floor);
     return t4(m.x, m.y, m.z, 1.0f);
 }

@@ -9,22 +9,23 @@
 // reads three (colour, modulation, emissive) and writes one = 64 B. Storing Mf is what keeps compose at half of demodulate: it reads one
 // image instead of the four planes the factor is computed from, and does none of its arithmetic. DESIGN.md section 20 has the register
 // counts and the times.
-#include <hip/hip_runtime.h>
-
+#include "pt_image_kernel.h"
 #include "pt_kernels.h"
 #include "pt_modulation.h"
 
 namespace hrt {
 
 namespace {
-constexpr int kTileX = 32, kTileY = 8;
+using img::kTileX;
+using img::kTileY;
+using img::ld4;
+using img::st4;
 
-__device__ __forceinline__ temporal::T4 ld4(const float4* img, size_t idx) { const float4 v = img[idx]; return temporal::t4(v.x, v.y, v.z, v.w); }
-__device__ __forceinline__ temporal::T3 emissive_at(const float4* emissive, size_t idx)
+__device__ __forceinline__ img::T3 emissive_at(const float4* emissive, size_t idx)
 {
-    if (!emissive) return temporal::t3(0.0f, 0.0f, 0.0f);
+    if (!emissive) return img::t3(0.0f, 0.0f, 0.0f);
     const float4 e = emissive[idx];
-    return temporal::t3(e.x, e.y, e.z);
+    return img::t3(e.x, e.y, e.z);
 }
 
 // color and colorOut may be the same image (no __restrict__ on them): a thread reads its own colour texel before it writes it.
@@ -34,43 +35,41 @@ __global__ __launch_bounds__(kTileX * kTileY) void modulation_demodulate(modulat
                                                                          const float* __restrict__ depth, const float4* __restrict__ emissive,
                                                                          float4* colorOut, float4* __restrict__ modulationOut)
 {
-    const int px = blockIdx.x * kTileX + threadIdx.x, py = blockIdx.y * kTileY + threadIdx.y;
-    if (px >= a.view.w || py >= a.view.h) return;
-    const size_t idx = (size_t)py * (size_t)a.view.w + (size_t)px;
-    const temporal::T4 M = modulation::modulation_pixel(a, albedo, normal, geoNormal, depth, px, py);
-    const temporal::T4 out = modulation::demodulate_color(ld4(color, idx), M, emissive_at(emissive, idx));
-    modulationOut[idx] = make_float4(M.x, M.y, M.z, M.w);
-    colorOut[idx] = make_float4(out.x, out.y, out.z, out.w);
+    int px, py;
+    if (!img::stage_pixel(a.view.w, a.view.h, &px, &py)) return;
+    const size_t idx = img::stage_index(a.view.w, px, py);
+    const img::T4 M = modulation::modulation_pixel(a, albedo, normal, geoNormal, depth, px, py);
+    const img::T4 out = modulation::demodulate_color(ld4(color, idx), M, emissive_at(emissive, idx));
+    st4(modulationOut, idx, M);
+    st4(colorOut, idx, out);
 }
 
 __global__ __launch_bounds__(kTileX * kTileY) void modulation_compose(int w, int h, const float4* color, const float4* __restrict__ modulation,
                                                                       const float4* __restrict__ emissive, float4* colorOut)
 {
-    const int px = blockIdx.x * kTileX + threadIdx.x, py = blockIdx.y * kTileY + threadIdx.y;
-    if (px >= w || py >= h) return;
-    const size_t idx = (size_t)py * (size_t)w + (size_t)px;
-    const temporal::T4 out = modulation::compose_color(ld4(color, idx), ld4(modulation, idx), emissive_at(emissive, idx));
-    colorOut[idx] = make_float4(out.x, out.y, out.z, out.w);
+    int px, py;
+    if (!img::stage_pixel(w, h, &px, &py)) return;
+    const size_t idx = img::stage_index(w, px, py);
+    st4(colorOut, idx, modulation::compose_color(ld4(color, idx), ld4(modulation, idx), emissive_at(emissive, idx)));
 }
 } // namespace
 
-hipError_t launch_demodulate(const HrptDemodulateImages& img, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+hipError_t launch_demodulate(const HrptDemodulateImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
                              const HrptModulationParams& params, hipStream_t stream)
 {
     const modulation::Args a = modulation::make_args(view, params, (int)width, (int)height);
-    const dim3 grid((width + kTileX - 1) / kTileX, (height + kTileY - 1) / kTileY), block(kTileX, kTileY);
-    hipLaunchKernelGGL(modulation_demodulate, grid, block, 0, stream, a, reinterpret_cast<const float4*>(img.color), img.albedo, img.normal,
-                       img.geoNormal, img.depth, reinterpret_cast<const float4*>(img.emissive), reinterpret_cast<float4*>(img.colorOut),
-                       reinterpret_cast<float4*>(img.modulationOut));
+    hipLaunchKernelGGL(modulation_demodulate, img::stage_grid(width, height), img::stage_block(), 0, stream, a,
+                       reinterpret_cast<const float4*>(images.color), images.albedo, images.normal, images.geoNormal, images.depth,
+                       reinterpret_cast<const float4*>(images.emissive), reinterpret_cast<float4*>(images.colorOut),
+                       reinterpret_cast<float4*>(images.modulationOut));
     return hipGetLastError();
 }
 
-hipError_t launch_compose(const HrptComposeImages& img, uint32_t width, uint32_t height, hipStream_t stream)
+hipError_t launch_compose(const HrptComposeImages& images, uint32_t width, uint32_t height, hipStream_t stream)
 {
-    const dim3 grid((width + kTileX - 1) / kTileX, (height + kTileY - 1) / kTileY), block(kTileX, kTileY);
-    hipLaunchKernelGGL(modulation_compose, grid, block, 0, stream, (int)width, (int)height, reinterpret_cast<const float4*>(img.color),
-                       reinterpret_cast<const float4*>(img.modulation), reinterpret_cast<const float4*>(img.emissive),
-                       reinterpret_cast<float4*>(img.colorOut));
+    hipLaunchKernelGGL(modulation_compose, img::stage_grid(width, height), img::stage_block(), 0, stream, (int)width, (int)height,
+                       reinterpret_cast<const float4*>(images.color), reinterpret_cast<const float4*>(images.modulation),
+                       reinterpret_cast<const float4*>(images.emissive), reinterpret_cast<float4*>(images.colorOut));
     return hipGetLastError();
 }
 

@@ -8,16 +8,11 @@
 // Images are W x H float4, row-major: `color` (Output of hrpt_render), `motion` (hrpt_render_motion_vectors), `depth` and `normal` (the
 // planes HRPT_GB_DEPTH and HRPT_GB_NORMAL of the same frame), `historyIn` / `historyOut` (rgb = accumulated radiance, a = age).
 //
-// What the HLSL leaves to the rasteriser and the samplers is DEFINED here, as in pt_bloom.h (whose functions are used):
-//   * pixel uv: bloom::pixel_u; SampleLevel(linearClamp, uv, 0): bloom::axis / bloom::taps and the a(1 - t) + bt filter, on all four channels
-//   * SampleLevel(pointClamp, r, 0): the texel ix = (int)clamp(floor(r.x * W), 0, W - 1), iy likewise -- clamped in fp32 before the
-//     conversion, so every float -> int conversion in this file is defined for every input (NaN converts as 0)
-//   * log(x) = hrt_log2(x) * 0.69314718f, exp = hrt_exp, pow = hrt_pow
-//   * device depth: the path tracer keeps the VIEW depth vd (HRPT_GB_DEPTH.y); the reference's reversed-Z value that ReconstructWorldPos
-//     takes is z = (vd * P[10] + P[14]) / vd with P = m_MatViewToClip
-//   * a pixel is a miss when depth.x == 1e10f (the sentinel of hrpt_render_gbuffer; the reference's DEPTH_FAR test). A miss passes its
-//     colour through with age 0. A reprojection that lands on a miss texel has confidence 0; the reference gets there through an infinite
-//     reconstructed position, here it is stated.
+// What the HLSL leaves to the rasteriser and the samplers is DEFINED in pt_image.h, whose functions are used: pixel uv, the linear and the
+// point sampler (every float -> int conversion is defined for every input), ReconstructWorldPos from the view depth, log. Here:
+//   * exp = hrt_exp, pow = hrt_pow
+//   * a miss (depth.x == kMissDepth) passes its colour through with age 0. A reprojection that lands on a miss texel has confidence 0; the
+//     reference gets there through an infinite reconstructed position, here it is stated.
 //
 // Differences from the reference pass, on purpose:
 //   * no history (first frame, reset, resize): acc = 0 AND confidence = 0, so temporalMix = 0, the output is the input and the age is 0.
@@ -32,77 +27,27 @@
 #include <stdint.h>
 
 #include "../../include/hobbyrt_pt.h"
-#include "pt_bloom.h"
+#include "pt_image.h"
 
 namespace hrt {
 namespace temporal {
 
-constexpr float kMissDepth = 1e10f;           // HRPT_GB_DEPTH.x of a pixel whose primary ray hit nothing
-constexpr float kLn2 = 0.69314718f;
+using namespace img;
 
-struct T2 { float x, y; };
-struct T3 { float x, y, z; };
-struct T4 { float x, y, z, w; };
-HRT_FN T2 t2(float x, float y) { T2 r; r.x = x; r.y = y; return r; }
-HRT_FN T3 t3(float x, float y, float z) { T3 r; r.x = x; r.y = y; r.z = z; return r; }
-HRT_FN T4 t4(float x, float y, float z, float w) { T4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
-HRT_FN T4 load4(const float* img, int w, int x, int y) { const float* p = img + ((size_t)y * (size_t)w + (size_t)x) * 4; return t4(p[0], p[1], p[2], p[3]); }
-HRT_FN T3 sub(T3 a, T3 b) { return t3(a.x - b.x, a.y - b.y, a.z - b.z); }
-HRT_FN float dot3(T3 a, T3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-HRT_FN float length3(T3 a) { return hrt_sqrt(dot3(a, a)); }
-HRT_FN float length2(T2 a) { return hrt_sqrt(a.x * a.x + a.y * a.y); }
-HRT_FN float lerp(float a, float b, float t) { return a + t * (b - a); }                      // pt_device.h:66
-HRT_FN float ln(float x) { return hrt_log2(x) * kLn2; }
-
-// The members of the two HrptPlanarViewConstants the pass reads, gathered once per call.
+// The view and what else the pass reads of the two HrptPlanarViewConstants and the params, gathered once per call.
 struct Args {
-    float clipToWorld[16];          // view->m_MatClipToWorld
-    float p10, p14;                 // view->m_MatViewToClip[10], [14]
-    float size[2], sizeInv[2];      // view->m_ViewportSize, m_ViewportSizeInv
-    float cam[3];                   // view->m_CameraDirectionOrPosition.xyz
+    ViewArgs view;
     float jitterOffsetUV[2];        // (prevView->m_PixelOffset - view->m_PixelOffset) * m_ViewportSizeInv
     float blend;
     uint32_t flags;
-    int w, h;
 };
 HRT_FN Args make_args(const HrptPlanarViewConstants& view, const HrptPlanarViewConstants& prev, float blend, uint32_t flags, int w, int h)
 {
     Args a;
-    for (int i = 0; i < 16; ++i) a.clipToWorld[i] = view.m_MatClipToWorld[i];
-    a.p10 = view.m_MatViewToClip[10]; a.p14 = view.m_MatViewToClip[14];
-    for (int i = 0; i < 2; ++i) {
-        a.size[i] = view.m_ViewportSize[i]; a.sizeInv[i] = view.m_ViewportSizeInv[i];
-        a.jitterOffsetUV[i] = (prev.m_PixelOffset[i] - view.m_PixelOffset[i]) * view.m_ViewportSizeInv[i];
-    }
-    for (int i = 0; i < 3; ++i) a.cam[i] = view.m_CameraDirectionOrPosition[i];
-    a.blend = blend; a.flags = flags; a.w = w; a.h = h;
+    a.view = make_view_args(view, w, h);
+    for (int i = 0; i < 2; ++i) a.jitterOffsetUV[i] = (prev.m_PixelOffset[i] - view.m_PixelOffset[i]) * view.m_ViewportSizeInv[i];
+    a.blend = blend; a.flags = flags;
     return a;
-}
-
-// ---- samplers ------------------------------------------------------------------------------------------------------------------------
-HRT_FN int point_index(float r, int n) { return (int)hrt_clamp(hrt_floor(r * (float)n), 0.0f, (float)(n - 1)); }
-HRT_FN T4 lerp4(T4 a, T4 b, float t)
-{
-    const float w = 1.0f - t;
-    return t4(a.x * w + b.x * t, a.y * w + b.y * t, a.z * w + b.z * t, a.w * w + b.w * t);
-}
-HRT_FN T4 sample_linear(const float* img, int w, int h, float u, float v)
-{
-    const bloom::Taps t = bloom::taps(u, v, w, h);
-    return lerp4(lerp4(load4(img, w, t.x0, t.y0), load4(img, w, t.x1, t.y0), t.fx), lerp4(load4(img, w, t.x0, t.y1), load4(img, w, t.x1, t.y1), t.fx), t.fy);
-}
-
-// ---- ReconstructWorldPos (Common.hlsli:50-53, 167-172) from a view depth ------------------------------------------------------------
-HRT_FN T3 recon(const Args& a, float u, float v, float vd)
-{
-    const float z = (vd * a.p10 + a.p14) / vd;
-    const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;                                // UVToClipXY
-    const float* M = a.clipToWorld;                                                          // float4(clipXY, z, 1) * M, left to right
-    const float hx = ((cx * M[0] + cy * M[4]) + z * M[8]) + 1.0f * M[12];
-    const float hy = ((cx * M[1] + cy * M[5]) + z * M[9]) + 1.0f * M[13];
-    const float hz = ((cx * M[2] + cy * M[6]) + z * M[10]) + 1.0f * M[14];
-    const float hw = ((cx * M[3] + cy * M[7]) + z * M[11]) + 1.0f * M[15];
-    return t3(hx / hw, hy / hw, hz / hw);
 }
 
 // ---- SampleTextureCatmullRom (Common.hlsli:111-164) ----------------------------------------------------------------------------------
@@ -155,14 +100,14 @@ HRT_FN float validate(const Args& a, const float* motion, const float* depth, bo
 {
     if (!haveHistory) return 0.0f;
     if (reprojUV.x < 0.0f || reprojUV.x > 1.0f || reprojUV.y < 0.0f || reprojUV.y > 1.0f) return 0.0f;
-    const int qx = point_index(reprojUV.x, a.w), qy = point_index(reprojUV.y, a.h);
-    const T4 lastDepth = load4(depth, a.w, qx, qy);
+    const int qx = point_index(reprojUV.x, a.view.w), qy = point_index(reprojUV.y, a.view.h);
+    const T4 lastDepth = load4(depth, a.view.w, qx, qy);
     if (lastDepth.x == kMissDepth) return 0.0f;
-    const T4 lastMotion = load4(motion, a.w, qx, qy);
-    const T2 lastVelocityUV = t2(lastMotion.x * a.sizeInv[0], lastMotion.y * a.sizeInv[1]);
-    const T3 lastWorldPos = recon(a, reprojUV.x, reprojUV.y, lastDepth.y);
+    const T4 lastMotion = load4(motion, a.view.w, qx, qy);
+    const T2 lastVelocityUV = t2(lastMotion.x * a.view.sizeInv[0], lastMotion.y * a.view.sizeInv[1]);
+    const T3 lastWorldPos = recon(a.view, reprojUV.x, reprojUV.y, lastDepth.y);
 
-    const float viewDist = length3(sub(worldPos, t3(a.cam[0], a.cam[1], a.cam[2])));
+    const float viewDist = length3(sub(worldPos, t3(a.view.cam[0], a.view.cam[1], a.view.cam[2])));
     const float distFactor = 1.0f + 1.0f / (viewDist + 1.0f);
 
     const T3 d = sub(worldPos, lastWorldPos);
@@ -178,27 +123,27 @@ HRT_FN float validate(const Args& a, const float* motion, const float* depth, bo
 HRT_FN void pixel(const Args& a, const float* color, const float* motion, const float* depth, const float* normal, const float* historyIn,
                   int px, int py, T4* historyOut, T4* colorOut)
 {
-    const int W = a.w, H = a.h;
+    const int W = a.view.w, H = a.view.h;
     const T4 C = load4(color, W, px, py), D = load4(depth, W, px, py);
     if (D.x == kMissDepth) { *historyOut = t4(C.x, C.y, C.z, 0.0f); *colorOut = C; return; }
 
     const float u = bloom::pixel_u(px, W), v = bloom::pixel_u(py, H);
-    const T3 worldPos = recon(a, u, v, D.y);
+    const T3 worldPos = recon(a.view, u, v, D.y);
     const T4 N4 = load4(normal, W, px, py);
     const T3 worldNormal = t3(N4.x, N4.y, N4.z);
 
     const T4 mv = load4(motion, W, px, py);
-    const T2 velocityUV = t2(mv.x * a.sizeInv[0], mv.y * a.sizeInv[1]);
+    const T2 velocityUV = t2(mv.x * a.view.sizeInv[0], mv.y * a.view.sizeInv[1]);
     const T2 reprojUV = t2(u + velocityUV.x, v + velocityUV.y);
     const T2 reprojNoJitter = t2(reprojUV.x - a.jitterOffsetUV[0], reprojUV.y - a.jitterOffsetUV[1]);
 
     const bool haveHistory = historyIn != nullptr;
     float confidence = validate(a, motion, depth, haveHistory, reprojNoJitter, worldPos, worldNormal, velocityUV);
 
-    const float moveFactor = hrt_saturate(length2(t2(velocityUV.x * a.size[0], velocityUV.y * a.size[1])) - 1.0f);
+    const float moveFactor = hrt_saturate(length2(t2(velocityUV.x * a.view.size[0], velocityUV.y * a.view.size[1])) - 1.0f);
 
     // SSGITemporalAccumulate, bWasSampled = true
-    T4 acc = haveHistory ? catmull_rom(historyIn, W, H, reprojUV.x, reprojUV.y, a.size[0], a.size[1]) : t4(0.0f, 0.0f, 0.0f, 0.0f);
+    T4 acc = haveHistory ? catmull_rom(historyIn, W, H, reprojUV.x, reprojUV.y, a.view.size[0], a.view.size[1]) : t4(0.0f, 0.0f, 0.0f, 0.0f);
     const bool linear = (a.flags & HRPT_TEMPORAL_LINEAR) != 0;
     T3 inp = t3(C.x, C.y, C.z);
     if (!linear) {

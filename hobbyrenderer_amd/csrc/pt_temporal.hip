@@ -7,15 +7,15 @@
 // The history is read in the plain form: the 13 bilinear taps of SampleTextureCatmullRom, 52 float4 loads per pixel, all inside a
 // 4 x 4 texel footprint (give or take the texel the uv round trip may move a floor by), which neighbouring lanes share -- they are served
 // by the vector cache, not by HBM. No LDS: the footprint of a tile follows the motion vectors, which differ per pixel.
-#include <hip/hip_runtime.h>
-
-#include "pt_temporal.h"
+#include "pt_image_kernel.h"
 #include "pt_kernels.h"
+#include "pt_temporal.h"
 
 namespace hrt {
 
 namespace {
-constexpr int kTileX = 32, kTileY = 8;
+using img::kTileX;
+using img::kTileY;
 
 // color and colorOut may be the same image (no __restrict__ on them): a thread reads its own colour texel before it writes it.
 __global__ __launch_bounds__(kTileX * kTileY) void temporal_accumulate(temporal::Args a, const float* color, const float* __restrict__ motion,
@@ -23,28 +23,23 @@ __global__ __launch_bounds__(kTileX * kTileY) void temporal_accumulate(temporal:
                                                                        const float* __restrict__ historyIn, float4* __restrict__ historyOut,
                                                                        float4* colorOut)
 {
-    const int px = blockIdx.x * kTileX + threadIdx.x, py = blockIdx.y * kTileY + threadIdx.y;
-    if (px >= a.w || py >= a.h) return;
-    temporal::T4 hist, col;
+    int px, py;
+    if (!img::stage_pixel(a.view.w, a.view.h, &px, &py)) return;
+    img::T4 hist, col;
     temporal::pixel(a, color, motion, depth, normal, historyIn, px, py, &hist, &col);
-    const size_t idx = (size_t)py * (size_t)a.w + (size_t)px;
-    historyOut[idx] = make_float4(hist.x, hist.y, hist.z, hist.w);
-    colorOut[idx] = make_float4(col.x, col.y, col.z, col.w);
+    const size_t idx = img::stage_index(a.view.w, px, py);
+    img::st4(historyOut, idx, hist);
+    img::st4(colorOut, idx, col);
 }
 } // namespace
 
-bool temporal_params_valid(const HrptTemporalParams& p)
-{
-    return p.blend >= 0.0f && p.blend <= 1.0f && (p.flags & ~(HRPT_TEMPORAL_LINEAR | HRPT_TEMPORAL_RESET)) == 0u && p.reserved[0] == 0u && p.reserved[1] == 0u;
-}
-
-hipError_t launch_temporal(const HrptTemporalImages& img, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
+hipError_t launch_temporal(const HrptTemporalImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
                            const HrptPlanarViewConstants& prevView, const HrptTemporalParams& params, hipStream_t stream)
 {
     const temporal::Args a = temporal::make_args(view, prevView, params.blend, params.flags, (int)width, (int)height);
-    const dim3 grid((width + kTileX - 1) / kTileX, (height + kTileY - 1) / kTileY), block(kTileX, kTileY);
-    hipLaunchKernelGGL(temporal_accumulate, grid, block, 0, stream, a, img.color, img.motion, img.depth, img.normal, img.historyIn,
-                       reinterpret_cast<float4*>(img.historyOut), reinterpret_cast<float4*>(img.colorOut));
+    hipLaunchKernelGGL(temporal_accumulate, img::stage_grid(width, height), img::stage_block(), 0, stream, a, images.color, images.motion,
+                       images.depth, images.normal, images.historyIn, reinterpret_cast<float4*>(images.historyOut),
+                       reinterpret_cast<float4*>(images.colorOut));
     return hipGetLastError();
 }
 

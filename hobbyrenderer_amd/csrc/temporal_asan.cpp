@@ -3,13 +3,7 @@
 // every image edge, reprojection outside [0, 1]), hostile values (NaN, inf, huge motion, zero and negative depth) sprinkled in, in both
 // colour spaces, with and without history, three chained frames. Any out-of-bounds read, undefined float -> int conversion or other report
 // ends the program with a non-zero status.   usage: temporal_asan [seed]
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <vector>
-
+#include "asan_common.h"
 #include "pt_temporal.h"
 
 namespace hrt {
@@ -17,31 +11,10 @@ void temporal_host(const HrptTemporalImages& images, uint32_t width, uint32_t he
                    const HrptPlanarViewConstants& prevView, const HrptTemporalParams& params, int nthreads);
 }
 
-static uint32_t g_state = 1;
-static float rnd() { g_state = hrt_pcg_hash(g_state); return (float)(g_state >> 8) * (1.0f / 16777216.0f); }
-
-static HrptPlanarViewConstants make_view(int w, int h, float ox, float oy)
-{
-    HrptPlanarViewConstants v;
-    std::memset(&v, 0, sizeof v);
-    const float n = 0.1f, sx = 1.2f, sy = 1.2f * (float)w / (float)h;
-    float* P = v.m_MatViewToClip;                   // reversed-Z, infinite far plane
-    P[0] = sx; P[5] = sy; P[11] = 1.0f; P[14] = n;
-    float* M = v.m_MatClipToWorld;                  // its inverse (camera at the origin of the world, shifted below)
-    M[0] = 1.0f / sx; M[5] = 1.0f / sy; M[11] = 1.0f / n; M[14] = 1.0f;
-    M[12] = 0.0f; M[13] = 0.0f;
-    v.m_ViewportSize[0] = (float)w; v.m_ViewportSize[1] = (float)h;
-    v.m_ViewportSizeInv[0] = 1.0f / (float)w; v.m_ViewportSizeInv[1] = 1.0f / (float)h;
-    v.m_PixelOffset[0] = ox; v.m_PixelOffset[1] = oy;
-    v.m_CameraDirectionOrPosition[3] = 1.0f;
-    return v;
-}
-
 static int run(int w, int h, float reach, bool hostile)
 {
     const size_t n = (size_t)w * h * 4;
     std::vector<float> color(n), motion(n), depth(n), normal(n), histA(n), histB(n), out(n);
-    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
     int calls = 0;
     for (int frame = 0; frame < 3; ++frame) {
         for (int y = 0; y < h; ++y)
@@ -54,9 +27,8 @@ static int run(int w, int h, float reach, bool hostile)
                 depth[i] = miss ? 1e10f : vd; depth[i + 1] = miss ? 1e10f : vd; depth[i + 2] = rnd(); depth[i + 3] = rnd();
                 normal[i] = 0.0f; normal[i + 1] = 0.6f; normal[i + 2] = -0.8f; normal[i + 3] = 0.5f;
                 if (hostile && rnd() < 0.1f) {
-                    const float bad[] = { nan, inf, -inf, 3e38f, -3e38f, 0.0f, -1.0f, 1e-42f };
                     float* planes[] = { color.data(), motion.data(), depth.data(), normal.data() };
-                    planes[(int)(rnd() * 3.999f)][i + (int)(rnd() * 3.999f)] = bad[(int)(rnd() * 7.999f)];
+                    planes[(int)(rnd() * 3.999f)][i + (int)(rnd() * 3.999f)] = kBad[(int)(rnd() * 7.999f)];
                 }
             }
         for (uint32_t flags = 0; flags < 2; ++flags)
@@ -71,17 +43,16 @@ static int run(int w, int h, float reach, bool hostile)
                     ++calls;
                 }
         histA.swap(histB);
-        if (hostile) for (size_t i = 0; i < n; i += 7) if (rnd() < 0.02f) histA[i] = (rnd() < 0.5f) ? nan : inf;
+        if (hostile) for (size_t i = 0; i < n; i += 7) if (rnd() < 0.02f) histA[i] = (rnd() < 0.5f) ? kNan : kInf;
     }
     return calls;
 }
 
 int main(int argc, char** argv)
 {
-    g_state = argc > 1 ? (uint32_t)std::strtoul(argv[1], nullptr, 10) : 1u;
+    seed_from(argc, argv);
     int calls = 0;
-    const int sizes[][2] = { { 1, 1 }, { 2, 3 }, { 37, 23 }, { 64, 36 } };
-    for (const auto& s : sizes)
+    for (const auto& s : kSizes)
         for (int hostile = 0; hostile < 2; ++hostile) {
             calls += run(s[0], s[1], 4.0f, hostile != 0);
             calls += run(s[0], s[1], 0.9f, hostile != 0);

@@ -122,6 +122,45 @@ class HrptError(RuntimeError):
         self.code = code
 
 
+def _check_rc(rc):
+    """A call without a context: its message is the library's process-wide one."""
+    if rc != 0:
+        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+_COUNT_WORDS = {2: "two", 4: "four", 5: "five"}
+
+
+def _same_shape_images(name, required, **optional):
+    """The image arguments of a host wrapper as contiguous float32 arrays: `required` all [H, W, 4] of one shape, each optional one None or
+    of that shape. Returns (required, optional in the order given, shape)."""
+    imgs = [np.ascontiguousarray(a, np.float32) for a in required]
+    shape = imgs[0].shape
+    if len(shape) != 3 or shape[2] != 4 or any(a.shape != shape for a in imgs):
+        raise ValueError(f"{name}: {_COUNT_WORDS[len(imgs)]} float32 [H, W, 4] images of one size expected")
+    opt = []
+    for key, a in optional.items():
+        a = None if a is None else np.ascontiguousarray(a, np.float32)
+        if a is not None and a.shape != shape:
+            raise ValueError(f"{name}: {key} must have the images' shape")
+        opt.append(a)
+    return imgs, opt, shape
+
+
+def _frame_params(constants, accum_count, tile, flags, stripes):
+    p = np.zeros((), S.FrameParams)
+    p["stripeCount"], p["stripeIndex"] = stripes
+    p["constants"] = constants
+    p["accumCount"] = accum_count
+    p["tileX0"], p["tileY0"], p["tileX1"], p["tileY1"] = tile
+    p["flags"] = flags
+    return p
+
+
 ATMOSPHERE_ORDERS = 4        # scattering orders of the default tables (Bruneton's demo value; the reference's own count is unknown)
 
 
@@ -175,9 +214,7 @@ def bloom_host(img, params=None, nthreads=0):
         raise ValueError("bloom_host: float32 [H, W, 4] image expected")
     params = params if params is not None else S.BloomParams()
     out = np.empty_like(img)
-    rc = lib.hrpt_bloom_host(img.ctypes.data, out.ctypes.data, img.shape[1], img.shape[0], C.byref(params), int(nthreads))
-    if rc != 0:
-        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    _check_rc(lib.hrpt_bloom_host(img.ctypes.data, out.ctypes.data, img.shape[1], img.shape[0], C.byref(params), int(nthreads)))
     return out
 
 
@@ -186,9 +223,7 @@ def bloom_pack_probe(rgb):
     rgb = np.ascontiguousarray(rgb, np.float32)
     packed = np.empty(rgb.shape[:-1], np.uint32)
     unpacked = np.empty_like(rgb)
-    rc = lib.hrpt_bloom_pack_probe(rgb.ctypes.data, packed.size, packed.ctypes.data, unpacked.ctypes.data)
-    if rc != 0:
-        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    _check_rc(lib.hrpt_bloom_pack_probe(rgb.ctypes.data, packed.size, packed.ctypes.data, unpacked.ctypes.data))
     return packed, unpacked
 
 
@@ -203,20 +238,12 @@ def temporal_host(color, motion, depth, normal, history, view, prev_view, params
     view / prev_view: S.PlanarViewConstants of this and of last frame. view["m_ViewportSize"] must be (W, H), and
     view["m_CameraDirectionOrPosition"] must hold (camera position, 1): scenes.planar_view leaves it zero, the caller fills it.
     Returns (colour out, history out): rgb = blended radiance in both, alpha = color's alpha / the age."""
-    imgs = [np.ascontiguousarray(a, np.float32) for a in (color, motion, depth, normal)]
-    shape = imgs[0].shape
-    if len(shape) != 3 or shape[2] != 4 or any(a.shape != shape for a in imgs):
-        raise ValueError("temporal_host: four float32 [H, W, 4] images of one size expected")
-    hist = None if history is None else np.ascontiguousarray(history, np.float32)
-    if hist is not None and hist.shape != shape:
-        raise ValueError("temporal_host: history must have the images' shape")
+    imgs, (hist,), shape = _same_shape_images("temporal_host", (color, motion, depth, normal), history=history)
     params = params if params is not None else S.TemporalParams()
     out, hout = np.empty(shape, np.float32), np.empty(shape, np.float32)
-    im = S.TemporalImages(*[a.ctypes.data for a in imgs], None if hist is None else hist.ctypes.data, hout.ctypes.data, out.ctypes.data)
+    im = S.TemporalImages(*[a.ctypes.data for a in imgs], _ptr(hist), hout.ctypes.data, out.ctypes.data)
     v, pv = _view_record(view), _view_record(prev_view)
-    rc = lib.hrpt_temporal_host(C.byref(im), shape[1], shape[0], v.ctypes.data, pv.ctypes.data, C.byref(params), int(nthreads))
-    if rc != 0:
-        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    _check_rc(lib.hrpt_temporal_host(C.byref(im), shape[1], shape[0], v.ctypes.data, pv.ctypes.data, C.byref(params), int(nthreads)))
     return out, hout
 
 
@@ -227,25 +254,17 @@ def denoise_host(input, depth, normal, geo_normal, view, params=None, noise=None
     noise: a float32 [64, 64, 2] tile, or None for the library's default tile (white noise); color: an image whose alpha the second
     result keeps. view: as for temporal_host. params.iterations must be 1; params.radius and params.frame are used as given.
     Returns output = (filtered rgb, age), or (output, colorOut) when color is given."""
-    imgs = [np.ascontiguousarray(a, np.float32) for a in (input, depth, normal, geo_normal)]
-    shape = imgs[0].shape
-    if len(shape) != 3 or shape[2] != 4 or any(a.shape != shape for a in imgs):
-        raise ValueError("denoise_host: four float32 [H, W, 4] images of one size expected")
+    imgs, _, shape = _same_shape_images("denoise_host", (input, depth, normal, geo_normal))
     tile = None if noise is None else np.ascontiguousarray(noise, np.float32)
     if tile is not None and tile.shape != (64, 64, 2):
         raise ValueError("denoise_host: noise must be a float32 [64, 64, 2] tile")
-    col = None if color is None else np.ascontiguousarray(color, np.float32)
-    if col is not None and col.shape != shape:
-        raise ValueError("denoise_host: color must have the images' shape")
+    _, (col,), _ = _same_shape_images("denoise_host", imgs, color=color)      # checked after the tile, as before the helper existed
     params = params if params is not None else S.DenoiseParams()
     out = np.empty(shape, np.float32)
     cout = None if col is None else np.empty(shape, np.float32)
-    im = S.DenoiseImages(*[a.ctypes.data for a in imgs], None if tile is None else tile.ctypes.data, out.ctypes.data,
-                         None if col is None else col.ctypes.data, None if cout is None else cout.ctypes.data)
+    im = S.DenoiseImages(*[a.ctypes.data for a in imgs], _ptr(tile), out.ctypes.data, _ptr(col), _ptr(cout))
     v = _view_record(view)
-    rc = lib.hrpt_denoise_host(C.byref(im), shape[1], shape[0], v.ctypes.data, C.byref(params), int(nthreads))
-    if rc != 0:
-        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    _check_rc(lib.hrpt_denoise_host(C.byref(im), shape[1], shape[0], v.ctypes.data, C.byref(params), int(nthreads)))
     return out if cout is None else (out, cout)
 
 
@@ -267,38 +286,22 @@ def demodulate_host(color, albedo, normal, geo_normal, depth, view, params=None,
     normal / geo_normal / depth / emissive: the planes S.GB_ALBEDO / S.GB_NORMAL / S.GB_GEO_NORMAL / S.GB_DEPTH / S.GB_EMISSIVE of the same
     frame (emissive None = 0). view: as for temporal_host. Returns (colour out, modulation): colour out = (max(rgb - E, 0) / Mf, alpha),
     modulation = (Mf, 1) at a hit and (1, 1, 1, 0) at a miss."""
-    imgs = [np.ascontiguousarray(a, np.float32) for a in (color, albedo, normal, geo_normal, depth)]
-    shape = imgs[0].shape
-    if len(shape) != 3 or shape[2] != 4 or any(a.shape != shape for a in imgs):
-        raise ValueError("demodulate_host: five float32 [H, W, 4] images of one size expected")
-    em = None if emissive is None else np.ascontiguousarray(emissive, np.float32)
-    if em is not None and em.shape != shape:
-        raise ValueError("demodulate_host: emissive must have the images' shape")
+    imgs, (em,), shape = _same_shape_images("demodulate_host", (color, albedo, normal, geo_normal, depth), emissive=emissive)
     params = params if params is not None else S.ModulationParams()
     out, mod = np.empty(shape, np.float32), np.empty(shape, np.float32)
-    im = S.DemodulateImages(*[a.ctypes.data for a in imgs], None if em is None else em.ctypes.data, out.ctypes.data, mod.ctypes.data)
+    im = S.DemodulateImages(*[a.ctypes.data for a in imgs], _ptr(em), out.ctypes.data, mod.ctypes.data)
     v = _view_record(view)
-    rc = lib.hrpt_demodulate_host(C.byref(im), shape[1], shape[0], v.ctypes.data, C.byref(params), int(nthreads))
-    if rc != 0:
-        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    _check_rc(lib.hrpt_demodulate_host(C.byref(im), shape[1], shape[0], v.ctypes.data, C.byref(params), int(nthreads)))
     return out, mod
 
 
 def compose_host(color, modulation, emissive=None, nthreads=0):
     """hrpt_compose_host: the compose stage on host threads: (rgb * Mf + E, alpha) with Mf from `modulation` (what demodulate_host
     returned); a texel whose modulation alpha is 0 (a miss) passes through. Bit-identical to PathTracerContext.compose / compose_device."""
-    imgs = [np.ascontiguousarray(a, np.float32) for a in (color, modulation)]
-    shape = imgs[0].shape
-    if len(shape) != 3 or shape[2] != 4 or imgs[1].shape != shape:
-        raise ValueError("compose_host: two float32 [H, W, 4] images of one size expected")
-    em = None if emissive is None else np.ascontiguousarray(emissive, np.float32)
-    if em is not None and em.shape != shape:
-        raise ValueError("compose_host: emissive must have the images' shape")
+    imgs, (em,), shape = _same_shape_images("compose_host", (color, modulation), emissive=emissive)
     out = np.empty(shape, np.float32)
-    im = S.ComposeImages(imgs[0].ctypes.data, imgs[1].ctypes.data, None if em is None else em.ctypes.data, out.ctypes.data)
-    rc = lib.hrpt_compose_host(C.byref(im), shape[1], shape[0], int(nthreads))
-    if rc != 0:
-        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    im = S.ComposeImages(imgs[0].ctypes.data, imgs[1].ctypes.data, _ptr(em), out.ctypes.data)
+    _check_rc(lib.hrpt_compose_host(C.byref(im), shape[1], shape[0], int(nthreads)))
     return out
 
 
@@ -307,9 +310,7 @@ def modulation_probe(albedo, normal, view_dir, rough, metal, floor=0.04):
     camera given directly instead of reconstructed from a depth."""
     a, n, v = [np.ascontiguousarray(x, np.float32).reshape(3) for x in (albedo, normal, view_dir)]
     out = np.empty(3, np.float32)
-    rc = lib.hrpt_modulation_probe(a.ctypes.data, n.ctypes.data, v.ctypes.data, float(rough), float(metal), float(floor), out.ctypes.data)
-    if rc != 0:
-        raise HrptError(rc, lib.hrpt_last_error(None).decode())
+    _check_rc(lib.hrpt_modulation_probe(a.ctypes.data, n.ctypes.data, v.ctypes.data, float(rough), float(metal), float(floor), out.ctypes.data))
     return out
 
 
@@ -344,9 +345,7 @@ def host_build_bvh(scene, structure=S.ACCEL_FLAT, separate_collapse=False):
     desc, keep = scene.desc()
 
     def call(d):
-        rc = lib.hrpt_selftest_host_build(C.byref(desc), int(structure), S.HOST_BUILD_SEPARATE_COLLAPSE if separate_collapse else 0, C.byref(d))
-        if rc != 0:
-            raise HrptError(rc, lib.hrpt_last_error(None).decode())
+        _check_rc(lib.hrpt_selftest_host_build(C.byref(desc), int(structure), S.HOST_BUILD_SEPARATE_COLLAPSE if separate_collapse else 0, C.byref(d)))
     out = _read_bvh_dump(call)
     del keep
     return out
@@ -366,14 +365,23 @@ class PathTracerContext:
     def __init__(self, device=0):
         self._h = C.c_void_p()
         desc = S.DeviceDesc(device, S.ABI_VERSION)
-        rc = lib.hrpt_create(C.byref(desc), C.byref(self._h))
-        if rc != 0:
-            raise HrptError(rc, lib.hrpt_last_error(None).decode())
+        _check_rc(lib.hrpt_create(C.byref(desc), C.byref(self._h)))
         self.width = self.height = 0
 
     def _check(self, rc):
         if rc != 0:
             raise HrptError(rc, lib.hrpt_last_error(self._h).decode())
+
+    def _read_image(self, fn, dtype=np.float32, args=()):
+        """A context image of the current size, [H, W, 4], through one of the library's readers (synchronises)."""
+        out = np.empty((self.height, self.width, 4), dtype)
+        self._check(fn(self._h, *args, out.ctypes.data, out.nbytes))
+        return out
+
+    def _device_ptr(self, fn, args=()):
+        ptr = C.c_void_p()
+        self._check(fn(self._h, *args, C.byref(ptr)))
+        return ptr.value
 
     def close(self):
         if self._h:
@@ -397,61 +405,38 @@ class PathTracerContext:
 
     def render(self, constants, accum_count=1, tile=(0, 0, 0, 0), flags=S.FRAME_DEFAULT, stripes=(1, 0)):
         """stripes = (count, index): of the tile's 8-pixel columns only those with column % count == index are rendered."""
-        p = np.zeros((), S.FrameParams)
-        p["stripeCount"], p["stripeIndex"] = stripes
-        p["constants"] = constants
-        p["accumCount"] = accum_count
-        p["tileX0"], p["tileY0"], p["tileX1"], p["tileY1"] = tile
-        p["flags"] = flags
+        p = _frame_params(constants, accum_count, tile, flags, stripes)
         self._check(lib.hrpt_render(self._h, p.ctypes.data))
 
     def render_gbuffer(self, constants, planes=S.GB_ALL_PLANES, tile=(0, 0, 0, 0), flags=S.FRAME_DEFAULT, stripes=(1, 0)):
         """hrpt_render_gbuffer: what the primary rays of one accumulation index saw (path vertex 0), into the planes of the bit mask `planes`
         (1 << S.GB_ALBEDO ...). constants.m_Jitter is used as given; tile / flags / stripes as in render. Asynchronous."""
-        p = np.zeros((), S.FrameParams)
-        p["stripeCount"], p["stripeIndex"] = stripes
-        p["constants"] = constants
-        p["accumCount"] = 1
-        p["tileX0"], p["tileY0"], p["tileX1"], p["tileY1"] = tile
-        p["flags"] = flags
+        p = _frame_params(constants, 1, tile, flags, stripes)
         self._check(lib.hrpt_render_gbuffer(self._h, p.ctypes.data, int(planes)))
 
     def read_gbuffer(self, plane):
         """One G-buffer plane: float32 [H, W, 4], or uint32 [H, W, 4] for S.GB_IDS (synchronises)."""
-        out = np.empty((self.height, self.width, 4), np.uint32 if plane == S.GB_IDS else np.float32)
-        self._check(lib.hrpt_read_gbuffer(self._h, int(plane), out.ctypes.data, out.nbytes))
-        return out
+        return self._read_image(lib.hrpt_read_gbuffer, np.uint32 if plane == S.GB_IDS else np.float32, (int(plane),))
 
     def gbuffer_device(self, plane):
         """Device pointer of one G-buffer plane (None when it was never requested)."""
-        ptr = C.c_void_p()
-        self._check(lib.hrpt_get_gbuffer_device(self._h, int(plane), C.byref(ptr)))
-        return ptr.value
+        return self._device_ptr(lib.hrpt_get_gbuffer_device, (int(plane),))
 
     def render_motion_vectors(self, constants, prev_view, planes=0, tile=(0, 0, 0, 0), flags=S.FRAME_DEFAULT, stripes=(1, 0)):
         """hrpt_render_motion_vectors: screen-space motion of the first hit (previous minus current window position in pixels, change of view
         depth, valid flag) for constants["m_View"] against last frame's `prev_view` (S.PlanarViewConstants) and the instances' m_PrevWorld.
         `planes`: G-buffer planes to write in the same pass (0 = motion only). tile / flags / stripes as in render_gbuffer. Asynchronous."""
-        p = np.zeros((), S.FrameParams)
-        p["stripeCount"], p["stripeIndex"] = stripes
-        p["constants"] = constants
-        p["accumCount"] = 1
-        p["tileX0"], p["tileY0"], p["tileX1"], p["tileY1"] = tile
-        p["flags"] = flags
+        p = _frame_params(constants, 1, tile, flags, stripes)
         pv = np.ascontiguousarray(np.asarray(prev_view, S.PlanarViewConstants))
         self._check(lib.hrpt_render_motion_vectors(self._h, p.ctypes.data, pv.ctypes.data, int(planes)))
 
     def read_motion_vectors(self):
         """The motion plane: float32 [H, W, 4] (synchronises)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._check(lib.hrpt_read_motion_vectors(self._h, out.ctypes.data, out.nbytes))
-        return out
+        return self._read_image(lib.hrpt_read_motion_vectors)
 
     def motion_vectors_device(self):
         """Device pointer of the motion plane (None before the first render_motion_vectors)."""
-        ptr = C.c_void_p()
-        self._check(lib.hrpt_get_motion_vectors_device(self._h, C.byref(ptr)))
-        return ptr.value
+        return self._device_ptr(lib.hrpt_get_motion_vectors_device)
 
     def set_stream(self, hip_stream):
         """hip_stream: integer handle (e.g. torch.cuda.current_stream().cuda_stream; 0 = the default stream), or None to go
@@ -470,14 +455,10 @@ class PathTracerContext:
         return a.value, o.value
 
     def read_accumulation(self):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._check(lib.hrpt_read_accumulation(self._h, out.ctypes.data, out.nbytes))
-        return out
+        return self._read_image(lib.hrpt_read_accumulation)
 
     def read_output(self):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._check(lib.hrpt_read_output(self._h, out.ctypes.data, out.nbytes))
-        return out
+        return self._read_image(lib.hrpt_read_output)
 
     def write_accumulation(self, img):
         img = np.ascontiguousarray(img, np.float32)
@@ -592,15 +573,11 @@ class PathTracerContext:
 
     def read_temporal_history(self):
         """The history the last temporal_accumulate wrote: float32 [H, W, 4], rgb = accumulated radiance, a = age (synchronises)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._check(lib.hrpt_read_temporal_history(self._h, out.ctypes.data, out.nbytes))
-        return out
+        return self._read_image(lib.hrpt_read_temporal_history)
 
     def temporal_history_device(self):
         """Device pointer of that image (None before the first temporal_accumulate)."""
-        ptr = C.c_void_p()
-        self._check(lib.hrpt_get_temporal_history_device(self._h, C.byref(ptr)))
-        return ptr.value
+        return self._device_ptr(lib.hrpt_get_temporal_history_device)
 
     def denoise(self, view, params=None):
         """hrpt_denoise: the edge-stopping Poisson filter over the temporal history (csrc/pt_denoise.h), after
@@ -657,20 +634,14 @@ class PathTracerContext:
 
     def read_modulation(self):
         """The factor image the last demodulate wrote: float32 [H, W, 4], rgb = Mf, a = 1 at a hit, 0 at a miss (synchronises)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._check(lib.hrpt_read_modulation(self._h, out.ctypes.data, out.nbytes))
-        return out
+        return self._read_image(lib.hrpt_read_modulation)
 
     def modulation_device(self):
         """Device pointer of that image (None before the first demodulate and after a resize)."""
-        ptr = C.c_void_p()
-        self._check(lib.hrpt_get_modulation_device(self._h, C.byref(ptr)))
-        return ptr.value
+        return self._device_ptr(lib.hrpt_get_modulation_device)
 
     def read_display(self):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._check(lib.hrpt_read_display(self._h, out.ctypes.data, out.nbytes))
-        return out
+        return self._read_image(lib.hrpt_read_display)
 
     def exposure(self):
         e = C.c_float(); h = np.zeros(256, np.uint32)

@@ -119,6 +119,8 @@ def test_host_properties():
     assert (out[..., :3] >= img[..., :3]).all()                            # additive, bloom >= 0
     assert np.isfinite(out).all()
     assert np.array_equal(bits(out), bits(native.bloom_host(img, params(DEFAULTS), nthreads=8)))
+    for n in (0, -1, 1000):                                                # the clamp: one per hardware thread up to 16; at most 256
+        assert np.array_equal(bits(out), bits(native.bloom_host(img, params(DEFAULTS), nthreads=n))), n
     zero = native.bloom_host(img, params((0.1, 0.0, 0.85)), nthreads=2)
     assert np.array_equal(bits(zero), bits(img))                           # intensity 0: every bit as it was
     inplace = img.copy()                                                   # hdrOut may be hdrIn
@@ -130,17 +132,24 @@ def test_host_argument_errors():
     img = hdr_image(8, 8)
     out = np.empty_like(img)
     call = native.lib.hrpt_bloom_host
+    err = lambda: native.lib.hrpt_last_error(None).decode()          # noqa: E731 -- the whole text, as the library has always worded it
     ok = params(DEFAULTS)
     assert call(img.ctypes.data, out.ctypes.data, 8, 8, C.byref(ok), 1) == 0
     assert call(None, out.ctypes.data, 8, 8, C.byref(ok), 1) == INVALID_ARGUMENT
+    assert err() == "hrpt_bloom_host: null image"
     assert call(img.ctypes.data, None, 8, 8, C.byref(ok), 1) == INVALID_ARGUMENT
+    assert err() == "hrpt_bloom_host: null image"
     assert call(img.ctypes.data, out.ctypes.data, 8, 8, None, 1) == INVALID_ARGUMENT
+    assert err() == "hrpt_bloom_host: null params"
     assert call(img.ctypes.data, out.ctypes.data, 0, 8, C.byref(ok), 1) == INVALID_ARGUMENT
     assert call(img.ctypes.data, out.ctypes.data, 8, 70000, C.byref(ok), 1) == INVALID_ARGUMENT
+    for ww, hh in ((0, 8), (8, 0), (0, 0), (65536, 8), (8, 65536), (8, 70000)):
+        assert call(img.ctypes.data, out.ctypes.data, ww, hh, C.byref(ok), 1) == INVALID_ARGUMENT and err() == "hrpt_bloom_host: size must be 1..65535", (ww, hh)
     for bad in [(-0.1, 0.005, 0.85), (0.1, -1.0, 0.85), (0.1, 0.005, -0.5), (float("nan"), 0.005, 0.85), (0.1, float("inf"), 0.85),
                 (0.1, 0.005, float("nan"))]:
         assert call(img.ctypes.data, out.ctypes.data, 8, 8, C.byref(params(bad)), 1) == INVALID_ARGUMENT, bad
         assert b"hrpt_bloom_host" in native.lib.hrpt_last_error(None)
+        assert err() == "hrpt_bloom_host: knee, intensity and upsampleRadius must be finite and >= 0", bad
     with pytest.raises(native.HrptError):
         native.bloom_host(img, params((0.1, -1.0, 0.85)))
 

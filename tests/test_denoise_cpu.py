@@ -157,6 +157,8 @@ def test_thread_count_independence():
     one = lib_call(c, 12.0, 2, nthreads=1)
     for n in (2, 3, 7, 64):
         assert np.array_equal(u32(lib_call(c, 12.0, 2, nthreads=n)), u32(one)), n
+    for n in (0, -1, 1000):                                  # the clamp: one per hardware thread up to 16; at most 256, and no more than rows
+        assert np.array_equal(u32(lib_call(c, 12.0, 2, nthreads=n)), u32(one)), n
 
 
 def test_noise_reduction_on_a_flat_plane():
@@ -209,33 +211,50 @@ def test_argument_errors():
         p = p if p is not None else S.DenoiseParams()
         return native.lib.hrpt_denoise_host(C.byref(im) if im != "null" else None, ww, hh, v.ctypes.data if v is not None else None,
                                             C.byref(p) if p != "null" else None, 1)
+    err = lambda: native.lib.hrpt_last_error(None).decode()          # noqa: E731 -- the whole text, as the library has always worded it
+    PARAMS = ("hrpt_denoise_host: radius and phi must be finite and > 0, the other phis finite and >= 0, iterations 1..5 with "
+              "radius * 2^(iterations - 1) finite, flags HRPT_DENOISE_* only, reserved 0")
     assert call() == 0
     assert call(im="null") == -1 and call(v=None) == -1 and call(p="null") == -1
+    for kw in (dict(im="null"), dict(v=None), dict(p="null")):
+        assert call(**kw) == -1 and err() == "hrpt_denoise_host: null argument", kw
     for k in KEYS + ("output",):
         assert call(im=images(**{k: None})) == -1, k
+        assert err() == "hrpt_denoise_host: null image (only noise, and color with colorOut, may be NULL)", k
     assert call(im=images(noise=None)) == 0 and call(im=images(color=None, colorOut=None)) == 0
     assert call(im=images(color=None)) == -1 and call(im=images(colorOut=None)) == -1
     assert b"both" in native.lib.hrpt_last_error(None)
+    assert err() == "hrpt_denoise_host: color and colorOut must both be NULL or both be set"
     assert call(im=images(output=imgs[0].ctypes.data)) == -1
     assert b"output must differ" in native.lib.hrpt_last_error(None)
+    assert err() == "hrpt_denoise_host: output must differ from input"
     assert call(im=images(color=imgs[0].ctypes.data)) == -1 and call(im=images(colorOut=imgs[0].ctypes.data)) == -1
+    assert err() == "hrpt_denoise_host: color and colorOut must differ from input"
     assert call(im=images(colorOut=color.ctypes.data)) == 0
     wrong = view.copy(); wrong["m_ViewportSize"] = (w + 1, h)
     assert call(v=wrong) == -1
     assert b"m_ViewportSize" in native.lib.hrpt_last_error(None)
+    assert err() == "hrpt_denoise_host: view->m_ViewportSize does not match the image size"
     assert call(ww=0) == -1 and call(hh=0) == -1 and call(ww=65536) == -1
+    for ww, hh in ((0, h), (w, 0), (0, 0), (65536, h), (w, 65536)):       # reported before the view is compared with it
+        assert call(ww=ww, hh=hh) == -1 and err() == "hrpt_denoise_host: size must be 1..65535", (ww, hh)
     bad = (float("nan"), float("inf"), -float("inf"))
     for field in ("radius", "phi", "lumaPhi", "depthPhi", "normalPhi", "roughnessPhi"):
         for value in bad + (-0.5,):
             assert call(p=S.DenoiseParams(**{field: value})) == -1, (field, value)
+            assert err() == PARAMS, (field, value)
         assert call(p=S.DenoiseParams(**{field: 0.0})) == (-1 if field in ("radius", "phi") else 0), field
     assert call(p=S.DenoiseParams(iterations=0)) == -1 and call(p=S.DenoiseParams(iterations=6)) == -1
+    assert err() == PARAMS
     assert call(p=S.DenoiseParams(iterations=2)) == -1        # one pass per call here; hrpt_denoise iterates
     assert b"iterations" in native.lib.hrpt_last_error(None)
+    assert err() == "hrpt_denoise_host: one pass per call, iterations must be 1 (hrpt_denoise iterates)"
     assert call(p=S.DenoiseParams(radius=3e38, iterations=1)) == 0
     assert call(p=S.DenoiseParams(flags=2)) == -1 and call(p=S.DenoiseParams(flags=0x80000000)) == -1
+    assert err() == PARAMS
     assert call(p=S.DenoiseParams(flags=S.DENOISE_OUTPUT_ONLY)) == 0
     assert call(p=S.DenoiseParams(reserved=1)) == -1
+    assert err() == PARAMS
     assert call(p=S.DenoiseParams(frame=0xFFFFFFFF)) == 0
     # context calls on a NULL context
     p = S.DenoiseParams()

@@ -121,6 +121,10 @@ def test_in_place_and_thread_count_independence():
         got = lib_demodulate(c, nthreads=n)
         assert np.array_equal(u32(got[0]), u32(one[0])) and np.array_equal(u32(got[1]), u32(one[1])), n
         assert np.array_equal(u32(native.compose_host(one[0], one[1], c["emissive"], nthreads=n)), u32(native.compose_host(one[0], one[1], c["emissive"], nthreads=1)))
+    for n in (0, -1, 1000):                                  # the clamp: one per hardware thread up to 16; at most 256, and no more than rows
+        got = lib_demodulate(c, nthreads=n)
+        assert np.array_equal(u32(got[0]), u32(one[0])) and np.array_equal(u32(got[1]), u32(one[1])), n
+        assert np.array_equal(u32(native.compose_host(one[0], one[1], c["emissive"], nthreads=n)), u32(native.compose_host(one[0], one[1], c["emissive"], nthreads=1))), n
 
 
 # ---------------------------------------------------------------- 2. properties, on the reference and on the library
@@ -209,6 +213,8 @@ def test_argument_errors():
     out, mod = np.empty_like(imgs["color"]), np.empty_like(imgs["color"])
     view = c["view"]
     err = lambda: native.lib.hrpt_last_error(None)                 # noqa: E731
+    text = lambda: err().decode()                                  # noqa: E731 -- the whole text, as the library has always worded it
+    PARAMS = "hrpt_demodulate_host: floor must be finite and > 0, flags 0, reserved 0"
 
     def images(**kw):
         ptrs = {k: a.ctypes.data for k, a in imgs.items()}
@@ -223,25 +229,37 @@ def test_argument_errors():
                                                C.byref(p) if p != "null" else None, 1)
     assert call() == 0
     assert call(im="null") == -1 and call(v=None) == -1 and call(p="null") == -1
+    for kw in (dict(im="null"), dict(v=None), dict(p="null")):
+        assert call(**kw) == -1 and text() == "hrpt_demodulate_host: null argument", kw
     for k in KEYS + ("colorOut", "modulationOut"):
         assert call(im=images(**{k: None})) == -1, k
+        assert text() == "hrpt_demodulate_host: null image (only emissive may be NULL)", k
     assert call(im=images(emissive=None)) == 0
     for k in KEYS + ("emissive",):                                 # forbidden aliasing
         assert call(im=images(modulationOut=imgs[k].ctypes.data)) == -1, k
         assert b"modulationOut must differ" in err()
+        assert text() == "hrpt_demodulate_host: modulationOut must differ from every input", k
         assert call(im=images(colorOut=imgs[k].ctypes.data)) == (0 if k == "color" else -1), k
+        assert k == "color" or text() == "hrpt_demodulate_host: colorOut may equal color, but no other input", k
     assert call(im=images(colorOut=mod.ctypes.data)) == -1
+    assert text() == "hrpt_demodulate_host: modulationOut must differ from colorOut"
     wrong = view.copy(); wrong["m_ViewportSize"] = (w + 1, h)
     assert call(v=wrong) == -1 and b"m_ViewportSize" in err()
+    assert text() == "hrpt_demodulate_host: view->m_ViewportSize does not match the image size"
     assert call(ww=0) == -1 and call(hh=0) == -1 and call(ww=65536) == -1 and call(hh=65536) == -1
+    for ww, hh in ((0, h), (w, 0), (0, 0), (65536, h), (w, 65536)):       # reported before the view is compared with it
+        assert call(ww=ww, hh=hh) == -1 and text() == "hrpt_demodulate_host: size must be 1..65535", (ww, hh)
     for floor in (float("nan"), float("inf"), -float("inf"), 0.0, -0.04):
         assert call(p=S.ModulationParams(floor)) == -1, floor
         assert b"floor" in err()
+        assert text() == PARAMS, floor
     assert call(p=S.ModulationParams(1e-30)) == 0 and call(p=S.ModulationParams(3e38)) == 0
     assert call(p=S.ModulationParams(flags=1)) == -1 and call(p=S.ModulationParams(flags=0x80000000)) == -1
+    assert text() == PARAMS
     for k in range(2):
         p = S.ModulationParams(); p.reserved[k] = 1
         assert call(p=p) == -1
+        assert text() == PARAMS, k
 
     def cimages(**kw):
         ptrs = dict(color=imgs["color"].ctypes.data, modulation=mod.ctypes.data, emissive=imgs["emissive"].ctypes.data, colorOut=out.ctypes.data)
@@ -252,12 +270,18 @@ def test_argument_errors():
         im = im if im is not None else cimages()
         return native.lib.hrpt_compose_host(C.byref(im) if im != "null" else None, ww, hh, 1)
     assert ccall() == 0 and ccall(im="null") == -1
+    assert text() == "hrpt_compose_host: null argument"
     for k in ("color", "modulation", "colorOut"):
         assert ccall(im=cimages(**{k: None})) == -1, k
+        assert text() == "hrpt_compose_host: null image (only emissive may be NULL)", k
     assert ccall(im=cimages(emissive=None)) == 0
     assert ccall(im=cimages(colorOut=imgs["color"].ctypes.data)) == 0
     assert ccall(im=cimages(colorOut=mod.ctypes.data)) == -1 and ccall(im=cimages(colorOut=imgs["emissive"].ctypes.data)) == -1
+    for k in (mod, imgs["emissive"]):
+        assert ccall(im=cimages(colorOut=k.ctypes.data)) == -1 and text() == "hrpt_compose_host: colorOut may equal color, but not modulation or emissive"
     assert ccall(ww=0) == -1 and ccall(hh=0) == -1 and ccall(ww=65536) == -1
+    for ww, hh in ((0, h), (w, 0), (0, 0), (65536, h), (w, 65536)):
+        assert ccall(ww=ww, hh=hh) == -1 and text() == "hrpt_compose_host: size must be 1..65535", (ww, hh)
     # context calls on a NULL context
     p = S.ModulationParams()
     assert native.lib.hrpt_demodulate(None, view.ctypes.data, C.byref(p)) == -1 and native.lib.hrpt_compose(None) == -1

@@ -205,34 +205,55 @@ def test_argument_errors():
         p = p if p is not None else S.TemporalParams()
         return native.lib.hrpt_temporal_host(C.byref(im) if im != "null" else None, ww, hh, v.ctypes.data if v is not None else None,
                                              pv.ctypes.data if pv is not None else None, C.byref(p) if p != "null" else None, 1)
+    err = lambda: native.lib.hrpt_last_error(None).decode()          # noqa: E731 -- the whole text, as the library has always worded it
+    PARAMS = "hrpt_temporal_host: blend must be finite and in [0, 1], flags HRPT_TEMPORAL_* only, reserved 0"
     assert call() == 0
     assert call(im="null") == -1 and call(v=None) == -1 and call(pv=None) == -1 and call(p="null") == -1
+    for kw in (dict(im="null"), dict(v=None), dict(pv=None), dict(p="null")):
+        assert call(**kw) == -1 and err() == "hrpt_temporal_host: null argument", kw
     for k in range(7):
         if k == 4:
             continue                                         # historyIn may be NULL
         ptrs = [a.ctypes.data for a in imgs] + [hout.ctypes.data, cout.ctypes.data]
         ptrs[k] = None
         assert call(im=S.TemporalImages(*ptrs)) == -1, k
+        assert err() == "hrpt_temporal_host: null image (only historyIn may be NULL)", k
     ptrs = [a.ctypes.data for a in imgs] + [imgs[4].ctypes.data, cout.ctypes.data]
     assert call(im=S.TemporalImages(*ptrs)) == -1            # historyOut == historyIn
     assert b"historyOut" in native.lib.hrpt_last_error(None)
+    assert err() == "hrpt_temporal_host: historyOut must differ from historyIn"
     wrong = view.copy(); wrong["m_ViewportSize"] = (w + 1, h)
     assert call(v=wrong) == -1
     assert b"m_ViewportSize" in native.lib.hrpt_last_error(None)
+    assert err() == "hrpt_temporal_host: view->m_ViewportSize does not match the image size"
     assert call(ww=0) == -1 and call(hh=0) == -1 and call(ww=65536) == -1
+    for ww, hh in ((0, h), (w, 0), (0, 0), (65536, h), (w, 65536)):       # reported before the view is compared with it
+        assert call(ww=ww, hh=hh) == -1 and err() == "hrpt_temporal_host: size must be 1..65535", (ww, hh)
     for blend in (-0.01, 1.01, float("nan"), float("inf"), -float("inf")):
         assert call(p=S.TemporalParams(blend)) == -1, blend
+        assert err() == PARAMS, blend
     for blend in (0.0, 1.0):
         assert call(p=S.TemporalParams(blend)) == 0
     assert call(p=S.TemporalParams(0.9, 4)) == -1 and call(p=S.TemporalParams(0.9, 0x80000000)) == -1
+    assert err() == PARAMS
     assert call(p=S.TemporalParams(0.9, S.TEMPORAL_LINEAR | S.TEMPORAL_RESET)) == 0
     p = S.TemporalParams(); p.reserved[1] = 1
     assert call(p=p) == -1
+    assert err() == PARAMS
     # context calls on a NULL context
     assert native.lib.hrpt_temporal_accumulate(None, view.ctypes.data, prev.ctypes.data, C.byref(S.TemporalParams())) == -1
     assert native.lib.hrpt_clear_accumulation(None) == -1
     assert native.lib.hrpt_read_temporal_history(None, hout.ctypes.data, hout.nbytes) == -1
     assert native.lib.hrpt_get_temporal_history_device(None, None) == -1
+
+
+def test_nthreads_is_clamped():
+    """nthreads <= 0 means one per hardware thread up to 16, and no more than 256 (nor than rows) are started: the image is that of one."""
+    c = TC.case("random", 37, 23, True)
+    one = native.temporal_host(c["color"], c["motion"], c["depth"], c["normal"], c["history"], c["view"], c["prev"], TC.params(0.9, False), nthreads=1)
+    for n in (0, -1, 1000):
+        got = native.temporal_host(c["color"], c["motion"], c["depth"], c["normal"], c["history"], c["view"], c["prev"], TC.params(0.9, False), nthreads=n)
+        assert np.array_equal(u32(got[0]), u32(one[0])) and np.array_equal(u32(got[1]), u32(one[1])), n
 
 
 # ---------------------------------------------------------------- 4. sanitizer build of the host side
