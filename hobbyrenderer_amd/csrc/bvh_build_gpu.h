@@ -38,6 +38,10 @@ public:
     // (Re)builds from the world matrices of `instances` (as many as at prepare(), same mesh / material indices). The tree is rebuilt
     // with fewer Morton bits until maxDepth + 2 <= maxStackDepth (the caller still checks the final depth). Synchronises `stream`.
     hipError_t build(const HrptPerInstanceData* instances, bool usePloc, uint32_t maxStackDepth, hipStream_t stream, GpuBuiltBvh& out, std::string& error);
+    // Deforming meshes (hrpt_update_vertices): overwrites the records [first, first + count) of the device vertex buffer prepare() filled, from
+    // host memory or (`fromDevice`) from device memory, on `stream`; the caller has checked the range against the scene's vertex count and the
+    // positions for finiteness. The hierarchy of the last build stays refittable: the next build() or refit() brings everything derived after.
+    hipError_t update_vertices(const HrptVertexQuantized* vertices, bool fromDevice, uint32_t first, uint32_t count, hipStream_t stream, std::string& error);
     size_t deviceBytes() const;
     // Box mode -- the tree over the instances of the two-level structure (pt_capi.cpp build_two_level): `count` boxes (6 floats each, min xyz
     // then max xyz, taken as they are), one per leaf, Morton grid over the cube of the largest extent. The result has nodes / nodes4 /

@@ -595,6 +595,7 @@ struct GpuBvhBuilder::Impl {
     std::vector<InstRec> inst;         // static part filled at prepare(), world matrices per build()
     size_t sortBytes = 0, scanBytes = 0, bytes = 0;
     uint32_t n = 0;
+    uint32_t vertexCount = 0;          // records of BuildBuffers::vertices (triangle mode)
     bool boxes = false;                // prepare_boxes(): the primitives are boxes (one per leaf), no triangle / attribute outputs
     uint32_t maxLeaf = 0;              // 0: the default leaf size (2, HRPT_GPU_BVH_MAX_LEAF); 1 in box mode
     uint32_t nodes4Capacity = 0;       // records of BuildBuffers::nodes4 (allocate)
@@ -647,7 +648,7 @@ hipError_t GpuBvhBuilder::allocate(uint32_t n, const HrptSceneDesc* s, bool need
 {
     Impl& m = *p;
     hipError_t e;
-    m.n = n;
+    m.n = n; m.vertexCount = s ? s->vertexCount : 0;
     if (hipEventCreate(&m.ev0) != hipSuccess || hipEventCreate(&m.ev1) != hipSuccess) { error = "hipEventCreate"; return hipErrorUnknown; }
 
     // rocPRIM scratch sizes
@@ -703,6 +704,18 @@ hipError_t GpuBvhBuilder::allocate(uint32_t n, const HrptSceneDesc* s, bool need
         (e = hipMemcpyAsync(const_cast<uint32_t*>(b.indices), s->indices, (size_t)s->indexCount * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
         (e = hipStreamSynchronize(stream)) != hipSuccess) { error = "hipMemcpyAsync(GPU BVH inputs)"; return e; }
     return hipSuccess;
+}
+
+hipError_t GpuBvhBuilder::update_vertices(const HrptVertexQuantized* vertices, bool fromDevice, uint32_t first, uint32_t count, hipStream_t stream, std::string& error)
+{
+    if (!p || p->boxes || !p->scratch) { error = "GPU BVH builder not prepared"; return hipErrorInvalidValue; }
+    if ((uint64_t)first + count > p->vertexCount) { error = "vertex range outside the builder's vertex buffer"; return hipErrorInvalidValue; }
+    if (count == 0) return hipSuccess;
+    // (b0 and `last` hold the same pointer: the buffer is patched in place for build() and refit() alike)
+    const hipError_t e = hipMemcpyAsync(const_cast<HrptVertexQuantized*>(p->b0.vertices) + first, vertices, (size_t)count * sizeof(HrptVertexQuantized),
+                                        fromDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) error = "hipMemcpyAsync(GPU BVH vertices)";
+    return e;
 }
 
 hipError_t GpuBvhBuilder::build_boxes(const float* boxes, bool usePloc, uint32_t maxStackDepth, hipStream_t stream, GpuBuiltBvh& out, std::string& error)

@@ -20,6 +20,7 @@
 #include "../../include/hobbyrt_pt.h"
 #include "bvh_build.h"
 #include "bvh_build_gpu.h"
+#include "pt_deform.h"
 #include "pt_device.h"
 #include "pt_kernels.h"
 #include "pt_motion.h"
@@ -58,6 +59,10 @@ struct HrptContext {
     MotionInst* dMotionInst = nullptr; size_t motionInstCapacity = 0;          // one record per instance: m_PrevWorld + the mesh's LOD-0 index offset
     float* dMotionPositions = nullptr; uint32_t* dMotionIndices = nullptr;     // object-space positions (12 B per vertex) and the index buffer
     bool motionInstStale = true, motionGeometryStale = true;                   // set by uploads / instance updates / rebuilds, cleared by the next motion call
+    // deforming meshes (hrpt_update_vertices): the object-space positions of the previous frame, 3 floats per vertex; EMPTY = previous == current
+    // (a context that never deforms pays nothing). The device copy is made by the next motion call (motionPositionsStale), like dMotionPositions.
+    std::vector<float> keptPrevPositions; float* dMotionPrevPositions = nullptr; bool motionPositionsStale = true;
+    void* dDeformStaging = nullptr; size_t deformStagingBytes = 0;             // hrpt_update_vertices_device: quantised records + the flag word, sized for the whole vertex buffer at first use
     // temporal accumulation (hrpt_temporal_accumulate): ping-pong history pair, allocated by the first call; [temporalCur] is the image the last call wrote
     float4* dTemporal[2] = {}; int temporalCur = 0; bool temporalValid = false;
     // denoise (hrpt_denoise): the default noise tile (uploaded by the first denoise call of the context) and the scratch pair of HRPT_DENOISE_OUTPUT_ONLY
@@ -143,8 +148,11 @@ static void free_motion_tables(HrptContext* c)
     if (c->dMotionInst) (void)hipFree(c->dMotionInst);
     if (c->dMotionPositions) (void)hipFree(c->dMotionPositions);
     if (c->dMotionIndices) (void)hipFree(c->dMotionIndices);
+    if (c->dMotionPrevPositions) (void)hipFree(c->dMotionPrevPositions);
+    if (c->dDeformStaging) (void)hipFree(c->dDeformStaging);
     c->dMotionInst = nullptr; c->motionInstCapacity = 0; c->dMotionPositions = nullptr; c->dMotionIndices = nullptr;
-    c->motionInstStale = c->motionGeometryStale = true;
+    c->dMotionPrevPositions = nullptr; c->dDeformStaging = nullptr; c->deformStagingBytes = 0; c->keptPrevPositions.clear();
+    c->motionInstStale = c->motionGeometryStale = c->motionPositionsStale = true;
 }
 
 static void free_scene(HrptContext* c)
@@ -713,6 +721,102 @@ static int update_instances_impl(HrptContext* c, const HrptPerInstanceData* inst
     return HRPT_OK;
 }
 
+// ---- deforming meshes: hrpt_update_vertices / hrpt_update_vertices_device (include/hobbyrt_pt.h has the contract) ----
+constexpr uint32_t kVertexUpdateFlags = HRPT_VERTICES_REFIT | HRPT_VERTICES_SAME_FRAME;
+
+// The argument checks both variants share (the answer without a scene is hrpt_update_instances').
+static int check_vertex_update(HrptContext* c, const char* what, const void* vertices, uint32_t firstVertex, uint32_t count, uint32_t flags)
+{
+    if (!c->haveScene) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": no scene uploaded");
+    if (flags & ~kVertexUpdateFlags) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown flag bits");
+    if (!vertices && count > 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": null vertex array");
+    if ((uint64_t)firstVertex + count > c->keptVertices.size()) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": range exceeds the scene's vertex count");
+    return HRPT_OK;
+}
+
+// The previous-position protocol: a call without HRPT_VERTICES_SAME_FRAME starts a frame (previous = current everywhere), every call records
+// the positions it is about to replace. While no call has recorded anything the table stays empty, which stands for previous == current.
+static void roll_previous_positions(HrptContext* c, uint32_t firstVertex, uint32_t count, uint32_t flags)
+{
+    const bool newFrame = (flags & HRPT_VERTICES_SAME_FRAME) == 0;
+    if (count == 0) {
+        if (newFrame && !c->keptPrevPositions.empty()) { c->keptPrevPositions.clear(); c->motionPositionsStale = true; }
+        return;
+    }
+    if (newFrame || c->keptPrevPositions.empty()) {
+        c->keptPrevPositions.resize(c->keptVertices.size() * 3);
+        for (size_t i = 0; i < c->keptVertices.size(); ++i) std::memcpy(&c->keptPrevPositions[3 * i], c->keptVertices[i].m_Pos, 12);
+    } else {
+        for (size_t i = firstVertex; i < (size_t)firstVertex + count; ++i) std::memcpy(&c->keptPrevPositions[3 * i], c->keptVertices[i].m_Pos, 12);
+    }
+    c->motionPositionsStale = true;
+}
+
+// Installs validated vertices: `quantised` (host, count records) goes into the kept copy; a flat structure's GPU builder gets its device
+// buffer patched from `deviceQuantised` when the records are already on the device, from the host array otherwise; then the structure follows.
+static int commit_vertices(HrptContext* c, const char* what, const HrptVertexQuantized* quantised, const HrptVertexQuantized* deviceQuantised,
+                           uint32_t firstVertex, uint32_t count, uint32_t flags)
+{
+    roll_previous_positions(c, firstVertex, count, flags);
+    std::memcpy(c->keptVertices.data() + firstVertex, quantised, (size_t)count * sizeof(HrptVertexQuantized));
+    const bool twoLevel = c->twoLevel != nullptr;
+    if (!twoLevel && c->gpuBuilder) {
+        std::string gerr;
+        const hipError_t e = c->gpuBuilder->update_vertices(deviceQuantised ? deviceQuantised : quantised, deviceQuantised != nullptr, firstVertex, count, c->stream, gerr);
+        if (e != hipSuccess) { c->haveScene = false; return fail(c, HRPT_ERR_HIP, std::string(what) + ": " + gerr + ": " + hipGetErrorString(e)); }
+    }
+    HrptSceneDesc s = kept_scene_desc(c);
+    SceneView v = c->view;
+    // flat: a rebuild like hrpt_update_instances' (the GPU builder keeps its buffers; the host builder starts from the kept copy). Two-level: the
+    // mesh trees hold the old vertices, so the whole structure is built again along the first-build path.
+    const int r = build_acceleration(c, s, kept_triangle_count(c), v, twoLevel, (flags & HRPT_VERTICES_REFIT) != 0);
+    if (r != HRPT_OK) { c->haveScene = false; return r; }   // the old tree is gone: the scene has to be uploaded again
+    c->view = v;
+    return HRPT_OK;
+}
+
+static int update_vertices_impl(HrptContext* c, const HrptVertexQuantized* vertices, uint32_t firstVertex, uint32_t count, uint32_t flags)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(check_vertex_update(c, "hrpt_update_vertices", vertices, firstVertex, count, flags));
+    for (uint32_t i = 0; i < count; ++i)
+        if (!deform::position_finite(vertices[i].m_Pos)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_update_vertices: non-finite vertex position");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // frames in flight still traverse the old tree and read the old motion tables
+    if (count == 0) { roll_previous_positions(c, 0, 0, flags); return HRPT_OK; }
+    return commit_vertices(c, "hrpt_update_vertices", vertices, nullptr, firstVertex, count, flags);
+}
+
+static int update_vertices_device_impl(HrptContext* c, const HrptVertexFloat* deviceVertices, uint32_t firstVertex, uint32_t count, uint32_t flags, hipStream_t stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(check_vertex_update(c, "hrpt_update_vertices_device", deviceVertices, firstVertex, count, flags));
+    if (reinterpret_cast<uintptr_t>(deviceVertices) & 15u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_update_vertices_device: deviceVertices must be 16-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (count == 0) { roll_previous_positions(c, 0, 0, flags); return HRPT_OK; }
+    HIP_TRY(c, hipStreamSynchronize(stream));           // whatever writes deviceVertices has to be done before the kernel below reads them
+    const size_t recordBytes = (size_t)count * sizeof(HrptVertexQuantized);
+    if (!c->dDeformStaging) {                           // once per scene: room for the whole vertex buffer + the flag word
+        const size_t bytes = c->keptVertices.size() * sizeof(HrptVertexQuantized) + sizeof(uint32_t);
+        HIP_TRY(c, hipMalloc(&c->dDeformStaging, bytes));
+        c->deformStagingBytes = bytes;
+    }
+    if (recordBytes + sizeof(uint32_t) > c->deformStagingBytes) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_update_vertices_device: range exceeds the staging buffer");
+    HrptVertexQuantized* staged = static_cast<HrptVertexQuantized*>(c->dDeformStaging);
+    uint32_t* dFlag = reinterpret_cast<uint32_t*>(static_cast<char*>(c->dDeformStaging) + recordBytes);
+    HIP_TRY(c, hipMemsetAsync(dFlag, 0, sizeof(uint32_t), c->stream));
+    HIP_TRY(c, launch_quantise_vertices(deviceVertices, count, staged, dFlag, c->stream));
+    // the copy-back that keeps the host copy current also brings the flag: nothing is committed before it is known to be clear
+    std::vector<HrptVertexQuantized> host((recordBytes + sizeof(uint32_t) + sizeof(HrptVertexQuantized) - 1) / sizeof(HrptVertexQuantized));
+    HIP_TRY(c, hipMemcpyAsync(host.data(), staged, recordBytes + sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint32_t flag = 0;
+    std::memcpy(&flag, reinterpret_cast<const char*>(host.data()) + recordBytes, sizeof flag);
+    if (flag) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_update_vertices_device: non-finite vertex position");
+    return commit_vertices(c, "hrpt_update_vertices_device", host.data(), staged, firstVertex, count, flags);
+}
+
 int hrpt_resize(HrptContext* c, uint32_t width, uint32_t height)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
@@ -825,6 +929,29 @@ int hrpt_update_materials(HrptContext* c, const HrptMaterialConstants* materials
     catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_update_materials: host allocation failed"); }
     catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_update_materials: ") + e.what()); }
 }
+int hrpt_update_vertices(HrptContext* c, const HrptVertexQuantized* vertices, uint32_t firstVertex, uint32_t count, uint32_t flags)
+{
+    try { return update_vertices_impl(c, vertices, firstVertex, count, flags); }
+    catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_update_vertices: host allocation failed"); }
+    catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_update_vertices: ") + e.what()); }
+}
+int hrpt_update_vertices_device(HrptContext* c, const HrptVertexFloat* deviceVertices, uint32_t firstVertex, uint32_t count, uint32_t flags, void* stream)
+{
+    try { return update_vertices_device_impl(c, deviceVertices, firstVertex, count, flags, static_cast<hipStream_t>(stream)); }
+    catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_update_vertices_device: host allocation failed"); }
+    catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_update_vertices_device: ") + e.what()); }
+}
+int hrpt_quantize_vertices_device(HrptContext* c, const HrptVertexFloat* deviceIn, uint32_t count, HrptVertexQuantized* deviceOut, void* stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (count == 0) return HRPT_OK;
+    if (!deviceIn || !deviceOut) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_quantize_vertices_device: null array");
+    if ((reinterpret_cast<uintptr_t>(deviceIn) & 15u) || (reinterpret_cast<uintptr_t>(deviceOut) & 3u))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_quantize_vertices_device: deviceIn must be 16-byte aligned, deviceOut 4-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_quantise_vertices(deviceIn, count, deviceOut, nullptr, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+}
 int hrpt_render(HrptContext* c, const HrptFrameParams* p)
 {
     try { return render_impl(c, p); }
@@ -871,22 +998,33 @@ int hrpt_read_accumulation(HrptContext* c, float* rgba, size_t bytes) { return r
 int hrpt_read_output(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->dOutput : nullptr, rgba, bytes, "hrpt_read_output"); }
 
 // The device tables of hrpt_render_motion_vectors, (re)built from the kept copies where a flag says they are stale: the instance records after
-// every upload / instance update / rebuild, positions and indices after an upload only. A context that never asks for motion never gets here.
+// every upload / instance update / rebuild, indices after an upload only, positions after an upload and after hrpt_update_vertices (12 bytes
+// per vertex from the kept copy, and as much again for the previous positions while a deformation lasts). A context that never asks for
+// motion never gets here.
 static int refresh_motion_tables(HrptContext* c)
 {
-    if (!c->motionInstStale && !c->motionGeometryStale) return HRPT_OK;
+    if (!c->motionInstStale && !c->motionGeometryStale && !c->motionPositionsStale) return HRPT_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));        // motion calls in flight still read the old tables
     std::vector<float> positions;
+    const size_t pb = c->keptVertices.size() * 3 * sizeof(float);
     if (c->motionGeometryStale) {
         if (c->dMotionPositions) { (void)hipFree(c->dMotionPositions); c->dMotionPositions = nullptr; }
+        if (c->dMotionPrevPositions) { (void)hipFree(c->dMotionPrevPositions); c->dMotionPrevPositions = nullptr; }
         if (c->dMotionIndices) { (void)hipFree(c->dMotionIndices); c->dMotionIndices = nullptr; }
-        positions.resize(c->keptVertices.size() * 3);
-        for (size_t i = 0; i < c->keptVertices.size(); ++i) std::memcpy(&positions[3 * i], c->keptVertices[i].m_Pos, 12);
-        const size_t pb = positions.size() * sizeof(float), ib = c->keptIndices.size() * sizeof(uint32_t);
+        const size_t ib = c->keptIndices.size() * sizeof(uint32_t);
         HIP_TRY(c, hipMalloc((void**)&c->dMotionPositions, pb ? pb : 16));
         HIP_TRY(c, hipMalloc((void**)&c->dMotionIndices, ib ? ib : 16));
-        if (pb) HIP_TRY(c, hipMemcpyAsync(c->dMotionPositions, positions.data(), pb, hipMemcpyHostToDevice, c->stream));
         if (ib) HIP_TRY(c, hipMemcpyAsync(c->dMotionIndices, c->keptIndices.data(), ib, hipMemcpyHostToDevice, c->stream));
+        c->motionPositionsStale = true;
+    }
+    if (c->motionPositionsStale) {
+        positions.resize(c->keptVertices.size() * 3);
+        for (size_t i = 0; i < c->keptVertices.size(); ++i) std::memcpy(&positions[3 * i], c->keptVertices[i].m_Pos, 12);
+        if (pb) HIP_TRY(c, hipMemcpyAsync(c->dMotionPositions, positions.data(), pb, hipMemcpyHostToDevice, c->stream));
+        if (!c->keptPrevPositions.empty()) {            // (same size as `positions`: hrpt_update_vertices fills it for all vertices)
+            if (!c->dMotionPrevPositions) HIP_TRY(c, hipMalloc((void**)&c->dMotionPrevPositions, pb ? pb : 16));
+            if (pb) HIP_TRY(c, hipMemcpyAsync(c->dMotionPrevPositions, c->keptPrevPositions.data(), pb, hipMemcpyHostToDevice, c->stream));
+        }
     }
     std::vector<MotionInst> records(c->keptInstances.size());
     for (size_t i = 0; i < records.size(); ++i) {
@@ -903,7 +1041,7 @@ static int refresh_motion_tables(HrptContext* c)
     }
     if (!records.empty()) HIP_TRY(c, hipMemcpyAsync(c->dMotionInst, records.data(), records.size() * sizeof(MotionInst), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));        // the staging vectors die at scope exit
-    c->motionInstStale = c->motionGeometryStale = false;
+    c->motionInstStale = c->motionGeometryStale = c->motionPositionsStale = false;
     return HRPT_OK;
 }
 
@@ -942,7 +1080,7 @@ static int render_gbuffer_impl(HrptContext* c, const HrptFrameParams* p, uint32_
         if (!c->dMotion) HRPT_TRY(realloc_image(c, c->dMotion, bytes));
         int r = refresh_motion_tables(c);
         if (r != HRPT_OK) return r;
-        m.inst = c->dMotionInst; m.positions = c->dMotionPositions; m.indices = c->dMotionIndices; m.plane = c->dMotion;
+        m.inst = c->dMotionInst; m.positions = c->dMotionPositions; m.prevPositions = c->keptPrevPositions.empty() ? c->dMotionPositions : c->dMotionPrevPositions; m.indices = c->dMotionIndices; m.plane = c->dMotion;
         std::memcpy(m.prevWorldToClip, prevView->m_MatWorldToClip, sizeof m.prevWorldToClip);
         m.prevScale[0] = prevView->m_ClipToWindowScale[0]; m.prevScale[1] = prevView->m_ClipToWindowScale[1];
         m.prevBias[0] = prevView->m_ClipToWindowBias[0]; m.prevBias[1] = prevView->m_ClipToWindowBias[1];
@@ -1529,6 +1667,12 @@ int hrpt_demodulate_host(const HrptDemodulateImages* img, uint32_t width, uint32
     return run_host("hrpt_demodulate_host", [&] { demodulate_host(*img, width, height, *view, *p, host_threads(nthreads)); });
 }
 
+int hrpt_quantize_vertices_host(const HrptVertexFloat* in, uint32_t count, HrptVertexQuantized* out, int nthreads)
+{
+    if (count == 0) return HRPT_OK;
+    if (!in || !out) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_quantize_vertices_host: null array");
+    return run_host("hrpt_quantize_vertices_host", [&] { (void)quantize_vertices_host(in, count, out, host_threads(nthreads)); });
+}
 int hrpt_compose_host(const HrptComposeImages* img, uint32_t width, uint32_t height, int nthreads)
 {
     HRPT_TRY(compose_check(nullptr, "hrpt_compose_host", img, width, height));

@@ -93,6 +93,12 @@ void demodulate_host(const HrptDemodulateImages& images, uint32_t width, uint32_
 void compose_host(const HrptComposeImages& images, uint32_t width, uint32_t height, int nthreads);
 void modulation_probe(const float* albedo3, const float* N3, const float* V3, float rough, float metal, float floor, float* outM3);
 
+// Vertex quantiser (pt_deform.hip; arithmetic in pt_deform.h): out[i] = the 24-byte scene-format record of the float vertex in[i], both in
+// device memory (in 16-byte aligned); *flag (device, may be null) is set to 1 when a position is not finite. quantize_vertices_host
+// (pt_deform_host.cpp): the same arithmetic on host threads; returns whether every position is finite.
+hipError_t launch_quantise_vertices(const HrptVertexFloat* in, uint32_t count, HrptVertexQuantized* out, uint32_t* flag, hipStream_t stream);
+bool quantize_vertices_host(const HrptVertexFloat* in, uint32_t count, HrptVertexQuantized* out, int nthreads);
+
 // Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
 hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
 

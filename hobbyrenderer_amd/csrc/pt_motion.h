@@ -19,6 +19,7 @@ static_assert(sizeof(MotionInst) == 64, "four 16-byte rows");
 struct MotionArgs {
     const MotionInst* inst;         // per instance
     const float* positions;         // object space, 3 floats per vertex (HrptVertexQuantized::m_Pos)
+    const float* prevPositions;     // the same one frame ago (hrpt_update_vertices); == positions where nothing deformed
     const uint32_t* indices;        // the scene's index buffer
     float4* plane;                  // W x H
     float prevWorldToClip[16];      // prevView->m_MatWorldToClip
@@ -39,6 +40,8 @@ struct MotionTri { f3 cur0, cur1, cur2, prev0, prev1, prev2; };
 // The gather: instance record -> three indices -> three object-space positions (a three-deep dependent chain; callers issue it before their
 // texture fetches). The current vertices are those the hit was found on: the GpuTri of the flat structure, tl_world_triangle's product at a
 // two-level leaf -- both are transform_point(q, m_World), the statement the previous vertices are formed with, so equal transforms give equal bits.
+// The previous vertices come from prevPositions (a deforming mesh: hrpt_update_vertices); with prevPositions == positions both tables hold the
+// same values and the arithmetic is the same.
 HRT_DEV MotionTri motion_gather(const SceneView& s, const MotionArgs& m, const Hit& hit)
 {
     const uint32_t* e = reinterpret_cast<const uint32_t*>(s.attrs + hit.tri) + 16;      // GpuTriAttr e{inst, prim, -, -}
@@ -47,12 +50,13 @@ HRT_DEV MotionTri motion_gather(const SceneView& s, const MotionArgs& m, const H
     const float4 w0 = rec[0], w1 = rec[1], w2 = rec[2];
     const uint32_t first = __float_as_uint(rec[3].x) + 3u * prim;
     const uint32_t i0 = m.indices[first], i1 = m.indices[first + 1u], i2 = m.indices[first + 2u];
-    const f3 q0 = mk3(m.positions + 3ull * i0), q1 = mk3(m.positions + 3ull * i1), q2 = mk3(m.positions + 3ull * i2);
+    const f3 q0 = mk3(m.prevPositions + 3ull * i0), q1 = mk3(m.prevPositions + 3ull * i1), q2 = mk3(m.prevPositions + 3ull * i2);
     MotionTri t;
     if (s.instances) {
+        const f3 p0 = mk3(m.positions + 3ull * i0), p1 = mk3(m.positions + 3ull * i1), p2 = mk3(m.positions + 3ull * i2);
         const float4* w = reinterpret_cast<const float4*>(s.instances[inst].world);
         const float4 c0 = w[0], c1 = w[1], c2 = w[2];
-        t.cur0 = motion_transform_point(q0, c0, c1, c2); t.cur1 = motion_transform_point(q1, c0, c1, c2); t.cur2 = motion_transform_point(q2, c0, c1, c2);
+        t.cur0 = motion_transform_point(p0, c0, c1, c2); t.cur1 = motion_transform_point(p1, c0, c1, c2); t.cur2 = motion_transform_point(p2, c0, c1, c2);
     } else {
         const GpuTri& g = s.tris[hit.tri];
         t.cur0 = mk3(g.p0); t.cur1 = mk3(g.p1); t.cur2 = mk3(g.p2);

@@ -29,7 +29,7 @@ lib = C.CDLL(LIB_PATH)
 EXPORTS = [
     "hrpt_create", "hrpt_destroy", "hrpt_last_error", "hrpt_upload_scene", "hrpt_resize", "hrpt_render",
     "hrpt_synchronize", "hrpt_set_stream", "hrpt_get_device_images", "hrpt_read_accumulation", "hrpt_read_output",
-    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
+    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_update_vertices", "hrpt_update_vertices_device", "hrpt_quantize_vertices_host", "hrpt_quantize_vertices_device", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_render_gbuffer", "hrpt_read_gbuffer", "hrpt_get_gbuffer_device",
     "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
@@ -69,6 +69,10 @@ lib.hrpt_update_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_ui
 lib.hrpt_refit_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
 lib.hrpt_update_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
 lib.hrpt_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+lib.hrpt_update_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+lib.hrpt_update_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+lib.hrpt_quantize_vertices_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
+lib.hrpt_quantize_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
 lib.hrpt_reset_stats.argtypes = [C.c_void_p]
 lib.hrpt_selftest_f16_decode.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_selftest_unorm8.argtypes = [C.c_void_p, C.c_void_p]
@@ -314,6 +318,15 @@ def modulation_probe(albedo, normal, view_dir, rough, metal, floor=0.04):
     return out
 
 
+def quantize_vertices_host(vertices, nthreads=0):
+    """hrpt_quantize_vertices_host: S.VertexFloat records -> S.VertexQuantized records by the library's quantiser (csrc/pt_deform.h) on host
+    threads; needs no GPU and is bit-identical to PathTracerContext.quantize_vertices_device and to scenes.quantize_vertices."""
+    v = np.ascontiguousarray(vertices, S.VertexFloat)
+    out = np.zeros(len(v), S.VertexQuantized)
+    _check_rc(lib.hrpt_quantize_vertices_host(v.ctypes.data if len(v) else None, len(v), out.ctypes.data if len(v) else None, int(nthreads)))
+    return out
+
+
 _BVH_DUMP_ARRAYS = (("nodes", S.GpuNode, "nodeCount"), ("nodes4", S.GpuNode4, "node4Count"), ("nodesQ", S.GpuNodeQ, "node4Count"),
                     ("triangles", S.GpuTri, "triangleCount"), ("attributes", S.GpuTriAttr, "triangleCount"),
                     ("tangents", S.GpuTriTangent, "triangleCount"), ("instances", S.GpuInstance, "instanceCount"))
@@ -524,6 +537,31 @@ class PathTracerContext:
         materials = np.ascontiguousarray(materials)
         assert materials.dtype.itemsize == 180, "MaterialConstants records expected"
         self._check(lib.hrpt_update_materials(self._h, materials.ctypes.data, int(first), len(materials)))
+
+    def update_vertices(self, vertices, first=0, flags=0):
+        """hrpt_update_vertices: new S.VertexQuantized records for the vertices [first, first + len(vertices)) of the scene's vertex buffer;
+        the acceleration structure and the per-triangle records follow. flags: S.VERTICES_REFIT (keep the hierarchy of a GPU-built flat
+        tree), S.VERTICES_SAME_FRAME (a further range of the same frame: the previous positions render_motion_vectors reads are not
+        reset first)."""
+        vertices = np.ascontiguousarray(vertices)
+        assert vertices.dtype.itemsize == 24, "VertexQuantized records expected"
+        self._check(lib.hrpt_update_vertices(self._h, vertices.ctypes.data if len(vertices) else None, int(first), len(vertices), int(flags)))
+
+    def update_vertices_device(self, ptr, first, count, flags=0, stream=0):
+        """hrpt_update_vertices_device: the same from `count` S.VertexFloat records in device memory at `ptr` (16-byte aligned; e.g. a torch
+        tensor's data_ptr()), quantised on the device. `stream` (integer handle, 0 = the default stream) is synchronised before they are read."""
+        self._check(lib.hrpt_update_vertices_device(self._h, C.c_void_p(int(ptr)) if ptr else None, int(first), int(count), int(flags),
+                                                    C.c_void_p(int(stream)) if stream else None))
+
+    def end_vertex_frame(self):
+        """A frame in which nothing deforms: previous positions = current positions, nothing is rebuilt (the count-0 call)."""
+        self._check(lib.hrpt_update_vertices(self._h, None, 0, 0, 0))
+
+    def quantize_vertices_device(self, in_ptr, count, out_ptr, stream=0):
+        """hrpt_quantize_vertices_device: the quantiser kernel alone, `count` S.VertexFloat records at in_ptr (16-byte aligned) ->
+        S.VertexQuantized records at out_ptr, both device addresses; asynchronous on `stream` (integer handle)."""
+        self._check(lib.hrpt_quantize_vertices_device(self._h, C.c_void_p(int(in_ptr)) if in_ptr else None, int(count),
+                                                      C.c_void_p(int(out_ptr)) if out_ptr else None, C.c_void_p(int(stream)) if stream else None))
 
     def build_info(self):
         bi = S.BuildInfo()

@@ -10,6 +10,8 @@ import numpy as np
 f32, u32 = np.float32, np.uint32
 
 VertexQuantized = np.dtype([("m_Pos", f32, 3), ("m_Normal", u32), ("m_Uv", u32), ("m_Tangent", u32)])
+# HrptVertexFloat: what hrpt_update_vertices_device / hrpt_quantize_vertices_* read; tangent[3] = handedness sign
+VertexFloat = np.dtype([("pos", f32, 3), ("normal", f32, 3), ("uv", f32, 2), ("tangent", f32, 4)])
 MeshData = np.dtype([("m_LODCount", u32), ("m_IndexOffsets", u32, 8), ("m_IndexCounts", u32, 8),
                      ("m_MeshletOffsets", u32, 8), ("m_MeshletCounts", u32, 8), ("m_LODErrors", f32, 8)])
 Meshlet = np.dtype([("m_CenterRadius", u32, 2), ("m_VertexOffset", u32), ("m_TriangleOffset", u32), ("m_VertexCount", u32),
@@ -45,6 +47,7 @@ PathTracerConstants = np.dtype([
 FrameParams = np.dtype([("constants", PathTracerConstants), ("accumCount", u32), ("tileX0", u32), ("tileY0", u32),
                         ("tileX1", u32), ("tileY1", u32), ("flags", u32), ("stripeCount", u32), ("stripeIndex", u32)])
 
+assert VertexFloat.itemsize == 48
 assert VertexQuantized.itemsize == 24 and MeshData.itemsize == 164 and PerInstanceData.itemsize == 160
 assert MaterialConstants.itemsize == 180 and GPULight.itemsize == 64
 assert PlanarViewConstants.itemsize == 704 and PathTracerConstants.itemsize == 768
@@ -244,6 +247,7 @@ class BvhDump(C.Structure):        # HrptBvhDump
 ABI_VERSION = 3                    # HRPT_ABI_VERSION (include/hobbyrt_pt.h)
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_GPU_LBVH, BVH_BUILDER_GPU_PLOC, BVH_BUILDER_AUTO = 0, 1, 2, 3
 BVH_BUILDER_REFITTED = 0x100     # ORed into BuildInfo.usedBuilder after a refit (hrpt_refit_instances)
+VERTICES_REFIT, VERTICES_SAME_FRAME = 1, 2            # HRPT_VERTICES_* (hrpt_update_vertices)
 ACCEL_AUTO, ACCEL_FLAT, ACCEL_TWO_LEVEL = 0, 1, 2     # HRPT_ACCEL_* (hrpt_set_acceleration_structure)
 
 

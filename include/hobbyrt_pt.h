@@ -382,6 +382,47 @@ int  hrpt_refit_instances(HrptContext* ctx, const HrptPerInstanceData* instances
 int  hrpt_update_lights(HrptContext* ctx, const HrptGPULight* lights, uint32_t count);
 int  hrpt_update_materials(HrptContext* ctx, const HrptMaterialConstants* materials, uint32_t firstMaterial, uint32_t count);
 
+/* Deforming meshes (skinning, cloth, morph targets, simulation output, an editor dragging a vertex): writes vertices[0..count) over the
+ * vertices [firstVertex, firstVertex + count) of the scene's vertex buffer -- which is global, shared by all meshes -- and brings the
+ * acceleration structure and every per-triangle record after them. Indices, meshes, instances, materials and the vertex count stay.
+ * Contract (that of hrpt_update_instances): after the call every product of the context -- hrpt_render on both kernel paths,
+ * hrpt_trace_rays, hrpt_render_gbuffer, hrpt_selftest_read_bvh -- is bit-identical to that of a context which uploaded a scene built with
+ * the new vertices. Synchronous: waits for frames in flight, returns when the new structure is in place.
+ *   flat structure held by a GPU builder: the builder's device vertex buffer is patched in place and its build kernels run; with
+ *     HRPT_VERTICES_REFIT the hierarchy of the previous build is kept where there is one (as hrpt_refit_instances; HrptBuildInfo::usedBuilder
+ *     then carries HRPT_BVH_BUILDER_REFITTED). No allocation, no index, texture or material traffic.
+ *   flat structure of the host builder: rebuilt on the host from the library's copy of the scene (HRPT_VERTICES_REFIT means rebuild).
+ *   two-level structure: the whole structure, mesh trees included, is rebuilt from the library's copy as at an upload.
+ * hrpt_update_vertices takes quantised vertices in host memory. hrpt_update_vertices_device takes float vertices in DEVICE memory
+ * (HrptVertexFloat, what a skinning or simulation kernel writes; 16-byte aligned), synchronises `stream` (NULL = the default stream)
+ * before it reads them, quantises them on the device by the arithmetic of hrpt_quantize_vertices_host and copies the quantised range
+ * back into the library's host copy (24 bytes per vertex over PCIe), which the host builder, the two-level build, later
+ * hrpt_update_instances / hrpt_update_materials calls and hrpt_selftest_* read.
+ * Atomic on bad input: a position that is not finite (found on the host, or by the quantising kernel before anything is committed), a
+ * NULL array with count > 0, a range beyond the vertex count, unknown flag bits: HRPT_ERR_INVALID_ARGUMENT, and the scene renders
+ * exactly as before the call. No scene: what hrpt_update_instances answers there. If the rebuild itself fails the scene is unusable
+ * until hrpt_upload_scene.
+ * Previous positions (what hrpt_render_motion_vectors forms the previous world position from): the context keeps, per vertex, the
+ * object-space position of the previous frame. A call WITHOUT HRPT_VERTICES_SAME_FRAME first sets previous = current for all vertices
+ * (what lies outside the range did not deform this frame), then records the old positions of its range as previous and installs the new
+ * ones; a call WITH the flag skips the reset (a second range updated in the same frame). count == 0 is HRPT_OK and builds nothing;
+ * without the flag it still resets, so hrpt_update_vertices(ctx, NULL, 0, 0, 0) ends a deformation. A context that never calls this has
+ * previous == current. */
+typedef struct HrptVertexFloat {           /* 48 B */
+    float pos[3]; float normal[3]; float uv[2]; float tangent[4];      /* tangent[3] = handedness sign */
+} HrptVertexFloat;
+enum { HRPT_VERTICES_REFIT = 1, HRPT_VERTICES_SAME_FRAME = 2 };
+int  hrpt_update_vertices(HrptContext* ctx, const HrptVertexQuantized* vertices, uint32_t firstVertex, uint32_t count, uint32_t flags);
+int  hrpt_update_vertices_device(HrptContext* ctx, const HrptVertexFloat* deviceVertices, uint32_t firstVertex, uint32_t count,
+                                 uint32_t flags, void* stream);
+/* The quantiser alone (csrc/pt_deform.h): QuantizeVertex of the scene format (10:10:10 snorm normal + tangent sign, 2 x fp16 uv, 8:8
+ * octahedral tangent), bit-identical on host threads (needs no GPU; nthreads <= 0: one per hardware thread, at most 16) and in the
+ * gfx950 kernel (asynchronous on `stream`; deviceIn 16-byte aligned, deviceOut 4-byte aligned, not overlapping). A NaN normal component,
+ * and the NaN an infinite tangent divides to, count as 0. Positions are copied as they are. NULL pointers with count > 0:
+ * HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_quantize_vertices_host(const HrptVertexFloat* in, uint32_t count, HrptVertexQuantized* out, int nthreads);
+int  hrpt_quantize_vertices_device(HrptContext* ctx, const HrptVertexFloat* deviceIn, uint32_t count, HrptVertexQuantized* deviceOut, void* stream);
+
 /* ---- in-process multi-GPU: one context per GPU inside ONE process ------------------------------------
  * Rank i of n has rendered the row band [i*H/n, (i+1)*H/n) of its accumulation image (HrptFrameParams::tile*; H must be a
  * multiple of n, every context the same size). hrpt_allgather sends every band to every other context with
@@ -446,7 +487,8 @@ int  hrpt_get_gbuffer_device(HrptContext* ctx, uint32_t plane, void** devicePtr)
  * The hit (instance i, primitive p, barycentrics u, v) is the one hrpt_render_gbuffer commits for the same params. With q_k the object-space
  * positions of the primitive's LOD-0 vertices, cur_k = q_k * m_World_i, prev_k = q_k * m_PrevWorld_i (row-vector products, left to right),
  * bx = (1 - u) - v:  worldPos = (cur_0 bx + cur_1 u) + cur_2 v  and prevWorldPos likewise -- the INTERPOLATED vertex position, not o + d t,
- * so equal transforms and equal views give exactly (0, 0, 0). Then
+ * so equal transforms and equal views give exactly (0, 0, 0). After hrpt_update_vertices, prev_k is formed from the object-space positions of
+ * the PREVIOUS frame (see there); a context that never deforms has previous == current. Then
  *   clip = float4(worldPos, 1) * params->constants.m_View.m_MatWorldToClip,   prevClip = float4(prevWorldPos, 1) * prevView->m_MatWorldToClip
  *   window = clip.xy / clip.w * m_ClipToWindowScale + m_ClipToWindowBias      (prevWindow with prevView's scale and bias)
  *   texel  = (prevWindow.x - window.x, prevWindow.y - window.y, prevClip.w - clip.w, 1)        miss: (0, 0, 0, 0)
