@@ -21,6 +21,7 @@
 #include "bvh_build.h"
 #include "bvh_build_gpu.h"
 #include "pt_deform.h"
+#include "pt_skin.h"
 #include "pt_device.h"
 #include "pt_kernels.h"
 #include "pt_motion.h"
@@ -62,7 +63,8 @@ struct HrptContext {
     // deforming meshes (hrpt_update_vertices): the object-space positions of the previous frame, 3 floats per vertex; EMPTY = previous == current
     // (a context that never deforms pays nothing). The device copy is made by the next motion call (motionPositionsStale), like dMotionPositions.
     std::vector<float> keptPrevPositions; float* dMotionPrevPositions = nullptr; bool motionPositionsStale = true;
-    void* dDeformStaging = nullptr; size_t deformStagingBytes = 0;             // hrpt_update_vertices_device: quantised records + the flag word, sized for the whole vertex buffer at first use
+    HrptVertexFloat* dSkinFloats = nullptr;                                    // hrpt_update_vertices_skinned: the skinned float vertices between its two kernels, sized for the whole vertex buffer at first use
+    void* dDeformStaging = nullptr; size_t deformStagingBytes = 0;             // hrpt_update_vertices_device / _skinned: quantised records + the two status words, sized for the whole vertex buffer at first use
     // temporal accumulation (hrpt_temporal_accumulate): ping-pong history pair, allocated by the first call; [temporalCur] is the image the last call wrote
     float4* dTemporal[2] = {}; int temporalCur = 0; bool temporalValid = false;
     // denoise (hrpt_denoise): the default noise tile (uploaded by the first denoise call of the context) and the scratch pair of HRPT_DENOISE_OUTPUT_ONLY
@@ -150,8 +152,9 @@ static void free_motion_tables(HrptContext* c)
     if (c->dMotionIndices) (void)hipFree(c->dMotionIndices);
     if (c->dMotionPrevPositions) (void)hipFree(c->dMotionPrevPositions);
     if (c->dDeformStaging) (void)hipFree(c->dDeformStaging);
+    if (c->dSkinFloats) (void)hipFree(c->dSkinFloats);
     c->dMotionInst = nullptr; c->motionInstCapacity = 0; c->dMotionPositions = nullptr; c->dMotionIndices = nullptr;
-    c->dMotionPrevPositions = nullptr; c->dDeformStaging = nullptr; c->deformStagingBytes = 0; c->keptPrevPositions.clear();
+    c->dMotionPrevPositions = nullptr; c->dDeformStaging = nullptr; c->dSkinFloats = nullptr; c->deformStagingBytes = 0; c->keptPrevPositions.clear();
     c->motionInstStale = c->motionGeometryStale = c->motionPositionsStale = true;
 }
 
@@ -787,34 +790,84 @@ static int update_vertices_impl(HrptContext* c, const HrptVertexQuantized* verti
     return commit_vertices(c, "hrpt_update_vertices", vertices, nullptr, firstVertex, count, flags);
 }
 
+// What hrpt_update_vertices_device and hrpt_update_vertices_skinned share once their arguments are checked: `launch(staged, dStatus2)` puts
+// a kernel on the context's stream that writes `count` quantised records into the staging buffer and raises the two status words behind
+// them (word 0: a position that is not finite; word 1: a joint index out of range); nothing is committed before both are known to be clear.
+extern "C++" template <class Launch>
+static int update_vertices_staged(HrptContext* c, const std::string& what, uint32_t firstVertex, uint32_t count, uint32_t flags, hipStream_t stream, Launch launch)
+{
+    constexpr size_t kStatusBytes = 2 * sizeof(uint32_t);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (count == 0) { roll_previous_positions(c, 0, 0, flags); return HRPT_OK; }
+    HIP_TRY(c, hipStreamSynchronize(stream));           // whatever writes the caller's arrays has to be done before the kernel below reads them
+    const size_t recordBytes = (size_t)count * sizeof(HrptVertexQuantized);
+    if (!c->dDeformStaging) {                           // once per scene: room for the whole vertex buffer + the status words
+        const size_t bytes = c->keptVertices.size() * sizeof(HrptVertexQuantized) + kStatusBytes;
+        HIP_TRY(c, hipMalloc(&c->dDeformStaging, bytes));
+        c->deformStagingBytes = bytes;
+    }
+    if (recordBytes + kStatusBytes > c->deformStagingBytes) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": range exceeds the staging buffer");
+    HrptVertexQuantized* staged = static_cast<HrptVertexQuantized*>(c->dDeformStaging);
+    uint32_t* dStatus = reinterpret_cast<uint32_t*>(static_cast<char*>(c->dDeformStaging) + recordBytes);
+    HIP_TRY(c, hipMemsetAsync(dStatus, 0, kStatusBytes, c->stream));
+    HIP_TRY(c, launch(staged, dStatus));
+    // the copy-back that keeps the host copy current also brings the status words
+    std::vector<HrptVertexQuantized> host((recordBytes + kStatusBytes + sizeof(HrptVertexQuantized) - 1) / sizeof(HrptVertexQuantized));
+    HIP_TRY(c, hipMemcpyAsync(host.data(), staged, recordBytes + kStatusBytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint32_t status[2] = { 0, 0 };
+    std::memcpy(status, reinterpret_cast<const char*>(host.data()) + recordBytes, sizeof status);
+    if (status[1]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": joint index out of range");
+    if (status[0]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": non-finite vertex position");
+    return commit_vertices(c, what.c_str(), host.data(), staged, firstVertex, count, flags);
+}
+
 static int update_vertices_device_impl(HrptContext* c, const HrptVertexFloat* deviceVertices, uint32_t firstVertex, uint32_t count, uint32_t flags, hipStream_t stream)
 {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     HRPT_TRY(check_vertex_update(c, "hrpt_update_vertices_device", deviceVertices, firstVertex, count, flags));
     if (reinterpret_cast<uintptr_t>(deviceVertices) & 15u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_update_vertices_device: deviceVertices must be 16-byte aligned");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (count == 0) { roll_previous_positions(c, 0, 0, flags); return HRPT_OK; }
-    HIP_TRY(c, hipStreamSynchronize(stream));           // whatever writes deviceVertices has to be done before the kernel below reads them
-    const size_t recordBytes = (size_t)count * sizeof(HrptVertexQuantized);
-    if (!c->dDeformStaging) {                           // once per scene: room for the whole vertex buffer + the flag word
-        const size_t bytes = c->keptVertices.size() * sizeof(HrptVertexQuantized) + sizeof(uint32_t);
-        HIP_TRY(c, hipMalloc(&c->dDeformStaging, bytes));
-        c->deformStagingBytes = bytes;
-    }
-    if (recordBytes + sizeof(uint32_t) > c->deformStagingBytes) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_update_vertices_device: range exceeds the staging buffer");
-    HrptVertexQuantized* staged = static_cast<HrptVertexQuantized*>(c->dDeformStaging);
-    uint32_t* dFlag = reinterpret_cast<uint32_t*>(static_cast<char*>(c->dDeformStaging) + recordBytes);
-    HIP_TRY(c, hipMemsetAsync(dFlag, 0, sizeof(uint32_t), c->stream));
-    HIP_TRY(c, launch_quantise_vertices(deviceVertices, count, staged, dFlag, c->stream));
-    // the copy-back that keeps the host copy current also brings the flag: nothing is committed before it is known to be clear
-    std::vector<HrptVertexQuantized> host((recordBytes + sizeof(uint32_t) + sizeof(HrptVertexQuantized) - 1) / sizeof(HrptVertexQuantized));
-    HIP_TRY(c, hipMemcpyAsync(host.data(), staged, recordBytes + sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    uint32_t flag = 0;
-    std::memcpy(&flag, reinterpret_cast<const char*>(host.data()) + recordBytes, sizeof flag);
-    if (flag) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_update_vertices_device: non-finite vertex position");
-    return commit_vertices(c, "hrpt_update_vertices_device", host.data(), staged, firstVertex, count, flags);
+    return update_vertices_staged(c, "hrpt_update_vertices_device", firstVertex, count, flags, stream, [&](HrptVertexQuantized* staged, uint32_t* dStatus) {
+        return launch_quantise_vertices(deviceVertices, count, staged, dStatus, c->stream);
+    });
+}
+
+// ---- the producer in front: hrpt_skin_vertices_host / _device, hrpt_update_vertices_skinned (csrc/pt_skin.h has the definition) ----
+// The argument checks all three share.
+static int skin_args_check(HrptContext* c, const char* what, const HrptSkinArgs* a)
+{
+    const std::string w(what);
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (!a) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null args");
+    if (a->reserved != 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": reserved must be 0");
+    if (misaligned(a->base, 15) || misaligned(a->joints, 7) || misaligned(a->weights, 15) || misaligned(a->jointMatrices, 15) || misaligned(a->deltas, 3) ||
+        misaligned(a->morphWeights, 3))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": base, weights and jointMatrices must be 16-byte aligned, joints 8-byte, deltas and morphWeights 4-byte");
+    if (a->joints && (!a->weights || !a->jointMatrices || a->jointCount == 0)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": joints need weights, jointMatrices and a jointCount > 0");
+    if (a->targetCount > 0 && (!a->deltas || !a->morphWeights)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": targetCount > 0 needs deltas and morphWeights");
+    if (!a->base && a->count > 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null base");
+    return HRPT_OK;
+}
+
+// HRPT_SKIN_PALETTE=1: gather every palette from global memory (the A/B of scripts/skin_bench.py); anything else: by joint count
+static int skin_palette_mode() { const char* e = getenv("HRPT_SKIN_PALETTE"); return e ? atoi(e) : 0; }
+
+static int update_vertices_skinned_impl(HrptContext* c, const HrptSkinArgs* args, uint32_t firstVertex, uint32_t flags, hipStream_t stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(skin_args_check(c, "hrpt_update_vertices_skinned", args));
+    HRPT_TRY(check_vertex_update(c, "hrpt_update_vertices_skinned", args->base, firstVertex, args->count, flags));
+    // Two kernels on the context's stream, the skinned floats in a buffer of the context between them. A kernel that quantised in
+    // registers instead was measured no faster than this and is not kept.
+    return update_vertices_staged(c, "hrpt_update_vertices_skinned", firstVertex, args->count, flags, stream, [&](HrptVertexQuantized* staged, uint32_t* dStatus) {
+        if (!c->dSkinFloats) {                          // once per scene: room for the whole vertex buffer
+            const hipError_t e = hipMalloc((void**)&c->dSkinFloats, c->keptVertices.size() * sizeof(HrptVertexFloat));
+            if (e != hipSuccess) { c->dSkinFloats = nullptr; return e; }
+        }
+        const hipError_t e = launch_skin_vertices(*args, c->dSkinFloats, dStatus, skin_palette_mode(), c->stream);
+        return e != hipSuccess ? e : launch_quantise_vertices(c->dSkinFloats, args->count, staged, dStatus, c->stream);
+    });
 }
 
 int hrpt_resize(HrptContext* c, uint32_t width, uint32_t height)
@@ -940,6 +993,25 @@ int hrpt_update_vertices_device(HrptContext* c, const HrptVertexFloat* deviceVer
     try { return update_vertices_device_impl(c, deviceVertices, firstVertex, count, flags, static_cast<hipStream_t>(stream)); }
     catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_update_vertices_device: host allocation failed"); }
     catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_update_vertices_device: ") + e.what()); }
+}
+int hrpt_update_vertices_skinned(HrptContext* c, const HrptSkinArgs* args, uint32_t firstVertex, uint32_t flags, void* stream)
+{
+    try { return update_vertices_skinned_impl(c, args, firstVertex, flags, static_cast<hipStream_t>(stream)); }
+    catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_update_vertices_skinned: host allocation failed"); }
+    catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_update_vertices_skinned: ") + e.what()); }
+}
+int hrpt_skin_vertices_device(HrptContext* c, const HrptSkinArgs* args, HrptVertexFloat* deviceOut, uint32_t* deviceStatus2, void* stream)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(skin_args_check(c, "hrpt_skin_vertices_device", args));
+    if (args->count == 0) return HRPT_OK;
+    if (!deviceOut || (reinterpret_cast<uintptr_t>(deviceOut) & 15u) || (reinterpret_cast<uintptr_t>(deviceStatus2) & 3u))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_skin_vertices_device: deviceOut must be 16-byte aligned and not NULL, deviceStatus2 4-byte aligned");
+    const uintptr_t in0 = reinterpret_cast<uintptr_t>(args->base), out0 = reinterpret_cast<uintptr_t>(deviceOut), bytes = (uintptr_t)args->count * sizeof(HrptVertexFloat);
+    if (in0 < out0 + bytes && out0 < in0 + bytes) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_skin_vertices_device: deviceOut overlaps base");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_skin_vertices(*args, deviceOut, deviceStatus2, skin_palette_mode(), static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
 }
 int hrpt_quantize_vertices_device(HrptContext* c, const HrptVertexFloat* deviceIn, uint32_t count, HrptVertexQuantized* deviceOut, void* stream)
 {
@@ -1672,6 +1744,16 @@ int hrpt_quantize_vertices_host(const HrptVertexFloat* in, uint32_t count, HrptV
     if (count == 0) return HRPT_OK;
     if (!in || !out) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_quantize_vertices_host: null array");
     return run_host("hrpt_quantize_vertices_host", [&] { (void)quantize_vertices_host(in, count, out, host_threads(nthreads)); });
+}
+int hrpt_skin_vertices_host(const HrptSkinArgs* args, HrptVertexFloat* out, int nthreads)
+{
+    HRPT_TRY(skin_args_check(nullptr, "hrpt_skin_vertices_host", args));
+    if (args->count == 0) return HRPT_OK;
+    if (!out) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_skin_vertices_host: null out");
+    uint32_t status = 0;
+    HRPT_TRY(run_host("hrpt_skin_vertices_host", [&] { status = skin_vertices_host(*args, out, host_threads(nthreads)); }));
+    if (status & skin::kJointOutOfRange) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_skin_vertices_host: joint index out of range");
+    return HRPT_OK;
 }
 int hrpt_compose_host(const HrptComposeImages* img, uint32_t width, uint32_t height, int nthreads)
 {

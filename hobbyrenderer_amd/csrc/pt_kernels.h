@@ -99,6 +99,14 @@ void modulation_probe(const float* albedo3, const float* N3, const float* V3, fl
 hipError_t launch_quantise_vertices(const HrptVertexFloat* in, uint32_t count, HrptVertexQuantized* out, uint32_t* flag, hipStream_t stream);
 bool quantize_vertices_host(const HrptVertexFloat* in, uint32_t count, HrptVertexQuantized* out, int nthreads);
 
+// Vertex producer (pt_skin.hip; arithmetic in pt_skin.h): morph targets + four-joint skinning of args.base, every pointer of args in device
+// memory, into float records (out 16-byte aligned). status2 (device; may be null): word 0 is set to 1 when an output position is not
+// finite, word 1 when a joint index is >= args.jointCount. palette: 0 = LDS up to HRPT_SKIN_LDS_MAX_JOINTS joints and a global gather beyond, 1 = always the
+// gather (for A/B measurements). skin_vertices_host (pt_skin_host.cpp): the same arithmetic on host threads, args in host memory; returns
+// the skin::k* bits, and writes nothing when a joint index is out of range.
+hipError_t launch_skin_vertices(const HrptSkinArgs& args, HrptVertexFloat* out, uint32_t* status2, int palette, hipStream_t stream);
+uint32_t skin_vertices_host(const HrptSkinArgs& args, HrptVertexFloat* out, int nthreads);
+
 // Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
 hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
 

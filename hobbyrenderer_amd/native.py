@@ -29,7 +29,7 @@ lib = C.CDLL(LIB_PATH)
 EXPORTS = [
     "hrpt_create", "hrpt_destroy", "hrpt_last_error", "hrpt_upload_scene", "hrpt_resize", "hrpt_render",
     "hrpt_synchronize", "hrpt_set_stream", "hrpt_get_device_images", "hrpt_read_accumulation", "hrpt_read_output",
-    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_update_vertices", "hrpt_update_vertices_device", "hrpt_quantize_vertices_host", "hrpt_quantize_vertices_device", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
+    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_update_vertices", "hrpt_update_vertices_device", "hrpt_quantize_vertices_host", "hrpt_quantize_vertices_device", "hrpt_skin_vertices_host", "hrpt_skin_vertices_device", "hrpt_update_vertices_skinned", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_render_gbuffer", "hrpt_read_gbuffer", "hrpt_get_gbuffer_device",
     "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
@@ -73,6 +73,9 @@ lib.hrpt_update_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uin
 lib.hrpt_update_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
 lib.hrpt_quantize_vertices_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
 lib.hrpt_quantize_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.hrpt_skin_vertices_host.argtypes = [C.POINTER(S.SkinArgs), C.c_void_p, C.c_int]
+lib.hrpt_skin_vertices_device.argtypes = [C.c_void_p, C.POINTER(S.SkinArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+lib.hrpt_update_vertices_skinned.argtypes = [C.c_void_p, C.POINTER(S.SkinArgs), C.c_uint32, C.c_uint32, C.c_void_p]
 lib.hrpt_reset_stats.argtypes = [C.c_void_p]
 lib.hrpt_selftest_f16_decode.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_selftest_unorm8.argtypes = [C.c_void_p, C.c_void_p]
@@ -327,6 +330,44 @@ def quantize_vertices_host(vertices, nthreads=0):
     return out
 
 
+def skin_arrays(base, joints=None, weights=None, joint_matrices=None, deltas=None, morph_weights=None):
+    """The arrays of an S.SkinArgs in the layout the library reads: base S.VertexFloat [count]; joints uint16 [count, 4], weights float32
+    [count, 4] and joint_matrices float32 [jointCount, 3, 4] (or all three None); deltas S.SkinMorphDelta [targetCount, count] and
+    morph_weights float32 [targetCount] (or both None). Returns (arrays, count, jointCount, targetCount); what was given as None stays None."""
+    base = np.ascontiguousarray(base, S.VertexFloat)
+    n = len(base)
+    if joints is not None:
+        joints = np.ascontiguousarray(joints, np.uint16).reshape(n, 4)
+        weights = np.ascontiguousarray(weights, np.float32).reshape(n, 4)
+        joint_matrices = np.ascontiguousarray(joint_matrices, np.float32).reshape(-1, 3, 4)
+    if deltas is not None:
+        morph_weights = np.ascontiguousarray(morph_weights, np.float32).reshape(-1)
+        deltas = np.ascontiguousarray(deltas, S.SkinMorphDelta).reshape(len(morph_weights), n)
+    arrays = (base, joints, weights, joint_matrices, deltas, morph_weights)
+    return arrays, n, 0 if joints is None else len(joint_matrices), 0 if deltas is None else len(morph_weights)
+
+
+def _aligned_copy(a, align=16):
+    """A copy of array `a` whose first byte lies on a multiple of `align` (NumPy promises no more than the item's own alignment)."""
+    raw = np.empty(a.nbytes + align, np.uint8)
+    start = -raw.ctypes.data % align
+    out = raw[start:start + a.nbytes].view(a.dtype).reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def skin_vertices_host(base, joints=None, weights=None, joint_matrices=None, deltas=None, morph_weights=None, nthreads=0):
+    """hrpt_skin_vertices_host: morph targets, then four-joint skinning, then unit normal and tangent (csrc/pt_skin.h) of the bind pose
+    `base` (S.VertexFloat records) on host threads; the arrays are those of skin_arrays(). Returns S.VertexFloat records. Needs no GPU and
+    is bit-identical to PathTracerContext.skin_vertices_device and to tests/skin_reference.py. A joint index out of range raises."""
+    arrays, n, joint_count, target_count = skin_arrays(base, joints, weights, joint_matrices, deltas, morph_weights)
+    arrays = [None if a is None else _aligned_copy(a) for a in arrays]
+    out = _aligned_copy(np.zeros(n, S.VertexFloat))
+    args = S.SkinArgs(*[None if a is None or not a.size else a.ctypes.data for a in arrays], n, joint_count, target_count, 0)
+    _check_rc(lib.hrpt_skin_vertices_host(C.byref(args), out.ctypes.data if n else None, int(nthreads)))
+    return out
+
+
 _BVH_DUMP_ARRAYS = (("nodes", S.GpuNode, "nodeCount"), ("nodes4", S.GpuNode4, "node4Count"), ("nodesQ", S.GpuNodeQ, "node4Count"),
                     ("triangles", S.GpuTri, "triangleCount"), ("attributes", S.GpuTriAttr, "triangleCount"),
                     ("tangents", S.GpuTriTangent, "triangleCount"), ("instances", S.GpuInstance, "instanceCount"))
@@ -562,6 +603,22 @@ class PathTracerContext:
         S.VertexQuantized records at out_ptr, both device addresses; asynchronous on `stream` (integer handle)."""
         self._check(lib.hrpt_quantize_vertices_device(self._h, C.c_void_p(int(in_ptr)) if in_ptr else None, int(count),
                                                       C.c_void_p(int(out_ptr)) if out_ptr else None, C.c_void_p(int(stream)) if stream else None))
+
+    def skin_vertices_device(self, base, joints, weights, joint_matrices, deltas, morph_weights, count, joint_count, target_count, out_ptr,
+                             status_ptr=0, stream=0):
+        """hrpt_skin_vertices_device: the skinning kernel alone. The first six arguments are device addresses (0 = NULL) of the arrays
+        skin_arrays() describes, out_ptr that of `count` S.VertexFloat records (16-byte aligned), status_ptr that of two zeroed uint32
+        (word 0: an output position is not finite; word 1: a joint index is out of range) or 0. Asynchronous on `stream`."""
+        args = S.SkinArgs(*[int(p) or None for p in (base, joints, weights, joint_matrices, deltas, morph_weights)], int(count), int(joint_count), int(target_count), 0)
+        self._check(lib.hrpt_skin_vertices_device(self._h, C.byref(args), C.c_void_p(int(out_ptr)) if out_ptr else None,
+                                                  C.c_void_p(int(status_ptr)) if status_ptr else None, C.c_void_p(int(stream)) if stream else None))
+
+    def update_vertices_skinned(self, base, joints, weights, joint_matrices, deltas, morph_weights, count, joint_count, target_count, first,
+                                flags=0, stream=0):
+        """hrpt_update_vertices_skinned: update_vertices_device with the skinning kernel in front of the quantiser, in one call; the same
+        device addresses as skin_vertices_device, for the vertices [first, first + count) of the scene."""
+        args = S.SkinArgs(*[int(p) or None for p in (base, joints, weights, joint_matrices, deltas, morph_weights)], int(count), int(joint_count), int(target_count), 0)
+        self._check(lib.hrpt_update_vertices_skinned(self._h, C.byref(args), int(first), int(flags), C.c_void_p(int(stream)) if stream else None))
 
     def build_info(self):
         bi = S.BuildInfo()

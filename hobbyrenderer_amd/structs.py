@@ -184,6 +184,19 @@ class ComposeImages(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("color", "modulation", "emissive", "colorOut")]
 
 
+# HrptSkinMorphDelta: one vertex of one morph target (hrpt_skin_vertices_* / hrpt_update_vertices_skinned), 36 B
+SkinMorphDelta = np.dtype([("pos", f32, 3), ("normal", f32, 3), ("tangent", f32, 3)])
+assert SkinMorphDelta.itemsize == 36
+SKIN_LDS_MAX_JOINTS = 256          # HRPT_SKIN_LDS_MAX_JOINTS: up to this many joints the kernels serve the palette from LDS
+
+
+class SkinArgs(C.Structure):
+    """HrptSkinArgs: host addresses for skin_vertices_host, device addresses for the two context calls. joints None: no skinning;
+    deltas None iff targetCount == 0."""
+    _fields_ = [(n, C.c_void_p) for n in ("base", "joints", "weights", "jointMatrices", "deltas", "morphWeights")] + \
+               [(n, C.c_uint32) for n in ("count", "jointCount", "targetCount", "reserved")]
+
+
 class Stats(C.Structure):
     _fields_ = [("closestRays", C.c_uint64), ("shadowRays", C.c_uint64), ("paths", C.c_uint64),
                 ("lastRenderMs", C.c_float), ("traceKernelMs", C.c_float), ("traceKernelLaunches", C.c_uint32),

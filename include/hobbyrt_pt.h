@@ -394,7 +394,8 @@ int  hrpt_update_materials(HrptContext* ctx, const HrptMaterialConstants* materi
  *   flat structure of the host builder: rebuilt on the host from the library's copy of the scene (HRPT_VERTICES_REFIT means rebuild).
  *   two-level structure: the whole structure, mesh trees included, is rebuilt from the library's copy as at an upload.
  * hrpt_update_vertices takes quantised vertices in host memory. hrpt_update_vertices_device takes float vertices in DEVICE memory
- * (HrptVertexFloat, what a skinning or simulation kernel writes; 16-byte aligned), synchronises `stream` (NULL = the default stream)
+ * (HrptVertexFloat, what a skinning or simulation kernel writes -- hrpt_skin_vertices_device below is one, and
+ * hrpt_update_vertices_skinned runs it in front of the quantiser in one call; 16-byte aligned), synchronises `stream` (NULL = the default stream)
  * before it reads them, quantises them on the device by the arithmetic of hrpt_quantize_vertices_host and copies the quantised range
  * back into the library's host copy (24 bytes per vertex over PCIe), which the host builder, the two-level build, later
  * hrpt_update_instances / hrpt_update_materials calls and hrpt_selftest_* read.
@@ -422,6 +423,46 @@ int  hrpt_update_vertices_device(HrptContext* ctx, const HrptVertexFloat* device
  * HRPT_ERR_INVALID_ARGUMENT. */
 int  hrpt_quantize_vertices_host(const HrptVertexFloat* in, uint32_t count, HrptVertexQuantized* out, int nthreads);
 int  hrpt_quantize_vertices_device(HrptContext* ctx, const HrptVertexFloat* deviceIn, uint32_t count, HrptVertexQuantized* deviceOut, void* stream);
+
+/* The producer in front of the quantiser (csrc/pt_skin.h has the definition, DESIGN.md section 22 the prose): morph targets, then
+ * linear-blend skinning with four joints per vertex, then unit normal and tangent, from a bind pose to HrptVertexFloat records with the
+ * conventions the quantiser expects (tangent[3] = handedness sign, flipped by a mirroring joint; unit normals). float32, one rounding per
+ * operation, bit-identical on host threads, in the gfx950 kernels and in tests/skin_reference.py. The reference renderer has no skinning:
+ * parity unpinned by the reference.
+ *   morph   for k < targetCount in order, w = morphWeights[k]: skipped when w == 0 (+0 or -0), else pos / normal / tangent += w * delta
+ *   skin    (joints != NULL) B = ((w0 M0 + w1 M1) + w2 M2) + w3 M3 with Mj = jointMatrices[joints[4i + j]], a row-major 3 x 4 with
+ *           p' = M [p; 1] (for glTF: the top three rows of globalJoint * inverseBind, pre-multiplied by the inverse of the mesh node's world
+ *           transform for object space). Weights are used as given. Position by B, tangent by its 3 x 3 part, normal by the cofactor
+ *           matrix of that part; a negative determinant negates the normal and tangent[3].
+ *   unit    normal and tangent are divided by their length where its square is positive and finite, and left as they are otherwise.
+ * A joint index >= jointCount, and an output position that is not finite, are errors of the input: _host returns
+ * HRPT_ERR_INVALID_ARGUMENT for the first and leaves `out` untouched (the second it writes like any other value, as the quantiser copies
+ * one); the kernels stay inside the palette (they read joint jointCount - 1) and raise a word of their status array: word 0 "output
+ * position not finite", word 1 "joint index out of range".
+ * hrpt_skin_vertices_device is asynchronous on `stream`; deviceOut is 16-byte aligned and does not overlap base; deviceStatus2 is two
+ * words the caller zeroed, or NULL. hrpt_update_vertices_skinned is hrpt_update_vertices_device with the skinning kernel in front of the
+ * quantiser, both on the context's stream: the caller parks no float vertices (the context holds them, 48 bytes per vertex of the scene,
+ * allocated at first use) and there is one call and one wait on `stream` instead of two. Same checks (count = args->count), same
+ * synchronisation, same previous-position protocol, same flags; either status word set is HRPT_ERR_INVALID_ARGUMENT and the scene renders
+ * exactly as before.
+ * All three: NULL args, non-zero reserved, a misaligned pointer, a NULL base with count > 0, joints without weights or jointMatrices or
+ * with jointCount == 0, targetCount > 0 with NULL deltas or morphWeights: HRPT_ERR_INVALID_ARGUMENT. count == 0 is HRPT_OK (in the update
+ * call it rolls the previous positions as hrpt_update_vertices_device does).
+ * A palette of at most HRPT_SKIN_LDS_MAX_JOINTS joints is served from LDS, a larger one gathered from global memory: same bits. */
+#define HRPT_SKIN_LDS_MAX_JOINTS 256
+typedef struct HrptSkinMorphDelta { float pos[3]; float normal[3]; float tangent[3]; } HrptSkinMorphDelta;   /* 36 B */
+typedef struct HrptSkinArgs {
+    const HrptVertexFloat*    base;           /* count records, the bind pose; 16-byte aligned */
+    const uint16_t*           joints;         /* count x 4, 8-byte aligned; NULL: no skinning (weights, jointMatrices, jointCount ignored) */
+    const float*              weights;        /* count x 4, 16-byte aligned */
+    const float*              jointMatrices;  /* jointCount x 12 (row-major 3x4, p' = M [p;1]); 16-byte aligned */
+    const HrptSkinMorphDelta* deltas;         /* targetCount x count, target-major; NULL iff targetCount == 0 */
+    const float*              morphWeights;   /* targetCount */
+    uint32_t count, jointCount, targetCount, reserved /* 0 */;
+} HrptSkinArgs;   /* every pointer: host memory for _host, device memory for the other two */
+int  hrpt_skin_vertices_host(const HrptSkinArgs* args, HrptVertexFloat* out, int nthreads);
+int  hrpt_skin_vertices_device(HrptContext* ctx, const HrptSkinArgs* args, HrptVertexFloat* deviceOut, uint32_t* deviceStatus2, void* stream);
+int  hrpt_update_vertices_skinned(HrptContext* ctx, const HrptSkinArgs* args, uint32_t firstVertex, uint32_t flags, void* stream);
 
 /* ---- in-process multi-GPU: one context per GPU inside ONE process ------------------------------------
  * Rank i of n has rendered the row band [i*H/n, (i+1)*H/n) of its accumulation image (HrptFrameParams::tile*; H must be a
