@@ -22,12 +22,24 @@
 #include "bvh_build_gpu.h"
 #include "pt_deform.h"
 #include "pt_skin.h"
+#include "pt_anim.h"
 #include "pt_device.h"
 #include "pt_kernels.h"
 #include "pt_motion.h"
 #include "pt_wavefront.h"
 
 using namespace hrt;
+
+// The device copy of one animation on one context (hrpt_animate): the resolved tables, and the state its kernels write.
+struct AnimDeviceCopy {
+    const HrptAnimation* anim = nullptr; uint64_t serial = 0;
+    std::vector<void*> allocations;
+    anim::Tables tables{};
+    uint32_t* groupFirst = nullptr; float* times = nullptr;
+    float* trs = nullptr; float* worlds = nullptr; float* weights = nullptr; float* palette = nullptr;
+    HrptPerInstanceData* records = nullptr;      // the closed instance range; equal to the context's host copy of it while recordsEpoch == instanceEpoch
+    uint64_t recordsEpoch = 0;
+};
 
 struct HrptContext {
     int device = 0;
@@ -82,6 +94,8 @@ struct HrptContext {
     std::vector<void*> meshAllocations;           // ... and the device copies of the per-mesh arrays, which survive instance updates
     uint32_t megakernelFallbacks = 0;             // renders that wanted the wavefront pipeline but could not use it (HrptStats)
     HrptBuildInfo buildInfo{};
+    std::vector<AnimDeviceCopy> animations;       // hrpt_animate: one device copy per animation seen, until hrpt_animation_release / hrpt_destroy
+    uint64_t instanceEpoch = 1;                   // bumped whenever keptInstances changes
 };
 
 static std::mutex g_errMutex;
@@ -167,7 +181,14 @@ static void free_scene(HrptContext* c)
     if (c->nodesQ) { (void)hipFree(c->nodesQ); c->nodesQ = nullptr; c->nodesQCapacity = 0; }
     c->keptVertices.clear(); c->keptIndices.clear(); c->keptMeshData.clear(); c->keptInstances.clear(); c->keptMaterials.clear(); c->keptLights.clear(); c->lightCapacity = 0;
     c->haveScene = false;
+    ++c->instanceEpoch;
     memset(&c->view, 0, sizeof c->view);
+}
+
+static void free_animation_copy(AnimDeviceCopy& a)
+{
+    for (void* p : a.allocations) (void)hipFree(p);
+    a = AnimDeviceCopy{};
 }
 
 template <class T>
@@ -233,6 +254,7 @@ void hrpt_destroy(HrptContext* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_scene(c);
+    for (AnimDeviceCopy& a : c->animations) free_animation_copy(a);
     wavefront_release(c->wf);
     if (c->dAccum) (void)hipFree(c->dAccum);
     if (c->dOutput) (void)hipFree(c->dOutput);
@@ -714,6 +736,7 @@ static int update_instances_impl(HrptContext* c, const HrptPerInstanceData* inst
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));        // frames in flight still traverse the old tree
     std::memcpy(c->keptInstances.data() + firstInstance, instances, (size_t)count * sizeof(HrptPerInstanceData));
+    ++c->instanceEpoch;
     c->motionInstStale = true;                          // m_PrevWorld travels in these records (hrpt_render_motion_vectors)
     HrptSceneDesc s = kept_scene_desc(c);
     const uint64_t sceneTris = kept_triangle_count(c);
@@ -721,6 +744,104 @@ static int update_instances_impl(HrptContext* c, const HrptPerInstanceData* inst
     int r = build_acceleration(c, s, sceneTris, v, false, refit);
     if (r != HRPT_OK) { c->haveScene = false; return r; }   // the old tree is gone: the scene has to be uploaded again
     c->view = v;
+    return HRPT_OK;
+}
+
+// ---- keyframe animation on the device: hrpt_animate and its companions (csrc/pt_anim.h has the definition) ----
+static AnimDeviceCopy* find_animation_copy(HrptContext* c, const HrptAnimation* anim)
+{
+    for (AnimDeviceCopy& a : c->animations) if (a.anim == anim && a.serial == anim->serial) return &a;
+    return nullptr;
+}
+
+// Uploads the resolved tables and seeds the state: once per (context, animation).
+static int upload_animation(HrptContext* c, const HrptAnimation* anim, AnimDeviceCopy*& out)
+{
+    for (size_t i = 0; i < c->animations.size(); ++i)          // an address reused by a newer animation: the old copy is dead
+        if (c->animations[i].anim == anim) { free_animation_copy(c->animations[i]); c->animations.erase(c->animations.begin() + (long)i); break; }
+    AnimDeviceCopy a;
+    a.anim = anim; a.serial = anim->serial;
+    int r = HRPT_OK;
+    auto put = [&](const auto& v, auto*& dev) {
+        using T = typename std::remove_reference<decltype(v)>::type::value_type;
+        const T* d = nullptr;
+        if (r == HRPT_OK) r = upload(c, v.data(), v.size(), &d, &a.allocations);
+        dev = const_cast<T*>(d);
+    };
+    HrptAnimSampler* samplers; float* keyTimes; float* keyValues; HrptAnimChannel* channels; uint32_t* targets; uint32_t* order; int32_t* orderParent;
+    uint32_t* rangeNode; uint32_t* jointNode; float* inverseBind;
+    put(anim->samplers, samplers); put(anim->keyTimes, keyTimes); put(anim->keyValues, keyValues); put(anim->channels, channels); put(anim->targets, targets);
+    put(anim->order, order); put(anim->orderParent, orderParent); put(anim->rangeNode, rangeNode); put(anim->jointNode, jointNode); put(anim->inverseBind, inverseBind);
+    put(anim->groupFirst, a.groupFirst); put(anim->times, a.times); put(anim->baseTrs, a.trs); put(anim->baseWorlds, a.worlds);
+    const std::vector<float> zeroWeights(anim->morphWeightCount, 0.0f), zeroPalette(12 * anim->jointNode.size(), 0.0f);
+    put(zeroWeights, a.weights); put(zeroPalette, a.palette);
+    const std::vector<HrptPerInstanceData> zeroRecords(anim->rangeNode.size());
+    put(zeroRecords, a.records);
+    if (r == HRPT_OK && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(c, HRPT_ERR_HIP, "hrpt_animate: table upload failed");   // the staging vectors above die here
+    if (r != HRPT_OK) { free_animation_copy(a); return r; }
+    a.tables = anim->tables();
+    a.tables.samplers = samplers; a.tables.keyTimes = keyTimes; a.tables.keyValues = keyValues; a.tables.channels = channels; a.tables.targets = targets;
+    a.tables.order = order; a.tables.orderParent = orderParent; a.tables.rangeNode = rangeNode; a.tables.jointNode = jointNode; a.tables.inverseBind = inverseBind;
+    c->animations.push_back(a);
+    out = &c->animations.back();
+    return HRPT_OK;
+}
+
+static int animate_impl(HrptContext* c, const HrptAnimation* anim, uint32_t flags)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!anim) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animate: null animation");
+    if (flags & ~(uint32_t)(HRPT_ANIMATE_REFIT | HRPT_ANIMATE_NO_COMMIT)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animate: unknown flag bits");
+    const bool evaluateInstances = (flags & HRPT_ANIMATE_NO_COMMIT) == 0;
+    if (evaluateInstances) {
+        if (!c->haveScene) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animate: no scene uploaded");
+        if (anim->instanceNeed > c->keptInstances.size()) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animate: an instance index of the animation exceeds the scene's instance count");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    AnimDeviceCopy* a = find_animation_copy(c, anim);
+    if (!a) HRPT_TRY(upload_animation(c, anim, a));
+    const uint32_t range = (uint32_t)anim->rangeNode.size();
+    const bool commit = evaluateInstances && range > 0;
+    if (!anim->times.empty()) HIP_TRY(c, hipMemcpyAsync(a->times, anim->times.data(), anim->times.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (commit && a->recordsEpoch != c->instanceEpoch) {       // something else wrote the instances since this copy was made
+        HIP_TRY(c, hipMemcpyAsync(a->records, c->keptInstances.data() + anim->instanceFirst, (size_t)range * sizeof(HrptPerInstanceData), hipMemcpyHostToDevice, c->stream));
+        a->recordsEpoch = 0;
+    }
+    // HRPT_ANIM_TIMING (scripts/anim_bench.py): device time of the kernels between events, host time of the read-back and of the commit, on stderr
+    const bool timing = getenv("HRPT_ANIM_TIMING") != nullptr;
+    if (timing) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
+    HIP_TRY(c, launch_animate(a->tables, a->times, a->groupFirst, anim->groupFirst.data(), (uint32_t)anim->groupFirst.size() - 1u, a->trs, a->worlds, a->weights, a->palette,
+                              commit ? a->records : nullptr, c->stream));
+    float kernelMs = 0.0f;
+    if (timing) {
+        HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
+        HIP_TRY(c, hipEventSynchronize(c->evStop));
+        HIP_TRY(c, hipEventElapsedTime(&kernelMs, c->evStart, c->evStop));
+        if (!commit) fprintf(stderr, "[animate] kernels %.4f ms\n", kernelMs);
+    }
+    if (!commit) return HRPT_OK;                                // evaluation only, or no instance hangs under a composed node: nothing to commit, nothing to build
+    const auto t0 = std::chrono::steady_clock::now();
+    // the commit of hrpt_update_instances: the evaluated range comes back into the host copy, the rest of the roll is host work
+    std::vector<HrptPerInstanceData> evaluated(range);
+    HIP_TRY(c, hipMemcpyAsync(evaluated.data(), a->records, (size_t)range * sizeof(HrptPerInstanceData), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < c->keptInstances.size(); ++i)
+        if (i < anim->instanceFirst || i - anim->instanceFirst >= range) std::memcpy(c->keptInstances[i].m_PrevWorld, c->keptInstances[i].m_World, sizeof(float) * 16);
+    const auto t1 = std::chrono::steady_clock::now();
+    const int r = update_instances_impl(c, evaluated.data(), anim->instanceFirst, range, (flags & HRPT_ANIMATE_REFIT) != 0);
+    if (timing) fprintf(stderr, "[animate] kernels %.4f ms read-back and roll %.4f ms commit %.4f ms\n", kernelMs, std::chrono::duration<float, std::milli>(t1 - t0).count(),
+                        std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count());
+    a = find_animation_copy(c, anim);
+    if (a) a->recordsEpoch = r == HRPT_OK ? c->instanceEpoch : 0;
+    return r;
+}
+
+static int animation_pointers(HrptContext* c, const char* what, const HrptAnimation* anim, AnimDeviceCopy*& a)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!anim) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": null animation");
+    a = find_animation_copy(c, anim);
+    if (!a) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": hrpt_animate has not run for this animation on this context");
     return HRPT_OK;
 }
 
@@ -999,6 +1120,46 @@ int hrpt_update_vertices_skinned(HrptContext* c, const HrptSkinArgs* args, uint3
     try { return update_vertices_skinned_impl(c, args, firstVertex, flags, static_cast<hipStream_t>(stream)); }
     catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_update_vertices_skinned: host allocation failed"); }
     catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_update_vertices_skinned: ") + e.what()); }
+}
+int hrpt_animate(HrptContext* c, const HrptAnimation* anim, uint32_t flags)
+{
+    try { return animate_impl(c, anim, flags); }
+    catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, "hrpt_animate: host allocation failed"); }
+    catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_animate: ") + e.what()); }
+}
+int hrpt_get_animation_device(HrptContext* c, const HrptAnimation* anim, void** palette, void** weights, void** nodeWorlds)
+{
+    AnimDeviceCopy* a = nullptr;
+    HRPT_TRY(animation_pointers(c, "hrpt_get_animation_device", anim, a));
+    if (palette) *palette = anim->jointNode.empty() ? nullptr : a->palette;
+    if (weights) *weights = anim->morphWeightCount ? a->weights : nullptr;
+    if (nodeWorlds) *nodeWorlds = anim->nodes.empty() ? nullptr : a->worlds;
+    return HRPT_OK;
+}
+int hrpt_read_animation(HrptContext* c, const HrptAnimation* anim, float* palette, float* weights, float* nodeWorlds)
+{
+    AnimDeviceCopy* a = nullptr;
+    HRPT_TRY(animation_pointers(c, "hrpt_read_animation", anim, a));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (palette && !anim->jointNode.empty()) HIP_TRY(c, hipMemcpyAsync(palette, a->palette, anim->jointNode.size() * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (weights && anim->morphWeightCount) HIP_TRY(c, hipMemcpyAsync(weights, a->weights, anim->morphWeightCount * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nodeWorlds && !anim->nodes.empty()) HIP_TRY(c, hipMemcpyAsync(nodeWorlds, a->worlds, anim->nodes.size() * 16 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HRPT_OK;
+}
+int hrpt_animation_release(HrptContext* c, const HrptAnimation* anim)
+{
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!anim) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animation_release: null animation");
+    HIP_TRY(c, hipSetDevice(c->device));
+    for (size_t i = 0; i < c->animations.size(); ++i)
+        if (c->animations[i].anim == anim) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            free_animation_copy(c->animations[i]);
+            c->animations.erase(c->animations.begin() + (long)i);
+            break;
+        }
+    return HRPT_OK;
 }
 int hrpt_skin_vertices_device(HrptContext* c, const HrptSkinArgs* args, HrptVertexFloat* deviceOut, uint32_t* deviceStatus2, void* stream)
 {
@@ -1745,6 +1906,46 @@ int hrpt_quantize_vertices_host(const HrptVertexFloat* in, uint32_t count, HrptV
     if (!in || !out) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_quantize_vertices_host: null array");
     return run_host("hrpt_quantize_vertices_host", [&] { (void)quantize_vertices_host(in, count, out, host_threads(nthreads)); });
 }
+// ---- keyframe animation without a context: the tables, the clock and the host executor (csrc/pt_anim_host.cpp) ----
+int hrpt_animation_create(const HrptAnimationDesc* desc, HrptAnimation** out)
+{
+    if (!out) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animation_create: null out");
+    *out = nullptr;
+    if (!desc) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animation_create: null desc");
+    std::string err;
+    HRPT_TRY(run_host("hrpt_animation_create", [&] { *out = animation_create(*desc, err); }));
+    return *out ? HRPT_OK : fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animation_create: " + err);
+}
+void hrpt_animation_destroy(HrptAnimation* anim) { delete anim; }
+int hrpt_animation_advance(HrptAnimation* anim, float dt)
+{
+    if (!anim) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animation_advance: null animation");
+    animation_advance(*anim, dt);
+    return HRPT_OK;
+}
+int hrpt_animation_set_times(HrptAnimation* anim, const float* times, uint32_t count)
+{
+    if (!anim || count != anim->times.size() || (count && !times)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animation_set_times: null argument, or count is not the animation count");
+    for (uint32_t i = 0; i < count; ++i) anim->times[i] = times[i];
+    return HRPT_OK;
+}
+int hrpt_animation_get_times(const HrptAnimation* anim, float* times, float* durations, uint32_t count)
+{
+    if (!anim || count != anim->times.size()) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animation_get_times: null animation, or count is not the animation count");
+    for (uint32_t i = 0; i < count; ++i) { if (times) times[i] = anim->times[i]; if (durations) durations[i] = anim->durations[i]; }
+    return HRPT_OK;
+}
+int hrpt_animate_host(const HrptAnimation* anim, const HrptPerInstanceData* prevInstances, HrptPerInstanceData* instancesInOut, uint32_t instanceCount,
+                      float* paletteOut, float* weightsOut, float* nodeWorldsOut, int nthreads)
+{
+    if (!anim) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animate_host: null animation");
+    if (instancesInOut && anim->instanceNeed > instanceCount) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_animate_host: an instance index of the animation exceeds instanceCount");
+    return run_host("hrpt_animate_host", [&] {
+        if (instancesInOut && prevInstances && prevInstances != instancesInOut) std::memmove(instancesInOut, prevInstances, (size_t)instanceCount * sizeof(HrptPerInstanceData));
+        animate_host(*anim, instancesInOut, instancesInOut ? instanceCount : 0u, paletteOut, weightsOut, nodeWorldsOut, host_threads(nthreads));
+    });
+}
+
 int hrpt_skin_vertices_host(const HrptSkinArgs* args, HrptVertexFloat* out, int nthreads)
 {
     HRPT_TRY(skin_args_check(nullptr, "hrpt_skin_vertices_host", args));

@@ -107,6 +107,15 @@ bool quantize_vertices_host(const HrptVertexFloat* in, uint32_t count, HrptVerte
 hipError_t launch_skin_vertices(const HrptSkinArgs& args, HrptVertexFloat* out, uint32_t* status2, int palette, hipStream_t stream);
 uint32_t skin_vertices_host(const HrptSkinArgs& args, HrptVertexFloat* out, int nthreads);
 
+// Animation stage (pt_anim.hip; arithmetic in pt_anim.h): the three kernels of hrpt_animate on `stream`, every pointer in device memory.
+// tables: anim::Tables with device arrays; times: one per animation; groupFirst: groups + 1 offsets into tables.order (device) and the same
+// on the host; trs (12 floats per node, seeded with the base pose), worlds (16 per node, seeded with baseWorld), weights and palette are
+// the state the kernels write. records: the instance records [tables.instanceFirst, + tables.instanceRange), 160 bytes each, or null to
+// leave instances alone.
+namespace anim { struct Tables; }
+hipError_t launch_animate(const anim::Tables& tables, const float* times, const uint32_t* groupFirst, const uint32_t* groupFirstHost, uint32_t groups,
+                          float* trs, float* worlds, float* weights, float* palette, void* records, hipStream_t stream);
+
 // Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
 hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
 

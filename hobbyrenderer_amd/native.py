@@ -39,6 +39,8 @@ EXPORTS = [
     "hrpt_demodulate_host", "hrpt_compose_host", "hrpt_demodulate_device", "hrpt_compose_device", "hrpt_demodulate", "hrpt_compose",
     "hrpt_read_modulation", "hrpt_get_modulation_device", "hrpt_modulation_probe",
     "hrpt_precompute_atmosphere", "hrpt_precompute_atmosphere_ex", "hrpt_atmosphere_pass",
+    "hrpt_animation_create", "hrpt_animation_destroy", "hrpt_animation_advance", "hrpt_animation_set_times", "hrpt_animation_get_times",
+    "hrpt_animate_host", "hrpt_animate", "hrpt_get_animation_device", "hrpt_read_animation", "hrpt_animation_release",
 ]
 
 lib.hrpt_create.argtypes = [C.POINTER(S.DeviceDesc), C.POINTER(C.c_void_p)]
@@ -76,6 +78,17 @@ lib.hrpt_quantize_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32
 lib.hrpt_skin_vertices_host.argtypes = [C.POINTER(S.SkinArgs), C.c_void_p, C.c_int]
 lib.hrpt_skin_vertices_device.argtypes = [C.c_void_p, C.POINTER(S.SkinArgs), C.c_void_p, C.c_void_p, C.c_void_p]
 lib.hrpt_update_vertices_skinned.argtypes = [C.c_void_p, C.POINTER(S.SkinArgs), C.c_uint32, C.c_uint32, C.c_void_p]
+lib.hrpt_animation_create.argtypes = [C.POINTER(S.AnimationDesc), C.POINTER(C.c_void_p)]
+lib.hrpt_animation_destroy.argtypes = [C.c_void_p]
+lib.hrpt_animation_destroy.restype = None
+lib.hrpt_animation_advance.argtypes = [C.c_void_p, C.c_float]
+lib.hrpt_animation_set_times.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+lib.hrpt_animation_get_times.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+lib.hrpt_animate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+lib.hrpt_animate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+lib.hrpt_get_animation_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+lib.hrpt_read_animation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.hrpt_animation_release.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_reset_stats.argtypes = [C.c_void_p]
 lib.hrpt_selftest_f16_decode.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_selftest_unorm8.argtypes = [C.c_void_p, C.c_void_p]
@@ -330,6 +343,80 @@ def quantize_vertices_host(vertices, nthreads=0):
     return out
 
 
+def animation_desc(samplers=(), channels=(), nodes=(), joints=(), key_times=(), key_values=(), targets=(), node_instances=(), animation_count=0,
+                   morph_weight_count=0, reserved=0):
+    """The tables of an animation as contiguous arrays in the library's layouts and the S.AnimationDesc over them: (desc, arrays). The
+    arrays must outlive the desc. samplers S.AnimSampler, channels S.AnimChannel, nodes S.AnimNode, joints S.AnimJoint, key_times float32
+    [keys], key_values float32 [keys, 4], targets and node_instances uint32."""
+    records = lambda a, dtype: np.ascontiguousarray(a, dtype) if len(a) else np.zeros(0, dtype)      # noqa: E731
+    arrays = [records(samplers, S.AnimSampler), records(channels, S.AnimChannel), records(nodes, S.AnimNode),
+              records(joints, S.AnimJoint), np.ascontiguousarray(key_times, np.float32).reshape(-1),
+              np.ascontiguousarray(key_values, np.float32).reshape(-1, 4), np.ascontiguousarray(targets, np.uint32).reshape(-1),
+              np.ascontiguousarray(node_instances, np.uint32).reshape(-1)]
+    if len(arrays[5]) != len(arrays[4]):
+        raise ValueError("animation_desc: one float4 value per key time expected")
+    counts = [len(arrays[k]) for k in (0, 1, 2, 3, 4, 6, 7)]
+    desc = S.AnimationDesc(*[a.ctypes.data if a.size else None for a in arrays], *counts, int(animation_count), int(morph_weight_count), int(reserved))
+    return desc, arrays
+
+
+class Animation:
+    """hrpt_animation_create: validated, resolved copy of animation tables (animation_desc's keywords); context-free. times / durations,
+    advance(dt) and set_times are the host clock; evaluate_host runs csrc/pt_anim.h on host threads; PathTracerContext.animate runs it on
+    the device."""
+
+    def __init__(self, **tables):
+        desc, arrays = animation_desc(**tables)
+        self._h = C.c_void_p()
+        _check_rc(lib.hrpt_animation_create(C.byref(desc), C.byref(self._h)))
+        self.animation_count, self.node_count = desc.animationCount, desc.nodeCount
+        self.joint_count, self.morph_weight_count = desc.jointCount, desc.morphWeightCount
+
+    def close(self):
+        if self._h:
+            lib.hrpt_animation_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def advance(self, dt):
+        _check_rc(lib.hrpt_animation_advance(self._h, float(dt)))
+
+    def set_times(self, times):
+        times = np.ascontiguousarray(times, np.float32).reshape(-1)
+        _check_rc(lib.hrpt_animation_set_times(self._h, times.ctypes.data if times.size else None, len(times)))
+
+    def _clock(self, which):
+        out = np.zeros(self.animation_count, np.float32)
+        args = [None, None]
+        args[which] = out.ctypes.data
+        _check_rc(lib.hrpt_animation_get_times(self._h, *args, self.animation_count))
+        return out
+
+    @property
+    def times(self):
+        return self._clock(0)
+
+    @property
+    def durations(self):
+        return self._clock(1)
+
+    def evaluate_host(self, instances=None, nthreads=0):
+        """hrpt_animate_host at the current times: (instances, palette [joints, 3, 4], weights, node worlds [nodes, 4, 4]). `instances`
+        (S.PerInstanceData records of the whole scene, or None) is not modified: the first result is the rolled and moved copy."""
+        out = None if instances is None else np.array(instances, S.PerInstanceData, copy=True, order="C")
+        palette = np.zeros((self.joint_count, 3, 4), np.float32)
+        weights = np.zeros(self.morph_weight_count, np.float32)
+        worlds = np.zeros((self.node_count, 4, 4), np.float32)
+        _check_rc(lib.hrpt_animate_host(self._h, None, None if out is None else out.ctypes.data, 0 if out is None else len(out),
+                                        palette.ctypes.data, weights.ctypes.data, worlds.ctypes.data, int(nthreads)))
+        return out, palette, weights, worlds
+
+
 def skin_arrays(base, joints=None, weights=None, joint_matrices=None, deltas=None, morph_weights=None):
     """The arrays of an S.SkinArgs in the layout the library reads: base S.VertexFloat [count]; joints uint16 [count, 4], weights float32
     [count, 4] and joint_matrices float32 [jointCount, 3, 4] (or all three None); deltas S.SkinMorphDelta [targetCount, count] and
@@ -566,6 +653,30 @@ class PathTracerContext:
         instances = np.ascontiguousarray(instances)
         assert instances.dtype.itemsize == 160, "PerInstanceData records expected"
         self._check(lib.hrpt_refit_instances(self._h, instances.ctypes.data, int(first), len(instances)))
+
+    def animate(self, animation, flags=0):
+        """hrpt_animate: evaluates `animation` (an Animation) at its current times on the device and commits the instances like
+        update_instances (S.ANIMATE_REFIT: like refit_instances); S.ANIMATE_NO_COMMIT: node worlds, palette and weights only, asynchronous."""
+        self._check(lib.hrpt_animate(self._h, animation._h, int(flags)))
+
+    def animation_device(self, animation):
+        """hrpt_get_animation_device: device addresses (palette, weights, node worlds) of the last animate of `animation`; None for an
+        empty array."""
+        p = [C.c_void_p() for _ in range(3)]
+        self._check(lib.hrpt_get_animation_device(self._h, animation._h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def read_animation(self, animation):
+        """hrpt_read_animation: (palette [joints, 3, 4], weights, node worlds [nodes, 4, 4]) of the last animate (synchronises)."""
+        palette = np.zeros((animation.joint_count, 3, 4), np.float32)
+        weights = np.zeros(animation.morph_weight_count, np.float32)
+        worlds = np.zeros((animation.node_count, 4, 4), np.float32)
+        self._check(lib.hrpt_read_animation(self._h, animation._h, palette.ctypes.data, weights.ctypes.data, worlds.ctypes.data))
+        return palette, weights, worlds
+
+    def release_animation(self, animation):
+        """hrpt_animation_release: drops the context's device copy of `animation`; the next animate uploads it again."""
+        self._check(lib.hrpt_animation_release(self._h, animation._h))
 
     def update_lights(self, lights):
         """Replaces the light buffer (GPULight records; the count may change)."""

@@ -197,6 +197,26 @@ class SkinArgs(C.Structure):
                [(n, C.c_uint32) for n in ("count", "jointCount", "targetCount", "reserved")]
 
 
+# ---- keyframe animation (hrpt_animation_create, hrpt_animate_host, hrpt_animate; csrc/pt_anim.h has the definition) ----
+ANIM_PATH_TRANSLATION, ANIM_PATH_ROTATION, ANIM_PATH_SCALE, ANIM_PATH_WEIGHTS = 0, 1, 2, 3
+ANIM_STEP, ANIM_LINEAR, ANIM_CUBICSPLINE, ANIM_CATMULLROM, ANIM_SLERP = 0, 1, 2, 3, 4
+ANIMATE_REFIT, ANIMATE_NO_COMMIT = 1, 2
+ANIM_LDS_MAX_ANIMATIONS = 256      # HRPT_ANIM_LDS_MAX_ANIMATIONS: up to this many animation times the sampling kernel stages in LDS
+AnimSampler = np.dtype([("interpolation", u32), ("firstKey", u32), ("keyCount", u32), ("animation", u32)])
+AnimChannel = np.dtype([("path", u32), ("sampler", u32), ("firstTarget", u32), ("targetCount", u32)])
+AnimNode = np.dtype([("parent", np.int32), ("translation", f32, 3), ("rotation", f32, 4), ("scale", f32, 3), ("baseWorld", f32, (4, 4)),
+                     ("firstInstance", u32), ("instanceCount", u32)])
+AnimJoint = np.dtype([("node", u32), ("inverseBind", f32, (4, 4))])
+assert AnimSampler.itemsize == 16 and AnimChannel.itemsize == 16 and AnimNode.itemsize == 116 and AnimJoint.itemsize == 68
+
+
+class AnimationDesc(C.Structure):
+    """HrptAnimationDesc: host addresses of the flat tables and their counts."""
+    _fields_ = [(n, C.c_void_p) for n in ("samplers", "channels", "nodes", "joints", "keyTimes", "keyValues", "targets", "nodeInstances")] + \
+               [(n, C.c_uint32) for n in ("samplerCount", "channelCount", "nodeCount", "jointCount", "keyCount", "targetCount", "nodeInstanceCount",
+                                          "animationCount", "morphWeightCount", "reserved")]
+
+
 class Stats(C.Structure):
     _fields_ = [("closestRays", C.c_uint64), ("shadowRays", C.c_uint64), ("paths", C.c_uint64),
                 ("lastRenderMs", C.c_float), ("traceKernelMs", C.c_float), ("traceKernelLaunches", C.c_uint32),

@@ -464,6 +464,87 @@ int  hrpt_skin_vertices_host(const HrptSkinArgs* args, HrptVertexFloat* out, int
 int  hrpt_skin_vertices_device(HrptContext* ctx, const HrptSkinArgs* args, HrptVertexFloat* deviceOut, uint32_t* deviceStatus2, void* stream);
 int  hrpt_update_vertices_skinned(HrptContext* ctx, const HrptSkinArgs* args, uint32_t firstVertex, uint32_t flags, void* stream);
 
+/* ---- keyframe animation and node hierarchies (csrc/pt_anim.h has the definition, DESIGN.md section 23 the prose) -----------------
+ * The producer at the head of a moving frame: animation times -> node poses -> instance matrices + joint palette + morph weights, what
+ * Scene::Update and EvaluateAnimSampler do on the host in the reference (src/Scene.cpp:345-570; composed set and order: :220-273).
+ * float32, one rounding per operation, bit-identical on host threads (hrpt_animate_host), in the gfx950 kernels (hrpt_animate) and in
+ * tests/anim_reference.py. Slerp uses this project's own sine and arctangent: parity with DirectXMath's approximations is unpinned.
+ *   clock     per animation: current += dt; duration > 0: current = fmodf(current, duration); duration = the largest last key time of
+ *             the animation's samplers. Host side (hrpt_animation_advance / _set_times); the evaluation gets one time per animation.
+ *   sampler   keys [firstKey, firstKey + keyCount): one time and one float4 each. No keys: its channels do nothing. One key: that value.
+ *             t <= first: the first value, t >= last: the last; else k0 = the last i <= n - 2 with t >= time[i], k1 = k0 + 1,
+ *             d = time[k1] - time[k0], alpha = d > 0 ? (t - time[k0]) / d : 0, and
+ *               STEP v0 | LINEAR, CUBICSPLINE v0 + alpha (v1 - v0) | CATMULLROM over v[k0-1], v0, v1, v[k1+1] with clamped neighbours |
+ *               SLERP of the normalised keys, the second negated when their dot product is negative, linear above a dot of 0.9995
+ *   channel   path TRANSLATION / SCALE: xyz of the value; ROTATION: the value normalised; WEIGHTS: .x, into the morph-weight slots its
+ *             targets name (the reference drops weight channels: defined here). targets[firstTarget .. + targetCount) are node indices,
+ *             or weight slots for WEIGHTS. Channels apply ordered by (animation of their sampler, channel index); the last writer of a
+ *             (node, path) or of a slot wins. A path no channel writes keeps the node's base value, a slot nothing writes is 0.
+ *   pose      local = scale . rotation . translation (row vectors, translation in row 3); world = local . world(parent), a full 4 x 4
+ *             product, each entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3; a root's world is its local. Composed: every node a channel with keys
+ *             targets, and all their descendants. Every other node keeps baseWorld.
+ *   instances m_PrevWorld = m_World for EVERY instance, then m_World = world(node) for the instances listed under composed nodes
+ *             (nodeInstances[firstInstance .. + instanceCount)); every other field stays.
+ *   joints    palette[j] = the top three rows of transpose(inverseBind[j] . world(node[j])): the row-major 3 x 4 with p' = M [p; 1] of
+ *             HrptSkinArgs::jointMatrices. The instance of a skinned mesh is expected to carry an identity world.
+ * hrpt_animation_create validates and copies everything (context-free): an index out of range (parent, node, sampler, animation, weight
+ * slot, a target or instance range beyond its array), a parent cycle, an instance listed twice, key times that decrease or are not finite,
+ * keys beyond the arrays, an unknown path or interpolation, a NULL array with a non-zero count, a non-zero reserved word:
+ * HRPT_ERR_INVALID_ARGUMENT and *out = NULL. All times start at 0.
+ * hrpt_animate_host: the evaluation on host threads (no GPU; nthreads as in hrpt_skin_vertices_host). Every output may be NULL.
+ * instancesInOut holds instanceCount records; with prevInstances != NULL these are first copied from there. instanceCount not above every
+ * listed instance index (with instancesInOut != NULL): HRPT_ERR_INVALID_ARGUMENT, nothing written. paletteOut: jointCount x 12 floats,
+ * weightsOut: morphWeightCount floats, nodeWorldsOut: nodeCount x 16 floats.
+ * hrpt_animate: the same on the device, on the context's stream. The tables are uploaded at the first call for this (context, animation)
+ * and kept until hrpt_animation_release / hrpt_destroy (destroy the animation only after that). Without HRPT_ANIMATE_NO_COMMIT it then
+ * commits like hrpt_update_instances (hrpt_refit_instances with HRPT_ANIMATE_REFIT): the closed range of the listed instances is evaluated
+ * in a device copy of those records, read back into the library's host copy, the m_PrevWorld roll of the instances outside it is done on
+ * the host, and the acceleration structure is rebuilt; an animation that lists no instance under a composed node commits and builds
+ * nothing. No scene, or an instance index beyond the scene's: what hrpt_update_instances answers, nothing changed. With
+ * HRPT_ANIMATE_NO_COMMIT the call is asynchronous, needs no scene, evaluates node worlds, palette and weights only and leaves the scene's
+ * instances alone (a scene that animates joints and no instances: follow with hrpt_update_vertices_skinned on the same stream).
+ * hrpt_get_animation_device: device pointers of the palette (jointCount x 12 floats), the weights and the node worlds of the last
+ * hrpt_animate, each at least 256-byte aligned -- palette and weights go straight into HrptSkinArgs::jointMatrices / ::morphWeights; valid
+ * until the animation is released from the context; an array of zero length gives NULL. hrpt_read_animation copies them to the host
+ * (synchronises; any pointer may be NULL). Before the first hrpt_animate of the pair both answer HRPT_ERR_INVALID_ARGUMENT.
+ * Not here: the reference's emissive-intensity channels (hrpt_update_materials takes their result), light nodes, bounding spheres. */
+enum { HRPT_ANIM_PATH_TRANSLATION = 0, HRPT_ANIM_PATH_ROTATION = 1, HRPT_ANIM_PATH_SCALE = 2, HRPT_ANIM_PATH_WEIGHTS = 3 };
+enum { HRPT_ANIM_STEP = 0, HRPT_ANIM_LINEAR = 1, HRPT_ANIM_CUBICSPLINE = 2, HRPT_ANIM_CATMULLROM = 3, HRPT_ANIM_SLERP = 4 };
+enum { HRPT_ANIMATE_REFIT = 1, HRPT_ANIMATE_NO_COMMIT = 2 };
+#define HRPT_ANIM_LDS_MAX_ANIMATIONS 256       /* up to this many animation times are staged in LDS by the sampling kernel */
+typedef struct HrptAnimSampler { uint32_t interpolation, firstKey, keyCount, animation; } HrptAnimSampler;             /* 16 B */
+typedef struct HrptAnimChannel { uint32_t path, sampler, firstTarget, targetCount; } HrptAnimChannel;                  /* 16 B */
+typedef struct HrptAnimNode {                  /* 116 B */
+    int32_t  parent;                           /* -1: a root */
+    float    translation[3], rotation[4] /* x, y, z, w */, scale[3];
+    float    baseWorld[16];                    /* row-major, row vectors: what the node's instances were uploaded with */
+    uint32_t firstInstance, instanceCount;     /* into nodeInstances */
+} HrptAnimNode;
+typedef struct HrptAnimJoint { uint32_t node; float inverseBind[16]; } HrptAnimJoint;                                   /* 68 B */
+typedef struct HrptAnimationDesc {
+    const HrptAnimSampler* samplers;
+    const HrptAnimChannel* channels;
+    const HrptAnimNode*    nodes;
+    const HrptAnimJoint*   joints;
+    const float*           keyTimes;           /* keyCount */
+    const float*           keyValues;          /* keyCount x 4 */
+    const uint32_t*        targets;            /* targetCount */
+    const uint32_t*        nodeInstances;      /* nodeInstanceCount scene instance indices */
+    uint32_t samplerCount, channelCount, nodeCount, jointCount, keyCount, targetCount, nodeInstanceCount, animationCount, morphWeightCount, reserved /* 0 */;
+} HrptAnimationDesc;                           /* 104 B */
+typedef struct HrptAnimation HrptAnimation;
+int  hrpt_animation_create(const HrptAnimationDesc* desc, HrptAnimation** out);
+void hrpt_animation_destroy(HrptAnimation* anim);
+int  hrpt_animation_advance(HrptAnimation* anim, float dt);
+int  hrpt_animation_set_times(HrptAnimation* anim, const float* times, uint32_t count);       /* count == animationCount; taken as given, not wrapped */
+int  hrpt_animation_get_times(const HrptAnimation* anim, float* times, float* durations, uint32_t count);   /* either array may be NULL */
+int  hrpt_animate_host(const HrptAnimation* anim, const HrptPerInstanceData* prevInstances, HrptPerInstanceData* instancesInOut, uint32_t instanceCount,
+                       float* paletteOut, float* weightsOut, float* nodeWorldsOut, int nthreads);
+int  hrpt_animate(HrptContext* ctx, const HrptAnimation* anim, uint32_t flags);
+int  hrpt_get_animation_device(HrptContext* ctx, const HrptAnimation* anim, void** palette, void** weights, void** nodeWorlds);
+int  hrpt_read_animation(HrptContext* ctx, const HrptAnimation* anim, float* palette, float* weights, float* nodeWorlds);
+int  hrpt_animation_release(HrptContext* ctx, const HrptAnimation* anim);
+
 /* ---- in-process multi-GPU: one context per GPU inside ONE process ------------------------------------
  * Rank i of n has rendered the row band [i*H/n, (i+1)*H/n) of its accumulation image (HrptFrameParams::tile*; H must be a
  * multiple of n, every context the same size). hrpt_allgather sends every band to every other context with

@@ -1,0 +1,322 @@
+"""The animation stage without a GPU (hrpt_animation_create, hrpt_animate_host): csrc/pt_anim.h on host threads
+against its NumPy statement (tests/anim_reference.py, written from the reference's Scene::Update), as bytes, on every case of
+tests/anim_cases.py; the statement against a float64 formulation that shares nothing with it; the clock against numpy.fmod; every
+validation error of hrpt_animation_create; the ABI of the new calls; and the sanitizer build of the host side (`make anim_asan`, a
+stand-alone program). Slerp uses the project's own sine and arctangent: parity with DirectXMath's approximations is unpinned."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from hobbyrenderer_amd import native, structs as S
+import anim_cases as K
+import anim_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "hobbyrenderer_amd", "csrc")
+CASES = list(K.cases())
+# The largest relative deviation of the statement from the float64 formulation over the case list, measured when the stage was defined
+# (per node world and per palette matrix: max |difference| / max |float64 entry|); the seeds are fixed, the cap of twice the value covers
+# the float64 side's libm.
+MEASURED_WORLD, MEASURED_PALETTE = 5.25e-6, 5.48e-6
+
+
+@pytest.fixture(scope="module")
+def statements():
+    """name -> [(times, instances, palette, weights, worlds)] by the NumPy statement, once for all tests."""
+    out = {}
+    for name, case in K.cases().items():
+        inst = K.scene_instances(case)
+        out[name] = [(t,) + R.animate(case["tables"], np.asarray(t, np.float32), inst) for t in case["times"]]
+    return out
+
+
+def _same(got, want):
+    return np.ascontiguousarray(got).tobytes() == np.ascontiguousarray(want).tobytes()
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_host_executor_equals_the_numpy_statement(statements, name):
+    case = K.cases()[name]
+    anim = native.Animation(**case["tables"])
+    inst = K.scene_instances(case)
+    assert _same(anim.durations, R.durations(case["tables"]))
+    for times, want_inst, want_palette, want_weights, want_worlds in statements[name]:
+        anim.set_times(times)
+        for nthreads in (1, 16):
+            got_inst, palette, weights, worlds = anim.evaluate_host(inst, nthreads=nthreads)
+            bad = np.nonzero((worlds != want_worlds).any((1, 2)))[0]
+            assert _same(worlds, want_worlds), (times, nthreads, bad[:8], worlds[bad[:1]], want_worlds[bad[:1]])
+            assert _same(got_inst["m_World"], want_inst["m_World"]) and _same(got_inst["m_PrevWorld"], want_inst["m_PrevWorld"]), (times, nthreads)
+            assert _same(got_inst, want_inst) and _same(palette, want_palette) and _same(weights, want_weights), (times, nthreads)
+        assert _same(got_inst["m_PrevWorld"], inst["m_World"])
+    none, palette, _, _ = anim.evaluate_host(None)                        # every output may be NULL
+    assert none is None and _same(palette, statements[name][-1][2])
+    assert native.lib.hrpt_animate_host(anim._h, None, None, 0, None, None, None, 1) == 0
+    anim.close()
+
+
+def test_the_cases_reach_what_they_name(statements):
+    """The case list holds what the definition's edges need: guards against a generator that silently stops producing them."""
+    tb, names = K.cases()["hierarchy"]["tables"], K.cases()["hierarchy"]["names"]
+    (_, inst, _, _, worlds), (_, _, _, _, worlds2) = statements["hierarchy"]
+    base = tb["nodes"]["baseWorld"]
+    depth = lambda n: 0 if tb["nodes"]["parent"][n] < 0 else 1 + depth(tb["nodes"]["parent"][n])
+    assert depth(names["chain"][-1]) == 8 and len(names["children"]) == 300
+    for n in names["untouched"] + [names["static_parent"], names["static_child"]]:
+        assert _same(worlds[n], base[n])
+    for n in names["chain"] + [names["parent"], names["grandchild"], names["animated_child"], names["twice"]] + names["children"] + names["several"]:
+        assert not _same(worlds[n], base[n]) and not _same(worlds[n], worlds2[n]), n
+    assert np.linalg.det(worlds[names["chain"][5]][:3, :3].astype(np.float64)) * np.linalg.det(worlds[names["chain"][3]][:3, :3].astype(np.float64)) < 0   # the mirrored link
+    assert sorted(set(tb["nodes"]["instanceCount"])) == [0, 1, 2, 3]
+    sl = K.cases()["slerp"]["tables"]
+    dots = []
+    for s in sl["samplers"]:
+        q0, q1 = (R._unit4(v) for v in sl["key_values"][s["firstKey"]:s["firstKey"] + 2])
+        dots.append(float(q0.astype(np.float64) @ q1))
+    assert min(dots) < -0.9999 and any(0.9995 < abs(d) < 0.9996 for d in dots) and any(0.9994 < abs(d) <= 0.9995 for d in dots) and any(d < -0.3 for d in dots)
+    assert len(K.cases()["skin300"]["tables"]["joints"]) == 300 > S.SKIN_LDS_MAX_JOINTS
+    assert K.cases()["skin5"]["tables"]["morph_weight_count"] == 4 and statements["skin5"][0][3][3] == 0 and (statements["skin5"][0][3][:3] != 0).all()
+
+
+def test_statement_against_float64(statements):
+    """Nothing in the project or the reference fixes this number in advance: it is measured here over the whole case list (DESIGN.md
+    section 23 records it) and capped at twice the measured value."""
+    world, palette = 0.0, 0.0
+    for name, case in K.cases().items():
+        for times, _, got_palette, _, got_worlds in statements[name]:
+            p64, w64 = R.animate_float64(case["tables"], np.asarray(times, np.float32))
+            for got, want in ((got_worlds, w64), (got_palette, p64)):
+                if len(want) == 0:
+                    continue
+                err = float((np.abs(got - want).max((1, 2)) / np.abs(want).max((1, 2))).max())
+                if got is got_worlds:
+                    world = max(world, err)
+                else:
+                    palette = max(palette, err)
+    print(f"largest relative deviation from float64: node worlds {world:.3e}, palette {palette:.3e}")
+    assert world <= 2 * MEASURED_WORLD and palette <= 2 * MEASURED_PALETTE
+
+
+def test_clock_equals_numpy_fmod():
+    case = K.cases()["clock"]
+    anim = native.Animation(**case["tables"])
+    durations = np.asarray(case["durations"], np.float32)
+    assert _same(anim.durations, durations) and not anim.times.any()
+    want, unwrapped = np.zeros(3, np.float32), np.float32(0)
+    for dt in case["steps"]:                                             # one of them larger than both durations
+        anim.advance(dt)
+        t = (want + np.float32(dt)).astype(np.float32)
+        assert _same(R.advance(want, durations, dt), np.where(durations > 0, np.fmod(t, np.where(durations > 0, durations, np.float32(1))), t).astype(np.float32))
+        want, unwrapped = R.advance(want, durations, dt), np.float32(unwrapped + np.float32(dt))
+        assert _same(anim.times, want), dt
+    assert want[2] == unwrapped > 11 and (want[:2] < durations[:2]).all()                 # duration 0: never wrapped
+    anim.set_times([9.0, -1.0, 0.5])                                                      # taken as given
+    assert anim.times.tolist() == [9.0, -1.0, 0.5]
+    assert native.lib.hrpt_animation_set_times(anim._h, anim.times.ctypes.data, 2) == -1
+    anim.close()
+
+
+def _create(tables, **changes):
+    t = dict(tables)
+    t.update(changes)
+    desc, keep = native.animation_desc(**t)
+    h = C.c_void_p(1)
+    rc = native.lib.hrpt_animation_create(C.byref(desc), C.byref(h))
+    if rc == 0:
+        native.lib.hrpt_animation_destroy(h)
+    return rc, h.value
+
+
+def _changed(array, index, field, value):
+    a = array.copy()
+    if field is None:
+        a[index] = value
+    else:
+        a[field][index] = value
+    return a
+
+
+def test_validation_errors():
+    tb = K.cases()["hierarchy_small"]["tables"]
+    sk = K.cases()["skin5"]["tables"]
+    assert _create(tb)[0] == 0 and _create(sk)[0] == 0
+    n, s, c = tb["nodes"], tb["samplers"], tb["channels"]
+    weights_channel = int(np.nonzero(sk["channels"]["path"] == S.ANIM_PATH_WEIGHTS)[0][0])
+    with_keys = int(np.nonzero(s["keyCount"] >= 3)[0][0])
+    child = int(np.nonzero(n["parent"] >= 0)[0][0])
+    cycle = _changed(n, int(n["parent"][child]), "parent", child)
+    with_instance = int(np.nonzero(n["instanceCount"] > 0)[0][0])
+    decreasing = _changed(tb["key_times"], int(s["firstKey"][with_keys]) + 1, None, -1.0)
+    bad = {
+        "parent out of range": dict(nodes=_changed(n, 3, "parent", len(n))),
+        "parent below -1": dict(nodes=_changed(n, 3, "parent", -2)),
+        "parent cycle": dict(nodes=cycle),
+        "self parent": dict(nodes=_changed(n, 0, "parent", 0)),
+        "node target out of range": dict(targets=_changed(tb["targets"], 0, None, len(n))),
+        "sampler out of range": dict(channels=_changed(c, 0, "sampler", len(s))),
+        "animation out of range": dict(samplers=_changed(s, 0, "animation", tb["animation_count"])),
+        "instance range beyond nodeInstances": dict(nodes=_changed(n, with_instance, "instanceCount", len(tb["node_instances"]) + 1)),
+        "instance listed twice": dict(node_instances=_changed(tb["node_instances"], 0, None, tb["node_instances"][1])),
+        "target range beyond targets": dict(channels=_changed(c, 0, "targetCount", len(tb["targets"]) + 1)),
+        "decreasing key times": dict(key_times=decreasing),
+        "nan key time": dict(key_times=_changed(tb["key_times"], int(s["firstKey"][with_keys]), None, np.nan)),
+        "infinite key time": dict(key_times=_changed(tb["key_times"], int(s["firstKey"][with_keys]) + 2, None, np.inf)),
+        "keyCount beyond the arrays": dict(samplers=_changed(s, with_keys, "keyCount", len(tb["key_times"]) + 1)),
+        "firstKey wraps": dict(samplers=_changed(_changed(s, with_keys, "firstKey", 0xFFFFFFFF), with_keys, "keyCount", 2)),
+        "unknown path": dict(channels=_changed(c, 0, "path", 4)),
+        "unknown interpolation": dict(samplers=_changed(s, 0, "interpolation", 5)),
+        "reserved": dict(reserved=1),
+    }
+    for what, change in bad.items():
+        assert _create(tb, **change) == (-1, None), what                  # *out is NULL
+        assert native.lib.hrpt_last_error(None)
+    assert _create(sk, morph_weight_count=2) == (-1, None)               # a weight slot out of range
+    assert _create(sk, channels=_changed(sk["channels"], weights_channel, "path", S.ANIM_PATH_TRANSLATION))[0] == 0    # slots 0, 2 are nodes too
+    assert _create(sk, joints=_changed(sk["joints"], 0, "node", len(sk["nodes"]))) == (-1, None)
+    desc, keep = native.animation_desc(**tb)
+    desc.nodes = None                                                    # a NULL array with a non-zero count
+    h = C.c_void_p(1)
+    assert native.lib.hrpt_animation_create(C.byref(desc), C.byref(h)) == -1 and h.value is None
+    assert native.lib.hrpt_animation_create(None, C.byref(h)) == -1 and native.lib.hrpt_animation_create(C.byref(desc), None) == -1
+    with pytest.raises(native.HrptError) as e:
+        native.Animation(**dict(tb, nodes=cycle))
+    assert e.value.code == -1 and "cycle" in str(e.value)
+
+
+def test_argument_errors_leave_the_outputs_untouched():
+    case = K.cases()["hierarchy_small"]
+    anim = native.Animation(**case["tables"])
+    inst = K.scene_instances(case)
+    short = inst[:int(case["tables"]["node_instances"].max())].copy()    # one record too few
+    before = short.tobytes()
+    palette = np.full(4, 7.5, np.float32)
+    assert native.lib.hrpt_animate_host(anim._h, None, short.ctypes.data, len(short), palette.ctypes.data, palette.ctypes.data, palette.ctypes.data, 1) == -1
+    assert short.tobytes() == before and (palette == 7.5).all()
+    assert native.lib.hrpt_animate_host(None, None, None, 0, None, None, None, 1) == -1
+    assert native.lib.hrpt_animation_advance(None, 0.5) == -1 and native.lib.hrpt_animation_get_times(None, None, None, 0) == -1
+    out = np.zeros(len(inst), S.PerInstanceData)                          # prevInstances: copied first, then evaluated
+    assert native.lib.hrpt_animate_host(anim._h, inst.ctypes.data, out.ctypes.data, len(out), None, None, None, 3) == 0
+    assert _same(out, anim.evaluate_host(inst)[0])
+    for name in ("hrpt_animate", "hrpt_get_animation_device", "hrpt_read_animation", "hrpt_animation_release"):      # no context: an error, not a crash
+        fn = getattr(native.lib, name)
+        assert fn(*[0 if t is C.c_uint32 else None for t in fn.argtypes]) == -1, name
+    anim.close()
+
+
+def test_abi(tmp_path):
+    structs = {"HrptAnimSampler": (S.AnimSampler, ["interpolation", "firstKey", "keyCount", "animation"]),
+               "HrptAnimChannel": (S.AnimChannel, ["path", "sampler", "firstTarget", "targetCount"]),
+               "HrptAnimNode": (S.AnimNode, ["parent", "translation", "rotation", "scale", "baseWorld", "firstInstance", "instanceCount"]),
+               "HrptAnimJoint": (S.AnimJoint, ["node", "inverseBind"]),
+               "HrptAnimationDesc": (S.AnimationDesc, [f for f, _ in S.AnimationDesc._fields_])}
+    lines = "".join(f'printf("%zu\\n", sizeof({n}));\n' + "".join(f'printf("%zu\\n", offsetof({n}, {f}));\n' for f in fields) for n, (_, fields) in structs.items())
+    constants = ["HRPT_ANIM_PATH_TRANSLATION", "HRPT_ANIM_PATH_ROTATION", "HRPT_ANIM_PATH_SCALE", "HRPT_ANIM_PATH_WEIGHTS", "HRPT_ANIM_STEP", "HRPT_ANIM_LINEAR",
+                 "HRPT_ANIM_CUBICSPLINE", "HRPT_ANIM_CATMULLROM", "HRPT_ANIM_SLERP", "HRPT_ANIMATE_REFIT", "HRPT_ANIMATE_NO_COMMIT", "HRPT_ANIM_LDS_MAX_ANIMATIONS",
+                 "HRPT_ABI_VERSION"]
+    src = tmp_path / "size.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hobbyrt_pt.h"\nint main(void){\n' + lines +
+                   "".join(f'printf("%d\\n", (int){k});\n' for k in constants) + "return 0;}\n")
+    exe = tmp_path / "size"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    out = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
+    want = []
+    for _, (t, fields) in structs.items():
+        if isinstance(t, np.dtype):
+            want += [t.itemsize] + [t.fields[f][1] for f in fields]
+        else:
+            want += [C.sizeof(t)] + [getattr(t, f).offset for f in fields]
+    want += [S.ANIM_PATH_TRANSLATION, S.ANIM_PATH_ROTATION, S.ANIM_PATH_SCALE, S.ANIM_PATH_WEIGHTS, S.ANIM_STEP, S.ANIM_LINEAR, S.ANIM_CUBICSPLINE,
+             S.ANIM_CATMULLROM, S.ANIM_SLERP, S.ANIMATE_REFIT, S.ANIMATE_NO_COMMIT, S.ANIM_LDS_MAX_ANIMATIONS, S.ABI_VERSION]
+    assert out == want and S.ABI_VERSION == 3 and C.sizeof(S.AnimationDesc) == 104
+    for name in ("hrpt_animation_create", "hrpt_animation_destroy", "hrpt_animation_advance", "hrpt_animation_set_times", "hrpt_animation_get_times",
+                 "hrpt_animate_host", "hrpt_animate", "hrpt_get_animation_device", "hrpt_read_animation", "hrpt_animation_release"):
+        assert name in native.EXPORTS and getattr(native.lib, name)
+
+
+@pytest.mark.parametrize("seed", [5, 6])
+def test_host_side_is_clean_under_the_sanitizers(seed):
+    """pt_anim.h + the table validation + the host executor + a driver with its own main, built with AddressSanitizer and UBSan (`make
+    anim_asan`): random valid tables over exactly sized arrays at 1, 3 and 16 threads, hostile times and key values, and every kind of
+    invalid table, which creation must refuse without reading past an array. Nothing is loaded into Python."""
+    subprocess.check_call(["make", "-C", CSRC, "anim_asan"], stdout=subprocess.DEVNULL)
+    env = dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1", ASAN_OPTIONS="detect_leaks=1")
+    r = subprocess.run([os.path.join(CSRC, "build", "anim_asan"), str(seed)], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "no report" in r.stdout
+
+
+def test_tables_from_gltf(tmp_path, luts):
+    """A synthetic asset: a rotating parent (matrix node) with a child mesh, a two-joint skin under an armature, a CUBICSPLINE translation
+    sampler, a STEP scale sampler, a LINEAR rotation sampler and a weights sampler with two targets. The tables against hand-written
+    expectations (right-handed glTF -> left-handed scene), the rest pose against the node worlds the C++ loader put into the instances."""
+    import json
+    from gltf_helpers import Asset, grid
+    from hobbyrenderer_amd import animation, scene_io
+
+    a = Asset()
+    pos, nrm, uv, idx = grid(2, 2)
+    a.add_primitive(0, pos, idx, nrm, uv)
+    a.j["materials"] = [{}]
+    c, s = np.cos(0.5), np.sin(0.5)
+    spin = [c, 0, -s, 0, 0, 1, 0, 0, s, 0, c, 0, 1.0, 2.0, 3.0, 1]      # column-major: a turn about y, then a translation (1, 2, 3)
+    a.j["nodes"] = [{"matrix": spin, "children": [1]}, {"mesh": 0, "translation": [0.5, 0.25, -2.0], "scale": [1, 2, 1]},
+                    {"children": [3], "translation": [0, 1, 0]}, {"children": [4], "rotation": [0.0, 0.0, float(np.sin(0.2)), float(np.cos(0.2))], "translation": [0, 0, 1.5]},
+                    {"translation": [0.1, 0.2, 0.3]}, {"mesh": 0, "skin": 0}]
+    a.j["scenes"][0]["nodes"] = [0, 2, 5]
+    f4 = lambda x: np.asarray(x, "<f4")
+    times3, times2 = a.add_accessor(f4([0.0, 1.0, 2.5]), 5126, "SCALAR"), a.add_accessor(f4([0.5, 1.5]), 5126, "SCALAR")
+    spline = np.arange(27, dtype=np.float32).reshape(3, 3, 3)            # [key, (in, value, out), xyz]
+    rot = f4([[0, 0, 0, 1], [0.1, 0.2, 0.3, 0.9], [0, 1, 0, 0]])
+    ibm = np.stack([np.eye(4), np.eye(4)]).astype(np.float32)
+    ibm[0, 3, :3], ibm[1, 3, :3] = (1, 2, 3), (-1, 0, 0.5)               # column-major storage: row 3 of the stored array is the translation
+    ibm[1, 0, 2], ibm[1, 2, 0] = 0.25, -0.25
+    acc = dict(spline=a.add_accessor(spline.reshape(9, 3), 5126, "VEC3"), step=a.add_accessor(f4([[1, 1, 1], [2, 3, 4]]), 5126, "VEC3"),
+               rot=a.add_accessor(rot, 5126, "VEC4"), weights=a.add_accessor(f4([0.0, 1.0, 0.5, 0.25]), 5126, "SCALAR"),
+               ibm=a.add_accessor(ibm.reshape(2, 16), 5126, "MAT4"))
+    a.j["skins"] = [{"joints": [3, 4], "inverseBindMatrices": acc["ibm"]}]
+    a.j["animations"] = [
+        {"samplers": [{"input": times3, "output": acc["spline"], "interpolation": "CUBICSPLINE"}, {"input": times3, "output": acc["rot"]}],
+         "channels": [{"sampler": 0, "target": {"node": 1, "path": "translation"}}, {"sampler": 1, "target": {"node": 0, "path": "rotation"}}]},
+        {"samplers": [{"input": times2, "output": acc["step"], "interpolation": "STEP"}, {"input": times2, "output": acc["weights"]}],
+         "channels": [{"sampler": 0, "target": {"node": 3, "path": "scale"}}, {"sampler": 1, "target": {"node": 5, "path": "weights"}},
+                      {"sampler": 1, "target": {"path": "weights"}}]}]
+    path = str(tmp_path / "animated.gltf")
+    a.write(path, "glb")
+    a.write(path)
+    tables, maps = animation.tables_from_gltf(json.loads(json.dumps(a.j)), [bytes(a.bin)])
+
+    assert tables["animation_count"] == 2 and tables["morph_weight_count"] == 2 and maps == {"weight_slots": {5: (0, 2)}, "skin_joints": [(0, 2)]}
+    assert tables["samplers"].tolist() == [(S.ANIM_CUBICSPLINE, 0, 3, 0), (S.ANIM_LINEAR, 3, 3, 0), (S.ANIM_STEP, 6, 2, 1), (S.ANIM_LINEAR, 8, 2, 1), (S.ANIM_LINEAR, 10, 2, 1)]
+    assert tables["channels"].tolist() == [(S.ANIM_PATH_TRANSLATION, 0, 0, 1), (S.ANIM_PATH_ROTATION, 1, 1, 1), (S.ANIM_PATH_SCALE, 2, 2, 1),
+                                           (S.ANIM_PATH_WEIGHTS, 3, 3, 1), (S.ANIM_PATH_WEIGHTS, 4, 4, 1)]
+    assert tables["targets"].tolist() == [1, 0, 3, 0, 1]
+    assert tables["key_times"].tolist() == [0, 1, 2.5, 0, 1, 2.5, 0.5, 1.5, 0.5, 1.5, 0.5, 1.5]
+    want_values = [[3, 4, -5, 0], [12, 13, -14, 0], [21, 22, -23, 0],                    # the value element of each triplet, z negated
+                   [0, 0, 0, 1], [-0.1, -0.2, 0.3, 0.9], [0, -1, 0, 0],                   # x and y negated
+                   [1, 1, 1, 0], [2, 3, 4, 0], [0, 0, 0, 0], [0.5, 0, 0, 0], [1, 0, 0, 0], [0.25, 0, 0, 0]]
+    assert np.array_equal(tables["key_values"], np.array(want_values, np.float32))          # (-0 where a zero was negated)
+    n = tables["nodes"]
+    assert n["parent"].tolist() == [-1, 0, -1, 2, 3, -1]
+    assert n["translation"][1].tolist() == [0.5, 0.25, 2.0] and n["scale"][1].tolist() == [1, 2, 1] and n["translation"][0].tolist() == [1, 2, -3]
+    assert np.allclose(n["rotation"][0], [0, -np.sin(0.25), 0, np.cos(0.25)], atol=1e-6)          # a turn by +0.5 about y in glTF: -0.5 in the scene
+    assert np.allclose(n["rotation"][3], [0, 0, np.sin(0.2), np.cos(0.2)], atol=1e-7) and n["translation"][3].tolist() == [0, 0, -1.5]
+    assert n["instanceCount"].tolist() == [0, 1, 0, 0, 0, 1] and tables["node_instances"].tolist() == [0, 1]
+    j = tables["joints"]
+    assert j["node"].tolist() == [3, 4] and j["inverseBind"][0][3].tolist() == [1, 2, -3, 1] and j["inverseBind"][1][3].tolist() == [-1, 0, -0.5, 1]
+    assert j["inverseBind"][1][0, 2] == -0.25 and j["inverseBind"][1][2, 0] == 0.25 and j["inverseBind"][0][:3, :3].tolist() == np.eye(3).tolist()
+
+    loaded = scene_io.load_gltf(path, luts)
+    inst = loaded.arrays.instances
+    assert len(inst) == 2
+    for node in (1, 5):                                                   # the rest pose is the loader's, to the bit
+        assert _same(n["baseWorld"][node], inst["m_World"][tables["node_instances"][n["firstInstance"][node]]]), node
+    anim = native.Animation(**tables)                                     # ... and the tables are valid
+    assert anim.durations.tolist() == [2.5, 1.5]
+    anim.set_times([1.0, 2.0])
+    _, palette, weights, worlds = anim.evaluate_host()
+    assert weights.tolist() == [0.5, 0.25] and _same(worlds[2], n["baseWorld"][2]) and not _same(worlds[1], n["baseWorld"][1])
+    assert worlds[3][:3, :3].astype(np.float64).round(5).tolist() != n["baseWorld"][3][:3, :3].astype(np.float64).round(5).tolist()      # the STEP scale
+    anim.close()
