@@ -1,0 +1,204 @@
+// pt_capi_internal.h -- what the pt_capi*.cpp files share: the context, the status / error plumbing, the exception guard and the owner of a
+// device allocation. Host code of the C boundary only: no .hip file and no header a kernel includes may include it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <stdexcept>
+#include <string>
+#include <system_error>
+#include <thread>
+#include <vector>
+
+#include "../../include/hobbyrt_pt.h"
+#include "bvh_build.h"
+#include "bvh_build_gpu.h"
+#include "pt_anim.h"
+#include "pt_device.h"
+#include "pt_kernels.h"
+#include "pt_motion.h"
+#include "pt_wavefront.h"
+
+namespace hrt::capi {
+
+// Owns one device allocation: move-only, freed on reset() and on destruction (hipFree waits for work in flight). Converts to the plain
+// pointer, so kernels and copies take it as they took the raw field.
+template <class T> class DeviceBuffer {
+public:
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    ~DeviceBuffer() { reset(); }
+    void reset() { if (p_) { (void)hipFree(p_); p_ = nullptr; } }
+    hipError_t alloc(size_t bytes)               // the old allocation goes first; empty after a failure
+    {
+        reset();
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p_), bytes);
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+private:
+    T* p_ = nullptr;
+};
+using DeviceAllocations = std::vector<DeviceBuffer<void>>;
+
+// The device copy of one animation on one context (hrpt_animate): the resolved tables, and the state its kernels write.
+struct AnimDeviceCopy {
+    AnimDeviceCopy() = default; AnimDeviceCopy(AnimDeviceCopy&&) = default; AnimDeviceCopy& operator=(AnimDeviceCopy&&) = default;   // move-only: it owns `allocations`
+    const HrptAnimation* anim = nullptr; uint64_t serial = 0;
+    DeviceAllocations allocations;
+    anim::Tables tables{};
+    uint32_t* groupFirst = nullptr; float* times = nullptr;
+    float* trs = nullptr; float* worlds = nullptr; float* weights = nullptr; float* palette = nullptr;
+    HrptPerInstanceData* records = nullptr;      // the closed instance range; equal to the context's host copy of it while recordsEpoch == instanceEpoch
+    uint64_t recordsEpoch = 0;
+};
+
+// Buffers that live as long as the uploaded scene: free_scene drops them with one assignment.
+struct PerSceneBuffers {
+    // the device tables the first motion call (hrpt_render_motion_vectors) builds from the kept copies
+    DeviceBuffer<MotionInst> dMotionInst; size_t motionInstCapacity = 0;       // one record per instance: m_PrevWorld + the mesh's LOD-0 index offset
+    DeviceBuffer<float> dMotionPositions; DeviceBuffer<uint32_t> dMotionIndices;   // object-space positions (12 B per vertex) and the index buffer
+    bool motionInstStale = true, motionGeometryStale = true;                   // set by uploads / instance updates / rebuilds, cleared by the next motion call
+    // deforming meshes (hrpt_update_vertices): the object-space positions of the previous frame, 3 floats per vertex; EMPTY = previous == current
+    // (a context that never deforms pays nothing). The device copy is made by the next motion call (motionPositionsStale), like dMotionPositions.
+    std::vector<float> keptPrevPositions; DeviceBuffer<float> dMotionPrevPositions; bool motionPositionsStale = true;
+    DeviceBuffer<HrptVertexFloat> dSkinFloats;                                 // hrpt_update_vertices_skinned: the skinned float vertices between its two kernels, sized for the whole vertex buffer at first use
+    DeviceBuffer<void> dDeformStaging; size_t deformStagingBytes = 0;          // hrpt_update_vertices_device / _skinned: quantised records + the two status words, sized for the whole vertex buffer at first use
+};
+
+// Images of width * height float4: hrpt_resize decides which of them survive a change of size.
+struct PerSizeImages {
+    DeviceBuffer<float4> dAccum, dOutput, dDisplay;
+    DeviceBuffer<float4> dGBuffer[HRPT_GB_PLANES];   // first-hit G-buffer planes (hrpt_render_gbuffer): allocated by the first call that requests one, re-allocated by hrpt_resize
+    DeviceBuffer<float4> dMotion;                    // first-hit motion vectors (hrpt_render_motion_vectors)
+    DeviceBuffer<float4> dTemporal[2];               // temporal accumulation (hrpt_temporal_accumulate): ping-pong history pair, allocated by the first call
+    DeviceBuffer<float4> dDenoiseScratch[2];         // the scratch pair of HRPT_DENOISE_OUTPUT_ONLY
+    DeviceBuffer<float4> dModulation;                // demodulate / compose: the stored factor, allocated by the first hrpt_demodulate, dropped by hrpt_resize
+};
+
+// Buffers that live as long as the context.
+struct PerContextBuffers {
+    DeviceBuffer<uint32_t> dHistogram; DeviceBuffer<float> dExposure;   // persistent exposure buffer (HDRRenderer m_RG_ExposureBuffer)
+    DeviceBuffer<uint32_t> dBloomDown, dBloomUp; size_t bloomWords = 0;    // bloom pyramids (packed R11G11B10_FLOAT), sized by the last bloom call
+    DeviceBuffer<float> dDenoiseTile;                // the default noise tile, uploaded by the first denoise call of the context
+    DeviceBuffer<DeviceCounters> dCounters;
+};
+
+struct Context {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t ownStream = nullptr;         // created by hrpt_create; `stream` may be redirected by hrpt_set_stream
+    std::string err;
+    // scene
+    DeviceAllocations allocations;           // scene-lifetime device allocations
+    DeviceAllocations bvhAllocations;        // acceleration structure of the host builder + per-instance records: replaced by hrpt_update_instances
+    DeviceBuffer<GpuNodeQ> nodesQ; size_t nodesQCapacity = 0;    // quantised copy of the flat 4-wide tree (pt_device.h GpuNodeQ), kept across rebuilds
+    uint32_t nodes4Capacity = 0;             // records behind view.nodes4 when it is the GPU builder's buffer (0: allocated to size), for hrpt_selftest_read_bvh
+    GpuBvhBuilder* gpuBuilder = nullptr;     // GPU builders: geometry + build buffers stay on the device for rebuilds
+    GpuBvhBuilder* tlasBuilder = nullptr; uint32_t tlasBuilderInstances = 0;   // two-level structure: the tree over the instances, built on the GPU (build_two_level)
+    // host copy of what a rebuild needs (the reference's Scene keeps the same vectors: m_InstanceData, m_Vertices, m_Indices, m_MeshData)
+    std::vector<HrptVertexQuantized> keptVertices; std::vector<uint32_t> keptIndices; std::vector<HrptMeshData> keptMeshData;
+    std::vector<HrptPerInstanceData> keptInstances; std::vector<HrptMaterialConstants> keptMaterials; std::vector<HrptGPULight> keptLights;
+    size_t lightCapacity = 0;                // entries the device light buffer can hold (hrpt_update_lights may grow it)
+    SceneView view{};
+    bool haveScene = false;
+    uint32_t bvhNodes = 0, bvhTris = 0;
+    PerSceneBuffers perScene;
+    // images
+    uint32_t width = 0, height = 0;
+    PerSizeImages perSize;
+    int temporalCur = 0; bool temporalValid = false;   // [temporalCur] is the history image the last hrpt_temporal_accumulate wrote
+    PerContextBuffers perContext;
+    uint32_t bloomTailTexels = 0;            // HRPT_BLOOM_FUSED_TAIL: levels of at most this many texels run in one workgroup's LDS (0 = one kernel per pass, the measured-faster default)
+    hipEvent_t evStart = nullptr, evStop = nullptr;
+    bool timed = false;
+    WavefrontState wf;
+    SceneTraits traits;
+    int bvhBuilder = HRPT_BVH_BUILDER_AUTO;       // hrpt_set_bvh_builder
+    int accelStructure = HRPT_ACCEL_AUTO;         // hrpt_set_acceleration_structure
+    BuiltTwoLevel* twoLevel = nullptr;            // two-level scenes: host copy (hrpt_update_instances rebuilds the instance tree from it)
+    DeviceAllocations meshAllocations;            // ... and the device copies of the per-mesh arrays, which survive instance updates
+    uint32_t megakernelFallbacks = 0;             // renders that wanted the wavefront pipeline but could not use it (HrptStats)
+    HrptBuildInfo buildInfo{};
+    std::vector<AnimDeviceCopy> animations;       // hrpt_animate: one device copy per animation seen, until hrpt_animation_release / hrpt_destroy
+    uint64_t instanceEpoch = 1;                   // bumped whenever keptInstances changes
+};
+
+} // namespace hrt::capi
+
+struct HrptContext : hrt::capi::Context {};
+
+namespace hrt::capi {
+
+// Records the message (on the context, or for hrpt_last_error(NULL) without one) and passes the code through.
+int fail(HrptContext* ctx, int code, const std::string& msg);
+inline int hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? HRPT_ERR_OUT_OF_MEMORY : HRPT_ERR_HIP; }
+#define HIP_TRY(ctx, expr)                                                                         \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return fail(ctx, hip_status(e_), std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+#define HRPT_TRY(expr) do { int r_ = (expr); if (r_ != HRPT_OK) return r_; } while (0)      // pass a failed status on (fail() has set the message)
+
+// No C++ exception crosses the C boundary: host-side allocation failures (std::bad_alloc on very large scenes) become status codes. Every
+// exported function that can allocate on the host (a std::vector, a std::string for fail()) is a function-try-block that ends in
+// `catch (...) { return caught(c, "hrpt_x"); }`: caught() rethrows the exception in flight and is the one place that maps it.
+inline int caught(HrptContext* c, const char* name)
+{
+    try { throw; }
+    catch (const std::bad_alloc&) { return fail(c, HRPT_ERR_OUT_OF_MEMORY, std::string(name) + ": host allocation failed"); }
+    catch (const std::exception& e) { return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(name) + ": " + e.what()); }
+}
+
+// The host executors (the *_host entry points, which take no context) keep a mapping of their own: what they may throw is their buffers
+// and their threads.
+template <class Fn> int run_host(const char* what, Fn fn)
+{
+    try { fn(); }
+    catch (const std::bad_alloc&) { return fail(nullptr, HRPT_ERR_OUT_OF_MEMORY, std::string(what) + ": out of memory"); }
+    catch (const std::system_error& e) { return fail(nullptr, HRPT_ERR_UNSUPPORTED, std::string(what) + ": " + e.what()); }
+    return HRPT_OK;
+}
+// Threads of a host executor: 0 or less = one per hardware thread up to 16; at most 256.
+inline int host_threads(int nthreads)
+{
+    if (nthreads <= 0) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; }
+    if (nthreads < 1) nthreads = 1;
+    return nthreads > 256 ? 256 : nthreads;
+}
+
+inline bool size_ok(uint32_t width, uint32_t height) { return !(width == 0 || height == 0 || width > 65535u || height > 65535u); }
+int realloc_image(HrptContext* c, DeviceBuffer<float4>& image, size_t bytes);      // a fresh image, zeroed on the context stream
+int read_image(HrptContext* c, const float4* src, float* dst, size_t bytes, const char* what);
+
+// A device copy of host[0 .. count), owned by `owner` (default: the scene's allocation list).
+template <class T>
+int upload(HrptContext* c, const T* host, size_t count, const T** dev, DeviceAllocations* owner = nullptr)
+{
+    *dev = nullptr;
+    size_t bytes = count * sizeof(T);
+    DeviceBuffer<void> p;
+    HIP_TRY(c, p.alloc(bytes ? bytes : 16));
+    void* d = p.get();
+    (owner ? *owner : c->allocations).push_back(std::move(p));
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream));
+    *dev = static_cast<const T*>(d);
+    return HRPT_OK;
+}
+
+// pt_capi_scene.cpp
+int build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t sceneTris, SceneView& v, bool firstBuild, bool refit = false);
+HrptSceneDesc kept_scene_desc(HrptContext* c);
+uint64_t kept_triangle_count(const HrptContext* c);
+int update_instances_impl(HrptContext* c, const HrptPerInstanceData* instances, uint32_t firstInstance, uint32_t count, bool refit);
+void free_scene(HrptContext* c);
+void refresh_traits(HrptContext* c);
+
+} // namespace hrt::capi

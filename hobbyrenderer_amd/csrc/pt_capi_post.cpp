@@ -1,0 +1,434 @@
+// pt_capi_post.cpp -- what works on finished images: hrpt_post_process and the exposure, then the screen-space stages (bloom, temporal
+// accumulation, denoise, demodulate / compose) with their _host, _device and probe entry points.
+#include <cmath>
+
+#include "pt_capi_internal.h"
+
+using namespace hrt;
+using namespace hrt::capi;
+
+int hrpt_post_process(HrptContext* c, const HrptPostParams* p)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process: null params");
+    if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process: hrpt_resize not called");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->perContext.dExposure) {
+        HIP_TRY(c, c->perContext.dExposure.alloc(16));
+        HIP_TRY(c, c->perContext.dHistogram.alloc(256 * sizeof(uint32_t)));
+        const float one[4] = { 1.0f, 0.0f, 0.0f, 0.0f };
+        HIP_TRY(c, hipMemcpy(c->perContext.dExposure, one, 16, hipMemcpyHostToDevice));
+    }
+    if (!c->perSize.dDisplay) HIP_TRY(c, c->perSize.dDisplay.alloc((size_t)c->width * c->height * sizeof(float4)));
+    HIP_TRY(c, launch_post_chain(c->perSize.dOutput, c->perSize.dDisplay, c->width * c->height, *p, c->perContext.dHistogram, c->perContext.dExposure, c->stream));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_post_process"); }
+
+// ---- screen-space stages: bloom, temporal accumulation, denoise, demodulate / compose ----
+// What the _host, _device and context entry points of a stage with a view check alike, in this order, after their null checks and, for
+// caller-owned images, the image checks: the size, then the view against it. The stage's parameter rule follows.
+static bool view_matches(const HrptPlanarViewConstants& view, uint32_t width, uint32_t height)
+{
+    return view.m_ViewportSize[0] == (float)width && view.m_ViewportSize[1] == (float)height;
+}
+static int size_and_view_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view)
+{
+    if (!size_ok(width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
+    if (!view_matches(view, width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
+    return HRPT_OK;
+}
+
+// Pyramids for a width x height image: kept while the size stays, re-allocated when it changes (hipFree waits for work in flight).
+static int bloom_run(HrptContext* c, float4* image, uint32_t width, uint32_t height, const HrptBloomParams& p, hipStream_t stream)
+{
+    const size_t words = bloom_pyramid_words(width, height);
+    if (words == 0) return HRPT_OK;
+    if (words != c->perContext.bloomWords) {
+        c->perContext.dBloomDown.reset(); c->perContext.dBloomUp.reset(); c->perContext.bloomWords = 0;     // both go before anything is allocated
+        HIP_TRY(c, c->perContext.dBloomDown.alloc(words * sizeof(uint32_t)));
+        HIP_TRY(c, c->perContext.dBloomUp.alloc(words * sizeof(uint32_t)));
+        c->perContext.bloomWords = words;
+    }
+    HIP_TRY(c, launch_bloom(image, width, height, p, c->perContext.dBloomDown, c->perContext.dBloomUp, c->bloomTailTexels, stream));
+    return HRPT_OK;
+}
+
+int hrpt_bloom(HrptContext* c, const HrptBloomParams* p)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom: null params");
+    if (!bloom_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom: knee, intensity and upsampleRadius must be finite and >= 0");
+    if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom: hrpt_resize not called");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return bloom_run(c, c->perSize.dOutput, c->width, c->height, *p, c->stream);
+} catch (...) { return caught(c, "hrpt_bloom"); }
+
+int hrpt_bloom_device(HrptContext* c, float* hdrDevice, uint32_t width, uint32_t height, const HrptBloomParams* p, void* stream)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: null params");
+    if (!hdrDevice) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: null image");
+    if (!size_ok(width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: size must be 1..65535");
+    if (!bloom_params_valid(*p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_device: knee, intensity and upsampleRadius must be finite and >= 0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return bloom_run(c, reinterpret_cast<float4*>(hdrDevice), width, height, *p, static_cast<hipStream_t>(stream));
+} catch (...) { return caught(c, "hrpt_bloom_device"); }
+
+int hrpt_bloom_host(const float* hdrIn, float* hdrOut, uint32_t width, uint32_t height, const HrptBloomParams* p, int nthreads)
+{
+    if (!p) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: null params");
+    if (!hdrIn || !hdrOut) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: null image");
+    if (!size_ok(width, height)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: size must be 1..65535");
+    if (!bloom_params_valid(*p)) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_host: knee, intensity and upsampleRadius must be finite and >= 0");
+    return run_host("hrpt_bloom_host", [&] { bloom_host(hdrIn, hdrOut, width, height, *p, host_threads(nthreads)); });
+}
+
+int hrpt_bloom_pack_probe(const float* rgb, uint32_t count, uint32_t* packed, float* unpackedRgb)
+{
+    if (!rgb && count) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_bloom_pack_probe: null input");
+    bloom_pack_probe(rgb, count, packed, unpackedRgb);
+    return HRPT_OK;
+}
+
+// ---- temporal accumulation (pt_temporal.h / pt_temporal.hip) ----
+// Size, view and parameters: all a context call has left to check once its arguments are not null (its images are the context's own).
+static int temporal_args_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view, const HrptTemporalParams& p)
+{
+    HRPT_TRY(size_and_view_check(c, w, width, height, view));
+    if (!temporal_params_valid(p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": blend must be finite and in [0, 1], flags HRPT_TEMPORAL_* only, reserved 0");
+    return HRPT_OK;
+}
+// Caller-owned images: the null checks and the aliasing rule first, then the above.
+static int temporal_check(HrptContext* c, const char* what, const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                          const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p)
+{
+    const std::string w(what);
+    if (!img || !view || !prevView || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->color || !img->motion || !img->depth || !img->normal || !img->historyOut || !img->colorOut)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only historyIn may be NULL)");
+    if (img->historyOut == img->historyIn) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": historyOut must differ from historyIn");
+    return temporal_args_check(c, w, width, height, *view, *p);
+}
+
+int hrpt_temporal_host(const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                       const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p, int nthreads)
+{
+    HRPT_TRY(temporal_check(nullptr, "hrpt_temporal_host", img, width, height, view, prevView, p));
+    return run_host("hrpt_temporal_host", [&] { temporal_host(*img, width, height, *view, *prevView, *p, host_threads(nthreads)); });
+}
+
+int hrpt_temporal_device(HrptContext* c, const HrptTemporalImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                         const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p, void* stream)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(temporal_check(c, "hrpt_temporal_device", img, width, height, view, prevView, p));
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_temporal(*img, width, height, *view, *prevView, *p, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_temporal_device"); }
+
+int hrpt_temporal_accumulate(HrptContext* c, const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptTemporalParams* p)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!view || !prevView || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: null argument");
+    if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: hrpt_resize not called");
+    if (!c->perSize.dMotion || !c->perSize.dGBuffer[HRPT_GB_DEPTH] || !c->perSize.dGBuffer[HRPT_GB_NORMAL])
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: the motion, depth or normal plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH | NORMAL fills them)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HRPT_TRY(temporal_args_check(c, "hrpt_temporal_accumulate", c->width, c->height, *view, *p));      // before anything is allocated
+    const bool fresh = !c->perSize.dTemporal[0];
+    const int next = fresh ? 0 : 1 - c->temporalCur;
+    if (fresh) {
+        for (DeviceBuffer<float4>& image : c->perSize.dTemporal) HRPT_TRY(realloc_image(c, image, (size_t)c->width * c->height * sizeof(float4)));
+        c->temporalValid = false;
+    }
+    HrptTemporalImages img{};
+    img.color = reinterpret_cast<const float*>(c->perSize.dOutput.get()); img.colorOut = reinterpret_cast<float*>(c->perSize.dOutput.get());
+    img.motion = reinterpret_cast<const float*>(c->perSize.dMotion.get());
+    img.depth = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get()); img.normal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_NORMAL].get());
+    const bool useHistory = c->temporalValid && (p->flags & HRPT_TEMPORAL_RESET) == 0;
+    img.historyIn = useHistory ? reinterpret_cast<const float*>(c->perSize.dTemporal[1 - next].get()) : nullptr;
+    img.historyOut = reinterpret_cast<float*>(c->perSize.dTemporal[next].get());
+    HIP_TRY(c, launch_temporal(img, c->width, c->height, *view, *prevView, *p, c->stream));
+    c->temporalCur = next; c->temporalValid = true;
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_temporal_accumulate"); }
+
+int hrpt_read_temporal_history(HrptContext* c, float* dst, size_t bytes)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->perSize.dTemporal[0]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_temporal_history: the history was never requested from hrpt_temporal_accumulate");
+    return read_image(c, c->perSize.dTemporal[c->temporalCur], dst, bytes, "hrpt_read_temporal_history");
+} catch (...) { return caught(c, "hrpt_read_temporal_history"); }
+
+int hrpt_get_temporal_history_device(HrptContext* c, void** devicePtr)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_temporal_history_device: null out");
+    *devicePtr = c->perSize.dTemporal[0] ? c->perSize.dTemporal[c->temporalCur] : nullptr;
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_get_temporal_history_device"); }
+
+// ---- denoise (pt_denoise.h / pt_denoise.hip) ----
+// Size, view and parameters: all a context call has left to check once its arguments are not null (its images are the context's own).
+static int denoise_args_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view, const HrptDenoiseParams& p,
+                              bool singlePass)
+{
+    HRPT_TRY(size_and_view_check(c, w, width, height, view));
+    if (!denoise_params_valid(p))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": radius and phi must be finite and > 0, the other phis finite and >= 0, iterations 1..5 with radius * 2^(iterations - 1) finite, flags HRPT_DENOISE_* only, reserved 0");
+    if (singlePass && p.iterations != 1u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": one pass per call, iterations must be 1 (hrpt_denoise iterates)");
+    return HRPT_OK;
+}
+// Caller-owned images, one pass: the null checks and the aliasing rules first, then the above.
+static int denoise_check(HrptContext* c, const char* what, const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                         const HrptDenoiseParams* p)
+{
+    const std::string w(what);
+    if (!img || !view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->input || !img->depth || !img->normal || !img->geoNormal || !img->output)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only noise, and color with colorOut, may be NULL)");
+    if ((img->color == nullptr) != (img->colorOut == nullptr)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": color and colorOut must both be NULL or both be set");
+    if (img->output == img->input) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": output must differ from input");
+    if (img->color && (img->color == img->input || img->colorOut == img->input)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": color and colorOut must differ from input");
+    return denoise_args_check(c, w, width, height, *view, *p, true);
+}
+
+static int denoise_tile(HrptContext* c)
+{
+    if (c->perContext.dDenoiseTile) return HRPT_OK;
+    std::vector<float> tile(denoise_noise_floats());
+    denoise_default_tile(tile.data());
+    DeviceBuffer<float> d;
+    HIP_TRY(c, d.alloc(tile.size() * sizeof(float)));
+    HIP_TRY(c, hipMemcpy(d, tile.data(), tile.size() * sizeof(float), hipMemcpyHostToDevice));     // complete on return: ordered before every later launch
+    c->perContext.dDenoiseTile = std::move(d);
+    return HRPT_OK;
+}
+
+int hrpt_set_denoise_noise(HrptContext* c, const float* hostTile)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    const size_t count = denoise_noise_floats();
+    std::vector<float> tile(count);
+    if (hostTile) {
+        for (size_t i = 0; i < count; ++i) {
+            if (!std::isfinite(hostTile[i])) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_set_denoise_noise: the tile holds a value that is not finite");
+            tile[i] = hostTile[i];
+        }
+    } else denoise_default_tile(tile.data());
+    HIP_TRY(c, hipSetDevice(c->device));
+    HRPT_TRY(denoise_tile(c));
+    // on the context stream: passes enqueued before this call still read the old tile. The source is pageable and local, so wait for the copy.
+    HIP_TRY(c, hipMemcpyAsync(c->perContext.dDenoiseTile, tile.data(), count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_set_denoise_noise"); }
+
+int hrpt_denoise_host(const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view, const HrptDenoiseParams* p, int nthreads)
+{
+    HRPT_TRY(denoise_check(nullptr, "hrpt_denoise_host", img, width, height, view, p));
+    return run_host("hrpt_denoise_host", [&] { denoise_host(*img, width, height, *view, *p, host_threads(nthreads)); });
+}
+
+int hrpt_denoise_device(HrptContext* c, const HrptDenoiseImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                        const HrptDenoiseParams* p, void* stream)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(denoise_check(c, "hrpt_denoise_device", img, width, height, view, p));
+    HIP_TRY(c, hipSetDevice(c->device));
+    HrptDenoiseImages im = *img;
+    if (!im.noise) { HRPT_TRY(denoise_tile(c)); im.noise = c->perContext.dDenoiseTile; }
+    HIP_TRY(c, launch_denoise(im, width, height, *view, *p, p->radius, p->frame, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_denoise_device"); }
+
+int hrpt_denoise(HrptContext* c, const HrptPlanarViewConstants* view, const HrptDenoiseParams* p)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: null argument");
+    if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: hrpt_resize not called");
+    if (!c->perSize.dTemporal[0] || !c->temporalValid)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: no temporal history at the current size (hrpt_temporal_accumulate writes the image this stage filters)");
+    if (!c->perSize.dGBuffer[HRPT_GB_DEPTH] || !c->perSize.dGBuffer[HRPT_GB_NORMAL] || !c->perSize.dGBuffer[HRPT_GB_GEO_NORMAL])
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: the depth, normal or geo-normal plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH | NORMAL | GEO_NORMAL fills them)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HRPT_TRY(denoise_args_check(c, "hrpt_denoise", c->width, c->height, *view, *p, false));
+    HRPT_TRY(denoise_tile(c));
+    HrptDenoiseImages img{};
+    img.input = reinterpret_cast<const float*>(c->perSize.dTemporal[c->temporalCur].get());
+    img.depth = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get()); img.normal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_NORMAL].get());
+    img.geoNormal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_GEO_NORMAL].get());
+    img.noise = c->perContext.dDenoiseTile;
+    const bool outputOnly = (p->flags & HRPT_DENOISE_OUTPUT_ONLY) != 0;
+    if (outputOnly) {
+        const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+        for (uint32_t k = 0; k < (p->iterations > 1u ? 2u : 1u); ++k)
+            if (!c->perSize.dDenoiseScratch[k]) HIP_TRY(c, c->perSize.dDenoiseScratch[k].alloc(bytes));
+    }
+    int cur = c->temporalCur;
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        // default: the two history images are the ping-pong pair (the stale one is free after the temporal call); the image a pass wrote is the history
+        float4* dst = outputOnly ? c->perSize.dDenoiseScratch[i & 1u] : c->perSize.dTemporal[1 - cur];
+        img.output = reinterpret_cast<float*>(dst);
+        const bool last = i + 1u == p->iterations;
+        img.color = last ? reinterpret_cast<const float*>(c->perSize.dOutput.get()) : nullptr;
+        img.colorOut = last ? reinterpret_cast<float*>(c->perSize.dOutput.get()) : nullptr;
+        HIP_TRY(c, launch_denoise(img, c->width, c->height, *view, *p, p->radius * (float)(1u << i), p->frame * p->iterations + i, c->stream));
+        img.input = reinterpret_cast<const float*>(dst);
+        if (!outputOnly) { cur = 1 - cur; c->temporalCur = cur; }
+    }
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_denoise"); }
+
+// ---- demodulate / compose (pt_modulation.h / pt_modulation.hip) ----
+// Size, view and parameters: all a context call has left to check once its arguments are not null (its images are the context's own).
+static int demodulate_args_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view, const HrptModulationParams& p)
+{
+    HRPT_TRY(size_and_view_check(c, w, width, height, view));
+    if (!modulation_params_valid(p)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": floor must be finite and > 0, flags 0, reserved 0");
+    return HRPT_OK;
+}
+// Caller-owned images: the null checks and the aliasing rules first, then the above.
+static int demodulate_check(HrptContext* c, const char* what, const HrptDemodulateImages* img, uint32_t width, uint32_t height,
+                            const HrptPlanarViewConstants* view, const HrptModulationParams* p)
+{
+    const std::string w(what);
+    if (!img || !view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->color || !img->albedo || !img->normal || !img->geoNormal || !img->depth || !img->colorOut || !img->modulationOut)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only emissive may be NULL)");
+    const float* inputs[6] = { img->color, img->albedo, img->normal, img->geoNormal, img->depth, img->emissive };
+    for (const float* in : inputs)
+        if (in && img->modulationOut == in) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": modulationOut must differ from every input");
+    if (img->modulationOut == img->colorOut) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": modulationOut must differ from colorOut");
+    for (int i = 1; i < 6; ++i)
+        if (inputs[i] && img->colorOut == inputs[i]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": colorOut may equal color, but no other input");
+    return demodulate_args_check(c, w, width, height, *view, *p);
+}
+
+static int compose_check(HrptContext* c, const char* what, const HrptComposeImages* img, uint32_t width, uint32_t height)
+{
+    const std::string w(what);
+    if (!img) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->color || !img->modulation || !img->colorOut) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only emissive may be NULL)");
+    if (img->colorOut == img->modulation || (img->emissive && img->colorOut == img->emissive))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": colorOut may equal color, but not modulation or emissive");
+    if (!size_ok(width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
+    return HRPT_OK;
+}
+
+int hrpt_demodulate_host(const HrptDemodulateImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                         const HrptModulationParams* p, int nthreads)
+{
+    HRPT_TRY(demodulate_check(nullptr, "hrpt_demodulate_host", img, width, height, view, p));
+    return run_host("hrpt_demodulate_host", [&] { demodulate_host(*img, width, height, *view, *p, host_threads(nthreads)); });
+}
+
+int hrpt_compose_host(const HrptComposeImages* img, uint32_t width, uint32_t height, int nthreads)
+{
+    HRPT_TRY(compose_check(nullptr, "hrpt_compose_host", img, width, height));
+    return run_host("hrpt_compose_host", [&] { compose_host(*img, width, height, host_threads(nthreads)); });
+}
+
+int hrpt_demodulate_device(HrptContext* c, const HrptDemodulateImages* img, uint32_t width, uint32_t height, const HrptPlanarViewConstants* view,
+                           const HrptModulationParams* p, void* stream)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(demodulate_check(c, "hrpt_demodulate_device", img, width, height, view, p));
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_demodulate(*img, width, height, *view, *p, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_demodulate_device"); }
+
+int hrpt_compose_device(HrptContext* c, const HrptComposeImages* img, uint32_t width, uint32_t height, void* stream)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(compose_check(c, "hrpt_compose_device", img, width, height));
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_compose(*img, width, height, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_compose_device"); }
+
+int hrpt_demodulate(HrptContext* c, const HrptPlanarViewConstants* view, const HrptModulationParams* p)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_demodulate: null argument");
+    if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_demodulate: hrpt_resize not called");
+    static const struct { int plane; const char* name; } needed[5] = { { HRPT_GB_ALBEDO, "HRPT_GB_ALBEDO" }, { HRPT_GB_NORMAL, "HRPT_GB_NORMAL" },
+        { HRPT_GB_GEO_NORMAL, "HRPT_GB_GEO_NORMAL" }, { HRPT_GB_EMISSIVE, "HRPT_GB_EMISSIVE" }, { HRPT_GB_DEPTH, "HRPT_GB_DEPTH" } };
+    for (const auto& n : needed)
+        if (!c->perSize.dGBuffer[n.plane])
+            return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_demodulate: the plane ") + n.name + " was never requested (hrpt_render_motion_vectors or hrpt_render_gbuffer with planeMask = ALBEDO | NORMAL | GEO_NORMAL | EMISSIVE | DEPTH fills them)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HRPT_TRY(demodulate_args_check(c, "hrpt_demodulate", c->width, c->height, *view, *p));      // before anything is allocated
+    if (!c->perSize.dModulation) HIP_TRY(c, c->perSize.dModulation.alloc((size_t)c->width * c->height * sizeof(float4)));
+    HrptDemodulateImages img{};
+    img.color = reinterpret_cast<const float*>(c->perSize.dOutput.get()); img.colorOut = reinterpret_cast<float*>(c->perSize.dOutput.get());
+    img.albedo = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_ALBEDO].get()); img.normal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_NORMAL].get());
+    img.geoNormal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_GEO_NORMAL].get()); img.depth = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get());
+    img.emissive = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_EMISSIVE].get());
+    img.modulationOut = reinterpret_cast<float*>(c->perSize.dModulation.get());
+    HIP_TRY(c, launch_demodulate(img, c->width, c->height, *view, *p, c->stream));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_demodulate"); }
+
+int hrpt_compose(HrptContext* c)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_compose: hrpt_resize not called");
+    if (!c->perSize.dModulation)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_compose: no modulation image at the current size (hrpt_demodulate writes the factor this stage multiplies back in)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HrptComposeImages img{};
+    img.color = reinterpret_cast<const float*>(c->perSize.dOutput.get()); img.colorOut = reinterpret_cast<float*>(c->perSize.dOutput.get());
+    img.modulation = reinterpret_cast<const float*>(c->perSize.dModulation.get());
+    img.emissive = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_EMISSIVE].get());      // set: hrpt_demodulate required it, and a resize drops the modulation image
+    HIP_TRY(c, launch_compose(img, c->width, c->height, c->stream));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_compose"); }
+
+int hrpt_read_modulation(HrptContext* c, float* dst, size_t bytes)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->perSize.dModulation) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_modulation: no modulation image at the current size (hrpt_demodulate writes it)");
+    return read_image(c, c->perSize.dModulation, dst, bytes, "hrpt_read_modulation");
+} catch (...) { return caught(c, "hrpt_read_modulation"); }
+
+int hrpt_get_modulation_device(HrptContext* c, void** devicePtr)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_modulation_device: null out");
+    *devicePtr = c->perSize.dModulation;
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_get_modulation_device"); }
+
+int hrpt_modulation_probe(const float* albedo3, const float* N3, const float* V3, float rough, float metal, float floor, float* outM3)
+{
+    if (!albedo3 || !N3 || !V3 || !outM3) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_modulation_probe: null argument");
+    modulation_probe(albedo3, N3, V3, rough, metal, floor, outM3);
+    return HRPT_OK;
+}
+
+int hrpt_get_exposure(HrptContext* c, float* exposure, uint32_t histogram256[256])
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!exposure || !c->perContext.dExposure) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_exposure: no post pass has run");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(exposure, c->perContext.dExposure, sizeof(float), hipMemcpyDeviceToHost));
+    if (histogram256) HIP_TRY(c, hipMemcpy(histogram256, c->perContext.dHistogram, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_get_exposure"); }
+
+int hrpt_set_exposure(HrptContext* c, float exposure)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->perContext.dExposure) {
+        HIP_TRY(c, c->perContext.dExposure.alloc(16));
+        HIP_TRY(c, c->perContext.dHistogram.alloc(256 * sizeof(uint32_t)));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(c->perContext.dExposure, &exposure, sizeof(float), hipMemcpyHostToDevice));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_set_exposure"); }
