@@ -242,11 +242,11 @@ try {
     }
     if (c->timed) { float ms = 0.0f; if (hipEventElapsedTime(&ms, c->evStart, c->evStop) == hipSuccess) out->lastRenderMs = ms; }
     wavefront_collect_timing(c->wf);
-    out->traceKernelMs = c->wf.kernelMs[0]; out->traceKernelLaunches = c->wf.kernelLaunches[0];
-    out->shadeKernelMs = c->wf.kernelMs[1]; out->shadeKernelLaunches = c->wf.kernelLaunches[1];
-    out->shadowKernelMs = c->wf.kernelMs[2]; out->shadowKernelLaunches = c->wf.kernelLaunches[2];
-    out->raygenKernelMs = c->wf.kernelMs[3]; out->raygenKernelLaunches = c->wf.kernelLaunches[3];
-    out->resolveKernelMs = c->wf.kernelMs[4]; out->resolveKernelLaunches = c->wf.kernelLaunches[4];
+    out->traceKernelMs = c->wf.kernelMs[kKernelExtend]; out->traceKernelLaunches = c->wf.kernelLaunches[kKernelExtend];
+    out->shadeKernelMs = c->wf.kernelMs[kKernelShade]; out->shadeKernelLaunches = c->wf.kernelLaunches[kKernelShade];
+    out->shadowKernelMs = c->wf.kernelMs[kKernelShadow]; out->shadowKernelLaunches = c->wf.kernelLaunches[kKernelShadow];
+    out->raygenKernelMs = c->wf.kernelMs[kKernelRaygen]; out->raygenKernelLaunches = c->wf.kernelLaunches[kKernelRaygen];
+    out->resolveKernelMs = c->wf.kernelMs[kKernelResolve]; out->resolveKernelLaunches = c->wf.kernelLaunches[kKernelResolve];
     out->bvhNodeCount = c->bvhNodes; out->bvhTriangleCount = c->bvhTris; out->bvhMaxDepth = c->traits.bvhMaxDepth;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_get_stats"); }

@@ -1,5 +1,5 @@
-// pt_capi_internal.h -- what the pt_capi*.cpp files share: the context, the status / error plumbing, the exception guard and the owner of a
-// device allocation. Host code of the C boundary only: no .hip file and no header a kernel includes may include it.
+// pt_capi_internal.h -- what the pt_capi*.cpp files share: the context, the status / error plumbing and the exception guard.
+// Host code of the C boundary only: no .hip file and no header a kernel includes may include it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,33 +19,14 @@
 #include "bvh_build_gpu.h"
 #include "pt_anim.h"
 #include "pt_device.h"
+#include "pt_device_buffer.h"
 #include "pt_kernels.h"
 #include "pt_motion.h"
 #include "pt_wavefront.h"
 
 namespace hrt::capi {
 
-// Owns one device allocation: move-only, freed on reset() and on destruction (hipFree waits for work in flight). Converts to the plain
-// pointer, so kernels and copies take it as they took the raw field.
-template <class T> class DeviceBuffer {
-public:
-    DeviceBuffer() = default;
-    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
-    ~DeviceBuffer() { reset(); }
-    void reset() { if (p_) { (void)hipFree(p_); p_ = nullptr; } }
-    hipError_t alloc(size_t bytes)               // the old allocation goes first; empty after a failure
-    {
-        reset();
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p_), bytes);
-        if (e != hipSuccess) p_ = nullptr;
-        return e;
-    }
-    T* get() const { return p_; }
-    operator T*() const { return p_; }
-private:
-    T* p_ = nullptr;
-};
+using hrt::DeviceBuffer;                     // pt_device_buffer.h: the owner of one device allocation
 using DeviceAllocations = std::vector<DeviceBuffer<void>>;
 
 // The device copy of one animation on one context (hrpt_animate): the resolved tables, and the state its kernels write.

@@ -263,7 +263,7 @@ try {
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_rays: this two-level structure is deeper than the thread-per-ray kernel's 64-entry stack");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool shadow = (flags & 0xFFu) == HRPT_RAYS_SHADOW;
-    // the persistent refilling traversal kernel (pt_wavefront.hip wf_trace_rays); the thread-per-ray kernel stays as the fallback for trees
+    // the persistent refilling traversal kernel (pt_wf_extend.h wf_trace_rays); the thread-per-ray kernel stays as the fallback for trees
     // deeper than its stacks allow and as the cross-check (HRPT_RAYS_THREAD_PER_RAY)
     const bool persistent = !(flags & HRPT_RAYS_THREAD_PER_RAY) && wavefront_trace_rays_supported(c->traits) && c->view.node4Count > 0;
     auto trace = [&](const HrptRay* dr, HrptRayHit* dh) -> hipError_t {

@@ -2,7 +2,7 @@
 // pixel. Contents follow GBufferOut of the reference's real-time modes (src/shaders/BasePass.hlsl:184-192, 485-493), computed
 // by the path tracer's own stages: the primary ray and RNG seed of init_path, the hit of TraceRayStandard, GetFullHitAttributes +
 // GetPBRAttributes and the normal flip of PathTracer.hlsl:110-117 -- the surface hrpt_render shades at bounce 0 for the same constants.
-// Both kernels (wf_gbuffer of pt_wavefront.hip, pt_gbuffer_kernel of pt_megakernel.hip) call gbuffer_texels / gbuffer_store below.
+// Both kernels (wf_gbuffer of pt_wf_gbuffer.h, pt_gbuffer_kernel of pt_megakernel.hip) call gbuffer_texels / gbuffer_store below.
 #pragma once
 
 #include "pt_path.h"

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/hobbyrt_pt.h"
+#include "pt_device_buffer.h"
 #include "pt_kernels.h"
 #include "pt_wavefront_plan.h"
 
@@ -15,22 +16,24 @@ namespace hrt {
 struct SceneView;
 struct MotionArgs;     // pt_motion.h
 
+// Kernel classes of the per-launch timing; the values index WavefrontState::kernelMs / kernelLaunches and name HrptStats fields in this order.
+enum KernelClass : int { kKernelExtend = 0, kKernelShade = 1, kKernelShadow = 2, kKernelRaygen = 3, kKernelResolve = 4, kKernelClasses = 5 };
+
 struct WavefrontState {
-    void* pool = nullptr;              // one device allocation carved into the SoA queues
+    DeviceBuffer<void> pool;           // one device allocation carved into the SoA queues
     size_t poolBytes = 0;
-    void* spill = nullptr;             // traversal-stack overflow columns (only for trees deeper than the LDS stack)
+    DeviceBuffer<void> spill;          // traversal-stack overflow columns (only for trees deeper than the LDS stack)
     size_t spillBytes = 0;
-    void* traceSpill = nullptr;        // the same for hrpt_trace_rays batches
+    DeviceBuffer<void> traceSpill;     // the same for hrpt_trace_rays batches
     size_t traceSpillBytes = 0;
-    void* gbPool = nullptr;            // queue pool of hrpt_render_gbuffer calls the render's pool is too small for (never rendered, or a smaller tile)
+    DeviceBuffer<void> gbPool;         // queue pool of hrpt_render_gbuffer calls the render's pool is too small for (never rendered, or a smaller tile)
     size_t gbPoolBytes = 0;
-    // start/stop event pairs around every extend / shade / shadow launch; kind[i] = 0,1,2
+    // start/stop event pairs around every timed launch; kind[i] = its KernelClass
     std::vector<hipEvent_t> events;
     std::vector<uint8_t> kind;
     uint32_t eventsUsed = 0;
-    // kernel classes: 0 extend, 1 shade, 2 shadow stage, 3 raygen, 4 resolve
-    float kernelMs[5] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };      // summed device time per kernel class since the last reset
-    uint32_t kernelLaunches[5] = { 0, 0, 0, 0, 0 };
+    float kernelMs[kKernelClasses] = {};            // summed device time per kernel class since the last reset
+    uint32_t kernelLaunches[kKernelClasses] = {};
     // queue-byte accounting (HrptStats::*QueueBytes): what the host knows per render is summed here, the rest follows from the device
     // counters and the record layout of the last render (its plan)
     uint64_t raygenBytes = 0, resolveBytes = 0;

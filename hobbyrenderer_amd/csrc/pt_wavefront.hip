@@ -44,1469 +44,12 @@ namespace hrt {
 
 namespace {
 
-constexpr uint32_t kMaxSppPerBatch = 64;
-
-struct WfBuffers {
-    float4 *rayO[2], *rayD[2], *thr[2], *med0[2], *med1[2];
-    uint32_t* pathCnt[2];
-    float4* hit;
-    uint32_t* hitInst;         // two-level structure only: CommittedInstanceIndex of the hit in `hit` (the record's triangle index is per mesh)
-    float4 *sh0, *sh1, *sh2, *sh3, *sh4, *shL;
-    uint32_t* shadowCnt;
-    // shadow-ray stage of scenes with non-opaque geometry: one compacted ray per valid light sample {o, tmin} {d, tmax}, the (entry, light)
-    // slot it belongs to, rays per segment, and the outcome of the opaque any-hit pass per (entry, light) slot (kVis*)
-    float4 *sqO, *sqD; uint32_t* sqId; uint32_t* sqCnt; uint32_t* shVis;
-    uint2* sqCand;             // kShadowCandidates (t, triangle) keys per (entry, light) slot: the non-opaque triangles a ray crossed, nearest first
-    float4* radiance;
-};
-
-struct WfArgs {
-    SceneView scene;
-    WfBuffers b;
-    uint32_t segSize;          // samples per segment (any size from 64 to kMaxSegment: chosen per batch so that the segments divide evenly among the waves of the grids)
-    uint32_t numSegments;      // segments in this batch
-    uint32_t numSamples;       // tilesX*tilesY*64*spp (padded to 8x8 pixel tiles)
-    uint32_t pixelsPadded;     // tilesX*tilesY*64
-    uint32_t tilesX, tilesY;
-    TileRect rect;
-    uint32_t imageWidth;
-    uint32_t spp;              // accumulation indices in this batch
-    uint32_t maxLights;        // per-path light-sample slots in the shadow queue
-    uint32_t hasMedium;        // scene has thick transmissive materials (medium state travels with the path)
-    uint32_t hasStochasticAlpha;
-    uint32_t allOpaque;        // no ForceNonOpaque instance in the scene: closest-hit launches take the OPQ instantiations of wf_extend
-    uint32_t refillMin;        // wf_extend refills its idle lanes once at least this many have finished their ray
-    uint32_t streamSegments;   // wf_extend moves on to its next segment while rays of the previous one are still in flight
-    uint32_t slimShadow;       // slim shadow-queue entries (scenes of the SIMPLE shade variant with one light): sh0{origin, input slot} sh1{N, material}
-    uint32_t shadowParity;     // ... and the path queue those slots index (the input queue of the bounce's wf_shade)
-    uint32_t nodeLoopMin;      // wf_extend leaves its node-descent loop once fewer lanes than this are still at inner nodes (0: never)
-    uint32_t sortShade;        // wf_shade (general variants) shades the entries of a segment grouped by shading class
-    uint32_t shadeInstances, shadeMaterials;   // wf_shade_lt: records of scene.instShade / scene.materials it copies to LDS (with scene.triCount records of scene.attrs)
-    const struct PrimaryArgs* primaryArgs;     // device copy (queue pool), valid when `primary`
-    uint32_t primary;          // this launch works on bounce 0 of a batch whose primary rays are NOT in the path queue: slot == sample index, every
-                               // wf_extend<PRIMARY> derives the ray of a slot from PrimaryArgs and leaves {direction, RNG seed} in rayD; origin = camera, throughput (1,1,1)
-                               // (no wf_raygen launch; SIMPLE scenes)
-    int32_t* spill[2];         // per-lane stack overflow columns of wf_extend / wf_shadow (they run concurrently), element k of thread g at [k * threads + g]
-    DeviceCounters* counters;
-};
-
-enum : uint32_t { kVisNoRay = 0, kVisBlocked = 1, kVisClear = 2, kVisCandidates = 3 };   // shVis codes
-
-struct JitterTable { float2 j[kMaxSppPerBatch]; };
-// what the primary ray of a sample is computed from (PathTracer.hlsl:61-72, PathTracerRenderer.cpp:62-65); by value to the bounce-0 launches
-struct PrimaryArgs { float clipToWorld[16]; float cam[3]; float invW, invH; uint32_t accumIndex; float2 j[kMaxSppPerBatch]; };
-
-// Tile enumeration: row-major over the rectangle; with interleaved columns (stripeCount > 1) column-major, so that the consecutive tiles
-// of a segment stay neighbours in the image (8 pixels apart vertically instead of 8 * stripeCount horizontally: -3 % per rank at 8 ranks).
-HRT_DEV void tile_position(const WfArgs& a, uint32_t tile, uint32_t& tcol, uint32_t& trow)
-{
-    if (a.rect.stripeCount > 1u) { tcol = tile / a.tilesY; trow = tile - tcol * a.tilesY; }
-    else { trow = tile / a.tilesX; tcol = tile - trow * a.tilesX; }
-}
-
-// Pixel and primary ray of sample `smp` of the batch (the body of wf_raygen; with a.primary the bounce-0 kernels call it instead of reading the
-// path queue). false: the sample's pixel lies outside the rectangle (tiles are padded to 8 x 8).
-HRT_DEV bool primary_ray(const WfArgs& a, const PrimaryArgs& pr, uint32_t smp, f3& o, f3& d, uint32_t& rng)
-{
-    const uint32_t k = smp / a.pixelsPadded, p = smp - k * a.pixelsPadded;
-    const uint32_t tile = p >> 6, within = p & 63u;
-    uint32_t tcol, trow; tile_position(a, tile, tcol, trow);
-    const uint32_t px = a.rect.column_x(tcol) + (within & 7u), py = a.rect.y0 + trow * 8u + (within >> 3);
-    if (!(px < a.rect.x1 && py < a.rect.y1)) return false;
-    // init_path (pt_path.h) with the jitter / RNG stream of accumulation index first + k (PathTracerRenderer.cpp:62,:65)
-    const float u = (((float)px + 0.5f) + pr.j[k].x) * pr.invW;
-    const float v = (((float)py + 0.5f) + pr.j[k].y) * pr.invH;
-    const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;
-    const float* M = pr.clipToWorld;
-    const float ex = ((cx * M[0] + cy * M[4]) + 0.9f * M[8]) + 1.0f * M[12];
-    const float ey = ((cx * M[1] + cy * M[5]) + 0.9f * M[9]) + 1.0f * M[13];
-    const float ez = ((cx * M[2] + cy * M[6]) + 0.9f * M[10]) + 1.0f * M[14];
-    const float ew = ((cx * M[3] + cy * M[7]) + 0.9f * M[11]) + 1.0f * M[15];
-    const f3 end = mk3(ex / ew, ey / ew, ez / ew);
-    o = mk3(pr.cam[0], pr.cam[1], pr.cam[2]);
-    d = normalize(end - o);
-    rng = hrt_rng_seed(px, py, pr.accumIndex + k);
-    return true;
-}
-// entries of segment `seg` of the input path queue: counted by the producing kernel, or -- bounce 0 without a raygen pass -- every slot of the batch
-HRT_DEV uint32_t path_count(const WfArgs& a, uint32_t in, uint32_t seg)
-{
-    (void)in;
-    const uint32_t base = seg * a.segSize, left = a.numSamples - base, size = a.segSize; return left < size ? left : size;
-}
-
-// per-lane traversal stack in LDS: element (sp, lane-in-block) at base[sp * kBlock]
-// DEPTH 64 = "deeper than 32": the first 32 entries stay in LDS, the (rarely reached) rest lives in a per-lane column of global memory.
-template <int DEPTH, int LDSMAX>
-struct LdsStack {
-    static constexpr int kLdsStackMax = LDSMAX;
-    static constexpr int kLds = DEPTH > kLdsStackMax ? kLdsStackMax : DEPTH;
-    static constexpr int kRows = kLds;
-    int32_t* base; int32_t* spill; uint32_t spillStride;
-    HRT_DEV void push(int sp, int32_t v)
-    {
-        if (DEPTH <= kLdsStackMax || sp < kLds) base[(sp & (kLds - 1)) * kBlock] = v;
-        else spill[(size_t)(sp - kLds) * spillStride] = v;
-    }
-    HRT_DEV int32_t pop(int sp)
-    {
-        if (DEPTH <= kLdsStackMax || sp < kLds) return base[(sp & (kLds - 1)) * kBlock];
-        return spill[(size_t)(sp - kLds) * spillStride];
-    }
-};
-// per-lane buffer of the K closest non-opaque shadow candidates: (t, triangle) of entry k at base[(k*2 + {0,1}) * kBlock];
-// the barycentrics are recomputed from the triangle when the candidate is processed (same test => same bits)
-struct LdsCandidates {
-    int32_t* base;
-    HRT_DEV void key(int k, float& t, uint32_t& tri) const { t = __int_as_float(base[(k * 2 + 0) * kBlock]); tri = (uint32_t)base[(k * 2 + 1) * kBlock]; }
-    HRT_DEV void set(int k, float t, uint32_t tri) { base[(k * 2 + 0) * kBlock] = __float_as_int(t); base[(k * 2 + 1) * kBlock] = (int32_t)tri; }
-    HRT_DEV void move(int dst, int src) { base[(dst * 2 + 0) * kBlock] = base[(src * 2 + 0) * kBlock]; base[(dst * 2 + 1) * kBlock] = base[(src * 2 + 1) * kBlock]; }
-};
-// ... with the instance next to the triangle (two-level structure: the triangle index is per mesh): entry k at base[(k*3 + {0,1,2}) * kBlock]
-struct LdsCandidates3 {
-    int32_t* base;
-    HRT_DEV void key(int k, float& t, uint32_t& tri, uint32_t& inst) const { t = __int_as_float(base[(k * 3 + 0) * kBlock]); tri = (uint32_t)base[(k * 3 + 1) * kBlock]; inst = (uint32_t)base[(k * 3 + 2) * kBlock]; }
-    HRT_DEV void set(int k, float t, uint32_t tri, uint32_t inst) { base[(k * 3 + 0) * kBlock] = __float_as_int(t); base[(k * 3 + 1) * kBlock] = (int32_t)tri; base[(k * 3 + 2) * kBlock] = (int32_t)inst; }
-    HRT_DEV void move(int dst, int src) { for (int w = 0; w < 3; ++w) base[(dst * 3 + w) * kBlock] = base[(src * 3 + w) * kBlock]; }
-};
-// candidate list of one shadow ray in global memory (written by wf_extend<ANYHIT> when the ray finishes, read by wf_shadow)
-struct GlobalCandidates {
-    const uint2* base;
-    HRT_DEV void key(int k, float& t, uint32_t& tri) const { uint2 v = base[k]; t = __uint_as_float(v.x); tri = v.y; }
-};
-// BVH copy in LDS; W = node width (2: GpuNode, 4: GpuNode4)
-template <int W>
-struct LdsBvh {
-    static constexpr int kWidth = W == 5 ? 4 : W; static constexpr bool kTwoLevel = false; static constexpr bool kLds = true;
-    const float4* nodes; const float4* tris;
-    HRT_DEV void node(int i, float4& a, float4& b, float4& c, float4& d) const { const float4* p = nodes + 4 * i; a = p[0]; b = p[1]; c = p[2]; d = p[3]; }
-    HRT_DEV void tri(uint32_t i, float4& a, float4& b, float4& c) const { const float4* p = tris + 3 * i; a = p[0]; b = p[1]; c = p[2]; }
-    // rows by 32-bit LDS address (the copy starts 128-byte aligned: setup_lds, so near ^ 16 is the far row of the same axis)
-    typedef __attribute__((address_space(3))) const char* LdsPtr;
-    HRT_DEV uint32_t rowoff(int i, uint32_t byteOffset) const { return (uint32_t)(uintptr_t)(LdsPtr) reinterpret_cast<const char*>(nodes) + (uint32_t)i * kLdsNode4Stride + byteOffset; }
-    HRT_DEV float4 load(uint32_t off) const { return *reinterpret_cast<const float4*>((const char*)(LdsPtr)(uintptr_t)off); }
-};
-template <int W> struct GlobalBvhOf;
-template <> struct GlobalBvhOf<2> { using type = GlobalBvh; static HRT_DEV GlobalBvh make(const SceneView& s) { GlobalBvh g; g.nodes = s.nodes; g.tris = s.tris; return g; } };
-constexpr int kTwoLevelTree = 44;     // GlobalBvhOf key of the two-level structure (4-wide nodes)
-template <> struct GlobalBvhOf<kTwoLevelTree> { using type = GlobalBvhTl; static HRT_DEV GlobalBvhTl make(const SceneView& s) { GlobalBvhTl g; g.nodes = s.nodes4; g.tris = s.tris; g.instances = s.instances; return g; } };
-template <> struct GlobalBvhOf<4> { using type = GlobalBvh4; static HRT_DEV GlobalBvh4 make(const SceneView& s) { GlobalBvh4 g; g.nodes = s.nodes4; g.tris = s.tris; return g; } };
-constexpr int kQuantisedTree = 5;     // template width code of the 4-wide tree through its 64-byte quantised nodes (global memory only; pt_device.h GpuNodeQ)
-template <> struct GlobalBvhOf<kQuantisedTree> { using type = GlobalBvhQ; static HRT_DEV GlobalBvhQ make(const SceneView& s) { GlobalBvhQ g; g.nodes = s.nodesQ; g.tris = s.tris; return g; } };
-
-// Carves dynamic LDS: [stack: min(DEPTH, 32)*kBlock ints][bvh copy]; copies the BVH when LDS_BVH.
-template <bool LDS_BVH, int DEPTH, int W, int LDSMAX>
-HRT_DEV void setup_lds(char* smem, const SceneView& s, LdsStack<DEPTH, LDSMAX>& stack, LdsBvh<W>& lbvh, size_t extraBytes = 0)
-{
-    stack.base = reinterpret_cast<int32_t*>(smem) + threadIdx.x;
-    stack.spill = nullptr; stack.spillStride = 0;
-    if (LDS_BVH) {
-        float4* dst = reinterpret_cast<float4*>(smem + (size_t)LdsStack<DEPTH, LDSMAX>::kRows * kBlock * 4 + extraBytes);
-        const float4* srcN = W == 2 ? reinterpret_cast<const float4*>(s.nodes) : reinterpret_cast<const float4*>(s.nodes4);
-        const float4* srcT = reinterpret_cast<const float4*>(s.tris);
-        uint32_t nN = W == 2 ? s.nodeCount * 4 : s.node4Count * 8, nT = s.triCount * 3;
-        uint32_t nNdst = nN;                                   // float4s the node copy occupies
-        if (W == 2 || kLdsNode4Stride == 128u) { for (uint32_t i = threadIdx.x; i < nN; i += kBlock) dst[i] = srcN[i]; }
-        else { nNdst = s.node4Count * (kLdsNode4Stride / 16u); for (uint32_t i = threadIdx.x; i < nN; i += kBlock) dst[(i >> 3) * (kLdsNode4Stride / 16u) + (i & 7u)] = srcN[i]; }
-        for (uint32_t i = threadIdx.x; i < nT; i += kBlock) dst[nNdst + i] = srcT[i];
-        lbvh.nodes = dst; lbvh.tris = dst + nNdst;
-        __syncthreads();
-    }
-}
-
-HRT_DEV uint32_t lane_id() { return threadIdx.x & 63u; }
-// A value every lane of the wave holds identically (segment cursors, counts read from memory, the wave's index), moved to a scalar
-// register: the compiler cannot prove uniformity of anything derived from threadIdx or from a load, and would otherwise keep such cursors
-// in VGPRs and turn every test on them into an exec-mask branch.
-HRT_DEV uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-HRT_DEV uint32_t prefix_rank(unsigned long long mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u)); }
-
-HRT_DEV unsigned long long wave_sum_u32(unsigned int v)
-{
-    unsigned long long x = v;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-// Statistics: one atomic per BLOCK on a counter shard (a returning-free add per wave on one word costs ~11 ns each and
-// serialises at the kernel tail: 8192 waves = ~0.1 ms per launch).
-HRT_DEV void block_count_add(unsigned long long* counterField0, size_t fieldOffsetWords, unsigned int perLane)
-{
-    __shared__ unsigned long long partial[kBlock / 64];
-    unsigned long long w = wave_sum_u32(perLane);
-    if (lane_id() == 0) partial[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (uint32_t i = 0; i < kBlock / 64; ++i) t += partial[i];
-        if (t) atomicAdd(counterField0 + (size_t)(blockIdx.x % kCounterShards) * (sizeof(DeviceCounters) / 8) + fieldOffsetWords, t);
-    }
-}
-// The same for N wave-uniform counts (each wave passes its own totals; fields = word indices into DeviceCounters).
-template <int N>
-HRT_DEV void block_count_add_uniform(DeviceCounters* counters, const int (&fields)[N], const unsigned int (&perWave)[N])
-{
-    __shared__ unsigned int partialU[N][kBlock / 64];
-    if (lane_id() == 0)
-        for (int k = 0; k < N; ++k) partialU[k][threadIdx.x >> 6] = perWave[k];
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)N) {
-        unsigned long long t = 0;
-        for (uint32_t i = 0; i < kBlock / 64; ++i) t += partialU[threadIdx.x][i];
-        if (t) atomicAdd(reinterpret_cast<unsigned long long*>(counters + blockIdx.x % kCounterShards) + fields[threadIdx.x], t);
-    }
-}
-
-// PrimaryArgs into the queue pool (the kernels index its jitter table per lane: a by-value kernel argument would be copied to scratch for that)
-__global__ void wf_store_primary(PrimaryArgs pr, PrimaryArgs* dst)
-{
-    if (threadIdx.x < 16) dst->clipToWorld[threadIdx.x] = pr.clipToWorld[threadIdx.x];
-    if (threadIdx.x < 3) dst->cam[threadIdx.x] = pr.cam[threadIdx.x];
-    if (threadIdx.x == 0) { dst->invW = pr.invW; dst->invH = pr.invH; dst->accumIndex = pr.accumIndex; }
-    if (threadIdx.x < kMaxSppPerBatch) dst->j[threadIdx.x] = pr.j[threadIdx.x];
-}
-
-// ------------------------------------------------------------------ raygen
-__global__ __launch_bounds__(kBlock) void wf_raygen(WfArgs a, HrptPathTracerConstants cb, JitterTable jt)
-{
-    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    unsigned int nPaths = 0;
-    for (uint32_t seg = gw; seg < a.numSegments; seg += totalWaves) {
-        uint32_t segBase = seg * a.segSize, outCount = 0;
-        for (uint32_t base = 0; base < a.segSize; base += 64) {
-            uint32_t smp = segBase + base + lane;
-            const bool mine = base + lane < a.segSize && smp < a.numSamples;      // (a segment need not be a multiple of 64 samples)
-            bool active = mine;
-            uint32_t k = 0, px = 0, py = 0;
-            if (active) {
-                k = smp / a.pixelsPadded;
-                uint32_t p = smp - k * a.pixelsPadded;
-                uint32_t tile = p >> 6, within = p & 63u;
-                uint32_t tcol, trow; tile_position(a, tile, tcol, trow);
-                px = a.rect.column_x(tcol) + (within & 7u);
-                py = a.rect.y0 + trow * 8u + (within >> 3);
-                active = px < a.rect.x1 && py < a.rect.y1;
-            }
-            if (mine) a.b.radiance[smp] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            unsigned long long m = __ballot(active);
-            if (active) {
-                PathState ps;
-                {
-                    // init_path (pt_path.h) with the jitter / RNG stream of accumulation index first+k (PathTracerRenderer.cpp:62,:65)
-                    float u = (((float)px + 0.5f) + jt.j[k].x) * cb.m_View.m_ViewportSizeInv[0];
-                    float v = (((float)py + 0.5f) + jt.j[k].y) * cb.m_View.m_ViewportSizeInv[1];
-                    float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;
-                    const float* M = cb.m_View.m_MatClipToWorldNoOffset;
-                    float ex = ((cx * M[0] + cy * M[4]) + 0.9f * M[8]) + 1.0f * M[12];
-                    float ey = ((cx * M[1] + cy * M[5]) + 0.9f * M[9]) + 1.0f * M[13];
-                    float ez = ((cx * M[2] + cy * M[6]) + 0.9f * M[10]) + 1.0f * M[14];
-                    float ew = ((cx * M[3] + cy * M[7]) + 0.9f * M[11]) + 1.0f * M[15];
-                    f3 end = mk3(ex / ew, ey / ew, ez / ew);
-                    ps.ray.o = mk3(cb.m_CameraPos[0], cb.m_CameraPos[1], cb.m_CameraPos[2]);
-                    ps.ray.d = normalize(end - ps.ray.o);
-                    ps.rng = hrt_rng_seed(px, py, cb.m_AccumulationIndex + k);
-                }
-                uint32_t o = segBase + outCount + prefix_rank(m);
-                a.b.rayO[0][o] = make_float4(ps.ray.o.x, ps.ray.o.y, ps.ray.o.z, 0.0f);
-                a.b.rayD[0][o] = make_float4(ps.ray.d.x, ps.ray.d.y, ps.ray.d.z, __uint_as_float(ps.rng));
-                a.b.thr[0][o] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(smp));
-                if (a.hasMedium) {
-                    a.b.med0[0][o] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-                    a.b.med1[0][o] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                }
-                ++nPaths;
-            }
-            outCount += (uint32_t)__popcll(m);
-        }
-        if (lane == 0) a.b.pathCnt[0][seg] = outCount;
-    }
-    block_count_add(&a.counters->closestRays, 2, nPaths);
-}
-
-// ------------------------------------------------------------------ extend (closest hit)
-// Persistent while-while traversal with lane refill: a wave keeps up to 64 rays of its segment in flight; whenever
-// at least kRefillMin lanes have finished their ray, they fetch the next rays of the segment (ballot + prefix rank),
-// so the traversal loop runs with full lanes instead of waiting for the slowest ray of a 64-ray batch.
-// Waves per SIMD the kernels are compiled for (amdgpu_waves_per_eu; measured on MI355X, built without the SLP vectoriser -- csrc/Makefile):
-//   wf_extend, tree in LDS      6   80 VGPRs without spills; the <PRIMARY> instantiation gives up 10 registers for it (-1.5 %)
-//   wf_extend, tree in global   6   80-82 VGPRs since nodes and triangles are addressed by 32-bit offsets (84 and +2 % at 6 waves before): config 4 -2 %
-//   wf_extend<TL>               5   100-117 VGPRs: a few spilled registers buy the fifth wave (-4 %); with the SLP vectoriser on the same
-//                                   setting doubled the kernel's time (128 VGPRs wanted)
-//   wf_shade, any variant       4   general single-light variant: 121-129 VGPRs wanted, -14 % against 3 waves. The same setting produced wrong sky
-//                                   radiance while the SLP vectoriser was on (138 VGPRs wanted). Root cause (round 3, profiles/r03_wrong_sky_isa_evidence.txt):
-//                                   a backend bug under register pressure -- the hoisted constant of mie_phase was kept alive through a live-range-split
-//                                   copy placed in ONE arm of a divergent if/else, so the lanes of the other arm restored garbage. The guards: the random
-//                                   trait scenes of the GPU suite (seed 1 fails on that build) and tests/test_kernel_resources.py (no scratch, <= 128
-//                                   VGPRs). Re-check both whenever this kernel, the flags or the compiler change. 5 waves on <SIMPLE>: no gain
-constexpr int kWavesExtendLds = 6, kWavesExtendGlobal = 6, kWavesExtendTwoLevel = 5, kWavesShade = 4;
-#ifndef HRPT_WAVES_EXTEND_LDS_OPAQUE
-#define HRPT_WAVES_EXTEND_LDS_OPAQUE 6
-#endif
-constexpr int kWavesExtendLdsOpaque = HRPT_WAVES_EXTEND_LDS_OPAQUE;
-static_assert(sizeof(GpuTriAttr) == kTriAttrBytes && sizeof(GpuInstShade) == kInstShadeBytes && sizeof(HrptMaterialConstants) == kMaterialBytes, "pt_wavefront_plan.h shade_table_bytes");
-constexpr uint32_t kNoPathRecord = 0xFFFFFFFEu;     // hit-record code of a slot without a path (wf_extend<PRIMARY>; 0xFFFFFFFF = miss)
-
-// ANYHIT: the same persistent loop over the shadow-ray queue (sqO / sqD / sqId, sqCnt rays per segment): the first hit on an opaque
-// triangle ends the ray (kVisBlocked); otherwise the ray is clear or, if it crossed non-opaque triangles, left to wf_shadow's candidate
-// pass (kVisCandidates). Shadow rays get the lane refill closest-hit rays have: 3.8 -> 8 Grays/s on the glass config.
-// TL: the two-level structure of instanced scenes (pt_device.h "two-level traversal"): tree in global memory, closest hits only, every
-// instance opaque; the hit's instance goes to its own stream (hitInst) next to the hit record.
-// PRIMARY: bounce 0 of a batch without a raygen pass (WfArgs::primary): the refill derives the ray from the sample index. A separate instantiation:
-// as a run-time branch the extra live state cost the kernel 6 VGPRs and 3 % on EVERY bounce.
-// TL: 0 flat tree, 1 two-level structure with ForceOpaque instances only, 2 two-level with non-opaque instances (candidate re-trace compiled in)
-// OPQ: no instance of the scene is ForceNonOpaque (closest-hit launches of the flat structure): the candidate rules of TraceRayStandard (lower
-// bound of a re-trace, stochastic-alpha draws) are compiled out -- every hit is committed.
-template <bool LDS_BVH, int DEPTH, int W, bool ANYHIT, int TL = 0, bool PRIMARY = false, bool OPQ = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TL ? kWavesExtendTwoLevel : (LDS_BVH ? (OPQ ? kWavesExtendLdsOpaque : kWavesExtendLds) : kWavesExtendGlobal)))) void wf_extend(WfArgs a, uint32_t parity)
-{
-    static_assert(!OPQ || (!ANYHIT && !TL), "OPQ: closest hits over the flat structure");
-    static_assert(!TL || (!LDS_BVH && !ANYHIT && W == 4), "two-level traversal: global 4-wide tree, closest hit");
-    static_assert(!PRIMARY || !ANYHIT, "primary rays are closest-hit rays");
-    static_assert(W != kQuantisedTree || (!LDS_BVH && !TL), "quantised nodes: flat tree in global memory");
-    extern __shared__ __attribute__((aligned(128))) char smem[];
-    LdsStack<DEPTH, kExtendLdsStack> stack; LdsBvh<W> lbvh;
-    constexpr size_t candBytes = ANYHIT ? (size_t)kShadowCandidates * 2 * kBlock * 4 : 0;
-    setup_lds<LDS_BVH, DEPTH, W>(smem, a.scene, stack, lbvh, candBytes);
-    LdsCandidates cand; cand.base = reinterpret_cast<int32_t*>(smem + (size_t)LdsStack<DEPTH, kExtendLdsStack>::kRows * kBlock * 4) + threadIdx.x;
-    if (DEPTH > kExtendLdsStack) { stack.spill = a.spill[ANYHIT ? 1 : 0] + blockIdx.x * kBlock + threadIdx.x; stack.spillStride = gridDim.x * kBlock; }
-    typename GlobalBvhOf<(TL ? kTwoLevelTree : W)>::type gbvh = GlobalBvhOf<(TL ? kTwoLevelTree : W)>::make(a.scene);
-    const SceneView& s = a.scene;
-
-    const uint32_t wavesPerBlock = kBlock / 64;
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    const float4* __restrict__ rayO = ANYHIT ? a.b.sqO : a.b.rayO[parity];
-    float4* __restrict__ rayD = ANYHIT ? a.b.sqD : a.b.rayD[parity];
-    const uint32_t* __restrict__ segCount = ANYHIT ? a.b.sqCnt : a.b.pathCnt[parity];
-    const uint32_t slotsPerSample = ANYHIT ? a.maxLights : 1u;
-    unsigned int nRays = 0;
-    const bool emptyScene = s.nodeCount == 0 && s.rootLeaf == 0;
-
-    // The wave streams through its segments (gw, gw + totalWaves, ...) without draining between them: when one segment has been
-    // handed out completely the idle lanes refill from the next one, so only the very end of the wave's work runs with few lanes.
-    {
-        uint32_t seg = gw, cnt = 0, segBase = 0, next = 0;      // wave-uniform cursor: next ray of the current segment to hand out
-        bool haveSeg = false;
-        auto open_segment = [&]() {                             // first non-empty segment at or after `seg`
-            haveSeg = false; cnt = 0; next = 0;
-            for (; seg < a.numSegments; seg += totalWaves) {
-                cnt = uniform(PRIMARY ? path_count(a, 0u, seg) : segCount[seg]);
-                if (cnt) { segBase = (seg * a.segSize) * slotsPerSample; haveSeg = true; break; }
-            }
-        };
-        open_segment();
-        // per-lane traversal state
-        bool active = false;
-        Ray r; r.o = mk3(0.0f, 0.0f, 0.0f); r.d = mk3(0.0f, 0.0f, 1.0f); r.tmin = 0.0f; r.tmax = 1e10f;
-        RayShear sh = make_shear(r.d); f3 inv = mk3(0.0f, 0.0f, 0.0f), noi = mk3(0.0f, 0.0f, 0.0f);
-        TlCull tl; tl.inv = inv; tl.noi = noi; tl.noiF = noi; tl.inst = -1;      // TL only (dead otherwise)
-        HitKey lower; lower.have = false; lower.t = 0.0f; lower.inst = 0; lower.prim = 0;
-        Hit best; best.valid = false; best.t = 0.0f; best.inst = 0; best.prim = 0; best.u = 0.0f; best.v = 0.0f; best.opaque = 0; best.tri = 0;
-        int32_t cur = kTraversalDone; int sp = 0; uint32_t slot = 0, rng = 0, rng0 = 0; float tlim = 0.0f;
-        bool blocked = false, candOverflow = false; int candCount = 0;
-        for (;;) {
-            if (haveSeg && next >= cnt && (a.streamSegments || __ballot(active) == 0ull)) { seg += totalWaves; open_segment(); }
-            // ---- refill idle lanes
-            unsigned long long mIdle = __ballot(!active);
-            uint32_t nIdle = (uint32_t)__popcll(mIdle);
-            if (active) HRT_PHASE(ANYHIT ? PH_ANY_ITER : PH_EXT_ITER);
-            if (haveSeg && (nIdle >= a.refillMin || nIdle == 64u)) {
-                const uint32_t idx = next + prefix_rank(mIdle);
-                bool take = !active && idx < cnt;
-                if constexpr (PRIMARY) {                // bounce 0, rays from the sample index (false: padding pixel of an 8 x 8 tile)
-                    if (take) {
-                        slot = segBase + idx; take = primary_ray(a, *a.primaryArgs, slot, r.o, r.d, rng); r.tmin = 0.0f; r.tmax = 1e10f; rng0 = rng;
-                        if (take) rayD[slot] = make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(rng));      // for wf_shade(0) / wf_shadow(0): direction + RNG seed
-                        else a.b.hit[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kNoPathRecord));   // padding pixel of an 8 x 8 tile: wf_shade skips the slot
-                    }
-                }
-                if (take) {
-                    HRT_PHASE(ANYHIT ? PH_ANY_REFILL : PH_EXT_REFILL);
-                    if constexpr (!PRIMARY) {
-                        slot = segBase + idx;
-                        float4 o = rayO[slot], d = rayD[slot];
-                        r.o = mk3(o.x, o.y, o.z); r.d = mk3(d.x, d.y, d.z); r.tmin = o.w; r.tmax = ANYHIT ? d.w : 1e10f;
-                        rng = __float_as_uint(d.w); rng0 = rng;
-                    }
-                    blocked = false; candOverflow = false; candCount = 0;
-                    lower.have = false;
-                    best.valid = false; tlim = r.tmax; sp = 0;
-                    bool finite = (r.d.x == r.d.x && r.d.y == r.d.y && r.d.z == r.d.z);
-                    sh = make_shear(r.d);
-                    if constexpr (TL) tl_world(tl, r); else { inv = traversal_rcp(r.d); noi = slab_origin_term(r.o, inv); }
-                    cur = (emptyScene || !finite) ? kTraversalDone : (s.nodeCount == 0 ? s.rootLeaf : 0);
-                    active = true; ++nRays;
-                }
-                next += nIdle;
-            }
-            if (__ballot(active) == 0ull) { if (haveSeg) continue; break; }
-            if (active) {
-                // ---- descend inner nodes until this lane holds a leaf (or its stack ran out)
-                // (the descent is cut short once fewer than nodeLoopMin lanes are still at inner nodes: the rest of the wave holds leaves and
-                // would only wait; the lanes cut off keep their node and go on in the next round. Thresholded while-while.)
-                if constexpr (TL) {
-                    while (cur >= 0 && cur != kExitBlas) {
-                        cur = inner_step(gbvh, cur, tl.noi, tl.noiF, tl.inv, r.tmin, tlim, stack, sp);
-                        if ((uint32_t)__popcll(__ballot(cur >= 0 && cur != kExitBlas)) < a.nodeLoopMin) break;
-                    }
-                    // leaving an instance / entering one: the lane continues with the next tree in the next round
-                    if (cur == kExitBlas || (cur < 0 && cur != kTraversalDone && tl.inst < 0)) cur = tl_switch(gbvh, cur, tl, r, stack, sp);
-                    else if (cur < 0 && cur != kTraversalDone) {
-                        const GpuInstance& I = s.instances[tl.inst];
-                        const uint32_t enc = (uint32_t)(~cur), first = enc >> 2, count = (enc & 3u) + 1u;
-                        const uint32_t inst = (uint32_t)tl.inst, iflags = I.flags & 7u;
-                        for (uint32_t i = 0; i < count; ++i) {
-                            float4 ta, tb, tc; gbvh.tri(first + i, ta, tb, tc);
-                            f3 p0, p1, p2; tl_world_triangle(I, ta, tb, tc, p0, p1, p2);
-                            float t, u, v;
-                            const bool hitTri = tri_test(p0, p1, p2, r, sh, t, u, v);
-                            const uint32_t prim = __float_as_uint(tb.w);
-                            // Written as selects on one flag (every closest-hit loop of the library is). As `if (take) { best.t = t; ... }` this loop was
-                            // compiled (ROCm 7.2, gfx950) to code that, on a tie in t won by (instance, primitive), took the new key but kept the OLD
-                            // barycentrics: hits on an edge shared by two triangles then shaded with the other triangle's (u, v).
-                            // tests/test_two_level_gpu.py::test_two_level_full_frame holds such a pixel; the select form is also 1 % faster.
-                            const bool ok = TL != 2 || !lower.have || key_less(lower.t, lower.inst, lower.prim, t, inst, prim);       // behind a rejected non-opaque candidate
-                            const bool take = hitTri && ok && (!best.valid || key_less(t, inst, prim, best.t, best.inst, best.prim));
-                            best.t = take ? t : best.t; best.u = take ? u : best.u; best.v = take ? v : best.v;
-                            best.inst = take ? inst : best.inst; best.prim = take ? prim : best.prim; best.tri = take ? first + i : best.tri;
-                            best.opaque = take ? iflags : best.opaque;
-                            best.valid = best.valid || take;
-                            tlim = take ? t : tlim;
-                        }
-                        cur = stack.pop(--sp);      // the exit marker is below every entry pushed inside an instance
-                    }
-                } else {
-                while (cur >= 0) {
-                    HRT_PHASE(ANYHIT ? PH_ANY_NODE : PH_EXT_NODE);
-                    if (LDS_BVH) cur = inner_step(lbvh, cur, noi, inv, r.tmin, tlim, stack, sp);
-                    else cur = inner_step(gbvh, cur, noi, inv, r.tmin, tlim, stack, sp);
-                    if ((uint32_t)__popcll(__ballot(cur >= 0)) < a.nodeLoopMin) break;
-                }
-                }
-                // ---- intersect the leaf
-                if (!TL && cur < 0 && cur != kTraversalDone) {
-                    uint32_t enc = (uint32_t)(~cur);
-                    uint32_t first = enc >> 2, count = (enc & 3u) + 1u;
-                    HRT_PHASE(ANYHIT ? PH_ANY_LEAF : PH_EXT_LEAF);
-                    for (uint32_t i = 0; i < count; ++i) {
-                        HRT_PHASE(ANYHIT ? PH_ANY_TRI : PH_EXT_TRI);
-                        float4 ta, tb, tc;
-                        if (LDS_BVH) lbvh.tri(first + i, ta, tb, tc); else gbvh.tri(first + i, ta, tb, tc);
-                        float t, u, v;
-                        if (tri_test(mk3(ta.x, ta.y, ta.z), mk3(tb.x, tb.y, tb.z), mk3(tc.x, tc.y, tc.z), r, sh, t, u, v)) {
-                            if (ANYHIT) {
-                                if (__float_as_uint(tc.w) & 1u) { blocked = true; break; }     // opaque instance: committed, whatever lies in front of it
-                                if (LDS_BVH) candidate_insert<kShadowCandidates>(lbvh, cand, candCount, candOverflow, t, first + i, __float_as_uint(ta.w), __float_as_uint(tb.w));
-                                else candidate_insert<kShadowCandidates>(gbvh, cand, candCount, candOverflow, t, first + i, __float_as_uint(ta.w), __float_as_uint(tb.w));
-                                continue;
-                            }
-                            uint32_t inst = __float_as_uint(ta.w), prim = __float_as_uint(tb.w);
-                            const bool ok = OPQ || !lower.have || key_less(lower.t, lower.inst, lower.prim, t, inst, prim);
-                            const bool take = ok && (!best.valid || key_less(t, inst, prim, best.t, best.inst, best.prim));      // selects: see the two-level loop above
-                            best.t = take ? t : best.t; best.u = take ? u : best.u; best.v = take ? v : best.v;
-                            best.inst = take ? inst : best.inst; best.prim = take ? prim : best.prim; best.tri = take ? first + i : best.tri;
-                            best.opaque = take ? (__float_as_uint(tc.w) & 7u) : best.opaque;     // bit 0 opaque, bits 1-2 shading class
-                            best.valid = best.valid || take;
-                            tlim = take ? t : tlim;
-                        }
-                    }
-                    cur = (blocked || sp == 0) ? kTraversalDone : stack.pop(--sp);
-                }
-                // ---- traversal finished: candidate resolution (TraceRayStandard) and hit record
-                if (ANYHIT) {
-                    if (cur == kTraversalDone) {
-                        HRT_PHASE(PH_ANY_FINISH);
-                        const uint32_t id = a.b.sqId[slot];
-                        uint32_t code = blocked ? kVisBlocked : kVisClear;
-                        if (!blocked && candCount > 0) {
-                            uint2* out = a.b.sqCand + (size_t)id * kShadowCandidates;
-                            for (int k = 0; k < candCount; ++k) { float ct; uint32_t ctri; cand.key(k, ct, ctri); out[k] = make_uint2(__float_as_uint(ct), ctri); }
-                            code = kVisCandidates | ((uint32_t)candCount << 8) | (candOverflow ? 1u << 16 : 0u);
-                        }
-                        a.b.shVis[id] = code;
-                        active = false;
-                    }
-                } else if (cur == kTraversalDone) {
-                    bool done = true;
-                    HRT_PHASE(PH_EXT_FINISH);
-                    if (!OPQ && TL != 1 && best.valid && !(best.opaque & 1u)) HRT_PHASE(PH_EXT_CANDIDATE);
-                    if (!OPQ && TL != 1 && best.valid && !(best.opaque & 1u) && !candidate_commits(s, best, rng)) {
-                        // rejected non-opaque candidate: it becomes the exclusive lower bound of a new closest-hit query
-                        lower.have = true; lower.t = best.t; lower.inst = best.inst; lower.prim = best.prim;
-                        best.valid = false; tlim = r.tmax; sp = 0;
-                        cur = s.nodeCount == 0 ? s.rootLeaf : 0;
-                        if constexpr (TL) tl_world(tl, r);
-                        done = false;
-                    }
-                    if (done) {
-                        if (!OPQ && a.hasStochasticAlpha && rng != rng0) { float4 d = rayD[slot]; d.w = __uint_as_float(rng); rayD[slot] = d; }
-                        // hit record: triangle (< 2^29: leaf references hold first << 2) | shading class << 29; 0xFFFFFFFF = miss
-                        a.b.hit[slot] = make_float4(best.t, best.u, best.v, __uint_as_float(best.valid ? (best.tri | ((best.opaque >> 1) << 29)) : 0xFFFFFFFFu));
-                        if constexpr (TL) a.b.hitInst[slot] = best.inst;
-                        active = false;
-                    }
-                }
-            }
-        }
-    }
-    if (!ANYHIT) block_count_add(&a.counters->closestRays, 0, nRays);      // shadow rays are counted by wf_shadow
-    if (PRIMARY) { __syncthreads(); block_count_add(&a.counters->closestRays, 2, nRays); }      // ... and the paths wf_raygen would have counted
-}
-
-// ------------------------------------------------------------------ stand-alone ray queries (hrpt_trace_rays) through the same persistent loop
-// TraceRayStandard (RaytracingCommon.hlsli:138-198) / CalculateRTShadow<true> (CommonLighting.hlsli:380-496) for the reference's other inline-RT
-// passes (DDGI ProbeTraceCS.hlsl:60-61,108-109, RT shadows, BrdfRayTracing.hlsl:138-140): a caller's array of HrptRay instead of the path queue,
-// HrptRayHit records instead of hit records. A wave owns chunks of 256 consecutive rays and refills idle lanes exactly like wf_extend; the
-// thread-per-ray kernel of round 1 (pt_megakernel.hip) was 1.8x slower on the same rays. SHADOW: the any-hit traversal gathers the non-opaque
-// triangles a ray crosses in per-lane LDS columns; when the ray ends unblocked they are resolved front to back right there.
-struct WfTraceArgs {
-    SceneView scene; const HrptRay* rays; HrptRayHit* hits; uint64_t count;
-    int32_t* spill; uint32_t refillMin, nodeLoopMin;
-    bool quantised;         // host-side only: the launch picks the instantiation that walks SceneView::nodesQ
-};
-constexpr uint32_t kTraceChunkShift = 8;
-template <bool LDS_BVH, int DEPTH, int W, bool SHADOW, bool TL = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHADOW ? 1 : (TL ? kWavesExtendTwoLevel : (LDS_BVH ? kWavesExtendLds : kWavesExtendGlobal))))) void wf_trace_rays(WfTraceArgs a)
-{
-    static_assert(!TL || (!LDS_BVH && W == 4), "two-level structure: global 4-wide trees (every instance opaque: a shadow ray ends at its first hit)");
-    static_assert(W != kQuantisedTree || (!LDS_BVH && !TL), "quantised nodes: flat tree in global memory");
-    extern __shared__ __attribute__((aligned(128))) char smem[];
-    LdsStack<DEPTH, kExtendLdsStack> stack; LdsBvh<W> lbvh;
-    constexpr size_t candBytes = SHADOW ? (size_t)kShadowCandidates * 2 * kBlock * 4 : 0;
-    setup_lds<LDS_BVH, DEPTH, W>(smem, a.scene, stack, lbvh, candBytes);
-    LdsCandidates cand; cand.base = reinterpret_cast<int32_t*>(smem + (size_t)LdsStack<DEPTH, kExtendLdsStack>::kRows * kBlock * 4) + threadIdx.x;
-    if (DEPTH > kExtendLdsStack) { stack.spill = a.spill + blockIdx.x * kBlock + threadIdx.x; stack.spillStride = gridDim.x * kBlock; }
-    typename GlobalBvhOf<(TL ? kTwoLevelTree : W)>::type gbvh = GlobalBvhOf<(TL ? kTwoLevelTree : W)>::make(a.scene);
-    const SceneView& s = a.scene;
-    const uint32_t wavesPerBlock = kBlock / 64;
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    TlCull tl; tl.inv = mk3(0.0f, 0.0f, 0.0f); tl.noi = tl.inv; tl.noiF = tl.inv; tl.inst = -1;      // TL only
-    const uint64_t numChunks = (a.count + (1u << kTraceChunkShift) - 1) >> kTraceChunkShift;
-    const bool emptyScene = s.nodeCount == 0 && s.rootLeaf == 0;
-
-    uint64_t chunk = gw; uint32_t cnt = 0, next = 0; uint64_t chunkBase = 0; bool haveChunk = false;
-    auto open_chunk = [&]() {
-        haveChunk = chunk < numChunks; next = 0;
-        if (haveChunk) { chunkBase = chunk << kTraceChunkShift; const uint64_t left = a.count - chunkBase; cnt = left < (1u << kTraceChunkShift) ? (uint32_t)left : (1u << kTraceChunkShift); }
-    };
-    open_chunk();
-    bool active = false;
-    Ray r; r.o = mk3(0.0f, 0.0f, 0.0f); r.d = mk3(0.0f, 0.0f, 1.0f); r.tmin = 0.0f; r.tmax = 1e10f;
-    RayShear sh = make_shear(r.d); f3 inv = mk3(0.0f, 0.0f, 0.0f), noi = mk3(0.0f, 0.0f, 0.0f);
-    HitKey lower; lower.have = false; lower.t = 0.0f; lower.inst = 0; lower.prim = 0;
-    Hit best; best.valid = false; best.t = 0.0f; best.inst = 0; best.prim = 0; best.u = 0.0f; best.v = 0.0f; best.opaque = 0; best.tri = 0;
-    int32_t cur = kTraversalDone; int sp = 0; uint64_t slot = 0; uint32_t rng = 0; float tlim = 0.0f;
-    bool blocked = false, candOverflow = false, finite = true; int candCount = 0;
-    for (;;) {
-        if (haveChunk && next >= cnt) { chunk += totalWaves; open_chunk(); }
-        const unsigned long long mIdle = __ballot(!active);
-        const uint32_t nIdle = (uint32_t)__popcll(mIdle);
-        if (haveChunk && (nIdle >= a.refillMin || nIdle == 64u)) {
-            const uint32_t idx = next + prefix_rank(mIdle);
-            if (!active && idx < cnt) {
-                slot = chunkBase + idx;
-                const float4* rp = reinterpret_cast<const float4*>(a.rays + slot);           // 48-byte records: three 16-byte loads
-                const float4 q0 = rp[0], q1 = rp[1]; const uint32_t rr = reinterpret_cast<const uint32_t*>(rp + 2)[0];
-                const f3 o = mk3(q0.x, q0.y, q0.z), d = mk3(q1.x, q1.y, q1.z);
-                finite = all_finite(o, d);
-                if (SHADOW) r = shadow_ray(o, d, q1.w);                                        // the query applies its own bias; tmax = distance to the light
-                else { r.o = o; r.d = d; r.tmin = q0.w; r.tmax = q1.w; }
-                rng = rr; blocked = false; candOverflow = false; candCount = 0; lower.have = false; best.valid = false; tlim = r.tmax; sp = 0;
-                sh = make_shear(r.d);
-                if constexpr (TL) tl_world(tl, r); else { inv = traversal_rcp(r.d); noi = slab_origin_term(r.o, inv); }
-                cur = (emptyScene || !finite) ? kTraversalDone : (s.nodeCount == 0 ? s.rootLeaf : 0);
-                active = true;
-            }
-            next += nIdle;
-        }
-        if (__ballot(active) == 0ull) { if (haveChunk) continue; break; }
-        if (active) {
-            if constexpr (TL) {
-                while (cur >= 0 && cur != kExitBlas) {
-                    cur = inner_step(gbvh, cur, tl.noi, tl.noiF, tl.inv, r.tmin, tlim, stack, sp);
-                    if ((uint32_t)__popcll(__ballot(cur >= 0 && cur != kExitBlas)) < a.nodeLoopMin) break;
-                }
-                if (cur == kExitBlas || (cur < 0 && cur != kTraversalDone && tl.inst < 0)) cur = tl_switch(gbvh, cur, tl, r, stack, sp);
-                else if (cur < 0 && cur != kTraversalDone) {
-                    const GpuInstance& I = s.instances[tl.inst];
-                    const uint32_t enc = (uint32_t)(~cur), first = enc >> 2, count = (enc & 3u) + 1u, inst = (uint32_t)tl.inst;
-                    for (uint32_t i = 0; i < count; ++i) {
-                        float4 ta, tb, tc; gbvh.tri(first + i, ta, tb, tc);
-                        f3 p0, p1, p2; tl_world_triangle(I, ta, tb, tc, p0, p1, p2);
-                        float t, u, v;
-                        const bool hitTri = tri_test(p0, p1, p2, r, sh, t, u, v);
-                        if (SHADOW) { if (hitTri) { if (I.flags & 1u) { blocked = true; break; } candCount = 1; } continue; }      // candCount: "crossed a non-opaque instance"
-                        const uint32_t prim = __float_as_uint(tb.w);
-                        const bool ok = !lower.have || key_less(lower.t, lower.inst, lower.prim, t, inst, prim);
-                        const bool take = hitTri && ok && (!best.valid || key_less(t, inst, prim, best.t, best.inst, best.prim));      // selects: see wf_extend<TL>
-                        best.t = take ? t : best.t; best.u = take ? u : best.u; best.v = take ? v : best.v;
-                        best.inst = take ? inst : best.inst; best.prim = take ? prim : best.prim; best.tri = take ? first + i : best.tri;
-                        best.valid = best.valid || take; best.opaque = take ? (I.flags & 1u) : best.opaque;
-                        tlim = take ? t : tlim;
-                    }
-                    cur = blocked ? kTraversalDone : stack.pop(--sp);
-                }
-            } else {
-            while (cur >= 0) {
-                if (LDS_BVH) cur = inner_step(lbvh, cur, noi, inv, r.tmin, tlim, stack, sp);
-                else cur = inner_step(gbvh, cur, noi, inv, r.tmin, tlim, stack, sp);
-                if ((uint32_t)__popcll(__ballot(cur >= 0)) < a.nodeLoopMin) break;
-            }
-            if (cur < 0 && cur != kTraversalDone) {
-                const uint32_t enc = (uint32_t)(~cur), first = enc >> 2, count = (enc & 3u) + 1u;
-                for (uint32_t i = 0; i < count; ++i) {
-                    float4 ta, tb, tc;
-                    if (LDS_BVH) lbvh.tri(first + i, ta, tb, tc); else gbvh.tri(first + i, ta, tb, tc);
-                    float t, u, v;
-                    if (tri_test(mk3(ta.x, ta.y, ta.z), mk3(tb.x, tb.y, tb.z), mk3(tc.x, tc.y, tc.z), r, sh, t, u, v)) {
-                        if (SHADOW) {
-                            if (__float_as_uint(tc.w) & 1u) { blocked = true; break; }
-                            if (LDS_BVH) candidate_insert<kShadowCandidates>(lbvh, cand, candCount, candOverflow, t, first + i, __float_as_uint(ta.w), __float_as_uint(tb.w));
-                            else candidate_insert<kShadowCandidates>(gbvh, cand, candCount, candOverflow, t, first + i, __float_as_uint(ta.w), __float_as_uint(tb.w));
-                            continue;
-                        }
-                        const uint32_t inst = __float_as_uint(ta.w), prim = __float_as_uint(tb.w);
-                        const bool ok = !lower.have || key_less(lower.t, lower.inst, lower.prim, t, inst, prim);
-                        const bool take = ok && (!best.valid || key_less(t, inst, prim, best.t, best.inst, best.prim));      // selects: see wf_extend
-                        best.t = take ? t : best.t; best.u = take ? u : best.u; best.v = take ? v : best.v;
-                        best.inst = take ? inst : best.inst; best.prim = take ? prim : best.prim; best.tri = take ? first + i : best.tri;
-                        best.opaque = take ? (__float_as_uint(tc.w) & 1u) : best.opaque;
-                        best.valid = best.valid || take;
-                        tlim = take ? t : tlim;
-                    }
-                }
-                cur = (blocked || sp == 0) ? kTraversalDone : stack.pop(--sp);
-            }
-            }
-            if (cur == kTraversalDone) {
-                HrptRayHit out; out.t = 0.0f; out.u = 0.0f; out.v = 0.0f; out.instance = 0; out.primitive = 0; out.hit = 0; out.rng = rng; out.pad = 0;
-                bool done = true;
-                if (SHADOW) {
-                    float vis = 1.0f;
-                    if (finite) {
-                        if (blocked) vis = 0.0f;
-                        else if (candCount > 0) {
-                            if constexpr (TL) vis = shadow_retrace_two_level(s, gbvh, r, stack);
-                            else if (LDS_BVH) vis = shadow_resolve_candidates(s, lbvh, r, sh, candCount, candOverflow, cand, stack);
-                            else vis = shadow_resolve_candidates(s, gbvh, r, sh, candCount, candOverflow, cand, stack);
-                        }
-                    }
-                    out.t = vis; out.hit = vis < 1.0f ? 1u : 0u;
-                } else if (best.valid && !best.opaque && !candidate_commits(s, best, rng)) {
-                    lower.have = true; lower.t = best.t; lower.inst = best.inst; lower.prim = best.prim;
-                    best.valid = false; tlim = r.tmax; sp = 0;
-                    cur = s.nodeCount == 0 ? s.rootLeaf : 0;
-                    if constexpr (TL) tl_world(tl, r);
-                    done = false;
-                } else if (best.valid) { out.t = best.t; out.u = best.u; out.v = best.v; out.instance = best.inst; out.primitive = best.prim; out.hit = 1u; out.rng = rng; }
-                if (done) {
-                    out.rng = rng;
-                    float4* hp = reinterpret_cast<float4*>(a.hits + slot);
-                    hp[0] = make_float4(out.t, out.u, out.v, __uint_as_float(out.instance));
-                    hp[1] = make_float4(__uint_as_float(out.primitive), __uint_as_float(out.hit), __uint_as_float(out.rng), 0.0f);
-                    active = false;
-                }
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------ shade (+ compaction, + NEE sample emission)
-template <int MAXL>
-struct NeeBuf { float ux[MAXL], uy[MAXL]; uint32_t light[MAXL]; };
-
-// Block-start copy of the three shading tables into LDS at `dst` (16-byte aligned), whole records in their global layout, all threads of the
-// block; the caller's __syncthreads() publishes it. Copied at every launch: material / instance updates and refits need no bookkeeping.
-HRT_DEV LdsShadeTables copy_shade_tables(char* dst, const WfArgs& a)
-{
-    const SceneView& s = a.scene;
-    const uint32_t nA = s.triCount * (uint32_t)(sizeof(GpuTriAttr) / 16), nI = a.shadeInstances * (uint32_t)(sizeof(GpuInstShade) / 16);
-    const uint32_t nM = a.shadeMaterials * (uint32_t)(sizeof(HrptMaterialConstants) / 4);
-    float4* const dA = reinterpret_cast<float4*>(dst); float4* const dI = dA + nA; uint32_t* const dM = reinterpret_cast<uint32_t*>(dI + nI);
-    const float4* const sA = reinterpret_cast<const float4*>(s.attrs); const float4* const sI = reinterpret_cast<const float4*>(s.instShade);
-    const uint32_t* const sM = reinterpret_cast<const uint32_t*>(s.materials);
-    for (uint32_t i = threadIdx.x; i < nA; i += kBlock) dA[i] = sA[i];
-    for (uint32_t i = threadIdx.x; i < nI; i += kBlock) dI[i] = sI[i];
-    for (uint32_t i = threadIdx.x; i < nM; i += kBlock) dM[i] = sM[i];
-    LdsShadeTables t;
-    t.attrs = (uint32_t)(uintptr_t)(LdsShadeTables::LdsPtr)dst; t.instShade = t.attrs + nA * 16u; t.materials = t.instShade + nI * 16u;
-    return t;
-}
-
-
-// One 64-lane iteration of the shading stream: the body of wf_shade / wf_shade_lt (fed from the path queue and the hit records by shade_paths)
-// and of wf_bounce0 (fed from the registers of its own trace). The feeder names the lanes and their records (ShadeLane) and the one or two
-// segments they belong to -- lanes `inA` to segment A at queue offset baseA, whose output counters are w.outCount / w.shCount, the others to
-// segment B at baseB, which this iteration opens (outCountB / shCountB) -- and says whether segment A ends with this iteration (endsA: whatever
-// is parked in the specular ring then runs, its out-queue slots belong to that segment). Everything a path computes, in which order, and its
-// RNG draws are the same for both feeders. RING: entries of the per-wave specular ring (a power of two). FUSED (wf_bounce0): the lanes that
-// emit a slim shadow entry also store their {direction, seed} record, which wf_shadow(0) reads and no kernel wrote before.
-struct ShadeLane { bool valid, inA; uint32_t slot; float4 o, d, t, ha; };       // path record {origin, tmin} {direction, rng} {throughput, sample} + hit record of `slot`
-struct ShadeWave { uint32_t outCount = 0, shCount = 0, ringHead = 0, pending = 0; unsigned int nEntriesOut = 0, nRadiance = 0; };      // wave-uniform
-template <int MAXL, bool SIMPLE, bool PRIMARY, uint32_t RING, bool FUSED, class TABLES>
-HRT_DEV void shade_iteration(const WfArgs& a, const HrptPathTracerConstants& cb, const TABLES& tables, float* const ring, uint32_t in, uint32_t out, int bounce, int lastBounce,
-                             const ShadeLane& L, uint32_t baseA, uint32_t baseB, bool endsA, ShadeWave& w, uint32_t& outCountB, uint32_t& shCountB)
-{
-    static_assert(!FUSED || (PRIMARY && SIMPLE && MAXL == 1), "wf_bounce0: the bounce-0 SIMPLE single-light body");
-    static_assert((RING & (RING - 1u)) == 0u && RING >= 1u && RING <= 64u, "ring positions are masked; one flush takes at most 64 entries");
-    constexpr uint32_t kRing = RING;
-    const SceneView& s = a.scene;
-    const uint32_t lane = lane_id();
-    const bool inA = L.inA;
-    uint32_t& outCount = w.outCount; uint32_t& shCount = w.shCount;
-    outCountB = 0; shCountB = 0;
-            bool valid = L.valid, alive = false, wantDefer = false, wantRadiance = false;
-            LobeDraw ld; ld.spec = false; ld.specProb = 0.0f; ld.root = 0.0f; ld.sp = 0.0f; ld.cp = 0.0f;
-            uint32_t nNee = 0, smp = 0, slotIn = 0;
-            PathState ps; f3 neeT = mk3(0.0f, 0.0f, 0.0f);
-            constexpr bool STREAMED = MAXL == 0;
-            NeeBuf<(STREAMED ? 1 : MAXL)> nee; SurfaceCarry carry;
-            if (valid) {
-                HRT_PHASE(PH_SHADE_ITER);
-                const uint32_t slot = L.slot;
-                slotIn = slot;
-                const float4 o = L.o, d = L.d, t = L.t, ha = L.ha;
-                uint32_t tri = __float_as_uint(ha.w);
-                const bool noPath = PRIMARY && tri == kNoPathRecord;        // padding pixel (only bounce 0 without a raygen pass has such slots)
-                if (tri < kNoPathRecord) tri &= 0x1FFFFFFFu;          // bits 29-31: shading class (wf_extend)
-                ps.ray.o = mk3(o.x, o.y, o.z); ps.ray.d = mk3(d.x, d.y, d.z); ps.ray.tmin = o.w; ps.ray.tmax = 1e10f;
-                ps.rng = __float_as_uint(d.w);
-                ps.throughput = mk3(t.x, t.y, t.z); smp = __float_as_uint(t.w);
-                ps.radiance = mk3(0.0f, 0.0f, 0.0f);   // contributions of THIS stage; added to sampleRadiance below
-                if (!SIMPLE && a.hasMedium) {
-                    float4 m0 = a.b.med0[in][slot], m1 = a.b.med1[in][slot];
-                    ps.sigmaA = mk3(m0.x, m0.y, m0.z); ps.interiorIOR = m0.w; ps.sigmaS = mk3(m1.x, m1.y, m1.z); ps.inVolume = m1.w != 0.0f;
-                } else { ps.sigmaA = mk3(0.0f, 0.0f, 0.0f); ps.sigmaS = mk3(0.0f, 0.0f, 0.0f); ps.interiorIOR = 1.0f; ps.inVolume = false; }
-                bool addRadiance = false; f3 add = mk3(0.0f, 0.0f, 0.0f);
-                if (noPath) {
-                } else if (tri != 0xFFFFFFFFu) {
-                    HRT_PHASE(PH_SHADE_HIT);
-                    Hit h; h.valid = true; h.t = ha.x; h.u = ha.y; h.v = ha.z; h.tri = tri; h.prim = 0; h.inst = s.instances ? a.b.hitInst[slot] : 0u; h.opaque = 1;
-                    f3 emissiveTerm = mk3(0.0f, 0.0f, 0.0f);
-                    SurfaceOutcome oc = shade_surface_a<!SIMPLE, !SIMPLE, SIMPLE>(s, tables, cb, ps, h, carry, [&](uint32_t li, float ux, float uy) {
-                        if (STREAMED) ++nNee;
-                        else if (nNee < (uint32_t)MAXL) { nee.ux[nNee] = ux; nee.uy[nNee] = uy; nee.light[nNee] = li; ++nNee; }
-                    });
-                    if (oc == SURFACE_TRANSMITTED) alive = true;
-                    else {
-                        // ps.radiance now holds throughput*emissive of this hit (PathTracer.hlsl:258)
-                        emissiveTerm = ps.radiance;
-                        if (emissiveTerm.x != 0.0f || emissiveTerm.y != 0.0f || emissiveTerm.z != 0.0f) { addRadiance = true; add = emissiveTerm; }
-                        neeT = ps.throughput;
-                        // the sample drawn at the last bounce is never traced (the bounce loop ends, PathTracer.hlsl:90): nothing of it is observable
-                        if (!lastBounce) {
-                            if (SIMPLE) {
-                                if (lobe_begin(ps, carry, bounce, ld)) {
-                                    if (ld.spec) wantDefer = true;
-                                    else alive = lobe_diffuse(ps, carry.worldPos, carry.N, carry.baseColor, carry.metallic, ld);
-                                }
-                            } else alive = shade_surface_b(ps, carry, bounce);
-                        }
-                    }
-                } else {
-                    miss_sky(s, cb, ps, bounce);   // ps.radiance = throughput * sky
-                    addRadiance = true; add = ps.radiance;
-#ifdef HRPT_SKY_DEBUG
-                    if (smp < 2048u && bounce == 0) {
-                        float* g = g_skyDebug + smp * 16u;
-                        g[0] = ps.ray.o.x; g[1] = ps.ray.o.y; g[2] = ps.ray.o.z; g[3] = ps.ray.d.x; g[4] = ps.ray.d.y; g[5] = ps.ray.d.z;
-                        g[6] = cb.m_SunDirection[0]; g[7] = cb.m_SunDirection[1]; g[8] = cb.m_SunDirection[2]; g[9] = s.lights[0].m_Intensity;
-                        g[10] = ps.radiance.x; g[11] = ps.radiance.y; g[12] = ps.radiance.z; g[13] = ps.throughput.x; g[14] = ps.throughput.y; g[15] = ps.throughput.z;
-                    }
-#endif
-                }
-                if constexpr (PRIMARY) {
-                    // first term of the sample (a padding slot gets a zero nobody reads): 0 + term, stored (no wf_raygen zeroed sampleRadiance; the addition keeps the sign of a -0 term as the
-                    // read-modify-write below would)
-                    a.b.radiance[smp] = addRadiance ? make_float4(0.0f + add.x, 0.0f + add.y, 0.0f + add.z, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                } else if (addRadiance) {
-                    // radiance_total = radiance_total + term, in path order (x + 0 == x, so zero terms are skipped)
-                    float4 r = a.b.radiance[smp];
-                    r.x = r.x + add.x; r.y = r.y + add.y; r.z = r.z + add.z;
-                    a.b.radiance[smp] = r;
-                }
-                if (lastBounce) alive = false;
-                wantRadiance = addRadiance && !PRIMARY;
-            }
-            w.nRadiance += (unsigned int)__popcll(__ballot(wantRadiance));
-            // ---- wave-local compaction of survivors into the out queue of their own segment
-            const unsigned long long mA = __ballot(alive && inA), mB = __ballot(alive && !inA);
-            if (alive) {
-                HRT_PHASE(PH_SHADE_WRITE);
-                uint32_t o = inA ? baseA + outCount + prefix_rank(mA) : baseB + prefix_rank(mB);
-                a.b.rayO[out][o] = make_float4(ps.ray.o.x, ps.ray.o.y, ps.ray.o.z, ps.ray.tmin);
-                a.b.rayD[out][o] = make_float4(ps.ray.d.x, ps.ray.d.y, ps.ray.d.z, __uint_as_float(ps.rng));
-                a.b.thr[out][o] = make_float4(ps.throughput.x, ps.throughput.y, ps.throughput.z, __uint_as_float(smp));
-                if (!SIMPLE && a.hasMedium) {
-                    a.b.med0[out][o] = make_float4(ps.sigmaA.x, ps.sigmaA.y, ps.sigmaA.z, ps.interiorIOR);
-                    a.b.med1[out][o] = make_float4(ps.sigmaS.x, ps.sigmaS.y, ps.sigmaS.z, ps.inVolume ? 1.0f : 0.0f);
-                }
-            }
-            // ---- wave-local compaction of NEE work into the shadow queue of their own segment
-            const unsigned long long msA = __ballot(nNee > 0 && inA), msB = __ballot(nNee > 0 && !inA);
-            if (SIMPLE && MAXL == 1 && a.slimShadow && nNee > 0) {
-                // Slim entry (32 instead of 96 bytes): in a scene of this variant nothing is drawn before the light loop and the throughput
-                // is not touched before it, so wf_shadow takes V, the RNG state of the two draws, T and the sample index from the path's INPUT
-                // record (slotIn), and roughness / metallic / base colour / IOR from the material constants (no texture can modify them).
-                uint32_t e = inA ? baseA + shCount + prefix_rank(msA) : baseB + prefix_rank(msB);
-                a.b.sh0[e] = make_float4(carry.worldPos.x, carry.worldPos.y, carry.worldPos.z, __uint_as_float(slotIn));
-                a.b.sh1[e] = make_float4(carry.N.x, carry.N.y, carry.N.z, __uint_as_float(carry.material));
-                if constexpr (FUSED) a.b.rayD[in][slotIn] = L.d;       // the input record wf_shadow(0) takes V and the RNG state from
-            } else if (nNee > 0) {
-                uint32_t e = inA ? baseA + shCount + prefix_rank(msA) : baseB + prefix_rank(msB);
-                a.b.sh0[e] = make_float4(carry.worldPos.x, carry.worldPos.y, carry.worldPos.z, __uint_as_float(smp));
-                a.b.sh1[e] = make_float4(carry.N.x, carry.N.y, carry.N.z, carry.roughness);
-                a.b.sh2[e] = make_float4(carry.V.x, carry.V.y, carry.V.z, carry.metallic);
-                a.b.sh3[e] = make_float4(carry.baseColor.x, carry.baseColor.y, carry.baseColor.z, carry.ior);
-                a.b.sh4[e] = make_float4(neeT.x, neeT.y, neeT.z, __uint_as_float(nNee));
-                if (STREAMED) {
-                    const f3 sunDir = mk3(cb.m_SunDirection[0], cb.m_SunDirection[1], cb.m_SunDirection[2]);
-                    uint32_t rng = carry.rngBeforeLights, j = 0;
-                    for (uint32_t i = 0; i < cb.m_LightCount; ++i) {
-                        HrptGPULight l = load_light(s, i);
-                        float ux, uy;
-                        if (nee_draw<false>(l, carry.N, carry.worldPos, sunDir, rng, ux, uy)) a.b.shL[(size_t)e * a.maxLights + j++] = make_float4(ux, uy, __uint_as_float(i), 0.0f);
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < (STREAMED ? 1 : MAXL); ++j)
-                        if ((uint32_t)j < nNee) a.b.shL[(size_t)e * a.maxLights + j] = make_float4(nee.ux[j], nee.uy[j], __uint_as_float(nee.light[j]), 0.0f);
-                }
-            }
-            outCount += (uint32_t)__popcll(mA); shCount += (uint32_t)__popcll(msA);
-            outCountB = (uint32_t)__popcll(mB); shCountB = (uint32_t)__popcll(msB);
-            w.nEntriesOut += (unsigned int)(__popcll(msA) + __popcll(msB));
-            if (SIMPLE) {
-                // ---- park the lanes that picked the specular lobe
-                const unsigned long long md = __ballot(wantDefer);
-                const uint32_t nNew = (uint32_t)__popcll(md);
-                uint32_t first = 0;        // lanes of md below this rank are parked already (RING < 64 only: a ring of 64 takes an iteration's lanes at once)
-                bool parked = false;
-                for (int round = 0; round < (kRing < 64u ? 3 : 2) && !parked; ++round) {
-                // (when this iteration's lanes do not fit behind what is pending, the pending ones run first -- 58+ of 64 lanes with the ring of 64, still
-                // dense -- and a ring shorter than the lanes that are left then takes them a ring-full at a time)
-                uint32_t nPark = nNew - first;
-                if (w.pending + nPark <= kRing) parked = true;
-                else nPark = (kRing < 64u && w.pending == 0u) ? kRing : 0u;
-                const uint32_t rank = prefix_rank(md) - first;
-                if (wantDefer && (kRing < 64u ? rank < nPark : parked)) {
-                    float* e = ring + ((w.ringHead + w.pending + rank) & (kRing - 1u));
-                    e[0 * kRing] = carry.N.x; e[1 * kRing] = carry.N.y; e[2 * kRing] = carry.N.z;
-                    e[3 * kRing] = carry.V.x; e[4 * kRing] = carry.V.y; e[5 * kRing] = carry.V.z;
-                    e[6 * kRing] = carry.F0.x; e[7 * kRing] = carry.F0.y; e[8 * kRing] = carry.F0.z;
-                    e[9 * kRing] = carry.roughness; e[10 * kRing] = ld.root; e[11 * kRing] = ld.sp; e[12 * kRing] = ld.cp; e[13 * kRing] = ld.specProb;
-                    e[14 * kRing] = carry.worldPos.x; e[15 * kRing] = carry.worldPos.y; e[16 * kRing] = carry.worldPos.z;
-                    e[17 * kRing] = ps.throughput.x; e[18 * kRing] = ps.throughput.y; e[19 * kRing] = ps.throughput.z;
-                    e[20 * kRing] = __uint_as_float(ps.rng); e[21 * kRing] = __uint_as_float(smp); e[22 * kRing] = inA ? 1.0f : 0.0f;
-                }
-                w.pending += nPark; first += nPark;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                // ---- run the lobe for 64 parked paths at once; when segment A closes, for everything that is parked
-                while (w.pending >= 64u || ((endsA || !parked) && w.pending)) {
-                    const uint32_t n = w.pending < 64u ? w.pending : 64u;
-                    bool alive2 = false, tagA = true; PathState q; uint32_t smp2 = 0;
-                    if (lane < n) {
-                        const float* e = ring + ((w.ringHead + lane) & (kRing - 1u));
-                        f3 N = mk3(e[0 * kRing], e[1 * kRing], e[2 * kRing]), V = mk3(e[3 * kRing], e[4 * kRing], e[5 * kRing]), F0 = mk3(e[6 * kRing], e[7 * kRing], e[8 * kRing]);
-                        LobeDraw d2; d2.spec = true; d2.root = e[10 * kRing]; d2.sp = e[11 * kRing]; d2.cp = e[12 * kRing]; d2.specProb = e[13 * kRing];
-                        f3 wp = mk3(e[14 * kRing], e[15 * kRing], e[16 * kRing]);
-                        q.throughput = mk3(e[17 * kRing], e[18 * kRing], e[19 * kRing]); q.rng = __float_as_uint(e[20 * kRing]); smp2 = __float_as_uint(e[21 * kRing]);
-                        tagA = e[22 * kRing] != 0.0f;
-                        alive2 = lobe_specular(q, wp, N, V, F0, e[9 * kRing], d2);
-                    }
-                    const unsigned long long m2A = __ballot(alive2 && tagA), m2B = __ballot(alive2 && !tagA);
-                    if (alive2) {
-                        uint32_t o = tagA ? baseA + outCount + prefix_rank(m2A) : baseB + outCountB + prefix_rank(m2B);
-                        a.b.rayO[out][o] = make_float4(q.ray.o.x, q.ray.o.y, q.ray.o.z, q.ray.tmin);
-                        a.b.rayD[out][o] = make_float4(q.ray.d.x, q.ray.d.y, q.ray.d.z, __uint_as_float(q.rng));
-                        a.b.thr[out][o] = make_float4(q.throughput.x, q.throughput.y, q.throughput.z, __uint_as_float(smp2));
-                    }
-                    outCount += (uint32_t)__popcll(m2A); outCountB += (uint32_t)__popcll(m2B);
-                    w.ringHead = (w.ringHead + n) & (kRing - 1u); w.pending -= n;
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                }
-                }
-            }
-}
-
-// SIMPLE: scene traits proven at upload -- no textures, no transmissive / BLEND material, directional lights only --
-// compile the corresponding branches out (the general variant is always correct).
-// Occupancy: the multi-light variant is forced to 4 waves per SIMD (28 B of scratch per lane; -9 % on the glass config); the single-light
-// variants stay at 3 (forcing 4 costs them +3 %: 44..108 B of spills on a kernel that is already latency-bound).
-// MAXL = 0: any number of lights. The light loop runs twice: once to draw (it fixes the RNG state and tells whether the vertex has any light
-// sample at all, which the compaction needs), and -- for the lanes that have one -- again from the saved RNG state, writing the samples
-// straight into the entry's slots instead of buffering them per lane (AccumulateDirectLighting loops over all m_LightCount lights,
-// CommonLighting.hlsli:877-908; the reference's UI does not bound them).
-// Waves per SIMD: 4 for every variant (kWavesShade above). The SIMPLE variant's ring of parked paths is 64 entries so that four blocks fit a
-// CU's LDS (-11 % shade time on config 2 against 3 waves with a 128-entry ring). The general single-light variant wants 129 VGPRs and runs
-// 14 % faster on config 4 than at 3 waves. History: while the library was built with the SLP vectoriser this variant wanted 138 VGPRs, and forced
-// to 128 it computed a WRONG sky radiance (tests/test_parity_gpu.py::test_random_material_subsets... seeds 1 and 10: every miss pixel ~10 % off;
-// DESIGN.md section 4) -- the random trait scenes are the guard for this setting.
-// The body of wf_shade / wf_shade_lt. LDS_TABLES: the triangle, instance and material records come from the block's LDS copy (wf_shade_lt;
-// the plan decides, pt_wavefront_plan.h), otherwise from global memory. Same records, same arithmetic, same bits.
-template <int MAXL, bool SIMPLE, bool PRIMARY, bool LDS_TABLES>
-HRT_DEV void shade_paths(const WfArgs& a, const HrptPathTracerConstants& cb, uint32_t parity, int bounce, int lastBounce)
-{
-    static_assert(!PRIMARY || SIMPLE, "no raygen pass: SIMPLE scenes only");
-    static_assert(!LDS_TABLES || SIMPLE, "tables in LDS: behind the ring of the SIMPLE variants");
-    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    const uint32_t in = parity, out = parity ^ 1u;
-    const SceneView& s = a.scene;
-    // Deferred specular lobe (SIMPLE variant). On diffuse-dominated scenes ~10 % of the paths pick the GGX-VNDF lobe, a long branch that
-    // used to run in every iteration with ~6 active lanes. Those lanes now park what the lobe needs in a per-wave LDS ring (SoA, 128
-    // entries) and the wave runs the lobe for 64 of them at once (or for whatever is pending when a segment closes: their out-queue slots
-    // belong to that segment). Per path the arithmetic is unchanged.
-    extern __shared__ __attribute__((aligned(16))) char shadeSmem[];
-    constexpr uint32_t kRing = kShadeRing, kRingFields = kShadeRingFields;
-    float* const ring = reinterpret_cast<float*>(shadeSmem) + (size_t)uniform(threadIdx.x >> 6) * kRing * kRingFields;
-    LdsShadeTables ldsTables; ldsTables.attrs = ldsTables.instShade = ldsTables.materials = 0u;
-    if constexpr (LDS_TABLES) { ldsTables = copy_shade_tables(shadeSmem + kShadeRingBytes, a); __syncthreads(); }
-    const GlobalShadeTables globalTables{ s };
-    ShadeWave w;         // output counters of the open segment, ring cursor, statistics (HrptStats queue-byte accounting)
-    uint32_t& outCount = w.outCount; uint32_t& shCount = w.shCount;
-    // Sort by shading class (general variants). wf_extend left the class of the hit triangle's material in the hit record (0 constants only,
-    // 1 textured, 2 transmission branch; a miss counts as class 3: the sky lookup). When a segment is opened the wave counting-sorts its
-    // entries by class into a permutation in LDS (two passes over the 4-byte class words, ballot + prefix rank) and then shades the entries
-    // in that order, so that a 64-lane iteration holds one class (two at a class boundary) instead of a mix that runs every branch of
-    // shade_surface_a / miss_sky with a fraction of the lanes. Per path nothing changes: every path carries its RNG state and sample index,
-    // and survivors / NEE entries still compact into their own segment, only in another order.
-    constexpr bool SORT = !SIMPLE;
-    const uint32_t segSize = a.segSize;
-    // two permutation tables per wave (the open segment A and its successor B, which fills the lanes A's last iteration leaves empty) + keys
-    uint16_t* const permBase = reinterpret_cast<uint16_t*>(shadeSmem) + (size_t)uniform(threadIdx.x >> 6) * segSize * 2;
-    uint8_t* const keys = reinterpret_cast<uint8_t*>(shadeSmem) + (size_t)wavesPerBlock * segSize * 4 + (size_t)uniform(threadIdx.x >> 6) * segSize;
-    uint32_t permSel = 0;                      // which of the two tables belongs to segment A
-    bool permuted = false, permutedB = false;
-    // counting sort of the `n` entries of the segment at `base` by shading class into `perm`; false when the segment is uniform (queue order kept)
-    auto sort_segment = [&](uint32_t base, uint32_t n, uint16_t* perm) -> bool {
-        HRT_PHASE(PH_SHADE_SORT);
-        uint32_t c0 = 0, c1 = 0, c2 = 0;
-        for (uint32_t b = 0; b < n; b += 64) {
-            const uint32_t e = b + lane; uint32_t k = 4u;
-            if (e < n) { k = __float_as_uint(a.b.hit[base + e].w) >> 29; k = k > 3u ? 3u : k; keys[e] = (uint8_t)k; }
-            c0 += (uint32_t)__popcll(__ballot(k == 0u)); c1 += (uint32_t)__popcll(__ballot(k == 1u)); c2 += (uint32_t)__popcll(__ballot(k == 2u));
-        }
-        const uint32_t c3 = n - c0 - c1 - c2;
-        if (c0 == n || c1 == n || c2 == n || c3 == n) return false;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        uint32_t b0 = 0, b1 = c0, b2 = c0 + c1, b3 = c0 + c1 + c2;
-        for (uint32_t b = 0; b < n; b += 64) {
-            const uint32_t e = b + lane; const uint32_t k = e < n ? keys[e] : 4u;
-            const unsigned long long m0 = __ballot(k == 0u), m1 = __ballot(k == 1u), m2 = __ballot(k == 2u), m3 = __ballot(k == 3u);
-            if (k == 0u) perm[b0 + prefix_rank(m0)] = (uint16_t)e;
-            if (k == 1u) perm[b1 + prefix_rank(m1)] = (uint16_t)e;
-            if (k == 2u) perm[b2 + prefix_rank(m2)] = (uint16_t)e;
-            if (k == 3u) perm[b3 + prefix_rank(m3)] = (uint16_t)e;
-            b0 += (uint32_t)__popcll(m0); b1 += (uint32_t)__popcll(m1); b2 += (uint32_t)__popcll(m2); b3 += (uint32_t)__popcll(m3);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        return true;
-    };
-    // The wave works through its segments (gw, gw + totalWaves, ...) as one stream of 64-lane iterations: when the open segment A
-    // has fewer than 64 entries left, the remaining lanes take the first entries of the next non-empty segment B, so only the wave's
-    // last iteration is partially filled (after compaction a 256-slot segment holds ~207 / 168 / 136 paths at bounces 1 / 2 / 3: one
-    // partly empty iteration per segment otherwise). Survivors and NEE entries still compact into their OWN segment (front of the
-    // out queue / shadow queue of A or B), so segments stay wave-owned and the layout deterministic.
-    {
-        uint32_t seg = gw, cnt = 0, segBase = 0, next = 0;      // segment A: cursor (its output counters: w)
-        bool haveSeg = false;
-        auto open_segment = [&]() {        // first non-empty segment at or after `seg`; empty ones get their (zero) counts written here
-            haveSeg = false; cnt = 0; next = 0; outCount = 0; shCount = 0;
-            for (; seg < a.numSegments; seg += totalWaves) {
-                cnt = uniform(PRIMARY ? path_count(a, in, seg) : a.b.pathCnt[in][seg]);
-                if (cnt) { segBase = seg * a.segSize; haveSeg = true; break; }
-                if (lane == 0) { a.b.pathCnt[out][seg] = 0; a.b.shadowCnt[seg] = 0; }
-            }
-            if (SORT && a.sortShade && haveSeg) permuted = sort_segment(segBase, cnt, permBase + permSel * segSize);
-        };
-        open_segment();
-        while (haveSeg) {
-            // lanes [0, takeA) continue segment A; if A ends inside this iteration, lanes [takeA, takeA + takeB) start segment B
-            const uint32_t takeA = cnt - next < 64u ? cnt - next : 64u;
-            const uint32_t segA = seg, baseA = segBase, nextA = next;
-            const bool endsA = nextA + takeA >= cnt;
-            uint32_t takeB = 0, segB = 0, baseB = 0, cntB = 0;
-            if (endsA && takeA < 64u) {
-                uint32_t probe = seg + totalWaves;
-                for (; probe < a.numSegments; probe += totalWaves) {
-                    cntB = uniform(PRIMARY ? path_count(a, in, probe) : a.b.pathCnt[in][probe]);
-                    if (cntB) break;
-                    if (lane == 0) { a.b.pathCnt[out][probe] = 0; a.b.shadowCnt[probe] = 0; }
-                }
-                if (probe < a.numSegments) {
-                    segB = probe; baseB = probe * a.segSize; takeB = cntB < 64u - takeA ? cntB : 64u - takeA;
-                    if (SORT && a.sortShade) permutedB = sort_segment(baseB, cntB, permBase + (permSel ^ 1u) * segSize);
-                } else segB = probe;          // no further segment: remembered so that the cursor below ends the loop
-            }
-            ShadeLane L; L.valid = lane < takeA + takeB; L.inA = lane < takeA; L.slot = 0;
-            if (L.valid) {
-                const uint32_t slot = L.inA ? baseA + ((SORT && permuted) ? (uint32_t)permBase[permSel * segSize + nextA + lane] : nextA + lane)
-                                          : baseB + ((SORT && permutedB) ? (uint32_t)permBase[(permSel ^ 1u) * segSize + (lane - takeA)] : lane - takeA);
-                L.slot = slot;
-                if constexpr (PRIMARY) {         // origin = camera, direction + seed as wf_extend<PRIMARY> left them, unit throughput, sample = slot
-                    const PrimaryArgs& pr = *a.primaryArgs;
-                    L.o = make_float4(pr.cam[0], pr.cam[1], pr.cam[2], 0.0f); L.d = a.b.rayD[in][slot];
-                    L.t = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(slot));
-                } else { L.o = a.b.rayO[in][slot]; L.d = a.b.rayD[in][slot]; L.t = a.b.thr[in][slot]; }
-                L.ha = a.b.hit[slot];
-            }
-            uint32_t outCountB = 0, shCountB = 0;
-            if constexpr (LDS_TABLES) shade_iteration<MAXL, SIMPLE, PRIMARY, kShadeRing, false>(a, cb, ldsTables, ring, in, out, bounce, lastBounce, L, baseA, baseB, endsA, w, outCountB, shCountB);
-            else shade_iteration<MAXL, SIMPLE, PRIMARY, kShadeRing, false>(a, cb, globalTables, ring, in, out, bounce, lastBounce, L, baseA, baseB, endsA, w, outCountB, shCountB);
-            // ---- advance the cursor
-            if (!endsA) next = nextA + takeA;
-            else {
-                if (lane == 0) { a.b.pathCnt[out][segA] = outCount; a.b.shadowCnt[segA] = shCount; }
-                if (takeB) {                 // B becomes the open segment, already takeB entries in
-                    seg = segB; segBase = baseB; cnt = cntB; next = takeB;
-                    outCount = outCountB; shCount = shCountB;
-                    haveSeg = true;
-                    if (SORT) { permSel ^= 1u; permuted = permutedB; permutedB = false; }
-                    if (next >= cnt) {       // B was short enough to end in the same iteration
-                        if (lane == 0) { a.b.pathCnt[out][seg] = outCount; a.b.shadowCnt[seg] = shCount; }
-                        seg += totalWaves; open_segment();
-                    }
-                } else if (takeA < 64u) { seg = segB; haveSeg = false; }     // probed to the end: nothing left
-                else { seg += totalWaves; open_segment(); }
-            }
-        }
-    }
-    block_count_add_uniform<2>(a.counters, { 3, 5 }, { w.nEntriesOut, w.nRadiance });
-}
-// Kernel names are looked up by tests/test_kernel_resources.py: wf_shade<...> are the global-table entry points, wf_shade_lt<...> the same
-// body over tables in LDS (SIMPLE single-light variants; launched with RenderPlan::shadeLdsBytes).
-template <int MAXL, bool SIMPLE, bool PRIMARY = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWavesShade, kWavesShade))) void wf_shade(WfArgs a, HrptPathTracerConstants cb, uint32_t parity, int bounce, int lastBounce)
-{
-    shade_paths<MAXL, SIMPLE, PRIMARY, false>(a, cb, parity, bounce, lastBounce);
-}
-template <int MAXL, bool SIMPLE, bool PRIMARY = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWavesShade, kWavesShade))) void wf_shade_lt(WfArgs a, HrptPathTracerConstants cb, uint32_t parity, int bounce, int lastBounce)
-{
-    shade_paths<MAXL, SIMPLE, PRIMARY, true>(a, cb, parity, bounce, lastBounce);
-}
-
-// ------------------------------------------------------------------ bounce 0 in one kernel (trace + shade)
-// wf_extend<LDS, OPQ, PRIMARY> and wf_shade_lt<1, SIMPLE, PRIMARY> in one: where the plan says so (RenderPlan::fusedBounce0: tree and shading tables
-// in LDS, every instance opaque, one light) a wave takes the slots of its segments 64 at a time, traces their primary rays to completion --
-// the same inner_step / tri_test / key_less walk with the thresholded descent, but no lane refill: the 64 rays start together and the loop
-// ends with the last of them -- and feeds hit and ray from registers to shade_iteration. Neither the hit record nor the {direction, seed}
-// record of every sample goes through memory; only the lanes that emit a shadow entry store the latter, for wf_shadow(0).
-// Budget: wf_shade's (four waves per SIMD, <= 128 VGPRs, no scratch: tests/test_kernel_resources_bounce0.py); LDS of one block, in this order:
-// stack columns | specular ring of kBounce0Ring entries per wave | shading tables, padded to 128 B | tree copy (pt_wavefront_plan.h).
-template <int DEPTH>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWavesShade, kWavesShade))) void wf_bounce0(WfArgs a, HrptPathTracerConstants cb, int lastBounce)
-{
-    extern __shared__ __attribute__((aligned(128))) char smem[];
-    using Stack = LdsStack<DEPTH, kExtendLdsStack>;
-    Stack stack; LdsBvh<4> lbvh;
-    const SceneView& s = a.scene;
-    char* const shadeSmem = smem + (size_t)Stack::kRows * kBlock * 4;
-    float* const ring = reinterpret_cast<float*>(shadeSmem) + (size_t)uniform(threadIdx.x >> 6) * kBounce0Ring * kShadeRingFields;
-    const LdsShadeTables ldsTables = copy_shade_tables(shadeSmem + kBounce0RingBytes, a);
-    setup_lds<true, DEPTH, 4>(smem, s, stack, lbvh, bounce0_shade_bytes(shade_table_bytes(s.triCount, a.shadeInstances, a.shadeMaterials)));     // (its barrier publishes the tables too)
-    if (DEPTH > kExtendLdsStack) { stack.spill = a.spill[0] + blockIdx.x * kBlock + threadIdx.x; stack.spillStride = gridDim.x * kBlock; }
-
-    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    const bool emptyScene = s.nodeCount == 0 && s.rootLeaf == 0;
-    const PrimaryArgs& pr = *a.primaryArgs;
-    unsigned int nRays = 0;
-    ShadeWave w;
-    for (uint32_t seg = gw; seg < a.numSegments; seg += totalWaves) {
-        const uint32_t cnt = uniform(path_count(a, 0u, seg)), segBase = seg * a.segSize;
-        w.outCount = 0; w.shCount = 0;
-        for (uint32_t next = 0; next < cnt; next += 64u) {
-            const uint32_t take = cnt - next < 64u ? cnt - next : 64u;
-            ShadeLane L; L.valid = lane < take; L.inA = true; L.slot = segBase + next + lane;
-            // ---- trace: closest hit of the slot's primary ray (wf_extend's loop for the lanes that have a path; a padding pixel has none)
-            Ray r; r.o = mk3(0.0f, 0.0f, 0.0f); r.d = mk3(0.0f, 0.0f, 1.0f); r.tmin = 0.0f; r.tmax = 1e10f;
-            uint32_t rng = 0;
-            bool active = L.valid && primary_ray(a, pr, L.slot, r.o, r.d, rng);
-            const bool havePath = active;
-            if (active) ++nRays;
-            Hit best; best.valid = false; best.t = 0.0f; best.inst = 0; best.prim = 0; best.u = 0.0f; best.v = 0.0f; best.opaque = 0; best.tri = 0;
-            float tlim = r.tmax; int sp = 0;
-            const RayShear sh = make_shear(r.d);
-            const f3 inv = traversal_rcp(r.d), noi = slab_origin_term(r.o, inv);
-            const bool finite = (r.d.x == r.d.x && r.d.y == r.d.y && r.d.z == r.d.z);
-            int32_t cur = (!active || emptyScene || !finite) ? kTraversalDone : (s.nodeCount == 0 ? s.rootLeaf : 0);
-            active = cur != kTraversalDone;
-            while (__ballot(active) != 0ull) {
-                if (active) {
-                    while (cur >= 0) {
-                        cur = inner_step(lbvh, cur, noi, inv, r.tmin, tlim, stack, sp);
-                        if ((uint32_t)__popcll(__ballot(cur >= 0)) < a.nodeLoopMin) break;
-                    }
-                    if (cur < 0 && cur != kTraversalDone) {
-                        const uint32_t enc = (uint32_t)(~cur), first = enc >> 2, count = (enc & 3u) + 1u;
-                        for (uint32_t i = 0; i < count; ++i) {
-                            float4 ta, tb, tc; lbvh.tri(first + i, ta, tb, tc);
-                            float t, u, v;
-                            if (tri_test(mk3(ta.x, ta.y, ta.z), mk3(tb.x, tb.y, tb.z), mk3(tc.x, tc.y, tc.z), r, sh, t, u, v)) {
-                                const uint32_t inst = __float_as_uint(ta.w), prim = __float_as_uint(tb.w);
-                                const bool takeHit = !best.valid || key_less(t, inst, prim, best.t, best.inst, best.prim);      // selects: see wf_extend's two-level loop
-                                best.t = takeHit ? t : best.t; best.u = takeHit ? u : best.u; best.v = takeHit ? v : best.v;
-                                best.inst = takeHit ? inst : best.inst; best.prim = takeHit ? prim : best.prim; best.tri = takeHit ? first + i : best.tri;
-                                best.opaque = takeHit ? (__float_as_uint(tc.w) & 7u) : best.opaque;
-                                best.valid = best.valid || takeHit;
-                                tlim = takeHit ? t : tlim;
-                            }
-                        }
-                        cur = sp == 0 ? kTraversalDone : stack.pop(--sp);
-                    }
-                    active = cur != kTraversalDone;
-                }
-            }
-            // ---- shade: the records wf_extend<PRIMARY> would have written and shade_paths<PRIMARY> read back, from registers
-            L.o = make_float4(pr.cam[0], pr.cam[1], pr.cam[2], 0.0f);
-            L.d = make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(rng));
-            L.t = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(L.slot));
-            L.ha = make_float4(best.t, best.u, best.v, __uint_as_float(!havePath ? kNoPathRecord : (best.valid ? (best.tri | ((best.opaque >> 1) << 29)) : 0xFFFFFFFFu)));
-            uint32_t outCountB, shCountB;       // (no segment B here: a chunk lies in one segment)
-            shade_iteration<1, true, true, kBounce0Ring, true>(a, cb, ldsTables, ring, 0u, 1u, 0, lastBounce, L, segBase, segBase, next + take >= cnt, w, outCountB, shCountB);
-        }
-        if (lane == 0) { a.b.pathCnt[1][seg] = w.outCount; a.b.shadowCnt[seg] = w.shCount; }
-    }
-    // counted as the pair counts: closest-hit rays and paths (wf_extend<PRIMARY>), shadow-queue entries and radiance read-modify-writes (wf_shade)
-    block_count_add(&a.counters->closestRays, 0, nRays);
-    __syncthreads();
-    block_count_add(&a.counters->closestRays, 2, nRays);
-    __syncthreads();
-    block_count_add(&a.counters->closestRays, 8, nRays);
-    block_count_add_uniform<3>(a.counters, { 3, 5, 9 }, { w.nEntriesOut, w.nRadiance, w.nEntriesOut });
-}
-
-// ------------------------------------------------------------------ shadow rays (scenes with non-opaque geometry)
-// One ray per valid light sample of every shadow-queue entry, compacted per segment, for the any-hit pass of wf_extend<ANYHIT>.
-// nee_direction is evaluated here and again in wf_shadow (same inputs, same bits) rather than stored: 40 B per sample less traffic.
-template <bool DIRONLY>
-__global__ __launch_bounds__(kBlock) void wf_shadow_rays(WfArgs a, HrptPathTracerConstants cb)
-{
-    const SceneView& s = a.scene;
-    const f3 sunDir = mk3(cb.m_SunDirection[0], cb.m_SunDirection[1], cb.m_SunDirection[2]);
-    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    for (uint32_t seg = gw; seg < a.numSegments; seg += totalWaves) {
-        const uint32_t cnt = uniform(a.b.shadowCnt[seg]), segBase = seg * a.segSize, items = cnt * a.maxLights;
-        uint32_t outCount = 0;
-        for (uint32_t i0 = 0; i0 < items; i0 += 64) {
-            const uint32_t i = i0 + lane;
-            bool valid = false; Ray ray; uint32_t id = 0;
-            if (i < items) {
-                HRT_PHASE(PH_SHADOW_RAYS_ITEM);
-                const uint32_t el = i / a.maxLights, j = i - el * a.maxLights, e = segBase + el;
-                id = e * a.maxLights + j;
-                float4 h4 = a.b.sh4[e];
-                if (j < __float_as_uint(h4.w)) {
-                    float4 h0 = a.b.sh0[e], h1 = a.b.sh1[e], ls = a.b.shL[(size_t)e * a.maxLights + j];
-                    HrptGPULight l = load_light(s, __float_as_uint(ls.z));
-                    f3 L; float maxDist;
-                    if (nee_direction<DIRONLY>(l, mk3(h1.x, h1.y, h1.z), mk3(h0.x, h0.y, h0.z), sunDir, cb.m_CosSunAngularRadius, ls.x, ls.y, L, maxDist)) {
-                        ray = shadow_ray(mk3(h0.x, h0.y, h0.z), L, maxDist);
-                        valid = true;
-                    }
-                }
-                if (!valid) a.b.shVis[id] = kVisNoRay;
-            }
-            const unsigned long long m = __ballot(valid);
-            if (valid) {
-                const uint32_t o = segBase * a.maxLights + outCount + prefix_rank(m);
-                a.b.sqO[o] = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tmin);
-                a.b.sqD[o] = make_float4(ray.d.x, ray.d.y, ray.d.z, ray.tmax);
-                a.b.sqId[o] = id;
-            }
-            outCount += (uint32_t)__popcll(m);
-        }
-        if (lane == 0) a.b.sqCnt[seg] = outCount;
-    }
-}
-
-// ------------------------------------------------------------------ shadow (NEE visibility + accumulation)
-// MODE: kShadowOpaque / kShadowBuffered / kShadowResolve / kShadowSlim (pt_wavefront_plan.h)
-// Waves per SIMD (built without the SLP vectoriser, csrc/Makefile): the buffered variant is held at 3 -- the gradient-sampled alpha test of
-// mip-mapped MASK textures, a rare path, would otherwise cost every scene with alpha-tested geometry a wave (145-152 VGPRs; at 4 waves config 4's
-// shadow stage is 6 % SLOWER: it traverses, and spills hurt its loops); the resolve variant runs at 4 (146-150 VGPRs wanted, 128 given: it waits
-// on its queue reads for 71 % of its cycles and only walks candidate lists: glass config shadow stage -6 %); the two-level variants at 3
-// (scenes with non-opaque instances -16 % shadow time). Forced budgets are re-checked with the random trait scenes (scripts/parity_campaign.sh:
-// HRPT_WF_SHADOW_PATH=1 / 2 and the two-level scenes), because one has broken wf_shade's general variant before.
-template <bool LDS_BVH, int DEPTH, int W, bool DIRONLY, int MODE, int TL = 0>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 2 && TL == 0 ? 4 : ((MODE == 1 || TL != 0) ? 3 : 1)))) void wf_shadow(WfArgs a, HrptPathTracerConstants cb, int bounce)
-{
-    static_assert(!TL || (!LDS_BVH && W == 4 && (MODE == kShadowOpaque || MODE == kShadowSlim)), "two-level structure: opaque any-hit query over the global tree");
-    static_assert(W != kQuantisedTree || (!LDS_BVH && !TL), "quantised nodes: flat tree in global memory");
-    constexpr bool NONOPAQUE = MODE == kShadowBuffered || MODE == kShadowResolve;
-    constexpr bool SLIM = MODE == kShadowSlim;
-    constexpr int kLdsMax = MODE == kShadowResolve ? kExtendLdsStack : kShadowLdsStack;
-    extern __shared__ __attribute__((aligned(128))) char smem[];
-    LdsStack<DEPTH, kLdsMax> stack; LdsBvh<W> lbvh;
-    constexpr size_t candBytes = MODE == kShadowBuffered ? (size_t)kShadowCandidates * 2 * kBlock * 4 : 0;
-    setup_lds<LDS_BVH, DEPTH, W>(smem, a.scene, stack, lbvh, candBytes);
-    if (DEPTH > kLdsMax) { stack.spill = a.spill[1] + blockIdx.x * kBlock + threadIdx.x; stack.spillStride = gridDim.x * kBlock; }
-    LdsCandidates cand; cand.base = reinterpret_cast<int32_t*>(smem + (size_t)LdsStack<DEPTH, kLdsMax>::kRows * kBlock * 4) + threadIdx.x;
-    LdsCandidates3 cand3; cand3.base = cand.base;        // TL == 2: (t, mesh triangle, instance) columns in the same place (the launch adds their bytes)
-    typename GlobalBvhOf<(TL ? kTwoLevelTree : W)>::type gbvh = GlobalBvhOf<(TL ? kTwoLevelTree : W)>::make(a.scene);
-    const SceneView& s = a.scene;
-    const f3 sunDir = mk3(cb.m_SunDirection[0], cb.m_SunDirection[1], cb.m_SunDirection[2]);
-    const float sunIntensity = s.lights[0].m_Intensity;      // g_Lights[0], PathTracer.hlsl:137 (reference quirk kept)
-
-    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    unsigned int nRays = 0, nSamples = 0, nRadiance = 0, nSkipped16 = 0;
-    // one shadow-queue entry: every light sample of one path vertex
-    auto process = [&](uint32_t e) {
-                HRT_PHASE(PH_SHADOW_ENTRY);
-                if (SLIM) {
-                    const float4 h0 = a.b.sh0[e], h1 = a.b.sh1[e];
-                    const uint32_t slot = __float_as_uint(h0.w);
-                    const float4 rd = a.b.rayD[a.shadowParity][slot];
-                    const f3 origin = mk3(h0.x, h0.y, h0.z), N = mk3(h1.x, h1.y, h1.z);
-                    uint32_t rng = __float_as_uint(rd.w);
-                    const float ux = hrt_rng_next(&rng), uy = hrt_rng_next(&rng);      // the two draws of nee_draw (CommonLighting.hlsli:730)
-                    ++nSamples;
-                    HrptGPULight l = load_light(s, 0u);
-                    f3 L; float maxDist;
-                    if (!nee_direction<true>(l, N, origin, sunDir, cb.m_CosSunAngularRadius, ux, uy, L, maxDist)) return;
-                    float shadow;
-                    if (LDS_BVH) shadow = shadow_query<true>(s, lbvh, origin, L, maxDist, stack);
-                    else if constexpr (TL == 2) shadow = shadow_query_two_level_buffered<kTwoLevelCandidates>(s, gbvh, shadow_ray(origin, L, maxDist), stack, cand3);
-                    else shadow = shadow_query<true>(s, gbvh, origin, L, maxDist, stack);
-                    ++nRays;
-                    if (shadow != 0.0f) {
-                        const float4 th = a.primary ? make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(slot)) : a.b.thr[a.shadowParity][slot];
-                        if (a.primary) ++nSkipped16;
-                        const HrptMaterialConstants& mat = s.materials[__float_as_uint(h1.w)];
-                        // GetPBRAttributes without textures (RaytracingCommon.hlsli:252-296): constants, roughness clamped at 0.04
-                        f3 dif, spec;
-                        nee_contribution<true>(s, l, nee_lighting(N, mk3(-rd.x, -rd.y, -rd.z), mk3(mat.m_BaseColor), hrt_max(mat.m_RoughnessMetallic[0], 0.04f),
-                                                                  mat.m_RoughnessMetallic[1], mat.m_IOR), origin, sunDir, sunIntensity, L, dif, spec);
-                        f3 totalDiffuse = mk3(0.0f, 0.0f, 0.0f) + dif * shadow, totalSpecular = mk3(0.0f, 0.0f, 0.0f);
-                        if (bounce == 0) totalSpecular = totalSpecular + spec * shadow;
-                        const f3 dsum = totalDiffuse + (bounce == 0 ? totalSpecular : mk3(0.0f, 0.0f, 0.0f));
-                        if (dsum.x != 0.0f || dsum.y != 0.0f || dsum.z != 0.0f) {
-                            const f3 term = mk3(th.x, th.y, th.z) * dsum;
-                            const uint32_t smp = __float_as_uint(th.w);
-                            float4 r = a.b.radiance[smp];
-                            r.x = r.x + term.x; r.y = r.y + term.y; r.z = r.z + term.z;
-                            a.b.radiance[smp] = r;
-                            ++nRadiance;
-                        }
-                    }
-                    return;
-                }
-                float4 h0 = a.b.sh0[e], h1 = a.b.sh1[e], h4 = a.b.sh4[e];
-                f3 origin = mk3(h0.x, h0.y, h0.z), N = mk3(h1.x, h1.y, h1.z), T = mk3(h4.x, h4.y, h4.z);
-                uint32_t smp = __float_as_uint(h0.w), n = __float_as_uint(h4.w);
-                nSamples += n;
-                f3 totalDiffuse = mk3(0.0f, 0.0f, 0.0f), totalSpecular = mk3(0.0f, 0.0f, 0.0f);
-                // Variants that traverse themselves request the first sample's record together with the entry (one dependent round trip less:
-                // single-light scenes -2 % shadow time). Not the resolve variant: it is held at 128 VGPRs and loses 3 % to the extra live
-                // registers; requesting sample j + 1 while j is worked on costs every variant more than it hides.
-                float4 ls0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (MODE != kShadowResolve && n) ls0 = a.b.shL[(size_t)e * a.maxLights];
-                for (uint32_t j = 0; j < n; ++j) {
-                    HRT_PHASE(PH_SHADOW_SAMPLE);
-                    uint32_t vis = kVisCandidates;
-                    if (MODE == kShadowResolve) {
-                        // outcome of the opaque any-hit pass (wf_shadow_rays + wf_extend<ANYHIT>): most rays are settled there
-                        vis = a.b.shVis[e * a.maxLights + j];
-                        if (vis == kVisNoRay) continue;                                  // nee_direction said no
-                        if (vis == kVisBlocked) { ++nRays; continue; }                   // shadow factor 0: contributes +0
-                    }
-                    float4 ls = ls0;
-                    if (MODE == kShadowResolve || j) ls = a.b.shL[(size_t)e * a.maxLights + j];
-                    HrptGPULight l = load_light(s, __float_as_uint(ls.z));
-                    f3 L; float maxDist;
-                    if (!nee_direction<DIRONLY>(l, N, origin, sunDir, cb.m_CosSunAngularRadius, ls.x, ls.y, L, maxDist)) continue;
-                    float shadow;
-                    HRT_PHASE(PH_SHADOW_QUERY);
-                    if (MODE == kShadowResolve) {
-                        if (vis == kVisClear) shadow = 1.0f;                             // no triangle at all in (tmin, tmax)
-                        else {                                                           // the non-opaque triangles it crossed, nearest first
-                            Ray sr = shadow_ray(origin, L, maxDist);
-                            GlobalCandidates gc; gc.base = a.b.sqCand + (size_t)(e * a.maxLights + j) * kShadowCandidates;
-                            const int cnt = (int)((vis >> 8) & 0xFFu); const bool ovf = (vis >> 16) & 1u;
-                            if (LDS_BVH) shadow = shadow_resolve_candidates(s, lbvh, sr, make_shear(sr.d), cnt, ovf, gc, stack);
-                            else shadow = shadow_resolve_candidates(s, gbvh, sr, make_shear(sr.d), cnt, ovf, gc, stack);
-                        }
-                    } else if (MODE == kShadowBuffered) {
-                        // (no descent threshold here: without lane refill it only costs: config 2 shadow +3 %, config 4 +2.5 %)
-                        if (LDS_BVH) shadow = shadow_query_buffered<kShadowCandidates>(s, lbvh, origin, L, maxDist, stack, cand);
-                        else shadow = shadow_query_buffered<kShadowCandidates>(s, gbvh, origin, L, maxDist, stack, cand);
-                    } else {
-                        if (LDS_BVH) shadow = shadow_query<true>(s, lbvh, origin, L, maxDist, stack);       // kShadowOpaque: no ForceNonOpaque instance in the scene
-                        else if constexpr (TL == 2) shadow = shadow_query_two_level_buffered<kTwoLevelCandidates>(s, gbvh, shadow_ray(origin, L, maxDist), stack, cand3);
-                    else shadow = shadow_query<true>(s, gbvh, origin, L, maxDist, stack);
-                    }
-                    ++nRays;
-                    if (shadow != 0.0f) {   // an occluded sample contributes +0: its BRDF x radiance evaluation is skipped
-                        HRT_PHASE(PH_SHADOW_CONTRIB);
-                        float4 h2 = a.b.sh2[e], h3 = a.b.sh3[e];
-                        f3 dif, spec;
-                        nee_contribution<DIRONLY>(s, l, nee_lighting(N, mk3(h2.x, h2.y, h2.z), mk3(h3.x, h3.y, h3.z), h1.w, h2.w, h3.w), origin, sunDir,
-                                                  sunIntensity, L, dif, spec);
-                        totalDiffuse = totalDiffuse + dif * shadow;
-                        if (bounce == 0) totalSpecular = totalSpecular + spec * shadow;
-                    }
-                }
-                f3 dsum = totalDiffuse + (bounce == 0 ? totalSpecular : mk3(0.0f, 0.0f, 0.0f));
-                if (dsum.x != 0.0f || dsum.y != 0.0f || dsum.z != 0.0f) {
-                    f3 term = T * dsum;                                         // PathTracer.hlsl:261
-                    float4 r = a.b.radiance[smp];
-                    r.x = r.x + term.x; r.y = r.y + term.y; r.z = r.z + term.z;
-                    a.b.radiance[smp] = r;
-                    ++nRadiance;
-                }
-    };
-    if (NONOPAQUE) {
-        // Buffered variant (long, uneven entries): the wave hands out the entries of its segments (gw, gw + totalWaves, ...) as one
-        // stream, an iteration whose segment runs out continues with the next one, so only the wave's last iteration is partly filled
-        // (-4 % on configs 4 / 5). The short opaque any-hit variant below is faster with the plain per-segment loop (config 2).
-        uint32_t seg = gw, cnt = 0, segBase = 0, next = 0; bool haveSeg = false;
-        auto open_segment = [&]() {
-            haveSeg = false; cnt = 0; next = 0;
-            for (; seg < a.numSegments; seg += totalWaves) {
-                cnt = uniform(a.b.shadowCnt[seg]);
-                if (cnt) { segBase = seg * a.segSize; haveSeg = true; break; }
-            }
-        };
-        open_segment();
-        while (haveSeg) {
-            uint32_t e = 0xFFFFFFFFu, filled = 0;
-            while (filled < 64u && haveSeg) {
-                uint32_t take = cnt - next < 64u - filled ? cnt - next : 64u - filled;
-                if (lane >= filled && lane < filled + take) e = segBase + next + (lane - filled);
-                next += take; filled += take;
-                if (next >= cnt) { seg += totalWaves; open_segment(); }
-            }
-            if (e != 0xFFFFFFFFu) process(e);
-        }
-    } else {
-        for (uint32_t seg = gw; seg < a.numSegments; seg += totalWaves) {
-            const uint32_t cnt = uniform(a.b.shadowCnt[seg]), segBase = seg * a.segSize;
-            for (uint32_t base = 0; base < cnt; base += 64) {
-                uint32_t i = base + lane;
-                if (i < cnt) process(segBase + i);
-            }
-        }
-    }
-    block_count_add(&a.counters->closestRays, 1, nRays);
-    __syncthreads();
-    block_count_add(&a.counters->closestRays, 4, nSamples);
-    __syncthreads();
-    block_count_add(&a.counters->closestRays, 6, nRadiance);
-    if (SLIM && a.primary) { __syncthreads(); block_count_add(&a.counters->closestRays, 7, nSkipped16); }
-}
-
-// ------------------------------------------------------------------ resolve: fold the indices in order (:332-339)
-__global__ __launch_bounds__(kBlock) void wf_resolve(WfArgs a, float4* __restrict__ accumulation, float4* __restrict__ output, uint32_t firstIndex)
-{
-    uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t stride = gridDim.x * blockDim.x;
-    for (; p < a.pixelsPadded; p += stride) {
-        uint32_t tile = p >> 6, within = p & 63u;
-        uint32_t tcol, trow; tile_position(a, tile, tcol, trow);
-        uint32_t px = a.rect.column_x(tcol) + (within & 7u), py = a.rect.y0 + trow * 8u + (within >> 3);
-        if (px >= a.rect.x1 || py >= a.rect.y1) continue;
-        size_t idx = (size_t)py * a.imageWidth + px;
-        float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        for (uint32_t k = 0; k < a.spp; ++k) {
-            float4 r = a.b.radiance[(size_t)k * a.pixelsPadded + p];
-            float4 cur = make_float4(r.x, r.y, r.z, 1.0f);
-            if (firstIndex + k > 0) {
-                float4 prev = (k == 0) ? accumulation[idx] : acc;
-                cur.x += prev.x; cur.y += prev.y; cur.z += prev.z; cur.w += prev.w;
-            }
-            acc = cur;
-        }
-        accumulation[idx] = acc;
-        output[idx] = make_float4(acc.x / acc.w, acc.y / acc.w, acc.z / acc.w, 1.0f);
-    }
-}
-
-// ------------------------------------------------------------------ first-hit G-buffer (hrpt_render_gbuffer)
-// Runs after wf_raygen + wf_extend(0) of a one-sample-per-pixel batch: persistent waves over the segments of path queue 0, like wf_shade. A lane
-// takes one path, reads its ray, sample index and hit record (+ instance on two-level scenes), gathers the triangle / instance / material records
-// from global memory, evaluates gbuffer_texels (pt_gbuffer.h: full_hit_attributes + pbr_attributes, the code wf_shade runs) and stores one float4
-// per requested plane at the sample's pixel. wf_raygen enumerates samples in 8 x 8 pixel tiles and compacts only the padding away, so eight
-// consecutive lanes hold eight consecutive pixels of a row: each plane store of a wave covers whole 128-byte row pieces. planeMask is a kernel
-// argument: the stores are the only code it guards. No shading-class sort and no LDS tables (wf_shade's answers to its long divergent branches and
-// its thirteen gathers per path): this kernel's divergent part is pbr_attributes alone, see DESIGN.md section 15.
-__global__ __launch_bounds__(kBlock) void wf_gbuffer(WfArgs a, HrptPathTracerConstants cb, GBufferPlanes g, uint32_t planeMask)
-{
-    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    const SceneView& s = a.scene;
-    for (uint32_t seg = gw; seg < a.numSegments; seg += totalWaves) {
-        const uint32_t cnt = uniform(a.b.pathCnt[0][seg]), segBase = seg * a.segSize;
-        for (uint32_t base = 0; base < cnt; base += 64) {
-            if (base + lane >= cnt) continue;
-            const uint32_t slot = segBase + base + lane;
-            const float4 o = a.b.rayO[0][slot], d = a.b.rayD[0][slot], ha = a.b.hit[slot];
-            const uint32_t smp = reinterpret_cast<const uint32_t*>(a.b.thr[0] + slot)[3];       // one accumulation index: sample == padded pixel
-            const uint32_t tile = smp >> 6, within = smp & 63u;
-            // tile_position with selects instead of two arms (as two arms the compiler parked the quotient / remainder pair in scratch here)
-            const bool columnMajor = a.rect.stripeCount > 1u;
-            const uint32_t den = columnMajor ? a.tilesY : a.tilesX, quo = tile / den, rem = tile - quo * den;
-            const uint32_t tcol = columnMajor ? quo : rem, trow = columnMajor ? rem : quo;
-            const uint32_t px = a.rect.column_x(tcol) + (within & 7u), py = a.rect.y0 + trow * 8u + (within >> 3);
-            uint32_t tri = __float_as_uint(ha.w);
-            float4 texel[kGbPlanes];
-            if (tri != 0xFFFFFFFFu) {
-                tri &= 0x1FFFFFFFu;                                  // bits 29-31: shading class (wf_extend)
-                Ray ray; ray.o = mk3(o.x, o.y, o.z); ray.d = mk3(d.x, d.y, d.z); ray.tmin = o.w; ray.tmax = 1e10f;
-                Hit h; h.valid = true; h.t = ha.x; h.u = ha.y; h.v = ha.z; h.tri = tri; h.prim = 0; h.inst = s.instances ? a.b.hitInst[slot] : 0u; h.opaque = 1;
-                gbuffer_texels(s, cb, ray, h, texel);
-            } else gbuffer_miss(texel);
-            gbuffer_store(g, planeMask, (size_t)py * a.imageWidth + px, texel);
-        }
-    }
-}
-
-// ------------------------------------------------------------------ first-hit motion vectors (hrpt_render_motion_vectors)
-// wf_gbuffer's loop with one more plane: the motion texel of pt_motion.h (16 bytes per pixel), and the G-buffer texels only when the call names
-// G-buffer planes too (PLANES = planeMask != 0: one traversal serves both; the motion-only instantiation carries none of gbuffer_texels'
-// registers). Held to four waves per SIMD (at most 128 VGPRs) like the shade kernels. The motion gather -- instance record, three indices, three positions, a
-// three-deep dependent chain -- is issued before gbuffer_texels so that it is in flight while pbr_attributes waits for its texels; lanes that
-// missed skip it and store zeros. The pixel lookup is wf_gbuffer's, restated here: that kernel stays the one hrpt_render_gbuffer has always run.
-template <bool PLANES>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void wf_gbuffer_motion(WfArgs a, HrptPathTracerConstants cb, GBufferPlanes g, uint32_t planeMask, MotionArgs m)
-{
-    const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
-    const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
-    const SceneView& s = a.scene;
-    for (uint32_t seg = gw; seg < a.numSegments; seg += totalWaves) {
-        const uint32_t cnt = uniform(a.b.pathCnt[0][seg]), segBase = seg * a.segSize;
-        for (uint32_t base = 0; base < cnt; base += 64) {
-            if (base + lane >= cnt) continue;
-            const uint32_t slot = segBase + base + lane;
-            const float4 o = a.b.rayO[0][slot], d = a.b.rayD[0][slot], ha = a.b.hit[slot];
-            const uint32_t smp = reinterpret_cast<const uint32_t*>(a.b.thr[0] + slot)[3];       // one accumulation index: sample == padded pixel
-            const uint32_t tile = smp >> 6, within = smp & 63u;
-            const bool columnMajor = a.rect.stripeCount > 1u;                                    // tile_position with selects, as in wf_gbuffer
-            const uint32_t den = columnMajor ? a.tilesY : a.tilesX, quo = tile / den, rem = tile - quo * den;
-            const uint32_t tcol = columnMajor ? quo : rem, trow = columnMajor ? rem : quo;
-            const uint32_t px = a.rect.column_x(tcol) + (within & 7u), py = a.rect.y0 + trow * 8u + (within >> 3);
-            const size_t idx = (size_t)py * a.imageWidth + px;
-            uint32_t tri = __float_as_uint(ha.w);
-            float4 texel[kGbPlanes];
-            float4 motion = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (tri != 0xFFFFFFFFu) {
-                tri &= 0x1FFFFFFFu;                                  // bits 29-31: shading class (wf_extend)
-                Hit h; h.valid = true; h.t = ha.x; h.u = ha.y; h.v = ha.z; h.tri = tri; h.prim = 0; h.inst = s.instances ? a.b.hitInst[slot] : 0u; h.opaque = 1;
-                const MotionTri mt = motion_gather(s, m, h);
-                if constexpr (PLANES) {
-                    Ray ray; ray.o = mk3(o.x, o.y, o.z); ray.d = mk3(d.x, d.y, d.z); ray.tmin = o.w; ray.tmax = 1e10f;
-                    gbuffer_texels(s, cb, ray, h, texel);
-                }
-                motion = motion_texel(cb.m_View, m, mt, h.u, h.v);
-            } else if constexpr (PLANES) gbuffer_miss(texel);
-            if constexpr (PLANES) gbuffer_store(g, planeMask, idx, texel);
-            m.plane[idx] = motion;
-        }
-    }
-}
+#include "pt_wf_common.h"      // the device code, one piece per stage, in this order
+#include "pt_wf_raygen.h"
+#include "pt_wf_extend.h"
+#include "pt_wf_shade.h"
+#include "pt_wf_shadow.h"
+#include "pt_wf_gbuffer.h"
 
 // ------------------------------------------------------------------ host side
 // What is launched, on which grid and with how much LDS is decided in pt_wavefront_plan.h; here the plan meets the kernels.
@@ -1608,6 +151,37 @@ void launch_wf_trace_rays(const Variant& v, uint32_t cus, dim3 g, hipStream_t st
         }
     });
 }
+// NEE visibility + accumulation of one bounce on stream `sst`. With non-opaque geometry in the scene: ray generation, the opaque any-hit pass in
+// the refilling traversal kernel, then wf_shadow for the contributions and the (few) rays that crossed non-opaque triangles.
+void shadow_stage(const RenderPlan& plan, const SceneTraits& traits, uint32_t cus, dim3 grid, hipStream_t sst, WfArgs& a, const HrptPathTracerConstants& cb, int bounce)
+{
+    a.shadowParity = (uint32_t)bounce & 1u;
+    if (plan.shadowMode == kShadowResolve) {
+        if (traits.directionalLightsOnly) hipLaunchKernelGGL((wf_shadow_rays<true>), grid, dim3(kBlock), 0, sst, a, cb);
+        else hipLaunchKernelGGL((wf_shadow_rays<false>), grid, dim3(kBlock), 0, sst, a, cb);
+        launch_extend(plan.vA, cus, grid, sst, a, 0u, true);
+    }
+    launch_shadow(plan.vS, grid, sst, a, cb, bounce, traits.directionalLightsOnly, plan.shadowMode);
+}
+// The shading of one bounce: wf_bounce0 (fusedBounce0: trace + shade of bounce 0, by the depth of vE) or the wf_shade / wf_shade_lt the plan and a.primary name
+void launch_shade(const RenderPlan& plan, bool fusedBounce0, dim3 g, hipStream_t st, const WfArgs& a, const HrptPathTracerConstants& cb, uint32_t parity, int bounce, int last)
+{
+    const size_t sortLds = (size_t)(kBlock / 64) * ((size_t)5 * a.segSize);      // per wave: two uint16 permutations (segments A, B) + uint8 class keys
+    auto bounce0 = [&](auto kernel) { hipLaunchKernelGGL(kernel, g, dim3(kBlock), plan.bounce0LdsBytes, st, a, cb, last); };
+    auto shade = [&](auto kernel, size_t ldsBytes) { hipLaunchKernelGGL(kernel, g, dim3(kBlock), ldsBytes, st, a, cb, parity, bounce, last); };
+    if (fusedBounce0) {
+        if (plan.vE.depth <= 16) bounce0(wf_bounce0<16>);
+        else if (plan.vE.depth <= 32) bounce0(wf_bounce0<32>);
+        else bounce0(wf_bounce0<64>);
+    }
+    else if (plan.maxLights > kMaxLights) shade(wf_shade<0, false>, sortLds);
+    else if (plan.maxLights > 1) shade(wf_shade<(int)kMaxLights, false>, sortLds);
+    else if (plan.simpleScene && plan.shadeLdsTables && a.primary) shade(wf_shade_lt<1, true, true>, plan.shadeLdsBytes);
+    else if (plan.simpleScene && plan.shadeLdsTables) shade(wf_shade_lt<1, true>, plan.shadeLdsBytes);
+    else if (plan.simpleScene && a.primary) shade(wf_shade<1, true, true>, plan.shadeLdsBytes);
+    else if (plan.simpleScene) shade(wf_shade<1, true>, plan.shadeLdsBytes);
+    else shade(wf_shade<1, false>, sortLds);
+}
 
 TreeCounts tree_counts(const SceneView& scene) { return { scene.nodeCount, scene.node4Count, scene.triCount, scene.nodesQ != nullptr, scene.instances != nullptr, 0u, 0u }; }
 
@@ -1620,6 +194,27 @@ hipError_t device_cus(WavefrontState& st, uint32_t& cus, std::string& error)
         st.cus = (uint32_t)prop.multiProcessorCount;
     }
     cus = st.cus;
+    return hipSuccess;
+}
+
+// Grows `buf` (of `have` bytes) to at least `bytes`. Work in flight on the context's streams may still use the old allocation, so both are
+// waited for before it goes. After a failure the buffer is empty and `have` 0.
+hipError_t grow_buffer(WavefrontState& st, hipStream_t stream, DeviceBuffer<void>& buf, size_t& have, size_t bytes)
+{
+    if (bytes <= have) return hipSuccess;
+    if (buf) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); }
+    const hipError_t e = buf.alloc(bytes);
+    have = e == hipSuccess ? bytes : 0;
+    return e;
+}
+// The traversal-stack overflow columns of a render or G-buffer plan: two sets (wf_extend and wf_shadow run concurrently) of `entries` ints
+// each (threads x entries per thread; 0 = the tree fits the LDS stack). A G-buffer call sizes them as a render does: the next render keeps the buffer.
+hipError_t reserve_spill(WavefrontState& st, hipStream_t stream, size_t entries, WfArgs& a, std::string& error)
+{
+    if (!entries) return hipSuccess;
+    const hipError_t e = grow_buffer(st, stream, st.spill, st.spillBytes, 2 * entries * 4);
+    if (e != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
+    a.spill[0] = static_cast<int32_t*>(st.spill.get()); a.spill[1] = a.spill[0] + entries;
     return hipSuccess;
 }
 
@@ -1637,13 +232,8 @@ hipError_t wavefront_trace_rays(WavefrontState& st, const SceneView& scene, cons
     a.refillMin = p.refillMin; a.nodeLoopMin = p.nodeLoopMin; a.quantised = p.v.quantised;
     if (p.spillEntries) {
         // own overflow columns (a render may be in flight on the context's buffers only in stream order, but sizes differ)
-        const size_t bytes = p.spillThreads * p.spillEntries * 4;
-        if (bytes > st.traceSpillBytes) {
-            if (st.traceSpill) { (void)hipStreamSynchronize(stream); (void)hipFree(st.traceSpill); st.traceSpill = nullptr; st.traceSpillBytes = 0; }
-            if ((e = hipMalloc(&st.traceSpill, bytes)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
-            st.traceSpillBytes = bytes;
-        }
-        a.spill = static_cast<int32_t*>(st.traceSpill);
+        if ((e = grow_buffer(st, stream, st.traceSpill, st.traceSpillBytes, p.spillThreads * p.spillEntries * 4)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
+        a.spill = static_cast<int32_t*>(st.traceSpill.get());
     }
     launch_wf_trace_rays(p.v, cus, dim3(p.grid), stream, a, shadow);
     if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }
@@ -1658,19 +248,12 @@ bool wavefront_supports(const SceneView& scene, const HrptPathTracerConstants& c
 
 void wavefront_release(WavefrontState& st)
 {
-    if (st.pool) (void)hipFree(st.pool);
-    st.pool = nullptr; st.poolBytes = 0;
-    if (st.spill) (void)hipFree(st.spill);
-    st.spill = nullptr; st.spillBytes = 0;
-    if (st.traceSpill) (void)hipFree(st.traceSpill);
-    st.traceSpill = nullptr; st.traceSpillBytes = 0;
-    if (st.gbPool) (void)hipFree(st.gbPool);
-    st.gbPool = nullptr; st.gbPoolBytes = 0;
-    for (hipEvent_t e : st.events) (void)hipEventDestroy(e);
-    st.events.clear(); st.eventsUsed = 0;
-    for (hipEvent_t e : st.forkEvents) (void)hipEventDestroy(e);
-    for (hipEvent_t e : st.joinEvents) (void)hipEventDestroy(e);
-    st.forkEvents.clear(); st.joinEvents.clear();
+    st.pool.reset(); st.poolBytes = 0;
+    st.spill.reset(); st.spillBytes = 0;
+    st.traceSpill.reset(); st.traceSpillBytes = 0;
+    st.gbPool.reset(); st.gbPoolBytes = 0;
+    for (auto* events : { &st.events, &st.forkEvents, &st.joinEvents }) { for (hipEvent_t e : *events) (void)hipEventDestroy(e); events->clear(); }
+    st.eventsUsed = 0;
     if (st.auxStream) (void)hipStreamDestroy(st.auxStream);
     st.auxStream = nullptr;
 }
@@ -1701,7 +284,7 @@ extern "C" int hrpt_phase_profile_read(unsigned long long* out128)
 void wavefront_reset_timing(WavefrontState& st)
 {
     st.eventsUsed = 0;
-    for (int k = 0; k < 5; ++k) { st.kernelMs[k] = 0.0f; st.kernelLaunches[k] = 0; }
+    for (int k = 0; k < kKernelClasses; ++k) { st.kernelMs[k] = 0.0f; st.kernelLaunches[k] = 0; }
     st.raygenBytes = 0; st.resolveBytes = 0;
 }
 
@@ -1733,7 +316,7 @@ void wavefront_queue_bytes(const WavefrontState& st, const DeviceCounters& c, ui
 
 namespace {
 // records an event; pairs are (begin, end) around one launch of kernel class `kind`
-bool timing_mark(WavefrontState& st, hipStream_t stream, int kind, bool begin)
+bool timing_mark(WavefrontState& st, hipStream_t stream, KernelClass kind, bool begin)
 {
     if (st.eventsUsed >= 4096) return true;   // a single render never needs more; stop timing rather than grow unbounded
     if (st.eventsUsed + 1 > st.events.size()) {
@@ -1746,33 +329,104 @@ bool timing_mark(WavefrontState& st, hipStream_t stream, int kind, bool begin)
     st.eventsUsed++;
     return true;
 }
-
-// Queue pool layout: every stream of WfBuffers (and the PrimaryArgs copy) at a 256-byte aligned offset from `base`, in this order; returns the
-// bytes used. Run against a null base for the size, then against the allocation. A stream the scene does not have points at the base (hitInst: null).
-size_t carve_pool(char* base, WfArgs& a, uint64_t capacity, uint32_t segs, uint32_t maxLights, const SceneTraits& traits, bool hasInstances)
-{
-    const bool hasMedium = traits.hasMedium, hasShadowRayQueue = traits.hasNonOpaque || maxLights > 1;
-    size_t off = 0;
-    auto carve = [&](auto*& stream, size_t bytes, bool present = true) {
-        stream = reinterpret_cast<std::remove_reference_t<decltype(stream)>>(reinterpret_cast<uintptr_t>(base) + (present ? off : 0));
+// Lays the streams of a queue pool down: each at a 256-byte aligned offset from `base`, in call order; a stream the scene does not have
+// (present = false) points at the base and takes no room. Run against a null base for the size (`off`), then against the allocation.
+struct PoolCarver {
+    char* base; size_t off = 0;
+    template <class T> void operator()(T*& stream, size_t bytes, bool present = true)
+    {
+        stream = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + (present ? off : 0));
         if (present) off += (bytes + 255) & ~(size_t)255;
-    };
-    WfBuffers& b = a.b;
-    for (int p = 0; p < 2; ++p) {
+    }
+};
+size_t counter_bytes(uint64_t capacity) { return (size_t)(capacity / 64) * 4; }      // one count per segment, sized for the smallest segment (64 samples)
+// What every pool starts with: the first `queues` path queues, the hit records and, on two-level scenes, the hit's instance (else hitInst: null)
+void carve_paths_and_hits(PoolCarver& carve, WfBuffers& b, int queues, uint64_t capacity, bool hasMedium, bool hasInstances)
+{
+    for (int p = 0; p < queues; ++p) {
         carve(b.rayO[p], capacity * 16); carve(b.rayD[p], capacity * 16); carve(b.thr[p], capacity * 16);
         carve(b.med0[p], capacity * 16, hasMedium); carve(b.med1[p], capacity * 16, hasMedium);
-        carve(b.pathCnt[p], (size_t)segs * 4);
+        carve(b.pathCnt[p], counter_bytes(capacity));
     }
     carve(b.hit, capacity * 16);
     carve(b.hitInst, capacity * 4, hasInstances); if (!hasInstances) b.hitInst = nullptr;
+}
+// Queue pool of a render: every stream of WfBuffers (and the PrimaryArgs copy), in this order; returns the bytes used.
+size_t carve_pool(char* base, WfArgs& a, uint64_t capacity, uint32_t maxLights, const SceneTraits& traits, bool hasInstances)
+{
+    const bool hasShadowRayQueue = traits.hasNonOpaque || maxLights > 1;
+    PoolCarver carve{ base };
+    WfBuffers& b = a.b;
+    carve_paths_and_hits(carve, b, 2, capacity, traits.hasMedium, hasInstances);
     carve(a.primaryArgs, sizeof(PrimaryArgs));
     carve(b.sh0, capacity * 16); carve(b.sh1, capacity * 16); carve(b.sh2, capacity * 16); carve(b.sh3, capacity * 16); carve(b.sh4, capacity * 16);
     carve(b.shL, capacity * 16 * maxLights);
-    carve(b.shadowCnt, (size_t)segs * 4); carve(b.radiance, capacity * 16);
+    carve(b.shadowCnt, counter_bytes(capacity)); carve(b.radiance, capacity * 16);
     // (the shadow mode is the plan's; the arrays are small next to the path queues)
     carve(b.sqO, capacity * 16 * maxLights, hasShadowRayQueue); carve(b.sqD, capacity * 16 * maxLights, hasShadowRayQueue); carve(b.sqId, capacity * 4 * maxLights, hasShadowRayQueue);
-    carve(b.sqCnt, (size_t)segs * 4, hasShadowRayQueue); carve(b.shVis, capacity * 4 * maxLights, hasShadowRayQueue); carve(b.sqCand, capacity * 8 * kShadowCandidates * maxLights, hasShadowRayQueue);
-    return off;
+    carve(b.sqCnt, counter_bytes(capacity), hasShadowRayQueue); carve(b.shVis, capacity * 4 * maxLights, hasShadowRayQueue); carve(b.sqCand, capacity * 8 * kShadowCandidates * maxLights, hasShadowRayQueue);
+    return carve.off;
+}
+// Queue pool of a G-buffer call: path queue 0, hit records, the radiance slots wf_raygen zeroes and a scratch counter block (the front end counts
+// rays and paths; HrptStats describes renders, so these counts go nowhere).
+size_t carve_gbuffer_pool(char* base, WfArgs& a, uint64_t capacity, bool hasMedium, bool hasInstances)
+{
+    PoolCarver carve{ base };
+    carve_paths_and_hits(carve, a.b, 1, capacity, hasMedium, hasInstances);
+    carve(a.b.radiance, capacity * 16);
+    carve(a.counters, sizeof(DeviceCounters) * kCounterShards);
+    return carve.off;
+}
+// The part of WfArgs that scene, traits, rectangle and knobs decide; what a plan decides is the caller's (everything else stays zero)
+void fill_scene_args(WfArgs& a, const WavefrontState& st, const SceneView& scene, const SceneTraits& traits, TileRect rect, uint32_t width)
+{
+    a.scene = scene;
+    a.tilesX = rect.columns(); a.tilesY = (rect.y1 - rect.y0 + 7) / 8; a.rect = rect; a.imageWidth = width; a.pixelsPadded = a.tilesX * a.tilesY * 64;
+    a.hasMedium = traits.hasMedium ? 1u : 0u; a.hasStochasticAlpha = traits.hasStochasticAlpha ? 1u : 0u; a.allOpaque = traits.hasNonOpaque ? 0u : 1u;
+    a.refillMin = st.knobs.refillMin ? st.knobs.refillMin : kRefillMinDefault; a.streamSegments = st.knobs.drainSegments ? 0u : 1u;
+}
+// Step 1 of a render: the accumulation indices per batch, so that one batch stays below maxSamples AND its queue pool below a byte budget,
+// and the queue pool of such a batch (again with half the indices per batch when the device refuses the allocation), carved into `a`.
+hipError_t size_batch_and_pool(WavefrontState& st, const RenderPlan& plan, const SceneTraits& traits, bool hasInstances, uint64_t pixelsPadded, uint32_t accumCount,
+                               hipStream_t stream, WfArgs& a, uint32_t& sppPerBatch, std::string& error)
+{
+    sppPerBatch = accumCount < kMaxSppPerBatch ? accumCount : kMaxSppPerBatch;
+    uint64_t maxSamples = 64ull << 20;
+    if (pixelsPadded * sppPerBatch * plan.bytesPerSample > st.poolBytes) {
+        // the pool has to grow: keep it within half of what the device has free (other contexts -- a second frame in flight -- need theirs)
+        size_t freeB = 0, totalB = 0;
+        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+            const uint64_t budget = (uint64_t)(freeB + st.poolBytes) / 2;
+            if (budget / plan.bytesPerSample < maxSamples) maxSamples = budget / plan.bytesPerSample;
+        }
+    }
+    if (maxSamples * plan.maxLights > 0xFFFFFFFFull) maxSamples = 0xFFFFFFFFull / plan.maxLights;      // (entry, light) slot ids are 32-bit
+    while (sppPerBatch > 1 && pixelsPadded * sppPerBatch > maxSamples) --sppPerBatch;
+    for (;;) {
+        const uint64_t capacity = ((pixelsPadded * sppPerBatch + kMaxSegment - 1) / kMaxSegment) * kMaxSegment;
+        if (capacity >= (1ull << 31)) { error = "tile too large for one batch"; return hipErrorInvalidValue; }
+        const size_t bytes = carve_pool(nullptr, a, capacity, plan.maxLights, traits, hasInstances);
+        const hipError_t e = grow_buffer(st, stream, st.pool, st.poolBytes, bytes);
+        if (e == hipSuccess) { carve_pool(static_cast<char*>(st.pool.get()), a, capacity, plan.maxLights, traits, hasInstances); return hipSuccess; }
+        (void)hipGetLastError();
+        if (sppPerBatch == 1) {       // nothing left to halve
+            error = "hipMalloc(queue pool, " + std::to_string(bytes >> 20) + " MiB for " + std::to_string(capacity) + " samples; render a smaller tile)";
+            return e;
+        }
+        sppPerBatch = (sppPerBatch + 1) / 2;
+    }
+}
+// The second stream and one fork and one join event per bounce, made at first use. false: the runtime refused one; this render runs serially
+bool prepare_overlap(WavefrontState& st, int maxBounces)
+{
+    if (!st.auxStream && hipStreamCreateWithFlags(&st.auxStream, hipStreamNonBlocking) != hipSuccess) { st.auxStream = nullptr; return false; }
+    while (st.forkEvents.size() < (size_t)maxBounces) {
+        hipEvent_t f, j;
+        if (hipEventCreateWithFlags(&f, hipEventDisableTiming) != hipSuccess) return false;
+        if (hipEventCreateWithFlags(&j, hipEventDisableTiming) != hipSuccess) { (void)hipEventDestroy(f); return false; }
+        st.forkEvents.push_back(f); st.joinEvents.push_back(j);
+    }
+    return true;
 }
 }
 
@@ -1787,60 +441,17 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
     TreeCounts tree = tree_counts(scene);
     tree.instanceCount = st.shadeInstances; tree.materialCount = st.shadeMaterials;
     const RenderPlan& plan = st.plan = plan_render(traits, tree, constants.m_LightCount, cus, st.knobs);
-    const uint32_t maxLights = plan.maxLights;
-    const uint32_t tilesX = rect.columns(), tilesY = (rect.y1 - rect.y0 + 7) / 8;
-    const uint64_t pixelsPadded = (uint64_t)tilesX * tilesY * 64;
-    // batch the accumulation indices so that one batch stays below maxSamples AND its queue pool below a byte budget
-    uint32_t sppPerBatch = accumCount < kMaxSppPerBatch ? accumCount : kMaxSppPerBatch;
-    uint64_t maxSamples = 64ull << 20;
-    if (pixelsPadded * sppPerBatch * plan.bytesPerSample > st.poolBytes) {
-        // the pool has to grow: keep it within half of what the device has free (other contexts -- a second frame in flight -- need theirs)
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-            const uint64_t budget = (uint64_t)(freeB + st.poolBytes) / 2;
-            if (budget / plan.bytesPerSample < maxSamples) maxSamples = budget / plan.bytesPerSample;
-        }
-    }
-    if (maxSamples * maxLights > 0xFFFFFFFFull) maxSamples = 0xFFFFFFFFull / maxLights;      // (entry, light) slot ids are 32-bit
-    while (sppPerBatch > 1 && pixelsPadded * sppPerBatch > maxSamples) --sppPerBatch;
-    // ---- queue pool (again with half the accumulation indices per batch when the device refuses the allocation)
+    // ---- 1. the batch size, the queue pool and the overflow columns
     WfArgs a{};
-    uint64_t capacity = 0; uint32_t segs = 0;
-    for (;;) {
-        capacity = ((pixelsPadded * sppPerBatch + kMaxSegment - 1) / kMaxSegment) * kMaxSegment;
-        if (capacity >= (1ull << 31)) { error = "tile too large for one batch"; return hipErrorInvalidValue; }
-        segs = (uint32_t)(capacity / 64);   // counter arrays sized for the smallest segment
-        const size_t bytes = carve_pool(nullptr, a, capacity, segs, maxLights, traits, scene.instances != nullptr);
-        if (bytes <= st.poolBytes) break;
-        if (st.pool) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); (void)hipFree(st.pool); st.pool = nullptr; st.poolBytes = 0; }
-        e = hipMalloc(&st.pool, bytes);
-        if (e == hipSuccess) { st.poolBytes = bytes; break; }
-        (void)hipGetLastError();
-        if (sppPerBatch == 1) {       // nothing left to halve
-            error = "hipMalloc(queue pool, " + std::to_string(bytes >> 20) + " MiB for " + std::to_string(capacity) + " samples; render a smaller tile)";
-            return e;
-        }
-        sppPerBatch = (sppPerBatch + 1) / 2;
-    }
-    carve_pool(static_cast<char*>(st.pool), a, capacity, segs, maxLights, traits, scene.instances != nullptr);
-    if (plan.spillEntries) {
-        const size_t bytes = 2 * plan.spillThreads * plan.spillEntries * 4;
-        if (bytes > st.spillBytes) {
-            if (st.spill) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); (void)hipFree(st.spill); st.spill = nullptr; st.spillBytes = 0; }
-            if ((e = hipMalloc(&st.spill, bytes)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
-            st.spillBytes = bytes;
-        }
-        a.spill[0] = static_cast<int32_t*>(st.spill); a.spill[1] = a.spill[0] + plan.spillThreads * plan.spillEntries;
-    }
-    a.scene = scene;
-    a.tilesX = tilesX; a.tilesY = tilesY; a.rect = rect; a.imageWidth = width; a.pixelsPadded = (uint32_t)pixelsPadded;
-    a.maxLights = maxLights; a.hasMedium = traits.hasMedium ? 1u : 0u; a.hasStochasticAlpha = traits.hasStochasticAlpha ? 1u : 0u; a.allOpaque = traits.hasNonOpaque ? 0u : 1u;
-    a.counters = counters;
-    a.refillMin = st.knobs.refillMin ? st.knobs.refillMin : kRefillMinDefault; a.streamSegments = st.knobs.drainSegments ? 0u : 1u; a.sortShade = plan.sortShade; a.nodeLoopMin = plan.nodeLoopMin;
-    a.slimShadow = plan.slim ? 1u : 0u;
+    fill_scene_args(a, st, scene, traits, rect, width);
+    const uint64_t pixelsPadded = (uint64_t)a.tilesX * a.tilesY * 64;
+    uint32_t sppPerBatch = 0;
+    if ((e = size_batch_and_pool(st, plan, traits, scene.instances != nullptr, pixelsPadded, accumCount, stream, a, sppPerBatch, error)) != hipSuccess) return e;
+    if ((e = reserve_spill(st, stream, plan.spillThreads * plan.spillEntries, a, error)) != hipSuccess) return e;
+    // ---- 2. the arguments the plan decides
+    a.maxLights = plan.maxLights; a.sortShade = plan.sortShade; a.nodeLoopMin = plan.nodeLoopMin; a.slimShadow = plan.slim ? 1u : 0u; a.counters = counters;
     a.shadeInstances = tree.instanceCount; a.shadeMaterials = tree.materialCount;       // the counts the plan sized the LDS tables from
-    const bool fusedPrimary = plan.fusedPrimary;
-
+    // ---- 3. per batch: raygen, the bounces (wf_shadow of one overlapping wf_extend of the next), resolve
     for (uint32_t first = 0; first < accumCount; first += sppPerBatch) {
         const uint32_t spp = (accumCount - first) < sppPerBatch ? (accumCount - first) : sppPerBatch;
         a.spp = spp; a.numSamples = (uint32_t)(pixelsPadded * spp);
@@ -1856,7 +467,7 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
             jt.j[k].y = hrpt_halton(cb.m_AccumulationIndex + k + 1, 3) - 0.5f;
         }
         PrimaryArgs pr{};
-        if (fusedPrimary) {
+        if (plan.fusedPrimary) {
             for (int i = 0; i < 16; ++i) pr.clipToWorld[i] = cb.m_View.m_MatClipToWorldNoOffset[i];
             for (int i = 0; i < 3; ++i) pr.cam[i] = cb.m_CameraPos[i];
             pr.invW = cb.m_View.m_ViewportSizeInv[0]; pr.invH = cb.m_View.m_ViewportSizeInv[1]; pr.accumIndex = cb.m_AccumulationIndex;
@@ -1864,15 +475,15 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
             hipLaunchKernelGGL(wf_store_primary, dim3(1), dim3(64), 0, stream, pr, const_cast<PrimaryArgs*>(a.primaryArgs));
         }
         const bool timedEnds = st.profile && st.eventsUsed + 4 <= 4096;
-        if (!fusedPrimary) {
-            if (timedEnds) timing_mark(st, stream, 3, true);
+        if (!plan.fusedPrimary) {
+            if (timedEnds) timing_mark(st, stream, kKernelRaygen, true);
             hipLaunchKernelGGL(wf_raygen, grid, dim3(kBlock), 0, stream, a, cb, jt);
-            if (timedEnds) timing_mark(st, stream, 3, false);
+            if (timedEnds) timing_mark(st, stream, kKernelRaygen, false);
         }
         {   // raygen: sampleRadiance zeroed + one path record per pixel of the rectangle and index; resolve: sampleRadiance read, Accumulation
             // read (when resuming) and written, Output written
             const uint64_t w = (uint64_t)rect.columns() * 8u, px = (w < rect.x1 - rect.x0 ? w : (uint64_t)rect.x1 - rect.x0) * (rect.y1 - rect.y0);
-            if (!fusedPrimary) st.raygenBytes += (uint64_t)a.numSamples * 16 + px * spp * st.plan.pathRecordBytes;
+            if (!plan.fusedPrimary) st.raygenBytes += (uint64_t)a.numSamples * 16 + px * spp * st.plan.pathRecordBytes;
             st.resolveBytes += px * ((uint64_t)spp * 16 + 32 + (cb.m_AccumulationIndex > 0 ? 16 : 0));
         }
         const int maxBounces = (int)cb.m_MaxBounces;
@@ -1880,93 +491,38 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
         // writes hit records: no shared buffer, so the two run concurrently (fork after shade(b), join before shade(b+1), which both
         // rewrites the shadow queue and adds the next radiance term -- the per-sample order of additions is unchanged).
         // Per-launch timing (HRPT_FRAME_PROFILE) needs stream order, so profiling renders serially.
-        bool overlap = !st.profile && !st.knobs.serialShadow && maxBounces > 1;
-        if (overlap) {
-            if (!st.auxStream && hipStreamCreateWithFlags(&st.auxStream, hipStreamNonBlocking) != hipSuccess) { st.auxStream = nullptr; overlap = false; }
-            while (overlap && st.forkEvents.size() < (size_t)maxBounces) {
-                hipEvent_t f, j;
-                if (hipEventCreateWithFlags(&f, hipEventDisableTiming) != hipSuccess) { overlap = false; break; }
-                if (hipEventCreateWithFlags(&j, hipEventDisableTiming) != hipSuccess) { (void)hipEventDestroy(f); overlap = false; break; }
-                st.forkEvents.push_back(f); st.joinEvents.push_back(j);
-            }
-        }
-        // NEE visibility + accumulation. With non-opaque geometry in the scene: ray generation, the opaque any-hit pass in the refilling
-        // traversal kernel, then wf_shadow for the contributions and the (few) rays that crossed non-opaque triangles.
-        auto shadow_stage = [&](hipStream_t sst, int bounce) {
-            a.shadowParity = (uint32_t)bounce & 1u;
-            if (plan.shadowMode == kShadowResolve) {
-                if (traits.directionalLightsOnly) hipLaunchKernelGGL((wf_shadow_rays<true>), grid, dim3(kBlock), 0, sst, a, cb);
-                else hipLaunchKernelGGL((wf_shadow_rays<false>), grid, dim3(kBlock), 0, sst, a, cb);
-                launch_extend(plan.vA, cus, grid, sst, a, 0u, true);
-            }
-            launch_shadow(plan.vS, grid, sst, a, cb, bounce, traits.directionalLightsOnly, plan.shadowMode);
-        };
+        const bool overlap = !st.profile && !st.knobs.serialShadow && maxBounces > 1 && prepare_overlap(st, maxBounces);
         bool pendingJoin = false;
         for (int bounce = 0; bounce < maxBounces; ++bounce) {
             const uint32_t parity = (uint32_t)bounce & 1u;
             const bool timed = st.profile && st.eventsUsed + 8 <= 4096;
-            a.primary = (fusedPrimary && bounce == 0) ? 1u : 0u;
+            a.primary = (plan.fusedPrimary && bounce == 0) ? 1u : 0u;
             const bool fusedBounce0 = plan.fusedBounce0 && bounce == 0;      // wf_bounce0 in place of the pair below, on the shade grid, timed as wf_shade
-            if (timed && !fusedBounce0) timing_mark(st, stream, 0, true);
+            if (timed && !fusedBounce0) timing_mark(st, stream, kKernelExtend, true);
             if (!fusedBounce0) launch_extend(plan.vE, cus, dim3(batch.gridExtend), stream, a, parity);
-            if (timed) { if (!fusedBounce0) timing_mark(st, stream, 0, false); timing_mark(st, stream, 1, true); }
+            if (timed) { if (!fusedBounce0) timing_mark(st, stream, kKernelExtend, false); timing_mark(st, stream, kKernelShade, true); }
             if (pendingJoin) { if ((e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)bounce - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; } pendingJoin = false; }
-            const int last = bounce + 1 == maxBounces ? 1 : 0;
-            const size_t sortLds = (size_t)(kBlock / 64) * ((size_t)5 * a.segSize);      // per wave: two uint16 permutations (segments A, B) + uint8 class keys
-            if (fusedBounce0) {
-                if (plan.vE.depth <= 16) hipLaunchKernelGGL((wf_bounce0<16>), grid, dim3(kBlock), plan.bounce0LdsBytes, stream, a, cb, last);
-                else if (plan.vE.depth <= 32) hipLaunchKernelGGL((wf_bounce0<32>), grid, dim3(kBlock), plan.bounce0LdsBytes, stream, a, cb, last);
-                else hipLaunchKernelGGL((wf_bounce0<64>), grid, dim3(kBlock), plan.bounce0LdsBytes, stream, a, cb, last);
-            }
-            else if (maxLights > kMaxLights) hipLaunchKernelGGL((wf_shade<0, false>), grid, dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
-            else if (maxLights > 1) hipLaunchKernelGGL((wf_shade<(int)kMaxLights, false>), grid, dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
-            else if (plan.simpleScene && plan.shadeLdsTables && a.primary) hipLaunchKernelGGL((wf_shade_lt<1, true, true>), grid, dim3(kBlock), plan.shadeLdsBytes, stream, a, cb, parity, bounce, last);
-            else if (plan.simpleScene && plan.shadeLdsTables) hipLaunchKernelGGL((wf_shade_lt<1, true>), grid, dim3(kBlock), plan.shadeLdsBytes, stream, a, cb, parity, bounce, last);
-            else if (plan.simpleScene && a.primary) hipLaunchKernelGGL((wf_shade<1, true, true>), grid, dim3(kBlock), plan.shadeLdsBytes, stream, a, cb, parity, bounce, last);
-            else if (plan.simpleScene) hipLaunchKernelGGL((wf_shade<1, true>), grid, dim3(kBlock), plan.shadeLdsBytes, stream, a, cb, parity, bounce, last);
-            else hipLaunchKernelGGL((wf_shade<1, false>), grid, dim3(kBlock), sortLds, stream, a, cb, parity, bounce, last);
-            if (timed) { timing_mark(st, stream, 1, false); timing_mark(st, stream, 2, true); }
+            launch_shade(plan, fusedBounce0, grid, stream, a, cb, parity, bounce, bounce + 1 == maxBounces ? 1 : 0);
+            if (timed) { timing_mark(st, stream, kKernelShade, false); timing_mark(st, stream, kKernelShadow, true); }
             if (overlap) {
                 if ((e = hipEventRecord(st.forkEvents[(size_t)bounce], stream)) != hipSuccess ||
                     (e = hipStreamWaitEvent(st.auxStream, st.forkEvents[(size_t)bounce], 0)) != hipSuccess) { error = "fork to the shadow stream"; return e; }
-                shadow_stage(st.auxStream, bounce);
+                shadow_stage(plan, traits, cus, grid, st.auxStream, a, cb, bounce);
                 if ((e = hipEventRecord(st.joinEvents[(size_t)bounce], st.auxStream)) != hipSuccess) { error = "hipEventRecord(join)"; return e; }
                 pendingJoin = true;
             } else {
-                shadow_stage(stream, bounce);
+                shadow_stage(plan, traits, cus, grid, stream, a, cb, bounce);
             }
-            if (timed) timing_mark(st, stream, 2, false);
+            if (timed) timing_mark(st, stream, kKernelShadow, false);
         }
         if (pendingJoin && (e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)maxBounces - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; }
         uint32_t rgrid = (uint32_t)((pixelsPadded + kBlock - 1) / kBlock); if (rgrid > cus * 8) rgrid = cus * 8;
-        if (timedEnds) timing_mark(st, stream, 4, true);
+        if (timedEnds) timing_mark(st, stream, kKernelResolve, true);
         hipLaunchKernelGGL(wf_resolve, dim3(rgrid), dim3(kBlock), 0, stream, a, accumulation, output, cb.m_AccumulationIndex);
-        if (timedEnds) timing_mark(st, stream, 4, false);
+        if (timedEnds) timing_mark(st, stream, kKernelResolve, false);
         if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }
     }
     return hipSuccess;
-}
-
-namespace {
-// Queue pool of a G-buffer call: path queue 0, hit records, the radiance slots wf_raygen zeroes and a scratch counter block (the front end counts
-// rays and paths; HrptStats describes renders, so these counts go nowhere). Same conventions as carve_pool.
-size_t carve_gbuffer_pool(char* base, WfArgs& a, uint64_t capacity, uint32_t segs, bool hasMedium, bool hasInstances)
-{
-    size_t off = 0;
-    auto carve = [&](auto*& stream, size_t bytes, bool present = true) {
-        stream = reinterpret_cast<std::remove_reference_t<decltype(stream)>>(reinterpret_cast<uintptr_t>(base) + (present ? off : 0));
-        if (present) off += (bytes + 255) & ~(size_t)255;
-    };
-    WfBuffers& b = a.b;
-    carve(b.rayO[0], capacity * 16); carve(b.rayD[0], capacity * 16); carve(b.thr[0], capacity * 16);
-    carve(b.med0[0], capacity * 16, hasMedium); carve(b.med1[0], capacity * 16, hasMedium);
-    carve(b.pathCnt[0], (size_t)segs * 4);
-    carve(b.hit, capacity * 16);
-    carve(b.hitInst, capacity * 4, hasInstances); if (!hasInstances) b.hitInst = nullptr;
-    carve(b.radiance, capacity * 16);
-    carve(a.counters, sizeof(DeviceCounters) * kCounterShards);
-    return off;
-}
 }
 
 // hrpt_render_gbuffer, wavefront path: wf_raygen + the render's closest-hit kernel over one sample per pixel of `rect` (plan_gbuffer), then
@@ -1978,39 +534,23 @@ hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const S
     if (rect.x1 <= rect.x0 || rect.y1 <= rect.y0 || rect.columns() == 0) return hipSuccess;
     hipError_t e; uint32_t cus = 0;
     if ((e = device_cus(st, cus, error)) != hipSuccess) return e;
-    const uint32_t tilesX = rect.columns(), tilesY = (rect.y1 - rect.y0 + 7) / 8;
-    const uint64_t pixelsPadded = (uint64_t)tilesX * tilesY * 64;
+    WfArgs a{};
+    fill_scene_args(a, st, scene, traits, rect, width);
+    const uint64_t pixelsPadded = (uint64_t)a.tilesX * a.tilesY * 64;
     const uint64_t capacity = ((pixelsPadded + kMaxSegment - 1) / kMaxSegment) * kMaxSegment;
     if (capacity >= (1ull << 31)) { error = "tile too large for one batch"; return hipErrorInvalidValue; }
     const GBufferPlan plan = plan_gbuffer(traits, tree_counts(scene), cus, st.knobs, (uint32_t)pixelsPadded);
-    WfArgs a{};
-    const uint32_t segs = (uint32_t)(capacity / 64);
-    const size_t bytes = carve_gbuffer_pool(nullptr, a, capacity, segs, traits.hasMedium, scene.instances != nullptr);
-    char* pool = static_cast<char*>(st.pool);
+    const size_t bytes = carve_gbuffer_pool(nullptr, a, capacity, traits.hasMedium, scene.instances != nullptr);
+    char* pool = static_cast<char*>(st.pool.get());
     if (bytes > st.poolBytes) {
-        if (bytes > st.gbPoolBytes) {
-            if (st.gbPool) { (void)hipStreamSynchronize(stream); (void)hipFree(st.gbPool); st.gbPool = nullptr; st.gbPoolBytes = 0; }
-            if ((e = hipMalloc(&st.gbPool, bytes)) != hipSuccess) { error = "hipMalloc(G-buffer queue pool, " + std::to_string(bytes >> 20) + " MiB)"; return e; }
-            st.gbPoolBytes = bytes;
-        }
-        pool = static_cast<char*>(st.gbPool);
+        if ((e = grow_buffer(st, stream, st.gbPool, st.gbPoolBytes, bytes)) != hipSuccess) { error = "hipMalloc(G-buffer queue pool, " + std::to_string(bytes >> 20) + " MiB)"; return e; }
+        pool = static_cast<char*>(st.gbPool.get());
     }
-    carve_gbuffer_pool(pool, a, capacity, segs, traits.hasMedium, scene.instances != nullptr);
-    if (plan.spillEntries) {
-        const size_t spillBytes = 2 * plan.spillThreads * plan.spillEntries * 4;      // sized as a render sizes it: the next render keeps the buffer
-        if (spillBytes > st.spillBytes) {
-            if (st.spill) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); (void)hipFree(st.spill); st.spill = nullptr; st.spillBytes = 0; }
-            if ((e = hipMalloc(&st.spill, spillBytes)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
-            st.spillBytes = spillBytes;
-        }
-        a.spill[0] = static_cast<int32_t*>(st.spill); a.spill[1] = a.spill[0] + plan.spillThreads * plan.spillEntries;
-    }
-    a.scene = scene;
-    a.tilesX = tilesX; a.tilesY = tilesY; a.rect = rect; a.imageWidth = width; a.pixelsPadded = (uint32_t)pixelsPadded;
-    a.spp = 1; a.numSamples = (uint32_t)pixelsPadded; a.segSize = plan.batch.segSize; a.numSegments = plan.batch.numSegments;
-    a.maxLights = 1; a.hasMedium = traits.hasMedium ? 1u : 0u; a.hasStochasticAlpha = traits.hasStochasticAlpha ? 1u : 0u; a.allOpaque = traits.hasNonOpaque ? 0u : 1u;
-    a.refillMin = st.knobs.refillMin ? st.knobs.refillMin : kRefillMinDefault; a.streamSegments = st.knobs.drainSegments ? 0u : 1u; a.nodeLoopMin = plan.nodeLoopMin;
-    a.primary = 0u;
+    carve_gbuffer_pool(pool, a, capacity, traits.hasMedium, scene.instances != nullptr);
+    if ((e = reserve_spill(st, stream, plan.spillThreads * plan.spillEntries, a, error)) != hipSuccess) return e;
+    // one sample per pixel, one light slot, rays from the path queue; no shading-class sort and no slim shadow entries (both stay zero)
+    a.maxLights = 1; a.spp = 1; a.primary = 0u; a.nodeLoopMin = plan.nodeLoopMin;
+    a.numSamples = (uint32_t)pixelsPadded; a.segSize = plan.batch.segSize; a.numSegments = plan.batch.numSegments;
     JitterTable jt{};
     jt.j[0].x = constants.m_Jitter[0]; jt.j[0].y = constants.m_Jitter[1];      // the caller's jitter, not the Halton point of the index (pass 0 for pixel centres)
     GBufferPlanes g; for (uint32_t k = 0; k < kGbPlanes; ++k) g.plane[k] = planes[k];

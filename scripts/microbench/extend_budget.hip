@@ -7,12 +7,12 @@
 using namespace hrt;
 namespace {
 constexpr uint32_t kBlk = 256;
-struct Stack {          // the LDS stack of pt_wavefront.hip (16 rows, no spill)
+struct Stack {          // the LDS stack of pt_wf_common.h (16 rows, no spill)
     int32_t* base;
     HRT_DEV void push(int sp, int32_t v) { base[(sp & 15) * kBlk] = v; }
     HRT_DEV int32_t pop(int sp) { return base[(sp & 15) * kBlk]; }
 };
-struct LdsTree {        // the LDS copy of the 4-wide tree (pt_wavefront.hip LdsBvh<4>)
+struct LdsTree {        // the LDS copy of the 4-wide tree (pt_wf_common.h LdsBvh<4>)
     static constexpr int kWidth = 4; static constexpr bool kTwoLevel = false; static constexpr bool kLds = true;
     const float4* nodes; const float4* tris;
     typedef __attribute__((address_space(3))) const char* LdsPtr;

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void walk_coop(const uint4* __restrict__ nodes
     out[blockIdx.x * 256u + threadIdx.x] = acc + idx;
 }
 
-// The gather pattern of wf_shade (pt_wavefront.hip): every lane reads ROWS 16-byte rows of one 80-byte record of a 3 KB table (38 records, config 2's
+// The gather pattern of wf_shade (pt_wf_shade.h): every lane reads ROWS 16-byte rows of one 80-byte record of a 3 KB table (38 records, config 2's
 // GpuTriAttr table), and RUN consecutive lanes address the SAME record (lanes of a wave that hit the same triangle). LDS = false: global_load_dwordx4
 // from the L1-resident table; LDS = true: the block copies the table to LDS first and reads it with ds_read_b128 (address_space(3) pointers).
 // Run with: ./gather_nodes shade

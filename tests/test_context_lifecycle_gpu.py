@@ -1,5 +1,5 @@
-"""Lifetime of a context's device buffers (csrc/pt_capi_internal.h: DeviceBuffer and the per-scene / per-size / per-context groups of
-HrptContext). One context goes twice through resize -> upload -> every call that allocates a buffer lazily -> resize to another size and
+"""Lifetime of a context's device buffers (csrc/pt_device_buffer.h: DeviceBuffer; csrc/pt_capi_internal.h: the per-scene / per-size /
+per-context groups of HrptContext). One context goes twice through resize -> upload -> every call that allocates a buffer lazily -> resize to another size and
 back -> upload again; every image read back in the second pass equals the first pass bit for bit, a released animation is unknown to the
 context afterwards, and a second context that lives and dies between the passes changes nothing. Cornell-class scene at 16 x 8, the
 gentle 4-joint pose of tests/skin_cases.py on its 28 vertices, the 5-joint skeleton of tests/anim_cases.py. No memory is measured."""

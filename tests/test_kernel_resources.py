@@ -1,6 +1,6 @@
 """Register / scratch budget of the wavefront kernels, read from the code-object metadata of the built library (no GPU needed).
 
-Why a test: several kernels are compiled for a FORCED number of waves per SIMD (amdgpu_waves_per_eu, pt_wavefront.hip), i.e. into fewer
+Why a test: several kernels are compiled for a FORCED number of waves per SIMD (amdgpu_waves_per_eu, pt_wf_extend.h), i.e. into fewer
 registers than the compiler would take. While the library was still built with the SLP vectoriser, exactly that forcing gave a wf_shade
 that spilled (68 B of scratch per lane) and rendered every sky pixel 5-10 % wrong (reproducible with
 `make -C hobbyrenderer_amd/csrc variant NAME=slp EXTRA="-Xarch_device -fslp-vectorize"` + tests/test_parity_gpu.py seed 1). The parity

@@ -1,4 +1,4 @@
-"""wf_bounce0 (bounce 0 traced and shaded in one kernel, pt_wavefront.hip): register, scratch and LDS budget of every instantiation, read from
+"""wf_bounce0 (bounce 0 traced and shaded in one kernel, pt_wf_shade.h): register, scratch and LDS budget of every instantiation, read from
 the code-object metadata of the built library -- the method of tests/test_kernel_resources_shade_lt.py, no GPU needed.
 
 The kernel is compiled for a forced four waves per SIMD like wf_shade, whose history of miscompiles under register pressure is told in

@@ -1,4 +1,4 @@
-"""wf_shade_lt (wf_shade over triangle / instance / material tables in LDS, pt_wavefront.hip): register, scratch and LDS budget of every
+"""wf_shade_lt (wf_shade over triangle / instance / material tables in LDS, pt_wf_shade.h): register, scratch and LDS budget of every
 instantiation, read from the code-object metadata of the built library -- the method of tests/test_kernel_resources.py, no GPU needed.
 
 The kernel is compiled for a forced four waves per SIMD like wf_shade, whose history of miscompiles under register pressure is told there:
