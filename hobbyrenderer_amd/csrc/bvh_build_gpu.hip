@@ -11,6 +11,7 @@
 // transform / attribute unpacking use the same expression order with -ffp-contract=off.
 #include "bvh_build_gpu.h"
 #include "bvh_build.h"
+#include "pt_device_buffer.h"
 
 #include <cstring>
 using std::memset;   // rocprim/iterator/texture_cache_iterator.hpp calls an unqualified memset
@@ -19,6 +20,8 @@ using std::memset;   // rocprim/iterator/texture_cache_iterator.hpp calls an unq
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <type_traits>
 #include <vector>
 
 namespace hrt {
@@ -577,49 +580,262 @@ struct Arena {          // one temporary allocation carved into aligned pieces
     template <class T> T* take(size_t n) { size_t o = off; off += (n * sizeof(T) + 255) & ~(size_t)255; return base ? reinterpret_cast<T*>(base + o) : nullptr; }
 };
 
-} // namespace
-
-// leaf size in force: box mode fixes it (Impl::maxLeaf = 1), else HRPT_GPU_BVH_MAX_LEAF (1..4), else 2 -- measured with the greedy collapse:
-// 2 beats 4 on all three test scenes for both hierarchies (-2..-6 % frame time)
-static uint32_t effective_max_leaf(uint32_t fixedLeaf)
+// ---- build variants from the environment, read here and nowhere else
+struct BuildOptions {
+    uint32_t maxLeaf = 2;           // HRPT_GPU_BVH_MAX_LEAF (1..4; box mode: always 1). 2 beats 4 on all three test scenes for both hierarchies (-2..-6 % frame time, greedy collapse)
+    bool greedy = true;             // HRPT_GPU_BVH_COLLAPSE=fixed: the two-levels-at-a-time rule instead of the area-greedy collapse (A/B runs)
+    int plocRadius = kPlocRadius;   // HRPT_GPU_PLOC_RADIUS (1..256)
+    uint32_t cubeMorton = 0;        // HRPT_GPU_BVH_CUBE_MORTON: BuildBuffers::cubeMorton. Default: box mode only
+};
+BuildOptions read_build_options(bool boxes)
 {
-    if (fixedLeaf >= 1 && fixedLeaf <= 4) return fixedLeaf;
-    if (const char* e = getenv("HRPT_GPU_BVH_MAX_LEAF")) { int v = atoi(e); if (v >= 1 && v <= 4) return (uint32_t)v; }
-    return 2;
+    BuildOptions o;
+    if (boxes) { o.maxLeaf = 1; o.cubeMorton = 1; }
+    else if (const char* e = getenv("HRPT_GPU_BVH_MAX_LEAF")) { int v = atoi(e); if (v >= 1 && v <= 4) o.maxLeaf = (uint32_t)v; }
+    if (const char* e = getenv("HRPT_GPU_BVH_COLLAPSE")) o.greedy = strcmp(e, "fixed") != 0;
+    if (const char* e = getenv("HRPT_GPU_PLOC_RADIUS")) { int v = atoi(e); if (v >= 1 && v <= 256) o.plocRadius = v; }
+    if (const char* e = getenv("HRPT_GPU_BVH_CUBE_MORTON")) o.cubeMorton = atoi(e) != 0;
+    return o;
 }
 
-struct GpuBvhBuilder::Impl {
+struct EventDestroyer { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroyer>;
+bool create_event(Event& ev) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return false; ev.reset(e); return true; }
+
+struct Tree {                          // one hierarchy in the build buffers
+    BuildBuffers b{};                  // the buffer set as the back end sees it (final leaf order in valB)
+    uint32_t nodeCount = 0, maxDepth = 0, bits = 0; bool ploc = false;     // 2-wide nodes and depth; Morton bits the hierarchy used; built by PLOC
+};
+struct BuilderState {                  // GpuBvhBuilder::Impl
     BuildBuffers b0{};                 // pointers as carved at prepare(); build() works on a copy (the PLOC path swaps order buffers)
-    void* scratch = nullptr; void* prim = nullptr;
-    GpuTri* tris = nullptr; GpuTriAttr* attrs = nullptr; GpuTriTangent* tangents = nullptr;
+    DeviceBuffer<char> scratch;        // the arena every build buffer is carved from
+    void* prim = nullptr;              // rocPRIM's temporary storage (a piece of the arena)
+    DeviceBuffer<GpuTri> tris; DeviceBuffer<GpuTriAttr> attrs; DeviceBuffer<GpuTriTangent> tangents;
     std::vector<InstRec> inst;         // static part filled at prepare(), world matrices per build()
     size_t sortBytes = 0, scanBytes = 0, bytes = 0;
     uint32_t n = 0;
     uint32_t vertexCount = 0;          // records of BuildBuffers::vertices (triangle mode)
     bool boxes = false;                // prepare_boxes(): the primitives are boxes (one per leaf), no triangle / attribute outputs
-    uint32_t maxLeaf = 0;              // 0: the default leaf size (2, HRPT_GPU_BVH_MAX_LEAF); 1 in box mode
+    uint32_t maxLeaf = 0;              // BuildOptions::maxLeaf as allocate() read it: sizes nodes4 AND classifies the leaves of every build
     uint32_t nodes4Capacity = 0;       // records of BuildBuffers::nodes4 (allocate)
     int lastBudget = -1; bool lastUsePloc = false;   // hierarchy attempt that fitted the stacks at the previous build(): a rebuild starts there
-    // what refit() needs of the last successful build: the buffer set as the back end saw it (final leaf order in valB), node count, 2-wide depth
-    BuildBuffers last{}; bool haveTree = false; uint32_t lastNodeCount = 0, lastMaxDepth = 0, lastBits = 0; bool lastPloc = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~Impl()
-    {
-        if (scratch) (void)hipFree(scratch);
-        if (tris) (void)hipFree(tris);
-        if (attrs) (void)hipFree(attrs);
-        if (tangents) (void)hipFree(tangents);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
+    Tree last; bool haveTree = false;  // the last successful build, for refit()
+    Event ev0, ev1;
 };
 
-GpuBvhBuilder::~GpuBvhBuilder() { delete p; }
+dim3 grid(uint32_t count) { return dim3((count + kB - 1) / kB); }       // one thread per item, blocks of kB
+const dim3 blk(kB);
+
+// every failure of the builder leaves through here: an allocation the device refused is out of memory whoever reports it
+hipError_t refuse(GpuBuildError& error, hipError_t e, GpuBuildFailure reason, const char* what) { error = GpuBuildError{ e == hipErrorOutOfMemory ? GpuBuildFailure::OutOfMemory : reason, what }; return e; }
+hipError_t device_error(GpuBuildError& error, hipError_t e, const char* what) { return refuse(error, e, GpuBuildFailure::DeviceError, what); }
+// a failed build or refit leaves no tree to refit and an idle stream
+hipError_t abandon(BuilderState& m, hipStream_t stream, hipError_t e) { m.haveTree = false; (void)hipStreamSynchronize(stream); return e; }
+
+// The host synchronisation points of build and refit. No launch is checked where it is made: the stream is idle here, so asking for the launch
+// error of everything enqueued since the last point (build_tree / refit_tree clear the thread's stale one first) costs nothing.
+hipError_t synchronise(hipStream_t stream) { const hipError_t e = hipStreamSynchronize(stream); return e != hipSuccess ? e : hipGetLastError(); }
+
+// total of an exclusive scan over `count` flags: its last output + the last flag. Synchronises.
+hipError_t scan_total(const uint32_t* scanned, const uint32_t* flags, uint32_t count, hipStream_t stream, uint32_t& total)
+{
+    uint32_t tail[2] = { 0, 0 }; hipError_t e;
+    if ((e = hipMemcpyAsync(&tail[0], scanned + (count - 1), 4, hipMemcpyDeviceToHost, stream)) == hipSuccess &&
+        (e = hipMemcpyAsync(&tail[1], flags + (count - 1), 4, hipMemcpyDeviceToHost, stream)) == hipSuccess) e = synchronise(stream);
+    total = tail[0] + tail[1];
+    return e;
+}
+
+// SAH cost of the 2-wide tree relative to the root's area (root box = union of the root's two child boxes)
+float relative_sah_cost(const GpuNode& root, float sahSum)
+{
+    float dx = std::max(root.lmax[0], root.rmax[0]) - std::min(root.lmin[0], root.rmin[0]);
+    float dy = std::max(root.lmax[1], root.rmax[1]) - std::min(root.lmin[1], root.rmin[1]);
+    float dz = std::max(root.lmax[2], root.rmax[2]) - std::min(root.lmin[2], root.rmin[2]);
+    float ra = dx * dy + dy * dz + dz * dx;
+    return ra > 0.0f ? 1.0f + sahSum / ra : 0.0f;
+}
+
+// ---- front end of build and refit: the boxes, or the instances' world matrices, to the device; then the device clock starts (GpuBuiltBvh::deviceMs),
+// the flags are cleared and the world-space primitives set up
+hipError_t upload_and_setup(BuilderState& m, const BuildBuffers& b, const HrptPerInstanceData* instances, const float* boxes, hipStream_t stream, GpuBuildError& error)
+{
+    if (!m.boxes) for (size_t i = 0; i < m.inst.size(); ++i) std::memcpy(m.inst[i].world, instances[i].m_World, sizeof m.inst[i].world);
+    const hipError_t e = m.boxes ? hipMemcpyAsync(const_cast<float*>(b.boxesIn), boxes, (size_t)m.n * 24, hipMemcpyHostToDevice, stream)
+                                 : hipMemcpyAsync(const_cast<InstRec*>(b.inst), m.inst.data(), m.inst.size() * sizeof(InstRec), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return device_error(error, e, m.boxes ? "hipMemcpyAsync(GPU BVH boxes)" : "hipMemcpyAsync(GPU BVH instances)");
+    (void)hipEventRecord(m.ev0.get(), stream);
+    hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, stream, b.sceneBounds, b.flags);
+    if (m.boxes) hipLaunchKernelGGL(k_setup_boxes, grid(m.n), blk, 0, stream, b);
+    else hipLaunchKernelGGL(k_setup, grid(m.n), blk, 0, stream, b);
+    return hipSuccess;
+}
+
+// ---- hierarchy by PLOC over the sorted primitives. !ok: the clustering did not come down to one tree (the caller goes on to the radix tree)
+hipError_t ploc_hierarchy(const BuilderState& m, BuildBuffers& b, int radius, bool& ok, hipStream_t stream, GpuBuildError& error)
+{
+    const uint32_t n = m.n;
+    size_t scanBytes = m.scanBytes; hipError_t e;                  // (rocPRIM takes the size by non-const reference)
+    ok = false;
+    hipLaunchKernelGGL(k_ploc_init, grid(n), blk, 0, stream, b);
+    uint32_t count = n, created = 0; uint32_t* cur = b.clusterA; uint32_t* nxt = b.clusterB;
+    const uint32_t init[4] = { n, 0u, 0u, 0u };
+    if ((e = hipMemcpyAsync(b.plocState, init, sizeof init, hipMemcpyHostToDevice, stream)) != hipSuccess) return device_error(error, e, "GPU BVH build (PLOC state)");
+    for (int batch = 0; count > 1 && batch < 64; ++batch) {
+        const uint32_t bound = count;                              // no cluster list of this batch is longer
+        const dim3 gC = grid(bound);
+        for (int it = 0; it < 6; ++it) {
+            hipLaunchKernelGGL(k_ploc_nn, gC, blk, 0, stream, b, cur, radius);
+            hipLaunchKernelGGL(k_ploc_flags, gC, blk, 0, stream, b, bound);
+            if ((e = rocprim::exclusive_scan(m.prim, scanBytes, b.mergeFlag, b.mergeIdx, 0u, bound, rocprim::plus<uint32_t>(), stream)) != hipSuccess ||
+                (e = rocprim::exclusive_scan(m.prim, scanBytes, b.validFlag, b.validIdx, 0u, bound, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return device_error(error, e, "rocprim::exclusive_scan(PLOC)");
+            hipLaunchKernelGGL(k_ploc_apply, gC, blk, 0, stream, b, cur, nxt);
+            hipLaunchKernelGGL(k_ploc_advance, dim3(1), dim3(1), 0, stream, b);
+            std::swap(cur, nxt);
+        }
+        uint32_t state[3] = { 0, 0, 0 };
+        if ((e = hipMemcpyAsync(state, b.plocState, sizeof state, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+            (e = synchronise(stream)) != hipSuccess) return device_error(error, e, "GPU BVH build (PLOC batch)");
+        if (state[2] || state[0] == 0 || state[0] > count) return hipSuccess;
+        count = state[0]; created = state[1];
+    }
+    if (count > 1 || created != n - 1) return hipSuccess;
+    hipLaunchKernelGGL(k_ploc_offsets, grid(2 * n - 1), blk, 0, stream, b);
+    hipLaunchKernelGGL(k_ploc_finish, grid(2 * n - 1), blk, 0, stream, b, b.valA);
+    b.valB = b.valA;                                               // depth-first leaf order replaces the Morton order downstream
+    ok = true;
+    return hipSuccess;
+}
+
+// ---- hierarchy by the radix tree over the Morton codes shifted right by `shift` (no re-sort: the order stays the full-code order), boxes fitted bottom-up
+void radix_hierarchy(const BuilderState& m, BuildBuffers& b, int shift, hipStream_t stream)
+{
+    b.valB = m.b0.valB;                                            // leaf k of the radix tree = primitive valB[k] of the sort (a failed PLOC attempt has switched it)
+    (void)hipMemsetAsync(b.visit, 0, (size_t)m.n * 4, stream);
+    hipLaunchKernelGGL(k_hierarchy, grid(m.n), blk, 0, stream, b, shift);
+    hipLaunchKernelGGL(k_fit, grid(m.n), blk, 0, stream, b);
+}
+
+// ---- leaves of up to maxLeaf primitives, depth-first numbering of the kept nodes, 2-wide emission; reads back t.nodeCount and t.maxDepth
+hipError_t number_and_emit2(const BuilderState& m, Tree& t, hipStream_t stream, GpuBuildError& error)
+{
+    const BuildBuffers& b = t.b; const uint32_t n = m.n;
+    size_t scanBytes = m.scanBytes; hipError_t e;
+    (void)hipMemsetAsync(b.flags + 1, 0, 4, stream);
+    hipLaunchKernelGGL(k_classify, grid(n), blk, 0, stream, b, m.maxLeaf);
+    hipLaunchKernelGGL(k_preorder, grid(n), blk, 0, stream, b);
+    if ((e = rocprim::exclusive_scan(m.prim, scanBytes, b.keepPre, b.densePre, 0u, n - 1, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return device_error(error, e, "rocprim::exclusive_scan(keep)");
+    hipLaunchKernelGGL(k_preorder_gather, grid(n), blk, 0, stream, b);
+    hipLaunchKernelGGL(k_emit2, grid(n), blk, 0, stream, b);
+    if ((e = scan_total(b.densePre, b.keepPre, n - 1, stream, t.nodeCount)) != hipSuccess) return device_error(error, e, "GPU BVH build (hierarchy)");
+    if (t.nodeCount == 0) return device_error(error, hipErrorUnknown, "GPU BVH build produced no inner node");
+    hipLaunchKernelGGL(k_depth, grid(t.nodeCount), blk, 0, stream, b, t.nodeCount);
+    if ((e = hipMemcpyAsync(&t.maxDepth, b.flags + 1, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = synchronise(stream)) != hipSuccess) return device_error(error, e, "GPU BVH build (depth)");
+    return hipSuccess;
+}
+
+// ---- back end of build and refit: 4-wide collapse of the 2-wide tree `t`, SAH sum, attribute records, and the result
+hipError_t finish(const BuilderState& m, const Tree& t, bool refitted, hipStream_t stream, GpuBuiltBvh& out, GpuBuildError& error)
+{
+    const BuildBuffers& b = t.b; const uint32_t nodeCount = t.nodeCount; const dim3 gN = grid(nodeCount);
+    size_t scanBytes = m.scanBytes; hipError_t e;
+    // Area-greedy collapse (fuller nodes with tighter boxes: it is what makes a PLOC tree as fast as the host's SAH tree) unless the fixed rule is asked for
+    const bool greedy = read_build_options(m.boxes).greedy;
+    (void)hipMemsetAsync(b.even, 0, (size_t)nodeCount * 4, stream);
+    hipLaunchKernelGGL(k_mark4_init, dim3(1), dim3(1), 0, stream, b);
+    for (uint32_t d = 0; d <= t.maxDepth; ++d) hipLaunchKernelGGL(k_mark4, gN, blk, 0, stream, b, nodeCount, d, greedy);
+    if ((e = rocprim::exclusive_scan(m.prim, scanBytes, b.even, b.index4, 0u, nodeCount, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return device_error(error, e, "rocprim::exclusive_scan(even)");
+    // k_emit4 writes nodes4[index4[k]] unchecked: the 4-wide node count is read first and a tree that does not fit the buffer is refused (the caller
+    // builds on the host instead). allocate() argues why that cannot happen: the leaf size is the one the buffer was sized for.
+    uint32_t node4Count = 0;
+    if ((e = scan_total(b.index4, b.even, nodeCount, stream, node4Count)) != hipSuccess) return device_error(error, e, refitted ? "GPU BVH refit (collapse)" : "GPU BVH build (collapse)");
+    if (node4Count > m.nodes4Capacity)
+        return refuse(error, hipErrorInvalidValue, GpuBuildFailure::DoesNotFit, refitted ? "GPU BVH refit: the 4-wide tree does not fit its buffer" : "GPU BVH build: the 4-wide tree does not fit its buffer");
+    hipLaunchKernelGGL(k_emit4, gN, blk, 0, stream, b, nodeCount, greedy);
+    float* sahDev = reinterpret_cast<float*>(b.flags + 4);
+    (void)hipMemsetAsync(sahDev, 0, 4, stream);
+    hipLaunchKernelGGL(k_sah, gN, blk, 0, stream, b, nodeCount, sahDev);
+    if (!m.boxes) hipLaunchKernelGGL(k_attrs, grid(m.n), blk, 0, stream, b);
+    (void)hipEventRecord(m.ev1.get(), stream);
+    uint32_t flags[4] = { 0, 0, 0, 0 }; float sahSum = 0.0f; GpuNode rootNode;
+    if ((e = hipMemcpyAsync(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(&sahSum, sahDev, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(&rootNode, b.nodes, sizeof rootNode, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = synchronise(stream)) != hipSuccess) return device_error(error, e, refitted ? "GPU BVH refit" : "GPU BVH build (emit)");
+    if (flags[0]) return refuse(error, hipErrorInvalidValue, GpuBuildFailure::NonFinitePosition, "non-finite vertex position");
+    float ms = 0.0f; (void)hipEventElapsedTime(&ms, m.ev0.get(), m.ev1.get());
+    out.nodes = b.nodes; out.nodeCount = nodeCount; out.nodes4 = b.nodes4; out.node4Count = node4Count; out.nodes4Capacity = m.nodes4Capacity;
+    out.tris = b.tris; out.attrs = b.attrs; out.tangents = b.tangents; out.triCount = m.n; out.leafOrder = b.valB;
+    out.sahCost = relative_sah_cost(rootNode, sahSum);
+    out.maxDepth = t.maxDepth; out.maxDepth4 = flags[2]; out.mortonBits = t.bits; out.ploc = t.ploc; out.deviceMs = ms; out.refitted = refitted;
+    return hipSuccess;
+}
+
+// ---- build: sort, then hierarchy attempts, best tree first, until the 2-wide depth fits the traversal stacks: PLOC (when asked for), the radix
+// tree over the full 63-bit codes, radix trees over fewer Morton bits
+hipError_t build_tree(BuilderState* builder, const HrptPerInstanceData* instances, const float* boxes, bool usePloc, uint32_t maxStackDepth, hipStream_t stream, GpuBuiltBvh& out, GpuBuildError& error)
+{
+    out = GpuBuiltBvh();
+    if (!builder || builder->boxes != (boxes != nullptr) || !builder->scratch) return device_error(error, hipErrorInvalidValue, boxes ? "GPU BVH builder not prepared for boxes" : "GPU BVH builder not prepared");
+    BuilderState& m = *builder;
+    m.haveTree = false;
+    (void)hipGetLastError();
+    Tree t; t.b = m.b0;                                                // a copy: the PLOC path switches the leaf-order buffer
+    BuildBuffers& b = t.b;
+    size_t sortBytes = m.sortBytes; hipError_t e;
+    if ((e = upload_and_setup(m, b, instances, boxes, stream, error)) != hipSuccess) return abandon(m, stream, e);
+    hipLaunchKernelGGL(k_morton, grid(m.n), blk, 0, stream, b);
+    if ((e = rocprim::radix_sort_pairs(m.prim, sortBytes, b.keyA, b.keyB, b.valA, b.valB, m.n, 0, 63, stream)) != hipSuccess) return abandon(m, stream, device_error(error, e, "rocprim::radix_sort_pairs"));
+    const int attempts[] = { 64, 63, 48, 39, 30, 21, 12, 0 };          // Morton bits; 64 = PLOC
+    if (m.lastUsePloc != usePloc) m.lastBudget = -1;
+    m.lastUsePloc = usePloc;
+    int fitted = -1;
+    for (int budget : attempts) {
+        if (m.lastBudget >= 0 && budget > m.lastBudget) continue;      // too deep last time: moving instances rarely changes that, and every attempt costs a host round trip
+        if (budget == 64) {
+            if (!usePloc) continue;
+            bool ok = false;
+            if ((e = ploc_hierarchy(m, b, read_build_options(m.boxes).plocRadius, ok, stream, error)) != hipSuccess) return abandon(m, stream, e);
+            if (!ok) continue;
+        } else radix_hierarchy(m, b, 63 - budget, stream);
+        if ((e = number_and_emit2(m, t, stream, error)) != hipSuccess) return abandon(m, stream, e);
+        t.bits = budget == 64 ? 63 : budget; t.ploc = budget == 64;
+        if (t.maxDepth + 2 <= maxStackDepth) { fitted = budget; break; }
+    }
+    m.lastBudget = fitted;
+    if ((e = finish(m, t, false, stream, out, error)) != hipSuccess) return abandon(m, stream, e);
+    m.last = t; m.haveTree = true;
+    return hipSuccess;
+}
+
+// ---- refit: new boxes on the hierarchy of the last build (hrpt_refit_instances: small motions). Runs the primitive set-up, the bottom-up box fit
+// over the stored parent links, the 2-wide emission, the 4-wide collapse (its greedy choices follow the new boxes, so the 4-wide node count
+// may change) and the attribute records; skips the Morton codes, the sort, the hierarchy (the ~300 launches of PLOC) and the numbering.
+hipError_t refit_tree(BuilderState* builder, const HrptPerInstanceData* instances, const float* boxes, hipStream_t stream, GpuBuiltBvh& out, GpuBuildError& error)
+{
+    out = GpuBuiltBvh();
+    if (!builder || builder->boxes != (boxes != nullptr) || !builder->haveTree) return device_error(error, hipErrorInvalidValue, "GPU BVH builder has no tree to refit");
+    BuilderState& m = *builder;
+    (void)hipGetLastError();
+    const BuildBuffers& b = m.last.b; hipError_t e;
+    if ((e = upload_and_setup(m, b, instances, boxes, stream, error)) != hipSuccess) return abandon(m, stream, e);
+    (void)hipMemsetAsync(b.visit, 0, (size_t)m.n * 4, stream);
+    hipLaunchKernelGGL(k_fit, grid(m.n), blk, 0, stream, b);
+    hipLaunchKernelGGL(k_emit2, grid(m.n), blk, 0, stream, b);
+    return (e = finish(m, m.last, true, stream, out, error)) == hipSuccess ? e : abandon(m, stream, e);
+}
+
+} // namespace
+
+struct GpuBvhBuilder::Impl : BuilderState {};
+
+GpuBvhBuilder::GpuBvhBuilder() = default;
+GpuBvhBuilder::~GpuBvhBuilder() = default;
 size_t GpuBvhBuilder::deviceBytes() const { return p ? p->bytes : 0; }
 
-hipError_t GpuBvhBuilder::prepare(const HrptSceneDesc& s, bool needTangents, hipStream_t stream, std::string& error)
+hipError_t GpuBvhBuilder::prepare(const HrptSceneDesc& s, bool needTangents, hipStream_t stream, GpuBuildError& error)
 {
-    delete p; p = new Impl();
+    p = std::make_unique<Impl>();
     Impl& m = *p;
     // instance table + triangle prefix (host, O(instances)); mesh / material / opacity of an instance never change between rebuilds
     m.inst.resize(s.instanceCount);
@@ -631,25 +847,26 @@ hipError_t GpuBvhBuilder::prepare(const HrptSceneDesc& s, bool needTangents, hip
         m.inst[i].opaque = triangle_flags_for_material(s.materials[in.m_MaterialIndex]);     // bit 0 opaque, bits 1-2 shading class
         T += md.m_IndexCounts[0] / 3;
     }
-    if (T < 8 || T >= (1ull << 29)) { error = "triangle count outside the GPU builder's range"; return hipErrorInvalidValue; }
+    if (T < 8 || T >= (1ull << 29)) return refuse(error, hipErrorInvalidValue, GpuBuildFailure::DoesNotFit, "triangle count outside the GPU builder's range");
     return allocate((uint32_t)T, &s, needTangents, stream, error);
 }
 
-hipError_t GpuBvhBuilder::prepare_boxes(uint32_t count, hipStream_t stream, std::string& error)
+hipError_t GpuBvhBuilder::prepare_boxes(uint32_t count, hipStream_t stream, GpuBuildError& error)
 {
-    delete p; p = new Impl();
-    p->boxes = true; p->maxLeaf = 1;
-    if (count < 8 || count >= (1u << 25)) { error = "box count outside the GPU builder's range"; return hipErrorInvalidValue; }
+    p = std::make_unique<Impl>();
+    p->boxes = true;
+    if (count < 8 || count >= (1u << 25)) return refuse(error, hipErrorInvalidValue, GpuBuildFailure::DoesNotFit, "box count outside the GPU builder's range");
     return allocate(count, nullptr, false, stream, error);
 }
 
 // every device buffer of a build over n primitives; `s` (triangle mode) also brings the geometry to the device
-hipError_t GpuBvhBuilder::allocate(uint32_t n, const HrptSceneDesc* s, bool needTangents, hipStream_t stream, std::string& error)
+hipError_t GpuBvhBuilder::allocate(uint32_t n, const HrptSceneDesc* s, bool needTangents, hipStream_t stream, GpuBuildError& error)
 {
-    Impl& m = *p;
-    hipError_t e;
+    Impl& m = *p; hipError_t e;
     m.n = n; m.vertexCount = s ? s->vertexCount : 0;
-    if (hipEventCreate(&m.ev0) != hipSuccess || hipEventCreate(&m.ev1) != hipSuccess) { error = "hipEventCreate"; return hipErrorUnknown; }
+    const BuildOptions opt = read_build_options(m.boxes);          // leaf size and Morton grid: fixed here for the builder's life
+    m.maxLeaf = opt.maxLeaf;
+    if (!create_event(m.ev0) || !create_event(m.ev1)) return device_error(error, hipErrorUnknown, "hipEventCreate");
 
     // rocPRIM scratch sizes
     (void)rocprim::radix_sort_pairs(nullptr, m.sortBytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 63, stream);
@@ -677,8 +894,9 @@ hipError_t GpuBvhBuilder::allocate(uint32_t n, const HrptSceneDesc* s, bool need
         // 2-wide node, i.e. more than L primitives; every other node has four children under the greedy collapse (it stops early only when no inner
         // child is left) and at least three under the fixed one. With T terminal nodes and l leaf children elsewhere: n >= (L + 1) T + l, and the node
         // count is at most T + (T + l - 1) / 2. For L >= 2 that is at most (n - 1) / 2 (greedy: 4 n / 9); for L = 1 up to 3 n / 4, and never more than the
-        // n - 1 two-wide nodes. build_any still checks the count against this capacity before k_emit4 writes.
-        m.nodes4Capacity = effective_max_leaf(m.maxLeaf) == 1 ? n : n / 2 + 1;
+        // n - 1 two-wide nodes. L is m.maxLeaf, the value every build classifies with; finish() still checks the count against this capacity before
+        // k_emit4 writes.
+        m.nodes4Capacity = m.maxLeaf == 1 ? n : n / 2 + 1;
         b.nodes4 = A.take<GpuNode4>(m.nodes4Capacity);
         m.prim = A.take<char>(std::max(m.sortBytes, m.scanBytes));
         char* vtx = A.take<char>(s ? (size_t)s->vertexCount * sizeof(HrptVertexQuantized) : 0);
@@ -687,22 +905,21 @@ hipError_t GpuBvhBuilder::allocate(uint32_t n, const HrptSceneDesc* s, bool need
         b.boxesIn = A.take<float>(m.boxes ? 6 * (size_t)n : 0);
         b.vertices = reinterpret_cast<const HrptVertexQuantized*>(vtx); b.indices = reinterpret_cast<const uint32_t*>(idx); b.inst = reinterpret_cast<const InstRec*>(ins);
         if (pass == 0) {
-            if ((e = hipMalloc(&m.scratch, A.off)) != hipSuccess) { error = "hipMalloc(GPU BVH build arena)"; return e; }
-            A.base = static_cast<char*>(m.scratch); A.cap = A.off;
+            if ((e = m.scratch.alloc(A.off)) != hipSuccess) return device_error(error, e, "hipMalloc(GPU BVH build arena)");
+            A.base = m.scratch.get(); A.cap = A.off;
         }
     }
-    b.instCount = (uint32_t)m.inst.size(); b.triCount = n; b.cubeMorton = m.boxes ? 1u : 0u;
-    if (const char* e = getenv("HRPT_GPU_BVH_CUBE_MORTON")) b.cubeMorton = atoi(e) != 0;
+    b.instCount = (uint32_t)m.inst.size(); b.triCount = n; b.cubeMorton = opt.cubeMorton;
     b.tris = nullptr; b.attrs = nullptr; b.tangents = nullptr;
     m.bytes = A.cap;
     if (m.boxes) return hipSuccess;
     m.bytes += (size_t)n * (sizeof(GpuTri) + sizeof(GpuTriAttr) + (needTangents ? sizeof(GpuTriTangent) : 0));
-    if ((e = hipMalloc((void**)&m.tris, (size_t)n * sizeof(GpuTri))) != hipSuccess || (e = hipMalloc((void**)&m.attrs, (size_t)n * sizeof(GpuTriAttr))) != hipSuccess ||
-        (needTangents && (e = hipMalloc((void**)&m.tangents, (size_t)n * sizeof(GpuTriTangent))) != hipSuccess)) { error = "hipMalloc(GPU BVH outputs)"; return hipErrorOutOfMemory; }
+    if (m.tris.alloc((size_t)n * sizeof(GpuTri)) != hipSuccess || m.attrs.alloc((size_t)n * sizeof(GpuTriAttr)) != hipSuccess ||
+        (needTangents && m.tangents.alloc((size_t)n * sizeof(GpuTriTangent)) != hipSuccess)) return refuse(error, hipErrorOutOfMemory, GpuBuildFailure::OutOfMemory, "hipMalloc(GPU BVH outputs)");
     b.tris = m.tris; b.attrs = m.attrs; b.tangents = m.tangents;
     if ((e = hipMemcpyAsync(const_cast<HrptVertexQuantized*>(b.vertices), s->vertices, (size_t)s->vertexCount * sizeof(HrptVertexQuantized), hipMemcpyHostToDevice, stream)) != hipSuccess ||
         (e = hipMemcpyAsync(const_cast<uint32_t*>(b.indices), s->indices, (size_t)s->indexCount * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess) { error = "hipMemcpyAsync(GPU BVH inputs)"; return e; }
+        (e = hipStreamSynchronize(stream)) != hipSuccess) return device_error(error, e, "hipMemcpyAsync(GPU BVH inputs)");
     return hipSuccess;
 }
 
@@ -718,230 +935,11 @@ hipError_t GpuBvhBuilder::update_vertices(const HrptVertexQuantized* vertices, b
     return e;
 }
 
-hipError_t GpuBvhBuilder::build_boxes(const float* boxes, bool usePloc, uint32_t maxStackDepth, hipStream_t stream, GpuBuiltBvh& out, std::string& error)
-{
-    if (!p || !p->boxes) { error = "GPU BVH builder not prepared for boxes"; return hipErrorInvalidValue; }
-    return build_any(nullptr, boxes, usePloc, maxStackDepth, stream, out, error);
-}
-hipError_t GpuBvhBuilder::build(const HrptPerInstanceData* instances, bool usePloc, uint32_t maxStackDepth, hipStream_t stream, GpuBuiltBvh& out, std::string& error)
-{
-    if (!p || p->boxes) { error = "GPU BVH builder not prepared"; return hipErrorInvalidValue; }
-    return build_any(instances, nullptr, usePloc, maxStackDepth, stream, out, error);
-}
-
-hipError_t GpuBvhBuilder::build_any(const HrptPerInstanceData* instances, const float* boxes, bool usePloc, uint32_t maxStackDepth, hipStream_t stream, GpuBuiltBvh& out, std::string& error)
-{
-    out = GpuBuiltBvh();
-    if (!p->scratch) { error = "GPU BVH builder not prepared"; return hipErrorInvalidValue; }
-    Impl& m = *p;
-    m.haveTree = false;
-    hipError_t e;
-    BuildBuffers b = m.b0;
-    const uint32_t n = m.n;
-    void* const prim = m.prim; size_t sortBytes = m.sortBytes, scanBytes = m.scanBytes;   // rocPRIM takes the size by non-const reference
-    auto fail = [&](hipError_t err, const char* what) { error = what; (void)hipStreamSynchronize(stream); return err; };
-    if (m.boxes) {
-        if ((e = hipMemcpyAsync(const_cast<float*>(b.boxesIn), boxes, (size_t)n * 24, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e, "hipMemcpyAsync(GPU BVH boxes)");
-    } else {
-        for (size_t i = 0; i < m.inst.size(); ++i) std::memcpy(m.inst[i].world, instances[i].m_World, sizeof m.inst[i].world);
-        if ((e = hipMemcpyAsync(const_cast<InstRec*>(b.inst), m.inst.data(), m.inst.size() * sizeof(InstRec), hipMemcpyHostToDevice, stream)) != hipSuccess)
-            return fail(e, "hipMemcpyAsync(GPU BVH instances)");
-    }
-    hipEvent_t ev0 = m.ev0, ev1 = m.ev1;
-    (void)hipEventRecord(ev0, stream);
-    const dim3 gT((n + kB - 1) / kB), blk(kB);
-    hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, stream, b.sceneBounds, b.flags);
-    if (m.boxes) hipLaunchKernelGGL(k_setup_boxes, gT, blk, 0, stream, b);
-    else hipLaunchKernelGGL(k_setup, gT, blk, 0, stream, b);
-    hipLaunchKernelGGL(k_morton, gT, blk, 0, stream, b);
-    if ((e = rocprim::radix_sort_pairs(prim, sortBytes, b.keyA, b.keyB, b.valA, b.valB, n, 0, 63, stream)) != hipSuccess) return fail(e, "rocprim::radix_sort_pairs");
-    // Hierarchy attempts, best tree first: PLOC (when asked for), then the radix tree over the full 63-bit codes, then radix trees over
-    // fewer Morton bits (no re-sort: the order stays the full-code order) until the depth fits the traversal stacks.
-    uint32_t nodeCount = 0, maxDepthSeen = 0; int usedBits = 0; bool usedPloc = false;
-    const uint32_t maxLeafTris = effective_max_leaf(m.maxLeaf);
-    int plocRadius = kPlocRadius;
-    if (const char* e = getenv("HRPT_GPU_PLOC_RADIUS")) { int v = atoi(e); if (v >= 1 && v <= 256) plocRadius = v; }
-    const int attempts[] = { 64, 63, 48, 39, 30, 21, 12, 0 };          // 64 = PLOC
-    uint32_t* const mortonOrder = b.valB;                              // leaf k of the radix tree = triangle mortonOrder[k]
-    if (m.lastUsePloc != usePloc) m.lastBudget = -1;
-    m.lastUsePloc = usePloc;
-    int fitted = -1;
-    for (int budget : attempts) {
-        if (m.lastBudget >= 0 && budget > m.lastBudget) continue;      // too deep last time: moving instances rarely changes that, and every attempt costs a host round trip
-        if (budget == 64) {
-            if (!usePloc) continue;
-            hipLaunchKernelGGL(k_ploc_init, gT, blk, 0, stream, b);
-            uint32_t count = n, created = 0; uint32_t* cur = b.clusterA; uint32_t* nxt = b.clusterB; bool ok = true;
-            const uint32_t init[4] = { n, 0u, 0u, 0u };
-            if ((e = hipMemcpyAsync(b.plocState, init, sizeof init, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e, "GPU BVH build (PLOC state)");
-            for (int batch = 0; count > 1 && ok && batch < 64; ++batch) {
-                const uint32_t bound = count;                          // no cluster list of this batch is longer
-                const dim3 gC((bound + kB - 1) / kB);
-                for (int it = 0; it < 6; ++it) {
-                    hipLaunchKernelGGL(k_ploc_nn, gC, blk, 0, stream, b, cur, plocRadius);
-                    hipLaunchKernelGGL(k_ploc_flags, gC, blk, 0, stream, b, bound);
-                    if ((e = rocprim::exclusive_scan(prim, scanBytes, b.mergeFlag, b.mergeIdx, 0u, bound, rocprim::plus<uint32_t>(), stream)) != hipSuccess ||
-                        (e = rocprim::exclusive_scan(prim, scanBytes, b.validFlag, b.validIdx, 0u, bound, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return fail(e, "rocprim::exclusive_scan(PLOC)");
-                    hipLaunchKernelGGL(k_ploc_apply, gC, blk, 0, stream, b, cur, nxt);
-                    hipLaunchKernelGGL(k_ploc_advance, dim3(1), dim3(1), 0, stream, b);
-                    std::swap(cur, nxt);
-                }
-                uint32_t state[3] = { 0, 0, 0 };
-                if ((e = hipMemcpyAsync(state, b.plocState, sizeof state, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-                    (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH build (PLOC batch)");
-                if (state[2] || state[0] == 0 || state[0] > count) { ok = false; break; }
-                count = state[0]; created = state[1];
-            }
-            if (count > 1) ok = false;
-            if (!ok || created != n - 1) continue;
-            hipLaunchKernelGGL(k_ploc_offsets, dim3((2 * n - 1 + kB - 1) / kB), blk, 0, stream, b);
-            hipLaunchKernelGGL(k_ploc_finish, dim3((2 * n - 1 + kB - 1) / kB), blk, 0, stream, b, b.valA);
-            b.valB = b.valA;                                           // depth-first leaf order replaces the Morton order downstream
-        } else {
-            const int shift = 63 - budget;
-            b.valB = mortonOrder;
-            (void)hipMemsetAsync(b.visit, 0, (size_t)n * 4, stream);
-            hipLaunchKernelGGL(k_hierarchy, gT, blk, 0, stream, b, shift);
-            hipLaunchKernelGGL(k_fit, gT, blk, 0, stream, b);
-        }
-        (void)hipMemsetAsync(b.flags + 1, 0, 4, stream);
-        hipLaunchKernelGGL(k_classify, gT, blk, 0, stream, b, maxLeafTris);
-        hipLaunchKernelGGL(k_preorder, gT, blk, 0, stream, b);
-        if ((e = rocprim::exclusive_scan(prim, scanBytes, b.keepPre, b.densePre, 0u, n - 1, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return fail(e, "rocprim::exclusive_scan(keep)");
-        hipLaunchKernelGGL(k_preorder_gather, gT, blk, 0, stream, b);
-        hipLaunchKernelGGL(k_emit2, gT, blk, 0, stream, b);
-        // dense node count = densePre[n-2] + keepPre[n-2]
-        uint32_t tail[2] = { 0, 0 };
-        if ((e = hipMemcpyAsync(&tail[0], b.densePre + (n - 2), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(&tail[1], b.keepPre + (n - 2), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH build (hierarchy)");
-        nodeCount = tail[0] + tail[1];
-        if (nodeCount == 0) return fail(hipErrorUnknown, "GPU BVH build produced no inner node");
-        hipLaunchKernelGGL(k_depth, dim3((nodeCount + kB - 1) / kB), blk, 0, stream, b, nodeCount);
-        uint32_t d = 0;
-        if ((e = hipMemcpyAsync(&d, b.flags + 1, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH build (depth)");
-        maxDepthSeen = d; usedBits = budget == 64 ? 63 : budget; usedPloc = budget == 64;
-        if (d + 2 <= maxStackDepth) { fitted = budget; break; }
-    }
-    m.lastBudget = fitted;
-    const dim3 gN((nodeCount + kB - 1) / kB);
-    // Area-greedy collapse (fuller nodes with tighter boxes: it is what makes a PLOC tree as fast as the host's SAH tree); the fixed
-    // two-levels-at-a-time rule stays available for A/B runs (HRPT_GPU_BVH_COLLAPSE=fixed).
-    bool greedy = true;
-    if (const char* e = getenv("HRPT_GPU_BVH_COLLAPSE")) greedy = strcmp(e, "fixed") != 0;
-    (void)hipMemsetAsync(b.even, 0, (size_t)nodeCount * 4, stream);
-    hipLaunchKernelGGL(k_mark4_init, dim3(1), dim3(1), 0, stream, b);
-    for (uint32_t d = 0; d <= maxDepthSeen; ++d) hipLaunchKernelGGL(k_mark4, gN, blk, 0, stream, b, nodeCount, d, greedy);
-    if ((e = rocprim::exclusive_scan(prim, scanBytes, b.even, b.index4, 0u, nodeCount, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return fail(e, "rocprim::exclusive_scan(even)");
-    // k_emit4 writes nodes4[index4[k]] unchecked: the 4-wide node count is read first and a tree that does not fit the buffer is refused (the caller
-    // builds on the host instead). allocate() argues why that cannot happen while the leaf size is the one the buffer was sized for.
-    uint32_t tail4[2] = { 0, 0 };
-    if ((e = hipMemcpyAsync(&tail4[0], b.index4 + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&tail4[1], b.even + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH build (collapse)");
-    const uint32_t node4Count = tail4[0] + tail4[1];
-    if (node4Count > m.nodes4Capacity) return fail(hipErrorInvalidValue, "GPU BVH build: the 4-wide tree does not fit its buffer");
-    hipLaunchKernelGGL(k_emit4, gN, blk, 0, stream, b, nodeCount, greedy);
-    float* sahDev = reinterpret_cast<float*>(b.flags + 4);
-    (void)hipMemsetAsync(sahDev, 0, 4, stream);
-    hipLaunchKernelGGL(k_sah, gN, blk, 0, stream, b, nodeCount, sahDev);
-    if (!m.boxes) hipLaunchKernelGGL(k_attrs, gT, blk, 0, stream, b);
-    (void)hipEventRecord(ev1, stream);
-    uint32_t flags[4] = { 0, 0, 0, 0 }; float sahSum = 0.0f; GpuNode rootNode;
-    if ((e = hipMemcpyAsync(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&sahSum, sahDev, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&rootNode, b.nodes, sizeof rootNode, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH build (emit)");
-    if (flags[0]) return fail(hipErrorInvalidValue, "non-finite vertex position");
-    float ms = 0.0f; (void)hipEventElapsedTime(&ms, ev0, ev1);
-    out.nodes = b.nodes; out.nodeCount = nodeCount; out.nodes4 = b.nodes4; out.node4Count = node4Count; out.nodes4Capacity = m.nodes4Capacity;
-    out.tris = b.tris; out.attrs = b.attrs; out.tangents = b.tangents; out.triCount = n; out.leafOrder = b.valB;
-    {   // root box = union of the root's two child boxes
-        float dx = std::max(rootNode.lmax[0], rootNode.rmax[0]) - std::min(rootNode.lmin[0], rootNode.rmin[0]);
-        float dy = std::max(rootNode.lmax[1], rootNode.rmax[1]) - std::min(rootNode.lmin[1], rootNode.rmin[1]);
-        float dz = std::max(rootNode.lmax[2], rootNode.rmax[2]) - std::min(rootNode.lmin[2], rootNode.rmin[2]);
-        float ra = dx * dy + dy * dz + dz * dx;
-        out.sahCost = ra > 0.0f ? 1.0f + sahSum / ra : 0.0f;
-    }
-    out.maxDepth = maxDepthSeen; out.maxDepth4 = flags[2]; out.mortonBits = (uint32_t)usedBits; out.ploc = usedPloc; out.deviceMs = ms;
-    m.last = b; m.haveTree = true; m.lastNodeCount = nodeCount; m.lastMaxDepth = maxDepthSeen; m.lastBits = (uint32_t)usedBits; m.lastPloc = usedPloc;
-    return hipSuccess;
-}
-
-// ---- refit: new boxes on the hierarchy of the last build (hrpt_refit_instances: small motions). Runs the primitive set-up, the bottom-up box fit
-// over the stored parent links, the 2-wide emission, the 4-wide collapse (its greedy choices follow the new boxes, so the 4-wide node count
-// may change) and the attribute records; skips the Morton codes, the sort, the hierarchy (the ~300 launches of PLOC) and the numbering.
+hipError_t GpuBvhBuilder::build(const HrptPerInstanceData* instances, bool usePloc, uint32_t maxStackDepth, hipStream_t stream, GpuBuiltBvh& out, GpuBuildError& error) { return build_tree(p.get(), instances, nullptr, usePloc, maxStackDepth, stream, out, error); }
+hipError_t GpuBvhBuilder::build_boxes(const float* boxes, bool usePloc, uint32_t maxStackDepth, hipStream_t stream, GpuBuiltBvh& out, GpuBuildError& error) { return build_tree(p.get(), nullptr, boxes, usePloc, maxStackDepth, stream, out, error); }
 bool GpuBvhBuilder::can_refit() const { return p && p->haveTree; }
-hipError_t GpuBvhBuilder::refit(const HrptPerInstanceData* instances, hipStream_t stream, GpuBuiltBvh& out, std::string& error)
-{
-    if (!p || p->boxes || !p->haveTree) { error = "GPU BVH builder has no tree to refit"; return hipErrorInvalidValue; }
-    return refit_any(instances, nullptr, stream, out, error);
-}
-hipError_t GpuBvhBuilder::refit_boxes(const float* boxes, hipStream_t stream, GpuBuiltBvh& out, std::string& error)
-{
-    if (!p || !p->boxes || !p->haveTree) { error = "GPU BVH builder has no tree to refit"; return hipErrorInvalidValue; }
-    return refit_any(nullptr, boxes, stream, out, error);
-}
-hipError_t GpuBvhBuilder::refit_any(const HrptPerInstanceData* instances, const float* boxes, hipStream_t stream, GpuBuiltBvh& out, std::string& error)
-{
-    out = GpuBuiltBvh();
-    Impl& m = *p;
-    hipError_t e;
-    const BuildBuffers b = m.last;
-    const uint32_t n = m.n, nodeCount = m.lastNodeCount;
-    void* const prim = m.prim; size_t scanBytes = m.scanBytes;
-    auto fail = [&](hipError_t err, const char* what) { error = what; m.haveTree = false; (void)hipStreamSynchronize(stream); return err; };
-    if (m.boxes) {
-        if ((e = hipMemcpyAsync(const_cast<float*>(b.boxesIn), boxes, (size_t)n * 24, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e, "hipMemcpyAsync(GPU BVH boxes)");
-    } else {
-        for (size_t i = 0; i < m.inst.size(); ++i) std::memcpy(m.inst[i].world, instances[i].m_World, sizeof m.inst[i].world);
-        if ((e = hipMemcpyAsync(const_cast<InstRec*>(b.inst), m.inst.data(), m.inst.size() * sizeof(InstRec), hipMemcpyHostToDevice, stream)) != hipSuccess)
-            return fail(e, "hipMemcpyAsync(GPU BVH instances)");
-    }
-    (void)hipEventRecord(m.ev0, stream);
-    const dim3 gT((n + kB - 1) / kB), gN((nodeCount + kB - 1) / kB), blk(kB);
-    hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, stream, b.sceneBounds, b.flags);
-    if (m.boxes) hipLaunchKernelGGL(k_setup_boxes, gT, blk, 0, stream, b);
-    else hipLaunchKernelGGL(k_setup, gT, blk, 0, stream, b);
-    (void)hipMemsetAsync(b.visit, 0, (size_t)n * 4, stream);
-    hipLaunchKernelGGL(k_fit, gT, blk, 0, stream, b);
-    hipLaunchKernelGGL(k_emit2, gT, blk, 0, stream, b);
-    bool greedy = true;
-    if (const char* env = getenv("HRPT_GPU_BVH_COLLAPSE")) greedy = strcmp(env, "fixed") != 0;
-    (void)hipMemsetAsync(b.even, 0, (size_t)nodeCount * 4, stream);
-    hipLaunchKernelGGL(k_mark4_init, dim3(1), dim3(1), 0, stream, b);
-    for (uint32_t d = 0; d <= m.lastMaxDepth; ++d) hipLaunchKernelGGL(k_mark4, gN, blk, 0, stream, b, nodeCount, d, greedy);
-    if ((e = rocprim::exclusive_scan(prim, scanBytes, b.even, b.index4, 0u, nodeCount, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return fail(e, "rocprim::exclusive_scan(even)");
-    uint32_t tail4[2] = { 0, 0 };                                      // as in build_any: the count is checked before k_emit4 writes
-    if ((e = hipMemcpyAsync(&tail4[0], b.index4 + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&tail4[1], b.even + (nodeCount - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH refit (collapse)");
-    if (tail4[0] + tail4[1] > m.nodes4Capacity) return fail(hipErrorInvalidValue, "GPU BVH refit: the 4-wide tree does not fit its buffer");
-    hipLaunchKernelGGL(k_emit4, gN, blk, 0, stream, b, nodeCount, greedy);
-    float* sahDev = reinterpret_cast<float*>(b.flags + 4);
-    (void)hipMemsetAsync(sahDev, 0, 4, stream);
-    hipLaunchKernelGGL(k_sah, gN, blk, 0, stream, b, nodeCount, sahDev);
-    if (!m.boxes) hipLaunchKernelGGL(k_attrs, gT, blk, 0, stream, b);
-    (void)hipEventRecord(m.ev1, stream);
-    uint32_t flags[4] = { 0, 0, 0, 0 }; float sahSum = 0.0f; GpuNode rootNode;
-    if ((e = hipMemcpyAsync(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&sahSum, sahDev, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(&rootNode, b.nodes, sizeof rootNode, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e, "GPU BVH refit");
-    if (flags[0]) return fail(hipErrorInvalidValue, "non-finite vertex position");
-    float ms = 0.0f; (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
-    out.nodes = b.nodes; out.nodeCount = nodeCount; out.nodes4 = b.nodes4; out.node4Count = tail4[0] + tail4[1]; out.nodes4Capacity = m.nodes4Capacity;
-    out.tris = b.tris; out.attrs = b.attrs; out.tangents = b.tangents; out.triCount = n; out.leafOrder = b.valB;
-    {
-        float dx = std::max(rootNode.lmax[0], rootNode.rmax[0]) - std::min(rootNode.lmin[0], rootNode.rmin[0]);
-        float dy = std::max(rootNode.lmax[1], rootNode.rmax[1]) - std::min(rootNode.lmin[1], rootNode.rmin[1]);
-        float dz = std::max(rootNode.lmax[2], rootNode.rmax[2]) - std::min(rootNode.lmin[2], rootNode.rmin[2]);
-        float ra = dx * dy + dy * dz + dz * dx;
-        out.sahCost = ra > 0.0f ? 1.0f + sahSum / ra : 0.0f;
-    }
-    out.maxDepth = m.lastMaxDepth; out.maxDepth4 = flags[2]; out.mortonBits = m.lastBits; out.ploc = m.lastPloc; out.deviceMs = ms; out.refitted = true;
-    return hipSuccess;
-}
+hipError_t GpuBvhBuilder::refit(const HrptPerInstanceData* instances, hipStream_t stream, GpuBuiltBvh& out, GpuBuildError& error) { return refit_tree(p.get(), instances, nullptr, stream, out, error); }
+hipError_t GpuBvhBuilder::refit_boxes(const float* boxes, hipStream_t stream, GpuBuiltBvh& out, GpuBuildError& error) { return refit_tree(p.get(), nullptr, boxes, stream, out, error); }
 
 // ---- the tree over the INSTANCES of the two-level structure (box mode): copies the nodes to the front of the scene's node array with every
 // leaf -- position k of the final leaf order -- turned into the instance reference the two-level traversal expects, ~(instance << 2)

@@ -82,8 +82,8 @@ struct Context {
     DeviceAllocations bvhAllocations;        // acceleration structure of the host builder + per-instance records: replaced by hrpt_update_instances
     DeviceBuffer<GpuNodeQ> nodesQ; size_t nodesQCapacity = 0;    // quantised copy of the flat 4-wide tree (pt_device.h GpuNodeQ), kept across rebuilds
     uint32_t nodes4Capacity = 0;             // records behind view.nodes4 when it is the GPU builder's buffer (0: allocated to size), for hrpt_selftest_read_bvh
-    GpuBvhBuilder* gpuBuilder = nullptr;     // GPU builders: geometry + build buffers stay on the device for rebuilds
-    GpuBvhBuilder* tlasBuilder = nullptr; uint32_t tlasBuilderInstances = 0;   // two-level structure: the tree over the instances, built on the GPU (build_two_level)
+    std::unique_ptr<GpuBvhBuilder> gpuBuilder;   // GPU builders: geometry + build buffers stay on the device for rebuilds
+    std::unique_ptr<GpuBvhBuilder> tlasBuilder; uint32_t tlasBuilderInstances = 0;   // two-level structure: the tree over the instances, built on the GPU (build_two_level)
     // host copy of what a rebuild needs (the reference's Scene keeps the same vectors: m_InstanceData, m_Vertices, m_Indices, m_MeshData)
     std::vector<HrptVertexQuantized> keptVertices; std::vector<uint32_t> keptIndices; std::vector<HrptMeshData> keptMeshData;
     std::vector<HrptPerInstanceData> keptInstances; std::vector<HrptMaterialConstants> keptMaterials; std::vector<HrptGPULight> keptLights;

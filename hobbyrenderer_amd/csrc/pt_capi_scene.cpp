@@ -31,8 +31,8 @@ static void free_acceleration(HrptContext* c, bool keepGpuBuilder)
 {
     c->bvhAllocations.clear();
     if (!keepGpuBuilder) {
-        delete c->gpuBuilder; c->gpuBuilder = nullptr;
-        delete c->tlasBuilder; c->tlasBuilder = nullptr; c->tlasBuilderInstances = 0;
+        c->gpuBuilder.reset();
+        c->tlasBuilder.reset(); c->tlasBuilderInstances = 0;
         c->meshAllocations.clear();
         delete c->twoLevel; c->twoLevel = nullptr;
     }
@@ -76,10 +76,10 @@ constexpr int kTwoLevelDoesNotFit = 1;
 // per instance and runs the kernels. false: not built (a device error, a tree too deep): the caller builds the tree on the host instead.
 static bool build_instance_tree_on_gpu(HrptContext* c, uint32_t instanceCount, const std::vector<float>& boxes, bool rebuild, bool refit, GpuNode4* dstNodes, uint32_t& depth4Levels)
 {
-    std::string gerr;
+    GpuBuildError gerr;
     if (!c->tlasBuilder || c->tlasBuilderInstances != instanceCount) {
-        delete c->tlasBuilder; c->tlasBuilder = new GpuBvhBuilder(); c->tlasBuilderInstances = 0;
-        if (c->tlasBuilder->prepare_boxes(instanceCount, c->stream, gerr) != hipSuccess) { delete c->tlasBuilder; c->tlasBuilder = nullptr; return false; }
+        c->tlasBuilder = std::make_unique<GpuBvhBuilder>(); c->tlasBuilderInstances = 0;
+        if (c->tlasBuilder->prepare_boxes(instanceCount, c->stream, gerr) != hipSuccess) { c->tlasBuilder.reset(); return false; }
         c->tlasBuilderInstances = instanceCount;
     }
     GpuBuiltBvh g;
@@ -202,13 +202,13 @@ int capi::build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t sc
     uint32_t maxDepth = 0, maxDepth4 = 0;
     bool built = false;
     const int builder = c->bvhBuilder == HRPT_BVH_BUILDER_AUTO ? (sceneTris >= 65536 ? HRPT_BVH_BUILDER_GPU_PLOC : HRPT_BVH_BUILDER_HOST_SAH) : c->bvhBuilder;
-    if (builder != HRPT_BVH_BUILDER_GPU_LBVH && builder != HRPT_BVH_BUILDER_GPU_PLOC) { delete c->gpuBuilder; c->gpuBuilder = nullptr; }
+    if (builder != HRPT_BVH_BUILDER_GPU_LBVH && builder != HRPT_BVH_BUILDER_GPU_PLOC) c->gpuBuilder.reset();
     if ((builder == HRPT_BVH_BUILDER_GPU_LBVH || builder == HRPT_BVH_BUILDER_GPU_PLOC) && sceneTris >= 8) {
         // the whole build runs on the device; only the per-instance adjugate rows (O(instances)) are prepared on the host
-        GpuBuiltBvh g; std::string gerr;
+        GpuBuiltBvh g; GpuBuildError gerr;
         hipError_t ge = hipSuccess;
         if (!c->gpuBuilder) {
-            c->gpuBuilder = new GpuBvhBuilder();
+            c->gpuBuilder = std::make_unique<GpuBvhBuilder>();
             ge = c->gpuBuilder->prepare(s, scene_needs_tangents(s), c->stream, gerr);
         }
         if (ge == hipSuccess) ge = (refit && !firstBuild && c->gpuBuilder->can_refit()) ? c->gpuBuilder->refit(s.instances, c->stream, g, gerr)
@@ -230,9 +230,12 @@ int capi::build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t sc
             if (g.refitted) c->buildInfo.usedBuilder |= HRPT_BVH_BUILDER_REFITTED;
         } else {
             // too deep for the traversal stacks (or a device error): drop the device-side builder and build on the host instead
-            delete c->gpuBuilder; c->gpuBuilder = nullptr;
-            if (ge == hipErrorInvalidValue && gerr == "non-finite vertex position") return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + gerr);
-            if (ge == hipErrorOutOfMemory) return fail(c, HRPT_ERR_OUT_OF_MEMORY, "acceleration structure: " + gerr);
+            c->gpuBuilder.reset();
+            switch (gerr.reason) {
+            case GpuBuildFailure::NonFinitePosition: return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + gerr.message);
+            case GpuBuildFailure::OutOfMemory: return fail(c, HRPT_ERR_OUT_OF_MEMORY, "acceleration structure: " + gerr.message);
+            case GpuBuildFailure::DoesNotFit: case GpuBuildFailure::DeviceError: case GpuBuildFailure::None: break;      // the host builder takes over
+            }
         }
         if (built) {
             std::vector<HostInstShade> shade; build_instance_shade(s, shade);

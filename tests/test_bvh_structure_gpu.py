@@ -266,6 +266,29 @@ def test_morton_bit_fallback(luts):
         ctx.close()
 
 
+def test_morton_bit_fallback_is_remembered(luts):
+    """What the builder keeps between builds, on the fallback path: a rebuild starts at the Morton-bit budget that fitted last time and gives
+    the same trees; a refit works on the hierarchy of that rebuild and, from unchanged transforms, gives the same 2-wide nodes (the fit is a
+    min / max over the same boxes: order-independent)."""
+    sc = B.triangle_scene(luts, caterpillar_triangles())
+    ctx = native.PathTracerContext(0)
+    try:
+        ctx.set_bvh_builder(S.BVH_BUILDER_GPU_LBVH)
+        ctx.upload_scene(sc)
+        first, bi, _ = check_flat_context(ctx, sc)
+        assert bi.usedBuilder == S.BVH_BUILDER_GPU_LBVH and bi.mortonBits < 63, (hex(bi.usedBuilder), bi.mortonBits)
+        ctx.update_instances(sc.instances)
+        again, bi2, _ = check_flat_context(ctx, sc)
+        assert bi2.mortonBits == bi.mortonBits
+        assert again["nodes"].tobytes() == first["nodes"].tobytes() and again["nodes4"].tobytes() == first["nodes4"].tobytes()
+        ctx.refit_instances(sc.instances)
+        refitted, bi3, _ = check_flat_context(ctx, sc)
+        assert bi3.usedBuilder & S.BVH_BUILDER_REFITTED, hex(bi3.usedBuilder)
+        assert refitted["nodes"].tobytes() == first["nodes"].tobytes()
+    finally:
+        ctx.close()
+
+
 # ------------------------------------------------------------------------------------------------ two-level structure
 def check_two_level_context(ctx, sc, gpu_tree):
     bi = ctx.build_info()
