@@ -30,7 +30,9 @@ inline uint32_t triangle_flags_for_material(const HrptMaterialConstants& m)
     return opaque | (cls << 1);
 }
 
-struct HostNode {           // mirrors hrt::GpuNode (pt_device.h), 64 B
+// The Host* records below are uploaded as they are and read by the kernels as the Gpu* records of pt_scene_records.h; pt_record_layout.h
+// asserts every pair's size and field offsets.
+struct HostNode {           // mirrors hrt::GpuNode (pt_scene_records.h), 64 B
     float lmin[3]; int32_t left;
     float lmax[3]; int32_t right;
     float rmin[3]; uint32_t pad0;
@@ -44,7 +46,7 @@ struct HostTri {            // mirrors hrt::GpuTri, 48 B
 // 4-wide node for the wavefront kernels (collapsed from the BVH2): child boxes in SoA (x of 4 children, y, z, ...) so
 // the four slab tests are data-parallel; 128 B = two cache lines fetched together. Empty slots: a degenerate box at 1e30.
 // Row order min/max interleaved per axis: the traversal picks the NEAR row of an axis by the sign of the ray direction
-// (byte offset axis * 32 + (d < 0 ? 16 : 0)) and gets the far row as near ^ 16 (pt_device.h inner_step).
+// (byte offset axis * 32 + (d < 0 ? 16 : 0)) and gets the far row as near ^ 16 (pt_traverse.h inner_step).
 struct HostNode4 {
     float minx[4], maxx[4], miny[4], maxy[4], minz[4], maxz[4];
     int32_t child[4];               // >= 0 inner node4 index, < 0 leaf (same encoding as HostNode), kEmptyChild = unused slot
@@ -66,8 +68,6 @@ struct HostTriAttr {
 struct HostTriTangent { float t0[4], t1[4], t2[4]; };   // DecodeOct tangents + sign, only built when a normal map exists
 // MakeAdjugateMatrix(world) rows (Common.hlsli:33-41), computed once per instance with the same cross products.
 struct HostInstShade { float adj0[4], adj1[4], adj2[4]; };
-static_assert(sizeof(HostNode4) == 128, "GPU layouts");
-static_assert(sizeof(HostNode) == 64 && sizeof(HostTri) == 48 && sizeof(HostTriAttr) == 80 && sizeof(HostInstShade) == 48, "GPU layouts");
 
 struct BuiltBvh {
     std::vector<HostNode> nodes;    // empty when the scene fits one leaf
@@ -88,7 +88,7 @@ struct BuiltBvh {
 // change: at a leaf the traversal transforms the three object-space vertices with the instance's m_World exactly as the flat upload
 // does (transform_point) and runs the same watertight test on the world-space ray, so (t, u, v) and the (t, instance, primitive) order
 // are bit-identical to the flat path; only the culling runs on an object-space ray.
-struct HostInstance {           // mirrors hrt::GpuInstance (pt_device.h), 128 B
+struct HostInstance {           // mirrors hrt::GpuInstance (pt_scene_records.h), 128 B
     float world[12];            // rows 0..3 of m_World, xyz each (row-vector convention: p_world = p * M, translation in row 3)
     float inv[12];              // the inverse map in the same layout: p_object = p_world * Minv
     int32_t blasRoot;           // node4 index of the mesh's tree (>= 0) or an encoded leaf (< 0) when the whole mesh is one leaf
@@ -101,7 +101,6 @@ struct HostInstance {           // mirrors hrt::GpuInstance (pt_device.h), 128 B
     float invNorm;              // max column sum of |Minv| (bounds |v * Minv| by invNorm * max|v_k|)
     uint32_t pad;
 };
-static_assert(sizeof(HostInstance) == 128, "GPU layouts");
 struct BuiltTwoLevel {
     std::vector<HostNode4> nodes4;        // [0, tlasNodeCount): the tree over instances (root 0, leaves = one instance: ~((instance << 2) | 0));
                                           // behind it the trees of the distinct meshes, child indices already offset into this array
@@ -130,7 +129,7 @@ constexpr uint32_t kTraversalStackDepth = 64;   // 2-wide trees: the builders gu
 constexpr uint32_t kHostBuilderDepthGoal = 32;  // the host SAH builder switches to median splits early enough to stay below this
 
 // Validates every index / range of the scene description (false + message); triCount = world triangles over all instances.
-// (flatLimit: the traversal kernels address nodes and triangle records by 32-bit byte offsets from the array base (pt_device.h GlobalBvh4), so one
+// (flatLimit: the traversal kernels address nodes and triangle records by 32-bit byte offsets from the array base (pt_traverse.h GlobalBvh4), so one
 // structure holds fewer than 2^32 / 48 triangle records and 2^25 nodes of 128 bytes (checked after the build: a 4-wide tree over N triangles
 // has between N / 12 and N nodes); the two-level structure only counts DISTINCT triangles, and instances as leaves of its upper tree)
 constexpr uint64_t kMaxStructureTriangles = 0xFFFFFFFFull / 48ull, kMaxStructureNodes = 1ull << 25;

@@ -7,7 +7,7 @@
 #include <string>
 
 #include "../../include/hobbyrt_pt.h"
-#include "pt_device.h"
+#include "pt_scene_records.h"
 
 namespace hrt {
 

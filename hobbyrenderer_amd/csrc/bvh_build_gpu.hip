@@ -6,7 +6,7 @@
 // touching a triangle. The reference hands this job to the D3D12 driver (BLAS/TLAS build on the graphics queue); real-time modes
 // rebuild the TLAS every frame (src/CommonRenderers.cpp:234-246), which is what a GPU build is for.
 //
-// Radiance does not depend on which builder ran: the hit definition of pt_device.h is BVH-independent (closest = min (t, inst, prim),
+// Radiance does not depend on which builder ran: the hit definition of pt_traverse.h is BVH-independent (closest = min (t, inst, prim),
 // candidates revisited through exclusive lower keys), boxes are padded conservatively with the host builder's rule, and the world
 // transform / attribute unpacking use the same expression order with -ffp-contract=off.
 #include "bvh_build_gpu.h"

@@ -7,7 +7,7 @@
 // D3D12 driver is unpinned for all three, like SampleGrad's level of detail):
 //   * pixel uv of a full-screen pass over a w x h target: ((px + 0.5f) / w, (py + 0.5f) / h)
 //   * SampleLevel(linearClamp, uv, 0): x = u * w - 0.5, x0 = floor(x), fx = x - x0, texels x0 and x0 + 1 clamped to [0, w - 1] (same in
-//     y), fp32 weights, a(1 - t) + bt along x, then along y -- the filter DESIGN section 2 fixes for textures (lerp4 of pt_device.h)
+//     y), fp32 weights, a(1 - t) + bt along x, then along y -- the filter DESIGN section 2 fixes for textures (lerp4 of pt_vec.h)
 //   * the pyramids are R11G11B10_FLOAT (BloomRenderer.cpp:31): every pass's result is rounded into one 32-bit word -- R bits 0-10 and
 //     G bits 11-21 with 5 exponent + 6 mantissa bits, B bits 22-31 with 5 + 5, bias 15, no sign -- and every sample reads the unpacked
 //     values. From fp32: negative -> 0, NaN -> NaN, +inf -> inf, anything else ROUNDS TOWARD ZERO (so a value above the largest finite

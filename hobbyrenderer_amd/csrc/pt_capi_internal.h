@@ -18,10 +18,10 @@
 #include "bvh_build.h"
 #include "bvh_build_gpu.h"
 #include "pt_anim.h"
-#include "pt_device.h"
 #include "pt_device_buffer.h"
 #include "pt_kernels.h"
-#include "pt_motion.h"
+#include "pt_motion_records.h"
+#include "pt_scene_records.h"
 #include "pt_wavefront.h"
 
 namespace hrt::capi {
@@ -80,7 +80,7 @@ struct Context {
     // scene
     DeviceAllocations allocations;           // scene-lifetime device allocations
     DeviceAllocations bvhAllocations;        // acceleration structure of the host builder + per-instance records: replaced by hrpt_update_instances
-    DeviceBuffer<GpuNodeQ> nodesQ; size_t nodesQCapacity = 0;    // quantised copy of the flat 4-wide tree (pt_device.h GpuNodeQ), kept across rebuilds
+    DeviceBuffer<GpuNodeQ> nodesQ; size_t nodesQCapacity = 0;    // quantised copy of the flat 4-wide tree (pt_scene_records.h GpuNodeQ), kept across rebuilds
     uint32_t nodes4Capacity = 0;             // records behind view.nodes4 when it is the GPU builder's buffer (0: allocated to size), for hrpt_selftest_read_bvh
     std::unique_ptr<GpuBvhBuilder> gpuBuilder;   // GPU builders: geometry + build buffers stay on the device for rebuilds
     std::unique_ptr<GpuBvhBuilder> tlasBuilder; uint32_t tlasBuilderInstances = 0;   // two-level structure: the tree over the instances, built on the GPU (build_two_level)
@@ -159,19 +159,29 @@ inline bool size_ok(uint32_t width, uint32_t height) { return !(width == 0 || he
 int realloc_image(HrptContext* c, DeviceBuffer<float4>& image, size_t bytes);      // a fresh image, zeroed on the context stream
 int read_image(HrptContext* c, const float4* src, float* dst, size_t bytes, const char* what);
 
-// A device copy of host[0 .. count), owned by `owner` (default: the scene's allocation list).
+// Device room for `count` records owned by `owner` (default: the scene's allocation list), with host[skip .. count) copied into place:
+// the records in front of `skip` are the caller's to write on the device.
 template <class T>
-int upload(HrptContext* c, const T* host, size_t count, const T** dev, DeviceAllocations* owner = nullptr)
+int upload_writable(HrptContext* c, const T* host, size_t count, T** dev, DeviceAllocations* owner = nullptr, size_t skip = 0)
 {
     *dev = nullptr;
     size_t bytes = count * sizeof(T);
     DeviceBuffer<void> p;
     HIP_TRY(c, p.alloc(bytes ? bytes : 16));
-    void* d = p.get();
+    T* d = static_cast<T*>(p.get());
     (owner ? *owner : c->allocations).push_back(std::move(p));
-    if (bytes) HIP_TRY(c, hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream));
-    *dev = static_cast<const T*>(d);
+    if (count > skip) HIP_TRY(c, hipMemcpyAsync(d + skip, host + skip, (count - skip) * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    *dev = d;
     return HRPT_OK;
+}
+// A device copy of host[0 .. count).
+template <class T>
+int upload(HrptContext* c, const T* host, size_t count, const T** dev, DeviceAllocations* owner = nullptr)
+{
+    T* d = nullptr;
+    const int r = upload_writable(c, host, count, &d, owner);
+    *dev = d;
+    return r;
 }
 
 // pt_capi_scene.cpp

@@ -4,9 +4,23 @@
 #include <chrono>
 
 #include "pt_capi_internal.h"
+#include "pt_record_layout.h"
 
 using namespace hrt;
 using namespace hrt::capi;
+
+// The one place a Host* array becomes the Gpu* array the kernels read (pt_record_layout.h holds the layout contract): a device copy of
+// `host` owned by `owner`. G is const GpuX for a table the device only reads; a caller that asks for a writable GpuX* fills the first `skip`
+// records, which are not copied, on the device itself.
+template <class H, class G>
+static int upload_records(HrptContext* c, const std::vector<H>& host, G** dev, DeviceAllocations* owner, size_t skip = 0)
+{
+    static_assert(std::is_same<typename std::remove_const<G>::type, typename GpuRecordOf<H>::type>::value, "pt_record_layout.h GpuRecordOf");
+    H* d = nullptr;
+    const int r = upload_writable(c, host.data(), host.size(), &d, owner, skip);
+    *dev = reinterpret_cast<G*>(d);
+    return r;
+}
 
 // DirectX::PackedVector::XMConvertFloatToHalf (round to nearest even), src/CommonResources.cpp:553
 static uint16_t float_to_half(float f)
@@ -97,9 +111,32 @@ static bool build_instance_tree_on_gpu(HrptContext* c, uint32_t instanceCount, c
     return true;
 }
 
+// The per-mesh arrays of the two-level structure into `v`: triangles, their attribute records and, where a material samples a normal map, tangents.
+static int upload_triangles(HrptContext* c, const BuiltTwoLevel& b, SceneView& v, DeviceAllocations* owner)
+{
+    HRPT_TRY(upload_records(c, b.tris, &v.tris, owner));
+    HRPT_TRY(upload_records(c, b.attrs, &v.attrs, owner));
+    v.triCount = (uint32_t)b.tris.size();
+    v.tangents = nullptr;
+    if (!b.tangents.empty()) HRPT_TRY(upload_records(c, b.tangents, &v.tangents, owner));
+    return HRPT_OK;
+}
+
+// What an instance update replaces, into `v`: the node array (the tree over the instances in front of the mesh trees), the instance records and
+// their adjugate rows. The first `reservedNodes` nodes are not copied: the caller writes them on the device, through `nodes4`.
+static int upload_instance_level(HrptContext* c, const BuiltTwoLevel& b, SceneView& v, uint32_t reservedNodes, GpuNode4*& nodes4)
+{
+    HRPT_TRY(upload_records(c, b.nodes4, &nodes4, &c->bvhAllocations, reservedNodes));
+    HRPT_TRY(upload_records(c, b.instances, &v.instances, &c->bvhAllocations));
+    HRPT_TRY(upload_records(c, b.instShade, &v.instShade, &c->bvhAllocations));
+    v.nodes4 = nodes4; v.node4Count = (uint32_t)b.nodes4.size(); v.nodesQ = nullptr;
+    v.instanceCount = (uint32_t)b.instances.size();
+    return HRPT_OK;
+}
+
 static int build_two_level(HrptContext* c, const HrptSceneDesc& s, SceneView& v, bool instancesOnly, bool refit)
 {
-    std::string berr; int r;
+    std::string berr;
     const bool timing = getenv("HRPT_BUILD_TIMING") != nullptr; auto tp = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (!timing) return; (void)hipStreamSynchronize(c->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[two-level] %-22s %7.3f ms\n", what, std::chrono::duration<float, std::milli>(t - tp).count()); tp = t; };
     // who builds the tree over the instances: the GPU from 1024 instances on (host SAH: 2 / 6 / 16 ms for 4 096 / 16 384 / 65 536 instances, the GPU
@@ -117,50 +154,27 @@ static int build_two_level(HrptContext* c, const HrptSceneDesc& s, SceneView& v,
     lap("host records");
     BuiltTwoLevel& b = *c->twoLevel;
     if (two_level_stack_need(b) > 128u) return kTwoLevelDoesNotFit;
-    if (!instancesOnly) {
-        const HostTri* dt; const HostTriAttr* da; const HostTriTangent* dtg;
-        if ((r = upload(c, b.tris.data(), b.tris.size(), &dt, &c->meshAllocations)) != HRPT_OK) return r;
-        if ((r = upload(c, b.attrs.data(), b.attrs.size(), &da, &c->meshAllocations)) != HRPT_OK) return r;
-        v.tris = reinterpret_cast<const GpuTri*>(dt); v.triCount = (uint32_t)b.tris.size(); v.attrs = reinterpret_cast<const GpuTriAttr*>(da);
-        v.tangents = nullptr;
-        if (!b.tangents.empty()) {
-            if ((r = upload(c, b.tangents.data(), b.tangents.size(), &dtg, &c->meshAllocations)) != HRPT_OK) return r;
-            v.tangents = reinterpret_cast<const GpuTriTangent*>(dtg);
-        }
-    }
-    const HostNode4* dn4; const HostInstance* di; const HostInstShade* dis;
+    if (!instancesOnly) HRPT_TRY(upload_triangles(c, b, v, &c->meshAllocations));
     if (b.nodes4.size() >= kMaxStructureNodes) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: more than 2^25 nodes (32-bit node offsets in the traversal kernels)");
-    if (gpuTree) {      // the reserved range at the front is written on the device (launch_tlas_fixup): only the mesh trees behind it cross PCIe
-        DeviceBuffer<void> nodes;
-        HIP_TRY(c, nodes.alloc(b.nodes4.size() * sizeof(HostNode4)));
-        void* p = nodes.get();
-        c->bvhAllocations.push_back(std::move(nodes));
-        dn4 = static_cast<const HostNode4*>(p);
-        HIP_TRY(c, hipMemcpyAsync(static_cast<HostNode4*>(p) + b.tlasNodeCount, b.nodes4.data() + b.tlasNodeCount, (b.nodes4.size() - b.tlasNodeCount) * sizeof(HostNode4), hipMemcpyHostToDevice, c->stream));
-    } else if ((r = upload(c, b.nodes4.data(), b.nodes4.size(), &dn4, &c->bvhAllocations)) != HRPT_OK) return r;
-    if ((r = upload(c, b.instances.data(), b.instances.size(), &di, &c->bvhAllocations)) != HRPT_OK) return r;
-    if ((r = upload(c, b.instShade.data(), b.instShade.size(), &dis, &c->bvhAllocations)) != HRPT_OK) return r;
+    // gpuTree: the reserved range at the front is written on the device (launch_tlas_fixup): only the mesh trees behind it cross PCIe
+    GpuNode4* nodes4 = nullptr;
+    HRPT_TRY(upload_instance_level(c, b, v, gpuTree ? b.tlasNodeCount : 0, nodes4));
     lap("uploads");
     if (gpuTree) {
         uint32_t levels = 0;
-        if (build_instance_tree_on_gpu(c, s.instanceCount, boxes, instancesOnly, refit, const_cast<GpuNode4*>(reinterpret_cast<const GpuNode4*>(dn4)), levels)) {
+        if (build_instance_tree_on_gpu(c, s.instanceCount, boxes, instancesOnly, refit, nodes4, levels)) {
             b.maxDepth4Tlas = levels;
         } else {
             // the host builds it after all: same layout rules as ever (the reserved node range shrinks to the tree's size)
             c->bvhAllocations.clear();
             if (!rebuild_two_level_instances(s, b, berr)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + berr);
-            if ((r = upload(c, b.nodes4.data(), b.nodes4.size(), &dn4, &c->bvhAllocations)) != HRPT_OK) return r;
-            if ((r = upload(c, b.instances.data(), b.instances.size(), &di, &c->bvhAllocations)) != HRPT_OK) return r;
-            if ((r = upload(c, b.instShade.data(), b.instShade.size(), &dis, &c->bvhAllocations)) != HRPT_OK) return r;
+            HRPT_TRY(upload_instance_level(c, b, v, 0, nodes4));
             gpuTree = false;
         }
     }
     lap("instance tree (GPU)");
     if (two_level_stack_need(b) > 128u) return kTwoLevelDoesNotFit;
     v.nodes = nullptr; v.nodeCount = b.tlasNodeCount; v.rootLeaf = b.tlasRootLeaf;      // nodeCount != 0: the walk starts at node4 0 (the instance tree)
-    v.nodes4 = reinterpret_cast<const GpuNode4*>(dn4); v.node4Count = (uint32_t)b.nodes4.size(); v.nodesQ = nullptr;
-    v.instances = reinterpret_cast<const GpuInstance*>(di); v.instanceCount = (uint32_t)b.instances.size();
-    v.instShade = reinterpret_cast<const GpuInstShade*>(dis);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!gpuTree) c->buildInfo.usedBuilder = HRPT_BVH_BUILDER_HOST_SAH;      // (the mesh trees are the host's either way; usedBuilder names who built the tree over the instances)
     c->buildInfo.structure = HRPT_ACCEL_TWO_LEVEL;
@@ -172,6 +186,118 @@ static int build_two_level(HrptContext* c, const HrptSceneDesc& s, SceneView& v,
     return HRPT_OK;
 }
 
+// ---- the flat structure: one route per builder, each says whether it built (a status other than HRPT_OK ends the build), then the quantised nodes ----
+struct TreeDepths { uint32_t maxDepth = 0, maxDepth4 = 0; };
+
+// experiment (HRPT_GPU_BVH_HOST_COLLAPSE): the GPU-built 2-wide tree with the host's area-greedy, depth-first 4-wide collapse
+static int collapse_gpu_tree_on_host(HrptContext* c, const GpuBuiltBvh& g, SceneView& v, TreeDepths& depths)
+{
+    std::vector<HostNode> n2(g.nodeCount); std::vector<HostNode4> n4; uint32_t d4 = 0;
+    HIP_TRY(c, hipMemcpy(n2.data(), g.nodes, n2.size() * sizeof(HostNode), hipMemcpyDeviceToHost));
+    collapse_bvh2_on_host(n2, n4, d4);
+    HRPT_TRY(upload_records(c, n4, &v.nodes4, &c->bvhAllocations));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    v.node4Count = (uint32_t)n4.size(); depths.maxDepth4 = d4; c->nodes4Capacity = 0;
+    return HRPT_OK;
+}
+
+// The GPU builders: the whole build runs on the device; only the per-instance adjugate rows (O(instances)) are prepared on the host.
+// Not built and HRPT_OK: too deep for the traversal stacks, or a device error -- the host builder takes over.
+static int build_flat_on_gpu(HrptContext* c, const HrptSceneDesc& s, bool usePloc, bool refit, SceneView& v, TreeDepths& depths, bool& built)
+{
+    GpuBuiltBvh g; GpuBuildError gerr;
+    hipError_t ge = hipSuccess;
+    if (!c->gpuBuilder) {
+        c->gpuBuilder = std::make_unique<GpuBvhBuilder>();
+        ge = c->gpuBuilder->prepare(s, scene_needs_tangents(s), c->stream, gerr);
+    }
+    if (ge == hipSuccess) ge = (refit && c->gpuBuilder->can_refit()) ? c->gpuBuilder->refit(s.instances, c->stream, g, gerr)
+                                                                     : c->gpuBuilder->build(s.instances, usePloc, kTraversalStackDepth, c->stream, g, gerr);
+    if (ge != hipSuccess || g.maxDepth + 2 > kTraversalStackDepth) {
+        c->gpuBuilder.reset();      // drop the device-side builder
+        switch (gerr.reason) {
+        case GpuBuildFailure::NonFinitePosition: return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + gerr.message);
+        case GpuBuildFailure::OutOfMemory: return fail(c, HRPT_ERR_OUT_OF_MEMORY, "acceleration structure: " + gerr.message);
+        case GpuBuildFailure::DoesNotFit: case GpuBuildFailure::DeviceError: case GpuBuildFailure::None: break;      // the host builder takes over
+        }
+        return HRPT_OK;
+    }
+    v.nodes = g.nodes; v.nodeCount = g.nodeCount; v.nodes4 = g.nodes4; v.node4Count = g.node4Count; v.tris = g.tris; v.triCount = g.triCount;
+    v.rootLeaf = 0; v.attrs = g.attrs; v.tangents = g.tangents;
+    depths.maxDepth = g.maxDepth; depths.maxDepth4 = g.maxDepth4; built = true; c->nodes4Capacity = g.nodes4Capacity;
+    if (getenv("HRPT_GPU_BVH_HOST_COLLAPSE")) HRPT_TRY(collapse_gpu_tree_on_host(c, g, v, depths));
+    c->buildInfo.usedBuilder = g.ploc ? HRPT_BVH_BUILDER_GPU_PLOC : HRPT_BVH_BUILDER_GPU_LBVH; c->buildInfo.deviceBuildMs = g.deviceMs; c->buildInfo.mortonBits = g.mortonBits; c->buildInfo.sahCost = g.sahCost;
+    if (g.refitted) c->buildInfo.usedBuilder |= HRPT_BVH_BUILDER_REFITTED;
+    std::vector<HostInstShade> shade; build_instance_shade(s, shade);
+    HRPT_TRY(upload_records(c, shade, &v.instShade, &c->bvhAllocations));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HRPT_OK;
+}
+
+// The host builder (binned SAH): always builds, or refuses the scene.
+static int build_flat_on_host(HrptContext* c, const HrptSceneDesc& s, SceneView& v, TreeDepths& depths)
+{
+    BuiltBvh bvh; std::string berr;
+    if (!build_scene_bvh(s, bvh, berr)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + berr);
+    DeviceAllocations* own = &c->bvhAllocations;
+    HRPT_TRY(upload_records(c, bvh.nodes, &v.nodes, own));
+    HRPT_TRY(upload_records(c, bvh.tris, &v.tris, own));
+    v.nodeCount = (uint32_t)bvh.nodes.size(); v.triCount = (uint32_t)bvh.tris.size();
+    v.rootLeaf = bvh.rootLeaf;
+    HRPT_TRY(upload_records(c, bvh.nodes4, &v.nodes4, own));
+    v.node4Count = (uint32_t)bvh.nodes4.size();
+    // The quantised vertex / index / mesh / instance buffers are consumed here: per-triangle attribute records and
+    // per-instance adjugate rows replace the per-hit GetTriangleVertices + UnpackVertex + MakeAdjugateMatrix work.
+    HRPT_TRY(upload_records(c, bvh.attrs, &v.attrs, own));
+    HRPT_TRY(upload_records(c, bvh.instShade, &v.instShade, own));
+    v.tangents = nullptr;
+    if (!bvh.tangents.empty()) HRPT_TRY(upload_records(c, bvh.tangents, &v.tangents, own));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // the BuiltBvh staging vectors die at scope exit
+    depths.maxDepth = bvh.maxDepth; depths.maxDepth4 = bvh.maxDepth4;
+    c->buildInfo.usedBuilder = HRPT_BVH_BUILDER_HOST_SAH; c->buildInfo.sahCost = bvh.sahCost;
+    return HRPT_OK;
+}
+
+// The 64-byte quantised form of the 4-wide tree, whichever builder made it (what the wavefront kernels may read when the tree is not in LDS),
+// and the choice of the form the kernels walk. quantised = false with HRPT_OK: there are no nodes (the scene fits one leaf), or the fp32 nodes are walked.
+static int quantise_nodes(HrptContext* c, const HrptSceneDesc& s, SceneView& v, bool& quantised)
+{
+    v.nodesQ = nullptr; quantised = false;
+    if (!v.node4Count) return HRPT_OK;
+    if (c->nodesQCapacity <= v.node4Count) {                   // (<=: record nodesQCapacity - 1 is the accumulator below, never a node)
+        c->nodesQ.reset(); c->nodesQCapacity = 0;
+        const size_t cap = (size_t)v.node4Count + v.node4Count / 8 + 64;
+        if (c->nodesQ.alloc(cap * sizeof(GpuNodeQ)) != hipSuccess) return fail(c, HRPT_ERR_OUT_OF_MEMORY, "acceleration structure: quantised nodes");
+        c->nodesQCapacity = cap;
+    }
+    double* dArea = reinterpret_cast<double*>(c->nodesQ + (c->nodesQCapacity - 1));       // the last (spare) record of the buffer: two doubles
+    HIP_TRY(c, hipMemsetAsync(dArea, 0, 4 * sizeof(double), c->stream));
+    HIP_TRY(c, launch_quantise_nodes(v.nodes4, v.node4Count, c->nodesQ, dArea, c->stream));
+    double area[4] = { 0.0, 0.0, 0.0, 0.0 };
+    HIP_TRY(c, hipMemcpyAsync(area, dArea, sizeof area, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    v.nodesQ = c->nodesQ;
+    // Which nodes the kernels walk when the tree is in global memory. The quantised form saves three of seven 16-byte requests per lane and
+    // step and pays in decode arithmetic and in looser boxes; what the looser LEAF boxes cost is triangle tests (three requests + a
+    // watertight test each). Measured (MI355X, 1080p): Sponza-class scene: wf_extend 6.66 -> 6.18 ms, frame 13.8 -> 13.3 ms; glass scene
+    // (18 k triangles of tessellated glass bodies): shadow-ray triangle tests x 2.4, closest-hit leaf visits + 43 %, frame +2 %.
+    const float inflation = area[0] > 0.0 ? (float)(area[1] / area[0]) : 1.0f;
+    if (getenv("HRPT_BVH_NODE_FORMAT_DEBUG")) fprintf(stderr, "quantised nodes: leaf area ratio %.4f (area-weighted), %.4f (mean over %.0f leaves)\n", inflation, area[3] > 0 ? area[2] / area[3] : 1.0, area[3]);
+    int format = 0;
+    if (const char* e = getenv("HRPT_BVH_NODE_FORMAT")) format = atoi(e);          // 1: fp32 nodes, 2: quantised nodes, else by the leaf-area ratio
+    // (the leaf-area ratio is ~1.01 on BOTH scenes, so it does not tell them apart: on the glass scene it is the paths that bounce inside and between
+    // the finely tessellated glass bodies that visit 40 % more leaves through the rounded boxes. Until that is understood the rule is empirical:
+    // quantised nodes unless some instance is transmissive or BLEND.)
+    bool glassy = false;
+    for (uint32_t i = 0; i < s.instanceCount && !glassy; ++i) {
+        const HrptMaterialConstants& m = s.materials[s.instances[i].m_MaterialIndex];
+        glassy = m.m_TransmissionFactor > 0.0f || m.m_AlphaMode == HRPT_ALPHA_MODE_BLEND;
+    }
+    quantised = format == 2 || (format != 1 && inflation <= 1.10f && !glassy);
+    c->buildInfo.leafAreaPermille = (uint32_t)(inflation * 1000.0f + 0.5f); c->buildInfo.nodeFormat = quantised ? 2u : 1u;
+    return HRPT_OK;
+}
+
 // The acceleration structure + the records derived from instance transforms (Scene::BuildAccelerationStructures, src/Scene.cpp:67-214),
 // written into `v`. First build of a scene or a rebuild after hrpt_update_instances (the GPU builder then keeps its device-resident
 // geometry and buffers).
@@ -179,15 +305,13 @@ static int build_two_level(HrptContext* c, const HrptSceneDesc& s, SceneView& v,
 int capi::build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t sceneTris, SceneView& v, bool firstBuild, bool refit)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    std::string berr;
-    int r;
     c->buildInfo = HrptBuildInfo{};
     c->buildInfo.requestedBuilder = (uint32_t)c->bvhBuilder;
     c->buildInfo.structure = HRPT_ACCEL_FLAT; c->nodes4Capacity = 0;
     const bool keepMeshTrees = !firstBuild && c->twoLevel != nullptr;       // hrpt_update_instances on a two-level scene
     free_acceleration(c, !firstBuild);
     if (keepMeshTrees || (firstBuild && two_level_wanted(c, s, sceneTris))) {
-        r = build_two_level(c, s, v, keepMeshTrees, refit);
+        const int r = build_two_level(c, s, v, keepMeshTrees, refit);
         if (r != kTwoLevelDoesNotFit) {
             c->buildInfo.buildMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
             return r;
@@ -199,121 +323,21 @@ int capi::build_acceleration(HrptContext* c, const HrptSceneDesc& s, uint64_t sc
     }
     v.instances = nullptr; v.instanceCount = 0; c->traits.twoLevelStackNeed = 0;
     if (sceneTris >= kMaxStructureTriangles) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: too many triangles for the flat structure (2^32 / 48 = 89 M world-space triangles; instanced scenes can use HRPT_ACCEL_TWO_LEVEL)");
-    uint32_t maxDepth = 0, maxDepth4 = 0;
+    TreeDepths depths;
     bool built = false;
     const int builder = c->bvhBuilder == HRPT_BVH_BUILDER_AUTO ? (sceneTris >= 65536 ? HRPT_BVH_BUILDER_GPU_PLOC : HRPT_BVH_BUILDER_HOST_SAH) : c->bvhBuilder;
-    if (builder != HRPT_BVH_BUILDER_GPU_LBVH && builder != HRPT_BVH_BUILDER_GPU_PLOC) c->gpuBuilder.reset();
-    if ((builder == HRPT_BVH_BUILDER_GPU_LBVH || builder == HRPT_BVH_BUILDER_GPU_PLOC) && sceneTris >= 8) {
-        // the whole build runs on the device; only the per-instance adjugate rows (O(instances)) are prepared on the host
-        GpuBuiltBvh g; GpuBuildError gerr;
-        hipError_t ge = hipSuccess;
-        if (!c->gpuBuilder) {
-            c->gpuBuilder = std::make_unique<GpuBvhBuilder>();
-            ge = c->gpuBuilder->prepare(s, scene_needs_tangents(s), c->stream, gerr);
-        }
-        if (ge == hipSuccess) ge = (refit && !firstBuild && c->gpuBuilder->can_refit()) ? c->gpuBuilder->refit(s.instances, c->stream, g, gerr)
-                                                                                          : c->gpuBuilder->build(s.instances, builder == HRPT_BVH_BUILDER_GPU_PLOC, kTraversalStackDepth, c->stream, g, gerr);
-        if (ge == hipSuccess && g.maxDepth + 2 <= kTraversalStackDepth) {
-            v.nodes = g.nodes; v.nodeCount = g.nodeCount; v.nodes4 = g.nodes4; v.node4Count = g.node4Count; v.tris = g.tris; v.triCount = g.triCount;
-            v.rootLeaf = 0; v.attrs = g.attrs; v.tangents = g.tangents;
-            maxDepth = g.maxDepth; maxDepth4 = g.maxDepth4; built = true; c->nodes4Capacity = g.nodes4Capacity;
-            if (getenv("HRPT_GPU_BVH_HOST_COLLAPSE")) {     // experiment: the GPU-built 2-wide tree with the host's area-greedy, depth-first 4-wide collapse
-                std::vector<HostNode> n2(g.nodeCount); std::vector<HostNode4> n4; uint32_t d4 = 0;
-                HIP_TRY(c, hipMemcpy(n2.data(), g.nodes, n2.size() * sizeof(HostNode), hipMemcpyDeviceToHost));
-                collapse_bvh2_on_host(n2, n4, d4);
-                const HostNode4* dn4;
-                if ((r = upload(c, n4.data(), n4.size(), &dn4, &c->bvhAllocations)) != HRPT_OK) return r;
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                v.nodes4 = reinterpret_cast<const GpuNode4*>(dn4); v.node4Count = (uint32_t)n4.size(); maxDepth4 = d4; c->nodes4Capacity = 0;
-            }
-            c->buildInfo.usedBuilder = g.ploc ? HRPT_BVH_BUILDER_GPU_PLOC : HRPT_BVH_BUILDER_GPU_LBVH; c->buildInfo.deviceBuildMs = g.deviceMs; c->buildInfo.mortonBits = g.mortonBits; c->buildInfo.sahCost = g.sahCost;
-            if (g.refitted) c->buildInfo.usedBuilder |= HRPT_BVH_BUILDER_REFITTED;
-        } else {
-            // too deep for the traversal stacks (or a device error): drop the device-side builder and build on the host instead
-            c->gpuBuilder.reset();
-            switch (gerr.reason) {
-            case GpuBuildFailure::NonFinitePosition: return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + gerr.message);
-            case GpuBuildFailure::OutOfMemory: return fail(c, HRPT_ERR_OUT_OF_MEMORY, "acceleration structure: " + gerr.message);
-            case GpuBuildFailure::DoesNotFit: case GpuBuildFailure::DeviceError: case GpuBuildFailure::None: break;      // the host builder takes over
-            }
-        }
-        if (built) {
-            std::vector<HostInstShade> shade; build_instance_shade(s, shade);
-            const HostInstShade* dis;
-            if ((r = upload(c, shade.data(), shade.size(), &dis, &c->bvhAllocations)) != HRPT_OK) return r;
-            v.instShade = reinterpret_cast<const GpuInstShade*>(dis);
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
-    }
-    if (!built) {
-        BuiltBvh bvh;
-        if (!build_scene_bvh(s, bvh, berr)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: " + berr);
-        DeviceAllocations* own = &c->bvhAllocations;
-        const HostNode* dn; const HostTri* dt;
-        if ((r = upload(c, bvh.nodes.data(), bvh.nodes.size(), &dn, own)) != HRPT_OK) return r;
-        if ((r = upload(c, bvh.tris.data(), bvh.tris.size(), &dt, own)) != HRPT_OK) return r;
-        v.nodes = reinterpret_cast<const GpuNode*>(dn); v.nodeCount = (uint32_t)bvh.nodes.size();
-        v.tris = reinterpret_cast<const GpuTri*>(dt); v.triCount = (uint32_t)bvh.tris.size();
-        v.rootLeaf = bvh.rootLeaf;
-        const HostNode4* dn4;
-        if ((r = upload(c, bvh.nodes4.data(), bvh.nodes4.size(), &dn4, own)) != HRPT_OK) return r;
-        v.nodes4 = reinterpret_cast<const GpuNode4*>(dn4); v.node4Count = (uint32_t)bvh.nodes4.size();
-        // The quantised vertex / index / mesh / instance buffers are consumed here: per-triangle attribute records and
-        // per-instance adjugate rows replace the per-hit GetTriangleVertices + UnpackVertex + MakeAdjugateMatrix work.
-        const HostTriAttr* da; const HostTriTangent* dtg; const HostInstShade* dis;
-        if ((r = upload(c, bvh.attrs.data(), bvh.attrs.size(), &da, own)) != HRPT_OK) return r;
-        if ((r = upload(c, bvh.instShade.data(), bvh.instShade.size(), &dis, own)) != HRPT_OK) return r;
-        v.attrs = reinterpret_cast<const GpuTriAttr*>(da); v.instShade = reinterpret_cast<const GpuInstShade*>(dis);
-        v.tangents = nullptr;
-        if (!bvh.tangents.empty()) {
-            if ((r = upload(c, bvh.tangents.data(), bvh.tangents.size(), &dtg, own)) != HRPT_OK) return r;
-            v.tangents = reinterpret_cast<const GpuTriTangent*>(dtg);
-        }
-        HIP_TRY(c, hipStreamSynchronize(c->stream));   // the BuiltBvh staging vectors die at scope exit
-        maxDepth = bvh.maxDepth; maxDepth4 = bvh.maxDepth4;
-        c->buildInfo.usedBuilder = HRPT_BVH_BUILDER_HOST_SAH; c->buildInfo.sahCost = bvh.sahCost;
-    }
+    const bool gpuBuilder = builder == HRPT_BVH_BUILDER_GPU_LBVH || builder == HRPT_BVH_BUILDER_GPU_PLOC;
+    if (!gpuBuilder) c->gpuBuilder.reset();
+    if (gpuBuilder && sceneTris >= 8) HRPT_TRY(build_flat_on_gpu(c, s, builder == HRPT_BVH_BUILDER_GPU_PLOC, refit && !firstBuild, v, depths, built));
+    if (!built) HRPT_TRY(build_flat_on_host(c, s, v, depths));
     if (v.node4Count >= kMaxStructureNodes) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "acceleration structure: more than 2^25 nodes (32-bit node offsets in the traversal kernels)");
-    // the 64-byte quantised form of the 4-wide tree, whichever builder made it (what the wavefront kernels may read when the tree is not in LDS)
-    v.nodesQ = nullptr; bool quantisedNodes = false;
-    if (v.node4Count) {
-        if (c->nodesQCapacity <= v.node4Count) {                   // (<=: record nodesQCapacity - 1 is the accumulator below, never a node)
-            c->nodesQ.reset(); c->nodesQCapacity = 0;
-            const size_t cap = (size_t)v.node4Count + v.node4Count / 8 + 64;
-            if (c->nodesQ.alloc(cap * sizeof(GpuNodeQ)) != hipSuccess) return fail(c, HRPT_ERR_OUT_OF_MEMORY, "acceleration structure: quantised nodes");
-            c->nodesQCapacity = cap;
-        }
-        double* dArea = reinterpret_cast<double*>(c->nodesQ + (c->nodesQCapacity - 1));       // the last (spare) record of the buffer: two doubles
-        HIP_TRY(c, hipMemsetAsync(dArea, 0, 4 * sizeof(double), c->stream));
-        HIP_TRY(c, launch_quantise_nodes(v.nodes4, v.node4Count, c->nodesQ, dArea, c->stream));
-        double area[4] = { 0.0, 0.0, 0.0, 0.0 };
-        HIP_TRY(c, hipMemcpyAsync(area, dArea, sizeof area, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        v.nodesQ = c->nodesQ;
-        // Which nodes the kernels walk when the tree is in global memory. The quantised form saves three of seven 16-byte requests per lane and
-        // step and pays in decode arithmetic and in looser boxes; what the looser LEAF boxes cost is triangle tests (three requests + a
-        // watertight test each). Measured (MI355X, 1080p): Sponza-class scene: wf_extend 6.66 -> 6.18 ms, frame 13.8 -> 13.3 ms; glass scene
-        // (18 k triangles of tessellated glass bodies): shadow-ray triangle tests x 2.4, closest-hit leaf visits + 43 %, frame +2 %.
-        const float inflation = area[0] > 0.0 ? (float)(area[1] / area[0]) : 1.0f;
-        if (getenv("HRPT_BVH_NODE_FORMAT_DEBUG")) fprintf(stderr, "quantised nodes: leaf area ratio %.4f (area-weighted), %.4f (mean over %.0f leaves)\n", inflation, area[3] > 0 ? area[2] / area[3] : 1.0, area[3]);
-        int format = 0;
-        if (const char* e = getenv("HRPT_BVH_NODE_FORMAT")) format = atoi(e);          // 1: fp32 nodes, 2: quantised nodes, else by the leaf-area ratio
-        // (the leaf-area ratio is ~1.01 on BOTH scenes, so it does not tell them apart: on the glass scene it is the paths that bounce inside and between
-        // the finely tessellated glass bodies that visit 40 % more leaves through the rounded boxes. Until that is understood the rule is empirical:
-        // quantised nodes unless some instance is transmissive or BLEND.)
-        bool glassy = false;
-        for (uint32_t i = 0; i < s.instanceCount && !glassy; ++i) {
-            const HrptMaterialConstants& m = s.materials[s.instances[i].m_MaterialIndex];
-            glassy = m.m_TransmissionFactor > 0.0f || m.m_AlphaMode == HRPT_ALPHA_MODE_BLEND;
-        }
-        quantisedNodes = format == 2 || (format != 1 && inflation <= 1.10f && !glassy);
-        c->buildInfo.leafAreaPermille = (uint32_t)(inflation * 1000.0f + 0.5f); c->buildInfo.nodeFormat = quantisedNodes ? 2u : 1u;
-    }
+    bool quantisedNodes = false;
+    HRPT_TRY(quantise_nodes(c, s, v, quantisedNodes));
     c->buildInfo.buildMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->buildInfo.triangleCount = v.triCount; c->buildInfo.nodeCount = v.nodeCount; c->buildInfo.node4Count = v.node4Count;
-    c->buildInfo.maxDepth = maxDepth; c->buildInfo.maxDepth4 = maxDepth4;
+    c->buildInfo.maxDepth = depths.maxDepth; c->buildInfo.maxDepth4 = depths.maxDepth4;
     c->bvhNodes = v.nodeCount; c->bvhTris = v.triCount;
-    c->traits.bvhMaxDepth = maxDepth; c->traits.bvh4MaxDepth = maxDepth4; c->traits.quantisedNodes = quantisedNodes;
+    c->traits.bvhMaxDepth = depths.maxDepth; c->traits.bvh4MaxDepth = depths.maxDepth4; c->traits.quantisedNodes = quantisedNodes;
     return HRPT_OK;
 }
 
@@ -333,6 +357,53 @@ void capi::refresh_traits(HrptContext* c)
     }
     for (const HrptGPULight& l : c->keptLights) if (l.m_Type != HRPT_LIGHT_DIRECTIONAL) t.directionalLightsOnly = false;
     c->traits = t;
+}
+
+// The descriptor table of the scene's textures: every texture's texels go to the device (the scene's allocation list), `table` is left to the caller.
+static int upload_texels(HrptContext* c, const HrptSceneDesc& s, std::vector<GpuTexture>& table)
+{
+    int r;
+    for (uint32_t i = 0; i < s.textureCount; ++i) {
+        const HrptTextureDesc& td = s.textures[i];
+        GpuTexture& g = table[i];
+        memset(&g, 0, sizeof g);
+        g.w = td.width; g.h = td.height; g.format = td.format; g.mipCount = td.mipCount ? td.mipCount : 1u;
+        if (!td.texels) continue;
+        if (td.width == 0 || td.height == 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: zero-sized texture");
+        if (td.format > HRPT_TEXTURE_FORMAT_RGBA32_FLOAT) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: unknown texture format");
+        if (g.mipCount > HRPT_TEXTURE_MAX_MIPS) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: more than HRPT_TEXTURE_MAX_MIPS mip levels");
+        uint64_t texels = 0;
+        for (uint32_t l = 0; l < g.mipCount; ++l) {
+            if (l > 0 && (td.width >> l) == 0 && (td.height >> l) == 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: more mip levels than the texture size allows");
+            g.mipOffset[l] = (uint32_t)texels;
+            texels += (uint64_t)((td.width >> l) ? (td.width >> l) : 1u) * ((td.height >> l) ? (td.height >> l) : 1u);
+        }
+        if (texels > 0xFFFFFFFFull) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: texture too large");
+        const size_t bpt = td.format <= HRPT_TEXTURE_FORMAT_RGBA8_SRGB ? 4 : (td.format == HRPT_TEXTURE_FORMAT_RGBA16_FLOAT ? 8 : 16);
+        const uint8_t* d;
+        if ((r = upload(c, static_cast<const uint8_t*>(td.texels), (size_t)texels * bpt, &d)) != HRPT_OK) return r;
+        g.texels = d;
+    }
+    return HRPT_OK;
+}
+
+// Bruneton LUTs: float32 file layout -> RGBA16F (src/CommonResources.cpp:534-558)
+static void convert_atmosphere_tables(const HrptSceneDesc& s, std::vector<uint16_t>& hT, std::vector<uint16_t>& hS)
+{
+    const size_t nT = hT.size(), nS = hS.size();
+    for (size_t i = 0; i < nT; ++i) hT[i] = float_to_half(s.brunetonTransmittance[i]);
+    {   // 4 M conversions: 9 ms of every upload on one thread
+        const float* src = s.brunetonScattering; uint16_t* dst = hS.data();
+        const unsigned threads = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
+        const size_t chunk = (nS + threads - 1) / threads;
+        auto part = [src, dst, nS, chunk](size_t t) { for (size_t i = t * chunk, e = std::min(nS, i + chunk); i < e; ++i) dst[i] = float_to_half(src[i]); };
+        std::vector<std::thread> pool;
+        size_t started = 1;
+        try { for (; started < threads; ++started) pool.emplace_back(part, started); } catch (const std::system_error&) {}
+        part(0);
+        for (std::thread& th : pool) th.join();
+        for (size_t t = started; t < threads; ++t) part(t);       // (threads that could not be started)
+    }
 }
 
 int hrpt_upload_scene(HrptContext* c, const HrptSceneDesc* s)
@@ -357,49 +428,15 @@ try {
     if ((r = upload(c, s->materials, s->materialCount, &v.materials)) != HRPT_OK) return r;
     if ((r = upload(c, s->lights, s->lightCount, &v.lights)) != HRPT_OK) return r;
     v.lightCount = s->lightCount; c->lightCapacity = s->lightCount;
-
     std::vector<GpuTexture> table(s->textureCount);
-    for (uint32_t i = 0; i < s->textureCount; ++i) {
-        const HrptTextureDesc& td = s->textures[i];
-        GpuTexture& g = table[i];
-        memset(&g, 0, sizeof g);
-        g.w = td.width; g.h = td.height; g.format = td.format; g.mipCount = td.mipCount ? td.mipCount : 1u;
-        if (!td.texels) continue;
-        if (td.width == 0 || td.height == 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: zero-sized texture");
-        if (td.format > HRPT_TEXTURE_FORMAT_RGBA32_FLOAT) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: unknown texture format");
-        if (g.mipCount > HRPT_TEXTURE_MAX_MIPS) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: more than HRPT_TEXTURE_MAX_MIPS mip levels");
-        uint64_t texels = 0;
-        for (uint32_t l = 0; l < g.mipCount; ++l) {
-            if (l > 0 && (td.width >> l) == 0 && (td.height >> l) == 0) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: more mip levels than the texture size allows");
-            g.mipOffset[l] = (uint32_t)texels;
-            texels += (uint64_t)((td.width >> l) ? (td.width >> l) : 1u) * ((td.height >> l) ? (td.height >> l) : 1u);
-        }
-        if (texels > 0xFFFFFFFFull) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upload_scene: texture too large");
-        const size_t bpt = td.format <= HRPT_TEXTURE_FORMAT_RGBA8_SRGB ? 4 : (td.format == HRPT_TEXTURE_FORMAT_RGBA16_FLOAT ? 8 : 16);
-        const uint8_t* d;
-        if ((r = upload(c, static_cast<const uint8_t*>(td.texels), (size_t)texels * bpt, &d)) != HRPT_OK) return r;
-        g.texels = d;
-    }
+    if ((r = upload_texels(c, *s, table)) != HRPT_OK) return r;
     if ((r = upload(c, table.data(), table.size(), &v.textures)) != HRPT_OK) return r;
     v.textureCount = s->textureCount;
     lap("materials, textures");
 
-    // Bruneton LUTs: float32 file layout -> RGBA16F (src/CommonResources.cpp:534-558)
     const size_t nT = 256u * 64u * 4u, nS = 256u * 128u * 32u * 4u;
     std::vector<uint16_t> hT(nT), hS(nS);
-    for (size_t i = 0; i < nT; ++i) hT[i] = float_to_half(s->brunetonTransmittance[i]);
-    {   // 4 M conversions: 9 ms of every upload on one thread
-        const float* src = s->brunetonScattering; uint16_t* dst = hS.data();
-        const unsigned threads = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-        const size_t chunk = (nS + threads - 1) / threads;
-        auto part = [src, dst, nS, chunk](size_t t) { for (size_t i = t * chunk, e = std::min(nS, i + chunk); i < e; ++i) dst[i] = float_to_half(src[i]); };
-        std::vector<std::thread> pool;
-        size_t started = 1;
-        try { for (; started < threads; ++started) pool.emplace_back(part, started); } catch (const std::system_error&) {}
-        part(0);
-        for (std::thread& th : pool) th.join();
-        for (size_t t = started; t < threads; ++t) part(t);       // (threads that could not be started)
-    }
+    convert_atmosphere_tables(*s, hT, hS);
     if ((r = upload(c, hT.data(), nT, &v.lutTransmittance)) != HRPT_OK) return r;
     if ((r = upload(c, hS.data(), nS, &v.lutScattering)) != HRPT_OK) return r;
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // host staging vectors die at scope exit

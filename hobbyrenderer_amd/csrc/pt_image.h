@@ -42,7 +42,7 @@ HRT_FN float length3(T3 a) { return hrt_sqrt(dot3(a, a)); }
 HRT_FN float length2(T2 a) { return hrt_sqrt(a.x * a.x + a.y * a.y); }
 HRT_FN T3 normalize(T3 v) { const float len = length3(v); return t3(v.x / len, v.y / len, v.z / len); }
 HRT_FN T3 reflect(T3 i, T3 n) { const float k = 2.0f * dot3(n, i); return t3(i.x - k * n.x, i.y - k * n.y, i.z - k * n.z); }
-HRT_FN float lerp(float a, float b, float t) { return a + t * (b - a); }                      // pt_device.h:66
+HRT_FN float lerp(float a, float b, float t) { return a + t * (b - a); }                      // pt_vec.h lerp
 HRT_FN float ln(float x) { return hrt_log2(x) * kLn2; }
 
 // The members of an HrptPlanarViewConstants that recon and the stages read, gathered once per call.

@@ -231,7 +231,7 @@ hipError_t launch_f16_table(float* out, hipStream_t stream)
 }
 
 // Self-test of texture sampling (hrpt_selftest_sample_textures): one thread per probe calls sample_texture, pbr_textures_batched and
-// sample_texture_grad of pt_device.h as the shade and any-hit code does, over the scene's own texture and material tables.
+// sample_texture_grad of pt_surface.h / pt_texture.h as the shade and any-hit code does, over the scene's own texture and material tables.
 __device__ __forceinline__ void store4(float* dst, const f4& v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w; }
 __global__ void pt_sample_textures_kernel(SceneView s, uint32_t materialCount, const HrptTextureProbe* __restrict__ probes,
                                           HrptTextureProbeResult* __restrict__ results, uint32_t count)
@@ -343,7 +343,7 @@ __global__ void pt_bvh_check_kernel(SceneView s, unsigned long long* violations)
     }
     if (bad) atomicAdd(violations, (unsigned long long)bad);
 }
-// GpuNode4 -> GpuNodeQ (see pt_device.h), one thread per node; run after every build / rebuild of the flat structure, whichever builder made it.
+// GpuNode4 -> GpuNodeQ (see pt_scene_records.h), one thread per node; run after every build / rebuild of the flat structure, whichever builder made it.
 __global__ void pt_quantise_nodes_kernel(const GpuNode4* __restrict__ in, uint32_t count, GpuNodeQ* __restrict__ out, double* __restrict__ leafArea)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

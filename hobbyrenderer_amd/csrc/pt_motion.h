@@ -6,25 +6,9 @@
 #pragma once
 
 #include "pt_gbuffer.h"
+#include "pt_motion_records.h"      // MotionInst, MotionArgs
 
 namespace hrt {
-
-// Per-instance record of the motion tables (pt_capi.cpp builds them at the first motion call): m_PrevWorld rows 0..3, xyz each (the layout of
-// GpuInstance::world), and where the mesh's LOD-0 indices start.
-struct MotionInst { float prevWorld[12]; uint32_t firstIndex; uint32_t pad[3]; };
-static_assert(sizeof(MotionInst) == 64, "four 16-byte rows");
-
-// What a motion kernel gets next to the scene: the tables, last frame's view (the three members of HrptPlanarViewConstants that
-// ComputeMotionVectors reads) and the plane.
-struct MotionArgs {
-    const MotionInst* inst;         // per instance
-    const float* positions;         // object space, 3 floats per vertex (HrptVertexQuantized::m_Pos)
-    const float* prevPositions;     // the same one frame ago (hrpt_update_vertices); == positions where nothing deformed
-    const uint32_t* indices;        // the scene's index buffer
-    float4* plane;                  // W x H
-    float prevWorldToClip[16];      // prevView->m_MatWorldToClip
-    float prevScale[2], prevBias[2];   // prevView->m_ClipToWindowScale / m_ClipToWindowBias
-};
 
 // mul(float4(p, 1), M).xyz over rows 0..3 of a 4 x 3 matrix, left to right (bvh_build.cpp transform_point, tl_world_triangle)
 HRT_DEV f3 motion_transform_point(f3 p, const float4 w0, const float4 w1, const float4 w2)

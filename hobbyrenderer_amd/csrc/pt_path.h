@@ -494,7 +494,7 @@ enum SurfaceOutcome { SURFACE_TRANSMITTED = 0, SURFACE_SCATTER = 1 };
 //   TEX     some material samples a texture          (false: every m_TextureFlags is 0 -> sampling code compiled out)
 //   TRANS   some material is transmissive or BLEND   (false: the transmission branch :149-255 is compiled out)
 //   DIRONLY every light is directional               (true: point / spot code compiled out)
-// TABLES: where the triangle, instance and material records are read from (pt_device.h GlobalShadeTables / LdsShadeTables)
+// TABLES: where the triangle, instance and material records are read from (pt_shade_tables.h GlobalShadeTables / LdsShadeTables)
 template <bool TEX, bool TRANS, bool DIRONLY, class TABLES, class EMIT>
 HRT_DEV SurfaceOutcome shade_surface_a(const SceneView& s, const TABLES& tables, const HrptPathTracerConstants& cb, PathState& ps, const Hit& hit,
                                        SurfaceCarry& carry, EMIT&& emit)

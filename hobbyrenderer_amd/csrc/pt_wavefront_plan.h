@@ -79,7 +79,7 @@ constexpr size_t kShadeRingBytes = (size_t)(kBlock / 64) * kShadeRing * kShadeRi
 constexpr uint32_t kShadeBlocksPerCu = 4;
 constexpr size_t kCuLdsBytes = 160 * 1024, kShadeLdsMargin = 1024;
 constexpr size_t kShadeLdsPerBlock = kCuLdsBytes / kShadeBlocksPerCu - kShadeLdsMargin;     // dynamic LDS a wf_shade block may ask for
-// Records of the three tables the shading path gathers from (pt_device.h GpuTriAttr, GpuInstShade; hobbyrt_pt.h HrptMaterialConstants;
+// Records of the three tables the shading path gathers from (pt_scene_records.h GpuTriAttr, GpuInstShade; hobbyrt_pt.h HrptMaterialConstants;
 // pt_wavefront.hip asserts the sizes). wf_shade_lt copies them whole, in their global layout, behind the ring.
 constexpr size_t kTriAttrBytes = 80, kInstShadeBytes = 48, kMaterialBytes = 180;
 constexpr size_t shade_table_bytes(uint32_t triCount, uint32_t instanceCount, uint32_t materialCount)
@@ -108,7 +108,7 @@ enum : int { kShadowOpaque = 0, kShadowBuffered = 1, kShadowResolve = 2, kShadow
 // kExtendLdsStack / kShadowLdsStack entries in LDS and the rest in the overflow columns (LdsStack)
 struct Variant { bool lds = false; int depth = 0, width = 0; size_t ldsBytes = 0; bool twoLevel = false; bool twoLevelCandidates = false; bool quantised = false; };
 
-// Entries the 4-wide traversal can hold at once: inner_step (pt_device.h) pushes up to three siblings at every inner node it visits, and the path to
+// Entries the 4-wide traversal can hold at once: inner_step (pt_traverse.h) pushes up to three siblings at every inner node it visits, and the path to
 // the deepest inner node (depth4, the root being 0) visits depth4 + 1 of them. (3 * depth4 + 2 stood here before: one entry short on a ray that
 // finds all four children of every node on the deepest path, where the LDS stack wraps and the overflow column is written one row past its end.)
 inline uint32_t stack_entries4(uint32_t depth4) { return 3 * depth4 + 3; }

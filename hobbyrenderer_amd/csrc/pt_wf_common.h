@@ -150,7 +150,7 @@ template <> struct GlobalBvhOf<2> { using type = GlobalBvh; static HRT_DEV Globa
 constexpr int kTwoLevelTree = 44;     // GlobalBvhOf key of the two-level structure (4-wide nodes)
 template <> struct GlobalBvhOf<kTwoLevelTree> { using type = GlobalBvhTl; static HRT_DEV GlobalBvhTl make(const SceneView& s) { GlobalBvhTl g; g.nodes = s.nodes4; g.tris = s.tris; g.instances = s.instances; return g; } };
 template <> struct GlobalBvhOf<4> { using type = GlobalBvh4; static HRT_DEV GlobalBvh4 make(const SceneView& s) { GlobalBvh4 g; g.nodes = s.nodes4; g.tris = s.tris; return g; } };
-constexpr int kQuantisedTree = 5;     // template width code of the 4-wide tree through its 64-byte quantised nodes (global memory only; pt_device.h GpuNodeQ)
+constexpr int kQuantisedTree = 5;     // template width code of the 4-wide tree through its 64-byte quantised nodes (global memory only; pt_scene_records.h GpuNodeQ)
 template <> struct GlobalBvhOf<kQuantisedTree> { using type = GlobalBvhQ; static HRT_DEV GlobalBvhQ make(const SceneView& s) { GlobalBvhQ g; g.nodes = s.nodesQ; g.tris = s.tris; return g; } };
 
 // Carves dynamic LDS: [stack: min(DEPTH, 32)*kBlock ints][bvh copy]; copies the BVH when LDS_BVH.

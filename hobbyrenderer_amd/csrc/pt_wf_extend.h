@@ -27,7 +27,7 @@ constexpr uint32_t kNoPathRecord = 0xFFFFFFFEu;     // hit-record code of a slot
 // ANYHIT: the same persistent loop over the shadow-ray queue (sqO / sqD / sqId, sqCnt rays per segment): the first hit on an opaque
 // triangle ends the ray (kVisBlocked); otherwise the ray is clear or, if it crossed non-opaque triangles, left to wf_shadow's candidate
 // pass (kVisCandidates). Shadow rays get the lane refill closest-hit rays have: 3.8 -> 8 Grays/s on the glass config.
-// TL: the two-level structure of instanced scenes (pt_device.h "two-level traversal"): tree in global memory, closest hits only, every
+// TL: the two-level structure of instanced scenes (pt_traverse.h "two-level traversal"): tree in global memory, closest hits only, every
 // instance opaque; the hit's instance goes to its own stream (hitInst) next to the hit record.
 // PRIMARY: bounce 0 of a batch without a raygen pass (WfArgs::primary): the refill derives the ray from the sample index. A separate instantiation:
 // as a run-time branch the extra live state cost the kernel 6 VGPRs and 3 % on EVERY bounce.

@@ -250,7 +250,7 @@ class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B
                 ("instanceNodeCount", C.c_uint32), ("distinctMeshes", C.c_uint32), ("leafAreaPermille", C.c_uint32), ("nodeFormat", C.c_uint32)]
 
 
-# Records of the acceleration structure as the kernels read them (csrc/pt_device.h), for hrpt_selftest_read_bvh / hrpt_selftest_host_build.
+# Records of the acceleration structure as the kernels read them (csrc/pt_scene_records.h), for hrpt_selftest_read_bvh / hrpt_selftest_host_build.
 i32 = np.int32
 GpuNode = np.dtype([("lmin", f32, 3), ("left", i32), ("lmax", f32, 3), ("right", i32), ("rmin", f32, 3), ("pad0", u32), ("rmax", f32, 3), ("pad1", u32)])
 GpuNode4 = np.dtype([("minx", f32, 4), ("maxx", f32, 4), ("miny", f32, 4), ("maxy", f32, 4), ("minz", f32, 4), ("maxz", f32, 4), ("child", i32, 4), ("pad", u32, 4)])

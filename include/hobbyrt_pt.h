@@ -907,7 +907,7 @@ int  hrpt_reset_stats(HrptContext* ctx);
  * not contain the boxes / triangle vertices below them. 0 for a sound tree; anything else means missed hits. Synchronises. */
 int  hrpt_selftest_bvh(HrptContext* ctx, uint64_t* violations);
 /* Read-back of an acceleration structure for host-side validation (tests/bvh_reference.py): the records exactly as the kernels read them
- * (layouts: hobbyrenderer_amd/csrc/pt_device.h GpuNode 64 B, GpuNode4 128 B, GpuNodeQ 64 B, GpuTri 48 B, GpuTriAttr 80 B, GpuTriTangent 48 B,
+ * (layouts: hobbyrenderer_amd/csrc/pt_scene_records.h GpuNode 64 B, GpuNode4 128 B, GpuNodeQ 64 B, GpuTri 48 B, GpuTriAttr 80 B, GpuTriTangent 48 B,
  * GpuInstance 128 B). Size query, then fill: every call writes the counts; an array pointer that is not NULL receives that array and must
  * have room for the count the query reported (nodes: nodeCount, nodes4 / nodesQ: node4Count, triangles / attributes / tangents:
  * triangleCount, instances: instanceCount). Flat structure: the 2-wide tree, its 4-wide collapse, the quantised nodes (hasNodesQ).

@@ -369,7 +369,7 @@ static Hit closest_any(const OrContext* c, const Ray* r, int haveLower, float lt
 {
     Hit best; memset(&best, 0, sizeof best);
     if (c->triCount == 0) return best;
-    /* a ray with a NaN or infinite component has no hits (pt_device.h all_finite: the kernels do not walk with it) */
+    /* a ray with a NaN or infinite component has no hits (pt_traverse.h all_finite: the kernels do not walk with it) */
     if (!((r->d.x - r->d.x) == 0.0f && (r->d.y - r->d.y) == 0.0f && (r->d.z - r->d.z) == 0.0f &&
           (r->o.x - r->o.x) == 0.0f && (r->o.y - r->o.y) == 0.0f && (r->o.z - r->o.z) == 0.0f)) return best;
     RayShear s = make_shear(r->d);
@@ -531,7 +531,7 @@ static v4 sample_texture(const OrContext* c, uint32_t texIndex, uint32_t sampler
     return sample_texture_level(&c->textures[texIndex], samplerIndex, uv, 0u);
 }
 /* tex.SampleGrad (Bindless.hlsli:127-132). Level of detail: the isotropic form of the D3D11.3 functional spec, fixed by the numeric
- * contract (see pt_device.h sample_texture_grad): lod = log2(max(|ddx * size|, |ddy * size|)) clamped to the chain; linear and
+ * contract (see pt_texture.h sample_texture_grad): lod = log2(max(|ddx * size|, |ddy * size|)) clamped to the chain; linear and
  * anisotropic samplers blend the two nearest levels, point samplers take the nearest. */
 static v4 sample_texture_grad(const OrContext* c, uint32_t texIndex, uint32_t samplerIndex, v2 uv, v2 ddx, v2 ddy)
 {

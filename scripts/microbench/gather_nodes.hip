@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void shade_tables(const uint4* __restrict__ ta
 {
     __shared__ uint4 copy[kShadeRecords * kShadeRecordRows];
     if (LDS) { for (uint32_t i = threadIdx.x; i < kShadeRecords * kShadeRecordRows; i += 256u) copy[i] = table[i]; __syncthreads(); }
-    typedef __attribute__((address_space(3))) const char* LdsPtr;        // 32-bit LDS addresses, as LdsShadeTables (pt_device.h)
+    typedef __attribute__((address_space(3))) const char* LdsPtr;        // 32-bit LDS addresses, as LdsShadeTables (pt_shade_tables.h)
     const uint32_t copyAddress = (uint32_t)(uintptr_t)(LdsPtr) reinterpret_cast<const char*>(copy);
     const uint32_t group = (blockIdx.x * 256u + threadIdx.x) / run;
     uint32_t idx = group * 2654435761u, acc = 0;

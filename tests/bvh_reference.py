@@ -1,7 +1,7 @@
 """Host-side validator of a built acceleration structure (hrpt_selftest_read_bvh / hrpt_selftest_host_build), in plain numpy.
 
 It shares no code with the product: record layouts come from hobbyrenderer_amd/structs.py, the rules from the comments of
-csrc/pt_device.h and csrc/bvh_build.h. Everything is level-synchronous and vectorised (one numpy pass per tree level), so a tree over a
+csrc/pt_scene_records.h and csrc/bvh_build.h. Everything is level-synchronous and vectorised (one numpy pass per tree level), so a tree over a
 million triangles is checked in seconds. validate() returns a Report of NAMED violations with counts and the first offender, e.g.
 "leaf_pad: 3 of 4-wide leaf slots, first node 812 slot 2".
 
@@ -296,7 +296,7 @@ def check_quantised(rep, nodes4, nodesq, depth):
 
 
 def quantise_reference(nodes4):
-    """A valid GpuNodeQ array for `nodes4` by the rule of pt_device.h (origin = min corner of the used child boxes, one step per axis, planes
+    """A valid GpuNodeQ array for `nodes4` by the rule of pt_scene_records.h (origin = min corner of the used child boxes, one step per axis, planes
     rounded outward under the separately rounded decode): lets the CPU tests exercise check_quantised on host-built trees."""
     child, bmin, bmax = tree_arrays4(nodes4)
     used = child != EMPTY
@@ -329,7 +329,7 @@ def fma32(a, b, c):
 
 
 def folded_decode_intervals(nodes4, nodesq, origin, direction, tmin=0.0, tlim=1e10):
-    """What inner_step (pt_device.h, the IsQuantised branch) computes for ONE ray at every slot of every node, restated operation by operation in
+    """What inner_step (pt_traverse.h, the IsQuantised branch) computes for ONE ray at every slot of every node, restated operation by operation in
     binary32: inv = 1 / d capped at +-1e20 (traversal_rcp; the hardware reciprocal may differ from the correctly rounded one used here by an ulp:
     whichever value it is, it is the `inv` of both sides of the comparison below), noi = -(o_ray * inv), ax = s * inv, bx = fma(o_node, inv, noi),
     plane distance = fma(float(q), ax, bx), near / far words by the sign of inv, lo = max(near distances, tmin),

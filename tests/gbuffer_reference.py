@@ -1,6 +1,6 @@
 """NumPy restatement of the first-hit G-buffer (hrpt_render_gbuffer) -- TEST INFRASTRUCTURE.
 
-Shares no code with hobbyrenderer_amd/csrc/pt_device.h: the primary rays are built here in binary32 step by step as init_path does
+Shares no code with hobbyrenderer_amd/csrc/pt_device.h or the headers it collects: the primary rays are built here in binary32 step by step as init_path does
 (PathTracer.hlsl:61-72), the hits come from the oracle's TraceRayStandard (Oracle.trace_standard, with the seeded RNG), vertices through
 or_unpack_vertex and texels through Oracle.sample_texture; interpolation, the normal transform by the adjugate rows, TransformNormalWithTBN,
 the flips, viewDepth and the plane packing are NumPy float32 with one rounding per operation, in the order DESIGN.md section 2 fixes

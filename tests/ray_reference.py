@@ -10,7 +10,7 @@ What is computed for a pair (ray o, d, tmin, tmax; triangle p0, p1, p2), with A 
     n = (p1 - p0) x (p2 - p0),   t = (A . n) / (d . n)                    the plane equation
     u = V3 / (U3 + V3 + W3),     v = W3 / (U3 + V3 + W3)                  the barycentrics of p1 and p2 (DXR convention)
 
-The fp32 test under judgement (tri_test / make_shear in csrc/pt_device.h, restated in the oracle) picks kz = the axis of the largest
+The fp32 test under judgement (tri_test / make_shear in csrc/pt_traverse.h, restated in the oracle) picks kz = the axis of the largest
 |d| component, kx, ky the other two, and works on sheared coordinates: with S = (d_kx / d_kz, d_ky / d_kz, 1 / d_kz) and a = A permuted,
 
     Ax = a_x - Sx a_z,  Ay = a_y - Sy a_z,  Az = Sz a_z      (B, C alike)

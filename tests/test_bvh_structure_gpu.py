@@ -340,6 +340,28 @@ def test_flattened_instance_comes_back_flat(luts):
         ctx.close()
 
 
+def test_two_level_structure_with_tangents(luts):
+    """A material that samples a normal map: the per-mesh tangent records are uploaded with the two-level structure. Eight instances of one
+    cube (12 triangles: more than two leaves, so the mesh has a tree of its own), the host's instance tree."""
+    b = scenes.SceneBuilder()
+    cube = b.add_mesh(*scenes.generate_default_cube())
+    normal_map = b.add_texture(np.full((4, 4, 4), (128, 128, 255, 255), np.uint8))
+    mat = b.add_material(m_TextureFlags=S.TEXFLAG_NORMAL, m_NormalTextureIndex=normal_map)
+    for i in range(8):
+        b.add_instance(cube, mat, scenes._mat((1.0, 1.0 + 0.1 * i, 1.0), None, (2.5 * (i % 4), 0.0, 2.5 * (i // 4))))
+    sc = b.finalize(luts)
+    ctx = native.PathTracerContext(0)
+    try:
+        ctx.set_bvh_builder(S.BVH_BUILDER_HOST_SAH)
+        ctx.set_acceleration_structure(S.ACCEL_TWO_LEVEL)
+        ctx.upload_scene(sc)
+        d, _ = check_two_level_context(ctx, sc, False)
+        assert d["hasTangents"] and d["tangents"] is not None and len(d["tangents"]) == d["triangleCount"] == 12
+        assert d["tangents"].tobytes() == native.host_build_bvh(sc, S.ACCEL_TWO_LEVEL)["tangents"].tobytes()
+    finally:
+        ctx.close()
+
+
 # ------------------------------------------------------------------------------------------------ every triangle can be found
 def oracle_hits(o, rays):
     out = np.zeros(len(rays), S.RayHit)

@@ -329,7 +329,7 @@ def test_forced_bvh_width(luts, width, monkeypatch):
 
 @pytest.mark.parametrize("fmt", [1, 2], ids=["fp32_nodes", "quantised_nodes"])
 def test_forced_node_format(luts, fmt, monkeypatch):
-    """Trees in global memory are walked through the 128-byte fp32 nodes or through their 64-byte quantised form (pt_device.h GpuNodeQ; chosen
+    """Trees in global memory are walked through the 128-byte fp32 nodes or through their 64-byte quantised form (pt_scene_records.h GpuNodeQ; chosen
     per scene by the leaf-area ratio, HRPT_BVH_NODE_FORMAT forces, read at every build). The boxes only cull, so both formats are bit-exact
     against the oracle: closest-hit and shadow kernels of both shadow schedules, stand-alone ray queries, and after a rebuild; the device
     self-test confirms that every decoded box contains the fp32 box it was rounded from."""

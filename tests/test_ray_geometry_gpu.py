@@ -217,7 +217,7 @@ def test_interval_ends_are_exact(luts):
 @pytest.mark.parametrize("size", list(RC.SOUP_SIZES))
 def test_non_finite_and_zero_rays_miss(luts, size):
     """NaN or +-inf in origin or direction, direction (0, 0, 0): hit == 0 and visibility 1.0, among ordinary rays of the same launch. A ray with a
-    non-finite component is not walked at all (pt_device.h all_finite: with 1 / inf == 0 the far-away box of an unused node slot would pass the
+    non-finite component is not walked at all (pt_traverse.h all_finite: with 1 / inf == 0 the far-away box of an unused node slot would pass the
     slab test, and its child reference is no node -- this test hung over the tree in global memory before the kernels checked). A zero
     direction is walked: traversal_rcp caps 1 / 0 at 1e20, unused slots are 1e50 away, and the walk only follows child references of an
     acyclic tree with stacks sized for a ray that finds every child of every node."""

@@ -1,5 +1,5 @@
 """Texture sampling of the device code pinned off the render path (GPU part): hrpt_selftest_sample_textures runs sample_texture,
-pbr_textures_batched and sample_texture_grad of csrc/pt_device.h as they are, one thread per probe, over an uploaded scene's own texture
+pbr_textures_batched and sample_texture_grad of csrc/pt_surface.h and csrc/pt_texture.h as they are, one thread per probe, over an uploaded scene's own texture
 and material tables (so the upload's level offsets, sizes and formats are under test too). The probes, the float64 reference and the
 tolerances are those of tests/test_texture_sampling.py / tests/texture_reference.py:
 

@@ -1,4 +1,4 @@
-"""Texture sampling as DESIGN.md section 2 and the contract comments of csrc/pt_device.h (sample_texture_level / sample_texture_grad)
+"""Texture sampling as DESIGN.md section 2 and the contract comments of csrc/pt_texture.h (sample_texture_level / sample_texture_grad)
 state it, in plain numpy: an independent statement of "bilinear / trilinear filtering of these texels", written from the text and not from
 the C of either the device code or the oracle.
 
