@@ -64,6 +64,7 @@ try {
     if (const char* e = getenv("HRPT_WF_SHADE_LDS_TABLES")) c->wf.knobs.noShadeLdsTables = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_NODE_LOOP_MIN")) c->wf.knobs.nodeLoopMin = (uint32_t)atoi(e);
     if (const char* e = getenv("HRPT_BLOOM_FUSED_TAIL")) { const int v = atoi(e); c->bloomTailTexels = v == 1 ? 8192u : (v > 0 ? (uint32_t)v : 0u); }
+    if (const char* e = getenv("HRPT_UPSCALE_STAGED")) c->upscaleStaged = atoi(e) != 0;
     *out = c;
     return HRPT_OK;
 } catch (...) { return caught(nullptr, "hrpt_create"); }
@@ -111,6 +112,8 @@ try {
         if (image) HRPT_TRY(realloc_image(c, image, bytes));
     for (DeviceBuffer<float4>& image : c->perSize.dDenoiseScratch) image.reset();        // allocated again by the call that needs it
     c->perSize.dModulation.reset();                                             // written again by the next hrpt_demodulate
+    for (DeviceBuffer<float4>& image : c->perSize.dUpscaleHistory) image.reset();        // allocated again, without history, by the next hrpt_upscale
+    c->perSize.dUpscaled.reset(); c->upscaleValid = false; c->upscaleCur = 0; c->upscaleWidth = c->upscaleHeight = 0;
     c->width = width; c->height = height;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_resize"); }

@@ -62,6 +62,9 @@ struct PerSizeImages {
     DeviceBuffer<float4> dTemporal[2];               // temporal accumulation (hrpt_temporal_accumulate): ping-pong history pair, allocated by the first call
     DeviceBuffer<float4> dDenoiseScratch[2];         // the scratch pair of HRPT_DENOISE_OUTPUT_ONLY
     DeviceBuffer<float4> dModulation;                // demodulate / compose: the stored factor, allocated by the first hrpt_demodulate, dropped by hrpt_resize
+    // temporal upscaling (hrpt_upscale): ping-pong history pair and the colour image, all of upscaleWidth x upscaleHeight (the DISPLAY size of
+    // the last call, not the context's); allocated by the first call, re-allocated when the display size changes, dropped by hrpt_resize
+    DeviceBuffer<float4> dUpscaleHistory[2], dUpscaled;
 };
 
 // Buffers that live as long as the context.
@@ -96,8 +99,10 @@ struct Context {
     uint32_t width = 0, height = 0;
     PerSizeImages perSize;
     int temporalCur = 0; bool temporalValid = false;   // [temporalCur] is the history image the last hrpt_temporal_accumulate wrote
+    uint32_t upscaleWidth = 0, upscaleHeight = 0; int upscaleCur = 0; bool upscaleValid = false;   // [upscaleCur] is the history the last hrpt_upscale wrote
     PerContextBuffers perContext;
     uint32_t bloomTailTexels = 0;            // HRPT_BLOOM_FUSED_TAIL: levels of at most this many texels run in one workgroup's LDS (0 = one kernel per pass, the measured-faster default)
+    bool upscaleStaged = false;              // HRPT_UPSCALE_STAGED: the upscale kernel serves its current-frame taps from an LDS-staged window (false = global gathers, the measured-faster default)
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
     WavefrontState wf;

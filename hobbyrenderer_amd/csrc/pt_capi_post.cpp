@@ -1,5 +1,5 @@
 // pt_capi_post.cpp -- what works on finished images: hrpt_post_process and the exposure, then the screen-space stages (bloom, temporal
-// accumulation, denoise, demodulate / compose) with their _host, _device and probe entry points.
+// accumulation, temporal upscaling, denoise, demodulate / compose) with their _host, _device and probe entry points.
 #include <cmath>
 
 #include "pt_capi_internal.h"
@@ -7,24 +7,44 @@
 using namespace hrt;
 using namespace hrt::capi;
 
+// The context's histogram and exposure (initially 1), allocated by the first post pass.
+static int post_buffers(HrptContext* c)
+{
+    if (c->perContext.dExposure) return HRPT_OK;
+    HIP_TRY(c, c->perContext.dExposure.alloc(16));
+    HIP_TRY(c, c->perContext.dHistogram.alloc(256 * sizeof(uint32_t)));
+    const float one[4] = { 1.0f, 0.0f, 0.0f, 0.0f };
+    HIP_TRY(c, hipMemcpy(c->perContext.dExposure, one, 16, hipMemcpyHostToDevice));
+    return HRPT_OK;
+}
+
+int hrpt_post_process_device(HrptContext* c, const float* hdrDevice, float* displayDevice, uint64_t pixelCount, const HrptPostParams* p, void* stream)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process_device: null params");
+    if (!hdrDevice || !displayDevice) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process_device: null image");
+    if (displayDevice == hdrDevice) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process_device: displayDevice must differ from hdrDevice");
+    if (pixelCount == 0 || pixelCount > 0xffffffffull) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process_device: pixelCount must be 1..2^32-1");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HRPT_TRY(post_buffers(c));
+    HIP_TRY(c, launch_post_chain(reinterpret_cast<const float4*>(hdrDevice), reinterpret_cast<float4*>(displayDevice), (uint32_t)pixelCount, *p,
+                                 c->perContext.dHistogram, c->perContext.dExposure, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_post_process_device"); }
+
 int hrpt_post_process(HrptContext* c, const HrptPostParams* p)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process: null params");
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process: hrpt_resize not called");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->perContext.dExposure) {
-        HIP_TRY(c, c->perContext.dExposure.alloc(16));
-        HIP_TRY(c, c->perContext.dHistogram.alloc(256 * sizeof(uint32_t)));
-        const float one[4] = { 1.0f, 0.0f, 0.0f, 0.0f };
-        HIP_TRY(c, hipMemcpy(c->perContext.dExposure, one, 16, hipMemcpyHostToDevice));
-    }
+    HRPT_TRY(post_buffers(c));
     if (!c->perSize.dDisplay) HIP_TRY(c, c->perSize.dDisplay.alloc((size_t)c->width * c->height * sizeof(float4)));
     HIP_TRY(c, launch_post_chain(c->perSize.dOutput, c->perSize.dDisplay, c->width * c->height, *p, c->perContext.dHistogram, c->perContext.dExposure, c->stream));
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_post_process"); }
 
-// ---- screen-space stages: bloom, temporal accumulation, denoise, demodulate / compose ----
+// ---- screen-space stages: bloom, temporal accumulation, temporal upscaling, denoise, demodulate / compose ----
 // What the _host, _device and context entry points of a stage with a view check alike, in this order, after their null checks and, for
 // caller-owned images, the image checks: the size, then the view against it. The stage's parameter rule follows.
 static bool view_matches(const HrptPlanarViewConstants& view, uint32_t width, uint32_t height)
@@ -168,6 +188,113 @@ try {
     *devicePtr = c->perSize.dTemporal[0] ? c->perSize.dTemporal[c->temporalCur] : nullptr;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_get_temporal_history_device"); }
+
+// ---- temporal upscaling (pt_upscale.h / pt_upscale.hip) ----
+// Sizes, view and parameters: all a context call has left to check once its arguments are not null (its images are the context's own).
+static int upscale_args_check(HrptContext* c, const std::string& w, uint32_t width, uint32_t height, uint32_t displayWidth, uint32_t displayHeight,
+                              const HrptPlanarViewConstants& view, const HrptUpscaleParams& p)
+{
+    if (!size_ok(width, height) || !size_ok(displayWidth, displayHeight)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": size must be 1..65535");
+    if (!upscale_ratio_ok(width, height, displayWidth, displayHeight))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": the display size must lie between the render size and four times it, per axis");
+    if (!view_matches(view, width, height)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": view->m_ViewportSize does not match the image size");
+    if (!upscale_params_valid(p))
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": jitter must be finite and in [-0.5, 0.5], kernel finite and in (0, 16], maxHistory finite and >= 0, flags HRPT_UPSCALE_* only, reserved 0");
+    return HRPT_OK;
+}
+// Caller-owned images: the null checks and the aliasing rules first, then the above.
+static int upscale_check(HrptContext* c, const char* what, const HrptUpscaleImages* img, uint32_t width, uint32_t height, uint32_t displayWidth,
+                         uint32_t displayHeight, const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptUpscaleParams* p)
+{
+    const std::string w(what);
+    if (!img || !view || !prevView || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null argument");
+    if (!img->color || !img->depth || !img->motion || !img->historyOut || !img->colorOut)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": null image (only historyIn may be NULL)");
+    if (img->historyOut == img->historyIn) return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": historyOut must differ from historyIn");
+    if (img->colorOut == img->historyIn || img->colorOut == img->historyOut)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, w + ": colorOut must differ from historyIn and historyOut");
+    return upscale_args_check(c, w, width, height, displayWidth, displayHeight, *view, *p);
+}
+
+int hrpt_upscale_host(const HrptUpscaleImages* img, uint32_t width, uint32_t height, uint32_t displayWidth, uint32_t displayHeight,
+                      const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptUpscaleParams* p, int nthreads)
+{
+    HRPT_TRY(upscale_check(nullptr, "hrpt_upscale_host", img, width, height, displayWidth, displayHeight, view, prevView, p));
+    return run_host("hrpt_upscale_host", [&] { upscale_host(*img, width, height, displayWidth, displayHeight, *view, *prevView, *p, host_threads(nthreads)); });
+}
+
+int hrpt_upscale_device(HrptContext* c, const HrptUpscaleImages* img, uint32_t width, uint32_t height, uint32_t displayWidth, uint32_t displayHeight,
+                        const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptUpscaleParams* p, void* stream)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    HRPT_TRY(upscale_check(c, "hrpt_upscale_device", img, width, height, displayWidth, displayHeight, view, prevView, p));
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_upscale(*img, width, height, displayWidth, displayHeight, *view, *prevView, *p, c->upscaleStaged, static_cast<hipStream_t>(stream)));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_upscale_device"); }
+
+int hrpt_upscale(HrptContext* c, uint32_t displayWidth, uint32_t displayHeight, const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView,
+                 const HrptUpscaleParams* p)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!view || !prevView || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upscale: null argument");
+    if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upscale: hrpt_resize not called");
+    if (!c->perSize.dMotion || !c->perSize.dGBuffer[HRPT_GB_DEPTH])
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upscale: the motion or depth plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH fills them)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HRPT_TRY(upscale_args_check(c, "hrpt_upscale", c->width, c->height, displayWidth, displayHeight, *view, *p));      // before anything is allocated
+    if (!c->perSize.dUpscaled || displayWidth != c->upscaleWidth || displayHeight != c->upscaleHeight) {
+        for (DeviceBuffer<float4>& image : c->perSize.dUpscaleHistory) image.reset();           // all three go before anything is allocated
+        c->perSize.dUpscaled.reset(); c->upscaleValid = false; c->upscaleCur = 0; c->upscaleWidth = c->upscaleHeight = 0;
+        const size_t bytes = (size_t)displayWidth * displayHeight * sizeof(float4);
+        for (DeviceBuffer<float4>& image : c->perSize.dUpscaleHistory) HRPT_TRY(realloc_image(c, image, bytes));
+        HRPT_TRY(realloc_image(c, c->perSize.dUpscaled, bytes));
+        c->upscaleWidth = displayWidth; c->upscaleHeight = displayHeight;
+    }
+    const int next = c->upscaleValid ? 1 - c->upscaleCur : 0;
+    HrptUpscaleImages img{};
+    img.color = reinterpret_cast<const float*>(c->perSize.dOutput.get());
+    img.depth = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get());
+    img.motion = reinterpret_cast<const float*>(c->perSize.dMotion.get());
+    const bool useHistory = c->upscaleValid && (p->flags & HRPT_UPSCALE_RESET) == 0;
+    img.historyIn = useHistory ? reinterpret_cast<const float*>(c->perSize.dUpscaleHistory[1 - next].get()) : nullptr;
+    img.historyOut = reinterpret_cast<float*>(c->perSize.dUpscaleHistory[next].get());
+    img.colorOut = reinterpret_cast<float*>(c->perSize.dUpscaled.get());
+    HIP_TRY(c, launch_upscale(img, c->width, c->height, displayWidth, displayHeight, *view, *prevView, *p, c->upscaleStaged, c->stream));
+    c->upscaleCur = next; c->upscaleValid = true;
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_upscale"); }
+
+// A display-size image of the upscale stage to the host: read_image's protocol with the size of the last hrpt_upscale.
+static int read_upscale_image(HrptContext* c, const float4* src, float* dst, size_t bytes, const char* what)
+{
+    if (!src) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": no upscaled image (hrpt_upscale writes it; hrpt_resize drops it)");
+    if (!dst || bytes != (size_t)c->upscaleWidth * c->upscaleHeight * 16) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": bad buffer size");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HRPT_OK;
+}
+
+int hrpt_read_upscaled(HrptContext* c, float* dst, size_t bytes)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    return read_upscale_image(c, c->perSize.dUpscaled, dst, bytes, "hrpt_read_upscaled");
+} catch (...) { return caught(c, "hrpt_read_upscaled"); }
+
+int hrpt_read_upscale_history(HrptContext* c, float* dst, size_t bytes)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    return read_upscale_image(c, c->perSize.dUpscaled ? c->perSize.dUpscaleHistory[c->upscaleCur].get() : nullptr, dst, bytes, "hrpt_read_upscale_history");
+} catch (...) { return caught(c, "hrpt_read_upscale_history"); }
+
+int hrpt_get_upscaled_device(HrptContext* c, void** devicePtr)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_upscaled_device: null out");
+    *devicePtr = c->perSize.dUpscaled;
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_get_upscaled_device"); }
 
 // ---- denoise (pt_denoise.h / pt_denoise.hip) ----
 // Size, view and parameters: all a context call has left to check once its arguments are not null (its images are the context's own).

@@ -70,6 +70,18 @@ hipError_t launch_temporal(const HrptTemporalImages& images, uint32_t width, uin
 void temporal_host(const HrptTemporalImages& images, uint32_t width, uint32_t height, const HrptPlanarViewConstants& view,
                    const HrptPlanarViewConstants& prevView, const HrptTemporalParams& params, int nthreads);
 
+// Temporal upscaling (pt_upscale.hip; arithmetic in pt_upscale.h): one kernel from width x height colour, depth and motion images into
+// displayWidth x displayHeight history and colour images. staged: false = the nine current-frame taps are global gathers (the measured-faster
+// default), true = they are served from an LDS-staged window (same bits). upscale_host (pt_upscale_host.cpp): the same arithmetic on host
+// threads. historyOut must not be historyIn, and colorOut neither of them.
+bool upscale_params_valid(const HrptUpscaleParams& params);
+bool upscale_ratio_ok(uint32_t width, uint32_t height, uint32_t displayWidth, uint32_t displayHeight);
+hipError_t launch_upscale(const HrptUpscaleImages& images, uint32_t width, uint32_t height, uint32_t displayWidth, uint32_t displayHeight,
+                          const HrptPlanarViewConstants& view, const HrptPlanarViewConstants& prevView, const HrptUpscaleParams& params, bool staged,
+                          hipStream_t stream);
+void upscale_host(const HrptUpscaleImages& images, uint32_t width, uint32_t height, uint32_t displayWidth, uint32_t displayHeight,
+                  const HrptPlanarViewConstants& view, const HrptPlanarViewConstants& prevView, const HrptUpscaleParams& params, int nthreads);
+
 // Denoise (pt_denoise.hip; arithmetic in pt_denoise.h): ONE pass of the Poisson filter with the given radius and frame over width x height
 // device images; images.noise must be set (a device tile of denoise_noise_floats() floats). denoise_host (pt_denoise_host.cpp): the same
 // arithmetic on host threads; a NULL images.noise means the default tile there. colorOut may be color; output must not be input.

@@ -35,6 +35,8 @@ EXPORTS = [
     "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
     "hrpt_temporal_host", "hrpt_temporal_device", "hrpt_temporal_accumulate", "hrpt_read_temporal_history", "hrpt_get_temporal_history_device",
     "hrpt_clear_accumulation",
+    "hrpt_upscale_host", "hrpt_upscale_device", "hrpt_upscale", "hrpt_read_upscaled", "hrpt_read_upscale_history", "hrpt_get_upscaled_device",
+    "hrpt_post_process_device",
     "hrpt_denoise_host", "hrpt_denoise_device", "hrpt_denoise", "hrpt_set_denoise_noise",
     "hrpt_demodulate_host", "hrpt_compose_host", "hrpt_demodulate_device", "hrpt_compose_device", "hrpt_demodulate", "hrpt_compose",
     "hrpt_read_modulation", "hrpt_get_modulation_device", "hrpt_modulation_probe",
@@ -116,6 +118,13 @@ lib.hrpt_temporal_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.P
 lib.hrpt_read_temporal_history.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.hrpt_get_temporal_history_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
 lib.hrpt_clear_accumulation.argtypes = [C.c_void_p]
+lib.hrpt_upscale_host.argtypes = [C.POINTER(S.UpscaleImages), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(S.UpscaleParams), C.c_int]
+lib.hrpt_upscale_device.argtypes = [C.c_void_p, C.POINTER(S.UpscaleImages), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(S.UpscaleParams), C.c_void_p]
+lib.hrpt_upscale.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(S.UpscaleParams)]
+lib.hrpt_read_upscaled.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+lib.hrpt_read_upscale_history.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+lib.hrpt_get_upscaled_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+lib.hrpt_post_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(S.PostParams), C.c_void_p]
 lib.hrpt_denoise_host.argtypes = [C.POINTER(S.DenoiseImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.DenoiseParams), C.c_int]
 lib.hrpt_denoise_device.argtypes = [C.c_void_p, C.POINTER(S.DenoiseImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.DenoiseParams), C.c_void_p]
 lib.hrpt_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(S.DenoiseParams)]
@@ -264,6 +273,26 @@ def temporal_host(color, motion, depth, normal, history, view, prev_view, params
     im = S.TemporalImages(*[a.ctypes.data for a in imgs], _ptr(hist), hout.ctypes.data, out.ctypes.data)
     v, pv = _view_record(view), _view_record(prev_view)
     _check_rc(lib.hrpt_temporal_host(C.byref(im), shape[1], shape[0], v.ctypes.data, pv.ctypes.data, C.byref(params), int(nthreads)))
+    return out, hout
+
+
+def upscale_host(color, depth, motion, history, display_size, view, prev_view, params=None, nthreads=0):
+    """hrpt_upscale_host: the upscale stage (csrc/pt_upscale.h) on host threads; needs no GPU and is bit-identical to
+    PathTracerContext.upscale / upscale_device. color / depth / motion: float32 [h, w, 4] images of one render-size frame (Output, the plane
+    S.GB_DEPTH, read_motion_vectors()); history: what the previous call returned, float32 [H, W, 4], or None; display_size = (W, H) with
+    w <= W <= 4 w and h <= H <= 4 h. view / prev_view: the render-size S.PlanarViewConstants of this and of last frame. params.jitter is the
+    sample offset the frame was rendered with. Returns (colour out, history out) at the display size: rgb = the resolved radiance in both,
+    alpha = the nearest render texel's alpha / the accumulated sample weight."""
+    imgs, _, shape = _same_shape_images("upscale_host", (color, depth, motion))
+    W, H = int(display_size[0]), int(display_size[1])
+    hist = None if history is None else np.ascontiguousarray(history, np.float32)
+    if hist is not None and hist.shape != (H, W, 4):
+        raise ValueError("upscale_host: history must be a float32 [H, W, 4] image of the display size")
+    params = params if params is not None else S.UpscaleParams()
+    out, hout = np.empty((H, W, 4), np.float32), np.empty((H, W, 4), np.float32)
+    im = S.UpscaleImages(*[a.ctypes.data for a in imgs], _ptr(hist), hout.ctypes.data, out.ctypes.data)
+    v, pv = _view_record(view), _view_record(prev_view)
+    _check_rc(lib.hrpt_upscale_host(C.byref(im), shape[1], shape[0], W, H, v.ctypes.data, pv.ctypes.data, C.byref(params), int(nthreads)))
     return out, hout
 
 
@@ -784,6 +813,50 @@ class PathTracerContext:
     def temporal_history_device(self):
         """Device pointer of that image (None before the first temporal_accumulate)."""
         return self._device_ptr(lib.hrpt_get_temporal_history_device)
+
+    def upscale(self, display_width, display_height, view, prev_view, params=None):
+        """hrpt_upscale: temporal upscaling of Output (the context's size) into a library-owned display_width x display_height image
+        (csrc/pt_upscale.h). Frame order: clear_accumulation -> render(accum_count=1 at index i) ->
+        render_motion_vectors(constants with m_Jitter = params.jitter, planes = 1 << S.GB_DEPTH) -> upscale -> bloom_device ->
+        post_process_device, the last two over upscaled_device(). params.jitter = (halton(i + 1, 2) - 0.5, halton(i + 1, 3) - 0.5); with
+        accum_count > 1 pass (0, 0) and render the planes without jitter. view / prev_view: the render-size views of this and of last
+        frame. The history lives in the context; the first call, a call with another display size, the first call after resize and
+        S.UPSCALE_RESET run without it. Asynchronous."""
+        params = params if params is not None else S.UpscaleParams()
+        v, pv = _view_record(view), _view_record(prev_view)
+        self._check(lib.hrpt_upscale(self._h, int(display_width), int(display_height), v.ctypes.data, pv.ctypes.data, C.byref(params)))
+        self._upscale_size = (int(display_width), int(display_height))
+
+    def upscale_device(self, images, width, height, display_width, display_height, view, prev_view, params=None, hip_stream=0):
+        """The same over caller-owned device images (S.UpscaleImages of device addresses), asynchronously on `hip_stream` (integer handle)."""
+        params = params if params is not None else S.UpscaleParams()
+        v, pv = _view_record(view), _view_record(prev_view)
+        self._check(lib.hrpt_upscale_device(self._h, C.byref(images), int(width), int(height), int(display_width), int(display_height),
+                                            v.ctypes.data, pv.ctypes.data, C.byref(params), C.c_void_p(int(hip_stream))))
+
+    def _read_upscale_image(self, fn):
+        W, H = getattr(self, "_upscale_size", (0, 0))
+        out = np.empty((H, W, 4), np.float32)
+        self._check(fn(self._h, out.ctypes.data, out.nbytes))
+        return out
+
+    def read_upscaled(self):
+        """The colour image the last upscale wrote: float32 [H, W, 4] at its display size (synchronises)."""
+        return self._read_upscale_image(lib.hrpt_read_upscaled)
+
+    def read_upscale_history(self):
+        """The history the last upscale wrote: rgb = resolved radiance, a = accumulated sample weight (synchronises)."""
+        return self._read_upscale_image(lib.hrpt_read_upscale_history)
+
+    def upscaled_device(self):
+        """Device pointer of the upscaled colour image (None before the first upscale and after resize)."""
+        return self._device_ptr(lib.hrpt_get_upscaled_device)
+
+    def post_process_device(self, hdr_ptr, display_ptr, pixel_count, params, hip_stream=0):
+        """hrpt_post_process_device: the HDR post chain over caller-owned device images (pixel_count float4 each), on the context's
+        histogram and exposure, asynchronously on `hip_stream` (integer handle). The way from upscaled_device() to the tonemapper."""
+        self._check(lib.hrpt_post_process_device(self._h, C.c_void_p(int(hdr_ptr)), C.c_void_p(int(display_ptr)), int(pixel_count), C.byref(params),
+                                                 C.c_void_p(int(hip_stream))))
 
     def denoise(self, view, params=None):
         """hrpt_denoise: the edge-stopping Poisson filter over the temporal history (csrc/pt_denoise.h), after

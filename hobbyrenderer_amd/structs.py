@@ -145,6 +145,25 @@ class TemporalImages(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("color", "motion", "depth", "normal", "historyIn", "historyOut", "colorOut")]
 
 
+UPSCALE_NO_CLAMP, UPSCALE_RESET = 1, 2          # HrptUpscaleParams::flags
+
+
+class UpscaleParams(C.Structure):
+    """HrptUpscaleParams. jitter: this frame's sample offset in render pixels (the m_Jitter it was rendered with), each in [-0.5, 0.5];
+    kernel: tap weight exp(-kernel * d^2) with d in display pixels, in (0, 16]; maxHistory: cap of the accumulated sample weight, >= 0.
+    flags: UPSCALE_NO_CLAMP skips the clamp of the history to the taps' colour range; UPSCALE_RESET ignores the context's stored history."""
+    _fields_ = [("jitter", C.c_float * 2), ("kernel", C.c_float), ("maxHistory", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def __init__(self, jitter=(0.0, 0.0), kernel=2.29, maxHistory=8.0, flags=0):
+        super().__init__((C.c_float * 2)(float(jitter[0]), float(jitter[1])), kernel, maxHistory, flags, (C.c_uint32 * 3)(0, 0, 0))
+
+
+class UpscaleImages(C.Structure):
+    """HrptUpscaleImages: host or device addresses of float4 images; color / depth / motion at the render size, historyIn (may be None) /
+    historyOut / colorOut at the display size."""
+    _fields_ = [(n, C.c_void_p) for n in ("color", "depth", "motion", "historyIn", "historyOut", "colorOut")]
+
+
 DENOISE_OUTPUT_ONLY = 1                         # HrptDenoiseParams::flags
 
 

@@ -668,6 +668,12 @@ int  hrpt_post_process(HrptContext* ctx, const HrptPostParams* params);
 int  hrpt_read_display(HrptContext* ctx, float* rgba, size_t bytes);           /* W*H*16 bytes */
 int  hrpt_get_exposure(HrptContext* ctx, float* exposure, uint32_t histogram256[256]);   /* histogram may be NULL */
 int  hrpt_set_exposure(HrptContext* ctx, float exposure);                      /* the persistent exposure buffer, initially 1 */
+/* The same chain over caller-owned DEVICE images (pixelCount float4 each; e.g. the upscaled image of hrpt_upscale, whose size is not the
+ * context's), asynchronous on the caller's stream (a hipStream_t; NULL = the default stream). It runs on the context's histogram and
+ * exposure, exactly as hrpt_post_process does: on a copy of Output it writes hrpt_post_process's display image bit for bit and leaves the
+ * same exposure. hdrDevice is only read; displayDevice must differ from it. NULL pointers or pixelCount outside 1..2^32-1:
+ * HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_post_process_device(HrptContext* ctx, const float* hdrDevice, float* displayDevice, uint64_t pixelCount, const HrptPostParams* params, void* stream);
 
 /* ---- Bloom: the stage in front of the post chain ---------------------------------------------------------------
  * BloomRenderer::Render (src/BloomRenderer.cpp:48-175) + src/shaders/Bloom.hlsl over the HDR colour image: soft-knee prefilter into a
@@ -748,6 +754,73 @@ int  hrpt_temporal_accumulate(HrptContext* ctx, const HrptPlanarViewConstants* v
 int  hrpt_read_temporal_history(HrptContext* ctx, float* dst, size_t bytes);
 /* Device pointer of that image (valid until the next hrpt_temporal_accumulate / hrpt_resize / hrpt_destroy); NULL before the first call. */
 int  hrpt_get_temporal_history_device(HrptContext* ctx, void** devicePtr);
+
+/* ---- Temporal upscaling: a display-size image from jittered render-size frames ------------------------------------------------
+ * The stage in the slot where the reference schedules its TAARenderer, between lighting and bloom / the HDR pass (src/Renderer.cpp:1296,1311).
+ * The reference's body there is a closed FSR3 call (src/TAARenderer.cpp:226-252) that it runs at render size == display size; none of its
+ * code is in the reference, so this stage is DEFINED by this library (hobbyrenderer_amd/csrc/pt_upscale.h) and parity
+ * with FSR is out of scope. Cost in a path tracer is proportional to pixels: render width x height, reconstruct displayWidth x displayHeight
+ * from the sub-pixel jitter of successive frames. Per display pixel: a Gaussian-weighted resolve of the 3 x 3 render texels around it (the
+ * weights measured in display pixels from where this frame's jittered samples lie), reprojection of the display-size history through the
+ * motion of the nearest-depth tap, SampleTextureCatmullRom, a clamp of the history to the taps' colour range, and a blend whose weight is
+ * how well this frame samples the pixel against the sample weight the history holds (kept in its alpha, capped at maxHistory).
+ * Images are row-major float4. width x height: color = Output of hrpt_render (rgb radiance, a); depth = the plane HRPT_GB_DEPTH; motion = the
+ * plane of hrpt_render_motion_vectors (.xy in render pixels). displayWidth x displayHeight: historyIn / historyOut (rgb, a = accumulated
+ * sample weight), colorOut (rgb, a = alpha of the nearest render texel). Sizes are 1..65535 with width <= displayWidth <= 4 * width and
+ * height <= displayHeight <= 4 * height; ratios need not be integers, and displayWidth == width is plain temporal antialiasing.
+ * view / prevView are the RENDER-size views of this and of last frame: view->m_ViewportSize must equal (width, height).
+ * Which jitter to pass: a frame rendered with accumCount == 1 at accumulation index i takes its primary-ray offset from that index, so pass
+ * jitter = (hrpt_halton(i + 1, 2) - 0.5, hrpt_halton(i + 1, 3) - 0.5), and pass the same pair as m_Jitter to hrpt_render_motion_vectors so
+ * that depth and motion belong to the same samples. With accumCount > 1 the samples of a pixel are already spread over it: pass (0, 0) and
+ * render the planes with zero jitter.
+ * Left out on purpose: sharpening (m_TAASharpness), tonemapped-space blend weights, a kept previous depth (disocclusion is handled by the
+ * clamp alone), a reactive mask. Opt-in: nothing calls it implicitly. Not part of multi-GPU tiles: it works on whole images, run it after
+ * the gather. */
+#define HRPT_UPSCALE_NO_CLAMP 1u   /* do not clamp the reprojected history to the colour range of the pixel's nine taps */
+#define HRPT_UPSCALE_RESET    2u   /* context call: ignore the stored history this call */
+typedef struct HrptUpscaleParams {
+    float jitter[2];      /* this frame's sample offset in render pixels (the m_Jitter it was rendered with); finite, each in [-0.5, 0.5] */
+    float kernel;         /* tap weight exp(-kernel * d^2), d in display pixels; default 2.29 (the Gaussian fit to Blackman-Harris); finite, in (0, 16] */
+    float maxHistory;     /* cap of the accumulated sample weight, default 8; finite, >= 0 */
+    uint32_t flags;       /* HRPT_UPSCALE_* */
+    uint32_t reserved[3]; /* 0 */
+} HrptUpscaleParams;
+typedef struct HrptUpscaleImages {
+    const float *color, *depth, *motion;   /* width x height */
+    const float *historyIn;                /* displayWidth x displayHeight; NULL = no history */
+    float *historyOut;                     /* must differ from historyIn */
+    float *colorOut;                       /* must differ from historyIn and historyOut */
+} HrptUpscaleImages;
+/* The stage on host threads over host images (no GPU needed; nthreads <= 0: one per hardware thread, at most 16). Bit-identical to the
+ * device calls. NULL arguments or images (historyIn excepted), historyOut == historyIn, colorOut == historyIn or historyOut, a size outside
+ * 1..65535, a display size outside [size, 4 * size], m_ViewportSize != (width, height), a parameter outside the ranges above, unknown flag
+ * bits, non-zero reserved: HRPT_ERR_INVALID_ARGUMENT, and nothing is written. HRPT_UPSCALE_RESET is accepted and means nothing here (pass
+ * historyIn = NULL). */
+int  hrpt_upscale_host(const HrptUpscaleImages* images, uint32_t width, uint32_t height, uint32_t displayWidth, uint32_t displayHeight,
+                       const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView, const HrptUpscaleParams* params, int nthreads);
+/* The same over caller-owned DEVICE images, asynchronous on the caller's stream (a hipStream_t; NULL = the default stream). */
+int  hrpt_upscale_device(HrptContext* ctx, const HrptUpscaleImages* deviceImages, uint32_t width, uint32_t height, uint32_t displayWidth,
+                         uint32_t displayHeight, const HrptPlanarViewConstants* view, const HrptPlanarViewConstants* prevView,
+                         const HrptUpscaleParams* params, void* stream);
+/* The stage over the context's own images: color = Output, depth and motion = the plane HRPT_GB_DEPTH and the motion plane as the caller
+ * filled them for this frame with hrpt_render_motion_vectors(..., planeMask = DEPTH), a library-owned ping-pong pair of display-size
+ * histories and a library-owned display-size colour image. These are allocated by the first call and re-allocated, with the history
+ * dropped, when the display size changes or after hrpt_resize. The first call, the first call after either, and a call with
+ * HRPT_UPSCALE_RESET run without history. Asynchronous on the context stream, honours hrpt_set_stream. It touches nothing else: Output,
+ * Accumulation, the planes, the temporal history, exposure and HrptStats stay as they were. Frame order:
+ *   hrpt_clear_accumulation -> hrpt_render -> hrpt_render_motion_vectors -> [hrpt_demodulate -> hrpt_temporal_accumulate -> hrpt_denoise
+ *   -> hrpt_compose] -> hrpt_upscale -> hrpt_bloom_device -> hrpt_post_process_device
+ * the last two over the upscaled image (hrpt_get_upscaled_device) at the display size. A motion or depth plane that was never requested,
+ * and the argument errors of hrpt_upscale_host: HRPT_ERR_INVALID_ARGUMENT, and nothing changes. */
+int  hrpt_upscale(HrptContext* ctx, uint32_t displayWidth, uint32_t displayHeight, const HrptPlanarViewConstants* view,
+                  const HrptPlanarViewConstants* prevView, const HrptUpscaleParams* params);
+/* Host read-backs of the colour image and of the history the last hrpt_upscale wrote (synchronise); bytes must be displayWidth *
+ * displayHeight * 16 of that call. With no such image (before the first call, after hrpt_resize): HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_read_upscaled(HrptContext* ctx, float* dst, size_t bytes);
+int  hrpt_read_upscale_history(HrptContext* ctx, float* dst, size_t bytes);
+/* Device pointer of the colour image (valid until a call of hrpt_upscale with another display size, hrpt_resize or hrpt_destroy); NULL
+ * where hrpt_read_upscaled would fail. */
+int  hrpt_get_upscaled_device(HrptContext* ctx, void** devicePtr);
 
 /* ---- Denoise: edge-stopping Poisson filter after the temporal accumulation ---------------------------------------------
  * The spatial half of the real-time chain: the reference's SSGI denoise pass (src/shaders/SSGIDenoise.hlsl, iterated with a doubling radius
