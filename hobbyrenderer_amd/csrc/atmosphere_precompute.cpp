@@ -535,21 +535,28 @@ extern "C" int hrpt_precompute_atmosphere(float* transmittance, float* scatterin
 {
     return precompute(transmittance, scattering, irradiance, 4, nthreads, -2);
 }
-// test hook: the texels [first, first + count) of one pass (3 = scattering density, 4 = indirect irradiance, 5 = multiple scattering) computed from
-// tables given in HOST memory, by host threads (device < 0) or by the kernel on HIP device `device` (the tables are copied there and back):
-// tests/test_atmosphere.py checks that both executors return the same bits. Every table is full size (3 floats per texel: 256 x 128 x 32 for the
-// scattering tables, 64 x 16 for deltaIrr; transmittance / scattering4 4 floats per texel); out3 (full size too) receives the texels asked for.
-extern "C" int hrpt_atmosphere_pass(int pass, int order, uint32_t first, uint32_t count, const float* transmittance, const float* deltaIrr, const float* deltaR, const float* deltaM,
-                                     const float* deltaDensity, const float* deltaMulti, float* scattering4, float* out3, int nthreads, int device)
+// test hook: the texels [first, first + count) of one pass (0 = transmittance, 1 = direct irradiance, 2 = single scattering, 3 = scattering density,
+// 4 = indirect irradiance, 5 = multiple scattering) computed from tables given in HOST memory, by host threads (device < 0) or by the kernel on HIP
+// device `device` (the tables are copied there and back): tests/test_atmosphere.py checks that both executors return the same bits,
+// tests/test_atmosphere_reference*.py that they are the numbers of the published model. Every table is full size (3 floats per texel: 256 x 128 x 32
+// for the scattering tables, 64 x 16 for deltaIrr; transmittance / scattering4 4 floats per texel). `out` (full size too) receives the texels asked
+// for: 3 floats per texel of the pass's own table, except pass 0, which writes the 256 x 64 table of 4 floats per texel there (and reads no table).
+// Pass 2 has three outputs and writes none of them to `out`: scattering4 (all four channels), deltaR and deltaM.
+extern "C" int hrpt_atmosphere_pass(int pass, int order, uint32_t first, uint32_t count, const float* transmittance, const float* deltaIrr, float* deltaR, float* deltaM,
+                                     const float* deltaDensity, const float* deltaMulti, float* scattering4, float* out, int nthreads, int device)
 {
-    if (pass != kDensity && pass != kMultiple && pass != kIndirect) return HRPT_ERR_INVALID_ARGUMENT;
-    if (!transmittance || !deltaIrr || !deltaR || !deltaM || !deltaDensity || !deltaMulti || !scattering4 || !out3 || first + count > pass_texels(pass)) return HRPT_ERR_INVALID_ARGUMENT;
-    const size_t nS = (size_t)SW * SH * SD, nI = (size_t)IW * IH, nOut = pass == kIndirect ? nI * 3 : nS * 3;
+    if (pass < kTransmittance || pass > kMultiple) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!transmittance || !deltaIrr || !deltaR || !deltaM || !deltaDensity || !deltaMulti || !scattering4 || !out || count > pass_texels(pass) || first > pass_texels(pass) - count)
+        return HRPT_ERR_INVALID_ARGUMENT;
+    const size_t nS = (size_t)SW * SH * SD, nI = (size_t)IW * IH;
+    const size_t nOut = pass == kTransmittance ? (size_t)TW * TH * 4 : ((pass == kDirectIrradiance || pass == kIndirect) ? nI * 3 : nS * 3);
     Executor ex; ex.nthreads = nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency(); ex.device = device;
     PassArgs a{}; a.order = order;
     if (device < 0) {
-        a.t.T = transmittance; a.t.deltaIrr = const_cast<float*>(deltaIrr); a.t.deltaR = const_cast<float*>(deltaR); a.t.deltaM = const_cast<float*>(deltaM);
-        a.t.deltaDensity = pass == kDensity ? out3 : const_cast<float*>(deltaDensity); a.t.deltaMulti = const_cast<float*>(deltaMulti); a.t.scattering = scattering4; a.out3 = out3;
+        std::vector<float> irr4(pass == kDirectIrradiance ? nI * 4 : 0);         // the accumulator the direct pass clears beside its output
+        a.Tw = pass == kTransmittance ? out : nullptr;
+        a.t.T = transmittance; a.t.deltaIrr = pass == kDirectIrradiance ? out : const_cast<float*>(deltaIrr); a.t.irradiance = irr4.data(); a.t.deltaR = deltaR; a.t.deltaM = deltaM;
+        a.t.deltaDensity = pass == kDensity ? out : const_cast<float*>(deltaDensity); a.t.deltaMulti = const_cast<float*>(deltaMulti); a.t.scattering = scattering4; a.out3 = out;
         return ex.run(pass, a, first, count) == hipSuccess ? HRPT_OK : HRPT_ERR_HIP;
     }
     if (hipSetDevice(device) != hipSuccess) return HRPT_ERR_NO_DEVICE;
@@ -557,9 +564,13 @@ extern "C" int hrpt_atmosphere_pass(int pass, int order, uint32_t first, uint32_
     float *dOut = nullptr;
     auto up = [&](float** d, const float* h, size_t floats) { return b.alloc(d, floats) == hipSuccess && hipMemcpy(*d, h, floats * 4, hipMemcpyHostToDevice) == hipSuccess; };
     if (!up(&b.T, transmittance, (size_t)TW * TH * 4) || !up(&b.dIrr, deltaIrr, nI * 3) || !up(&b.dR, deltaR, nS * 3) || !up(&b.dM, deltaM, nS * 3) || !up(&b.dDens, deltaDensity, nS * 3) ||
-        !up(&b.dMulti, deltaMulti, nS * 3) || !up(&b.scat, scattering4, nS * 4) || !up(&dOut, out3, nOut)) return HRPT_ERR_OUT_OF_MEMORY;
-    a.t.T = b.T; a.t.deltaIrr = b.dIrr; a.t.deltaR = b.dR; a.t.deltaM = b.dM; a.t.deltaDensity = pass == kDensity ? dOut : b.dDens; a.t.deltaMulti = b.dMulti; a.t.scattering = b.scat; a.out3 = dOut;
+        !up(&b.dMulti, deltaMulti, nS * 3) || !up(&b.scat, scattering4, nS * 4) || !up(&dOut, out, nOut)) return HRPT_ERR_OUT_OF_MEMORY;
+    if (pass == kDirectIrradiance && b.alloc(&b.irr, nI * 4) != hipSuccess) return HRPT_ERR_OUT_OF_MEMORY;
+    a.Tw = pass == kTransmittance ? dOut : nullptr;
+    a.t.T = b.T; a.t.deltaIrr = pass == kDirectIrradiance ? dOut : b.dIrr; a.t.irradiance = b.irr; a.t.deltaR = b.dR; a.t.deltaM = b.dM;
+    a.t.deltaDensity = pass == kDensity ? dOut : b.dDens; a.t.deltaMulti = b.dMulti; a.t.scattering = b.scat; a.out3 = dOut;
     if (ex.run(pass, a, first, count) != hipSuccess) return HRPT_ERR_HIP;
-    if (hipMemcpy(out3, dOut, nOut * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(scattering4, b.scat, nS * 16, hipMemcpyDeviceToHost) != hipSuccess) return HRPT_ERR_HIP;
+    if (hipMemcpy(out, dOut, nOut * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(scattering4, b.scat, nS * 16, hipMemcpyDeviceToHost) != hipSuccess) return HRPT_ERR_HIP;
+    if (pass == kSingle && (hipMemcpy(deltaR, b.dR, nS * 12, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(deltaM, b.dM, nS * 12, hipMemcpyDeviceToHost) != hipSuccess)) return HRPT_ERR_HIP;
     return HRPT_OK;
 }

@@ -1,4 +1,4 @@
-// pt_capi_selftest.cpp -- the hrpt_selftest_* entry points: device decode tables, BVH checks and read-back, the host builders, texture probes.
+// pt_capi_selftest.cpp -- the hrpt_selftest_* entry points: device decode tables, BVH checks and read-back, the host builders, texture and atmosphere probes.
 #include "pt_capi_internal.h"
 
 using namespace hrt;
@@ -131,3 +131,22 @@ try {
     if (e != hipSuccess) return fail(c, hip_status(e), std::string("hrpt_selftest_sample_textures: ") + hipGetErrorString(e));
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_selftest_sample_textures"); }
+
+int hrpt_selftest_atmosphere(HrptContext* c, const HrptAtmosphereProbe* probes, HrptAtmosphereProbeResult* results, uint64_t count)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->haveScene) return fail(c, HRPT_ERR_NO_SCENE, "hrpt_selftest_atmosphere: no scene uploaded");
+    if (count == 0) return HRPT_OK;
+    if (!probes || !results) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_selftest_atmosphere: null array");
+    if (count > (1ull << 24)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_selftest_atmosphere: too many probes in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    DeviceBuffer<HrptAtmosphereProbe> dProbes; DeviceBuffer<HrptAtmosphereProbeResult> dResults;
+    hipError_t e = dProbes.alloc(count * sizeof(HrptAtmosphereProbe));
+    if (e == hipSuccess) e = dResults.alloc(count * sizeof(HrptAtmosphereProbeResult));
+    if (e == hipSuccess) e = hipMemcpyAsync(dProbes, probes, count * sizeof(HrptAtmosphereProbe), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_atmosphere_probes(c->view, dProbes, dResults, (uint32_t)count, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, dResults, count * sizeof(HrptAtmosphereProbeResult), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, hip_status(e), std::string("hrpt_selftest_atmosphere: ") + hipGetErrorString(e));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_selftest_atmosphere"); }

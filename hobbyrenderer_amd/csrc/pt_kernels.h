@@ -142,6 +142,8 @@ hipError_t launch_f16_table(float* out, hipStream_t stream);
 // Self-test: results[i] = the shader's texture sampling functions on probes[i] (hrpt_selftest_sample_textures); device arrays.
 hipError_t launch_sample_textures(const SceneView& scene, uint32_t materialCount, const HrptTextureProbe* probes, HrptTextureProbeResult* results,
                                   uint32_t count, hipStream_t stream);
+// Self-test: results[i] = the run-time atmosphere lookups (sky radiance, sun radiance, transmittance) on probes[i] (hrpt_selftest_atmosphere); device arrays.
+hipError_t launch_atmosphere_probes(const SceneView& scene, const HrptAtmosphereProbe* probes, HrptAtmosphereProbeResult* results, uint32_t count, hipStream_t stream);
 
 // Output[xy] = accum.rgb / accum.a (PathTracer.hlsl:339) over the whole image.
 hipError_t launch_resolve(const float4* accumulation, float4* output, uint32_t pixelCount, hipStream_t stream);

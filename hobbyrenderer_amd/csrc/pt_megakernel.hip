@@ -272,6 +272,34 @@ hipError_t launch_sample_textures(const SceneView& scene, uint32_t materialCount
     return hipGetLastError();
 }
 
+// Self-test of the run-time atmosphere lookups (hrpt_selftest_atmosphere): one thread per probe calls atm::sky_radiance, atm::sun_radiance
+// and atm::transmittance_to_top of pt_atmosphere.h as the miss and sun-light code of pt_path.h does, over the scene's own RGBA16F tables.
+__global__ void pt_atmosphere_probe_kernel(SceneView s, const HrptAtmosphereProbe* __restrict__ probes, HrptAtmosphereProbeResult* __restrict__ results,
+                                           uint32_t count)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const HrptAtmosphereProbe p = probes[i];
+    HrptAtmosphereProbeResult& r = results[i];
+    const f3 cam = mk3(p.cameraPos[0], p.cameraPos[1], p.cameraPos[2]), view = mk3(p.viewRay[0], p.viewRay[1], p.viewRay[2]);
+    const f3 sunDir = mk3(p.sunDir[0], p.sunDir[1], p.sunDir[2]);
+    const f3 pa = atm::atmosphere_pos(cam);
+    const f3 sky = atm::sky_radiance(s, cam, view, sunDir, p.sunIntensity, p.addSunDisk != 0u);
+    const f3 sun = atm::sun_radiance(s, pa, sunDir, p.sunIntensity);
+    const float rr = length(pa), mu = dot(pa, view) / rr;
+    const f3 tr = atm::transmittance_to_top(s, rr, mu);
+    r.sky[0] = sky.x; r.sky[1] = sky.y; r.sky[2] = sky.z;
+    r.sun[0] = sun.x; r.sun[1] = sun.y; r.sun[2] = sun.z;
+    r.transmittance[0] = tr.x; r.transmittance[1] = tr.y; r.transmittance[2] = tr.z;
+    r.r = rr; r.mu = mu; r.pad = 0.0f;
+}
+hipError_t launch_atmosphere_probes(const SceneView& scene, const HrptAtmosphereProbe* probes, HrptAtmosphereProbeResult* results, uint32_t count, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(pt_atmosphere_probe_kernel, dim3((count + 63u) / 64u), dim3(64), 0, stream, scene, probes, results, count);
+    return hipGetLastError();
+}
+
 // Self-test of the acceleration structure (hrpt_selftest_bvh): every child box stored in a node must contain what hangs below it -- the
 // child's own child boxes when it is an inner node, the vertices of its triangles when it is a leaf. The GPU builder fits boxes bottom-up
 // with relaxed agent-scope atomics and write-through stores (bvh_build_gpu.hip k_fit); a stale read there would give a parent box that is

@@ -29,7 +29,7 @@ lib = C.CDLL(LIB_PATH)
 EXPORTS = [
     "hrpt_create", "hrpt_destroy", "hrpt_last_error", "hrpt_upload_scene", "hrpt_resize", "hrpt_render",
     "hrpt_synchronize", "hrpt_set_stream", "hrpt_get_device_images", "hrpt_read_accumulation", "hrpt_read_output",
-    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_update_vertices", "hrpt_update_vertices_device", "hrpt_quantize_vertices_host", "hrpt_quantize_vertices_device", "hrpt_skin_vertices_host", "hrpt_skin_vertices_device", "hrpt_update_vertices_skinned", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
+    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_update_vertices", "hrpt_update_vertices_device", "hrpt_quantize_vertices_host", "hrpt_quantize_vertices_device", "hrpt_skin_vertices_host", "hrpt_skin_vertices_device", "hrpt_update_vertices_skinned", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_atmosphere", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_render_gbuffer", "hrpt_read_gbuffer", "hrpt_get_gbuffer_device",
     "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
@@ -95,6 +95,7 @@ lib.hrpt_reset_stats.argtypes = [C.c_void_p]
 lib.hrpt_selftest_f16_decode.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_selftest_unorm8.argtypes = [C.c_void_p, C.c_void_p]
 lib.hrpt_selftest_sample_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+lib.hrpt_selftest_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
 lib.hrpt_selftest_bvh.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 lib.hrpt_selftest_read_bvh.argtypes = [C.c_void_p, C.POINTER(S.BvhDump)]
 lib.hrpt_selftest_host_build.argtypes = [C.POINTER(S.SceneDesc), C.c_uint32, C.c_uint32, C.POINTER(S.BvhDump)]
@@ -233,6 +234,28 @@ def precompute_atmosphere(nthreads=0, orders=ATMOSPHERE_ORDERS, device=-2, cache
         except OSError:
             pass
     return t, s, i
+
+
+ATM_PASS_TRANSMITTANCE, ATM_PASS_DIRECT_IRRADIANCE, ATM_PASS_SINGLE, ATM_PASS_DENSITY, ATM_PASS_INDIRECT, ATM_PASS_MULTIPLE = range(6)
+_ATM_NS, _ATM_NI, _ATM_NT = 32 * 128 * 256, 16 * 64, 64 * 256
+
+
+def atmosphere_pass(pass_id, order, first, count, tables, device=-1, nthreads=0):
+    """hrpt_atmosphere_pass: texels [first, first + count) of one producer pass (ATM_PASS_*) from the full-size float32 tables in `tables`
+    (keys T [64 * 256, 4], dIrr [16 * 64, 3], dR / dM / dDens / dMulti [32 * 128 * 256, 3], scat [32 * 128 * 256, 4]; none is modified), by
+    host threads (device < 0) or on that GPU. Returns a dict of the tables the pass writes, zero outside the texels asked for unless the
+    table was an input: "out" (pass 0: [64 * 256, 4]; passes 1, 4: [16 * 64, 3]; passes 3, 5: [32 * 128 * 256, 3]), "scat" (passes 2 and
+    5: a copy of tables["scat"] with the texels written / accumulated), "dR" and "dM" (pass 2)."""
+    shapes = {"T": (_ATM_NT, 4), "dIrr": (_ATM_NI, 3), "dR": (_ATM_NS, 3), "dM": (_ATM_NS, 3), "dDens": (_ATM_NS, 3), "dMulti": (_ATM_NS, 3), "scat": (_ATM_NS, 4)}
+    written = ("scat", "dR", "dM") if pass_id == ATM_PASS_SINGLE else (("scat",) if pass_id == ATM_PASS_MULTIPLE else ())
+    t = {k: (np.array(tables[k], np.float32) if k in written else np.ascontiguousarray(tables[k], np.float32)).reshape(shape) for k, shape in shapes.items()}
+    out = np.zeros((_ATM_NT, 4) if pass_id == ATM_PASS_TRANSMITTANCE else ((_ATM_NI, 3) if pass_id in (ATM_PASS_DIRECT_IRRADIANCE, ATM_PASS_INDIRECT) else (_ATM_NS, 3)), np.float32)
+    _check_rc(lib.hrpt_atmosphere_pass(int(pass_id), int(order), int(first), int(count), t["T"].ctypes.data, t["dIrr"].ctypes.data, t["dR"].ctypes.data, t["dM"].ctypes.data,
+                                       t["dDens"].ctypes.data, t["dMulti"].ctypes.data, t["scat"].ctypes.data, out.ctypes.data, int(nthreads), int(device)))
+    res = {"out": out, "scat": t["scat"]}
+    if pass_id == ATM_PASS_SINGLE:
+        res["dR"], res["dM"] = t["dR"], t["dM"]
+    return res
 
 
 def bloom_host(img, params=None, nthreads=0):
@@ -957,6 +980,15 @@ class PathTracerContext:
         results = np.zeros(len(probes), S.TextureProbeResult)
         self._check(lib.hrpt_selftest_sample_textures(self._h, probes.ctypes.data if len(probes) else None, results.ctypes.data if len(probes) else None,
                                                       len(probes)))
+        return results
+
+    def selftest_atmosphere(self, probes):
+        """hrpt_selftest_atmosphere: probes = structured array of S.AtmosphereProbe; returns a structured array of S.AtmosphereProbeResult
+        (the device's sky radiance, sun radiance and transmittance lookup of every probe over the uploaded scene's tables)."""
+        probes = np.ascontiguousarray(probes, S.AtmosphereProbe)
+        results = np.zeros(len(probes), S.AtmosphereProbeResult)
+        self._check(lib.hrpt_selftest_atmosphere(self._h, probes.ctypes.data if len(probes) else None, results.ctypes.data if len(probes) else None,
+                                                 len(probes)))
         return results
 
     def reset_stats(self):

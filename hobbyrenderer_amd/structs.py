@@ -260,6 +260,10 @@ GB_FLAG_HIT, GB_FLAG_FRONT_FACE = 1, 2
 TextureProbe = np.dtype([("material", u32), ("uv", f32, 2), ("ddx", f32, 2), ("ddy", f32, 2), ("texFlags", u32)])                       # HrptTextureProbe, 32 B
 TextureProbeResult = np.dtype([("single", f32, (4, 4)), ("batched", f32, (4, 4)), ("batchedAccepted", u32), ("pad", u32, 3), ("grad", f32, 4)])   # HrptTextureProbeResult, 160 B
 assert TextureProbe.itemsize == 32 and TextureProbeResult.itemsize == 160
+# hrpt_selftest_atmosphere: the run-time sky / sun / transmittance lookups on one camera position, view ray and sun direction
+AtmosphereProbe = np.dtype([("cameraPos", f32, 3), ("viewRay", f32, 3), ("sunDir", f32, 3), ("sunIntensity", f32), ("addSunDisk", u32), ("pad", u32)])   # HrptAtmosphereProbe, 48 B
+AtmosphereProbeResult = np.dtype([("sky", f32, 3), ("sun", f32, 3), ("transmittance", f32, 3), ("r", f32), ("mu", f32), ("pad", f32)])                  # HrptAtmosphereProbeResult, 48 B
+assert AtmosphereProbe.itemsize == 48 and AtmosphereProbeResult.itemsize == 48
 
 
 class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B

@@ -1018,6 +1018,16 @@ int  hrpt_selftest_unorm8(HrptContext* ctx, float* out512);
 typedef struct HrptTextureProbe { uint32_t material; float uv[2], ddx[2], ddy[2]; uint32_t texFlags; } HrptTextureProbe;                /* 32 B */
 typedef struct HrptTextureProbeResult { float single[4][4]; float batched[4][4]; uint32_t batchedAccepted, pad[3]; float grad[4]; } HrptTextureProbeResult;   /* 160 B */
 int  hrpt_selftest_sample_textures(HrptContext* ctx, const HrptTextureProbe* probes, HrptTextureProbeResult* results, uint64_t count);
+/* Device self-test of the run-time atmosphere lookups over the uploaded scene's RGBA16F tables (tests/atmosphere_reference.py states the
+ * same lookups in float64): one thread per probe calls the device functions the miss and sun-light code calls, as they are. cameraPos is a
+ * world position in metres, viewRay and sunDir unit vectors. sky: the sky radiance along viewRay (with the sun disk when addSunDisk is
+ * non-zero); sun: the sun's radiance arriving at cameraPos; transmittance: the table lookup towards the top of the atmosphere for
+ * r = that position's distance from the planet's centre in km and mu = the cosine between its zenith and viewRay, both returned too
+ * (the lookup is made with them as they are, also below the ground and above the atmosphere, where the addressing clamps).
+ * probes / results are host arrays; count == 0 does nothing. Synchronises. */
+typedef struct HrptAtmosphereProbe { float cameraPos[3], viewRay[3], sunDir[3]; float sunIntensity; uint32_t addSunDisk, pad; } HrptAtmosphereProbe;   /* 48 B */
+typedef struct HrptAtmosphereProbeResult { float sky[3], sun[3], transmittance[3], r, mu, pad; } HrptAtmosphereProbeResult;                          /* 48 B */
+int  hrpt_selftest_atmosphere(HrptContext* ctx, const HrptAtmosphereProbe* probes, HrptAtmosphereProbeResult* results, uint64_t count);
 
 /* Host-side helpers of PathTracerRenderer::Render, exported so that callers in other languages
  * produce the same constants: Halton (src/Utilities.cpp:67-79) and the CB fill (:58-75). */
@@ -1034,11 +1044,16 @@ float hrpt_halton(uint32_t index, uint32_t base);
  * arithmetic of hobbyrt/detmath.h). Four orders: ~0.1 s on an MI355X, ~40 s on 8 host threads. */
 int  hrpt_precompute_atmosphere(float* transmittance, float* scattering, float* irradiance, int nthreads);
 int  hrpt_precompute_atmosphere_ex(float* transmittance, float* scattering, float* irradiance, int orders, int nthreads, int device);
-/* Test hook: texels [first, first + count) of one pass (3 scattering density, 4 indirect irradiance, 5 multiple scattering) of order `order`
- * from tables in host memory (3 floats per texel; transmittance / scattering4: 4), by host threads (device < 0) or on HIP device `device`. */
+/* Test hook: texels [first, first + count) of one pass (0 transmittance, 1 direct irradiance, 2 single scattering, 3 scattering density,
+ * 4 indirect irradiance, 5 multiple scattering; any other id is refused) of order `order` (passes 3 to 5) from full-size tables in host
+ * memory (3 floats per texel; transmittance / scattering4: 4), by host threads (device < 0) or on HIP device `device`. Every pointer must
+ * be non-null whatever the pass reads. `out` receives the texels of the pass's own table, 3 floats per texel (passes 1 and 4: 64 x 16,
+ * passes 3 and 5: 256 x 128 x 32); pass 0 writes the 256 x 64 transmittance table there with 4 floats per texel and reads no table.
+ * Pass 2 leaves `out` alone and writes its three outputs in place: scattering4 (rgb Rayleigh, a red Mie), deltaRayleigh and deltaMie.
+ * Pass 5 also adds its texels, divided by the Rayleigh phase function, to scattering4. */
 int  hrpt_atmosphere_pass(int pass, int order, uint32_t first, uint32_t count, const float* transmittance, const float* deltaIrradiance,
-                          const float* deltaRayleigh, const float* deltaMie, const float* deltaDensity, const float* deltaMultiple,
-                          float* scattering4, float* out3, int nthreads, int device);
+                          float* deltaRayleigh, float* deltaMie, const float* deltaDensity, const float* deltaMultiple,
+                          float* scattering4, float* out, int nthreads, int device);
 
 #ifdef __cplusplus
 } /* extern "C" */

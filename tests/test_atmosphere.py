@@ -85,7 +85,8 @@ def test_pass_hook_argument_checks():
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     out = np.zeros((NS, 3), np.float32)
     args = (p(inp["T"]), p(inp["dIrr"]), p(inp["dR"]), p(inp["dM"]), p(inp["dDens"]), p(inp["dMulti"]), p(inp["scat"]), p(out), 0, -1)
-    assert native.lib.hrpt_atmosphere_pass(2, 2, 0, 1, *args) == -1            # not a hooked pass
+    assert native.lib.hrpt_atmosphere_pass(-1, 2, 0, 1, *args) == -1           # not a pass: the ids are 0 to 5
+    assert native.lib.hrpt_atmosphere_pass(6, 2, 0, 1, *args) == -1
     assert native.lib.hrpt_atmosphere_pass(3, 2, NS - 1, 2, *args) == -1       # range past the table
     assert native.lib.hrpt_atmosphere_pass(4, 1, 0, NI, *args) == 0
 
