@@ -26,8 +26,8 @@ HRT_DEV unsigned long long wave_sum(unsigned int v)
     return x;
 }
 
-// TL: the scene holds the two-level structure (SceneView::instances): the same shader over closest_two_level / shadow_query_two_level
-// (pt_device.h, pt_path.h), so that the two-level kernels of the wavefront pipeline keep the wavefront == megakernel cross-check every other
+// TL: the scene holds the two-level structure (SceneView::instances): the same shader over closest_two_level / any_hit_two_level (shadow_query)
+// (pt_traverse.h, pt_shadow.h), so that the two-level kernels of the wavefront pipeline keep the wavefront == megakernel cross-check every other
 // path has. Private 64-entry stack: scenes whose two-level stack need is larger are refused by hrpt_render.
 template <bool TL>
 __global__ __launch_bounds__(64) void pt_megakernel(SceneView s, HrptPathTracerConstants cb, float4* __restrict__ accumulation,

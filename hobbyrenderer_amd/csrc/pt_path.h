@@ -3,13 +3,16 @@
 //   primary_ray        :61-72     TraceRayStandard  RaytracingCommon.hlsli:138-198
 //   shade_surface_a    :92-261    (attributes, transmission branch, emissive, NEE sample generation)
 //   shade_surface_b    :264-313   (Russian roulette, BRDF lobe pick + sample, ray advance)
-//   shadow_query       CommonLighting.hlsli:380-496 (CalculateRTShadow<true>)
 //   miss_sky           :315-328
+// plus trace_standard / candidate_commits (the closest-hit query with its candidate branch), the three stages of one NEE light sample and
+// the BRDF lobes. The visibility of an NEE shadow ray (CalculateRTShadow<true>) is pt_shadow.h, included here: every user of a path stage
+// traces shadow rays too.
 // NEE shadow rays draw no random numbers, so a stage may defer them: shade_surface_a hands every
 // light sample to an `emit` callback (direction, distance, unshadowed diffuse/specular radiance).
 #pragma once
 
 #include "pt_device.h"
+#include "pt_shadow.h"
 
 namespace hrt {
 
@@ -70,325 +73,15 @@ HRT_DEV bool candidate_commits(const SceneView& s, const Hit& h, uint32_t& rng)
 template <class BVH, class STACK>
 HRT_DEV bool trace_standard(const SceneView& s, const BVH& bvh, const Ray& ray, uint32_t& rng, STACK& stack, Hit& out)
 {
-    HitKey lower; lower.have = false; lower.t = 0.0f; lower.inst = 0; lower.prim = 0;
+    HitKey lower = hit_key_none();
     for (;;) {
         Hit h;
         if constexpr (BVH::kTwoLevel) h = closest_two_level(bvh, s.rootLeaf, s.nodeCount, ray, lower, stack);
         else h = closest_any(bvh, s.rootLeaf, s.nodeCount, ray, lower, stack);
         if (!h.valid) return false;
         if ((h.opaque & 1u) || candidate_commits(s, h, rng)) { out = h; return true; }
-        lower.have = true; lower.t = h.t; lower.inst = h.inst; lower.prim = h.prim;
+        hit_key_advance(lower, h);
     }
-}
-
-// ---- CalculateRTShadow<true>, CommonLighting.hlsli:380-496 ------------------------------------------------------
-// State carried from candidate to candidate (:404-407) and the per-candidate body (:409-470); returns true when the
-// candidate commits (the query then returns 0).
-struct ShadowState { float transmission; bool inVolume; float inVolumeStartT; f3 sigmaT; };
-
-HRT_DEV bool shadow_candidate(const SceneView& s, const Ray& ray, float hitT, uint32_t tri, float bu, float bv, ShadowState& st)
-{
-    TriVerts tv = load_tri_attr(s, tri);           // inst.m_LODIndex is 0 on this path (validated at upload), :423
-    const HrptMaterialConstants& mat = s.materials[tv.material];
-    f2 uv = interpolated_uv(tv, bu, bv);
-    if (mat.m_AlphaMode == HRPT_ALPHA_MODE_MASK) {
-        // AlphaTestGrad (RaytracingCommon.hlsli:112-130) with GetShadowRayGradients (:207-240); level 0 unless the texture has a mip chain
-        return candidate_alpha_grad(s, mat, uv, tv, tri, bu, bv, ray.o) >= mat.m_AlphaCutoff;
-    }
-    if (mat.m_AlphaMode != HRPT_ALPHA_MODE_BLEND) return true;
-    float alpha = candidate_alpha(s, mat, uv);
-    float opacity = hrt_saturate(alpha * (1.0f - mat.m_TransmissionFactor));
-    st.transmission *= (1.0f - opacity);
-    if (mat.m_TransmissionFactor > 0.0f && mat.m_IsThinSurface == 0) {
-        float w0 = (1.0f - bu) - bv;
-        f3 ln = (tv.n0 * w0 + tv.n1 * bu) + tv.n2 * bv;
-        f3 wn = normalize(transform_normal(ln, s.instShade[tv.inst]));
-        bool front = dot(wn, ray.d) < 0.0f;
-        if (front) { st.inVolume = true; st.inVolumeStartT = hitT; st.sigmaT = mk3(mat.m_SigmaA) + mk3(mat.m_SigmaS); }
-        else if (st.inVolume) {
-            float seg = hrt_max(0.0f, hitT - st.inVolumeStartT);
-            f3 tr = mk3(hrt_exp(-st.sigmaT.x * seg), hrt_exp(-st.sigmaT.y * seg), hrt_exp(-st.sigmaT.z * seg));
-            st.transmission *= dot(tr, mk3(0.2126f, 0.7152f, 0.0722f));
-            st.inVolume = false;
-        }
-    }
-    return st.transmission <= 1e-3f;
-}
-HRT_DEV float shadow_finish(const Ray& ray, ShadowState& st)                       // :477-495
-{
-    if (st.inVolume) {
-        float seg = hrt_max(0.0f, ray.tmax - st.inVolumeStartT);
-        f3 tr = mk3(hrt_exp(-st.sigmaT.x * seg), hrt_exp(-st.sigmaT.y * seg), hrt_exp(-st.sigmaT.z * seg));
-        st.transmission *= dot(tr, mk3(0.2126f, 0.7152f, 0.0722f));
-    }
-    return hrt_saturate(st.transmission);
-}
-HRT_DEV Ray shadow_ray(f3 worldPos, f3 L, float maxDist)                           // :391-396
-{
-    const float kShadowBias = 0.01f;
-    Ray ray; ray.o = worldPos; ray.d = L; ray.tmin = kShadowBias; ray.tmax = hrt_max(kShadowBias, maxDist - kShadowBias * 2.0f);
-    return ray;
-}
-
-// A crossed non-opaque triangle of a two-level scene (the per-candidate body above; material and transform come from the hit's instance, the
-// world-space vertices the mip-selecting alpha test wants from the instance's m_World).
-HRT_DEV bool shadow_candidate_two_level(const SceneView& s, const Ray& ray, const Hit& h, ShadowState& st)
-{
-    TriVerts tv = load_hit_attr(s, h);
-    const HrptMaterialConstants& mat = s.materials[tv.material];
-    f2 uv = interpolated_uv(tv, h.u, h.v);
-    if (mat.m_AlphaMode == HRPT_ALPHA_MODE_MASK) {
-        float alpha = mat.m_BaseColor[3];
-        if (mat.m_TextureFlags & HRPT_TEXFLAG_ALBEDO) {
-            const uint32_t ti = mat.m_AlbedoTextureIndex;
-            if (ti >= s.textureCount || !s.textures[ti].texels) alpha *= 0.0f;
-            else {
-                const GpuTexture& t = s.textures[ti];
-                if (t.mipCount <= 1u) alpha *= sample_texture_level(t.texels, t.format, (int)t.w, (int)t.h, 0u, mat.m_AlbedoSamplerIndex, uv).w;
-                else {      // GetShadowRayGradients (RaytracingCommon.hlsli:207-240) from the world-space triangle, as candidate_alpha_grad
-                    const float4* tp = reinterpret_cast<const float4*>(s.tris + h.tri);
-                    f3 p0, p1, p2; tl_world_triangle(s.instances[h.inst], tp[0], tp[1], tp[2], p0, p1, p2);
-                    const float w0 = (1.0f - h.u) - h.v;
-                    const f3 hitPos = (p0 * w0 + p1 * h.u) + p2 * h.v;
-                    const float dist = length(hitPos - ray.o);
-                    const float triangleArea = length(cross(p1 - p0, p2 - p0)) * 0.5f;
-                    f2 uvRange;
-                    uvRange.x = hrt_max(tv.uv0.x, hrt_max(tv.uv1.x, tv.uv2.x)) - hrt_min(tv.uv0.x, hrt_min(tv.uv1.x, tv.uv2.x));
-                    uvRange.y = hrt_max(tv.uv0.y, hrt_max(tv.uv1.y, tv.uv2.y)) - hrt_min(tv.uv0.y, hrt_min(tv.uv1.y, tv.uv2.y));
-                    const float gradientScale = triangleArea / hrt_max(dist, 0.1f);
-                    f2 grad; grad.x = uvRange.x * gradientScale; grad.y = uvRange.y * gradientScale;
-                    alpha *= sample_texture_grad(t, mat.m_AlbedoSamplerIndex, uv, grad, grad).w;
-                }
-            }
-        }
-        return alpha >= mat.m_AlphaCutoff;
-    }
-    if (mat.m_AlphaMode != HRPT_ALPHA_MODE_BLEND) return true;
-    float alpha = candidate_alpha(s, mat, uv);
-    float opacity = hrt_saturate(alpha * (1.0f - mat.m_TransmissionFactor));
-    st.transmission *= (1.0f - opacity);
-    if (mat.m_TransmissionFactor > 0.0f && mat.m_IsThinSurface == 0) {
-        float w0 = (1.0f - h.u) - h.v;
-        f3 ln = (tv.n0 * w0 + tv.n1 * h.u) + tv.n2 * h.v;
-        f3 wn = normalize(transform_normal(ln, s.instShade[tv.inst]));
-        bool front = dot(wn, ray.d) < 0.0f;
-        if (front) { st.inVolume = true; st.inVolumeStartT = h.t; st.sigmaT = mk3(mat.m_SigmaA) + mk3(mat.m_SigmaS); }
-        else if (st.inVolume) {
-            float seg = hrt_max(0.0f, h.t - st.inVolumeStartT);
-            f3 tr = mk3(hrt_exp(-st.sigmaT.x * seg), hrt_exp(-st.sigmaT.y * seg), hrt_exp(-st.sigmaT.z * seg));
-            st.transmission *= dot(tr, mk3(0.2126f, 0.7152f, 0.0722f));
-            st.inVolume = false;
-        }
-    }
-    return st.transmission <= 1e-3f;
-}
-// CalculateRTShadow<true> over the two-level structure, re-trace form: an any-hit pass over the opaque instances, then -- only for a ray that
-// crossed triangles of non-opaque instances -- one closest-hit query per candidate, front to back (the visiting order of every other form).
-template <class STACK>
-HRT_DEV float shadow_retrace_two_level(const SceneView& s, const GlobalBvhTl& bvh, const Ray& ray, STACK& stack)
-{
-    ShadowState st; st.transmission = 1.0f; st.inVolume = false; st.inVolumeStartT = 0.0f; st.sigmaT = mk3(0.0f, 0.0f, 0.0f);
-    HitKey lower; lower.have = false; lower.t = 0.0f; lower.inst = 0; lower.prim = 0;
-    for (;;) {
-        Hit h = closest_two_level(bvh, s.rootLeaf, s.nodeCount, ray, lower, stack);
-        if (!h.valid) break;
-        if (h.opaque) return 0.0f;      // (cannot happen: the any-hit pass would have returned; kept for the symmetry with shadow_resolve_candidates)
-        if (shadow_candidate_two_level(s, ray, h, st)) return 0.0f;
-        lower.have = true; lower.t = h.t; lower.inst = h.inst; lower.prim = h.prim;
-    }
-    return shadow_finish(ray, st);
-}
-// Buffered form over the two-level structure (wf_shadow<TL = 2>): ONE traversal that returns at the first triangle of an opaque instance and keeps
-// the K nearest triangles of non-opaque instances, sorted by (t, instance, primitive), in per-lane LDS columns CAND3 of (t, mesh triangle,
-// instance); they are then visited front to back, and only a ray that crossed more than K continues with the re-trace loop behind the K-th.
-// Same visiting order as shadow_query_two_level, hence the same result.
-template <int K, class STACK, class CAND3>
-HRT_DEV float shadow_query_two_level_buffered(const SceneView& s, const GlobalBvhTl& bvh, const Ray& ray, STACK& stack, CAND3& cand, uint32_t nodeLoopMin = 0)
-{
-    if (!(ray.d.x == ray.d.x && ray.d.y == ray.d.y && ray.d.z == ray.d.z)) return 1.0f;
-    RayShear sh = make_shear(ray.d);
-    TlCull c; tl_world(c, ray);
-    int sp = 0, count = 0; bool overflow = false;
-    int32_t cur;
-    if (s.nodeCount == 0) { if (s.rootLeaf == 0) return 1.0f; cur = s.rootLeaf; } else cur = 0;
-    auto prim_of = [&](uint32_t tri) { return reinterpret_cast<const uint32_t*>(bvh.tris + tri)[7]; };      // GpuTri::prim
-    for (;;) {
-        while (cur >= 0 && cur != kExitBlas) {
-            cur = inner_step(bvh, cur, c.noi, c.noiF, c.inv, ray.tmin, ray.tmax, stack, sp);
-            if ((uint32_t)__popcll(__ballot(cur >= 0 && cur != kExitBlas)) < nodeLoopMin) break;
-        }
-        if (cur == kTraversalDone) break;
-        if (cur == kExitBlas || (cur < 0 && c.inst < 0)) { cur = tl_switch(bvh, cur, c, ray, stack, sp); continue; }
-        if (cur >= 0) continue;
-        const GpuInstance& I = bvh.instances[c.inst];
-        const uint32_t enc = (uint32_t)(~cur), first = enc >> 2, n = (enc & 3u) + 1u, inst = (uint32_t)c.inst;
-        for (uint32_t i = 0; i < n; ++i) {
-            float4 ta, tb, tc; bvh.tri(first + i, ta, tb, tc);
-            f3 p0, p1, p2; tl_world_triangle(I, ta, tb, tc, p0, p1, p2);
-            float t, u, v;
-            if (!tri_test(p0, p1, p2, ray, sh, t, u, v)) continue;
-            if (I.flags & 1u) return 0.0f;                                        // opaque instance: committed
-            const uint32_t prim = __float_as_uint(tb.w);
-            int pos = count;
-            if (count == K) {
-                float lt; uint32_t ltri, linst; cand.key(K - 1, lt, ltri, linst);
-                overflow = true;
-                if (!key_less(t, inst, prim, lt, linst, prim_of(ltri))) continue;
-                pos = K - 1;
-            } else ++count;
-            while (pos > 0) {
-                float pt; uint32_t ptri, pinst; cand.key(pos - 1, pt, ptri, pinst);
-                const bool less = t != pt ? t < pt : key_less(t, inst, prim, pt, pinst, prim_of(ptri));
-                if (!less) break;
-                cand.move(pos, pos - 1);
-                --pos;
-            }
-            cand.set(pos, t, first + i, inst);
-        }
-        cur = stack.pop(--sp);
-    }
-    if (count == 0) return 1.0f;
-    ShadowState st; st.transmission = 1.0f; st.inVolume = false; st.inVolumeStartT = 0.0f; st.sigmaT = mk3(0.0f, 0.0f, 0.0f);
-    Hit h; h.valid = true; h.opaque = 0; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.inst = 0; h.prim = 0;
-    for (int k = 0; k < count; ++k) {
-        float kt; cand.key(k, kt, h.tri, h.inst);
-        float4 ta, tb, tc; bvh.tri(h.tri, ta, tb, tc);
-        f3 p0, p1, p2; tl_world_triangle(bvh.instances[h.inst], ta, tb, tc, p0, p1, p2);
-        tri_test(p0, p1, p2, ray, sh, h.t, h.u, h.v);                               // recomputes (t, u, v) bit for bit
-        h.prim = __float_as_uint(tb.w);
-        if (shadow_candidate_two_level(s, ray, h, st)) return 0.0f;
-    }
-    if (overflow) {   // more than K candidates: continue behind the K-th with the re-trace loop
-        HitKey lower; lower.have = true; lower.t = h.t; lower.inst = h.inst; lower.prim = h.prim;
-        for (;;) {
-            Hit n = closest_two_level(bvh, s.rootLeaf, s.nodeCount, ray, lower, stack);
-            if (!n.valid) break;
-            if (n.opaque) return 0.0f;
-            if (shadow_candidate_two_level(s, ray, n, st)) return 0.0f;
-            lower.t = n.t; lower.inst = n.inst; lower.prim = n.prim;
-        }
-    }
-    return shadow_finish(ray, st);
-}
-template <class STACK>
-HRT_DEV float shadow_query_two_level(const SceneView& s, const GlobalBvhTl& bvh, const Ray& ray, STACK& stack, uint32_t nodeLoopMin = 0)
-{
-    bool sawNonOpaque;
-    if (any_hit_two_level(bvh, s.rootLeaf, s.nodeCount, ray, stack, sawNonOpaque, nodeLoopMin)) return 0.0f;
-    return sawNonOpaque ? shadow_retrace_two_level(s, bvh, ray, stack) : 1.0f;
-}
-
-// Re-trace form: one closest-hit query per non-opaque candidate (validation megakernel).
-// ALL_OPAQUE: the scene is known (upload-time trait) to hold ForceOpaque instances only: the candidate pass is compiled out.
-template <bool ALL_OPAQUE = false, class BVH, class STACK>
-HRT_DEV float shadow_query(const SceneView& s, const BVH& bvh, f3 worldPos, f3 L, float maxDist, STACK& stack, uint32_t nodeLoopMin = 0)
-{
-    Ray ray = shadow_ray(worldPos, L, maxDist);
-    if constexpr (BVH::kTwoLevel) {
-        if constexpr (ALL_OPAQUE) { bool none; return any_hit_two_level(bvh, s.rootLeaf, s.nodeCount, ray, stack, none, nodeLoopMin) ? 0.0f : 1.0f; }
-        else return shadow_query_two_level(s, bvh, ray, stack, nodeLoopMin);
-    }
-    // Any hit on a ForceOpaque instance commits -> 0, whatever lies in front of it.
-    bool sawNonOpaque;
-    if (any_opaque(bvh, s.rootLeaf, s.nodeCount, ray, stack, sawNonOpaque, nodeLoopMin)) return 0.0f;
-    if (ALL_OPAQUE || !sawNonOpaque) return 1.0f;
-    ShadowState st; st.transmission = 1.0f; st.inVolume = false; st.inVolumeStartT = 0.0f; st.sigmaT = mk3(0.0f, 0.0f, 0.0f);
-    HitKey lower; lower.have = false; lower.t = 0.0f; lower.inst = 0; lower.prim = 0;
-    for (;;) {   // non-opaque candidates, front to back
-        Hit h = closest_any(bvh, s.rootLeaf, s.nodeCount, ray, lower, stack);
-        if (!h.valid) break;
-        if (shadow_candidate(s, ray, h.t, h.tri, h.u, h.v, st)) return 0.0f;
-        lower.have = true; lower.t = h.t; lower.inst = h.inst; lower.prim = h.prim;
-    }
-    return shadow_finish(ray, st);
-}
-
-// Buffered form (wavefront shadow stage): the any-hit pass over opaque triangles also collects the K closest non-opaque
-// candidates, sorted by (t, inst, prim), into a per-lane buffer CAND (LDS columns of (t, triangle)); they are then processed front to
-// back without further traversals. More than K candidates: the re-trace loop continues behind the K-th. Same visiting
-// order as the re-trace form, hence the same result.
-// (t, triangle) of a non-opaque hit into the per-lane buffer of the K smallest keys, kept sorted; `overflow` once a hit did not fit.
-template <int K, class BVH, class CAND>
-HRT_DEV void candidate_insert(const BVH& bvh, CAND& cand, int& count, bool& overflow, float t, uint32_t tri, uint32_t inst, uint32_t prim)
-{
-    int pos = count;
-    if (count == K) {
-        float lt; uint32_t ltri; cand.key(K - 1, lt, ltri);
-        float4 la, lb, lc; bvh.tri(ltri, la, lb, lc);
-        overflow = true;
-        if (!key_less(t, inst, prim, lt, __float_as_uint(la.w), __float_as_uint(lb.w))) return;
-        pos = K - 1;
-    } else ++count;
-    while (pos > 0) {
-        float pt; uint32_t ptri; cand.key(pos - 1, pt, ptri);
-        bool less;
-        if (t != pt) less = t < pt;
-        else { float4 pa, pb, pc; bvh.tri(ptri, pa, pb, pc); less = key_less(t, inst, prim, pt, __float_as_uint(pa.w), __float_as_uint(pb.w)); }
-        if (!less) break;
-        cand.move(pos, pos - 1);
-        --pos;
-    }
-    cand.set(pos, t, tri);
-}
-// The candidates front to back (CalculateRTShadow's per-candidate body), then -- if more than K existed -- the re-trace loop behind the
-// K-th, then the closing Beer-Lambert segment. `cand.key(k, t, tri)` yields the k-th smallest key.
-template <class BVH, class STACK, class CAND>
-HRT_DEV float shadow_resolve_candidates(const SceneView& s, const BVH& bvh, const Ray& ray, const RayShear& sh, int count, bool overflow, const CAND& cand, STACK& stack)
-{
-    if (count == 0) return 1.0f;
-    ShadowState st; st.transmission = 1.0f; st.inVolume = false; st.inVolumeStartT = 0.0f; st.sigmaT = mk3(0.0f, 0.0f, 0.0f);
-    float lastT = 0.0f; uint32_t lastTri = 0;
-    for (int k = 0; k < count; ++k) {
-        float t; uint32_t tri; cand.key(k, t, tri);
-        float4 a, b, c; bvh.tri(tri, a, b, c);
-        float t2, u, v;
-        tri_test(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), ray, sh, t2, u, v);   // recomputes (t, u, v) bit for bit
-        if (shadow_candidate(s, ray, t, tri, u, v, st)) return 0.0f;
-        lastT = t; lastTri = tri;
-    }
-    if (overflow) {   // more than K candidates: continue behind the K-th with the re-trace loop
-        float4 la, lb, lc; bvh.tri(lastTri, la, lb, lc);
-        HitKey lower; lower.have = true; lower.t = lastT; lower.inst = __float_as_uint(la.w); lower.prim = __float_as_uint(lb.w);
-        for (;;) {
-            Hit h = closest_any(bvh, s.rootLeaf, s.nodeCount, ray, lower, stack);
-            if (!h.valid) break;
-            if (h.opaque) return 0.0f;
-            if (shadow_candidate(s, ray, h.t, h.tri, h.u, h.v, st)) return 0.0f;
-            lower.t = h.t; lower.inst = h.inst; lower.prim = h.prim;
-        }
-    }
-    return shadow_finish(ray, st);
-}
-template <int K, class BVH, class STACK, class CAND>
-HRT_DEV float shadow_query_buffered(const SceneView& s, const BVH& bvh, f3 worldPos, f3 L, float maxDist, STACK& stack, CAND& cand, uint32_t nodeLoopMin = 0)
-{
-    Ray ray = shadow_ray(worldPos, L, maxDist);
-    if (!(ray.d.x == ray.d.x && ray.d.y == ray.d.y && ray.d.z == ray.d.z)) return 1.0f;
-    RayShear sh = make_shear(ray.d);
-    f3 inv = traversal_rcp(ray.d), noi = slab_origin_term(ray.o, inv);
-    int sp = 0, count = 0; bool overflow = false;
-    int32_t cur;
-    if (s.nodeCount == 0) { if (s.rootLeaf == 0) return 1.0f; cur = s.rootLeaf; } else cur = 0;
-    for (;;) {
-        while (cur >= 0) {
-            cur = inner_step(bvh, cur, noi, inv, ray.tmin, ray.tmax, stack, sp);
-            if ((uint32_t)__popcll(__ballot(cur >= 0)) < nodeLoopMin) break;
-        }
-        if (cur == kTraversalDone) break;
-        if (cur >= 0) continue;
-        uint32_t enc = (uint32_t)(~cur);
-        uint32_t first = enc >> 2, n = (enc & 3u) + 1u;
-        for (uint32_t i = 0; i < n; ++i) {
-            float4 a, b, c; bvh.tri(first + i, a, b, c);
-            float t, u, v;
-            if (!tri_test(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), ray, sh, t, u, v)) continue;
-            if (__float_as_uint(c.w) & 1u) return 0.0f;                           // opaque instance: committed
-            candidate_insert<K>(bvh, cand, count, overflow, t, first + i, __float_as_uint(a.w), __float_as_uint(b.w));
-        }
-        if (sp == 0) break;
-        cur = stack.pop(--sp);
-    }
-    return shadow_resolve_candidates(s, bvh, ray, sh, count, overflow, cand, stack);
 }
 
 // One light of AccumulateDirectLighting (CommonLighting.hlsli:877-908) in three stages, so that a schedule may run the

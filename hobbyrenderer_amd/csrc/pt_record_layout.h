@@ -46,7 +46,7 @@ HRT_SAME_RECORD(HostTri, GpuTri, 48);
 HRT_SAME_FIELD(HostTri, GpuTri, p0); HRT_SAME_FIELD(HostTri, GpuTri, inst);
 HRT_SAME_FIELD(HostTri, GpuTri, p1); HRT_SAME_FIELD(HostTri, GpuTri, prim);
 HRT_SAME_FIELD(HostTri, GpuTri, p2); HRT_SAME_FIELD(HostTri, GpuTri, flags);
-HRT_FIELD_AT(HostTri, prim, 7 * 4);         // pt_path.h reads word [7] of a triangle record
+HRT_FIELD_AT(HostTri, prim, 7 * 4);         // pt_shadow.h candidate_insert and the leaf loops read the primitive as b.w of a triangle record
 
 // No field has a name on both sides: the device reads five float4 rows (unpack_tri_attr states which word is what), the host names the words.
 HRT_SAME_RECORD(HostTriAttr, GpuTriAttr, 80);

@@ -16,8 +16,10 @@ HRT_DEV float candidate_alpha(const SceneView& s, const HrptMaterialConstants& m
 
 // AlphaTestGrad's alpha (RaytracingCommon.hlsli:112-130) with the synthetic gradients of GetShadowRayGradients (:207-240): ddx = ddy =
 // uvRange * triangleArea / max(dist, 0.1), from the world-space triangle, the hit's barycentrics and the ray origin. Only textures with a
-// mip chain need them (a single-level texture is sampled at level 0 whatever the gradients are).
-HRT_DEV float candidate_alpha_grad(const SceneView& s, const HrptMaterialConstants& mat, f2 uv, const TriVerts& tv, uint32_t tri, float bu, float bv, f3 rayOrigin)
+// mip chain need them (a single-level texture is sampled at level 0 whatever the gradients are): worldTriangle(p0, p1, p2) yields the
+// triangle and is called on that path alone, so every other candidate does not load it.
+template <class TRI>
+HRT_DEV float candidate_alpha_grad(const SceneView& s, const HrptMaterialConstants& mat, f2 uv, const TriVerts& tv, float bu, float bv, f3 rayOrigin, TRI&& worldTriangle)
 {
     float alpha = mat.m_BaseColor[3];
     if (!(mat.m_TextureFlags & HRPT_TEXFLAG_ALBEDO)) return alpha;
@@ -27,8 +29,7 @@ HRT_DEV float candidate_alpha_grad(const SceneView& s, const HrptMaterialConstan
     const uint8_t* texels = t.texels;
     if (!texels) return alpha * 0.0f;
     if (t.mipCount <= 1u) return alpha * sample_texture_level(texels, t.format, (int)t.w, (int)t.h, 0u, mat.m_AlbedoSamplerIndex, uv).w;
-    const GpuTri& g = s.tris[tri];
-    const f3 p0 = mk3(g.p0), p1 = mk3(g.p1), p2 = mk3(g.p2);
+    f3 p0, p1, p2; worldTriangle(p0, p1, p2);
     const float w0 = (1.0f - bu) - bv;
     const f3 hitPos = (p0 * w0 + p1 * bu) + p2 * bv;
     const float dist = length(hitPos - rayOrigin);

@@ -114,11 +114,14 @@ struct LdsStack {
     }
 };
 // per-lane buffer of the K closest non-opaque shadow candidates: (t, triangle) of entry k at base[(k*2 + {0,1}) * kBlock];
-// the barycentrics are recomputed from the triangle when the candidate is processed (same test => same bits)
+// the barycentrics are recomputed from the triangle when the candidate is processed (same test => same bits).
+// One interface for the three buffers (pt_shadow.h candidate_insert / shadow_resolve_candidates): key and set carry an instance, which the
+// two-column buffers neither store nor yield -- the triangle record of a flat tree names it.
 struct LdsCandidates {
     int32_t* base;
     HRT_DEV void key(int k, float& t, uint32_t& tri) const { t = __int_as_float(base[(k * 2 + 0) * kBlock]); tri = (uint32_t)base[(k * 2 + 1) * kBlock]; }
-    HRT_DEV void set(int k, float t, uint32_t tri) { base[(k * 2 + 0) * kBlock] = __float_as_int(t); base[(k * 2 + 1) * kBlock] = (int32_t)tri; }
+    HRT_DEV void key(int k, float& t, uint32_t& tri, uint32_t&) const { key(k, t, tri); }
+    HRT_DEV void set(int k, float t, uint32_t tri, uint32_t) { base[(k * 2 + 0) * kBlock] = __float_as_int(t); base[(k * 2 + 1) * kBlock] = (int32_t)tri; }
     HRT_DEV void move(int dst, int src) { base[(dst * 2 + 0) * kBlock] = base[(src * 2 + 0) * kBlock]; base[(dst * 2 + 1) * kBlock] = base[(src * 2 + 1) * kBlock]; }
 };
 // ... with the instance next to the triangle (two-level structure: the triangle index is per mesh): entry k at base[(k*3 + {0,1,2}) * kBlock]
@@ -131,7 +134,7 @@ struct LdsCandidates3 {
 // candidate list of one shadow ray in global memory (written by wf_extend<ANYHIT> when the ray finishes, read by wf_shadow)
 struct GlobalCandidates {
     const uint2* base;
-    HRT_DEV void key(int k, float& t, uint32_t& tri) const { uint2 v = base[k]; t = __uint_as_float(v.x); tri = v.y; }
+    HRT_DEV void key(int k, float& t, uint32_t& tri, uint32_t&) const { uint2 v = base[k]; t = __uint_as_float(v.x); tri = v.y; }
 };
 // BVH copy in LDS; W = node width (2: GpuNode, 4: GpuNode4)
 template <int W>

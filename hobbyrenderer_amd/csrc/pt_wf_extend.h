@@ -363,7 +363,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHADOW ?
                     if (finite) {
                         if (blocked) vis = 0.0f;
                         else if (candCount > 0) {
-                            if constexpr (TL) vis = shadow_retrace_two_level(s, gbvh, r, stack);
+                            if constexpr (TL) vis = shadow_retrace(s, gbvh, r, stack);
                             else if (LDS_BVH) vis = shadow_resolve_candidates(s, lbvh, r, sh, candCount, candOverflow, cand, stack);
                             else vis = shadow_resolve_candidates(s, gbvh, r, sh, candCount, candOverflow, cand, stack);
                         }

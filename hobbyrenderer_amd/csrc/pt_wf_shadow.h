@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void wf_shadow_rays(WfArgs a, HrptPathTrace
 template <bool LDS_BVH, int DEPTH, int W, bool DIRONLY, int MODE, int TL = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 2 && TL == 0 ? 4 : ((MODE == 1 || TL != 0) ? 3 : 1)))) void wf_shadow(WfArgs a, HrptPathTracerConstants cb, int bounce)
 {
-    static_assert(!TL || (!LDS_BVH && W == 4 && (MODE == kShadowOpaque || MODE == kShadowSlim)), "two-level structure: opaque any-hit query over the global tree");
+    static_assert(!TL || (!LDS_BVH && W == 4 && (MODE == kShadowOpaque || MODE == kShadowSlim)), "two-level structure: the opaque / slim modes over the global tree (any-hit query, or with TL == 2 the buffered candidate query)");
     static_assert(W != kQuantisedTree || (!LDS_BVH && !TL), "quantised nodes: flat tree in global memory");
     constexpr bool NONOPAQUE = MODE == kShadowBuffered || MODE == kShadowResolve;
     constexpr bool SLIM = MODE == kShadowSlim;
@@ -77,6 +77,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
     const uint32_t wavesPerBlock = kBlock / 64, lane = lane_id();
     const uint32_t gw = uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), totalWaves = gridDim.x * wavesPerBlock;
     unsigned int nRays = 0, nSamples = 0, nRadiance = 0, nSkipped16 = 0;
+    // the query of kShadowOpaque / kShadowSlim (no ForceNonOpaque instance in a flat scene): the any-hit pass over the LDS or the global tree;
+    // TL == 2: the buffered query over the two-level structure, whose instances may be non-opaque
+    auto opaque_query = [&](f3 origin, f3 L, float maxDist) {
+        if (LDS_BVH) return shadow_query<true>(s, lbvh, origin, L, maxDist, stack);
+        else if constexpr (TL == 2) return shadow_query_two_level_buffered<kTwoLevelCandidates>(s, gbvh, shadow_ray(origin, L, maxDist), stack, cand3);
+        else return shadow_query<true>(s, gbvh, origin, L, maxDist, stack);
+    };
     // one shadow-queue entry: every light sample of one path vertex
     auto process = [&](uint32_t e) {
                 HRT_PHASE(PH_SHADOW_ENTRY);
@@ -91,10 +98,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
                     HrptGPULight l = load_light(s, 0u);
                     f3 L; float maxDist;
                     if (!nee_direction<true>(l, N, origin, sunDir, cb.m_CosSunAngularRadius, ux, uy, L, maxDist)) return;
-                    float shadow;
-                    if (LDS_BVH) shadow = shadow_query<true>(s, lbvh, origin, L, maxDist, stack);
-                    else if constexpr (TL == 2) shadow = shadow_query_two_level_buffered<kTwoLevelCandidates>(s, gbvh, shadow_ray(origin, L, maxDist), stack, cand3);
-                    else shadow = shadow_query<true>(s, gbvh, origin, L, maxDist, stack);
+                    const float shadow = opaque_query(origin, L, maxDist);
                     ++nRays;
                     if (shadow != 0.0f) {
                         const float4 th = a.primary ? make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(slot)) : a.b.thr[a.shadowParity][slot];
@@ -157,11 +161,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
                         // (no descent threshold here: without lane refill it only costs: config 2 shadow +3 %, config 4 +2.5 %)
                         if (LDS_BVH) shadow = shadow_query_buffered<kShadowCandidates>(s, lbvh, origin, L, maxDist, stack, cand);
                         else shadow = shadow_query_buffered<kShadowCandidates>(s, gbvh, origin, L, maxDist, stack, cand);
-                    } else {
-                        if (LDS_BVH) shadow = shadow_query<true>(s, lbvh, origin, L, maxDist, stack);       // kShadowOpaque: no ForceNonOpaque instance in the scene
-                        else if constexpr (TL == 2) shadow = shadow_query_two_level_buffered<kTwoLevelCandidates>(s, gbvh, shadow_ray(origin, L, maxDist), stack, cand3);
-                    else shadow = shadow_query<true>(s, gbvh, origin, L, maxDist, stack);
-                    }
+                    } else shadow = opaque_query(origin, L, maxDist);
                     ++nRays;
                     if (shadow != 0.0f) {   // an occluded sample contributes +0: its BRDF x radiance evaluation is skipped
                         HRT_PHASE(PH_SHADOW_CONTRIB);

@@ -69,3 +69,25 @@ def test_traversal_kernels_keep_their_occupancy(kernels):
     assert seen >= 40
     # the slim / opaque shadow kernels of LDS trees: seven waves
     assert _waves(kernels["wf_shadow<true, 16, 2, true, 3, 0>"]["vgpr"]) >= 7
+
+
+# scratch bytes of wf_shadow<LDS_BVH, DEPTH, W, false, kShadowResolve, 0> in the build before pt_shadow.h existed: (LDS_BVH, DEPTH, W) -> bytes
+RESOLVE_SCRATCH = {
+    (False, 8, 2): 20, (False, 16, 2): 20, (False, 16, 4): 44, (False, 16, 5): 16, (False, 32, 2): 28, (False, 32, 4): 44, (False, 32, 5): 28,
+    (False, 64, 2): 28, (False, 64, 4): 44, (False, 64, 5): 28,
+    (True, 8, 2): 28, (True, 16, 2): 28, (True, 16, 4): 52, (True, 32, 2): 28, (True, 32, 4): 60, (True, 64, 2): 28, (True, 64, 4): 60,
+}
+
+
+def test_shadow_resolve_variants_keep_their_spill_budget(kernels):
+    """wf_shadow's resolve variants (MODE 2) are compiled into 128 VGPRs for the fourth wave and spill a few registers; how many depends on
+    how shadow_resolve_candidates (pt_shadow.h) is spelled, and with other spellings the glass config lost 0.5 to 2 %. No variant may take
+    more scratch than it did before that function moved to pt_shadow.h."""
+    seen = set()
+    for name, k in kernels.items():
+        m = re.match(r"wf_shadow<(true|false), (\d+), (\d), false, 2, 0>", name)
+        if m:
+            key = (m.group(1) == "true", int(m.group(2)), int(m.group(3)))
+            seen.add(key)
+            assert k["vgpr"] <= 128 and k["scratch"] <= RESOLVE_SCRATCH[key], (name, k)
+    assert seen == set(RESOLVE_SCRATCH)

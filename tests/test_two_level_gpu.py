@@ -416,10 +416,84 @@ def test_ray_queries_over_a_two_level_scene_with_non_opaque_instances(luts):
     assert np.array_equal(vf["t"].view(np.uint32), vt["t"].view(np.uint32))
 
 
+def _mask_chain_scene(luts, chain):
+    """Five instances of one upright quad mesh over a floor quad, staggered in depth and rotated a little: a MASK one whose 16 x 16 albedo
+    texture has its full mip chain (random alpha, every level drawn on its own; `chain=False` keeps level 0 only), a glass one, a
+    stochastic-alpha one and two opaque ones; a point light behind them."""
+    rng = np.random.default_rng(31)
+    b = scenes.SceneBuilder()
+    floor = b.add_mesh(*scenes.generate_floor_quad())
+    pos = [(0.5, -0.5, 0.0), (-0.5, -0.5, 0.0), (-0.5, 0.5, 0.0), (0.5, 0.5, 0.0)]
+    quad = b.add_mesh(*scenes._faces_to_mesh([(pos, (0, 0, -1), (-1, 0, 0), 1.0, [(0, 1), (1, 1), (1, 0), (0, 0)])]))
+    levels = []
+    for w, h in S.mip_dims(16, 16, 5):
+        lv = np.full((h, w, 4), 200, np.uint8)
+        lv[..., 3] = rng.integers(0, 256, (h, w))
+        levels.append(lv)
+    tex = S.Texture(np.concatenate([lv.reshape(-1) for lv in levels]), 16, 16, S.TEXTURE_FORMAT_RGBA8_UNORM, 5) if chain \
+        else S.Texture(levels[0], 16, 16, S.TEXTURE_FORMAT_RGBA8_UNORM, 1)
+    mats = [b.add_material(m_BaseColor=(1, 1, 1, 1), m_TextureFlags=S.TEXFLAG_ALBEDO, m_AlbedoTextureIndex=b.add_texture(tex),
+                           m_AlphaMode=S.ALPHA_MODE_MASK, m_AlphaCutoff=0.5),
+            b.add_material(m_BaseColor=(0.9, 0.95, 1.0, 1.0), m_RoughnessMetallic=(0.05, 0.0), m_TransmissionFactor=0.9, m_IOR=1.5,
+                           m_AlphaMode=S.ALPHA_MODE_BLEND, m_SigmaA=(0.4, 0.1, 0.05), m_IsThinSurface=0),
+            b.add_material(m_BaseColor=(0.6, 0.8, 0.6, 0.4), m_AlphaMode=S.ALPHA_MODE_BLEND),
+            b.add_material(m_BaseColor=(0.7, 0.2, 0.15, 1)), b.add_material(m_BaseColor=(0.2, 0.3, 0.8, 1))]
+    b.add_instance(floor, b.add_material(m_BaseColor=(0.8, 0.8, 0.8, 1)), scenes._mat((14, 1, 14), None, (0, 0, 2)))
+    for k, (m, x, z) in enumerate(zip(mats, (0.0, 0.5, -0.5, 1.1, -1.2), (0.0, 0.5, 0.9, 1.3, 0.4))):
+        a = 0.25 * (k - 2)
+        roty = np.array([[math.cos(a), 0, -math.sin(a)], [0, 1, 0], [math.sin(a), 0, math.cos(a)]])
+        b.add_instance(quad, m, scenes._mat((1.6 - 0.2 * k, 1.2, 1), roty, (x, 0.62, z)))
+    b.add_light(S.LIGHT_POINT, position=(0.0, 1.3, 3.2), intensity=40.0)        # behind the quads: their shadows fall towards the camera
+    return b.finalize(luts)
+
+
+def test_two_level_mask_instance_with_a_mip_chain(luts):
+    """A MASK material whose albedo texture has a mip chain, on a non-opaque instance of a two-level scene: the shadow candidate takes the
+    gradient-sampled alpha test (GetShadowRayGradients over the instance's world-space triangle). Ray queries and frames equal the flat
+    structure's bit for bit, and the chain is known to have been used: the level-0-only texture gives other visibilities."""
+    from hobbyrenderer_amd.native import PathTracerContext
+    rng = np.random.default_rng(6)
+    m = 400
+    rays = np.zeros(m, S.Ray)
+    rays["origin"] = (rng.random((m, 3)) * [1.6, 1.0, 2.5] + [-0.8, 0.1, -3.0]).astype(np.float32)
+    d = (rng.random((m, 3)) * [1.4, 1.0, 0.0] + [-0.7, 0.12, 0.0]).astype(np.float32) - rays["origin"]      # through the MASK quad
+    rays["direction"] = d / np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
+    rays["tmax"] = np.where(rng.random(m) < 0.6, 1e10, 1.0 + rng.random(m) * 5).astype(np.float32)
+    rays["rng"] = rng.integers(0, 2 ** 32, m, dtype=np.uint64).astype(np.uint32)
+    vis = {}
+    view, pos = scenes.planar_view(64, 48, position=(0.0, 2.0, -2.6), pitch=0.55, aspect=64 / 48)
+    frames = {}
+    for chain in (True, False):
+        sc = _mask_chain_scene(luts, chain)
+        out = {}
+        for mode in (S.ACCEL_FLAT, S.ACCEL_TWO_LEVEL):
+            c = PathTracerContext(0)
+            try:
+                c.set_acceleration_structure(mode)
+                c.upload_scene(sc)
+                assert c.build_info().structure == mode
+                out[mode] = (c.trace_rays(rays), c.trace_rays(rays, shadow=True), c.trace_rays(rays, shadow=True, thread_per_ray=True))
+            finally:
+                c.close()
+        (hf, vf, pf), (ht, vt, pt) = out[S.ACCEL_FLAT], out[S.ACCEL_TWO_LEVEL]
+        assert (hf["rng"] != rays["rng"]).any() and ((vf["t"] > 0) & (vf["t"] < 1)).any()        # stochastic alpha drew numbers; partial visibility through glass
+        for f in ("hit", "instance", "primitive", "rng"):
+            assert np.array_equal(hf[f], ht[f]), f
+        for f in ("t", "u", "v"):
+            assert np.array_equal(hf[f].view(np.uint32), ht[f].view(np.uint32)), f
+        assert np.array_equal(vf["t"].view(np.uint32), vt["t"].view(np.uint32))
+        assert vf.tobytes() == pf.tobytes() and vt.tobytes() == pt.tobytes()
+        vis[chain] = vt["t"].copy()
+        _same_frames(luts, sc, 64, 48, 2, 3, view, pos)
+        frames[chain] = _render(luts, sc, S.ACCEL_TWO_LEVEL, 64, 48, 2, 3, view, pos)[0]
+    assert (vis[True] != vis[False]).any(), "the mip chain did not influence any shadow ray: the gradient-sampled alpha test was not exercised"
+    assert not np.array_equal(frames[True], frames[False]), "the mip chain did not influence the frame's shadows"
+
+
 @pytest.mark.parametrize("kind", ["opaque-three-lights", "mask+glass"])
 def test_megakernel_and_thread_per_ray_walk_the_two_level_structure(luts, kind):
     """The validation megakernel (HRPT_FRAME_MEGAKERNEL) and the thread-per-ray query kernel (HRPT_RAYS_THREAD_PER_RAY) traverse the two-level
-    structure too (closest_two_level / shadow_query_two_level with a private stack): wavefront == megakernel on a two-level scene, and the
+    structure too (closest_two_level / shadow_query with a private stack): wavefront == megakernel on a two-level scene, and the
     persistent ray-query kernel == the thread-per-ray kernel -- the cross-checks every other path has. hrpt_selftest_bvh stays a flat-structure
     check (its boxes are per mesh, in object space) and says so."""
     from hobbyrenderer_amd.native import PathTracerContext, HrptError
