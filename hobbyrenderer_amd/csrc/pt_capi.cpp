@@ -63,6 +63,7 @@ try {
     if (const char* e = getenv("HRPT_WF_FUSED_BOUNCE0")) c->wf.knobs.noFusedBounce0 = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_SHADE_LDS_TABLES")) c->wf.knobs.noShadeLdsTables = atoi(e) == 0;
     if (const char* e = getenv("HRPT_WF_NODE_LOOP_MIN")) c->wf.knobs.nodeLoopMin = (uint32_t)atoi(e);
+    if (const char* e = getenv("HRPT_RADIANCE_BATCH")) c->wf.knobs.radianceBatch = (uint32_t)atoi(e);
     if (const char* e = getenv("HRPT_BLOOM_FUSED_TAIL")) { const int v = atoi(e); c->bloomTailTexels = v == 1 ? 8192u : (v > 0 ? (uint32_t)v : 0u); }
     if (const char* e = getenv("HRPT_UPSCALE_STAGED")) c->upscaleStaged = atoi(e) != 0;
     *out = c;

@@ -1,5 +1,5 @@
-// pt_capi_render.cpp -- what traces rays: hrpt_render, the first-hit G-buffer and motion vectors, hrpt_trace_rays, the resolves and
-// hrpt_allgather.
+// pt_capi_render.cpp -- what traces rays: hrpt_render, the first-hit G-buffer and motion vectors, hrpt_trace_rays, hrpt_trace_radiance, the
+// resolves and hrpt_allgather.
 #include "pt_capi_internal.h"
 
 using namespace hrt;
@@ -287,6 +287,48 @@ try {
     if (e != hipSuccess) return fail(c, hip_status(e), std::string("hrpt_trace_rays: ") + hipGetErrorString(e));
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_trace_rays"); }
+
+// Path-traced radiance along the caller's rays: the checks of hrpt_render that apply (bounces, lights), then the wavefront pipeline between
+// wf_raygen_rays and wf_store_radiance, or one thread per ray. No events, no counters, no fallback count: HrptStats keeps describing renders.
+int hrpt_trace_radiance(HrptContext* c, const HrptRay* rays, float* radiance4, uint64_t count, const HrptPathTracerConstants* constants, uint32_t flags)
+try {
+    if (!c) return HRPT_ERR_INVALID_ARGUMENT;
+    if (!c->haveScene) return fail(c, HRPT_ERR_NO_SCENE, "hrpt_trace_radiance: no scene uploaded");
+    if (!constants) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: null constants");
+    if (flags & ~(HRPT_RADIANCE_DEVICE_POINTERS | HRPT_RADIANCE_THREAD_PER_RAY | HRPT_RADIANCE_ACCUMULATE)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: unknown flags");
+    if (constants->m_MaxBounces > 64u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: m_MaxBounces above 64 (one kernel sequence is launched per bounce)");
+    if (constants->m_LightCount > c->view.lightCount) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: m_LightCount exceeds the scene's light buffer");
+    if (count == 0) return HRPT_OK;
+    if (!rays || !radiance4) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: null array");
+    if (count > (1ull << 31)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: too many rays in one call");
+    const bool wavefront = !(flags & HRPT_RADIANCE_THREAD_PER_RAY) && wavefront_supports(c->view, *constants);
+    if (!wavefront && c->view.instances && c->traits.twoLevelStackNeed > 64u)
+        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: this two-level structure is deeper than the thread-per-ray kernel's 64-entry stack");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool accumulate = (flags & HRPT_RADIANCE_ACCUMULATE) != 0;
+    auto trace = [&](const HrptRay* dr, float4* dl) -> hipError_t {
+        if (!wavefront) return launch_radiance_rays(c->view, *constants, dr, dl, count, accumulate, c->stream);
+        std::string werr;
+        c->wf.shadeInstances = (uint32_t)c->keptInstances.size(); c->wf.shadeMaterials = (uint32_t)c->keptMaterials.size();    // as hrpt_render sets them
+        hipError_t te = wavefront_radiance(c->wf, c->view, c->traits, *constants, dr, dl, count, accumulate, c->stream, werr);
+        if (te != hipSuccess) c->err = "hrpt_trace_radiance: " + werr;
+        return te;
+    };
+    if (flags & HRPT_RADIANCE_DEVICE_POINTERS) {
+        HIP_TRY(c, trace(rays, reinterpret_cast<float4*>(radiance4)));
+        return HRPT_OK;
+    }
+    DeviceBuffer<HrptRay> dRays; DeviceBuffer<float4> dRadiance;
+    hipError_t e = dRays.alloc(count * sizeof(HrptRay));
+    if (e == hipSuccess) e = dRadiance.alloc(count * sizeof(float4));
+    if (e == hipSuccess) e = hipMemcpyAsync(dRays, rays, count * sizeof(HrptRay), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && accumulate) e = hipMemcpyAsync(dRadiance, radiance4, count * sizeof(float4), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = trace(dRays, dRadiance);
+    if (e == hipSuccess) e = hipMemcpyAsync(radiance4, dRadiance, count * sizeof(float4), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, hip_status(e), std::string("hrpt_trace_radiance: ") + hipGetErrorString(e));
+    return HRPT_OK;
+} catch (...) { return caught(c, "hrpt_trace_radiance"); }
 
 int hrpt_resolve_columns_device(HrptContext* c, const float* shardsDevice, float* accumulationDevice, float* outputDevice, uint32_t width, uint32_t height, uint32_t ranks, void* stream)
 try {

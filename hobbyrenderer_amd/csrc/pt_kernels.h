@@ -131,6 +131,11 @@ hipError_t launch_animate(const anim::Tables& tables, const float* times, const 
 // Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
 hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
 
+// Path-traced radiance along a caller's rays (hrpt_trace_radiance), validation path: one thread per ray, the megakernel's bounce loop from the
+// ray's record; radiance[i] = (L, 1), or with `accumulate` (old.rgb + L, old.w + 1). Device arrays.
+hipError_t launch_radiance_rays(const SceneView& scene, const HrptPathTracerConstants& constants, const HrptRay* rays, float4* radiance, uint64_t count,
+                                bool accumulate, hipStream_t stream);
+
 // The flat 4-wide tree in its 64-byte quantised form (pt_scene_records.h GpuNodeQ): out[i] from nodes4[i]. leafArea (two zeroed doubles, or null)
 // receives the summed surface area of the leaf boxes before / after the rounding: what the looser boxes will cost in triangle tests.
 hipError_t launch_quantise_nodes(const GpuNode4* nodes4, uint32_t count, GpuNodeQ* out, double* leafArea, hipStream_t stream);

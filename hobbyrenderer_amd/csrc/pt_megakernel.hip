@@ -26,6 +26,48 @@ HRT_DEV unsigned long long wave_sum(unsigned int v)
     return x;
 }
 
+// The bounce loop of PathTracer_CSMain (PathTracer.hlsl:90-330) for one path from the state `ps` holds (init_path, or a caller's ray record):
+// what pt_megakernel and pt_radiance_kernel both run. Leaves the path's radiance in ps.radiance; nClosest / nShadow count its queries.
+template <class BVH>
+HRT_DEV void trace_path(const SceneView& s, const BVH& bvh, const HrptPathTracerConstants& cb, PathState& ps, PrivateStack& stack,
+                        unsigned int& nClosest, unsigned int& nShadow)
+{
+    int maxBounces = (int)cb.m_MaxBounces;
+    for (int bounce = 0; bounce < maxBounces; ++bounce) {
+        Hit hit;
+        ++nClosest;
+        if (trace_standard(s, bvh, ps.ray, ps.rng, stack, hit)) {
+            SurfaceCarry carry;
+            f3 totalDiffuse = mk3(0.0f, 0.0f, 0.0f), totalSpecular = mk3(0.0f, 0.0f, 0.0f);
+            f3 neeThroughput;
+            const f3 sunDir = mk3(cb.m_SunDirection[0], cb.m_SunDirection[1], cb.m_SunDirection[2]);
+            const float sunIntensity = s.lights[0].m_Intensity;                  // g_Lights[0], PathTracer.hlsl:137 (quirk kept)
+            SurfaceOutcome oc = shade_surface_a<true, true, false>(s, GlobalShadeTables{ s }, cb, ps, hit, carry, [&](uint32_t li, float ux, float uy) {
+                HrptGPULight l = load_light(s, li);
+                f3 L; float maxDist;
+                if (!nee_direction<false>(l, carry.N, carry.worldPos, sunDir, cb.m_CosSunAngularRadius, ux, uy, L, maxDist)) return;
+                ++nShadow;
+                float shadow = shadow_query(s, bvh, carry.worldPos, L, maxDist, stack);
+                if (shadow != 0.0f) {                                              // an occluded sample contributes +0
+                    f3 dif, spec;
+                    nee_contribution<false>(s, l, nee_lighting(carry.N, carry.V, carry.baseColor, carry.roughness, carry.metallic, carry.ior),
+                                            carry.worldPos, sunDir, sunIntensity, L, dif, spec);
+                    totalDiffuse = totalDiffuse + dif * shadow;
+                    totalSpecular = totalSpecular + spec * shadow;
+                }
+            });
+            if (oc == SURFACE_TRANSMITTED) continue;
+            neeThroughput = ps.throughput;
+            f3 dsum = totalDiffuse + (bounce == 0 ? totalSpecular : mk3(0.0f, 0.0f, 0.0f));
+            ps.radiance = ps.radiance + neeThroughput * dsum;                   // PathTracer.hlsl:261
+            if (!shade_surface_b(ps, carry, bounce)) break;
+        } else {
+            miss_sky(s, cb, ps, bounce);
+            break;
+        }
+    }
+}
+
 // TL: the scene holds the two-level structure (SceneView::instances): the same shader over closest_two_level / any_hit_two_level (shadow_query)
 // (pt_traverse.h, pt_shadow.h), so that the two-level kernels of the wavefront pipeline keep the wavefront == megakernel cross-check every other
 // path has. Private 64-entry stack: scenes whose two-level stack need is larger are refused by hrpt_render.
@@ -45,40 +87,7 @@ __global__ __launch_bounds__(64) void pt_megakernel(SceneView s, HrptPathTracerC
         if constexpr (TL) { bvh.nodes = s.nodes4; bvh.tris = s.tris; bvh.instances = s.instances; } else { bvh.nodes = s.nodes; bvh.tris = s.tris; }
         PrivateStack stack;
         PathState ps; init_path(ps, cb, px, py);
-        int maxBounces = (int)cb.m_MaxBounces;
-        for (int bounce = 0; bounce < maxBounces; ++bounce) {
-            Hit hit;
-            ++nClosest;
-            if (trace_standard(s, bvh, ps.ray, ps.rng, stack, hit)) {
-                SurfaceCarry carry;
-                f3 totalDiffuse = mk3(0.0f, 0.0f, 0.0f), totalSpecular = mk3(0.0f, 0.0f, 0.0f);
-                f3 neeThroughput;
-                const f3 sunDir = mk3(cb.m_SunDirection[0], cb.m_SunDirection[1], cb.m_SunDirection[2]);
-                const float sunIntensity = s.lights[0].m_Intensity;                  // g_Lights[0], PathTracer.hlsl:137 (quirk kept)
-                SurfaceOutcome oc = shade_surface_a<true, true, false>(s, GlobalShadeTables{ s }, cb, ps, hit, carry, [&](uint32_t li, float ux, float uy) {
-                    HrptGPULight l = load_light(s, li);
-                    f3 L; float maxDist;
-                    if (!nee_direction<false>(l, carry.N, carry.worldPos, sunDir, cb.m_CosSunAngularRadius, ux, uy, L, maxDist)) return;
-                    ++nShadow;
-                    float shadow = shadow_query(s, bvh, carry.worldPos, L, maxDist, stack);
-                    if (shadow != 0.0f) {                                              // an occluded sample contributes +0
-                        f3 dif, spec;
-                        nee_contribution<false>(s, l, nee_lighting(carry.N, carry.V, carry.baseColor, carry.roughness, carry.metallic, carry.ior),
-                                                carry.worldPos, sunDir, sunIntensity, L, dif, spec);
-                        totalDiffuse = totalDiffuse + dif * shadow;
-                        totalSpecular = totalSpecular + spec * shadow;
-                    }
-                });
-                if (oc == SURFACE_TRANSMITTED) continue;
-                neeThroughput = ps.throughput;
-                f3 dsum = totalDiffuse + (bounce == 0 ? totalSpecular : mk3(0.0f, 0.0f, 0.0f));
-                ps.radiance = ps.radiance + neeThroughput * dsum;                   // PathTracer.hlsl:261
-                if (!shade_surface_b(ps, carry, bounce)) break;
-            } else {
-                miss_sky(s, cb, ps, bounce);
-                break;
-            }
-        }
+        trace_path(s, bvh, cb, ps, stack, nClosest, nShadow);
         // accumulate + resolve, PathTracer.hlsl:332-339
         size_t idx = (size_t)py * imageWidth + px;
         float4 accum = make_float4(ps.radiance.x, ps.radiance.y, ps.radiance.z, 1.0f);
@@ -96,6 +105,42 @@ __global__ __launch_bounds__(64) void pt_megakernel(SceneView s, HrptPathTracerC
         atomicAdd(&shard->shadowRays, sh);
         atomicAdd(&shard->paths, pa);
     }
+}
+
+// hrpt_trace_radiance, validation path (HRPT_RADIANCE_THREAD_PER_RAY, and scenes the wavefront pipeline does not take): one thread per ray runs
+// trace_path from the caller's record -- origin, direction as given, tmin, RNG state; unbounded, throughput 1, outside any medium -- and
+// leaves the radiance by store_ray_radiance. No counters: HrptStats describes renders.
+template <bool TL>
+__global__ __launch_bounds__(64) void pt_radiance_kernel(SceneView s, HrptPathTracerConstants cb, const HrptRay* __restrict__ rays,
+                                                         float4* __restrict__ radiance, uint64_t count, uint32_t accumulate)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const HrptRay r = rays[i];
+    PathState ps;
+    ps.ray.o = mk3(r.origin[0], r.origin[1], r.origin[2]); ps.ray.d = mk3(r.direction[0], r.direction[1], r.direction[2]);
+    ps.ray.tmin = r.tmin; ps.ray.tmax = 1e10f;
+    ps.rng = r.rng;
+    ps.throughput = mk3(1.0f, 1.0f, 1.0f); ps.radiance = mk3(0.0f, 0.0f, 0.0f);
+    ps.inVolume = false; ps.interiorIOR = 1.0f; ps.sigmaA = mk3(0.0f, 0.0f, 0.0f); ps.sigmaS = mk3(0.0f, 0.0f, 0.0f);
+    const bool traced = all_finite(ps.ray.o, ps.ray.d) && (r.tmin - r.tmin) == 0.0f;
+    if (traced) {
+        typename std::conditional<TL, GlobalBvhTl, GlobalBvh>::type bvh;
+        if constexpr (TL) { bvh.nodes = s.nodes4; bvh.tris = s.tris; bvh.instances = s.instances; } else { bvh.nodes = s.nodes; bvh.tris = s.tris; }
+        PrivateStack stack;
+        unsigned int nClosest = 0, nShadow = 0;
+        trace_path(s, bvh, cb, ps, stack, nClosest, nShadow);
+    }
+    store_ray_radiance(radiance + i, ps.radiance, traced, accumulate != 0u);
+}
+hipError_t launch_radiance_rays(const SceneView& scene, const HrptPathTracerConstants& constants, const HrptRay* rays, float4* radiance, uint64_t count,
+                                bool accumulate, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    const dim3 grid((unsigned)((count + 63) / 64));
+    if (scene.instances) hipLaunchKernelGGL(pt_radiance_kernel<true>, grid, dim3(64), 0, stream, scene, constants, rays, radiance, count, accumulate ? 1u : 0u);
+    else hipLaunchKernelGGL(pt_radiance_kernel<false>, grid, dim3(64), 0, stream, scene, constants, rays, radiance, count, accumulate ? 1u : 0u);
+    return hipGetLastError();
 }
 
 // First-hit G-buffer, validation path (hrpt_render_gbuffer with HRPT_FRAME_MEGAKERNEL): one thread per pixel, 8x8 pixel tile per wave like

@@ -332,6 +332,19 @@ HRT_DEV bool shade_surface_b(PathState& ps, const SurfaceCarry& c, int bounce)
     return ld.spec ? lobe_specular(ps, c.worldPos, c.N, c.V, c.F0, c.roughness, ld) : lobe_diffuse(ps, c.worldPos, c.N, c.baseColor, c.metallic, ld);
 }
 
+// What hrpt_trace_radiance leaves in a ray's slot: (L, 1), or with `accumulate` (old.rgb + L, old.w + 1) -- the addition of
+// PathTracer.hlsl:332-337 for an index above 0. A ray that was not traced (non-finite record) stores zeros, or with `accumulate` nothing.
+HRT_DEV void store_ray_radiance(float4* slot, f3 L, bool traced, bool accumulate)
+{
+    float4 cur = traced ? make_float4(L.x, L.y, L.z, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (accumulate) {
+        if (!traced) return;
+        const float4 prev = *slot;
+        cur.x += prev.x; cur.y += prev.y; cur.z += prev.z; cur.w += prev.w;
+    }
+    *slot = cur;
+}
+
 // PathTracer.hlsl:315-328
 HRT_DEV void miss_sky(const SceneView& s, const HrptPathTracerConstants& cb, PathState& ps, int bounce)
 {

@@ -28,6 +28,8 @@ struct WavefrontState {
     size_t traceSpillBytes = 0;
     DeviceBuffer<void> gbPool;         // queue pool of hrpt_render_gbuffer calls the render's pool is too small for (never rendered, or a smaller tile)
     size_t gbPoolBytes = 0;
+    DeviceBuffer<void> radPool;        // the same for hrpt_trace_radiance batches
+    size_t radPoolBytes = 0;
     // start/stop event pairs around every timed launch; kind[i] = its KernelClass
     std::vector<hipEvent_t> events;
     std::vector<uint8_t> kind;
@@ -60,6 +62,10 @@ hipError_t wavefront_trace_rays(WavefrontState& st, const SceneView& scene, cons
 hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
                              float4* const* planes, uint32_t planeMask, uint32_t width, TileRect rect, hipStream_t stream, std::string& error,
                              const MotionArgs* motion = nullptr);
+// hrpt_trace_radiance: radiance[i] = (L, 1) -- or, accumulate, (old.rgb + L, old.w + 1) -- of the path that starts as rays[i], by the render's
+// kernels between wf_raygen_rays and wf_store_radiance (device arrays). Leaves the statistics, the plan and the timing state of renders alone.
+hipError_t wavefront_radiance(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
+                              const HrptRay* rays, float4* radiance, uint64_t count, bool accumulate, hipStream_t stream, std::string& error);
 void wavefront_release(WavefrontState& st);
 void wavefront_collect_timing(WavefrontState& st);   // call after the stream is synchronised; folds pending events into kernelMs
 void wavefront_reset_timing(WavefrontState& st);

@@ -252,6 +252,7 @@ void wavefront_release(WavefrontState& st)
     st.spill.reset(); st.spillBytes = 0;
     st.traceSpill.reset(); st.traceSpillBytes = 0;
     st.gbPool.reset(); st.gbPoolBytes = 0;
+    st.radPool.reset(); st.radPoolBytes = 0;
     for (auto* events : { &st.events, &st.forkEvents, &st.joinEvents }) { for (hipEvent_t e : *events) (void)hipEventDestroy(e); events->clear(); }
     st.eventsUsed = 0;
     if (st.auxStream) (void)hipStreamDestroy(st.auxStream);
@@ -428,6 +429,45 @@ bool prepare_overlap(WavefrontState& st, int maxBounces)
     }
     return true;
 }
+// The bounces of one batch whose path queue 0 is filled (or, plan.fusedPrimary, derived by the bounce-0 kernels): per bounce wf_extend, wf_shade and the
+// shadow stage, for renders and hrpt_trace_radiance alike. `profile`: HIP events around every launch (renders with HRPT_FRAME_PROFILE).
+hipError_t run_bounces(WavefrontState& st, const RenderPlan& plan, const SceneTraits& traits, uint32_t cus, const BatchPlan& batch, hipStream_t stream,
+                       WfArgs& a, const HrptPathTracerConstants& cb, bool profile, std::string& error)
+{
+    hipError_t e;
+    const dim3 grid(batch.grid);
+    const int maxBounces = (int)cb.m_MaxBounces;
+    // wf_shadow(b) only reads the shadow queue of shade(b) and adds into sampleRadiance; wf_extend(b+1) reads the path queue and
+    // writes hit records: no shared buffer, so the two run concurrently (fork after shade(b), join before shade(b+1), which both
+    // rewrites the shadow queue and adds the next radiance term -- the per-sample order of additions is unchanged).
+    // Per-launch timing (HRPT_FRAME_PROFILE) needs stream order, so profiling renders serially.
+    const bool overlap = !profile && !st.knobs.serialShadow && maxBounces > 1 && prepare_overlap(st, maxBounces);
+    bool pendingJoin = false;
+    for (int bounce = 0; bounce < maxBounces; ++bounce) {
+        const uint32_t parity = (uint32_t)bounce & 1u;
+        const bool timed = profile && st.eventsUsed + 8 <= 4096;
+        a.primary = (plan.fusedPrimary && bounce == 0) ? 1u : 0u;
+        const bool fusedBounce0 = plan.fusedBounce0 && bounce == 0;      // wf_bounce0 in place of the pair below, on the shade grid, timed as wf_shade
+        if (timed && !fusedBounce0) timing_mark(st, stream, kKernelExtend, true);
+        if (!fusedBounce0) launch_extend(plan.vE, cus, dim3(batch.gridExtend), stream, a, parity);
+        if (timed) { if (!fusedBounce0) timing_mark(st, stream, kKernelExtend, false); timing_mark(st, stream, kKernelShade, true); }
+        if (pendingJoin) { if ((e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)bounce - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; } pendingJoin = false; }
+        launch_shade(plan, fusedBounce0, grid, stream, a, cb, parity, bounce, bounce + 1 == maxBounces ? 1 : 0);
+        if (timed) { timing_mark(st, stream, kKernelShade, false); timing_mark(st, stream, kKernelShadow, true); }
+        if (overlap) {
+            if ((e = hipEventRecord(st.forkEvents[(size_t)bounce], stream)) != hipSuccess ||
+                (e = hipStreamWaitEvent(st.auxStream, st.forkEvents[(size_t)bounce], 0)) != hipSuccess) { error = "fork to the shadow stream"; return e; }
+            shadow_stage(plan, traits, cus, grid, st.auxStream, a, cb, bounce);
+            if ((e = hipEventRecord(st.joinEvents[(size_t)bounce], st.auxStream)) != hipSuccess) { error = "hipEventRecord(join)"; return e; }
+            pendingJoin = true;
+        } else {
+            shadow_stage(plan, traits, cus, grid, stream, a, cb, bounce);
+        }
+        if (timed) timing_mark(st, stream, kKernelShadow, false);
+    }
+    if (pendingJoin && (e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)maxBounces - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; }
+    return hipSuccess;
+}
 }
 
 hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
@@ -486,36 +526,7 @@ hipError_t wavefront_render(WavefrontState& st, const SceneView& scene, const Sc
             if (!plan.fusedPrimary) st.raygenBytes += (uint64_t)a.numSamples * 16 + px * spp * st.plan.pathRecordBytes;
             st.resolveBytes += px * ((uint64_t)spp * 16 + 32 + (cb.m_AccumulationIndex > 0 ? 16 : 0));
         }
-        const int maxBounces = (int)cb.m_MaxBounces;
-        // wf_shadow(b) only reads the shadow queue of shade(b) and adds into sampleRadiance; wf_extend(b+1) reads the path queue and
-        // writes hit records: no shared buffer, so the two run concurrently (fork after shade(b), join before shade(b+1), which both
-        // rewrites the shadow queue and adds the next radiance term -- the per-sample order of additions is unchanged).
-        // Per-launch timing (HRPT_FRAME_PROFILE) needs stream order, so profiling renders serially.
-        const bool overlap = !st.profile && !st.knobs.serialShadow && maxBounces > 1 && prepare_overlap(st, maxBounces);
-        bool pendingJoin = false;
-        for (int bounce = 0; bounce < maxBounces; ++bounce) {
-            const uint32_t parity = (uint32_t)bounce & 1u;
-            const bool timed = st.profile && st.eventsUsed + 8 <= 4096;
-            a.primary = (plan.fusedPrimary && bounce == 0) ? 1u : 0u;
-            const bool fusedBounce0 = plan.fusedBounce0 && bounce == 0;      // wf_bounce0 in place of the pair below, on the shade grid, timed as wf_shade
-            if (timed && !fusedBounce0) timing_mark(st, stream, kKernelExtend, true);
-            if (!fusedBounce0) launch_extend(plan.vE, cus, dim3(batch.gridExtend), stream, a, parity);
-            if (timed) { if (!fusedBounce0) timing_mark(st, stream, kKernelExtend, false); timing_mark(st, stream, kKernelShade, true); }
-            if (pendingJoin) { if ((e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)bounce - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; } pendingJoin = false; }
-            launch_shade(plan, fusedBounce0, grid, stream, a, cb, parity, bounce, bounce + 1 == maxBounces ? 1 : 0);
-            if (timed) { timing_mark(st, stream, kKernelShade, false); timing_mark(st, stream, kKernelShadow, true); }
-            if (overlap) {
-                if ((e = hipEventRecord(st.forkEvents[(size_t)bounce], stream)) != hipSuccess ||
-                    (e = hipStreamWaitEvent(st.auxStream, st.forkEvents[(size_t)bounce], 0)) != hipSuccess) { error = "fork to the shadow stream"; return e; }
-                shadow_stage(plan, traits, cus, grid, st.auxStream, a, cb, bounce);
-                if ((e = hipEventRecord(st.joinEvents[(size_t)bounce], st.auxStream)) != hipSuccess) { error = "hipEventRecord(join)"; return e; }
-                pendingJoin = true;
-            } else {
-                shadow_stage(plan, traits, cus, grid, stream, a, cb, bounce);
-            }
-            if (timed) timing_mark(st, stream, kKernelShadow, false);
-        }
-        if (pendingJoin && (e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)maxBounces - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; }
+        if ((e = run_bounces(st, plan, traits, cus, batch, stream, a, cb, st.profile, error)) != hipSuccess) return e;
         uint32_t rgrid = (uint32_t)((pixelsPadded + kBlock - 1) / kBlock); if (rgrid > cus * 8) rgrid = cus * 8;
         if (timedEnds) timing_mark(st, stream, kKernelResolve, true);
         hipLaunchKernelGGL(wf_resolve, dim3(rgrid), dim3(kBlock), 0, stream, a, accumulation, output, cb.m_AccumulationIndex);
@@ -561,6 +572,63 @@ hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const S
     else if (motion) hipLaunchKernelGGL(wf_gbuffer_motion<false>, grid, dim3(kBlock), 0, stream, a, constants, g, planeMask, *motion);
     else hipLaunchKernelGGL(wf_gbuffer, grid, dim3(kBlock), 0, stream, a, constants, g, planeMask);
     if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }
+    return hipSuccess;
+}
+
+// hrpt_trace_radiance, wavefront path: wf_raygen_rays, the render's bounces (run_bounces with plan_radiance's plan), wf_store_radiance, in batches of
+// radiance_batch_rays. Like wavefront_gbuffer it touches neither st.plan nor the byte / timing accounting of renders and counts into a scratch
+// counter block; it works in the render's queue pool when that holds a batch, otherwise in a pool of its own.
+hipError_t wavefront_radiance(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
+                              const HrptRay* rays, float4* radiance, uint64_t count, bool accumulate, hipStream_t stream, std::string& error)
+{
+    if (count == 0) return hipSuccess;
+    hipError_t e; uint32_t cus = 0;
+    if ((e = device_cus(st, cus, error)) != hipSuccess) return e;
+    TreeCounts tree = tree_counts(scene);
+    tree.instanceCount = st.shadeInstances; tree.materialCount = st.shadeMaterials;
+    const RenderPlan plan = plan_radiance(traits, tree, constants.m_LightCount, cus, st.knobs);
+    WfArgs a{};
+    fill_scene_args(a, st, scene, traits, TileRect{}, 0u);     // (no rectangle: nothing between raygen and resolve reads one)
+    // ---- 1. the batch size and the queue pool: a render's streams and, behind them, the scratch counters
+    const bool hasInstances = scene.instances != nullptr;
+    auto carve = [&](char* base, uint64_t capacity) {
+        const size_t bytes = carve_pool(base, a, capacity, plan.maxLights, traits, hasInstances);
+        a.counters = reinterpret_cast<DeviceCounters*>(reinterpret_cast<uintptr_t>(base) + bytes);
+        return bytes + sizeof(DeviceCounters) * kCounterShards;
+    };
+    uint64_t batchRays = radiance_batch_rays(count, plan, 0, st.knobs);
+    size_t bytes = carve(nullptr, radiance_capacity(batchRays));
+    char* pool = static_cast<char*>(st.pool.get());
+    if (bytes > st.poolBytes) {
+        if (bytes > st.radPoolBytes) {     // the pool has to grow: within half of what the device has free, as a render's
+            size_t freeB = 0, totalB = 0;
+            if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) batchRays = radiance_batch_rays(count, plan, (uint64_t)(freeB + st.radPoolBytes) / 2, st.knobs);
+        }
+        for (;;) {
+            bytes = carve(nullptr, radiance_capacity(batchRays));
+            if ((e = grow_buffer(st, stream, st.radPool, st.radPoolBytes, bytes)) == hipSuccess) break;
+            (void)hipGetLastError();
+            if (batchRays <= kMaxSegment) { error = "hipMalloc(radiance queue pool, " + std::to_string(bytes >> 20) + " MiB)"; return e; }
+            batchRays = (batchRays + 1) / 2;
+        }
+        pool = static_cast<char*>(st.radPool.get());
+    }
+    carve(pool, radiance_capacity(batchRays));
+    if ((e = reserve_spill(st, stream, plan.spillThreads * plan.spillEntries, a, error)) != hipSuccess) return e;
+    // ---- 2. the arguments the plan decides (one sample per ray; a.primary stays 0: every bounce reads the path queue)
+    a.maxLights = plan.maxLights; a.sortShade = plan.sortShade; a.nodeLoopMin = plan.nodeLoopMin; a.slimShadow = plan.slim ? 1u : 0u; a.spp = 1;
+    a.shadeInstances = tree.instanceCount; a.shadeMaterials = tree.materialCount;
+    // ---- 3. per batch: the rays into path queue 0, the bounces, sampleRadiance out
+    for (uint64_t first = 0; first < count; first += batchRays) {
+        a.numSamples = (uint32_t)((count - first) < batchRays ? (count - first) : batchRays);
+        const BatchPlan batch = plan_batch(plan, st.knobs, a.numSamples);
+        a.segSize = batch.segSize; a.numSegments = batch.numSegments;
+        hipLaunchKernelGGL(wf_raygen_rays, dim3(batch.grid), dim3(kBlock), 0, stream, a, reinterpret_cast<const float4*>(rays + first));
+        if ((e = run_bounces(st, plan, traits, cus, batch, stream, a, constants, false, error)) != hipSuccess) return e;
+        uint32_t sgrid = (a.numSamples + kBlock - 1) / kBlock; if (sgrid > cus * 8) sgrid = cus * 8;
+        hipLaunchKernelGGL(wf_store_radiance, dim3(sgrid), dim3(kBlock), 0, stream, a, radiance + first, accumulate ? 1u : 0u);
+        if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }
+    }
     return hipSuccess;
 }
 

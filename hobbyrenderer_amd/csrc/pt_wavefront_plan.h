@@ -47,6 +47,7 @@ struct WavefrontKnobs {
     bool noFusedBounce0 = false;       // HRPT_WF_FUSED_BOUNCE0=0: bounce 0 keeps the wf_extend<PRIMARY> + wf_shade<PRIMARY> pair where wf_bounce0 would run (A/B knob)
     bool noShadeLdsTables = false;     // HRPT_WF_SHADE_LDS_TABLES=0: wf_shade gathers triangle / instance / material records from global memory even when they fit LDS (A/B knob)
     int shadowPath = 0;                // scenes with non-opaque geometry: 0 = automatic, 1 = wf_shadow traverses itself (buffered query), 2 = any-hit pass + resolve
+    uint32_t radianceBatch = 0;        // HRPT_RADIANCE_BATCH: most rays hrpt_trace_radiance runs through the pipeline at once (0 = no cap of its own)
 };
 
 constexpr uint32_t kMaxSegment = 1024;       // largest wave-owned segment (samples); the size is chosen per batch, 64..1024
@@ -289,6 +290,28 @@ inline GBufferPlan plan_gbuffer(const SceneTraits& traits, const TreeCounts& tre
     g.bytesPerSample = p.pathRecordBytes + 16u + (tree.hasInstances ? 4u : 0u) + 16u;
     return g;
 }
+
+// hrpt_trace_radiance (wavefront path): the render's pipeline between wf_raygen_rays and wf_store_radiance over a caller's rays. The plan is the
+// render's for these traits and lights -- kernel variants, shadow mode, slim queue, LDS shade tables, class sort, grids -- with the two bounce-0
+// forms off that derive their rays from the sample index (fusedPrimary, and fusedBounce0 which needs it): the rays are in the path queue.
+inline RenderPlan plan_radiance(const SceneTraits& traits, const TreeCounts& tree, uint32_t lightCount, uint32_t cus, WavefrontKnobs k)
+{
+    k.noFusedPrimary = true;
+    return plan_render(traits, tree, lightCount, cus, k);
+}
+// Rays per batch: at most 64 Mi, what `budgetBytes` of queue pool hold (0 = no such limit), what keeps the 32-bit (entry, light) slot ids in
+// range and HRPT_RADIANCE_BATCH; never below one ray. The batch's pool is laid out for radiance_capacity samples: whole kMaxSegment segments.
+constexpr uint64_t kMaxRadianceBatch = 64ull << 20;
+inline uint64_t radiance_batch_rays(uint64_t count, const RenderPlan& p, uint64_t budgetBytes, const WavefrontKnobs& k)
+{
+    uint64_t n = kMaxRadianceBatch;
+    if (budgetBytes && budgetBytes / p.bytesPerSample < n) n = budgetBytes / p.bytesPerSample;
+    if (n * p.maxLights > 0xFFFFFFFFull) n = 0xFFFFFFFFull / p.maxLights;
+    if (k.radianceBatch && k.radianceBatch < n) n = k.radianceBatch;
+    if (count < n) n = count;
+    return n ? n : 1;
+}
+inline uint64_t radiance_capacity(uint64_t batchRays) { return (batchRays + kMaxSegment - 1) / kMaxSegment * kMaxSegment; }
 
 // hrpt_trace_rays over device arrays through the persistent refilling traversal kernel (wf_trace_rays): the closest-hit kernel class of the
 // render path (4-wide, kExtendLdsStack), with these differences: HRPT_WF_BVH_WIDTH and HRPT_WF_PAD_LDS do not apply, and there is no 2-wide

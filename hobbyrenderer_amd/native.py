@@ -29,7 +29,7 @@ lib = C.CDLL(LIB_PATH)
 EXPORTS = [
     "hrpt_create", "hrpt_destroy", "hrpt_last_error", "hrpt_upload_scene", "hrpt_resize", "hrpt_render",
     "hrpt_synchronize", "hrpt_set_stream", "hrpt_get_device_images", "hrpt_read_accumulation", "hrpt_read_output",
-    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_update_vertices", "hrpt_update_vertices_device", "hrpt_quantize_vertices_host", "hrpt_quantize_vertices_device", "hrpt_skin_vertices_host", "hrpt_skin_vertices_device", "hrpt_update_vertices_skinned", "hrpt_trace_rays", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_atmosphere", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
+    "hrpt_write_accumulation", "hrpt_resolve_output", "hrpt_resolve_device", "hrpt_resolve_columns_device", "hrpt_get_stats", "hrpt_reset_stats", "hrpt_set_bvh_builder", "hrpt_set_acceleration_structure", "hrpt_set_shadow_overlap", "hrpt_get_build_info", "hrpt_update_instances", "hrpt_refit_instances", "hrpt_update_lights", "hrpt_update_materials", "hrpt_update_vertices", "hrpt_update_vertices_device", "hrpt_quantize_vertices_host", "hrpt_quantize_vertices_device", "hrpt_skin_vertices_host", "hrpt_skin_vertices_device", "hrpt_update_vertices_skinned", "hrpt_trace_rays", "hrpt_trace_radiance", "hrpt_allgather", "hrpt_selftest_f16_decode", "hrpt_selftest_unorm8", "hrpt_selftest_sample_textures", "hrpt_selftest_atmosphere", "hrpt_selftest_bvh", "hrpt_selftest_read_bvh", "hrpt_selftest_host_build", "hrpt_post_process", "hrpt_read_display", "hrpt_get_exposure", "hrpt_set_exposure", "hrpt_halton",
     "hrpt_bloom", "hrpt_bloom_device", "hrpt_bloom_host", "hrpt_bloom_pack_probe",
     "hrpt_render_gbuffer", "hrpt_read_gbuffer", "hrpt_get_gbuffer_device",
     "hrpt_render_motion_vectors", "hrpt_read_motion_vectors", "hrpt_get_motion_vectors_device",
@@ -68,6 +68,7 @@ lib.hrpt_set_shadow_overlap.argtypes = [C.c_void_p, C.c_int]
 lib.hrpt_set_acceleration_structure.argtypes = [C.c_void_p, C.c_int]
 lib.hrpt_allgather.argtypes = [C.POINTER(C.c_void_p), C.c_int]
 lib.hrpt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+lib.hrpt_trace_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
 lib.hrpt_get_build_info.argtypes = [C.c_void_p, C.POINTER(S.BuildInfo)]
 lib.hrpt_update_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
 lib.hrpt_refit_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
@@ -678,6 +679,30 @@ class PathTracerContext:
         flags = (S.RAYS_SHADOW if shadow else S.RAYS_CLOSEST) | (S.RAYS_THREAD_PER_RAY if thread_per_ray else 0)
         self._check(lib.hrpt_trace_rays(self._h, rays.ctypes.data, hits.ctypes.data, len(rays), flags))
         return hits
+
+    def trace_radiance(self, rays, constants, accumulate=False, thread_per_ray=False, out=None):
+        """hrpt_trace_radiance: the path-traced radiance along each of `rays` (structured array of S.Ray: origin, unit direction, tmin and RNG
+        state; tmax is ignored), float32 [n, 4] = (L.rgb, 1). Of `constants` (S.PathTracerConstants) the sun, m_LightCount and m_MaxBounces
+        are read. accumulate: add (L, 1) to `out` (float32 [n, 4], required then) instead; out: the array to write, returned.
+        thread_per_ray: the one-thread-per-ray cross-check kernel instead of the wavefront pipeline. Synchronises."""
+        rays = np.ascontiguousarray(rays, S.Ray)
+        if out is None:
+            if accumulate:
+                raise ValueError("trace_radiance: accumulate needs the array to add to (out)")
+            out = np.zeros((len(rays), 4), np.float32)
+        if out.dtype != np.float32 or out.shape != (len(rays), 4) or not out.flags.c_contiguous:
+            raise ValueError("trace_radiance: out must be a contiguous float32 [len(rays), 4] array")
+        cb = np.ascontiguousarray(constants, S.PathTracerConstants)
+        flags = (S.RADIANCE_ACCUMULATE if accumulate else 0) | (S.RADIANCE_THREAD_PER_RAY if thread_per_ray else 0)
+        self._check(lib.hrpt_trace_radiance(self._h, rays.ctypes.data, out.ctypes.data, len(rays), cb.ctypes.data, flags))
+        return out
+
+    def trace_radiance_device(self, rays_ptr, out_ptr, count, constants, flags=0):
+        """hrpt_trace_radiance over device arrays (integer addresses of `count` S.Ray records and `count` float4 slots, e.g. a torch tensor's
+        data_ptr()): no copies, asynchronous on the context stream. flags: S.RADIANCE_ACCUMULATE / S.RADIANCE_THREAD_PER_RAY."""
+        cb = np.ascontiguousarray(constants, S.PathTracerConstants)
+        self._check(lib.hrpt_trace_radiance(self._h, C.c_void_p(int(rays_ptr)), C.c_void_p(int(out_ptr)), int(count), cb.ctypes.data,
+                                            int(flags) | S.RADIANCE_DEVICE_POINTERS))
 
     def set_shadow_overlap(self, enabled):
         """Intra-frame overlap of the shadow stage with the next bounce's traversal (default on); turn off for contexts used as lanes of

@@ -252,6 +252,7 @@ class Stats(C.Structure):
 Ray = np.dtype([("origin", f32, 3), ("tmin", f32), ("direction", f32, 3), ("tmax", f32), ("rng", u32), ("pad", u32, 3)])       # HrptRay, 48 B
 RayHit = np.dtype([("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32), ("hit", u32), ("rng", u32), ("pad", u32)])   # HrptRayHit, 32 B
 RAYS_CLOSEST, RAYS_SHADOW, RAYS_DEVICE_POINTERS, RAYS_THREAD_PER_RAY = 0, 1, 0x100, 0x200
+RADIANCE_DEVICE_POINTERS, RADIANCE_THREAD_PER_RAY, RADIANCE_ACCUMULATE = 0x100, 0x200, 0x400       # hrpt_trace_radiance flags
 # first-hit G-buffer (hrpt_render_gbuffer): plane indices HRPT_GB_*, the all-planes mask, the flag bits of the ids plane's w
 GB_ALBEDO, GB_NORMAL, GB_GEO_NORMAL, GB_EMISSIVE, GB_DEPTH, GB_IDS, GB_PLANES = 0, 1, 2, 3, 4, 5, 6
 GB_ALL_PLANES = 0x3F

@@ -573,6 +573,33 @@ typedef struct HrptRayHit { float t, u, v; uint32_t instance, primitive, hit, rn
 #define HRPT_RAYS_THREAD_PER_RAY  0x200u   /* testing: the one-thread-per-ray kernel instead of the persistent refilling traversal kernel (same results) */
 int  hrpt_trace_rays(HrptContext* ctx, const HrptRay* rays, HrptRayHit* hits, uint64_t count, uint32_t flags);
 
+/* ---- path-traced radiance for arbitrary ray batches -----------------------------------------------------------------
+ * The radiance that arrives along rays the caller made (probes, cube maps, panoramas, other sensor models, lightmap texels, ray-sampled
+ * training sets): the estimator of hrpt_render on rays that do not come from its pinhole camera.
+ * Ray i is path segment 0 of PathTracer_CSMain (src/shaders/PathTracer.hlsl:53-340) with ray.o = rays[i].origin, ray.d = rays[i].direction
+ * AS GIVEN (the library does not normalise it: pass a unit vector, which keeps camera rays bit-identical to the render's), ray.tmin =
+ * rays[i].tmin, the RNG state rays[i].rng, throughput 1, outside any medium. rays[i].tmax is IGNORED: the first segment is unbounded at 1e10
+ * as in the reference. From there it is the render's loop with no change of arithmetic or order: constants->m_MaxBounces bounces, next event
+ * estimation over the first constants->m_LightCount lights, the sun disk on a bounce-0 miss, specular direct light at bounce 0 only, Russian
+ * roulette from bounce 2, the g_Lights[0] sun-intensity quirk. Of `constants` only m_SunDirection, m_CosSunAngularRadius, m_LightCount and
+ * m_MaxBounces are read; the view, the jitter, the camera position and the accumulation index are not. For the origin, direction and
+ * seed of PathTracer.hlsl:61-72 the result is, bit for bit, the term hrpt_render adds to Accumulation for that pixel and index.
+ * radiance4 receives one float4 per ray: (L.r, L.g, L.b, 1); with HRPT_RADIANCE_ACCUMULATE (old.rgb + L, old.w + 1), the addition the
+ * render performs for an accumulation index above 0. A ray with a NaN or infinite origin, direction or tmin is not traced (the rule of
+ * hrpt_trace_rays): it writes (0, 0, 0, 0), and with HRPT_RADIANCE_ACCUMULATE leaves its slot alone.
+ * rays / radiance4 are host arrays (the call synchronises) unless HRPT_RADIANCE_DEVICE_POINTERS is set: then both are device pointers, 16-byte
+ * aligned, nothing is copied and the call is asynchronous on the context stream. Either way it is ordered on that stream with renders and
+ * scene updates. hrpt_resize is not required. Accumulation, Output, every G-buffer plane and every history, the exposure buffer and every
+ * HrptStats field (megakernelFallbacks included) stay as they were.
+ * count == 0: HRPT_OK, nothing happens. No scene: HRPT_ERR_NO_SCENE. m_MaxBounces above 64 or m_LightCount above the scene's light count (as
+ * hrpt_render), unknown flag bits, a NULL pointer, more than 2^31 rays, HRPT_RADIANCE_THREAD_PER_RAY on a two-level structure deeper than
+ * that kernel's 64-entry stack: HRPT_ERR_INVALID_ARGUMENT. An error changes nothing. */
+#define HRPT_RADIANCE_DEVICE_POINTERS 0x100u  /* rays / radiance are device pointers; asynchronous on the context stream */
+#define HRPT_RADIANCE_THREAD_PER_RAY  0x200u  /* testing: the one-thread-per-ray kernel (same results) */
+#define HRPT_RADIANCE_ACCUMULATE      0x400u  /* radiance[i].rgb += L, radiance[i].w += 1 instead of (L, 1) */
+int  hrpt_trace_radiance(HrptContext* ctx, const HrptRay* rays, float* radiance4, uint64_t count,
+                         const HrptPathTracerConstants* constants, uint32_t flags);
+
 /* ---- first-hit G-buffer ------------------------------------------------------------------------------------------
  * What the primary ray of every pixel saw: path vertex 0 of ONE accumulation index, with the contents of the reference's GBufferOut
  * (src/shaders/BasePass.hlsl:184-192, 485-493) computed by the path tracer's own stages. For pixel (px, py) and params->constants:
