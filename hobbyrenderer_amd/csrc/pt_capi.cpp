@@ -114,6 +114,7 @@ try {
     for (DeviceBuffer<float4>& image : c->perSize.dDenoiseScratch) image.reset();        // allocated again by the call that needs it
     c->perSize.dModulation.reset();                                             // written again by the next hrpt_demodulate
     for (DeviceBuffer<float4>& image : c->perSize.dUpscaleHistory) image.reset();        // allocated again, without history, by the next hrpt_upscale
+    c->perSize.dProbeIrradiance.reset();                                        // written again by the next hrpt_probes_shade_gbuffer
     c->perSize.dUpscaled.reset(); c->upscaleValid = false; c->upscaleCur = 0; c->upscaleWidth = c->upscaleHeight = 0;
     c->width = width; c->height = height;
     return HRPT_OK;

@@ -65,6 +65,7 @@ struct PerSizeImages {
     // temporal upscaling (hrpt_upscale): ping-pong history pair and the colour image, all of upscaleWidth x upscaleHeight (the DISPLAY size of
     // the last call, not the context's); allocated by the first call, re-allocated when the display size changes, dropped by hrpt_resize
     DeviceBuffer<float4> dUpscaleHistory[2], dUpscaled;
+    DeviceBuffer<float4> dProbeIrradiance;           // hrpt_probes_shade_gbuffer: the probe volume's irradiance at the first hits, allocated by the first call, dropped by hrpt_resize
 };
 
 // Buffers that live as long as the context.

@@ -105,6 +105,24 @@ void demodulate_host(const HrptDemodulateImages& images, uint32_t width, uint32_
 void compose_host(const HrptComposeImages& images, uint32_t width, uint32_t height, int nthreads);
 void modulation_probe(const float* albedo3, const float* N3, const float* V3, float rough, float metal, float floor, float* outM3);
 
+// Irradiance probe volume (pt_probes.hip; arithmetic in pt_probes.h): ray records and shared directions of an update, the blend of traced
+// rays into the atlases (in place), the query at points and at the first hits of the G-buffer; every pointer in device memory, 16-byte
+// aligned. probes_*_host (pt_probes_host.cpp): the same arithmetic on host threads; raysOut / directions4Out may be null there.
+bool probes_volume_valid(const HrptProbeVolume& volume);
+hipError_t launch_probes_raygen(const HrptProbeVolume& volume, uint32_t frameSeed, HrptRay* rays, float* directions4, hipStream_t stream);
+hipError_t launch_probes_blend(const HrptProbeVolume& volume, const float* directions4, const float* radiance4, const HrptRayHit* hits, float* irradiance,
+                               float* distance, bool hasHistory, hipStream_t stream);
+hipError_t launch_probes_query(const HrptProbeVolume& volume, const float* irradiance, const float* distance, const HrptProbePoint* points, float* out4,
+                               uint64_t count, hipStream_t stream);
+hipError_t launch_probes_shade_gbuffer(const HrptProbeVolume& volume, const HrptPlanarViewConstants& view, uint32_t width, uint32_t height, float intensity,
+                                       const float* irradiance, const float* distance, const float* normal, const float* depth, float4* out,
+                                       hipStream_t stream);
+void probes_rays_host(const HrptProbeVolume& volume, uint32_t frameSeed, HrptRay* raysOut, float* directions4Out);
+void probes_blend_host(const HrptProbeVolume& volume, const float* directions4, const float* radiance4, const HrptRayHit* hits, float* irradiance,
+                       float* distance, bool hasHistory, int nthreads);
+void probes_query_host(const HrptProbeVolume& volume, const float* irradiance, const float* distance, const HrptProbePoint* points, float* out4,
+                       uint64_t count, int nthreads);
+
 // Vertex quantiser (pt_deform.hip; arithmetic in pt_deform.h): out[i] = the 24-byte scene-format record of the float vertex in[i], both in
 // device memory (in 16-byte aligned); *flag (device, may be null) is set to 1 when a position is not finite. quantize_vertices_host
 // (pt_deform_host.cpp): the same arithmetic on host threads; returns whether every position is finite.

@@ -265,6 +265,13 @@ assert TextureProbe.itemsize == 32 and TextureProbeResult.itemsize == 160
 AtmosphereProbe = np.dtype([("cameraPos", f32, 3), ("viewRay", f32, 3), ("sunDir", f32, 3), ("sunIntensity", f32), ("addSunDisk", u32), ("pad", u32)])   # HrptAtmosphereProbe, 48 B
 AtmosphereProbeResult = np.dtype([("sky", f32, 3), ("sun", f32, 3), ("transmittance", f32, 3), ("r", f32), ("mu", f32), ("pad", f32)])                  # HrptAtmosphereProbeResult, 48 B
 assert AtmosphereProbe.itemsize == 48 and AtmosphereProbeResult.itemsize == 48
+# irradiance probe volume (hrpt_probes_*)
+ProbeVolume = np.dtype([("origin", f32, 3), ("hysteresis", f32), ("spacing", f32, 3), ("maxRayDistance", f32), ("counts", u32, 3), ("raysPerProbe", u32),
+                        ("distanceExponent", f32), ("normalBias", f32), ("viewBias", f32), ("pad", u32)])                               # HrptProbeVolume, 64 B
+ProbePoint = np.dtype([("position", f32, 3), ("pad0", f32), ("normal", f32, 3), ("pad1", f32), ("view", f32, 3), ("pad2", f32)])       # HrptProbePoint, 48 B
+assert ProbeVolume.itemsize == 64 and ProbePoint.itemsize == 48
+PROBES_RESET, PROBES_DEVICE_POINTERS = 1, 0x100
+PROBE_IRRADIANCE_SHAPE, PROBE_DISTANCE_SHAPE = (8, 8, 4), (16, 16, 2)      # one probe's tiles; the atlases are [P, 8, 8, 4] and [P, 16, 16, 2]
 
 
 class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B

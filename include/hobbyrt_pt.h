@@ -995,6 +995,80 @@ int  hrpt_modulation_probe(const float* albedo3, const float* N3, const float* V
  * reuse the same RNG seeds every frame, and a temporal accumulator fed by it converges to one fixed sample set. */
 int  hrpt_clear_accumulation(HrptContext* ctx);
 
+/* ---- irradiance probe volume ---------------------------------------------------------------------------------------------
+ * A grid of probes that shoot path-traced rays, folds them into octahedral irradiance and distance atlases, and answers "what diffuse
+ * light arrives at this point with this normal": the reference's real-time indirect-diffuse chain (src/shaders/ddgi/ProbeTraceCS.hlsl, the
+ * two blending passes, IndirectQueryCS.hlsl -> g_RG_DDGIIndirect). The SDK arithmetic behind those shaders is not in the reference tree, so
+ * the stage is DEFINED by this project after the published algorithm (Majercik et al., "Dynamic Diffuse Global Illumination with Ray-Traced
+ * Irradiance Fields"); DESIGN.md section 26 has every operation in order, and pt_probes.h is its one source for kernels and host executors.
+ * Parity with the RTXGI SDK, its texture formats and gamma blend, probe relocation / classification / scrolling, back-face detection and a
+ * specular lookup are out of scope. Unlike the reference, a probe ray carries the path tracer's full estimate (hrpt_trace_radiance), so
+ * there is no feedback of last frame's atlas and no energy clamp.
+ *
+ * Volume. Probe (x, y, z) has index p = x + counts[0] * (y + counts[1] * z) and position origin + (x, y, z) * spacing; P = the number of
+ * probes. Valid: counts >= 1 and P <= 2^20; 1 <= raysPerProbe <= 1024; spacing and maxRayDistance finite and > 0; hysteresis in [0, 1);
+ * distanceExponent finite and >= 1; normalBias and viewBias finite and >= 0; pad == 0. Anything else: HRPT_ERR_INVALID_ARGUMENT.
+ * Atlases, per probe and contiguous, linear binary32: irradiance [P][8][8] float4 (6 x 6 interior texels plus a one-texel border; a texel
+ * is (M, 1) with M the cosine-weighted mean radiance, so irradiance is pi * M), 1 KiB per probe; distance [P][16][16] float2 (14 x 14
+ * interior plus border; (mean d, mean d^2)), 2 KiB per probe. */
+typedef struct HrptProbeVolume {
+    float origin[3]; float hysteresis;
+    float spacing[3]; float maxRayDistance;
+    uint32_t counts[3]; uint32_t raysPerProbe;
+    float distanceExponent, normalBias, viewBias; uint32_t pad;
+} HrptProbeVolume;                                                                                                         /* 64 B */
+typedef struct HrptProbePoint { float position[3]; float pad0; float normal[3]; float pad1; float view[3]; float pad2; } HrptProbePoint;   /* 48 B */
+typedef struct HrptProbes HrptProbes;
+#define HRPT_PROBES_RESET           1u        /* hrpt_probes_update: ignore the stored history, store the new values */
+#define HRPT_PROBES_DEVICE_POINTERS 0x100u    /* hrpt_probes_query: points / irradiance4 are device pointers; asynchronous on the context stream */
+/* A volume on `ctx` with zeroed atlases and its own ray, radiance and hit buffers (P * raysPerProbe records each, sized here). Destroy it
+ * before its context. hrpt_probes_destroy(NULL) is allowed. */
+int  hrpt_probes_create(HrptContext* ctx, const HrptProbeVolume* volume, HrptProbes** out);
+void hrpt_probes_destroy(HrptProbes* probes);
+/* One update: ray generation for `frameSeed` (raysPerProbe directions shared by all probes: a spherical Fibonacci set under a rotation drawn
+ * from the seed), hrpt_trace_radiance and hrpt_trace_rays (HRPT_RAYS_CLOSEST) on those records, and the blend into the atlases: the first
+ * update after creation or with HRPT_PROBES_RESET stores the new value, later ones new + hysteresis * (old - new). The result equals, bit
+ * for bit, hrpt_probes_rays_host -> hrpt_trace_radiance -> hrpt_trace_rays -> hrpt_probes_blend_host through the public calls.
+ * Asynchronous on the context stream, ordered with renders and scene updates; Accumulation, Output, every plane and history, the exposure
+ * and every HrptStats field stay as they were (the guarantees of hrpt_trace_radiance). No scene: HRPT_ERR_NO_SCENE. The argument rules of
+ * the two trace calls apply to `constants`; unknown flag bits: HRPT_ERR_INVALID_ARGUMENT. An error leaves the atlases as they were. */
+int  hrpt_probes_update(HrptProbes* probes, const HrptPathTracerConstants* constants, uint32_t frameSeed, uint32_t flags);
+/* irradiance4[i] = (E.rgb, inside) at points[i]: position, unit normal, unit direction to the viewer (for the view bias). E is the
+ * irradiance (pi * the blended mean radiance): a Lambertian surface reflects albedo / pi * E. inside = 1 when the biased point lies in the
+ * grid's box; a point outside still gets the answer of the clamped cell. A non-finite position, normal or view gives (0, 0, 0, 0).
+ * Host arrays (the call synchronises), or device pointers (16-byte aligned) with HRPT_PROBES_DEVICE_POINTERS. count == 0: HRPT_OK. */
+int  hrpt_probes_query(HrptProbes* probes, const HrptProbePoint* points, float* irradiance4, uint64_t count, uint32_t flags);
+/* The query at the first hit of every pixel, into a library-owned width x height float4 plane of the context (allocated on first use, dropped
+ * by hrpt_resize): (E * intensity, 1) at a hit, (0, 0, 0, 0) at a miss. It reads the planes HRPT_GB_NORMAL and HRPT_GB_DEPTH as the caller
+ * filled them for this frame (either never requested: HRPT_ERR_INVALID_ARGUMENT, the message names the plane); the world position is
+ * ReconstructWorldPos of the view depth and the view vector normalize(camera position - world position), as hrpt_demodulate forms them.
+ * This is the reference's g_RG_DDGIIndirect: multiply by albedo * (1 - metallic) / pi and add it to Output.
+ * view->m_ViewportSize != the context's size, intensity not finite or < 0: HRPT_ERR_INVALID_ARGUMENT. Asynchronous on the context stream. */
+int  hrpt_probes_shade_gbuffer(HrptProbes* probes, const HrptPlanarViewConstants* view, float intensity);
+/* Host read-back of that plane (synchronises; bytes must be width * height * 16) and its device pointer (NULL before the first
+ * hrpt_probes_shade_gbuffer and after hrpt_resize, where the read answers HRPT_ERR_INVALID_ARGUMENT). */
+int  hrpt_read_probe_irradiance(HrptContext* ctx, float* dst, size_t bytes);
+int  hrpt_get_probe_irradiance_device(HrptContext* ctx, void** devicePtr);
+/* The atlases: host read-back (synchronises), device pointers (valid until hrpt_probes_destroy), and hrpt_probes_write, which installs
+ * atlases (tests, baked volumes; synchronises) and makes them the history of the next update. irradiance: P * 256 floats, distance: P * 512
+ * floats; either pointer may be NULL (skipped); a byte count that is not exactly that: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_probes_read(HrptProbes* probes, float* irradiance, size_t irradianceBytes, float* distance, size_t distanceBytes);
+int  hrpt_probes_get_device(HrptProbes* probes, void** irradiance, void** distance);
+int  hrpt_probes_write(HrptProbes* probes, const float* irradiance, size_t irradianceBytes, const float* distance, size_t distanceBytes);
+/* The stages alone, with no context (_host: host arrays, host threads, nthreads <= 0 = one per hardware thread up to 16) or on caller-owned
+ * device memory (_device: every pointer 16-byte aligned, asynchronous on `stream`). Same bits as the stages inside hrpt_probes_update /
+ * hrpt_probes_query. rays: raysOut receives P * raysPerProbe records (record p * N + k: origin = probe p, direction k, tmin 0, tmax 1e10,
+ * rng = pcg(g + pcg(frameSeed))), directions4Out the N shared directions as float4 (w = 0); either may be NULL. blend: directions4 [N],
+ * radiance4 and hits [P * N] as the trace calls wrote them (a ray with radiance4.w == 0 takes no part), the atlases updated in place;
+ * hasHistory == 0 stores the new values. */
+int  hrpt_probes_rays_host(const HrptProbeVolume* volume, uint32_t frameSeed, HrptRay* raysOut, float* directions4Out);
+int  hrpt_probes_blend_host(const HrptProbeVolume* volume, const float* directions4, const float* radiance4, const HrptRayHit* hits,
+                            float* irradianceInOut, float* distanceInOut, uint32_t hasHistory, int nthreads);
+int  hrpt_probes_blend_device(HrptContext* ctx, const HrptProbeVolume* volume, const float* directions4, const float* radiance4, const HrptRayHit* hits,
+                              float* irradianceInOut, float* distanceInOut, uint32_t hasHistory, void* stream);
+int  hrpt_probes_query_host(const HrptProbeVolume* volume, const float* irradiance, const float* distance, const HrptProbePoint* points, float* out4,
+                            uint64_t count, int nthreads);
+
 /* Intra-frame overlap: by default the shadow stage of bounce b runs on a second, library-owned stream next to the traversal of bounce
  * b + 1 (they share no buffer). That fills the tails of a context that renders one frame at a time (-3 % per frame). A host that keeps
  * two frames in flight on two contexts already fills those tails with the other frame; there the fork / join events only cost
