@@ -66,6 +66,7 @@ try {
     if (const char* e = getenv("HRPT_RADIANCE_BATCH")) c->wf.knobs.radianceBatch = (uint32_t)atoi(e);
     if (const char* e = getenv("HRPT_BLOOM_FUSED_TAIL")) { const int v = atoi(e); c->bloomTailTexels = v == 1 ? 8192u : (v > 0 ? (uint32_t)v : 0u); }
     if (const char* e = getenv("HRPT_UPSCALE_STAGED")) c->upscaleStaged = atoi(e) != 0;
+    if (const char* e = getenv("HRPT_DEFERRED_LIGHT_BATCH")) { const int v = atoi(e); c->deferredLightBatch = (v >= 1 && v <= 16) ? (uint32_t)v : 0u; }
     *out = c;
     return HRPT_OK;
 } catch (...) { return caught(nullptr, "hrpt_create"); }
@@ -115,6 +116,9 @@ try {
     c->perSize.dModulation.reset();                                             // written again by the next hrpt_demodulate
     for (DeviceBuffer<float4>& image : c->perSize.dUpscaleHistory) image.reset();        // allocated again, without history, by the next hrpt_upscale
     c->perSize.dProbeIrradiance.reset();                                        // written again by the next hrpt_probes_shade_gbuffer
+    c->perSize.dDeferredRays.reset(); c->perSize.dDeferredHits.reset(); c->perSize.deferredPairs = 0;      // sized again by the next hrpt_deferred_lighting
+    for (DeviceBuffer<float4>& image : c->perSize.dDeferredCarry) image.reset();
+    c->perSize.deferredCarryPixels = 0;
     c->perSize.dUpscaled.reset(); c->upscaleValid = false; c->upscaleCur = 0; c->upscaleWidth = c->upscaleHeight = 0;
     c->width = width; c->height = height;
     return HRPT_OK;

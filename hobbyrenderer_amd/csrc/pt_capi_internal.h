@@ -66,6 +66,10 @@ struct PerSizeImages {
     // the last call, not the context's); allocated by the first call, re-allocated when the display size changes, dropped by hrpt_resize
     DeviceBuffer<float4> dUpscaleHistory[2], dUpscaled;
     DeviceBuffer<float4> dProbeIrradiance;           // hrpt_probes_shade_gbuffer: the probe volume's irradiance at the first hits, allocated by the first call, dropped by hrpt_resize
+    // deferred lighting (hrpt_deferred_lighting): shadow-ray and hit records of one light batch (deferredPairs = pixels * batch of the last
+    // allocation) and the two running-sum images of a multi-batch call; allocated on first use, grown on demand, dropped by hrpt_resize
+    DeviceBuffer<HrptRay> dDeferredRays; DeviceBuffer<HrptRayHit> dDeferredHits; size_t deferredPairs = 0;
+    DeviceBuffer<float4> dDeferredCarry[2]; size_t deferredCarryPixels = 0;
 };
 
 // Buffers that live as long as the context.
@@ -103,7 +107,8 @@ struct Context {
     uint32_t upscaleWidth = 0, upscaleHeight = 0; int upscaleCur = 0; bool upscaleValid = false;   // [upscaleCur] is the history the last hrpt_upscale wrote
     PerContextBuffers perContext;
     uint32_t bloomTailTexels = 0;            // HRPT_BLOOM_FUSED_TAIL: levels of at most this many texels run in one workgroup's LDS (0 = one kernel per pass, the measured-faster default)
-    bool upscaleStaged = false;              // HRPT_UPSCALE_STAGED: the upscale kernel serves its current-frame taps from an LDS-staged window (false = global gathers, the measured-faster default)
+    uint32_t deferredLightBatch = 0;         // HRPT_DEFERRED_LIGHT_BATCH: lights per pass of hrpt_deferred_lighting, 1..16 (0 = min(m_LightCount, 4))
+    bool upscaleStaged = false;             // HRPT_UPSCALE_STAGED: the upscale kernel serves its current-frame taps from an LDS-staged window (false = global gathers, the measured-faster default)
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
     WavefrontState wf;

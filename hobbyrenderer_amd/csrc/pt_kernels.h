@@ -123,6 +123,23 @@ void probes_blend_host(const HrptProbeVolume& volume, const float* directions4, 
 void probes_query_host(const HrptProbeVolume& volume, const float* irradiance, const float* distance, const HrptProbePoint* points, float* out4,
                        uint64_t count, int nthreads);
 
+// Deferred lighting (pt_deferred.hip; arithmetic in pt_deferred.h): the shadow-ray records of lights [first, first + count) at every pixel
+// (rays: count * W * H records), and the shade pass of the same lights over the hit records hrpt_trace_rays left (hits null = visibility 1),
+// which carries the running sums in carryD / carryS between batches (read unless isFirst, written unless isLast; may be null for a single
+// batch) and finishes images.colorOut on the last one. Every pointer in device memory, 16-byte aligned. deferred_*_host
+// (pt_deferred_host.cpp): the same arithmetic on host threads, the atmosphere terms and visibilities as images.
+namespace deferred { struct Frame; }
+bool deferred_params_valid(const HrptDeferredParams& params);
+hipError_t launch_deferred_rays(const deferred::Frame& frame, const HrptGPULight* lights, uint32_t first, uint32_t count, const float* depth, const float* normal,
+                                HrptRay* rays, hipStream_t stream);
+hipError_t launch_deferred_shade(const SceneView& scene, const deferred::Frame& frame, const HrptGPULight* lights, uint32_t first, uint32_t count, bool isFirst,
+                                 bool isLast, const HrptDeferredImages& images, const HrptRayHit* hits, float4* carryD, float4* carryS, hipStream_t stream);
+void deferred_rays_host(const HrptDeferredImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptGPULight* lights,
+                        uint32_t firstLight, uint32_t lightCount, HrptRay* raysOut);
+void deferred_shade_host(const HrptDeferredImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptGPULight* lights,
+                         uint32_t lightCount, const float* visibility, const float* sunRadiance, const float* sky, const HrptDeferredParams& params,
+                         int nthreads);
+
 // Vertex quantiser (pt_deform.hip; arithmetic in pt_deform.h): out[i] = the 24-byte scene-format record of the float vertex in[i], both in
 // device memory (in 16-byte aligned); *flag (device, may be null) is set to 1 when a position is not finite. quantize_vertices_host
 // (pt_deform_host.cpp): the same arithmetic on host threads; returns whether every position is finite.

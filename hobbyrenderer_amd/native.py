@@ -46,6 +46,7 @@ EXPORTS = [
     "hrpt_probes_create", "hrpt_probes_destroy", "hrpt_probes_update", "hrpt_probes_query", "hrpt_probes_shade_gbuffer",
     "hrpt_read_probe_irradiance", "hrpt_get_probe_irradiance_device", "hrpt_probes_read", "hrpt_probes_get_device", "hrpt_probes_write",
     "hrpt_probes_rays_host", "hrpt_probes_blend_host", "hrpt_probes_blend_device", "hrpt_probes_query_host",
+    "hrpt_deferred_lighting", "hrpt_deferred_lighting_device", "hrpt_deferred_rays_host", "hrpt_deferred_shade_host",
 ]
 
 lib.hrpt_create.argtypes = [C.POINTER(S.DeviceDesc), C.POINTER(C.c_void_p)]
@@ -158,6 +159,11 @@ lib.hrpt_probes_rays_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_vo
 lib.hrpt_probes_blend_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
 lib.hrpt_probes_blend_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
 lib.hrpt_probes_query_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+lib.hrpt_deferred_lighting.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(S.DeferredParams)]
+lib.hrpt_deferred_lighting_device.argtypes = [C.c_void_p, C.POINTER(S.DeferredImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.DeferredParams), C.c_void_p]
+lib.hrpt_deferred_rays_host.argtypes = [C.POINTER(S.DeferredImages), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+lib.hrpt_deferred_shade_host.argtypes = [C.POINTER(S.DeferredImages), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(S.DeferredParams), C.c_int]
 lib.hrpt_halton.argtypes = [C.c_uint32, C.c_uint32]
 lib.hrpt_halton.restype = C.c_float
 lib.hrpt_precompute_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -460,6 +466,43 @@ def probes_query_host(volume, irradiance, distance, points, nthreads=0):
     points = np.ascontiguousarray(points, S.ProbePoint)
     out = np.zeros((len(points), 4), np.float32)
     _check_rc(lib.hrpt_probes_query_host(v.ctypes.data, irr.ctypes.data, dist.ctypes.data, points.ctypes.data, out.ctypes.data, len(points), int(nthreads)))
+    return out
+
+
+def deferred_rays_host(depth, normal, constants, lights, first_light=0, light_count=None):
+    """hrpt_deferred_rays_host: the shadow-ray records (S.Ray [light_count, H, W]) of lights[first_light : first_light + light_count] at every
+    pixel of the float32 [H, W, 4] planes S.GB_DEPTH / S.GB_NORMAL rendered with `constants` (csrc/pt_deferred.h). A lit
+    pair: origin X, direction L, tmax = the distance to the light; an unlit pair or a miss: origin NaN, the rest 0. Needs no GPU."""
+    (depth, normal), _, shape = _same_shape_images("deferred_rays_host", (depth, normal))
+    lights = np.ascontiguousarray(lights, S.GPULight).reshape(-1)
+    light_count = len(lights) - first_light if light_count is None else int(light_count)
+    if first_light < 0 or light_count < 0 or first_light + light_count > len(lights):
+        raise ValueError("deferred_rays_host: light range outside the list")
+    rays = np.zeros((light_count, shape[0], shape[1]), S.Ray)
+    im = S.DeferredImages(None, normal.ctypes.data, None, None, depth.ctypes.data, None, None)
+    cb = np.ascontiguousarray(constants)
+    _check_rc(lib.hrpt_deferred_rays_host(C.byref(im), shape[1], shape[0], cb.ctypes.data, lights.ctypes.data if len(lights) else None, int(first_light), light_count,
+                                          rays.ctypes.data if light_count else None))
+    return rays
+
+
+def deferred_shade_host(albedo, normal, geo_normal, emissive, depth, constants, lights, visibility=None, sun_radiance=None, sky=None, indirect=None,
+                        params=None, nthreads=0):
+    """hrpt_deferred_shade_host: the lit image, float32 [H, W, 4], of all `lights` over the five float32 [H, W, 4] planes; needs no GPU and is
+    bit-identical to PathTracerContext.deferred_lighting / deferred_lighting_device given the same visibilities and atmosphere terms.
+    visibility: float32 [len(lights), H, W] (None = 1); sun_radiance: [H, W, 4], the radiance of a directional light at each first hit (None =
+    colour x intensity); sky: [H, W, 4] stored at misses (None = zeros); indirect: [H, W, 4], read with S.DEFERRED_INDIRECT in params.flags."""
+    imgs, (sun, sk, ind), shape = _same_shape_images("deferred_shade_host", (albedo, normal, geo_normal, emissive, depth), sun_radiance=sun_radiance, sky=sky, indirect=indirect)
+    lights = np.ascontiguousarray(lights, S.GPULight).reshape(-1)
+    vis = None if visibility is None else np.ascontiguousarray(visibility, np.float32)
+    if vis is not None and vis.shape != (len(lights), shape[0], shape[1]):
+        raise ValueError("deferred_shade_host: visibility must be [lights, H, W]")
+    params = params if params is not None else S.DeferredParams()
+    out = np.empty(shape, np.float32)
+    im = S.DeferredImages(*[a.ctypes.data for a in imgs], _ptr(ind), out.ctypes.data)
+    cb = np.ascontiguousarray(constants)
+    _check_rc(lib.hrpt_deferred_shade_host(C.byref(im), shape[1], shape[0], cb.ctypes.data, lights.ctypes.data if len(lights) else None, len(lights), _ptr(vis), _ptr(sun),
+                                           _ptr(sk), C.byref(params), int(nthreads)))
     return out
 
 
@@ -1120,6 +1163,22 @@ class PathTracerContext:
     def modulation_device(self):
         """Device pointer of that image (None before the first demodulate and after a resize)."""
         return self._device_ptr(lib.hrpt_get_modulation_device)
+
+    def deferred_lighting(self, constants, params=None):
+        """hrpt_deferred_lighting: direct light with traced shadows, sky and optional probe indirect at the first hits, from the planes
+        S.GB_ALBEDO, S.GB_NORMAL, S.GB_GEO_NORMAL, S.GB_EMISSIVE and S.GB_DEPTH of a render_gbuffer / render_motion_vectors with the same
+        `constants`, into Output (csrc/pt_deferred.h). Accumulation is not touched. Default params: shadows and sky.
+        Asynchronous."""
+        params = params if params is not None else S.DeferredParams(S.DEFERRED_SHADOWS | S.DEFERRED_SKY)
+        cb = np.ascontiguousarray(constants)
+        self._check(lib.hrpt_deferred_lighting(self._h, cb.ctypes.data, C.byref(params)))
+
+    def deferred_lighting_device(self, images, width, height, constants, params=None, hip_stream=0):
+        """The same over caller-owned device images (S.DeferredImages of device addresses), with this context's scene and lights, every step
+        on `hip_stream` (integer handle)."""
+        params = params if params is not None else S.DeferredParams(S.DEFERRED_SHADOWS | S.DEFERRED_SKY)
+        cb = np.ascontiguousarray(constants)
+        self._check(lib.hrpt_deferred_lighting_device(self._h, C.byref(images), int(width), int(height), cb.ctypes.data, C.byref(params), C.c_void_p(int(hip_stream))))
 
     def read_display(self):
         return self._read_image(lib.hrpt_read_display)

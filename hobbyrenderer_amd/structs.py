@@ -272,6 +272,22 @@ ProbePoint = np.dtype([("position", f32, 3), ("pad0", f32), ("normal", f32, 3), 
 assert ProbeVolume.itemsize == 64 and ProbePoint.itemsize == 48
 PROBES_RESET, PROBES_DEVICE_POINTERS = 1, 0x100
 PROBE_IRRADIANCE_SHAPE, PROBE_DISTANCE_SHAPE = (8, 8, 4), (16, 16, 2)      # one probe's tiles; the atlases are [P, 8, 8, 4] and [P, 16, 16, 2]
+# deferred lighting (hrpt_deferred_lighting)
+DEFERRED_SHADOWS, DEFERRED_SKY, DEFERRED_INDIRECT = 1, 2, 4
+
+
+class DeferredParams(C.Structure):
+    """HrptDeferredParams. flags: DEFERRED_SHADOWS traces one shadow ray per lit (pixel, light) pair, DEFERRED_SKY takes the sky at misses and
+    the sun's radiance from the atmosphere, DEFERRED_INDIRECT adds the diffuse indirect image times indirectIntensity."""
+    _fields_ = [("flags", C.c_uint32), ("indirectIntensity", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, flags=0, indirectIntensity=1.0):
+        super().__init__(flags, indirectIntensity)
+
+
+class DeferredImages(C.Structure):
+    """HrptDeferredImages: host or device addresses of width x height float4 images; indirect may be None without DEFERRED_INDIRECT."""
+    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "geoNormal", "emissive", "depth", "indirect", "colorOut")]
 
 
 class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B

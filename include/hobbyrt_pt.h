@@ -1069,6 +1069,64 @@ int  hrpt_probes_blend_device(HrptContext* ctx, const HrptProbeVolume* volume, c
 int  hrpt_probes_query_host(const HrptProbeVolume* volume, const float* irradiance, const float* distance, const HrptProbePoint* points, float* out4,
                             uint64_t count, int nthreads);
 
+/* ---- deferred lighting -----------------------------------------------------------------------------------------------------
+ * Turns the first-hit G-buffer into a lit image: the reference's DeferredLighting.hlsl with AccumulateDirectLighting
+ * (src/shaders/CommonLighting.hlsli:501-603) and Sky.hlsl, over the planes HRPT_GB_ALBEDO (A), HRPT_GB_NORMAL (N, roughness in .w),
+ * HRPT_GB_GEO_NORMAL (metallic in .w), HRPT_GB_EMISSIVE (E) and HRPT_GB_DEPTH (.x = t, miss == 1e10f) of a frame rendered with `constants`.
+ * One source for kernels and host executors: hobbyrenderer_amd/csrc/pt_deferred.h; DESIGN.md section 27 has every operation in order.
+ * Per pixel: (o, d) = the primary ray of `constants` (no RNG). Miss: (sky_radiance(o, d, sun, I0, sun disk), 1) with HRPT_DEFERRED_SKY,
+ * else (0, 0, 0, 0); I0 = lights[0].m_Intensity (0 with an empty list). Hit: X = o + d * t, V = -d, ior 1.5; lights 0 .. m_LightCount - 1 in
+ * order -- directional: L = m_SunDirection, skipped when dot(N, L) <= 0, radiance = sun_radiance(X) with HRPT_DEFERRED_SKY else m_Color *
+ * m_Intensity; point / spot: the culls of the path tracer's light sample (intensity, range, spot facing and outer cone), L = normalize(
+ * m_Position - X) (m_Radius ignored: hard shadows), skipped when dot(N, L) <= 0, radiance with distance and cone attenuation; other types
+ * skipped -- each adding (diffuse, specular) of EvaluateDirectLight times vis, vis = CalculateRTShadow<true>(X, L, maxDist) with
+ * HRPT_DEFERRED_SHADOWS else 1. rgb = (sumDiffuse + sumSpecular) + E.rgb; with HRPT_DEFERRED_INDIRECT, where the indirect texel's w == 1,
+ * rgb += (((irr.rgb * A.rgb) * (1 - metallic)) * 0.31830988618f) * indirectIntensity; alpha = A.a.
+ * Differences from DeferredLighting.hlsl, on purpose: X and V come from the primary ray and t, not from a depth reconstruction at the pixel
+ * centre; the sun's shadow goes through CalculateRTShadow<true> like the path tracer's; point lights are lit (the reference's raster loop
+ * skips type 1); the CSM mask, IBL, ReSTIR / SHARC / SSGI inputs and the debug views are not reproduced. */
+#define HRPT_DEFERRED_SHADOWS  1u   /* one shadow ray per lit (pixel, light) pair through hrpt_trace_rays(HRPT_RAYS_SHADOW) */
+#define HRPT_DEFERRED_SKY      2u   /* the atmosphere: sky at misses, sun_radiance(X) for directional lights */
+#define HRPT_DEFERRED_INDIRECT 4u   /* add the diffuse indirect image (context call: the plane of hrpt_probes_shade_gbuffer) */
+typedef struct HrptDeferredParams {
+    uint32_t flags;              /* HRPT_DEFERRED_* */
+    float indirectIntensity;     /* finite; read with HRPT_DEFERRED_INDIRECT */
+    uint32_t reserved[2];        /* 0 */
+} HrptDeferredParams;
+typedef struct HrptDeferredImages {
+    const float *albedo, *normal, *geoNormal, *emissive, *depth;
+    const float *indirect;       /* NULL unless HRPT_DEFERRED_INDIRECT */
+    float *colorOut;             /* must differ from every other image */
+} HrptDeferredImages;
+/* Over the context's own planes into Output (Accumulation is not touched, like hrpt_demodulate). Three steps per batch of B consecutive
+ * lights (B = min(m_LightCount, 4); HRPT_DEFERRED_LIGHT_BATCH = 1..16 at hrpt_create overrides it; the result does not depend on B, bit for
+ * bit): a kernel writes one HrptRay per (light in batch, pixel) at g = j * W * H + y * W + x (a lit pair: origin X, direction L, tmin 0,
+ * tmax maxDist; an unlit pair or a miss: origin = NaN, the rest 0, which hrpt_trace_rays does not trace), hrpt_trace_rays(HRPT_RAYS_SHADOW |
+ * HRPT_RAYS_DEVICE_POINTERS) on library-owned buffers (W * H * B records, allocated on first use, dropped by hrpt_resize; skipped without
+ * HRPT_DEFERRED_SHADOWS), and a shade kernel that adds the batch's lights into running sums and on the last batch writes Output. The
+ * result equals, bit for bit, hrpt_deferred_rays_host -> hrpt_trace_rays -> hrpt_deferred_shade_host through the public calls.
+ * Asynchronous on the context stream. No scene: HRPT_ERR_NO_SCENE. hrpt_resize not called, one of the five planes never requested (the
+ * message names it), HRPT_DEFERRED_INDIRECT without a probe plane at the current size (the message names hrpt_probes_shade_gbuffer),
+ * m_LightCount above the scene's light count, unknown flag bits, non-zero reserved, a non-finite indirectIntensity:
+ * HRPT_ERR_INVALID_ARGUMENT. An error changes nothing. */
+int  hrpt_deferred_lighting(HrptContext* ctx, const HrptPathTracerConstants* constants, const HrptDeferredParams* params);
+/* The same over caller-owned DEVICE images of width x height float4 (16-byte aligned), with the scene, lights and ray buffers of `ctx`;
+ * every step runs on `stream` (a hipStream_t; NULL = the default stream). */
+int  hrpt_deferred_lighting_device(HrptContext* ctx, const HrptDeferredImages* deviceImages, uint32_t width, uint32_t height,
+                                   const HrptPathTracerConstants* constants, const HrptDeferredParams* params, void* stream);
+/* The two stages on the host, with no GPU and no scene; same bits as the kernels. `lights` is a host array; constants->m_LightCount is
+ * not read (the arguments say which lights).
+ * rays: raysOut receives lightCount * width * height records for lights[firstLight .. firstLight + lightCount), laid out as above.
+ * shade: all of lights[0 .. lightCount) in one pass. visibility: float [lightCount][height][width], read at lit pairs only, NULL = 1.
+ * sunRadiance: a float4 image, rgb = the radiance of a directional light at the pixel's X, NULL = m_Color * m_Intensity. sky: a float4
+ * image whose texel is stored at a miss, NULL = (0, 0, 0, 0). The atmosphere terms enter as images because the tables live with a
+ * scene; the device path computes them in the kernel. params->flags: only HRPT_DEFERRED_INDIRECT is read (images->indirect required). */
+int  hrpt_deferred_rays_host(const HrptDeferredImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
+                             const HrptGPULight* lights, uint32_t firstLight, uint32_t lightCount, HrptRay* raysOut);
+int  hrpt_deferred_shade_host(const HrptDeferredImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
+                              const HrptGPULight* lights, uint32_t lightCount, const float* visibility, const float* sunRadiance, const float* sky,
+                              const HrptDeferredParams* params, int nthreads);
+
 /* Intra-frame overlap: by default the shadow stage of bounce b runs on a second, library-owned stream next to the traversal of bounce
  * b + 1 (they share no buffer). That fills the tails of a context that renders one frame at a time (-3 % per frame). A host that keeps
  * two frames in flight on two contexts already fills those tails with the other frame; there the fork / join events only cost
