@@ -46,14 +46,14 @@ __global__ __launch_bounds__(img::kTileX * img::kTileY) void deferred_shade(Scen
     if (!img::stage_pixel(f.w, f.h, &px, &py)) return;
     const size_t idx = img::stage_index(f.w, px, py), WH = (size_t)f.w * (size_t)f.h;
     const T4 D = img::ld4(depth, idx);
-    T3 o, d;
-    primary_ray(f, px, py, &o, &d);
-    const T3 sunDir = t3(f.sun[0], f.sun[1], f.sun[2]);
+    f3 o, d;
+    frame_ray(f, px, py, o, d);
+    const f3 sunDir = mk3(f.sun);
     if (D.x == img::kMissDepth) {
         if (!isLast) return;
         T4 sky = t4(0.0f, 0.0f, 0.0f, 0.0f);
         if (f.flags & HRPT_DEFERRED_SKY) {
-            const f3 r = atm::sky_radiance(scene, mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), mk3(sunDir.x, sunDir.y, sunDir.z), f.sunIntensity, true);
+            const f3 r = atm::sky_radiance(scene, o, d, sunDir, f.sunIntensity, true);
             sky = t4(r.x, r.y, r.z, 1.0f);
         }
         img::st4(out, idx, sky);
@@ -61,20 +61,15 @@ __global__ __launch_bounds__(img::kTileX * img::kTileY) void deferred_shade(Scen
     }
     const T4 A = img::ld4(albedo, idx);
     const float metallic = geoNormal[idx].w;
-    const T3 X = hit_position(o, d, D.x);
-    const Surface s = make_surface(A, img::ld4(normal, idx), metallic, d);
-    T3 totalD = t3(0.0f, 0.0f, 0.0f), totalS = totalD;
-    if (!isFirst) {
-        const T4 cd = img::ld4(carryD, idx), cs = img::ld4(carryS, idx);
-        totalD = t3(cd.x, cd.y, cd.z); totalS = t3(cs.x, cs.y, cs.z);
-    }
+    const f3 X = o + d * D.x;
+    const Lighting s = make_surface(A, img::ld4(normal, idx), metallic, d);
+    f3 totalD = mk3(0.0f, 0.0f, 0.0f), totalS = totalD;
+    if (!isFirst) { totalD = xyz(img::ld4(carryD, idx)); totalS = xyz(img::ld4(carryS, idx)); }
     add_lights(s, X, sunDir, lights, first, count,
                [&](const HrptGPULight& l) {
-                   if (!(f.flags & HRPT_DEFERRED_SKY)) return light_color(l);
-                   const f3 r = atm::sun_radiance(scene, atm::atmosphere_pos(mk3(X.x, X.y, X.z)), mk3(sunDir.x, sunDir.y, sunDir.z), f.sunIntensity);
-                   return t3(r.x, r.y, r.z);
+                   return (f.flags & HRPT_DEFERRED_SKY) ? atm::sun_radiance(scene, atm::atmosphere_pos(X), sunDir, f.sunIntensity) : light_color(l);
                },
-               [&](uint32_t j) { return hits ? hits[(size_t)j * WH + idx].t : 1.0f; }, &totalD, &totalS);
+               [&](uint32_t j) { return hits ? hits[(size_t)j * WH + idx].t : 1.0f; }, totalD, totalS);
     if (!isLast) {
         img::st4(carryD, idx, t4(totalD.x, totalD.y, totalD.z, 0.0f));
         img::st4(carryS, idx, t4(totalS.x, totalS.y, totalS.z, 0.0f));

@@ -35,7 +35,7 @@ void deferred_shade_host(const HrptDeferredImages& im, uint32_t width, uint32_t 
 {
     const Frame f = make_frame(cb, params, 0.0f, (int)width, (int)height);
     const size_t WH = (size_t)width * height;
-    const T3 sunDir = t3(f.sun[0], f.sun[1], f.sun[2]);
+    const f3 sunDir = mk3(f.sun);
     over_rows(f.h, nthreads, [&](int py) {
         for (int px = 0; px < f.w; ++px) {
             const size_t idx = (size_t)py * width + px;
@@ -47,14 +47,14 @@ void deferred_shade_host(const HrptDeferredImages& im, uint32_t width, uint32_t 
             }
             const T4 A = load4(im.albedo, f.w, px, py), E = load4(im.emissive, f.w, px, py);
             const float metallic = load4(im.geoNormal, f.w, px, py).w;
-            T3 o, d;
-            primary_ray(f, px, py, &o, &d);
-            const T3 X = hit_position(o, d, D.x);
-            const Surface s = make_surface(A, load4(im.normal, f.w, px, py), metallic, d);
-            T3 totalD = t3(0.0f, 0.0f, 0.0f), totalS = totalD;
+            f3 o, d;
+            frame_ray(f, px, py, o, d);
+            const f3 X = o + d * D.x;
+            const Lighting s = make_surface(A, load4(im.normal, f.w, px, py), metallic, d);
+            f3 totalD = mk3(0.0f, 0.0f, 0.0f), totalS = totalD;
             add_lights(s, X, sunDir, lights, 0u, lightCount,
-                       [&](const HrptGPULight& l) { if (!sunRadiance) return light_color(l); const T4 r = load4(sunRadiance, f.w, px, py); return t3(r.x, r.y, r.z); },
-                       [&](uint32_t j) { return visibility ? visibility[(size_t)j * WH + idx] : 1.0f; }, &totalD, &totalS);
+                       [&](const HrptGPULight& l) { return sunRadiance ? xyz(load4(sunRadiance, f.w, px, py)) : light_color(l); },
+                       [&](uint32_t j) { return visibility ? visibility[(size_t)j * WH + idx] : 1.0f; }, totalD, totalS);
             const T4 irr = (f.flags & HRPT_DEFERRED_INDIRECT) ? load4(im.indirect, f.w, px, py) : t4(0.0f, 0.0f, 0.0f, 0.0f);
             store4(out, finish_hit(f, A, E, metallic, totalD, totalS, irr));
         }

@@ -18,7 +18,8 @@
 #include "../../include/hobbyrt/srgb_table.h"
 
 // The code, one subject per header. Every header includes what it needs; this order is the order of declaration the kernels were built with,
-// and keeping it keeps their code objects as they are.
+// and keeping it keeps their code objects as they are. pt_vec.h, pt_lighting.h and pt_direct.h are __host__ __device__ and need no HIP
+// runtime: the deferred stage's host executors and its sanitizer program build them with a plain C++ compiler.
 #include "pt_phase.h"
 #include "pt_vec.h"
 #include "pt_scene_records.h"
@@ -27,4 +28,5 @@
 #include "pt_texture.h"
 #include "pt_atmosphere.h"
 #include "pt_lighting.h"
+#include "pt_direct.h"
 #include "pt_surface.h"

@@ -33,18 +33,8 @@ struct SurfaceCarry {
 
 HRT_DEV void init_path(PathState& ps, const HrptPathTracerConstants& cb, uint32_t px, uint32_t py)
 {
-    // primary ray, PathTracer.hlsl:61-72; UVToClipXY Common.hlsli:50-53
-    float u = (((float)px + 0.5f) + cb.m_Jitter[0]) * cb.m_View.m_ViewportSizeInv[0];
-    float v = (((float)py + 0.5f) + cb.m_Jitter[1]) * cb.m_View.m_ViewportSizeInv[1];
-    float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;
-    const float* M = cb.m_View.m_MatClipToWorldNoOffset;
-    float ex = ((cx * M[0] + cy * M[4]) + 0.9f * M[8]) + 1.0f * M[12];
-    float ey = ((cx * M[1] + cy * M[5]) + 0.9f * M[9]) + 1.0f * M[13];
-    float ez = ((cx * M[2] + cy * M[6]) + 0.9f * M[10]) + 1.0f * M[14];
-    float ew = ((cx * M[3] + cy * M[7]) + 0.9f * M[11]) + 1.0f * M[15];
-    f3 end = mk3(ex / ew, ey / ew, ez / ew);
-    ps.ray.o = mk3(cb.m_CameraPos[0], cb.m_CameraPos[1], cb.m_CameraPos[2]);
-    ps.ray.d = normalize(end - ps.ray.o);
+    camera_ray(cb.m_View.m_MatClipToWorldNoOffset, cb.m_CameraPos, cb.m_Jitter[0], cb.m_Jitter[1], cb.m_View.m_ViewportSizeInv[0],
+               cb.m_View.m_ViewportSizeInv[1], px, py, ps.ray.o, ps.ray.d);
     ps.ray.tmin = 0.0f; ps.ray.tmax = 1e10f;
     ps.rng = hrt_rng_seed(px, py, cb.m_AccumulationIndex);        // RNG.hlsli:21-27
     ps.throughput = mk3(1.0f, 1.0f, 1.0f); ps.radiance = mk3(0.0f, 0.0f, 0.0f);
@@ -91,29 +81,7 @@ HRT_DEV bool trace_standard(const SceneView& s, const BVH& bvh, const Ray& ray, 
 //   nee_contribution  radiance (sun: atmosphere LUT; point/spot: attenuation) + per-sample byproducts + EvaluateDirectLight
 //                     without the shadow factor
 // DIRONLY: the scene's light list is known to hold directional lights only (point/spot code compiled out).
-template <bool DIRONLY>
-HRT_DEV bool nee_draw(const HrptGPULight& l, f3 N, f3 worldPos, f3 sunDirection, uint32_t& rng, float& ux, float& uy)
-{
-    if (DIRONLY || l.m_Type == HRPT_LIGHT_DIRECTIONAL) {                        // :716-745
-        if (dot(N, sunDirection) <= 0.0f) return false;
-    } else if (!DIRONLY && (l.m_Type == HRPT_LIGHT_POINT || l.m_Type == HRPT_LIGHT_SPOT)) {   // :752-804, :809-874
-        if (l.m_Intensity <= 0.0f) return false;
-        f3 toLight = mk3(l.m_Position) - worldPos;
-        float distSq = dot(toLight, toLight);
-        if (l.m_Range > 0.0f && distSq > l.m_Range * l.m_Range) return false;
-        if (l.m_Type == HRPT_LIGHT_SPOT) {
-            float dist = hrt_sqrt(distSq);
-            f3 Lc = toLight / dist;
-            if (dot(N, Lc) <= 0.0f) return false;
-            f3 lightDir = normalize(mk3(l.m_Direction));
-            float cosTheta = dot(-Lc, lightDir);
-            if (cosTheta < hrt_cos(l.m_SpotOuterConeAngle)) return false;
-        }
-    } else return false;
-    ux = hrt_rng_next(&rng); uy = hrt_rng_next(&rng);
-    return true;
-}
-
+// nee_draw reads no scene and lives in pt_direct.h, where the deferred stage shares its culls.
 template <bool DIRONLY>
 HRT_DEV bool nee_direction(const HrptGPULight& l, f3 N, f3 worldPos, f3 sunDirection, float cosSun, float ux, float uy, f3& L, float& maxDist)
 {
@@ -144,6 +112,7 @@ HRT_DEV void nee_contribution(const SceneView& s, const HrptGPULight& l, Lightin
         // inputs.sunRadiance (PathTracer.hlsl:137): a pure function of the hit position, read only by directional lights
         radiance = atm::sun_radiance(s, atm::atmosphere_pos(worldPos), sunDirection, sunIntensity);
     } else {
+        // deferred::light_radiance (pt_deferred.h) is a deliberate copy of this branch: DESIGN.md section 27
         f3 toLight = mk3(l.m_Position) - worldPos;
         float distSq = dot(toLight, toLight);
         float dist = hrt_sqrt(distSq);
@@ -161,14 +130,6 @@ HRT_DEV void nee_contribution(const SceneView& s, const HrptGPULight& l, Lightin
     in.L = L;
     prepare_byproducts(in);
     evaluate_direct_unshadowed(in, radiance, diffuse, specular);
-}
-
-// The surface terms a deferred NEE evaluation needs (what LightingInputs carries into AccumulateDirectLighting).
-HRT_DEV Lighting nee_lighting(f3 N, f3 V, f3 baseColor, float roughness, float metallic, float ior)
-{
-    Lighting in;
-    in.N = N; in.V = V; in.L = mk3(0.0f, 0.0f, 0.0f); in.baseColor = baseColor; in.roughness = roughness; in.metallic = metallic; in.ior = ior;
-    return in;
 }
 
 HRT_DEV HrptGPULight load_light(const SceneView& s, uint32_t i)

@@ -4,6 +4,7 @@
 // block), a single 256-thread adaptation block that reduces with the reference's shared-memory tree (same order => same
 // bits as the oracle), and a streaming tonemap (float4 in, float4 out).
 #include "pt_kernels.h"
+#include "pt_phase.h"
 #include "pt_vec.h"
 
 namespace hrt {

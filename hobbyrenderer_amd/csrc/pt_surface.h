@@ -1,4 +1,4 @@
-// pt_surface.h -- candidate alpha, hit attributes and PBR evaluation of a surface point, light distance attenuation.
+// pt_surface.h -- candidate alpha, hit attributes and PBR evaluation of a surface point.
 #pragma once
 
 #include "pt_shade_tables.h"
@@ -184,18 +184,6 @@ HRT_DEV Pbr pbr_attributes(const SceneView& s, const SurfaceAttr& a, const HrptM
         p.normal = normal_with_tbn(t.x, t.y, a.worldNormal, a.worldTangent, a.tangentSign);
     } else p.normal = normalize(a.worldNormal);
     return p;
-}
-
-// Light distance attenuation, CommonLighting.hlsli:766-769 / :835-837 (pow(x,4), pow(x,2) by multiplication)
-HRT_DEV float distance_attenuation(const HrptGPULight& l, float distSq, float dist)
-{
-    float a = 1.0f / (distSq + 1.0f);
-    if (l.m_Range > 0.0f) {
-        float q = dist / l.m_Range; float q2 = q * q; float q4 = q2 * q2;
-        float sa = hrt_saturate(1.0f - q4);
-        a *= sa * sa;
-    }
-    return a;
 }
 
 } // namespace hrt

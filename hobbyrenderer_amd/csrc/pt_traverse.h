@@ -3,6 +3,7 @@
 #pragma once
 
 #include "pt_scene_records.h"
+#include "pt_phase.h"
 #include "pt_vec.h"
 
 namespace hrt {

@@ -72,7 +72,8 @@ HRT_DEV bool primary_ray(const WfArgs& a, const PrimaryArgs& pr, uint32_t smp, f
     uint32_t tcol, trow; tile_position(a, tile, tcol, trow);
     const uint32_t px = a.rect.column_x(tcol) + (within & 7u), py = a.rect.y0 + trow * 8u + (within >> 3);
     if (!(px < a.rect.x1 && py < a.rect.y1)) return false;
-    // init_path (pt_path.h) with the jitter / RNG stream of accumulation index first + k (PathTracerRenderer.cpp:62,:65)
+    // a deliberate copy of camera_ray's body (pt_direct.h) with the jitter / RNG stream of accumulation index
+    // first + k (PathTracerRenderer.cpp:62,:65)
     const float u = (((float)px + 0.5f) + pr.j[k].x) * pr.invW;
     const float v = (((float)py + 0.5f) + pr.j[k].y) * pr.invH;
     const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;

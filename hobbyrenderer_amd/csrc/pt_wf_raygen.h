@@ -38,21 +38,10 @@ __global__ __launch_bounds__(kBlock) void wf_raygen(WfArgs a, HrptPathTracerCons
             unsigned long long m = __ballot(active);
             if (active) {
                 PathState ps;
-                {
-                    // init_path (pt_path.h) with the jitter / RNG stream of accumulation index first+k (PathTracerRenderer.cpp:62,:65)
-                    float u = (((float)px + 0.5f) + jt.j[k].x) * cb.m_View.m_ViewportSizeInv[0];
-                    float v = (((float)py + 0.5f) + jt.j[k].y) * cb.m_View.m_ViewportSizeInv[1];
-                    float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;
-                    const float* M = cb.m_View.m_MatClipToWorldNoOffset;
-                    float ex = ((cx * M[0] + cy * M[4]) + 0.9f * M[8]) + 1.0f * M[12];
-                    float ey = ((cx * M[1] + cy * M[5]) + 0.9f * M[9]) + 1.0f * M[13];
-                    float ez = ((cx * M[2] + cy * M[6]) + 0.9f * M[10]) + 1.0f * M[14];
-                    float ew = ((cx * M[3] + cy * M[7]) + 0.9f * M[11]) + 1.0f * M[15];
-                    f3 end = mk3(ex / ew, ey / ew, ez / ew);
-                    ps.ray.o = mk3(cb.m_CameraPos[0], cb.m_CameraPos[1], cb.m_CameraPos[2]);
-                    ps.ray.d = normalize(end - ps.ray.o);
-                    ps.rng = hrt_rng_seed(px, py, cb.m_AccumulationIndex + k);
-                }
+                // camera_ray (pt_direct.h) with the jitter / RNG stream of accumulation index first+k (PathTracerRenderer.cpp:62,:65)
+                camera_ray(cb.m_View.m_MatClipToWorldNoOffset, cb.m_CameraPos, jt.j[k].x, jt.j[k].y, cb.m_View.m_ViewportSizeInv[0],
+                           cb.m_View.m_ViewportSizeInv[1], px, py, ps.ray.o, ps.ray.d);
+                ps.rng = hrt_rng_seed(px, py, cb.m_AccumulationIndex + k);
                 uint32_t o = segBase + outCount + prefix_rank(m);
                 a.b.rayO[0][o] = make_float4(ps.ray.o.x, ps.ray.o.y, ps.ray.o.z, 0.0f);
                 a.b.rayD[0][o] = make_float4(ps.ray.d.x, ps.ray.d.y, ps.ray.d.z, __uint_as_float(ps.rng));
