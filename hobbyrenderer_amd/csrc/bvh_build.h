@@ -127,6 +127,11 @@ bool rebuild_two_level_instances(const HrptSceneDesc& scene, BuiltTwoLevel& out,
 constexpr uint32_t kMaxLeafTris = 4;
 constexpr uint32_t kTraversalStackDepth = 64;   // 2-wide trees: the builders guarantee depth + 2 <= this (private / LDS + overflow stacks of the kernels)
 constexpr uint32_t kHostBuilderDepthGoal = 32;  // the host SAH builder switches to median splits early enough to stay below this
+// Entries of the private stack of the thread-per-query kernels (pt_megakernel.hip PrivateStack), which wraps its index with a mask. Every
+// 2-wide tree fits by the builders' guarantee; a two-level structure that needs more (two_level_stack_need) is refused by the C API.
+constexpr uint32_t kPrivateStackDepth = 64;
+static_assert((kPrivateStackDepth & (kPrivateStackDepth - 1u)) == 0u, "PrivateStack masks its index: the depth is a power of two");
+static_assert(kPrivateStackDepth >= kTraversalStackDepth, "the private stack holds every 2-wide tree the builders make");
 
 // Validates every index / range of the scene description (false + message); triCount = world triangles over all instances.
 // (flatLimit: the traversal kernels address nodes and triangle records by 32-bit byte offsets from the array base (pt_traverse.h GlobalBvh4), so one

@@ -70,7 +70,7 @@ static int common_check(HrptContext* c, const char* what, const HrptPathTracerCo
     if (!constants || !params) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
     if (!deferred_params_valid(*params)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + kParamsRule);
     if (constants->m_LightCount > c->view.lightCount) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": m_LightCount exceeds the scene's light buffer");
-    if ((params->flags & HRPT_DEFERRED_SHADOWS) && c->view.instances && !wavefront_trace_rays_supported(c->traits) && c->traits.twoLevelStackNeed > 64u)
+    if ((params->flags & HRPT_DEFERRED_SHADOWS) && c->view.instances && !wavefront_trace_rays_supported(c->traits) && exceeds_private_stack(c->traits))
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": this two-level structure is deeper than the thread-per-ray kernel's 64-entry stack");
     return HRPT_OK;
 }

@@ -166,6 +166,11 @@ inline int host_threads(int nthreads)
     return nthreads > 256 ? 256 : nthreads;
 }
 
+// The scene's two-level structure needs more stack than the thread-per-query kernels have (bvh_build.h kPrivateStackDepth): the calls that
+// would run one of them refuse.
+static_assert(kPrivateStackDepth == 64u, "the refusal messages say \"64-entry stack\"; tests match on them");
+inline bool exceeds_private_stack(const SceneTraits& traits) { return traits.twoLevelStackNeed > kPrivateStackDepth; }
+
 inline bool size_ok(uint32_t width, uint32_t height) { return !(width == 0 || height == 0 || width > 65535u || height > 65535u); }
 int realloc_image(HrptContext* c, DeviceBuffer<float4>& image, size_t bytes);      // a fresh image, zeroed on the context stream
 int read_image(HrptContext* c, const float4* src, float* dst, size_t bytes, const char* what);

@@ -34,7 +34,7 @@ try {
     HIP_TRY(c, hipSetDevice(c->device));
 
     bool wavefront = (p->flags & HRPT_FRAME_MEGAKERNEL) == 0 && wavefront_supports(c->view, p->constants);
-    if (!wavefront && c->view.instances && c->traits.twoLevelStackNeed > 64u)
+    if (!wavefront && c->view.instances && exceeds_private_stack(c->traits))
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_render: this two-level structure is deeper than the validation megakernel's 64-entry stack");
     if (!wavefront && (p->flags & HRPT_FRAME_MEGAKERNEL) == 0) c->megakernelFallbacks++;
     HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
@@ -123,7 +123,7 @@ static int render_gbuffer_impl(HrptContext* c, const HrptFrameParams* p, uint32_
     HRPT_TRY(frame_rect(c, what, *p, rect));
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = (p->flags & HRPT_FRAME_MEGAKERNEL) == 0;
-    if (!wavefront && c->view.instances && c->traits.twoLevelStackNeed > 64u)
+    if (!wavefront && c->view.instances && exceeds_private_stack(c->traits))
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": this two-level structure is deeper than the validation kernel's 64-entry stack");
     const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
     for (uint32_t k = 0; k < HRPT_GB_PLANES; ++k) {
@@ -259,7 +259,7 @@ try {
     if (!rays || !hits) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_rays: null array");
     if ((flags & 0xFFu) > HRPT_RAYS_SHADOW || (flags & ~(0xFFu | HRPT_RAYS_DEVICE_POINTERS | HRPT_RAYS_THREAD_PER_RAY))) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_rays: unknown flags");
     if (count > (1ull << 31)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_rays: too many rays in one call");
-    if (c->view.instances && ((flags & HRPT_RAYS_THREAD_PER_RAY) || !wavefront_trace_rays_supported(c->traits)) && c->traits.twoLevelStackNeed > 64u)
+    if (c->view.instances && ((flags & HRPT_RAYS_THREAD_PER_RAY) || !wavefront_trace_rays_supported(c->traits)) && exceeds_private_stack(c->traits))
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_rays: this two-level structure is deeper than the thread-per-ray kernel's 64-entry stack");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool shadow = (flags & 0xFFu) == HRPT_RAYS_SHADOW;
@@ -302,7 +302,7 @@ try {
     if (!rays || !radiance4) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: null array");
     if (count > (1ull << 31)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: too many rays in one call");
     const bool wavefront = !(flags & HRPT_RADIANCE_THREAD_PER_RAY) && wavefront_supports(c->view, *constants);
-    if (!wavefront && c->view.instances && c->traits.twoLevelStackNeed > 64u)
+    if (!wavefront && c->view.instances && exceeds_private_stack(c->traits))
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: this two-level structure is deeper than the thread-per-ray kernel's 64-entry stack");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool accumulate = (flags & HRPT_RADIANCE_ACCUMULATE) != 0;

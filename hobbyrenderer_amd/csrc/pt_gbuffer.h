@@ -2,7 +2,8 @@
 // pixel. Contents follow GBufferOut of the reference's real-time modes (src/shaders/BasePass.hlsl:184-192, 485-493), computed
 // by the path tracer's own stages: the primary ray and RNG seed of init_path, the hit of TraceRayStandard, GetFullHitAttributes +
 // GetPBRAttributes and the normal flip of PathTracer.hlsl:110-117 -- the surface hrpt_render shades at bounce 0 for the same constants.
-// Both kernels (wf_gbuffer of pt_wf_gbuffer.h, pt_gbuffer_kernel of pt_megakernel.hip) call gbuffer_texels / gbuffer_store below.
+// Both paths call gbuffer_texels / gbuffer_store below: wf_gbuffer and wf_gbuffer_motion of pt_wf_gbuffer.h, and pt_gbuffer_kernel and
+// pt_motion_kernel among the thread-per-query kernels of pt_megakernel.hip.
 #pragma once
 
 #include "pt_path.h"

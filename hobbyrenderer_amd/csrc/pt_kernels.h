@@ -34,19 +34,50 @@ struct TileRect {
     __host__ __device__ uint32_t column_x(uint32_t k) const { return x0 + (k * stripeCount + stripeIndex) * 8u; }
 };
 
+// ---- thread-per-query kernels (pt_megakernel.hip): the validation paths, one thread per pixel or ray with a private traversal stack
 // One dispatch of the reference shader: one path per pixel of `rect` for constants.m_AccumulationIndex.
-// Validation path: one thread per pixel, private traversal stack.
 hipError_t launch_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* accumulation,
                              float4* output, uint32_t imageWidth, TileRect rect, DeviceCounters* counters, hipStream_t stream);
 
-// First-hit G-buffer through the validation path (pt_gbuffer.h): planes[HRPT_GB_PLANES] device images of imageWidth x H float4, of which those in
+// First-hit G-buffer (pt_gbuffer.h): planes[HRPT_GB_PLANES] device images of imageWidth x H float4, of which those in
 // planeMask are written inside `rect`; constants.m_Jitter / m_AccumulationIndex are used as given.
 hipError_t launch_gbuffer_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* const* planes, uint32_t planeMask,
                                      uint32_t imageWidth, TileRect rect, hipStream_t stream);
 
-// First-hit motion vectors through the validation path (pt_motion.h): launch_gbuffer_megakernel's pass plus motion.plane; planeMask may be 0.
+// First-hit motion vectors (pt_motion.h): launch_gbuffer_megakernel's pass plus motion.plane; planeMask may be 0.
 hipError_t launch_motion_megakernel(const SceneView& scene, const HrptPathTracerConstants& constants, float4* const* planes, uint32_t planeMask,
                                     const MotionArgs& motion, uint32_t imageWidth, TileRect rect, hipStream_t stream);
+
+// Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
+hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
+
+// Path-traced radiance along a caller's rays (hrpt_trace_radiance): the megakernel's bounce loop from the ray's record;
+// radiance[i] = (L, 1), or with `accumulate` (old.rgb + L, old.w + 1). Device arrays.
+hipError_t launch_radiance_rays(const SceneView& scene, const HrptPathTracerConstants& constants, const HrptRay* rays, float4* radiance, uint64_t count,
+                                bool accumulate, hipStream_t stream);
+
+// ---- accumulation to output (pt_resolve.hip)
+// Output[xy] = accum.rgb / accum.a (PathTracer.hlsl:339) over the whole image; launch_resolve_columns: the same from the rank-major column
+// shards of an all-gather, with the assembled accumulation image when `accumulation` is not null.
+hipError_t launch_resolve(const float4* accumulation, float4* output, uint32_t pixelCount, hipStream_t stream);
+hipError_t launch_resolve_columns(const float4* shards, float4* accumulation, float4* output, uint32_t width, uint32_t height, uint32_t ranks, hipStream_t stream);
+
+// ---- the GpuNodeQ encoding (pt_bvh_nodes.hip)
+// The flat 4-wide tree in its 64-byte quantised form (pt_scene_records.h GpuNodeQ): out[i] from nodes4[i]. leafArea (two zeroed doubles, or null)
+// receives the summed surface area of the leaf boxes before / after the rounding: what the looser boxes will cost in triangle tests.
+hipError_t launch_quantise_nodes(const GpuNode4* nodes4, uint32_t count, GpuNodeQ* out, double* leafArea, hipStream_t stream);
+// Self-test: counts child boxes of the 2-wide and 4-wide trees that do not contain their subtree's boxes / triangle vertices (0 = sound).
+hipError_t launch_bvh_check(const SceneView& scene, unsigned long long* violations, hipStream_t stream);
+
+// ---- decode and lookup self-tests (pt_selftest.hip)
+// out[i] = device decode of the binary16 pattern i, i in [0, 65536); out512 = the unorm8 decode of every byte, then the division it replaces.
+hipError_t launch_unorm8_table(float* out512, hipStream_t stream);
+hipError_t launch_f16_table(float* out, hipStream_t stream);
+// results[i] = the shader's texture sampling functions on probes[i] (hrpt_selftest_sample_textures); device arrays.
+hipError_t launch_sample_textures(const SceneView& scene, uint32_t materialCount, const HrptTextureProbe* probes, HrptTextureProbeResult* results,
+                                  uint32_t count, hipStream_t stream);
+// results[i] = the run-time atmosphere lookups (sky radiance, sun radiance, transmittance) on probes[i] (hrpt_selftest_atmosphere); device arrays.
+hipError_t launch_atmosphere_probes(const SceneView& scene, const HrptAtmosphereProbe* probes, HrptAtmosphereProbeResult* results, uint32_t count, hipStream_t stream);
 
 // HDR post chain over `hdr` (W*H float4): histogram[256] + exposure[1] are context-owned device buffers.
 hipError_t launch_post_chain(const float4* hdr, float4* display, uint32_t pixelCount, const HrptPostParams& params, uint32_t* histogram,
@@ -162,31 +193,5 @@ uint32_t skin_vertices_host(const HrptSkinArgs& args, HrptVertexFloat* out, int 
 namespace anim { struct Tables; }
 hipError_t launch_animate(const anim::Tables& tables, const float* times, const uint32_t* groupFirst, const uint32_t* groupFirstHost, uint32_t groups,
                           float* trs, float* worlds, float* weights, float* palette, void* records, hipStream_t stream);
-
-// Batch ray queries (hrpt_trace_rays): closest hit with the candidate rules of TraceRayStandard, or NEE-style visibility.
-hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRayHit* hits, uint64_t count, bool shadow, hipStream_t stream);
-
-// Path-traced radiance along a caller's rays (hrpt_trace_radiance), validation path: one thread per ray, the megakernel's bounce loop from the
-// ray's record; radiance[i] = (L, 1), or with `accumulate` (old.rgb + L, old.w + 1). Device arrays.
-hipError_t launch_radiance_rays(const SceneView& scene, const HrptPathTracerConstants& constants, const HrptRay* rays, float4* radiance, uint64_t count,
-                                bool accumulate, hipStream_t stream);
-
-// The flat 4-wide tree in its 64-byte quantised form (pt_scene_records.h GpuNodeQ): out[i] from nodes4[i]. leafArea (two zeroed doubles, or null)
-// receives the summed surface area of the leaf boxes before / after the rounding: what the looser boxes will cost in triangle tests.
-hipError_t launch_quantise_nodes(const GpuNode4* nodes4, uint32_t count, GpuNodeQ* out, double* leafArea, hipStream_t stream);
-// Self-test: counts child boxes of the 2-wide and 4-wide trees that do not contain their subtree's boxes / triangle vertices (0 = sound).
-hipError_t launch_bvh_check(const SceneView& scene, unsigned long long* violations, hipStream_t stream);
-// Self-test: out[i] = device decode of the binary16 pattern i, i in [0, 65536).
-hipError_t launch_unorm8_table(float* out512, hipStream_t stream);
-hipError_t launch_f16_table(float* out, hipStream_t stream);
-// Self-test: results[i] = the shader's texture sampling functions on probes[i] (hrpt_selftest_sample_textures); device arrays.
-hipError_t launch_sample_textures(const SceneView& scene, uint32_t materialCount, const HrptTextureProbe* probes, HrptTextureProbeResult* results,
-                                  uint32_t count, hipStream_t stream);
-// Self-test: results[i] = the run-time atmosphere lookups (sky radiance, sun radiance, transmittance) on probes[i] (hrpt_selftest_atmosphere); device arrays.
-hipError_t launch_atmosphere_probes(const SceneView& scene, const HrptAtmosphereProbe* probes, HrptAtmosphereProbeResult* results, uint32_t count, hipStream_t stream);
-
-// Output[xy] = accum.rgb / accum.a (PathTracer.hlsl:339) over the whole image.
-hipError_t launch_resolve(const float4* accumulation, float4* output, uint32_t pixelCount, hipStream_t stream);
-hipError_t launch_resolve_columns(const float4* shards, float4* accumulation, float4* output, uint32_t width, uint32_t height, uint32_t ranks, hipStream_t stream);
 
 } // namespace hrt

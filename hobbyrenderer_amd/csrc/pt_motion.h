@@ -1,8 +1,8 @@
 // pt_motion.h -- screen-space motion of the first hit (hrpt_render_motion_vectors): ComputeMotionVectors of the reference
 // (src/shaders/CommonLighting.hlsli:242-260) fed as its raster pass feeds it (src/shaders/BasePass.hlsl:53,492): the INTERPOLATED vertex position
 // of the hit triangle under the instance's current and previous transform, each through its frame's jittered m_MatWorldToClip. The hit is the one
-// hrpt_render_gbuffer commits for the same constants. Both kernels (wf_gbuffer_motion of pt_wf_gbuffer.h, pt_motion_kernel of
-// pt_megakernel.hip) call motion_gather / motion_texel below; DESIGN.md section 16 has the definition.
+// hrpt_render_gbuffer commits for the same constants. Both kernels (wf_gbuffer_motion of pt_wf_gbuffer.h, pt_motion_kernel among the
+// thread-per-query kernels of pt_megakernel.hip) call motion_gather / motion_texel below; DESIGN.md section 16 has the definition.
 #pragma once
 
 #include "pt_gbuffer.h"

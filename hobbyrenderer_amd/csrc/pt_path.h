@@ -315,4 +315,13 @@ HRT_DEV void miss_sky(const SceneView& s, const HrptPathTracerConstants& cb, Pat
     ps.radiance = ps.radiance + ps.throughput * sky;
 }
 
+// A per-lane count (rays, paths) summed over the 64 lanes of the wave: the statistics of both pipelines.
+HRT_DEV unsigned long long wave_sum_u32(unsigned int v)
+{
+    unsigned long long x = v;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
 } // namespace hrt

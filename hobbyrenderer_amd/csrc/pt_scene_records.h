@@ -1,5 +1,5 @@
-// pt_scene_records.h -- the records of an uploaded scene as the kernels read them, and SceneView; plain structs, no device functions
-// (host units include this header alone; pt_record_layout.h ties the records to the Host* ones of bvh_build.h).
+// pt_scene_records.h -- the records of an uploaded scene as the kernels read them, and SceneView; plain structs and, next to GpuNodeQ, the
+// decode of its planes (host units include this header alone; pt_record_layout.h ties the records to the Host* ones of bvh_build.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -33,6 +33,11 @@ struct GpuNodeQ {
     int32_t child[4];
 };
 static_assert(sizeof(GpuNodeQ) == 64, "four 16-byte rows");
+// The decode of a plane: byte q of an axis with origin o and step s, and the byte of child c in a plane word (lo_* or hi_*) of that axis.
+// The quantiser rounds against this arithmetic and hrpt_selftest_bvh checks it (pt_bvh_nodes.hip); inner_step (pt_traverse.h) folds the
+// same o + q * s into the ray's plane distances.
+__host__ __device__ inline float node_q_decode(float o, float s, uint32_t q) { return o + (float)q * s; }
+__host__ __device__ inline float node_q_plane(float o, float s, uint32_t word, int c) { return node_q_decode(o, s, (word >> (8 * c)) & 255u); }
 struct GpuTri {             // 48 B world-space triangle (instance transform applied at upload)
     float p0[3]; uint32_t inst;
     float p1[3]; uint32_t prim;

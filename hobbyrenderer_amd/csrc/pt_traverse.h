@@ -1,5 +1,5 @@
-// pt_traverse.h -- rays and hits, the watertight triangle test, the BVH fetch policies, inner_step and the walks over the flat and the
-// two-level structure.
+// pt_traverse.h -- rays and hits, the watertight triangle test, the BVH fetch policies, inner_step, the walks over the flat and the
+// two-level structure, and the fetch policy of a scene by key (GlobalBvhOf).
 #pragma once
 
 #include "pt_scene_records.h"
@@ -475,5 +475,16 @@ HRT_DEV Hit closest_two_level(const GlobalBvhTl& bvh, int32_t rootLeaf, uint32_t
     }
     return best;
 }
+
+// ------------------------------------------------------------------ the tree views of a scene
+// GlobalBvhOf<key>::make(scene): the fetch policy over the scene's arrays in global memory. Keys: the node width (2, 4), kQuantisedTree,
+// kTwoLevelTree. What the wavefront kernels (pt_wf_*.h) and the thread-per-query kernels (pt_megakernel.hip) build their tree from.
+template <int W> struct GlobalBvhOf;
+template <> struct GlobalBvhOf<2> { using type = GlobalBvh; static HRT_DEV GlobalBvh make(const SceneView& s) { GlobalBvh g; g.nodes = s.nodes; g.tris = s.tris; return g; } };
+constexpr int kTwoLevelTree = 44;     // GlobalBvhOf key of the two-level structure (4-wide nodes)
+template <> struct GlobalBvhOf<kTwoLevelTree> { using type = GlobalBvhTl; static HRT_DEV GlobalBvhTl make(const SceneView& s) { GlobalBvhTl g; g.nodes = s.nodes4; g.tris = s.tris; g.instances = s.instances; return g; } };
+template <> struct GlobalBvhOf<4> { using type = GlobalBvh4; static HRT_DEV GlobalBvh4 make(const SceneView& s) { GlobalBvh4 g; g.nodes = s.nodes4; g.tris = s.tris; return g; } };
+constexpr int kQuantisedTree = 5;     // template width code of the 4-wide tree through its 64-byte quantised nodes (global memory only; pt_scene_records.h GpuNodeQ)
+template <> struct GlobalBvhOf<kQuantisedTree> { using type = GlobalBvhQ; static HRT_DEV GlobalBvhQ make(const SceneView& s) { GlobalBvhQ g; g.nodes = s.nodesQ; g.tris = s.tris; return g; } };
 
 } // namespace hrt

@@ -1,6 +1,6 @@
 // pt_wf_common.h -- what every wavefront kernel shares: the queue pool's streams (WfBuffers) and the per-launch arguments (WfArgs, PrimaryArgs,
 // JitterTable), the sample -> tile -> pixel enumeration and the primary ray, the per-lane LDS traversal stack and candidate columns, the tree
-// views (LdsBvh, GlobalBvhOf) with the block-start LDS copy (setup_lds), the wave helpers (lane_id, uniform, prefix_rank, wave_sum_u32) and the
+// view in LDS (LdsBvh) with the block-start LDS copy (setup_lds), the wave helpers (lane_id, uniform, prefix_rank) and the
 // per-block statistics adds. A piece of pt_wavefront.hip, which includes it inside hrt's anonymous namespace after pt_path.h: no stand-alone header.
 
 constexpr uint32_t kMaxSppPerBatch = 64;
@@ -149,13 +149,7 @@ struct LdsBvh {
     HRT_DEV uint32_t rowoff(int i, uint32_t byteOffset) const { return (uint32_t)(uintptr_t)(LdsPtr) reinterpret_cast<const char*>(nodes) + (uint32_t)i * kLdsNode4Stride + byteOffset; }
     HRT_DEV float4 load(uint32_t off) const { return *reinterpret_cast<const float4*>((const char*)(LdsPtr)(uintptr_t)off); }
 };
-template <int W> struct GlobalBvhOf;
-template <> struct GlobalBvhOf<2> { using type = GlobalBvh; static HRT_DEV GlobalBvh make(const SceneView& s) { GlobalBvh g; g.nodes = s.nodes; g.tris = s.tris; return g; } };
-constexpr int kTwoLevelTree = 44;     // GlobalBvhOf key of the two-level structure (4-wide nodes)
-template <> struct GlobalBvhOf<kTwoLevelTree> { using type = GlobalBvhTl; static HRT_DEV GlobalBvhTl make(const SceneView& s) { GlobalBvhTl g; g.nodes = s.nodes4; g.tris = s.tris; g.instances = s.instances; return g; } };
-template <> struct GlobalBvhOf<4> { using type = GlobalBvh4; static HRT_DEV GlobalBvh4 make(const SceneView& s) { GlobalBvh4 g; g.nodes = s.nodes4; g.tris = s.tris; return g; } };
-constexpr int kQuantisedTree = 5;     // template width code of the 4-wide tree through its 64-byte quantised nodes (global memory only; pt_scene_records.h GpuNodeQ)
-template <> struct GlobalBvhOf<kQuantisedTree> { using type = GlobalBvhQ; static HRT_DEV GlobalBvhQ make(const SceneView& s) { GlobalBvhQ g; g.nodes = s.nodesQ; g.tris = s.tris; return g; } };
+// (the trees in global memory: GlobalBvhOf, pt_traverse.h)
 
 // Carves dynamic LDS: [stack: min(DEPTH, 32)*kBlock ints][bvh copy]; copies the BVH when LDS_BVH.
 template <bool LDS_BVH, int DEPTH, int W, int LDSMAX>
@@ -184,14 +178,7 @@ HRT_DEV uint32_t lane_id() { return threadIdx.x & 63u; }
 HRT_DEV uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 HRT_DEV uint32_t prefix_rank(unsigned long long mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u)); }
 
-HRT_DEV unsigned long long wave_sum_u32(unsigned int v)
-{
-    unsigned long long x = v;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-// Statistics: one atomic per BLOCK on a counter shard (a returning-free add per wave on one word costs ~11 ns each and
+// Statistics (wave_sum_u32: pt_path.h): one atomic per BLOCK on a counter shard (a returning-free add per wave on one word costs ~11 ns each and
 // serialises at the kernel tail: 8192 waves = ~0.1 ms per launch).
 HRT_DEV void block_count_add(unsigned long long* counterField0, size_t fieldOffsetWords, unsigned int perLane)
 {

@@ -9,19 +9,15 @@ GPU: the kernels == NumPy == the host executor, fused tail on and off, a caller-
 against the post chain's oracle, and a resize."""
 import ctypes as C
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import bloom_reference as ref
+import kernel_metadata
 from hobbyrenderer_amd import native, scenes, structs as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-OBJ = os.path.join(ROOT, "hobbyrenderer_amd", "csrc", "build", "pt_bloom.hip.o")
 
 DEFAULTS = (0.1, 0.005, 0.85)
 OTHER = (0.5, 0.25, 1.5)
@@ -157,17 +153,7 @@ def test_host_argument_errors():
 def test_bloom_kernels_use_no_scratch():
     """Every kernel of pt_bloom.hip.o has private_segment_fixed_size 0: no spills, no private arrays (the fused tail runs 512 lanes of up
     to 256 VGPRs for exactly this reason)."""
-    if not os.path.exists(OBJ) or not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("pt_bloom.hip.o or the LLVM tools are not here (the object is built by __graft_entry__.build())")
-    with tempfile.TemporaryDirectory() as t:
-        fb, co = os.path.join(t, "fb"), os.path.join(t, "co")
-        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fb}", OBJ])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fb}",
-                               f"--output={co}", "--unbundle"])
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    found = {}
-    for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)", notes, re.S):
-        found[m.group(1)] = int(m.group(2))
+    found = {n: k["scratch"] for n, k in kernel_metadata.kernels("pt_bloom.hip.o").items()}
     for kernel in ("bloom_prefilter", "bloom_downsample", "bloom_upsample", "bloom_composite", "bloom_tail"):
         assert any(kernel in name for name in found), (kernel, sorted(found))
     assert all(v == 0 for v in found.values()), found

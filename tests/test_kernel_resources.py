@@ -6,32 +6,16 @@ that spilled (68 B of scratch per lane) and rendered every sky pixel 5-10 % wron
 `make -C hobbyrenderer_amd/csrc variant NAME=slp EXTRA="-Xarch_device -fslp-vectorize"` + tests/test_parity_gpu.py seed 1). The parity
 tests on the GPU are the real guard; this one fails earlier, on the CPU, when a compiler or flag change pushes one of these kernels into
 spilling or over its occupancy budget again."""
-import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-OBJ = os.path.join(ROOT, "hobbyrenderer_amd", "csrc", "build", "pt_wavefront.hip.o")
+import kernel_metadata
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(OBJ) or not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("pt_wavefront.hip.o or the LLVM tools are not here (the object is built by __graft_entry__.build())")
-    with tempfile.TemporaryDirectory() as t:
-        fb, co = os.path.join(t, "fb"), os.path.join(t, "co")
-        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fb}", OBJ])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fb}", f"--output={co}", "--unbundle"])
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    out = {}
-    for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+)", notes, re.S):
-        name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-        name = name.replace("hrt::(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-        out[name] = {"scratch": int(m.group(2)), "sgpr": int(m.group(3)), "vgpr": int(m.group(4))}
+    out = kernel_metadata.kernels("pt_wavefront.hip.o")
     assert len(out) > 100
     return out
 

@@ -1,11 +1,11 @@
 """The kernels of the animation stage (hrpt_animate): register, scratch and LDS budget, read from the code-object
-metadata of the built object -- the method of tests/test_kernel_resources_skin.py, no GPU needed. All four are held to the project's
+metadata of the built object -- tests/kernel_metadata.py reads it, no GPU needed. All four are held to the project's
 standing bar, no scratch and at most 128 VGPRs; the sampling kernel's LDS is the staged animation times (4 bytes x
 HRPT_ANIM_LDS_MAX_ANIMATIONS) and nothing more, the others have none."""
 import pytest
 
 from hobbyrenderer_amd import structs as S
-from test_kernel_resources_motion import _kernels
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")

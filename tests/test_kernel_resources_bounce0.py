@@ -1,18 +1,17 @@
 """wf_bounce0 (bounce 0 traced and shaded in one kernel, pt_wf_shade.h): register, scratch and LDS budget of every instantiation, read from
-the code-object metadata of the built library -- the method of tests/test_kernel_resources_shade_lt.py, no GPU needed.
+the code-object metadata of the built library -- tests/kernel_metadata.py reads it, no GPU needed.
 
 The kernel is compiled for a forced four waves per SIMD like wf_shade, whose history of miscompiles under register pressure is told in
 tests/test_kernel_resources.py: no scratch and at most 128 VGPRs. Four waves per SIMD are four 256-thread blocks per CU, so the static LDS
 plus the dynamic LDS of the plan (at most kShadeLdsPerBlock: above it the plan keeps the two-kernel pair) must fit a quarter of the CU's 160 KiB."""
 import json
-import os
-import re
 import subprocess
-import tempfile
 
 import pytest
 
-from test_kernel_resources_shade_lt import BLOCKS_PER_CU, CSRC, CU_LDS, LLVM, OBJ, _short
+import kernel_metadata
+from kernel_metadata import CSRC
+from test_kernel_resources_shade_lt import BLOCKS_PER_CU, CU_LDS
 from test_wavefront_plan import CORNELL
 
 PLAN = r"""
@@ -33,18 +32,7 @@ int main()
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(OBJ) or not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("pt_wavefront.hip.o or the LLVM tools are not here (the object is built by __graft_entry__.build())")
-    with tempfile.TemporaryDirectory() as t:
-        fb, co = os.path.join(t, "fb"), os.path.join(t, "co")
-        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fb}", OBJ])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fb}", f"--output={co}", "--unbundle"])
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    out = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+)", notes, re.S):
-        if "wf_bounce0" in m.group(2):
-            out[_short(m.group(2))] = {"lds": int(m.group(1)), "scratch": int(m.group(3)), "vgpr": int(m.group(5))}
-    return out
+    return {n: k for n, k in kernel_metadata.kernels("pt_wavefront.hip.o").items() if "wf_bounce0" in n}
 
 
 @pytest.fixture(scope="module")

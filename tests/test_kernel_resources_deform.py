@@ -1,9 +1,9 @@
 """The kernel of the vertex quantiser (hrpt_quantize_vertices_device / hrpt_update_vertices_device): register and
-scratch budget, read from the code-object metadata of the built object -- the method of tests/test_kernel_resources_modulation.py, no GPU
+scratch budget, read from the code-object metadata of the built object -- tests/kernel_metadata.py reads it, no GPU
 needed. Held to the project's standing bar: no scratch, no LDS and at most 128 VGPRs."""
 import pytest
 
-from test_kernel_resources_motion import _kernels
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")

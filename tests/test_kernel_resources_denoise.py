@@ -1,9 +1,9 @@
 """The kernel of hrpt_denoise: register and scratch budget, read from the code-object metadata of the built object --
-the method of tests/test_kernel_resources_motion.py, no GPU needed. denoise_poisson is held to the project's standing bar: no scratch and at
+tests/kernel_metadata.py reads it, no GPU needed. denoise_poisson is held to the project's standing bar: no scratch and at
 most 128 VGPRs (four waves per SIMD); it uses no LDS."""
 import pytest
 
-from test_kernel_resources_motion import _kernels
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")

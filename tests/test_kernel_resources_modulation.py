@@ -1,9 +1,9 @@
 """The kernels of hrpt_demodulate / hrpt_compose: register and scratch budget, read from the code-object metadata of
-the built object -- the method of tests/test_kernel_resources_denoise.py, no GPU needed. Both are held to the project's standing bar: no
+the built object -- tests/kernel_metadata.py reads it, no GPU needed. Both are held to the project's standing bar: no
 scratch and at most 128 VGPRs (four waves per SIMD); neither uses LDS."""
 import pytest
 
-from test_kernel_resources_motion import _kernels
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")

@@ -1,38 +1,11 @@
 """The kernels of hrpt_render_motion_vectors: register and scratch budget, read from the code-object metadata of the
-built objects -- the method of tests/test_kernel_resources_shade_lt.py, no GPU needed.
+built objects -- tests/kernel_metadata.py reads it, no GPU needed.
 
 wf_gbuffer_motion is held to what the shade kernels are held to: no scratch and at most 128 VGPRs (four waves per SIMD). pt_motion_kernel,
 the validation path, may use no scratch beyond the private traversal stack pt_gbuffer_kernel has."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-BUILD = os.path.join(ROOT, "hobbyrenderer_amd", "csrc", "build")
-
-
-def _short(mangled):
-    name = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip()
-    return name.replace("hrt::(anonymous namespace)::", "").replace("hrt::", "").replace("void ", "").split("(")[0]
-
-
-def _kernels(obj):
-    path = os.path.join(BUILD, obj)
-    if not os.path.exists(path) or not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip(f"{obj} or the LLVM tools are not here (the object is built by __graft_entry__.build())")
-    with tempfile.TemporaryDirectory() as t:
-        fb, co = os.path.join(t, "fb"), os.path.join(t, "co")
-        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fb}", path])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fb}", f"--output={co}", "--unbundle"])
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    out = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+)", notes, re.S):
-        out[_short(m.group(2))] = {"lds": int(m.group(1)), "scratch": int(m.group(3)), "vgpr": int(m.group(5))}
-    return out
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")

@@ -1,10 +1,10 @@
 """The kernels of the irradiance probe volume: register, scratch and LDS budget, read from the code-object metadata of
-the built object -- the method of tests/test_kernel_resources_temporal.py, no GPU needed. All four are held to the project's standing bar: no
+the built object -- tests/kernel_metadata.py reads it, no GPU needed. All four are held to the project's standing bar: no
 scratch and at most 128 VGPRs (four waves per SIMD). probes_blend stages its rays and passes its tiles through static LDS of at most 34 KiB;
 the other three use none."""
 import pytest
 
-from test_kernel_resources_motion import _kernels
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")

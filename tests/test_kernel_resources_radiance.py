@@ -1,11 +1,11 @@
 """The kernels of hrpt_trace_radiance: register, scratch and LDS budget, read from the code-object metadata of the
-built objects -- the method of tests/test_kernel_resources_motion.py, no GPU needed.
+built objects -- tests/kernel_metadata.py reads it, no GPU needed.
 
 The two streaming kernels around the pipeline use no scratch, no LDS and at most 128 VGPRs (the project's standing bar); pt_radiance_kernel,
 the one-thread-per-ray path, runs pt_megakernel's bounce loop and may take no more registers or scratch than that kernel in the same object."""
 import pytest
 
-from test_kernel_resources_motion import _kernels
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")

@@ -1,21 +1,19 @@
 """wf_shade_lt (wf_shade over triangle / instance / material tables in LDS, pt_wf_shade.h): register, scratch and LDS budget of every
-instantiation, read from the code-object metadata of the built library -- the method of tests/test_kernel_resources.py, no GPU needed.
+instantiation, read from the code-object metadata of the built library -- tests/kernel_metadata.py reads it, no GPU needed.
 
-The kernel is compiled for a forced four waves per SIMD like wf_shade, whose history of miscompiles under register pressure is told there:
+The kernel is compiled for a forced four waves per SIMD like wf_shade, whose history of miscompiles under register pressure is told in
+tests/test_kernel_resources.py:
 no scratch and at most 128 VGPRs. Four waves per SIMD are four 256-thread blocks per CU, so the static LDS plus the largest dynamic LDS the
 launch plan ever asks for (pt_wavefront_plan.h kShadeLdsPerBlock) must fit a quarter of the CU's 160 KiB; and the table reads must be
 ds_read, neither flat_load nor more global_load than the global-table kernel minus its gathers."""
-import os
 import re
 import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-CSRC = os.path.join(ROOT, "hobbyrenderer_amd", "csrc")
-OBJ = os.path.join(CSRC, "build", "pt_wavefront.hip.o")
+import kernel_metadata
+from kernel_metadata import CSRC
+
 CU_LDS, BLOCKS_PER_CU = 160 * 1024, 4
 
 LIMITS = r"""
@@ -25,28 +23,10 @@ int main() { printf("%zu %zu %zu\n", hrt::kShadeLdsPerBlock, hrt::kShadeRingByte
 """
 
 
-def _short(mangled):
-    name = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip()
-    return name.replace("hrt::(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-
-
 @pytest.fixture(scope="module")
 def code_object():
-    if not os.path.exists(OBJ) or not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("pt_wavefront.hip.o or the LLVM tools are not here (the object is built by __graft_entry__.build())")
-    with tempfile.TemporaryDirectory() as t:
-        fb, co = os.path.join(t, "fb"), os.path.join(t, "co")
-        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fb}", OBJ])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fb}", f"--output={co}", "--unbundle"])
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-        asm = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-    kernels = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+)", notes, re.S):
-        if "wf_shade" in m.group(2):
-            kernels[_short(m.group(2))] = {"lds": int(m.group(1)), "scratch": int(m.group(3)), "vgpr": int(m.group(5))}
-    bodies = {}
-    for m in re.finditer(r"\n[0-9a-f]+ <(\S*wf_shade\S*)>:\n(.*?)(?=\n[0-9a-f]+ <|\Z)", asm, re.S):
-        bodies[_short(m.group(1))] = m.group(2)
+    kernels = {n: k for n, k in kernel_metadata.kernels("pt_wavefront.hip.o").items() if "wf_shade" in n}
+    bodies = {n: b for n, b in kernel_metadata.disassembly("pt_wavefront.hip.o").items() if "wf_shade" in n}
     return kernels, bodies
 
 

@@ -1,12 +1,12 @@
 """The kernel of the vertex producer (hrpt_skin_vertices_device / hrpt_update_vertices_skinned): register, scratch
-and LDS budget, read from the code-object metadata of the built object -- the method of tests/test_kernel_resources_motion.py, no GPU
+and LDS budget, read from the code-object metadata of the built object -- tests/kernel_metadata.py reads it, no GPU
 needed. Both instantiations are held to the project's standing bar, no scratch and at most 128 VGPRs; the one that gathers its palette
 from global memory has no LDS, the staged one has the palette stage (48 bytes x HRPT_SKIN_LDS_MAX_JOINTS) and nothing more. (The kernel
 that also quantised was measured no faster than this one followed by the quantiser and is not built: section 22.)"""
 import pytest
 
 from hobbyrenderer_amd import structs as S
-from test_kernel_resources_motion import _kernels
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")

@@ -1,10 +1,10 @@
 """The kernels of hrpt_upscale: register, scratch and LDS budget, read from the code-object metadata of the built
-object -- the method of tests/test_kernel_resources_temporal.py, no GPU needed. upscale_resolve (the default: global gathers) and
+object -- tests/kernel_metadata.py reads it, no GPU needed. upscale_resolve (the default: global gathers) and
 upscale_resolve_staged (HRPT_UPSCALE_STAGED=1) are held to the project's standing bar: no scratch and at most 128 VGPRs (four waves per
 SIMD); the staged window of render texels is static LDS of at most 16 KiB."""
 import pytest
 
-from test_kernel_resources_motion import _kernels
+from kernel_metadata import kernels as _kernels
 
 
 @pytest.fixture(scope="module")
