@@ -119,6 +119,8 @@ try {
     c->perSize.dDeferredRays.reset(); c->perSize.dDeferredHits.reset(); c->perSize.deferredPairs = 0;      // sized again by the next hrpt_deferred_lighting
     for (DeviceBuffer<float4>& image : c->perSize.dDeferredCarry) image.reset();
     c->perSize.deferredCarryPixels = 0;
+    for (DeviceBuffer<float4>& image : c->perSize.dIndirect) image.reset();               // written again by the next hrpt_indirect_lighting
+    c->perSize.dIndirectRays.reset(); c->perSize.dIndirectRadiance.reset(); c->perSize.indirectRecords = 0;
     c->perSize.dUpscaled.reset(); c->upscaleValid = false; c->upscaleCur = 0; c->upscaleWidth = c->upscaleHeight = 0;
     c->width = width; c->height = height;
     return HRPT_OK;

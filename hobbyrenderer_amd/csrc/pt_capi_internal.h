@@ -70,6 +70,10 @@ struct PerSizeImages {
     // allocation) and the two running-sum images of a multi-batch call; allocated on first use, grown on demand, dropped by hrpt_resize
     DeviceBuffer<HrptRay> dDeferredRays; DeviceBuffer<HrptRayHit> dDeferredHits; size_t deferredPairs = 0;
     DeviceBuffer<float4> dDeferredCarry[2]; size_t deferredCarryPixels = 0;
+    // traced indirect lighting (hrpt_indirect_lighting): the two resolved planes ([0] diffuse, [1] specular) and the ray and radiance records
+    // of one call (indirectRecords = what the last allocation holds); allocated on first use, grown on demand, dropped by hrpt_resize
+    DeviceBuffer<float4> dIndirect[2];
+    DeviceBuffer<HrptRay> dIndirectRays; DeviceBuffer<float4> dIndirectRadiance; size_t indirectRecords = 0;
 };
 
 // Buffers that live as long as the context.

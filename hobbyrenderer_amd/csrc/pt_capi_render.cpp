@@ -295,7 +295,7 @@ try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!c->haveScene) return fail(c, HRPT_ERR_NO_SCENE, "hrpt_trace_radiance: no scene uploaded");
     if (!constants) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: null constants");
-    if (flags & ~(HRPT_RADIANCE_DEVICE_POINTERS | HRPT_RADIANCE_THREAD_PER_RAY | HRPT_RADIANCE_ACCUMULATE)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: unknown flags");
+    if (flags & ~(HRPT_RADIANCE_DEVICE_POINTERS | HRPT_RADIANCE_THREAD_PER_RAY | HRPT_RADIANCE_ACCUMULATE | HRPT_RADIANCE_SECONDARY)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: unknown flags");
     if (constants->m_MaxBounces > 64u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: m_MaxBounces above 64 (one kernel sequence is launched per bounce)");
     if (constants->m_LightCount > c->view.lightCount) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: m_LightCount exceeds the scene's light buffer");
     if (count == 0) return HRPT_OK;
@@ -305,12 +305,12 @@ try {
     if (!wavefront && c->view.instances && exceeds_private_stack(c->traits))
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_trace_radiance: this two-level structure is deeper than the thread-per-ray kernel's 64-entry stack");
     HIP_TRY(c, hipSetDevice(c->device));
-    const bool accumulate = (flags & HRPT_RADIANCE_ACCUMULATE) != 0;
+    const bool accumulate = (flags & HRPT_RADIANCE_ACCUMULATE) != 0, secondary = (flags & HRPT_RADIANCE_SECONDARY) != 0;
     auto trace = [&](const HrptRay* dr, float4* dl) -> hipError_t {
-        if (!wavefront) return launch_radiance_rays(c->view, *constants, dr, dl, count, accumulate, c->stream);
+        if (!wavefront) return launch_radiance_rays(c->view, *constants, dr, dl, count, accumulate, secondary, c->stream);
         std::string werr;
         c->wf.shadeInstances = (uint32_t)c->keptInstances.size(); c->wf.shadeMaterials = (uint32_t)c->keptMaterials.size();    // as hrpt_render sets them
-        hipError_t te = wavefront_radiance(c->wf, c->view, c->traits, *constants, dr, dl, count, accumulate, c->stream, werr);
+        hipError_t te = wavefront_radiance(c->wf, c->view, c->traits, *constants, dr, dl, count, accumulate, secondary, c->stream, werr);
         if (te != hipSuccess) c->err = "hrpt_trace_radiance: " + werr;
         return te;
     };

@@ -54,7 +54,7 @@ hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRa
 // Path-traced radiance along a caller's rays (hrpt_trace_radiance): the megakernel's bounce loop from the ray's record;
 // radiance[i] = (L, 1), or with `accumulate` (old.rgb + L, old.w + 1). Device arrays.
 hipError_t launch_radiance_rays(const SceneView& scene, const HrptPathTracerConstants& constants, const HrptRay* rays, float4* radiance, uint64_t count,
-                                bool accumulate, hipStream_t stream);
+                                bool accumulate, bool secondary, hipStream_t stream);
 
 // ---- accumulation to output (pt_resolve.hip)
 // Output[xy] = accum.rgb / accum.a (PathTracer.hlsl:339) over the whole image; launch_resolve_columns: the same from the rank-major column
@@ -170,6 +170,21 @@ void deferred_rays_host(const HrptDeferredImages& images, uint32_t width, uint32
 void deferred_shade_host(const HrptDeferredImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptGPULight* lights,
                          uint32_t lightCount, const float* visibility, const float* sunRadiance, const float* sky, const HrptDeferredParams& params,
                          int nthreads);
+
+// Traced indirect lighting (pt_indirect.hip; arithmetic in pt_indirect.h): the diffuse and specular ray records of every pixel (rays: W * H
+// records per flagged lobe, diffuse first), the resolve of the radiance hrpt_trace_radiance left for them into images.diffuse /
+// images.specular (either may be null), and the compose into images.colorInOut. Every pointer in device memory, 16-byte aligned.
+// indirect_*_host (pt_indirect_host.cpp): the same arithmetic on host threads.
+namespace indirect { struct Frame; }
+bool indirect_params_valid(const HrptIndirectParams& params);
+hipError_t launch_indirect_rays(const indirect::Frame& frame, const HrptIndirectImages& images, HrptRay* rays, hipStream_t stream);
+hipError_t launch_indirect_resolve(const indirect::Frame& frame, const HrptIndirectImages& images, const float4* radiance, hipStream_t stream);
+hipError_t launch_indirect_compose(const HrptIndirectImages& images, uint32_t width, uint32_t height, float intensity, hipStream_t stream);
+void indirect_rays_host(const HrptIndirectImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptIndirectParams& params,
+                        HrptRay* raysOut, int nthreads);
+void indirect_resolve_host(const HrptIndirectImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptIndirectParams& params,
+                           const float* radiance4, int nthreads);
+void indirect_compose_host(const HrptIndirectImages& images, uint32_t width, uint32_t height, const HrptIndirectParams& params, int nthreads);
 
 // Vertex quantiser (pt_deform.hip; arithmetic in pt_deform.h): out[i] = the 24-byte scene-format record of the float vertex in[i], both in
 // device memory (in 16-byte aligned); *flag (device, may be null) is set to 1 when a position is not finite. quantize_vertices_host

@@ -46,13 +46,14 @@ HRT_DEV void load_ray(const HrptRay& r, Ray& ray)
 }
 
 // The bounce loop of PathTracer_CSMain (PathTracer.hlsl:90-330) for one path from the state `ps` holds (init_path, or a caller's ray record):
-// what pt_megakernel and pt_radiance_kernel both run. Leaves the path's radiance in ps.radiance; nClosest / nShadow count its queries.
+// what pt_megakernel and the radiance kernels run. `firstBounce`: the path segment `ps` holds (0; 1 for HRPT_RADIANCE_SECONDARY). Leaves the
+// path's radiance in ps.radiance; nClosest / nShadow count its queries.
 template <class BVH>
 HRT_DEV void trace_path(const SceneView& s, const BVH& bvh, const HrptPathTracerConstants& cb, PathState& ps, PrivateStack& stack,
-                        unsigned int& nClosest, unsigned int& nShadow)
+                        unsigned int& nClosest, unsigned int& nShadow, int firstBounce)
 {
     int maxBounces = (int)cb.m_MaxBounces;
-    for (int bounce = 0; bounce < maxBounces; ++bounce) {
+    for (int bounce = firstBounce; bounce < maxBounces; ++bounce) {
         Hit hit;
         ++nClosest;
         if (trace_standard(s, bvh, ps.ray, ps.rng, stack, hit)) {
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(64) void pt_megakernel(SceneView s, HrptPathTracerC
         const auto bvh = GlobalBvhOf<tree_key<TL>>::make(s);
         PrivateStack stack;
         PathState ps; init_path(ps, cb, px, py);
-        trace_path(s, bvh, cb, ps, stack, nClosest, nShadow);
+        trace_path(s, bvh, cb, ps, stack, nClosest, nShadow, 0);
         // accumulate + resolve, PathTracer.hlsl:332-339
         size_t idx = (size_t)py * imageWidth + px;
         float4 accum = make_float4(ps.radiance.x, ps.radiance.y, ps.radiance.z, 1.0f);
@@ -129,34 +130,43 @@ hipError_t launch_megakernel(const SceneView& scene, const HrptPathTracerConstan
 
 // hrpt_trace_radiance, validation path (HRPT_RADIANCE_THREAD_PER_RAY, and scenes the wavefront pipeline does not take): one thread per ray runs
 // trace_path from the caller's record -- origin, direction as given, tmin, RNG state; unbounded, throughput 1, outside any medium -- and
-// leaves the radiance by store_ray_radiance. No counters: HrptStats describes renders.
-template <bool TL>
-__global__ __launch_bounds__(64) void pt_radiance_kernel(SceneView s, HrptPathTracerConstants cb, const HrptRay* __restrict__ rays,
-                                                         float4* __restrict__ radiance, uint64_t count, uint32_t accumulate)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const HrptRay r = rays[i];
-    PathState ps;
-    load_ray(r, ps.ray); ps.ray.tmax = 1e10f;
-    ps.rng = r.rng;
-    ps.throughput = mk3(1.0f, 1.0f, 1.0f); ps.radiance = mk3(0.0f, 0.0f, 0.0f);
-    ps.inVolume = false; ps.interiorIOR = 1.0f; ps.sigmaA = mk3(0.0f, 0.0f, 0.0f); ps.sigmaS = mk3(0.0f, 0.0f, 0.0f);
-    const bool traced = all_finite(ps.ray.o, ps.ray.d) && (r.tmin - r.tmin) == 0.0f;
-    if (traced) {
-        const auto bvh = GlobalBvhOf<tree_key<TL>>::make(s);
-        PrivateStack stack;
-        unsigned int nClosest = 0, nShadow = 0;
-        trace_path(s, bvh, cb, ps, stack, nClosest, nShadow);
+// leaves the radiance by store_ray_radiance. No counters: HrptStats describes renders. Two kernels of one text: pt_radiance_kernel starts at
+// path segment 0, pt_radiance_secondary_kernel at segment 1 (HRPT_RADIANCE_SECONDARY). The text is a macro and not a function both call: through
+// a function, however it was spelled, the segment-0 kernel came out with its instructions in another order than before the second one existed.
+#define HRT_RADIANCE_KERNEL(NAME, FIRST)                                                                                                   \
+    template <bool TL>                                                                                                                     \
+    __global__ __launch_bounds__(64) void NAME(SceneView s, HrptPathTracerConstants cb, const HrptRay* __restrict__ rays,                  \
+                                               float4* __restrict__ radiance, uint64_t count, uint32_t accumulate)                         \
+    {                                                                                                                                      \
+        const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;                                                                \
+        if (i >= count) return;                                                                                                            \
+        const HrptRay r = rays[i];                                                                                                         \
+        PathState ps;                                                                                                                      \
+        load_ray(r, ps.ray); ps.ray.tmax = 1e10f;                                                                                          \
+        ps.rng = r.rng;                                                                                                                    \
+        ps.throughput = mk3(1.0f, 1.0f, 1.0f); ps.radiance = mk3(0.0f, 0.0f, 0.0f);                                                        \
+        ps.inVolume = false; ps.interiorIOR = 1.0f; ps.sigmaA = mk3(0.0f, 0.0f, 0.0f); ps.sigmaS = mk3(0.0f, 0.0f, 0.0f);                  \
+        const bool traced = all_finite(ps.ray.o, ps.ray.d) && (r.tmin - r.tmin) == 0.0f;                                                   \
+        if (traced) {                                                                                                                      \
+            const auto bvh = GlobalBvhOf<tree_key<TL>>::make(s);                                                                           \
+            PrivateStack stack;                                                                                                            \
+            unsigned int nClosest = 0, nShadow = 0;                                                                                        \
+            trace_path(s, bvh, cb, ps, stack, nClosest, nShadow, FIRST);                                                                   \
+        }                                                                                                                                  \
+        store_ray_radiance(radiance + i, ps.radiance, traced, accumulate != 0u);                                                           \
     }
-    store_ray_radiance(radiance + i, ps.radiance, traced, accumulate != 0u);
-}
+HRT_RADIANCE_KERNEL(pt_radiance_kernel, 0)
+HRT_RADIANCE_KERNEL(pt_radiance_secondary_kernel, 1)
+#undef HRT_RADIANCE_KERNEL
 hipError_t launch_radiance_rays(const SceneView& scene, const HrptPathTracerConstants& constants, const HrptRay* rays, float4* radiance, uint64_t count,
-                                bool accumulate, hipStream_t stream)
+                                bool accumulate, bool secondary, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
     const dim3 grid((unsigned)((count + 63) / 64));
-    with_tree_of(scene, [&](auto tl) { hipLaunchKernelGGL(pt_radiance_kernel<decltype(tl)::value>, grid, dim3(64), 0, stream, scene, constants, rays, radiance, count, accumulate ? 1u : 0u); });
+    with_tree_of(scene, [&](auto tl) {
+        if (secondary) hipLaunchKernelGGL(pt_radiance_secondary_kernel<decltype(tl)::value>, grid, dim3(64), 0, stream, scene, constants, rays, radiance, count, accumulate ? 1u : 0u);
+        else hipLaunchKernelGGL(pt_radiance_kernel<decltype(tl)::value>, grid, dim3(64), 0, stream, scene, constants, rays, radiance, count, accumulate ? 1u : 0u);
+    });
     return hipGetLastError();
 }
 

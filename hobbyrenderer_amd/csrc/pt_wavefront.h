@@ -65,7 +65,7 @@ hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const S
 // hrpt_trace_radiance: radiance[i] = (L, 1) -- or, accumulate, (old.rgb + L, old.w + 1) -- of the path that starts as rays[i], by the render's
 // kernels between wf_raygen_rays and wf_store_radiance (device arrays). Leaves the statistics, the plan and the timing state of renders alone.
 hipError_t wavefront_radiance(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
-                              const HrptRay* rays, float4* radiance, uint64_t count, bool accumulate, hipStream_t stream, std::string& error);
+                              const HrptRay* rays, float4* radiance, uint64_t count, bool accumulate, bool secondary, hipStream_t stream, std::string& error);
 void wavefront_release(WavefrontState& st);
 void wavefront_collect_timing(WavefrontState& st);   // call after the stream is synchronised; folds pending events into kernelMs
 void wavefront_reset_timing(WavefrontState& st);

@@ -153,9 +153,9 @@ void launch_wf_trace_rays(const Variant& v, uint32_t cus, dim3 g, hipStream_t st
 }
 // NEE visibility + accumulation of one bounce on stream `sst`. With non-opaque geometry in the scene: ray generation, the opaque any-hit pass in
 // the refilling traversal kernel, then wf_shadow for the contributions and the (few) rays that crossed non-opaque triangles.
-void shadow_stage(const RenderPlan& plan, const SceneTraits& traits, uint32_t cus, dim3 grid, hipStream_t sst, WfArgs& a, const HrptPathTracerConstants& cb, int bounce)
+void shadow_stage(const RenderPlan& plan, const SceneTraits& traits, uint32_t cus, dim3 grid, hipStream_t sst, WfArgs& a, const HrptPathTracerConstants& cb, int bounce, uint32_t parity)
 {
-    a.shadowParity = (uint32_t)bounce & 1u;
+    a.shadowParity = parity;
     if (plan.shadowMode == kShadowResolve) {
         if (traits.directionalLightsOnly) hipLaunchKernelGGL((wf_shadow_rays<true>), grid, dim3(kBlock), 0, sst, a, cb);
         else hipLaunchKernelGGL((wf_shadow_rays<false>), grid, dim3(kBlock), 0, sst, a, cb);
@@ -431,8 +431,10 @@ bool prepare_overlap(WavefrontState& st, int maxBounces)
 }
 // The bounces of one batch whose path queue 0 is filled (or, plan.fusedPrimary, derived by the bounce-0 kernels): per bounce wf_extend, wf_shade and the
 // shadow stage, for renders and hrpt_trace_radiance alike. `profile`: HIP events around every launch (renders with HRPT_FRAME_PROFILE).
+// `firstBounce`: the path segment the queue holds (0, or 1 with HRPT_RADIANCE_SECONDARY). The kernels take the true bounce index; the queue and
+// shadow parities and the fork / join events follow bounce - firstBounce, so path queue 0 is the input of the first bounce that runs.
 hipError_t run_bounces(WavefrontState& st, const RenderPlan& plan, const SceneTraits& traits, uint32_t cus, const BatchPlan& batch, hipStream_t stream,
-                       WfArgs& a, const HrptPathTracerConstants& cb, bool profile, std::string& error)
+                       WfArgs& a, const HrptPathTracerConstants& cb, bool profile, std::string& error, int firstBounce = 0)
 {
     hipError_t e;
     const dim3 grid(batch.grid);
@@ -441,31 +443,32 @@ hipError_t run_bounces(WavefrontState& st, const RenderPlan& plan, const SceneTr
     // writes hit records: no shared buffer, so the two run concurrently (fork after shade(b), join before shade(b+1), which both
     // rewrites the shadow queue and adds the next radiance term -- the per-sample order of additions is unchanged).
     // Per-launch timing (HRPT_FRAME_PROFILE) needs stream order, so profiling renders serially.
-    const bool overlap = !profile && !st.knobs.serialShadow && maxBounces > 1 && prepare_overlap(st, maxBounces);
+    const bool overlap = !profile && !st.knobs.serialShadow && maxBounces - firstBounce > 1 && prepare_overlap(st, maxBounces - firstBounce);
     bool pendingJoin = false;
-    for (int bounce = 0; bounce < maxBounces; ++bounce) {
-        const uint32_t parity = (uint32_t)bounce & 1u;
+    for (int bounce = firstBounce; bounce < maxBounces; ++bounce) {
+        const size_t step = (size_t)(bounce - firstBounce);
+        const uint32_t parity = (uint32_t)step & 1u;
         const bool timed = profile && st.eventsUsed + 8 <= 4096;
         a.primary = (plan.fusedPrimary && bounce == 0) ? 1u : 0u;
         const bool fusedBounce0 = plan.fusedBounce0 && bounce == 0;      // wf_bounce0 in place of the pair below, on the shade grid, timed as wf_shade
         if (timed && !fusedBounce0) timing_mark(st, stream, kKernelExtend, true);
         if (!fusedBounce0) launch_extend(plan.vE, cus, dim3(batch.gridExtend), stream, a, parity);
         if (timed) { if (!fusedBounce0) timing_mark(st, stream, kKernelExtend, false); timing_mark(st, stream, kKernelShade, true); }
-        if (pendingJoin) { if ((e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)bounce - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; } pendingJoin = false; }
+        if (pendingJoin) { if ((e = hipStreamWaitEvent(stream, st.joinEvents[step - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; } pendingJoin = false; }
         launch_shade(plan, fusedBounce0, grid, stream, a, cb, parity, bounce, bounce + 1 == maxBounces ? 1 : 0);
         if (timed) { timing_mark(st, stream, kKernelShade, false); timing_mark(st, stream, kKernelShadow, true); }
         if (overlap) {
-            if ((e = hipEventRecord(st.forkEvents[(size_t)bounce], stream)) != hipSuccess ||
-                (e = hipStreamWaitEvent(st.auxStream, st.forkEvents[(size_t)bounce], 0)) != hipSuccess) { error = "fork to the shadow stream"; return e; }
-            shadow_stage(plan, traits, cus, grid, st.auxStream, a, cb, bounce);
-            if ((e = hipEventRecord(st.joinEvents[(size_t)bounce], st.auxStream)) != hipSuccess) { error = "hipEventRecord(join)"; return e; }
+            if ((e = hipEventRecord(st.forkEvents[step], stream)) != hipSuccess ||
+                (e = hipStreamWaitEvent(st.auxStream, st.forkEvents[step], 0)) != hipSuccess) { error = "fork to the shadow stream"; return e; }
+            shadow_stage(plan, traits, cus, grid, st.auxStream, a, cb, bounce, parity);
+            if ((e = hipEventRecord(st.joinEvents[step], st.auxStream)) != hipSuccess) { error = "hipEventRecord(join)"; return e; }
             pendingJoin = true;
         } else {
-            shadow_stage(plan, traits, cus, grid, stream, a, cb, bounce);
+            shadow_stage(plan, traits, cus, grid, stream, a, cb, bounce, parity);
         }
         if (timed) timing_mark(st, stream, kKernelShadow, false);
     }
-    if (pendingJoin && (e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)maxBounces - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; }
+    if (pendingJoin && (e = hipStreamWaitEvent(stream, st.joinEvents[(size_t)(maxBounces - firstBounce) - 1], 0)) != hipSuccess) { error = "hipStreamWaitEvent(join)"; return e; }
     return hipSuccess;
 }
 }
@@ -575,11 +578,11 @@ hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const S
     return hipSuccess;
 }
 
-// hrpt_trace_radiance, wavefront path: wf_raygen_rays, the render's bounces (run_bounces with plan_radiance's plan), wf_store_radiance, in batches of
+// hrpt_trace_radiance, wavefront path: wf_raygen_rays, the render's bounces (run_bounces with plan_radiance's plan; from bounce 1 with `secondary`), wf_store_radiance, in batches of
 // radiance_batch_rays. Like wavefront_gbuffer it touches neither st.plan nor the byte / timing accounting of renders and counts into a scratch
 // counter block; it works in the render's queue pool when that holds a batch, otherwise in a pool of its own.
 hipError_t wavefront_radiance(WavefrontState& st, const SceneView& scene, const SceneTraits& traits, const HrptPathTracerConstants& constants,
-                              const HrptRay* rays, float4* radiance, uint64_t count, bool accumulate, hipStream_t stream, std::string& error)
+                              const HrptRay* rays, float4* radiance, uint64_t count, bool accumulate, bool secondary, hipStream_t stream, std::string& error)
 {
     if (count == 0) return hipSuccess;
     hipError_t e; uint32_t cus = 0;
@@ -624,7 +627,7 @@ hipError_t wavefront_radiance(WavefrontState& st, const SceneView& scene, const 
         const BatchPlan batch = plan_batch(plan, st.knobs, a.numSamples);
         a.segSize = batch.segSize; a.numSegments = batch.numSegments;
         hipLaunchKernelGGL(wf_raygen_rays, dim3(batch.grid), dim3(kBlock), 0, stream, a, reinterpret_cast<const float4*>(rays + first));
-        if ((e = run_bounces(st, plan, traits, cus, batch, stream, a, constants, false, error)) != hipSuccess) return e;
+        if ((e = run_bounces(st, plan, traits, cus, batch, stream, a, constants, false, error, secondary ? 1 : 0)) != hipSuccess) return e;
         uint32_t sgrid = (a.numSamples + kBlock - 1) / kBlock; if (sgrid > cus * 8) sgrid = cus * 8;
         hipLaunchKernelGGL(wf_store_radiance, dim3(sgrid), dim3(kBlock), 0, stream, a, radiance + first, accumulate ? 1u : 0u);
         if ((e = hipGetLastError()) != hipSuccess) { error = "kernel launch"; return e; }

@@ -47,6 +47,8 @@ EXPORTS = [
     "hrpt_read_probe_irradiance", "hrpt_get_probe_irradiance_device", "hrpt_probes_read", "hrpt_probes_get_device", "hrpt_probes_write",
     "hrpt_probes_rays_host", "hrpt_probes_blend_host", "hrpt_probes_blend_device", "hrpt_probes_query_host",
     "hrpt_deferred_lighting", "hrpt_deferred_lighting_device", "hrpt_deferred_rays_host", "hrpt_deferred_shade_host",
+    "hrpt_indirect_lighting", "hrpt_indirect_compose", "hrpt_read_indirect", "hrpt_get_indirect_device", "hrpt_indirect_lighting_device",
+    "hrpt_indirect_compose_device", "hrpt_indirect_rays_device", "hrpt_indirect_resolve_device", "hrpt_indirect_rays_host", "hrpt_indirect_resolve_host", "hrpt_indirect_compose_host",
 ]
 
 lib.hrpt_create.argtypes = [C.POINTER(S.DeviceDesc), C.POINTER(C.c_void_p)]
@@ -164,6 +166,17 @@ lib.hrpt_deferred_lighting_device.argtypes = [C.c_void_p, C.POINTER(S.DeferredIm
 lib.hrpt_deferred_rays_host.argtypes = [C.POINTER(S.DeferredImages), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
 lib.hrpt_deferred_shade_host.argtypes = [C.POINTER(S.DeferredImages), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(S.DeferredParams), C.c_int]
+lib.hrpt_indirect_lighting.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(S.IndirectParams)]
+lib.hrpt_indirect_compose.argtypes = [C.c_void_p, C.POINTER(S.IndirectParams)]
+lib.hrpt_read_indirect.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+lib.hrpt_get_indirect_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+lib.hrpt_indirect_lighting_device.argtypes = [C.c_void_p, C.POINTER(S.IndirectImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.IndirectParams), C.c_void_p]
+lib.hrpt_indirect_compose_device.argtypes = [C.c_void_p, C.POINTER(S.IndirectImages), C.c_uint32, C.c_uint32, C.POINTER(S.IndirectParams), C.c_void_p]
+lib.hrpt_indirect_rays_device.argtypes = [C.c_void_p, C.POINTER(S.IndirectImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.IndirectParams), C.c_void_p, C.c_void_p]
+lib.hrpt_indirect_resolve_device.argtypes = [C.c_void_p, C.POINTER(S.IndirectImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.IndirectParams), C.c_void_p, C.c_void_p]
+lib.hrpt_indirect_rays_host.argtypes = [C.POINTER(S.IndirectImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.IndirectParams), C.c_void_p, C.c_int]
+lib.hrpt_indirect_resolve_host.argtypes = [C.POINTER(S.IndirectImages), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(S.IndirectParams), C.c_void_p, C.c_int]
+lib.hrpt_indirect_compose_host.argtypes = [C.POINTER(S.IndirectImages), C.c_uint32, C.c_uint32, C.POINTER(S.IndirectParams), C.c_int]
 lib.hrpt_halton.argtypes = [C.c_uint32, C.c_uint32]
 lib.hrpt_halton.restype = C.c_float
 lib.hrpt_precompute_atmosphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -466,6 +479,51 @@ def probes_query_host(volume, irradiance, distance, points, nthreads=0):
     points = np.ascontiguousarray(points, S.ProbePoint)
     out = np.zeros((len(points), 4), np.float32)
     _check_rc(lib.hrpt_probes_query_host(v.ctypes.data, irr.ctypes.data, dist.ctypes.data, points.ctypes.data, out.ctypes.data, len(points), int(nthreads)))
+    return out
+
+
+def _indirect_lobes(params):
+    return int(bool(params.flags & S.INDIRECT_DIFFUSE)) + int(bool(params.flags & S.INDIRECT_SPECULAR))
+
+
+def indirect_rays_host(albedo, normal, geo_normal, depth, constants, params=None, nthreads=0):
+    """hrpt_indirect_rays_host: the ray records (S.Ray [lobes, H, W], diffuse first) of every pixel of the four float32 [H, W, 4] planes
+    rendered with `constants` (csrc/pt_indirect.h). An untraced record has a NaN origin and zeros elsewhere. Needs no
+    GPU; bit-identical to the kernel."""
+    imgs, _, shape = _same_shape_images("indirect_rays_host", (albedo, normal, geo_normal, depth))
+    params = params if params is not None else S.IndirectParams()
+    cb = np.ascontiguousarray(constants, S.PathTracerConstants)
+    out = np.zeros((max(_indirect_lobes(params), 1), shape[0], shape[1]), S.Ray)
+    im = S.IndirectImages(*[a.ctypes.data for a in imgs], None, None, None)
+    _check_rc(lib.hrpt_indirect_rays_host(C.byref(im), shape[1], shape[0], cb.ctypes.data, C.byref(params), out.ctypes.data, int(nthreads)))
+    return out
+
+
+def indirect_resolve_host(albedo, normal, geo_normal, depth, constants, radiance, params=None, nthreads=0):
+    """hrpt_indirect_resolve_host: (diffuse, specular) float32 [H, W, 4] from the radiance of the records (float32 [lobes, H, W, 4], the layout
+    of indirect_rays_host); the plane of a lobe that is not flagged comes back as zeros."""
+    imgs, _, shape = _same_shape_images("indirect_resolve_host", (albedo, normal, geo_normal, depth))
+    params = params if params is not None else S.IndirectParams()
+    rad = np.ascontiguousarray(radiance, np.float32)
+    if rad.shape != (max(_indirect_lobes(params), 1),) + shape:
+        raise ValueError("indirect_resolve_host: radiance must be [lobes, H, W, 4]")
+    cb = np.ascontiguousarray(constants, S.PathTracerConstants)
+    dif, spec = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+    im = S.IndirectImages(*[a.ctypes.data for a in imgs], dif.ctypes.data, spec.ctypes.data, None)
+    _check_rc(lib.hrpt_indirect_resolve_host(C.byref(im), shape[1], shape[0], cb.ctypes.data, C.byref(params), rad.ctypes.data, int(nthreads)))
+    return dif, spec
+
+
+def indirect_compose_host(color, albedo, geo_normal, depth, diffuse, specular, params=None, nthreads=0):
+    """hrpt_indirect_compose_host: color + (diffuse * albedo * (1 - metallic) + specular) * intensity at hits, float32 [H, W, 4] (a new array)."""
+    imgs, _, shape = _same_shape_images("indirect_compose_host", (color, albedo, geo_normal, depth, diffuse))
+    (spec,), _, sshape = _same_shape_images("indirect_compose_host", (specular,))
+    if sshape != shape:
+        raise ValueError("indirect_compose_host: specular must have the images' shape")
+    params = params if params is not None else S.IndirectParams()
+    out = imgs[0].copy()
+    im = S.IndirectImages(imgs[1].ctypes.data, None, imgs[2].ctypes.data, imgs[3].ctypes.data, imgs[4].ctypes.data, spec.ctypes.data, out.ctypes.data)
+    _check_rc(lib.hrpt_indirect_compose_host(C.byref(im), shape[1], shape[0], C.byref(params), int(nthreads)))
     return out
 
 
@@ -859,11 +917,12 @@ class PathTracerContext:
         self._check(lib.hrpt_trace_rays(self._h, rays.ctypes.data, hits.ctypes.data, len(rays), flags))
         return hits
 
-    def trace_radiance(self, rays, constants, accumulate=False, thread_per_ray=False, out=None):
+    def trace_radiance(self, rays, constants, accumulate=False, thread_per_ray=False, out=None, secondary=False):
         """hrpt_trace_radiance: the path-traced radiance along each of `rays` (structured array of S.Ray: origin, unit direction, tmin and RNG
         state; tmax is ignored), float32 [n, 4] = (L.rgb, 1). Of `constants` (S.PathTracerConstants) the sun, m_LightCount and m_MaxBounces
         are read. accumulate: add (L, 1) to `out` (float32 [n, 4], required then) instead; out: the array to write, returned.
-        thread_per_ray: the one-thread-per-ray cross-check kernel instead of the wavefront pipeline. Synchronises."""
+        thread_per_ray: the one-thread-per-ray cross-check kernel instead of the wavefront pipeline. secondary (S.RADIANCE_SECONDARY): the rays
+        are path segment 1 -- they leave a first hit that is lit elsewhere -- so the bounce loop starts at index 1. Synchronises."""
         rays = np.ascontiguousarray(rays, S.Ray)
         if out is None:
             if accumulate:
@@ -872,7 +931,7 @@ class PathTracerContext:
         if out.dtype != np.float32 or out.shape != (len(rays), 4) or not out.flags.c_contiguous:
             raise ValueError("trace_radiance: out must be a contiguous float32 [len(rays), 4] array")
         cb = np.ascontiguousarray(constants, S.PathTracerConstants)
-        flags = (S.RADIANCE_ACCUMULATE if accumulate else 0) | (S.RADIANCE_THREAD_PER_RAY if thread_per_ray else 0)
+        flags = (S.RADIANCE_ACCUMULATE if accumulate else 0) | (S.RADIANCE_THREAD_PER_RAY if thread_per_ray else 0) | (S.RADIANCE_SECONDARY if secondary else 0)
         self._check(lib.hrpt_trace_radiance(self._h, rays.ctypes.data, out.ctypes.data, len(rays), cb.ctypes.data, flags))
         return out
 
@@ -896,10 +955,56 @@ class PathTracerContext:
 
     def trace_radiance_device(self, rays_ptr, out_ptr, count, constants, flags=0):
         """hrpt_trace_radiance over device arrays (integer addresses of `count` S.Ray records and `count` float4 slots, e.g. a torch tensor's
-        data_ptr()): no copies, asynchronous on the context stream. flags: S.RADIANCE_ACCUMULATE / S.RADIANCE_THREAD_PER_RAY."""
+        data_ptr()): no copies, asynchronous on the context stream. flags: S.RADIANCE_ACCUMULATE / S.RADIANCE_THREAD_PER_RAY / S.RADIANCE_SECONDARY."""
         cb = np.ascontiguousarray(constants, S.PathTracerConstants)
         self._check(lib.hrpt_trace_radiance(self._h, C.c_void_p(int(rays_ptr)), C.c_void_p(int(out_ptr)), int(count), cb.ctypes.data,
                                             int(flags) | S.RADIANCE_DEVICE_POINTERS))
+
+    def indirect_lighting(self, constants, params=None):
+        """hrpt_indirect_lighting: one traced diffuse and one traced specular ray per first hit, from the planes S.GB_ALBEDO, GB_NORMAL,
+        GB_GEO_NORMAL and GB_DEPTH that render_gbuffer wrote with the same `constants`, into two library-owned planes (read_indirect). Output
+        and Accumulation are not touched (csrc/pt_indirect.h). Default params: both lobes, seed 0. Asynchronous."""
+        params = params if params is not None else S.IndirectParams()
+        cb = np.ascontiguousarray(constants, S.PathTracerConstants)
+        self._check(lib.hrpt_indirect_lighting(self._h, cb.ctypes.data, C.byref(params)))
+
+    def indirect_compose(self, params=None):
+        """hrpt_indirect_compose: Output += (diffuse * albedo * (1 - metallic) + specular) * params.intensity at hits."""
+        params = params if params is not None else S.IndirectParams()
+        self._check(lib.hrpt_indirect_compose(self._h, C.byref(params)))
+
+    def read_indirect(self, which):
+        """One of the planes indirect_lighting wrote (0 = diffuse, 1 = specular): float32 [H, W, 4] (synchronises)."""
+        return self._read_image(lib.hrpt_read_indirect, args=(int(which),))
+
+    def indirect_device(self, which):
+        """Device pointer of that plane (None before the first indirect_lighting and after a resize)."""
+        return self._device_ptr(lib.hrpt_get_indirect_device, (int(which),))
+
+    def indirect_lighting_device(self, images, width, height, constants, params=None, hip_stream=0):
+        """The same over caller-owned device images (S.IndirectImages of device addresses), with this context's scene, on `hip_stream`."""
+        params = params if params is not None else S.IndirectParams()
+        cb = np.ascontiguousarray(constants, S.PathTracerConstants)
+        self._check(lib.hrpt_indirect_lighting_device(self._h, C.byref(images), int(width), int(height), cb.ctypes.data, C.byref(params), C.c_void_p(int(hip_stream))))
+
+    def indirect_rays_device(self, images, width, height, constants, rays_ptr, params=None, hip_stream=0):
+        """hrpt_indirect_rays_device: the ray-record kernel alone, into a device array of width * height S.Ray per flagged lobe."""
+        params = params if params is not None else S.IndirectParams()
+        cb = np.ascontiguousarray(constants, S.PathTracerConstants)
+        self._check(lib.hrpt_indirect_rays_device(self._h, C.byref(images), int(width), int(height), cb.ctypes.data, C.byref(params), C.c_void_p(int(rays_ptr)),
+                                                  C.c_void_p(int(hip_stream))))
+
+    def indirect_resolve_device(self, images, width, height, constants, radiance_ptr, params=None, hip_stream=0):
+        """hrpt_indirect_resolve_device: the resolve kernel alone, from a device array of one float4 per record into images.diffuse / specular."""
+        params = params if params is not None else S.IndirectParams()
+        cb = np.ascontiguousarray(constants, S.PathTracerConstants)
+        self._check(lib.hrpt_indirect_resolve_device(self._h, C.byref(images), int(width), int(height), cb.ctypes.data, C.byref(params), C.c_void_p(int(radiance_ptr)),
+                                                     C.c_void_p(int(hip_stream))))
+
+    def indirect_compose_device(self, images, width, height, params=None, hip_stream=0):
+        """hrpt_indirect_compose_device: images.colorInOut += the composed images.diffuse / images.specular, on `hip_stream`."""
+        params = params if params is not None else S.IndirectParams()
+        self._check(lib.hrpt_indirect_compose_device(self._h, C.byref(images), int(width), int(height), C.byref(params), C.c_void_p(int(hip_stream))))
 
     def set_shadow_overlap(self, enabled):
         """Intra-frame overlap of the shadow stage with the next bounce's traversal (default on); turn off for contexts used as lanes of

@@ -253,6 +253,7 @@ Ray = np.dtype([("origin", f32, 3), ("tmin", f32), ("direction", f32, 3), ("tmax
 RayHit = np.dtype([("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32), ("hit", u32), ("rng", u32), ("pad", u32)])   # HrptRayHit, 32 B
 RAYS_CLOSEST, RAYS_SHADOW, RAYS_DEVICE_POINTERS, RAYS_THREAD_PER_RAY = 0, 1, 0x100, 0x200
 RADIANCE_DEVICE_POINTERS, RADIANCE_THREAD_PER_RAY, RADIANCE_ACCUMULATE = 0x100, 0x200, 0x400       # hrpt_trace_radiance flags
+RADIANCE_SECONDARY = 0x1000     # ray i is path segment 1 (a ray that leaves a first hit), not 0
 # first-hit G-buffer (hrpt_render_gbuffer): plane indices HRPT_GB_*, the all-planes mask, the flag bits of the ids plane's w
 GB_ALBEDO, GB_NORMAL, GB_GEO_NORMAL, GB_EMISSIVE, GB_DEPTH, GB_IDS, GB_PLANES = 0, 1, 2, 3, 4, 5, 6
 GB_ALL_PLANES = 0x3F
@@ -288,6 +289,25 @@ class DeferredParams(C.Structure):
 class DeferredImages(C.Structure):
     """HrptDeferredImages: host or device addresses of width x height float4 images; indirect may be None without DEFERRED_INDIRECT."""
     _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "geoNormal", "emissive", "depth", "indirect", "colorOut")]
+
+
+# traced indirect lighting (hrpt_indirect_lighting; DESIGN.md section 29)
+INDIRECT_DIFFUSE, INDIRECT_SPECULAR, INDIRECT_THREAD_PER_RAY = 1, 2, 0x200
+
+
+class IndirectParams(C.Structure):
+    """HrptIndirectParams. flags: INDIRECT_DIFFUSE / INDIRECT_SPECULAR pick the lobes (at least one), INDIRECT_THREAD_PER_RAY traces with the
+    one-thread-per-ray kernel; frameSeed seeds the per-pixel draws; intensity scales what compose adds."""
+    _fields_ = [("flags", C.c_uint32), ("frameSeed", C.c_uint32), ("intensity", C.c_float), ("reserved", C.c_uint32)]
+
+    def __init__(self, flags=INDIRECT_DIFFUSE | INDIRECT_SPECULAR, frameSeed=0, intensity=1.0):
+        super().__init__(flags, frameSeed, intensity)
+
+
+class IndirectImages(C.Structure):
+    """HrptIndirectImages: host or device addresses of width x height float4 images. Lighting / resolve write diffuse and specular (the plane of
+    a lobe that is not flagged may be None); compose reads them and adds into colorInOut."""
+    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "geoNormal", "depth", "diffuse", "specular", "colorInOut")]
 
 
 class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B

@@ -591,12 +591,17 @@ int  hrpt_trace_rays(HrptContext* ctx, const HrptRay* rays, HrptRayHit* hits, ui
  * aligned, nothing is copied and the call is asynchronous on the context stream. Either way it is ordered on that stream with renders and
  * scene updates. hrpt_resize is not required. Accumulation, Output, every G-buffer plane and every history, the exposure buffer and every
  * HrptStats field (megakernelFallbacks included) stay as they were.
+ * HRPT_RADIANCE_SECONDARY: ray i is path segment 1, a ray that leaves a first hit somebody else has lit (hrpt_indirect_lighting). The bounce
+ * loop runs bounce = 1 .. m_MaxBounces - 1 and everything that depends on the bounce index takes the true index: no sun disk at a miss, no
+ * specular direct light, roulette from index 2. With m_MaxBounces <= 1 nothing is traced and a finite ray stores (0, 0, 0, 1). The record,
+ * the batching, the other flags, the non-finite rule and the errors are the same.
  * count == 0: HRPT_OK, nothing happens. No scene: HRPT_ERR_NO_SCENE. m_MaxBounces above 64 or m_LightCount above the scene's light count (as
  * hrpt_render), unknown flag bits, a NULL pointer, more than 2^31 rays, HRPT_RADIANCE_THREAD_PER_RAY on a two-level structure deeper than
  * that kernel's 64-entry stack: HRPT_ERR_INVALID_ARGUMENT. An error changes nothing. */
 #define HRPT_RADIANCE_DEVICE_POINTERS 0x100u  /* rays / radiance are device pointers; asynchronous on the context stream */
 #define HRPT_RADIANCE_THREAD_PER_RAY  0x200u  /* testing: the one-thread-per-ray kernel (same results) */
 #define HRPT_RADIANCE_ACCUMULATE      0x400u  /* radiance[i].rgb += L, radiance[i].w += 1 instead of (L, 1) */
+#define HRPT_RADIANCE_SECONDARY       0x1000u /* ray i is path segment 1 instead of 0 (0x800 stays an unknown bit) */
 int  hrpt_trace_radiance(HrptContext* ctx, const HrptRay* rays, float* radiance4, uint64_t count,
                          const HrptPathTracerConstants* constants, uint32_t flags);
 
@@ -1126,6 +1131,71 @@ int  hrpt_deferred_rays_host(const HrptDeferredImages* images, uint32_t width, u
 int  hrpt_deferred_shade_host(const HrptDeferredImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
                               const HrptGPULight* lights, uint32_t lightCount, const float* visibility, const float* sunRadiance, const float* sky,
                               const HrptDeferredParams* params, int nthreads);
+
+/* ---- traced indirect lighting at the first hit --------------------------------------------------------------------------------------
+ * The producer of the reference's SSGI.hlsl -- one GGX-VNDF specular ray and one cosine diffuse ray per pixel from the G-buffer, two
+ * demodulated signals for the temporal, denoise and compose passes -- with the screen-space march replaced by path-traced rays
+ * (hrpt_trace_radiance with HRPT_RADIANCE_SECONDARY). Additive; HRPT_ABI_VERSION stays 3.
+ * One source for kernels and host executors: hobbyrenderer_amd/csrc/pt_indirect.h; DESIGN.md section 29 has every operation in order.
+ * Per pixel (x, y), g = y * W + x, over the planes ALBEDO (A), NORMAL (N, roughness in w), GEO_NORMAL (metallic in w), DEPTH (.x = t):
+ * (o, d) = the primary ray of `constants` (the ones the G-buffer was rendered with); X = o + d * t, V = -d; s = pcg_hash(g +
+ * pcg_hash(frameSeed)), u0..u3 = rng_next(&s). Diffuse record: untraced when !(1 - metallic > 0) or !(dot(N, dirD) > 0), dirD =
+ * sample_hemisphere_cosine(u0, u1, N); else origin X, tmin 1e-4f, direction dirD, tmax 1e10f, rng s. Specular record: H =
+ * sample_ggx_vndf(u2, u3, N, V, roughness), dirS = reflect(-V, H), wS = eval_ggx_vndf_weight(compute_f0(A.rgb, metallic, 1.5f), N, V, dirS,
+ * H, roughness); untraced when !(dot(N, dirS) > 0) or !(maxcomp(wS) > 0); else origin X, tmin 1e-4f, direction dirS, tmax 1e10f, rng
+ * pcg_hash(s). An untraced record (every record of a miss): origin = NaN, the rest 0. Diffuse records at [g], specular records at
+ * [W * H + g]; with one lobe flagged its records sit at [g]. Resolve: diffuse = (Ld.rgb, 1) where the record's radiance has w == 1, else
+ * zeros (DEMODULATED: no albedo, cosine-sampling weight 1); specular = (Ls.rgb * wS, 1), else zeros (carries F * G1). A miss resolves to
+ * zeros. Compose, where depth.x != 1e10f: rgb = C.rgb + ((((Dp.rgb * A.rgb) * (1 - metallic)) + Sp.rgb) * intensity); alpha is kept and
+ * misses pass through. */
+#define HRPT_INDIRECT_DIFFUSE        1u
+#define HRPT_INDIRECT_SPECULAR       2u
+#define HRPT_INDIRECT_THREAD_PER_RAY 0x200u   /* testing: passed to the trace as HRPT_RADIANCE_THREAD_PER_RAY (same results) */
+typedef struct HrptIndirectParams {
+    uint32_t flags;              /* HRPT_INDIRECT_*; at least one lobe */
+    uint32_t frameSeed;
+    float intensity;             /* finite; read by compose */
+    uint32_t reserved;           /* 0 */
+} HrptIndirectParams;
+typedef struct HrptIndirectImages {
+    const float *albedo, *normal, *geoNormal, *depth;
+    float *diffuse, *specular;   /* lighting / resolve: written (the plane of a lobe that is not flagged may be NULL); compose: read */
+    float *colorInOut;           /* compose only; lighting ignores it */
+} HrptIndirectImages;            /* a written image must differ from every other image of the call */
+/* Over the context's own planes into two library-owned float4 planes (allocated on first use, dropped by hrpt_resize; the plane of a lobe
+ * that is not flagged is zeroed): a kernel writes the records, hrpt_trace_radiance(HRPT_RADIANCE_DEVICE_POINTERS | HRPT_RADIANCE_SECONDARY)
+ * runs on library-owned buffers and reads m_MaxBounces, m_LightCount and the sun from `constants`, a kernel resolves. The result equals,
+ * bit for bit, hrpt_indirect_rays_host -> hrpt_trace_radiance -> hrpt_indirect_resolve_host through the public calls. Accumulation, Output,
+ * the G-buffer, histories, exposure and HrptStats are untouched. Asynchronous on the context stream. No scene: HRPT_ERR_NO_SCENE.
+ * hrpt_resize not called, one of the four planes never requested (the message names it), no lobe flag, unknown flag bits, non-zero
+ * reserved, a non-finite intensity, the argument errors of hrpt_trace_radiance: HRPT_ERR_INVALID_ARGUMENT. An error changes nothing. */
+int  hrpt_indirect_lighting(HrptContext* ctx, const HrptPathTracerConstants* constants, const HrptIndirectParams* params);
+/* Output.rgb += the composed planes of the last hrpt_indirect_lighting at the current size (before one: HRPT_ERR_INVALID_ARGUMENT). */
+int  hrpt_indirect_compose(HrptContext* ctx, const HrptIndirectParams* params);
+/* which: 0 = diffuse, 1 = specular. read synchronises; bytes = width * height * 16. */
+int  hrpt_read_indirect(HrptContext* ctx, uint32_t which, float* dst, size_t bytes);
+int  hrpt_get_indirect_device(HrptContext* ctx, uint32_t which, void** devicePtr);
+/* The same over caller-owned DEVICE images of width x height float4 (16-byte aligned), with the scene and ray buffers of `ctx`; every step
+ * runs on `stream` (a hipStream_t; NULL = the default stream). Null or aliased images: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_indirect_lighting_device(HrptContext* ctx, const HrptIndirectImages* deviceImages, uint32_t width, uint32_t height,
+                                   const HrptPathTracerConstants* constants, const HrptIndirectParams* params, void* stream);
+int  hrpt_indirect_compose_device(HrptContext* ctx, const HrptIndirectImages* deviceImages, uint32_t width, uint32_t height,
+                                  const HrptIndirectParams* params, void* stream);
+/* The two kernels around the trace on their own, for a caller that traces the records itself: raysOut receives width * height HrptRay per
+ * flagged lobe, radiance4 holds one float4 per record, both DEVICE arrays in the layout above. Neither needs a scene. */
+int  hrpt_indirect_rays_device(HrptContext* ctx, const HrptIndirectImages* deviceImages, uint32_t width, uint32_t height,
+                               const HrptPathTracerConstants* constants, const HrptIndirectParams* params, HrptRay* raysOut, void* stream);
+int  hrpt_indirect_resolve_device(HrptContext* ctx, const HrptIndirectImages* deviceImages, uint32_t width, uint32_t height,
+                                  const HrptPathTracerConstants* constants, const HrptIndirectParams* params, const float* radiance4, void* stream);
+/* The three stages on the host, with no GPU and no scene; same bits as the kernels. rays: raysOut receives width * height records per
+ * flagged lobe, laid out as above (only albedo, normal, geoNormal and depth of `images` are read). resolve: radiance4 holds one float4
+ * per record in the same layout. */
+int  hrpt_indirect_rays_host(const HrptIndirectImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
+                             const HrptIndirectParams* params, HrptRay* raysOut, int nthreads);
+int  hrpt_indirect_resolve_host(const HrptIndirectImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
+                                const HrptIndirectParams* params, const float* radiance4, int nthreads);
+int  hrpt_indirect_compose_host(const HrptIndirectImages* images, uint32_t width, uint32_t height, const HrptIndirectParams* params,
+                                int nthreads);
 
 /* Intra-frame overlap: by default the shadow stage of bounce b runs on a second, library-owned stream next to the traversal of bounce
  * b + 1 (they share no buffer). That fills the tails of a context that renders one frame at a time (-3 % per frame). A host that keeps
