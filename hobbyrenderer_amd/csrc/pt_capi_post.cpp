@@ -7,14 +7,20 @@
 using namespace hrt;
 using namespace hrt::capi;
 
-// The context's histogram and exposure (initially 1), allocated by the first post pass.
+// The context's histogram (initially all zero) and exposure (initially 1), allocated by the first post pass or hrpt_set_exposure: the one
+// place that allocates and initialises them.
 static int post_buffers(HrptContext* c)
 {
     if (c->perContext.dExposure) return HRPT_OK;
-    HIP_TRY(c, c->perContext.dExposure.alloc(16));
-    HIP_TRY(c, c->perContext.dHistogram.alloc(256 * sizeof(uint32_t)));
+    DeviceBuffer<float> exposure;
+    DeviceBuffer<uint32_t> histogram;
+    HIP_TRY(c, exposure.alloc(16));
+    HIP_TRY(c, histogram.alloc(256 * sizeof(uint32_t)));
     const float one[4] = { 1.0f, 0.0f, 0.0f, 0.0f };
-    HIP_TRY(c, hipMemcpy(c->perContext.dExposure, one, 16, hipMemcpyHostToDevice));
+    const uint32_t zero[256] = {};
+    HIP_TRY(c, hipMemcpy(exposure, one, 16, hipMemcpyHostToDevice));      // both complete on return: ordered before every later launch
+    HIP_TRY(c, hipMemcpy(histogram, zero, sizeof zero, hipMemcpyHostToDevice));
+    c->perContext.dExposure = std::move(exposure); c->perContext.dHistogram = std::move(histogram);
     return HRPT_OK;
 }
 
@@ -551,10 +557,7 @@ int hrpt_set_exposure(HrptContext* c, float exposure)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->perContext.dExposure) {
-        HIP_TRY(c, c->perContext.dExposure.alloc(16));
-        HIP_TRY(c, c->perContext.dHistogram.alloc(256 * sizeof(uint32_t)));
-    }
+    HRPT_TRY(post_buffers(c));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(c->perContext.dExposure, &exposure, sizeof(float), hipMemcpyHostToDevice));
     return HRPT_OK;

@@ -17,7 +17,7 @@ __global__ __launch_bounds__(256) void post_histogram(const float4* __restrict__
     __shared__ uint32_t local[256];
     local[threadIdx.x] = 0;
     __syncthreads();
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {   // 64-bit: n may lie within one stride of 2^32
         float4 c = hdr[i];
         float lum = dot(mk3(c.x, c.y, c.z), mk3(0.2126f, 0.7152f, 0.0722f));       // GetLuminance
         uint32_t bin = 0;                                                             // ColorToBin
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void post_tonemap(const float4* __restrict__ h
                                                     const float* __restrict__ exposure, uint32_t hdrDisplay, float maxNits)
 {
     float e = exposure[0];
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {   // 64-bit: n may lie within one stride of 2^32
         float4 c4 = hdr[i];
         f3 c = mk3(c4.x, c4.y, c4.z) * e;
         f3 o;

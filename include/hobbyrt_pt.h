@@ -698,13 +698,16 @@ typedef struct HrptPostParams {
 } HrptPostParams;
 int  hrpt_post_process(HrptContext* ctx, const HrptPostParams* params);
 int  hrpt_read_display(HrptContext* ctx, float* rgba, size_t bytes);           /* W*H*16 bytes */
-int  hrpt_get_exposure(HrptContext* ctx, float* exposure, uint32_t histogram256[256]);   /* histogram may be NULL */
+/* The exposure and the histogram of the last auto-exposure pass (histogram may be NULL). The histogram is all zero until the first
+ * auto-exposure pass, and again after every manual-exposure pass; before any post pass or hrpt_set_exposure: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_get_exposure(HrptContext* ctx, float* exposure, uint32_t histogram256[256]);
 int  hrpt_set_exposure(HrptContext* ctx, float exposure);                      /* the persistent exposure buffer, initially 1 */
 /* The same chain over caller-owned DEVICE images (pixelCount float4 each; e.g. the upscaled image of hrpt_upscale, whose size is not the
  * context's), asynchronous on the caller's stream (a hipStream_t; NULL = the default stream). It runs on the context's histogram and
  * exposure, exactly as hrpt_post_process does: on a copy of Output it writes hrpt_post_process's display image bit for bit and leaves the
- * same exposure. hdrDevice is only read; displayDevice must differ from it. NULL pointers or pixelCount outside 1..2^32-1:
- * HRPT_ERR_INVALID_ARGUMENT. */
+ * same exposure. hdrDevice is only read; displayDevice must differ from it. pixelCount may be anything in 1..2^32-1: above 524288 pixels
+ * (2048 blocks of 256 threads) the kernels walk the image in strides, with a 64-bit index that cannot wrap. NULL pointers or pixelCount
+ * outside 1..2^32-1: HRPT_ERR_INVALID_ARGUMENT, before anything is launched. */
 int  hrpt_post_process_device(HrptContext* ctx, const float* hdrDevice, float* displayDevice, uint64_t pixelCount, const HrptPostParams* params, void* stream);
 
 /* ---- Bloom: the stage in front of the post chain ---------------------------------------------------------------
