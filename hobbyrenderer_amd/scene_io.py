@@ -13,8 +13,14 @@ LIB_PATH = os.path.join(_HERE, "libhobbyrt_scene.so")
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: run `make -C hobbyrenderer_amd/csrc` (or __graft_entry__.build())")
 lib = C.CDLL(LIB_PATH)
+EXPORTS = []
 
-EXPORTS = ["hrsc_last_error", "hrsc_cooked_mesh_load", "hrsc_cooked_mesh_free", "hrsc_cooked_mesh_save", "hrsc_cache_is_valid"]
+
+def declare(name, argtypes, restype=C.c_int):
+    """The one declaration of entry point `name`: native's helper, copied so that this module loads without libhobbyrt_pt.so."""
+    fn = getattr(lib, name)
+    fn.argtypes, fn.restype = argtypes, restype
+    EXPORTS.append(name)
 
 
 class _CookedMesh(C.Structure):
@@ -24,12 +30,11 @@ class _CookedMesh(C.Structure):
                 ("vertexCount", C.c_uint64), ("vertices", C.c_void_p), ("indexCount", C.c_uint64), ("indices", C.c_void_p)]
 
 
-lib.hrsc_last_error.restype = C.c_char_p
-lib.hrsc_cooked_mesh_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(_CookedMesh))]
-lib.hrsc_cooked_mesh_free.argtypes = [C.POINTER(_CookedMesh)]
-lib.hrsc_cooked_mesh_free.restype = None
-lib.hrsc_cooked_mesh_save.argtypes = [C.c_char_p, C.POINTER(_CookedMesh)]
-lib.hrsc_cache_is_valid.argtypes = [C.c_char_p, C.c_char_p]
+declare("hrsc_last_error", [], restype=C.c_char_p)
+declare("hrsc_cooked_mesh_load", [C.c_char_p, C.POINTER(C.POINTER(_CookedMesh))])
+declare("hrsc_cooked_mesh_free", [C.POINTER(_CookedMesh)], restype=None)
+declare("hrsc_cooked_mesh_save", [C.c_char_p, C.POINTER(_CookedMesh)])
+declare("hrsc_cache_is_valid", [C.c_char_p, C.c_char_p])
 
 HRSC_ERR_IO, HRSC_ERR_FORMAT = -2, -3
 
@@ -117,18 +122,15 @@ class _SceneView(C.Structure):
                 ("loadedFromMeshCache", C.c_uint32)]
 
 
-EXPORTS += ["hrsc_scene_load", "hrsc_scene_free", "hrsc_scene_view", "hrsc_scene_warning", "hrsc_decode_image", "hrsc_decode_image_ex", "hrsc_free_pixels", "hrsc_selftest_bc7_tables"]
-lib.hrsc_decode_image_ex.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                     C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-lib.hrsc_scene_load.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
-lib.hrsc_scene_free.argtypes = [C.c_void_p]
-lib.hrsc_scene_free.restype = None
-lib.hrsc_scene_view.argtypes = [C.c_void_p, C.POINTER(_SceneView)]
-lib.hrsc_scene_warning.argtypes = [C.c_void_p, C.c_uint32]
-lib.hrsc_scene_warning.restype = C.c_char_p
-lib.hrsc_decode_image.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
-lib.hrsc_free_pixels.argtypes = [C.c_void_p]
-lib.hrsc_free_pixels.restype = None
+declare("hrsc_scene_load", [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)])
+declare("hrsc_scene_free", [C.c_void_p], restype=None)
+declare("hrsc_scene_view", [C.c_void_p, C.POINTER(_SceneView)])
+declare("hrsc_scene_warning", [C.c_void_p, C.c_uint32], restype=C.c_char_p)
+declare("hrsc_decode_image", [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)])
+declare("hrsc_decode_image_ex", [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)])
+declare("hrsc_free_pixels", [C.c_void_p], restype=None)
+declare("hrsc_selftest_bc7_tables", [])
 
 LOAD_USE_MESH_CACHE = 1
 

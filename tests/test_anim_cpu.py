@@ -206,31 +206,8 @@ def test_argument_errors_leave_the_outputs_untouched():
     anim.close()
 
 
-def test_abi(tmp_path):
-    structs = {"HrptAnimSampler": (S.AnimSampler, ["interpolation", "firstKey", "keyCount", "animation"]),
-               "HrptAnimChannel": (S.AnimChannel, ["path", "sampler", "firstTarget", "targetCount"]),
-               "HrptAnimNode": (S.AnimNode, ["parent", "translation", "rotation", "scale", "baseWorld", "firstInstance", "instanceCount"]),
-               "HrptAnimJoint": (S.AnimJoint, ["node", "inverseBind"]),
-               "HrptAnimationDesc": (S.AnimationDesc, [f for f, _ in S.AnimationDesc._fields_])}
-    lines = "".join(f'printf("%zu\\n", sizeof({n}));\n' + "".join(f'printf("%zu\\n", offsetof({n}, {f}));\n' for f in fields) for n, (_, fields) in structs.items())
-    constants = ["HRPT_ANIM_PATH_TRANSLATION", "HRPT_ANIM_PATH_ROTATION", "HRPT_ANIM_PATH_SCALE", "HRPT_ANIM_PATH_WEIGHTS", "HRPT_ANIM_STEP", "HRPT_ANIM_LINEAR",
-                 "HRPT_ANIM_CUBICSPLINE", "HRPT_ANIM_CATMULLROM", "HRPT_ANIM_SLERP", "HRPT_ANIMATE_REFIT", "HRPT_ANIMATE_NO_COMMIT", "HRPT_ANIM_LDS_MAX_ANIMATIONS",
-                 "HRPT_ABI_VERSION"]
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hobbyrt_pt.h"\nint main(void){\n' + lines +
-                   "".join(f'printf("%d\\n", (int){k});\n' for k in constants) + "return 0;}\n")
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
-    want = []
-    for _, (t, fields) in structs.items():
-        if isinstance(t, np.dtype):
-            want += [t.itemsize] + [t.fields[f][1] for f in fields]
-        else:
-            want += [C.sizeof(t)] + [getattr(t, f).offset for f in fields]
-    want += [S.ANIM_PATH_TRANSLATION, S.ANIM_PATH_ROTATION, S.ANIM_PATH_SCALE, S.ANIM_PATH_WEIGHTS, S.ANIM_STEP, S.ANIM_LINEAR, S.ANIM_CUBICSPLINE,
-             S.ANIM_CATMULLROM, S.ANIM_SLERP, S.ANIMATE_REFIT, S.ANIMATE_NO_COMMIT, S.ANIM_LDS_MAX_ANIMATIONS, S.ABI_VERSION]
-    assert out == want and S.ABI_VERSION == 3 and C.sizeof(S.AnimationDesc) == 104
+def test_abi():
+    assert S.ABI_VERSION == 3 and C.sizeof(S.AnimationDesc) == 104      # that the C header says the same: test_binding_contract.py
     for name in ("hrpt_animation_create", "hrpt_animation_destroy", "hrpt_animation_advance", "hrpt_animation_set_times", "hrpt_animation_get_times",
                  "hrpt_animate_host", "hrpt_animate", "hrpt_get_animation_device", "hrpt_read_animation", "hrpt_animation_release"):
         assert name in native.EXPORTS and getattr(native.lib, name)

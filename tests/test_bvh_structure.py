@@ -2,7 +2,6 @@
 the validator of tests/bvh_reference.py -- and the validator itself, which must report each hand-made corruption (twelve of the flat structure, six of the two-level one, the folded decode) by name."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -26,18 +25,6 @@ def check_flat(scene, **kw):
         assert not rep, str(rep)
     assert own["nodes4"].tobytes() == sep["nodes4"].tobytes() and own["maxDepth4"] == sep["maxDepth4"]
     return own
-
-
-def test_dump_struct_matches_header(tmp_path):
-    src = tmp_path / "dump.c"
-    fields = [f for f, _ in S.BvhDump._fields_]
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hobbyrt_pt.h"\nint main(void){printf("%zu\\n", sizeof(HrptBvhDump));\n' +
-                   "".join(f'printf("%zu\\n", offsetof(HrptBvhDump, {f}));\n' for f in fields) + "return 0;}\n")
-    exe = tmp_path / "dump"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
-    assert out[0] == C.sizeof(S.BvhDump)
-    assert out[1:] == [getattr(S.BvhDump, f).offset for f in fields]
 
 
 def test_cornell(luts):

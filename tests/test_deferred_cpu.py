@@ -6,7 +6,6 @@ import ctypes as C
 import math
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -42,13 +41,7 @@ def test_symbols_are_exported_declared_and_bound():
         assert name in native.EXPORTS and hasattr(native.lib, name) and f" {name}(" in header, name
     assert "#define HRPT_ABI_VERSION 3" in header and S.ABI_VERSION == 3
     assert (S.DEFERRED_SHADOWS, S.DEFERRED_SKY, S.DEFERRED_INDIRECT) == (1, 2, 4)
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"hobbyrt_pt.h\"\nint main(void){printf(\"%zu %zu %zu %zu %zu %zu %zu %u %u %u\\n\", sizeof(HrptDeferredParams), " \
-          "offsetof(HrptDeferredParams, indirectIntensity), offsetof(HrptDeferredParams, reserved), sizeof(HrptDeferredImages), offsetof(HrptDeferredImages, depth), " \
-          "offsetof(HrptDeferredImages, indirect), offsetof(HrptDeferredImages, colorOut), HRPT_DEFERRED_SHADOWS, HRPT_DEFERRED_SKY, HRPT_DEFERRED_INDIRECT);return 0;}\n"
-    with tempfile.TemporaryDirectory() as tmp:              # the C header says the same, to a C compiler
-        exe = os.path.join(tmp, "deferred_layout")
-        subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-        assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split() == ["16", "4", "8", "56", "32", "40", "48", "1", "2", "4"]
+    # that the C header says the same as the mirrors: test_binding_contract.py
     assert C.sizeof(S.DeferredParams) == 16 and S.DeferredParams.indirectIntensity.offset == 4 and S.DeferredParams.reserved.offset == 8
     assert C.sizeof(S.DeferredImages) == 56 and (S.DeferredImages.depth.offset, S.DeferredImages.indirect.offset, S.DeferredImages.colorOut.offset) == (32, 40, 48)
 

@@ -59,14 +59,8 @@ def _finite_tangent(v):
     return v
 
 
-def test_abi_and_argument_errors(tmp_path):
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "hobbyrt_pt.h"\nint main(void){printf("%zu %d %d %d\\n", sizeof(HrptVertexFloat), '
-                   'HRPT_VERTICES_REFIT, HRPT_VERTICES_SAME_FRAME, HRPT_ABI_VERSION);return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    assert subprocess.check_output([str(exe)]).decode().split() == ["48", str(S.VERTICES_REFIT), str(S.VERTICES_SAME_FRAME), "3"]
-    assert S.VertexFloat.itemsize == 48 and S.ABI_VERSION == 3
+def test_abi_and_argument_errors():
+    assert S.VertexFloat.itemsize == 48 and S.ABI_VERSION == 3      # that the C header says the same: test_binding_contract.py
     one_in, one_out = np.zeros(1, S.VertexFloat), np.zeros(1, S.VertexQuantized)
     assert native.lib.hrpt_quantize_vertices_host(None, 1, one_out.ctypes.data, 1) == -1
     assert native.lib.hrpt_quantize_vertices_host(one_in.ctypes.data, 1, None, 1) == -1

@@ -5,7 +5,6 @@ invariance; the argument errors; and the sanitizer build of the host side (`make
 import ctypes as C
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -45,14 +44,7 @@ def test_symbols_are_exported_declared_and_bound():
         assert name in native.EXPORTS and hasattr(native.lib, name) and f" {name}(" in header, name
     assert "#define HRPT_ABI_VERSION 3" in header and S.ABI_VERSION == 3
     assert S.ProbeVolume.itemsize == 64 and S.ProbePoint.itemsize == 48 and (S.PROBES_RESET, S.PROBES_DEVICE_POINTERS) == (1, 0x100)
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"hobbyrt_pt.h\"\nint main(void){printf(\"%zu %zu %zu %zu %zu %zu %u %u\\n\", sizeof(HrptProbeVolume), " \
-          "sizeof(HrptProbePoint), offsetof(HrptProbeVolume, counts), offsetof(HrptProbeVolume, distanceExponent), offsetof(HrptProbeVolume, pad), " \
-          "offsetof(HrptProbePoint, view), HRPT_PROBES_RESET, HRPT_PROBES_DEVICE_POINTERS);return 0;}\n"
-    with tempfile.TemporaryDirectory() as tmp:              # the C header says the same, to a C compiler
-        exe = os.path.join(tmp, "probes_layout")
-        subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-        assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split() == ["64", "48", "32", "48", "60", "32", "1", "256"]
-    fields = {k: S.ProbeVolume.fields[k][1] for k in S.ProbeVolume.names}
+    fields = {k: S.ProbeVolume.fields[k][1] for k in S.ProbeVolume.names}      # that the C header says the same: test_binding_contract.py
     assert (fields["counts"], fields["distanceExponent"], fields["pad"], S.ProbePoint.fields["view"][1]) == (32, 48, 60, 32)
 
 

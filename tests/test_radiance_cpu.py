@@ -20,17 +20,8 @@ def test_symbol_is_exported_and_declared():
     assert callable(native.PathTracerContext.trace_radiance) and callable(native.PathTracerContext.trace_radiance_device)
 
 
-def test_flag_values_match_header(tmp_path):
-    names = ["HRPT_RADIANCE_DEVICE_POINTERS", "HRPT_RADIANCE_THREAD_PER_RAY", "HRPT_RADIANCE_ACCUMULATE", "HRPT_RAYS_DEVICE_POINTERS",
-             "HRPT_RAYS_THREAD_PER_RAY", "HRPT_RAYS_SHADOW", "HRPT_ABI_VERSION"]
-    src = tmp_path / "flags.c"
-    src.write_text('#include <stdio.h>\n#include "hobbyrt_pt.h"\nint main(void){\n' + "".join(f'printf("%ld\\n", (long)({n}));\n' for n in names) +
-                   'printf("%zu\\n", sizeof(HrptRay));return 0;}\n')
-    exe = tmp_path / "flags"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
-    assert out == [S.RADIANCE_DEVICE_POINTERS, S.RADIANCE_THREAD_PER_RAY, S.RADIANCE_ACCUMULATE, S.RAYS_DEVICE_POINTERS, S.RAYS_THREAD_PER_RAY,
-                   S.RAYS_SHADOW, S.ABI_VERSION, S.Ray.itemsize]
+def test_flag_values_match_header():
+    # that the C header gives the mirrored names the same values, and HrptRay the same size: test_binding_contract.py
     assert (S.RADIANCE_DEVICE_POINTERS, S.RADIANCE_THREAD_PER_RAY, S.RADIANCE_ACCUMULATE, S.ABI_VERSION) == (0x100, 0x200, 0x400, 3)
     # the same meaning keeps the same bit as in hrpt_trace_rays; the new one is a bit of its own, clear of that call's query kinds too
     assert S.RADIANCE_DEVICE_POINTERS == S.RAYS_DEVICE_POINTERS and S.RADIANCE_THREAD_PER_RAY == S.RAYS_THREAD_PER_RAY

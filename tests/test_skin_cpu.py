@@ -105,19 +105,8 @@ def test_skin_then_quantise(case, statement):
     assert ((got["m_Normal"] >> 30) & 1).any() and not ((got["m_Normal"] >> 30) & 1).all()
 
 
-def test_abi(tmp_path):
-    fields = ["base", "joints", "weights", "jointMatrices", "deltas", "morphWeights", "count", "jointCount", "targetCount", "reserved"]
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hobbyrt_pt.h"\nint main(void){printf("%zu %zu %d %d\\n", sizeof(HrptSkinMorphDelta), '
-                   'sizeof(HrptSkinArgs), HRPT_SKIN_LDS_MAX_JOINTS, HRPT_ABI_VERSION);\n' +
-                   "".join(f'printf("%zu\\n", offsetof(HrptSkinArgs, {f}));\n' for f in fields) +
-                   "".join(f'printf("%zu\\n", offsetof(HrptSkinMorphDelta, {f}));\n' for f in ("pos", "normal", "tangent")) + "return 0;}\n")
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    out = subprocess.check_output([str(exe)]).decode().split()
-    assert out[:4] == ["36", str(C.sizeof(S.SkinArgs)), str(S.SKIN_LDS_MAX_JOINTS), "3"] and C.sizeof(S.SkinArgs) == 64 and S.ABI_VERSION == 3
-    assert [int(x) for x in out[4:14]] == [getattr(S.SkinArgs, f).offset for f in fields]
-    assert [int(x) for x in out[14:]] == [S.SkinMorphDelta.fields[f][1] for f in ("pos", "normal", "tangent")] and S.SkinMorphDelta.itemsize == 36
+def test_abi():
+    assert C.sizeof(S.SkinArgs) == 64 and S.ABI_VERSION == 3 and S.SkinMorphDelta.itemsize == 36      # that the C header says the same: test_binding_contract.py
     for name in ("hrpt_skin_vertices_host", "hrpt_skin_vertices_device", "hrpt_update_vertices_skinned"):
         assert name in native.EXPORTS and getattr(native.lib, name)
 
