@@ -26,6 +26,21 @@ int capi::realloc_image(HrptContext* c, DeviceBuffer<float4>& image, size_t byte
     return HRPT_OK;
 }
 
+int capi::planes_requested(HrptContext* c, const char* what, uint32_t gbMask, bool motion)
+{
+    static const char* const kNames[HRPT_GB_PLANES] = { "ALBEDO", "NORMAL", "GEO_NORMAL", "EMISSIVE", "DEPTH", "IDS" };
+    uint32_t first = HRPT_GB_PLANES;             // the first G-buffer plane of the mask that is missing
+    for (uint32_t k = HRPT_GB_PLANES; k-- > 0;)
+        if ((gbMask & (1u << k)) && !c->perSize.dGBuffer[k]) first = k;
+    const bool noMotion = motion && !c->perSize.dMotion;
+    if (!noMotion && first == HRPT_GB_PLANES) return HRPT_OK;        // the text is built for a failure only
+    std::string mask;
+    for (uint32_t k = 0; k < HRPT_GB_PLANES; ++k)
+        if (gbMask & (1u << k)) mask += std::string(mask.empty() ? "" : " | ") + kNames[k];
+    return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": " + (noMotion ? std::string("the motion plane") : std::string("the plane HRPT_GB_") + kNames[first]) +
+                                              " was never requested (" + (motion ? "" : "hrpt_render_gbuffer or ") + "hrpt_render_motion_vectors with planeMask = " + mask + " fills them)");
+}
+
 int hrpt_create(const HrptDeviceDesc* desc, HrptContext** out)
 try {
     if (!desc || !out) return fail(nullptr, HRPT_ERR_INVALID_ARGUMENT, "hrpt_create: null argument");
@@ -102,26 +117,17 @@ try {
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_resize: size must be 1..65535 (RNG seed packs y*65536+x, RNG.hlsli:24)");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->perSize.dAccum.reset(); c->perSize.dOutput.reset(); c->perSize.dDisplay.reset();      // all three go before anything is allocated
+    PerSizeImages& ps = c->perSize;
+    ps.dAccum.reset(); ps.dOutput.reset(); ps.stage = StageImages{};      // Accumulation, Output, Display and whatever else a stage allocated go before anything is allocated
     const size_t bytes = (size_t)width * height * sizeof(float4);
-    HRPT_TRY(realloc_image(c, c->perSize.dAccum, bytes));
-    HRPT_TRY(realloc_image(c, c->perSize.dOutput, bytes));
-    for (DeviceBuffer<float4>& plane : c->perSize.dGBuffer)         // the G-buffer planes a caller has asked for follow the image size (zeroed, like a first request)
+    HRPT_TRY(realloc_image(c, ps.dAccum, bytes));
+    HRPT_TRY(realloc_image(c, ps.dOutput, bytes));
+    for (DeviceBuffer<float4>& plane : ps.dGBuffer)         // the G-buffer planes a caller has asked for follow the image size (zeroed, like a first request)
         if (plane) HRPT_TRY(realloc_image(c, plane, bytes));
-    if (c->perSize.dMotion) HRPT_TRY(realloc_image(c, c->perSize.dMotion, bytes));       // ... and so does the motion plane
-    c->temporalValid = false; c->temporalCur = 0;     // the temporal history does not survive a resize
-    for (DeviceBuffer<float4>& image : c->perSize.dTemporal)
+    if (ps.dMotion) HRPT_TRY(realloc_image(c, ps.dMotion, bytes));       // ... and so does the motion plane
+    ps.temporalValid = false; ps.temporalCur = 0;     // the temporal history does not survive a resize
+    for (DeviceBuffer<float4>& image : ps.dTemporal)
         if (image) HRPT_TRY(realloc_image(c, image, bytes));
-    for (DeviceBuffer<float4>& image : c->perSize.dDenoiseScratch) image.reset();        // allocated again by the call that needs it
-    c->perSize.dModulation.reset();                                             // written again by the next hrpt_demodulate
-    for (DeviceBuffer<float4>& image : c->perSize.dUpscaleHistory) image.reset();        // allocated again, without history, by the next hrpt_upscale
-    c->perSize.dProbeIrradiance.reset();                                        // written again by the next hrpt_probes_shade_gbuffer
-    c->perSize.dDeferredRays.reset(); c->perSize.dDeferredHits.reset(); c->perSize.deferredPairs = 0;      // sized again by the next hrpt_deferred_lighting
-    for (DeviceBuffer<float4>& image : c->perSize.dDeferredCarry) image.reset();
-    c->perSize.deferredCarryPixels = 0;
-    for (DeviceBuffer<float4>& image : c->perSize.dIndirect) image.reset();               // written again by the next hrpt_indirect_lighting
-    c->perSize.dIndirectRays.reset(); c->perSize.dIndirectRadiance.reset(); c->perSize.indirectRecords = 0;
-    c->perSize.dUpscaled.reset(); c->upscaleValid = false; c->upscaleCur = 0; c->upscaleWidth = c->upscaleHeight = 0;
     c->width = width; c->height = height;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_resize"); }
@@ -176,7 +182,7 @@ try {
 } catch (...) { return caught(c, what); }
 int hrpt_read_accumulation(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->perSize.dAccum : nullptr, rgba, bytes, "hrpt_read_accumulation"); }
 int hrpt_read_output(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->perSize.dOutput : nullptr, rgba, bytes, "hrpt_read_output"); }
-int hrpt_read_display(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->perSize.dDisplay : nullptr, rgba, bytes, "hrpt_read_display"); }
+int hrpt_read_display(HrptContext* c, float* rgba, size_t bytes) { return read_image(c, c ? c->perSize.stage.dDisplay : nullptr, rgba, bytes, "hrpt_read_display"); }
 
 int hrpt_write_accumulation(HrptContext* c, const float* rgba, size_t bytes)
 try {
@@ -246,7 +252,7 @@ try {
     }
     out->closestRays = total.closestRays; out->shadowRays = total.shadowRays; out->paths = total.paths;
     out->neeEntries = total.neeEntries; out->neeSamples = total.neeSamples;
-    out->megakernelFallbacks = c->megakernelFallbacks; out->queuePoolBytes = c->wf.poolBytes;
+    out->megakernelFallbacks = c->megakernelFallbacks; out->queuePoolBytes = c->wf.pool.bytes();
     if (total.neeEntries || c->wf.raygenBytes || c->wf.resolveBytes) {     // the wavefront pipeline ran since the last reset
         wavefront_queue_bytes(c->wf, total, out->traceQueueBytes, out->shadeQueueBytes, out->shadowQueueBytes);
         out->raygenQueueBytes = c->wf.raygenBytes; out->resolveQueueBytes = c->wf.resolveBytes;

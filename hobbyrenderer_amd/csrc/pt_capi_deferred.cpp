@@ -34,22 +34,16 @@ static int deferred_run(HrptContext* c, const HrptDeferredImages& im, uint32_t w
     if (B < 1u) B = 1u;
     while (B > 1u && WH * B > (1ull << 31)) --B;                  // one hrpt_trace_rays call takes at most 2^31 rays
     const bool shadows = (p.flags & HRPT_DEFERRED_SHADOWS) != 0u && n > 0u;
-    PerSizeImages& ps = c->perSize;
-    if (shadows && ps.deferredPairs < WH * B) {
-        ps.deferredPairs = 0;
-        HIP_TRY(c, ps.dDeferredRays.alloc(WH * B * sizeof(HrptRay)));
-        HIP_TRY(c, ps.dDeferredHits.alloc(WH * B * sizeof(HrptRayHit)));
-        ps.deferredPairs = WH * B;
+    StageImages& ps = c->perSize.stage;
+    if (shadows) {
+        HIP_TRY(c, ps.dDeferredRays.reserve(WH * B * sizeof(HrptRay)));
+        HIP_TRY(c, ps.dDeferredHits.reserve(WH * B * sizeof(HrptRayHit)));
     }
-    if (n > B && ps.deferredCarryPixels < WH) {
-        ps.deferredCarryPixels = 0;
-        for (DeviceBuffer<float4>& image : ps.dDeferredCarry) HIP_TRY(c, image.alloc(WH * sizeof(float4)));
-        ps.deferredCarryPixels = WH;
-    }
+    if (n > B)
+        for (DeviceBuffer<float4>& image : ps.dDeferredCarry) HIP_TRY(c, image.reserve(WH * sizeof(float4)));
     const float sunIntensity = c->keptLights.empty() ? 0.0f : c->keptLights[0].m_Intensity;
     const deferred::Frame f = deferred::make_frame(cb, p, sunIntensity, (int)width, (int)height);
-    struct StreamGuard { HrptContext* c; hipStream_t saved; ~StreamGuard() { c->stream = saved; } } guard = { c, c->stream };
-    c->stream = stream;
+    const ScopedStream redirect(c, stream);
     uint32_t first = 0;
     do {
         const uint32_t count = n - first < B ? n - first : B;
@@ -80,19 +74,15 @@ try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     HRPT_TRY(common_check(c, "hrpt_deferred_lighting", constants, params));
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_deferred_lighting: hrpt_resize not called");
-    static const struct { int plane; const char* name; } needed[5] = { { HRPT_GB_ALBEDO, "HRPT_GB_ALBEDO" }, { HRPT_GB_NORMAL, "HRPT_GB_NORMAL" },
-        { HRPT_GB_GEO_NORMAL, "HRPT_GB_GEO_NORMAL" }, { HRPT_GB_EMISSIVE, "HRPT_GB_EMISSIVE" }, { HRPT_GB_DEPTH, "HRPT_GB_DEPTH" } };
-    for (const auto& n : needed)
-        if (!c->perSize.dGBuffer[n.plane])
-            return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_deferred_lighting: the plane ") + n.name + " was never requested (hrpt_render_gbuffer or hrpt_render_motion_vectors with planeMask = ALBEDO | NORMAL | GEO_NORMAL | EMISSIVE | DEPTH fills them)");
-    if ((params->flags & HRPT_DEFERRED_INDIRECT) && !c->perSize.dProbeIrradiance)
+    PerSizeImages& ps = c->perSize;
+    HRPT_TRY(planes_requested(c, "hrpt_deferred_lighting", 1u << HRPT_GB_ALBEDO | 1u << HRPT_GB_NORMAL | 1u << HRPT_GB_GEO_NORMAL | 1u << HRPT_GB_EMISSIVE | 1u << HRPT_GB_DEPTH, false));
+    if ((params->flags & HRPT_DEFERRED_INDIRECT) && !ps.stage.dProbeIrradiance)
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_deferred_lighting: HRPT_DEFERRED_INDIRECT with no probe irradiance plane at the current size (hrpt_probes_shade_gbuffer writes it)");
     HIP_TRY(c, hipSetDevice(c->device));
-    auto plane = [&](int i) { return reinterpret_cast<const float*>(c->perSize.dGBuffer[i].get()); };
     HrptDeferredImages im = {};
-    im.albedo = plane(HRPT_GB_ALBEDO); im.normal = plane(HRPT_GB_NORMAL); im.geoNormal = plane(HRPT_GB_GEO_NORMAL); im.emissive = plane(HRPT_GB_EMISSIVE);
-    im.depth = plane(HRPT_GB_DEPTH); im.indirect = reinterpret_cast<const float*>(c->perSize.dProbeIrradiance.get());
-    im.colorOut = reinterpret_cast<float*>(c->perSize.dOutput.get());
+    im.albedo = floats(ps.dGBuffer[HRPT_GB_ALBEDO]); im.normal = floats(ps.dGBuffer[HRPT_GB_NORMAL]); im.geoNormal = floats(ps.dGBuffer[HRPT_GB_GEO_NORMAL]);
+    im.emissive = floats(ps.dGBuffer[HRPT_GB_EMISSIVE]); im.depth = floats(ps.dGBuffer[HRPT_GB_DEPTH]); im.indirect = floats(ps.stage.dProbeIrradiance);
+    im.colorOut = floats(ps.dOutput);
     return deferred_run(c, im, c->width, c->height, *constants, *params, c->stream);
 } catch (...) { return caught(c, "hrpt_deferred_lighting"); }
 

@@ -218,12 +218,8 @@ static int update_vertices_staged(HrptContext* c, const std::string& what, uint3
     if (count == 0) { roll_previous_positions(c, 0, 0, flags); return HRPT_OK; }
     HIP_TRY(c, hipStreamSynchronize(stream));           // whatever writes the caller's arrays has to be done before the kernel below reads them
     const size_t recordBytes = (size_t)count * sizeof(HrptVertexQuantized);
-    if (!c->perScene.dDeformStaging) {                           // once per scene: room for the whole vertex buffer + the status words
-        const size_t bytes = c->keptVertices.size() * sizeof(HrptVertexQuantized) + kStatusBytes;
-        HIP_TRY(c, c->perScene.dDeformStaging.alloc(bytes));
-        c->perScene.deformStagingBytes = bytes;
-    }
-    if (recordBytes + kStatusBytes > c->perScene.deformStagingBytes) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": range exceeds the staging buffer");
+    HIP_TRY(c, c->perScene.dDeformStaging.reserve(c->keptVertices.size() * sizeof(HrptVertexQuantized) + kStatusBytes));      // once per scene: room for the whole vertex buffer + the status words
+    if (recordBytes + kStatusBytes > c->perScene.dDeformStaging.bytes()) return fail(c, HRPT_ERR_INVALID_ARGUMENT, what + ": range exceeds the staging buffer");
     HrptVertexQuantized* staged = static_cast<HrptVertexQuantized*>(c->perScene.dDeformStaging.get());
     uint32_t* dStatus = reinterpret_cast<uint32_t*>(static_cast<char*>(c->perScene.dDeformStaging.get()) + recordBytes);
     HIP_TRY(c, hipMemsetAsync(dStatus, 0, kStatusBytes, c->stream));

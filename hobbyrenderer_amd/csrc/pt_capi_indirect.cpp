@@ -61,42 +61,32 @@ static int lighting_run(HrptContext* c, const HrptIndirectImages& im, uint32_t w
 {
     const size_t WH = (size_t)width * height, n = indirect::record_count(p.flags, WH);
     if (n > (1ull << 31)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_indirect_lighting: more than 2^31 ray records (one hrpt_trace_radiance call)");
-    PerSizeImages& ps = c->perSize;
-    if (ps.indirectRecords < n) {
-        ps.indirectRecords = 0;
-        HIP_TRY(c, ps.dIndirectRays.alloc(n * sizeof(HrptRay)));
-        HIP_TRY(c, ps.dIndirectRadiance.alloc(n * sizeof(float4)));
-        ps.indirectRecords = n;
-    }
+    StageImages& ps = c->perSize.stage;
+    HIP_TRY(c, ps.dIndirectRays.reserve(n * sizeof(HrptRay)));
+    HIP_TRY(c, ps.dIndirectRadiance.reserve(n * sizeof(float4)));
     const indirect::Frame f = indirect::make_frame(cb, p, (int)width, (int)height);
-    struct StreamGuard { HrptContext* c; hipStream_t saved; ~StreamGuard() { c->stream = saved; } } guard = { c, c->stream };
-    c->stream = stream;
+    const ScopedStream redirect(c, stream);
     HIP_TRY(c, launch_indirect_rays(f, im, ps.dIndirectRays, stream));
     const uint32_t traceFlags = HRPT_RADIANCE_DEVICE_POINTERS | HRPT_RADIANCE_SECONDARY | ((p.flags & HRPT_INDIRECT_THREAD_PER_RAY) ? HRPT_RADIANCE_THREAD_PER_RAY : 0u);
-    HRPT_TRY(hrpt_trace_radiance(c, ps.dIndirectRays, reinterpret_cast<float*>(ps.dIndirectRadiance.get()), (uint64_t)n, &cb, traceFlags));
+    HRPT_TRY(hrpt_trace_radiance(c, ps.dIndirectRays, floats(ps.dIndirectRadiance), (uint64_t)n, &cb, traceFlags));
     HIP_TRY(c, launch_indirect_resolve(f, im, ps.dIndirectRadiance, stream));
     return HRPT_OK;
 }
-
-static const float* plane_of(HrptContext* c, int i) { return reinterpret_cast<const float*>(c->perSize.dGBuffer[i].get()); }
 
 int hrpt_indirect_lighting(HrptContext* c, const HrptPathTracerConstants* constants, const HrptIndirectParams* params)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     HRPT_TRY(lighting_check(c, "hrpt_indirect_lighting", constants, params));
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_indirect_lighting: hrpt_resize not called");
-    static const struct { int plane; const char* name; } needed[4] = { { HRPT_GB_ALBEDO, "HRPT_GB_ALBEDO" }, { HRPT_GB_NORMAL, "HRPT_GB_NORMAL" },
-        { HRPT_GB_GEO_NORMAL, "HRPT_GB_GEO_NORMAL" }, { HRPT_GB_DEPTH, "HRPT_GB_DEPTH" } };
-    for (const auto& n : needed)
-        if (!c->perSize.dGBuffer[n.plane])
-            return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_indirect_lighting: the plane ") + n.name + " was never requested (hrpt_render_gbuffer or hrpt_render_motion_vectors with planeMask = ALBEDO | NORMAL | GEO_NORMAL | DEPTH fills them)");
+    PerSizeImages& ps = c->perSize;
+    HRPT_TRY(planes_requested(c, "hrpt_indirect_lighting", 1u << HRPT_GB_ALBEDO | 1u << HRPT_GB_NORMAL | 1u << HRPT_GB_GEO_NORMAL | 1u << HRPT_GB_DEPTH, false));
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
-    for (DeviceBuffer<float4>& image : c->perSize.dIndirect)
+    for (DeviceBuffer<float4>& image : ps.stage.dIndirect)
         if (!image) HRPT_TRY(realloc_image(c, image, bytes));
     HrptIndirectImages im = {};
-    im.albedo = plane_of(c, HRPT_GB_ALBEDO); im.normal = plane_of(c, HRPT_GB_NORMAL); im.geoNormal = plane_of(c, HRPT_GB_GEO_NORMAL); im.depth = plane_of(c, HRPT_GB_DEPTH);
-    im.diffuse = reinterpret_cast<float*>(c->perSize.dIndirect[0].get()); im.specular = reinterpret_cast<float*>(c->perSize.dIndirect[1].get());
+    im.albedo = floats(ps.dGBuffer[HRPT_GB_ALBEDO]); im.normal = floats(ps.dGBuffer[HRPT_GB_NORMAL]); im.geoNormal = floats(ps.dGBuffer[HRPT_GB_GEO_NORMAL]);
+    im.depth = floats(ps.dGBuffer[HRPT_GB_DEPTH]); im.diffuse = floats(ps.stage.dIndirect[0]); im.specular = floats(ps.stage.dIndirect[1]);
     return lighting_run(c, im, c->width, c->height, *constants, *params, c->stream);
 } catch (...) { return caught(c, "hrpt_indirect_lighting"); }
 
@@ -115,13 +105,13 @@ try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     HRPT_TRY(params_check(c, "hrpt_indirect_compose", params));
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_indirect_compose: hrpt_resize not called");
-    if (!c->perSize.dIndirect[0] || !c->perSize.dIndirect[1])
+    PerSizeImages& ps = c->perSize;
+    if (!ps.stage.dIndirect[0] || !ps.stage.dIndirect[1])
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_indirect_compose: no indirect planes at the current size (hrpt_indirect_lighting writes them)");
     HIP_TRY(c, hipSetDevice(c->device));
     HrptIndirectImages im = {};
-    im.albedo = plane_of(c, HRPT_GB_ALBEDO); im.geoNormal = plane_of(c, HRPT_GB_GEO_NORMAL); im.depth = plane_of(c, HRPT_GB_DEPTH);
-    im.diffuse = reinterpret_cast<float*>(c->perSize.dIndirect[0].get()); im.specular = reinterpret_cast<float*>(c->perSize.dIndirect[1].get());
-    im.colorInOut = reinterpret_cast<float*>(c->perSize.dOutput.get());
+    im.albedo = floats(ps.dGBuffer[HRPT_GB_ALBEDO]); im.geoNormal = floats(ps.dGBuffer[HRPT_GB_GEO_NORMAL]); im.depth = floats(ps.dGBuffer[HRPT_GB_DEPTH]);
+    im.diffuse = floats(ps.stage.dIndirect[0]); im.specular = floats(ps.stage.dIndirect[1]); im.colorInOut = floats(ps.dOutput);
     HIP_TRY(c, launch_indirect_compose(im, c->width, c->height, params->intensity, c->stream));
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_indirect_compose"); }
@@ -170,15 +160,15 @@ int hrpt_read_indirect(HrptContext* c, uint32_t which, float* dst, size_t bytes)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (which > 1u) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_indirect: which must be 0 (diffuse) or 1 (specular)");
-    if (!c->perSize.dIndirect[which]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_indirect: no indirect planes at the current size (hrpt_indirect_lighting writes them)");
-    return read_image(c, c->perSize.dIndirect[which], dst, bytes, "hrpt_read_indirect");
+    if (!c->perSize.stage.dIndirect[which]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_indirect: no indirect planes at the current size (hrpt_indirect_lighting writes them)");
+    return read_image(c, c->perSize.stage.dIndirect[which], dst, bytes, "hrpt_read_indirect");
 } catch (...) { return caught(c, "hrpt_read_indirect"); }
 
 int hrpt_get_indirect_device(HrptContext* c, uint32_t which, void** devicePtr)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (which > 1u || !devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_indirect_device: which must be 0 or 1, and out not null");
-    *devicePtr = c->perSize.dIndirect[which];
+    *devicePtr = c->perSize.stage.dIndirect[which];
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_get_indirect_device"); }
 

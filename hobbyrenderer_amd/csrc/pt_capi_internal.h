@@ -1,4 +1,5 @@
-// pt_capi_internal.h -- what the pt_capi*.cpp files share: the context, the status / error plumbing and the exception guard.
+// pt_capi_internal.h -- what the pt_capi*.cpp files share: the context, the status / error plumbing, the exception guard and the way from
+// the context's images to a stage's image struct.
 // Host code of the C boundary only: no .hip file and no header a kernel includes may include it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -44,42 +45,50 @@ struct AnimDeviceCopy {
 // Buffers that live as long as the uploaded scene: free_scene drops them with one assignment.
 struct PerSceneBuffers {
     // the device tables the first motion call (hrpt_render_motion_vectors) builds from the kept copies
-    DeviceBuffer<MotionInst> dMotionInst; size_t motionInstCapacity = 0;       // one record per instance: m_PrevWorld + the mesh's LOD-0 index offset
+    DeviceBuffer<MotionInst> dMotionInst;                                      // one record per instance: m_PrevWorld + the mesh's LOD-0 index offset
     DeviceBuffer<float> dMotionPositions; DeviceBuffer<uint32_t> dMotionIndices;   // object-space positions (12 B per vertex) and the index buffer
     bool motionInstStale = true, motionGeometryStale = true;                   // set by uploads / instance updates / rebuilds, cleared by the next motion call
     // deforming meshes (hrpt_update_vertices): the object-space positions of the previous frame, 3 floats per vertex; EMPTY = previous == current
     // (a context that never deforms pays nothing). The device copy is made by the next motion call (motionPositionsStale), like dMotionPositions.
     std::vector<float> keptPrevPositions; DeviceBuffer<float> dMotionPrevPositions; bool motionPositionsStale = true;
     DeviceBuffer<HrptVertexFloat> dSkinFloats;                                 // hrpt_update_vertices_skinned: the skinned float vertices between its two kernels, sized for the whole vertex buffer at first use
-    DeviceBuffer<void> dDeformStaging; size_t deformStagingBytes = 0;          // hrpt_update_vertices_device / _skinned: quantised records + the two status words, sized for the whole vertex buffer at first use
+    DeviceBuffer<void> dDeformStaging;                                         // hrpt_update_vertices_device / _skinned: quantised records + the two status words, sized for the whole vertex buffer at first use
 };
 
-// Images of width * height float4: hrpt_resize decides which of them survive a change of size.
+// What a stage allocates at first use, grows on demand and finds gone after a resize: hrpt_resize drops all of it with one assignment, and
+// the stage's next call makes its part again at the new size. A stage with images of this kind adds them here and nowhere else.
+struct StageImages {
+    DeviceBuffer<float4> dDisplay;                   // hrpt_post_process
+    DeviceBuffer<float4> dDenoiseScratch[2];         // the scratch pair of HRPT_DENOISE_OUTPUT_ONLY
+    DeviceBuffer<float4> dModulation;                // demodulate / compose: the stored factor, written by hrpt_demodulate
+    // temporal upscaling (hrpt_upscale): ping-pong history pair and the colour image, all of upscaleWidth x upscaleHeight (the DISPLAY size of
+    // the last call, not the context's), re-allocated when the display size changes; [upscaleCur] is the history the last call wrote
+    DeviceBuffer<float4> dUpscaleHistory[2], dUpscaled;
+    uint32_t upscaleWidth = 0, upscaleHeight = 0; int upscaleCur = 0; bool upscaleValid = false;
+    DeviceBuffer<float4> dProbeIrradiance;           // hrpt_probes_shade_gbuffer: the probe volume's irradiance at the first hits
+    // deferred lighting (hrpt_deferred_lighting): shadow-ray and hit records of one light batch, and the two running-sum images of a multi-batch call
+    DeviceBuffer<HrptRay> dDeferredRays; DeviceBuffer<HrptRayHit> dDeferredHits;
+    DeviceBuffer<float4> dDeferredCarry[2];
+    // traced indirect lighting (hrpt_indirect_lighting): the two resolved planes ([0] diffuse, [1] specular) and the ray and radiance records of one call
+    DeviceBuffer<float4> dIndirect[2];
+    DeviceBuffer<HrptRay> dIndirectRays; DeviceBuffer<float4> dIndirectRadiance;
+};
+
+// Images of width * height float4. The members named here are the ones hrpt_resize makes again at the new size, zeroed and without
+// history (the G-buffer planes, the motion plane and the temporal pair only where a call has requested them); `stage` it drops.
 struct PerSizeImages {
-    DeviceBuffer<float4> dAccum, dOutput, dDisplay;
-    DeviceBuffer<float4> dGBuffer[HRPT_GB_PLANES];   // first-hit G-buffer planes (hrpt_render_gbuffer): allocated by the first call that requests one, re-allocated by hrpt_resize
+    DeviceBuffer<float4> dAccum, dOutput;
+    DeviceBuffer<float4> dGBuffer[HRPT_GB_PLANES];   // first-hit G-buffer planes (hrpt_render_gbuffer): allocated by the first call that requests one
     DeviceBuffer<float4> dMotion;                    // first-hit motion vectors (hrpt_render_motion_vectors)
     DeviceBuffer<float4> dTemporal[2];               // temporal accumulation (hrpt_temporal_accumulate): ping-pong history pair, allocated by the first call
-    DeviceBuffer<float4> dDenoiseScratch[2];         // the scratch pair of HRPT_DENOISE_OUTPUT_ONLY
-    DeviceBuffer<float4> dModulation;                // demodulate / compose: the stored factor, allocated by the first hrpt_demodulate, dropped by hrpt_resize
-    // temporal upscaling (hrpt_upscale): ping-pong history pair and the colour image, all of upscaleWidth x upscaleHeight (the DISPLAY size of
-    // the last call, not the context's); allocated by the first call, re-allocated when the display size changes, dropped by hrpt_resize
-    DeviceBuffer<float4> dUpscaleHistory[2], dUpscaled;
-    DeviceBuffer<float4> dProbeIrradiance;           // hrpt_probes_shade_gbuffer: the probe volume's irradiance at the first hits, allocated by the first call, dropped by hrpt_resize
-    // deferred lighting (hrpt_deferred_lighting): shadow-ray and hit records of one light batch (deferredPairs = pixels * batch of the last
-    // allocation) and the two running-sum images of a multi-batch call; allocated on first use, grown on demand, dropped by hrpt_resize
-    DeviceBuffer<HrptRay> dDeferredRays; DeviceBuffer<HrptRayHit> dDeferredHits; size_t deferredPairs = 0;
-    DeviceBuffer<float4> dDeferredCarry[2]; size_t deferredCarryPixels = 0;
-    // traced indirect lighting (hrpt_indirect_lighting): the two resolved planes ([0] diffuse, [1] specular) and the ray and radiance records
-    // of one call (indirectRecords = what the last allocation holds); allocated on first use, grown on demand, dropped by hrpt_resize
-    DeviceBuffer<float4> dIndirect[2];
-    DeviceBuffer<HrptRay> dIndirectRays; DeviceBuffer<float4> dIndirectRadiance; size_t indirectRecords = 0;
+    int temporalCur = 0; bool temporalValid = false; // [temporalCur] is the history image the last hrpt_temporal_accumulate wrote
+    StageImages stage;
 };
 
 // Buffers that live as long as the context.
 struct PerContextBuffers {
     DeviceBuffer<uint32_t> dHistogram; DeviceBuffer<float> dExposure;   // persistent exposure buffer (HDRRenderer m_RG_ExposureBuffer)
-    DeviceBuffer<uint32_t> dBloomDown, dBloomUp; size_t bloomWords = 0;    // bloom pyramids (packed R11G11B10_FLOAT), sized by the last bloom call
+    DeviceBuffer<uint32_t> dBloomDown, dBloomUp;                        // bloom pyramids (packed R11G11B10_FLOAT), sized by the last bloom call
     DeviceBuffer<float> dDenoiseTile;                // the default noise tile, uploaded by the first denoise call of the context
     DeviceBuffer<DeviceCounters> dCounters;
 };
@@ -92,7 +101,7 @@ struct Context {
     // scene
     DeviceAllocations allocations;           // scene-lifetime device allocations
     DeviceAllocations bvhAllocations;        // acceleration structure of the host builder + per-instance records: replaced by hrpt_update_instances
-    DeviceBuffer<GpuNodeQ> nodesQ; size_t nodesQCapacity = 0;    // quantised copy of the flat 4-wide tree (pt_scene_records.h GpuNodeQ), kept across rebuilds
+    DeviceBuffer<GpuNodeQ> nodesQ;           // quantised copy of the flat 4-wide tree (pt_scene_records.h GpuNodeQ), kept across rebuilds
     uint32_t nodes4Capacity = 0;             // records behind view.nodes4 when it is the GPU builder's buffer (0: allocated to size), for hrpt_selftest_read_bvh
     std::unique_ptr<GpuBvhBuilder> gpuBuilder;   // GPU builders: geometry + build buffers stay on the device for rebuilds
     std::unique_ptr<GpuBvhBuilder> tlasBuilder; uint32_t tlasBuilderInstances = 0;   // two-level structure: the tree over the instances, built on the GPU (build_two_level)
@@ -107,8 +116,6 @@ struct Context {
     // images
     uint32_t width = 0, height = 0;
     PerSizeImages perSize;
-    int temporalCur = 0; bool temporalValid = false;   // [temporalCur] is the history image the last hrpt_temporal_accumulate wrote
-    uint32_t upscaleWidth = 0, upscaleHeight = 0; int upscaleCur = 0; bool upscaleValid = false;   // [upscaleCur] is the history the last hrpt_upscale wrote
     PerContextBuffers perContext;
     uint32_t bloomTailTexels = 0;            // HRPT_BLOOM_FUSED_TAIL: levels of at most this many texels run in one workgroup's LDS (0 = one kernel per pass, the measured-faster default)
     uint32_t deferredLightBatch = 0;         // HRPT_DEFERRED_LIGHT_BATCH: lights per pass of hrpt_deferred_lighting, 1..16 (0 = min(m_LightCount, 4))
@@ -178,6 +185,23 @@ inline bool exceeds_private_stack(const SceneTraits& traits) { return traits.two
 inline bool size_ok(uint32_t width, uint32_t height) { return !(width == 0 || height == 0 || width > 65535u || height > 65535u); }
 int realloc_image(HrptContext* c, DeviceBuffer<float4>& image, size_t bytes);      // a fresh image, zeroed on the context stream
 int read_image(HrptContext* c, const float4* src, float* dst, size_t bytes, const char* what);
+
+// ---- from the context's images to a stage's image struct ----
+// An image as the stages' image structs take it, a plain array of floats: the one place that recasts.
+inline const float* floats(const DeviceBuffer<float4>& image) { return reinterpret_cast<const float*>(image.get()); }
+inline float* floats(DeviceBuffer<float4>& image) { return reinterpret_cast<float*>(image.get()); }
+// The G-buffer planes of `gbMask` (bits 1 << HRPT_GB_*), and the motion plane if `motion`, must have been requested from a G-buffer or
+// motion call: the message names `what`, the first plane that is missing and the planeMask that would fill them all.
+int planes_requested(HrptContext* c, const char* what, uint32_t gbMask, bool motion);
+// c->stream redirected for a scope: the public trace calls a stage is composed of then run on the stage's stream.
+class ScopedStream {
+public:
+    ScopedStream(HrptContext* c, hipStream_t stream) : c_(c), saved_(c->stream) { c->stream = stream; }
+    ~ScopedStream() { c_->stream = saved_; }
+    ScopedStream(const ScopedStream&) = delete; ScopedStream& operator=(const ScopedStream&) = delete;
+private:
+    HrptContext* c_; hipStream_t saved_;
+};
 
 // Device room for `count` records owned by `owner` (default: the scene's allocation list), with host[skip .. count) copied into place:
 // the records in front of `skip` are the caller's to write on the device.

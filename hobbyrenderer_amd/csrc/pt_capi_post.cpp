@@ -45,8 +45,8 @@ try {
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_post_process: hrpt_resize not called");
     HIP_TRY(c, hipSetDevice(c->device));
     HRPT_TRY(post_buffers(c));
-    if (!c->perSize.dDisplay) HIP_TRY(c, c->perSize.dDisplay.alloc((size_t)c->width * c->height * sizeof(float4)));
-    HIP_TRY(c, launch_post_chain(c->perSize.dOutput, c->perSize.dDisplay, c->width * c->height, *p, c->perContext.dHistogram, c->perContext.dExposure, c->stream));
+    HIP_TRY(c, c->perSize.stage.dDisplay.reserve((size_t)c->width * c->height * sizeof(float4)));
+    HIP_TRY(c, launch_post_chain(c->perSize.dOutput, c->perSize.stage.dDisplay, c->width * c->height, *p, c->perContext.dHistogram, c->perContext.dExposure, c->stream));
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_post_process"); }
 
@@ -67,13 +67,12 @@ static int size_and_view_check(HrptContext* c, const std::string& w, uint32_t wi
 // Pyramids for a width x height image: kept while the size stays, re-allocated when it changes (hipFree waits for work in flight).
 static int bloom_run(HrptContext* c, float4* image, uint32_t width, uint32_t height, const HrptBloomParams& p, hipStream_t stream)
 {
-    const size_t words = bloom_pyramid_words(width, height);
-    if (words == 0) return HRPT_OK;
-    if (words != c->perContext.bloomWords) {
-        c->perContext.dBloomDown.reset(); c->perContext.dBloomUp.reset(); c->perContext.bloomWords = 0;     // both go before anything is allocated
-        HIP_TRY(c, c->perContext.dBloomDown.alloc(words * sizeof(uint32_t)));
-        HIP_TRY(c, c->perContext.dBloomUp.alloc(words * sizeof(uint32_t)));
-        c->perContext.bloomWords = words;
+    const size_t bytes = bloom_pyramid_words(width, height) * sizeof(uint32_t);
+    if (bytes == 0) return HRPT_OK;
+    if (bytes != c->perContext.dBloomDown.bytes() || bytes != c->perContext.dBloomUp.bytes()) {
+        c->perContext.dBloomDown.reset(); c->perContext.dBloomUp.reset();     // both go before anything is allocated
+        HIP_TRY(c, c->perContext.dBloomDown.alloc(bytes));
+        HIP_TRY(c, c->perContext.dBloomUp.alloc(bytes));
     }
     HIP_TRY(c, launch_bloom(image, width, height, p, c->perContext.dBloomDown, c->perContext.dBloomUp, c->bloomTailTexels, stream));
     return HRPT_OK;
@@ -158,25 +157,24 @@ try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!view || !prevView || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: null argument");
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: hrpt_resize not called");
-    if (!c->perSize.dMotion || !c->perSize.dGBuffer[HRPT_GB_DEPTH] || !c->perSize.dGBuffer[HRPT_GB_NORMAL])
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_temporal_accumulate: the motion, depth or normal plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH | NORMAL fills them)");
+    HRPT_TRY(planes_requested(c, "hrpt_temporal_accumulate", 1u << HRPT_GB_DEPTH | 1u << HRPT_GB_NORMAL, true));
     HIP_TRY(c, hipSetDevice(c->device));
     HRPT_TRY(temporal_args_check(c, "hrpt_temporal_accumulate", c->width, c->height, *view, *p));      // before anything is allocated
-    const bool fresh = !c->perSize.dTemporal[0];
-    const int next = fresh ? 0 : 1 - c->temporalCur;
+    PerSizeImages& ps = c->perSize;
+    const bool fresh = !ps.dTemporal[0];
+    const int next = fresh ? 0 : 1 - ps.temporalCur;
     if (fresh) {
-        for (DeviceBuffer<float4>& image : c->perSize.dTemporal) HRPT_TRY(realloc_image(c, image, (size_t)c->width * c->height * sizeof(float4)));
-        c->temporalValid = false;
+        for (DeviceBuffer<float4>& image : ps.dTemporal) HRPT_TRY(realloc_image(c, image, (size_t)c->width * c->height * sizeof(float4)));
+        ps.temporalValid = false;
     }
     HrptTemporalImages img{};
-    img.color = reinterpret_cast<const float*>(c->perSize.dOutput.get()); img.colorOut = reinterpret_cast<float*>(c->perSize.dOutput.get());
-    img.motion = reinterpret_cast<const float*>(c->perSize.dMotion.get());
-    img.depth = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get()); img.normal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_NORMAL].get());
-    const bool useHistory = c->temporalValid && (p->flags & HRPT_TEMPORAL_RESET) == 0;
-    img.historyIn = useHistory ? reinterpret_cast<const float*>(c->perSize.dTemporal[1 - next].get()) : nullptr;
-    img.historyOut = reinterpret_cast<float*>(c->perSize.dTemporal[next].get());
+    img.color = floats(ps.dOutput); img.colorOut = floats(ps.dOutput); img.motion = floats(ps.dMotion);
+    img.depth = floats(ps.dGBuffer[HRPT_GB_DEPTH]); img.normal = floats(ps.dGBuffer[HRPT_GB_NORMAL]);
+    const bool useHistory = ps.temporalValid && (p->flags & HRPT_TEMPORAL_RESET) == 0;
+    img.historyIn = useHistory ? floats(ps.dTemporal[1 - next]) : nullptr;
+    img.historyOut = floats(ps.dTemporal[next]);
     HIP_TRY(c, launch_temporal(img, c->width, c->height, *view, *prevView, *p, c->stream));
-    c->temporalCur = next; c->temporalValid = true;
+    ps.temporalCur = next; ps.temporalValid = true;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_temporal_accumulate"); }
 
@@ -184,14 +182,14 @@ int hrpt_read_temporal_history(HrptContext* c, float* dst, size_t bytes)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!c->perSize.dTemporal[0]) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_temporal_history: the history was never requested from hrpt_temporal_accumulate");
-    return read_image(c, c->perSize.dTemporal[c->temporalCur], dst, bytes, "hrpt_read_temporal_history");
+    return read_image(c, c->perSize.dTemporal[c->perSize.temporalCur], dst, bytes, "hrpt_read_temporal_history");
 } catch (...) { return caught(c, "hrpt_read_temporal_history"); }
 
 int hrpt_get_temporal_history_device(HrptContext* c, void** devicePtr)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_temporal_history_device: null out");
-    *devicePtr = c->perSize.dTemporal[0] ? c->perSize.dTemporal[c->temporalCur] : nullptr;
+    *devicePtr = c->perSize.dTemporal[0] ? c->perSize.dTemporal[c->perSize.temporalCur] : nullptr;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_get_temporal_history_device"); }
 
@@ -245,29 +243,27 @@ try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!view || !prevView || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upscale: null argument");
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upscale: hrpt_resize not called");
-    if (!c->perSize.dMotion || !c->perSize.dGBuffer[HRPT_GB_DEPTH])
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_upscale: the motion or depth plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH fills them)");
+    HRPT_TRY(planes_requested(c, "hrpt_upscale", 1u << HRPT_GB_DEPTH, true));
     HIP_TRY(c, hipSetDevice(c->device));
     HRPT_TRY(upscale_args_check(c, "hrpt_upscale", c->width, c->height, displayWidth, displayHeight, *view, *p));      // before anything is allocated
-    if (!c->perSize.dUpscaled || displayWidth != c->upscaleWidth || displayHeight != c->upscaleHeight) {
-        for (DeviceBuffer<float4>& image : c->perSize.dUpscaleHistory) image.reset();           // all three go before anything is allocated
-        c->perSize.dUpscaled.reset(); c->upscaleValid = false; c->upscaleCur = 0; c->upscaleWidth = c->upscaleHeight = 0;
+    StageImages& st = c->perSize.stage;
+    if (!st.dUpscaled || displayWidth != st.upscaleWidth || displayHeight != st.upscaleHeight) {
+        for (DeviceBuffer<float4>& image : st.dUpscaleHistory) image.reset();           // all three go before anything is allocated
+        st.dUpscaled.reset(); st.upscaleValid = false; st.upscaleCur = 0; st.upscaleWidth = st.upscaleHeight = 0;
         const size_t bytes = (size_t)displayWidth * displayHeight * sizeof(float4);
-        for (DeviceBuffer<float4>& image : c->perSize.dUpscaleHistory) HRPT_TRY(realloc_image(c, image, bytes));
-        HRPT_TRY(realloc_image(c, c->perSize.dUpscaled, bytes));
-        c->upscaleWidth = displayWidth; c->upscaleHeight = displayHeight;
+        for (DeviceBuffer<float4>& image : st.dUpscaleHistory) HRPT_TRY(realloc_image(c, image, bytes));
+        HRPT_TRY(realloc_image(c, st.dUpscaled, bytes));
+        st.upscaleWidth = displayWidth; st.upscaleHeight = displayHeight;
     }
-    const int next = c->upscaleValid ? 1 - c->upscaleCur : 0;
+    const int next = st.upscaleValid ? 1 - st.upscaleCur : 0;
     HrptUpscaleImages img{};
-    img.color = reinterpret_cast<const float*>(c->perSize.dOutput.get());
-    img.depth = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get());
-    img.motion = reinterpret_cast<const float*>(c->perSize.dMotion.get());
-    const bool useHistory = c->upscaleValid && (p->flags & HRPT_UPSCALE_RESET) == 0;
-    img.historyIn = useHistory ? reinterpret_cast<const float*>(c->perSize.dUpscaleHistory[1 - next].get()) : nullptr;
-    img.historyOut = reinterpret_cast<float*>(c->perSize.dUpscaleHistory[next].get());
-    img.colorOut = reinterpret_cast<float*>(c->perSize.dUpscaled.get());
+    img.color = floats(c->perSize.dOutput); img.depth = floats(c->perSize.dGBuffer[HRPT_GB_DEPTH]); img.motion = floats(c->perSize.dMotion);
+    const bool useHistory = st.upscaleValid && (p->flags & HRPT_UPSCALE_RESET) == 0;
+    img.historyIn = useHistory ? floats(st.dUpscaleHistory[1 - next]) : nullptr;
+    img.historyOut = floats(st.dUpscaleHistory[next]);
+    img.colorOut = floats(st.dUpscaled);
     HIP_TRY(c, launch_upscale(img, c->width, c->height, displayWidth, displayHeight, *view, *prevView, *p, c->upscaleStaged, c->stream));
-    c->upscaleCur = next; c->upscaleValid = true;
+    st.upscaleCur = next; st.upscaleValid = true;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_upscale"); }
 
@@ -275,7 +271,7 @@ try {
 static int read_upscale_image(HrptContext* c, const float4* src, float* dst, size_t bytes, const char* what)
 {
     if (!src) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": no upscaled image (hrpt_upscale writes it; hrpt_resize drops it)");
-    if (!dst || bytes != (size_t)c->upscaleWidth * c->upscaleHeight * 16) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": bad buffer size");
+    if (!dst || bytes != (size_t)c->perSize.stage.upscaleWidth * c->perSize.stage.upscaleHeight * 16) return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string(what) + ": bad buffer size");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -285,20 +281,20 @@ static int read_upscale_image(HrptContext* c, const float4* src, float* dst, siz
 int hrpt_read_upscaled(HrptContext* c, float* dst, size_t bytes)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    return read_upscale_image(c, c->perSize.dUpscaled, dst, bytes, "hrpt_read_upscaled");
+    return read_upscale_image(c, c->perSize.stage.dUpscaled, dst, bytes, "hrpt_read_upscaled");
 } catch (...) { return caught(c, "hrpt_read_upscaled"); }
 
 int hrpt_read_upscale_history(HrptContext* c, float* dst, size_t bytes)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    return read_upscale_image(c, c->perSize.dUpscaled ? c->perSize.dUpscaleHistory[c->upscaleCur].get() : nullptr, dst, bytes, "hrpt_read_upscale_history");
+    return read_upscale_image(c, c->perSize.stage.dUpscaled ? c->perSize.stage.dUpscaleHistory[c->perSize.stage.upscaleCur].get() : nullptr, dst, bytes, "hrpt_read_upscale_history");
 } catch (...) { return caught(c, "hrpt_read_upscale_history"); }
 
 int hrpt_get_upscaled_device(HrptContext* c, void** devicePtr)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_upscaled_device: null out");
-    *devicePtr = c->perSize.dUpscaled;
+    *devicePtr = c->perSize.stage.dUpscaled;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_get_upscaled_device"); }
 
@@ -381,35 +377,32 @@ try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: null argument");
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: hrpt_resize not called");
-    if (!c->perSize.dTemporal[0] || !c->temporalValid)
+    PerSizeImages& ps = c->perSize;
+    if (!ps.dTemporal[0] || !ps.temporalValid)
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: no temporal history at the current size (hrpt_temporal_accumulate writes the image this stage filters)");
-    if (!c->perSize.dGBuffer[HRPT_GB_DEPTH] || !c->perSize.dGBuffer[HRPT_GB_NORMAL] || !c->perSize.dGBuffer[HRPT_GB_GEO_NORMAL])
-        return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_denoise: the depth, normal or geo-normal plane was never requested (hrpt_render_motion_vectors with planeMask = DEPTH | NORMAL | GEO_NORMAL fills them)");
+    HRPT_TRY(planes_requested(c, "hrpt_denoise", 1u << HRPT_GB_DEPTH | 1u << HRPT_GB_NORMAL | 1u << HRPT_GB_GEO_NORMAL, false));
     HIP_TRY(c, hipSetDevice(c->device));
     HRPT_TRY(denoise_args_check(c, "hrpt_denoise", c->width, c->height, *view, *p, false));
     HRPT_TRY(denoise_tile(c));
     HrptDenoiseImages img{};
-    img.input = reinterpret_cast<const float*>(c->perSize.dTemporal[c->temporalCur].get());
-    img.depth = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get()); img.normal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_NORMAL].get());
-    img.geoNormal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_GEO_NORMAL].get());
+    img.input = floats(ps.dTemporal[ps.temporalCur]);
+    img.depth = floats(ps.dGBuffer[HRPT_GB_DEPTH]); img.normal = floats(ps.dGBuffer[HRPT_GB_NORMAL]); img.geoNormal = floats(ps.dGBuffer[HRPT_GB_GEO_NORMAL]);
     img.noise = c->perContext.dDenoiseTile;
     const bool outputOnly = (p->flags & HRPT_DENOISE_OUTPUT_ONLY) != 0;
     if (outputOnly) {
-        const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
-        for (uint32_t k = 0; k < (p->iterations > 1u ? 2u : 1u); ++k)
-            if (!c->perSize.dDenoiseScratch[k]) HIP_TRY(c, c->perSize.dDenoiseScratch[k].alloc(bytes));
+        for (uint32_t k = 0; k < (p->iterations > 1u ? 2u : 1u); ++k) HIP_TRY(c, ps.stage.dDenoiseScratch[k].reserve((size_t)c->width * c->height * sizeof(float4)));
     }
-    int cur = c->temporalCur;
+    int cur = ps.temporalCur;
     for (uint32_t i = 0; i < p->iterations; ++i) {
         // default: the two history images are the ping-pong pair (the stale one is free after the temporal call); the image a pass wrote is the history
-        float4* dst = outputOnly ? c->perSize.dDenoiseScratch[i & 1u] : c->perSize.dTemporal[1 - cur];
-        img.output = reinterpret_cast<float*>(dst);
+        DeviceBuffer<float4>& dst = outputOnly ? ps.stage.dDenoiseScratch[i & 1u] : ps.dTemporal[1 - cur];
+        img.output = floats(dst);
         const bool last = i + 1u == p->iterations;
-        img.color = last ? reinterpret_cast<const float*>(c->perSize.dOutput.get()) : nullptr;
-        img.colorOut = last ? reinterpret_cast<float*>(c->perSize.dOutput.get()) : nullptr;
+        img.color = last ? floats(ps.dOutput) : nullptr;
+        img.colorOut = last ? floats(ps.dOutput) : nullptr;
         HIP_TRY(c, launch_denoise(img, c->width, c->height, *view, *p, p->radius * (float)(1u << i), p->frame * p->iterations + i, c->stream));
-        img.input = reinterpret_cast<const float*>(dst);
-        if (!outputOnly) { cur = 1 - cur; c->temporalCur = cur; }
+        img.input = floats(dst);
+        if (!outputOnly) { cur = 1 - cur; ps.temporalCur = cur; }
     }
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_denoise"); }
@@ -487,20 +480,16 @@ try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!view || !p) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_demodulate: null argument");
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_demodulate: hrpt_resize not called");
-    static const struct { int plane; const char* name; } needed[5] = { { HRPT_GB_ALBEDO, "HRPT_GB_ALBEDO" }, { HRPT_GB_NORMAL, "HRPT_GB_NORMAL" },
-        { HRPT_GB_GEO_NORMAL, "HRPT_GB_GEO_NORMAL" }, { HRPT_GB_EMISSIVE, "HRPT_GB_EMISSIVE" }, { HRPT_GB_DEPTH, "HRPT_GB_DEPTH" } };
-    for (const auto& n : needed)
-        if (!c->perSize.dGBuffer[n.plane])
-            return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_demodulate: the plane ") + n.name + " was never requested (hrpt_render_motion_vectors or hrpt_render_gbuffer with planeMask = ALBEDO | NORMAL | GEO_NORMAL | EMISSIVE | DEPTH fills them)");
+    HRPT_TRY(planes_requested(c, "hrpt_demodulate", 1u << HRPT_GB_ALBEDO | 1u << HRPT_GB_NORMAL | 1u << HRPT_GB_GEO_NORMAL | 1u << HRPT_GB_EMISSIVE | 1u << HRPT_GB_DEPTH, false));
     HIP_TRY(c, hipSetDevice(c->device));
     HRPT_TRY(demodulate_args_check(c, "hrpt_demodulate", c->width, c->height, *view, *p));      // before anything is allocated
-    if (!c->perSize.dModulation) HIP_TRY(c, c->perSize.dModulation.alloc((size_t)c->width * c->height * sizeof(float4)));
+    PerSizeImages& ps = c->perSize;
+    HIP_TRY(c, ps.stage.dModulation.reserve((size_t)c->width * c->height * sizeof(float4)));
     HrptDemodulateImages img{};
-    img.color = reinterpret_cast<const float*>(c->perSize.dOutput.get()); img.colorOut = reinterpret_cast<float*>(c->perSize.dOutput.get());
-    img.albedo = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_ALBEDO].get()); img.normal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_NORMAL].get());
-    img.geoNormal = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_GEO_NORMAL].get()); img.depth = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get());
-    img.emissive = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_EMISSIVE].get());
-    img.modulationOut = reinterpret_cast<float*>(c->perSize.dModulation.get());
+    img.color = floats(ps.dOutput); img.colorOut = floats(ps.dOutput);
+    img.albedo = floats(ps.dGBuffer[HRPT_GB_ALBEDO]); img.normal = floats(ps.dGBuffer[HRPT_GB_NORMAL]); img.geoNormal = floats(ps.dGBuffer[HRPT_GB_GEO_NORMAL]);
+    img.depth = floats(ps.dGBuffer[HRPT_GB_DEPTH]); img.emissive = floats(ps.dGBuffer[HRPT_GB_EMISSIVE]);
+    img.modulationOut = floats(ps.stage.dModulation);
     HIP_TRY(c, launch_demodulate(img, c->width, c->height, *view, *p, c->stream));
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_demodulate"); }
@@ -509,13 +498,13 @@ int hrpt_compose(HrptContext* c)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_compose: hrpt_resize not called");
-    if (!c->perSize.dModulation)
+    if (!c->perSize.stage.dModulation)
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_compose: no modulation image at the current size (hrpt_demodulate writes the factor this stage multiplies back in)");
     HIP_TRY(c, hipSetDevice(c->device));
     HrptComposeImages img{};
-    img.color = reinterpret_cast<const float*>(c->perSize.dOutput.get()); img.colorOut = reinterpret_cast<float*>(c->perSize.dOutput.get());
-    img.modulation = reinterpret_cast<const float*>(c->perSize.dModulation.get());
-    img.emissive = reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_EMISSIVE].get());      // set: hrpt_demodulate required it, and a resize drops the modulation image
+    img.color = floats(c->perSize.dOutput); img.colorOut = floats(c->perSize.dOutput);
+    img.modulation = floats(c->perSize.stage.dModulation);
+    img.emissive = floats(c->perSize.dGBuffer[HRPT_GB_EMISSIVE]);      // set: hrpt_demodulate required it, and a resize drops the modulation image
     HIP_TRY(c, launch_compose(img, c->width, c->height, c->stream));
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_compose"); }
@@ -523,15 +512,15 @@ try {
 int hrpt_read_modulation(HrptContext* c, float* dst, size_t bytes)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    if (!c->perSize.dModulation) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_modulation: no modulation image at the current size (hrpt_demodulate writes it)");
-    return read_image(c, c->perSize.dModulation, dst, bytes, "hrpt_read_modulation");
+    if (!c->perSize.stage.dModulation) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_modulation: no modulation image at the current size (hrpt_demodulate writes it)");
+    return read_image(c, c->perSize.stage.dModulation, dst, bytes, "hrpt_read_modulation");
 } catch (...) { return caught(c, "hrpt_read_modulation"); }
 
 int hrpt_get_modulation_device(HrptContext* c, void** devicePtr)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_modulation_device: null out");
-    *devicePtr = c->perSize.dModulation;
+    *devicePtr = c->perSize.stage.dModulation;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_get_modulation_device"); }
 

@@ -104,33 +104,30 @@ try {
     HrptContext* c = p->ctx;
     if (!view) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_probes_shade_gbuffer: null view");
     if (!c->perSize.dOutput) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_probes_shade_gbuffer: hrpt_resize not called");
-    static const struct { int plane; const char* name; } needed[2] = { { HRPT_GB_NORMAL, "HRPT_GB_NORMAL" }, { HRPT_GB_DEPTH, "HRPT_GB_DEPTH" } };
-    for (const auto& n : needed)
-        if (!c->perSize.dGBuffer[n.plane])
-            return fail(c, HRPT_ERR_INVALID_ARGUMENT, std::string("hrpt_probes_shade_gbuffer: the plane ") + n.name + " was never requested (hrpt_render_gbuffer or hrpt_render_motion_vectors with planeMask = NORMAL | DEPTH fills them)");
+    HRPT_TRY(planes_requested(c, "hrpt_probes_shade_gbuffer", 1u << HRPT_GB_NORMAL | 1u << HRPT_GB_DEPTH, false));
     if (view->m_ViewportSize[0] != (float)c->width || view->m_ViewportSize[1] != (float)c->height)
         return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_probes_shade_gbuffer: view->m_ViewportSize does not match the image size");
     if (!(intensity >= 0.0f && intensity <= 3.402823466e38f)) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_probes_shade_gbuffer: intensity must be finite and >= 0");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->perSize.dProbeIrradiance) HRPT_TRY(realloc_image(c, c->perSize.dProbeIrradiance, (size_t)c->width * c->height * sizeof(float4)));
-    HIP_TRY(c, launch_probes_shade_gbuffer(p->volume, *view, c->width, c->height, intensity, p->dIrradiance, p->dDistance,
-                                           reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_NORMAL].get()),
-                                           reinterpret_cast<const float*>(c->perSize.dGBuffer[HRPT_GB_DEPTH].get()), c->perSize.dProbeIrradiance, c->stream));
+    PerSizeImages& ps = c->perSize;
+    if (!ps.stage.dProbeIrradiance) HRPT_TRY(realloc_image(c, ps.stage.dProbeIrradiance, (size_t)c->width * c->height * sizeof(float4)));
+    HIP_TRY(c, launch_probes_shade_gbuffer(p->volume, *view, c->width, c->height, intensity, p->dIrradiance, p->dDistance, floats(ps.dGBuffer[HRPT_GB_NORMAL]),
+                                           floats(ps.dGBuffer[HRPT_GB_DEPTH]), ps.stage.dProbeIrradiance, c->stream));
     return HRPT_OK;
 } catch (...) { return caught(p ? p->ctx : nullptr, "hrpt_probes_shade_gbuffer"); }
 
 int hrpt_read_probe_irradiance(HrptContext* c, float* dst, size_t bytes)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
-    if (!c->perSize.dProbeIrradiance) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_probe_irradiance: no probe irradiance plane at the current size (hrpt_probes_shade_gbuffer writes it)");
-    return read_image(c, c->perSize.dProbeIrradiance, dst, bytes, "hrpt_read_probe_irradiance");
+    if (!c->perSize.stage.dProbeIrradiance) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_probe_irradiance: no probe irradiance plane at the current size (hrpt_probes_shade_gbuffer writes it)");
+    return read_image(c, c->perSize.stage.dProbeIrradiance, dst, bytes, "hrpt_read_probe_irradiance");
 } catch (...) { return caught(c, "hrpt_read_probe_irradiance"); }
 
 int hrpt_get_probe_irradiance_device(HrptContext* c, void** devicePtr)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!devicePtr) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_get_probe_irradiance_device: null out");
-    *devicePtr = c->perSize.dProbeIrradiance;
+    *devicePtr = c->perSize.stage.dProbeIrradiance;
     return HRPT_OK;
 } catch (...) { return caught(c, "hrpt_get_probe_irradiance_device"); }
 

@@ -94,11 +94,7 @@ static int refresh_motion_tables(HrptContext* c)
         r.firstIndex = c->keptMeshData[in.m_MeshDataIndex].m_IndexOffsets[0];         // LOD 0 (PathTracer.hlsl:102-103)
         r.pad[0] = r.pad[1] = r.pad[2] = 0;
     }
-    if (records.size() > c->perScene.motionInstCapacity || !c->perScene.dMotionInst) {
-        c->perScene.motionInstCapacity = 0;
-        HIP_TRY(c, c->perScene.dMotionInst.alloc(records.empty() ? 64 : records.size() * sizeof(MotionInst)));
-        c->perScene.motionInstCapacity = records.size();
-    }
+    HIP_TRY(c, c->perScene.dMotionInst.reserve(records.empty() ? 64 : records.size() * sizeof(MotionInst)));
     if (!records.empty()) HIP_TRY(c, hipMemcpyAsync(c->perScene.dMotionInst, records.data(), records.size() * sizeof(MotionInst), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));        // the staging vectors die at scope exit
     c->perScene.motionInstStale = c->perScene.motionGeometryStale = c->perScene.motionPositionsStale = false;
@@ -158,7 +154,7 @@ try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;
     if (!c->perSize.dMotion) return fail(c, HRPT_ERR_INVALID_ARGUMENT, "hrpt_read_motion_vectors: the motion plane was never requested from hrpt_render_motion_vectors");
     return read_image(c, c->perSize.dMotion, dst, bytes, "hrpt_read_motion_vectors");
-} catch (...) { return caught(c, "hrpt_render_gbuffer"); }
+} catch (...) { return caught(c, "hrpt_read_motion_vectors"); }
 int hrpt_get_motion_vectors_device(HrptContext* c, void** devicePtr)
 try {
     if (!c) return HRPT_ERR_INVALID_ARGUMENT;

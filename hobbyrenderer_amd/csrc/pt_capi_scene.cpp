@@ -57,7 +57,7 @@ void capi::free_scene(HrptContext* c)
     free_acceleration(c, false);
     c->perScene = PerSceneBuffers{};        // motion tables, deform staging, skin floats, previous positions; the stale flags are set again
     c->allocations.clear();
-    c->nodesQ.reset(); c->nodesQCapacity = 0;
+    c->nodesQ.reset();
     c->keptVertices.clear(); c->keptIndices.clear(); c->keptMeshData.clear(); c->keptInstances.clear(); c->keptMaterials.clear(); c->keptLights.clear(); c->lightCapacity = 0;
     c->haveScene = false;
     ++c->instanceEpoch;
@@ -264,13 +264,12 @@ static int quantise_nodes(HrptContext* c, const HrptSceneDesc& s, SceneView& v, 
 {
     v.nodesQ = nullptr; quantised = false;
     if (!v.node4Count) return HRPT_OK;
-    if (c->nodesQCapacity <= v.node4Count) {                   // (<=: record nodesQCapacity - 1 is the accumulator below, never a node)
-        c->nodesQ.reset(); c->nodesQCapacity = 0;
-        const size_t cap = (size_t)v.node4Count + v.node4Count / 8 + 64;
+    size_t cap = c->nodesQ.bytes() / sizeof(GpuNodeQ);         // records the buffer holds
+    if (cap <= v.node4Count) {                                  // (<=: record cap - 1 is the accumulator below, never a node)
+        cap = (size_t)v.node4Count + v.node4Count / 8 + 64;
         if (c->nodesQ.alloc(cap * sizeof(GpuNodeQ)) != hipSuccess) return fail(c, HRPT_ERR_OUT_OF_MEMORY, "acceleration structure: quantised nodes");
-        c->nodesQCapacity = cap;
     }
-    double* dArea = reinterpret_cast<double*>(c->nodesQ + (c->nodesQCapacity - 1));       // the last (spare) record of the buffer: two doubles
+    double* dArea = reinterpret_cast<double*>(c->nodesQ + (cap - 1));       // the last (spare) record of the buffer: two doubles
     HIP_TRY(c, hipMemsetAsync(dArea, 0, 4 * sizeof(double), c->stream));
     HIP_TRY(c, launch_quantise_nodes(v.nodes4, v.node4Count, c->nodesQ, dArea, c->stream));
     double area[4] = { 0.0, 0.0, 0.0, 0.0 };

@@ -53,7 +53,7 @@ try {
     d->maxDepth = c->buildInfo.maxDepth; d->maxDepth4 = c->buildInfo.maxDepth4;
     d->maxDepth4Tlas = twoLevel && c->twoLevel ? c->twoLevel->maxDepth4Tlas : 0u; d->maxDepth4Blas = twoLevel && c->twoLevel ? c->twoLevel->maxDepth4Blas : 0u;
     d->sahCost = c->buildInfo.sahCost;
-    d->nodes4Capacity = twoLevel ? 0u : c->nodes4Capacity; d->nodesQCapacity = v.nodesQ ? (uint32_t)c->nodesQCapacity : 0u;
+    d->nodes4Capacity = twoLevel ? 0u : c->nodes4Capacity; d->nodesQCapacity = v.nodesQ ? (uint32_t)(c->nodesQ.bytes() / sizeof(GpuNodeQ)) : 0u;
     auto fetch = [&](void* dst, const void* src, size_t bytes) { return (dst && src && bytes) ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
     HIP_TRY(c, fetch(d->nodes, twoLevel ? nullptr : v.nodes, (size_t)d->nodeCount * sizeof(GpuNode)));
     HIP_TRY(c, fetch(d->nodes4, v.nodes4, (size_t)v.node4Count * sizeof(GpuNode4)));

@@ -21,15 +21,10 @@ enum KernelClass : int { kKernelExtend = 0, kKernelShade = 1, kKernelShadow = 2,
 
 struct WavefrontState {
     DeviceBuffer<void> pool;           // one device allocation carved into the SoA queues
-    size_t poolBytes = 0;
     DeviceBuffer<void> spill;          // traversal-stack overflow columns (only for trees deeper than the LDS stack)
-    size_t spillBytes = 0;
     DeviceBuffer<void> traceSpill;     // the same for hrpt_trace_rays batches
-    size_t traceSpillBytes = 0;
     DeviceBuffer<void> gbPool;         // queue pool of hrpt_render_gbuffer calls the render's pool is too small for (never rendered, or a smaller tile)
-    size_t gbPoolBytes = 0;
     DeviceBuffer<void> radPool;        // the same for hrpt_trace_radiance batches
-    size_t radPoolBytes = 0;
     // start/stop event pairs around every timed launch; kind[i] = its KernelClass
     std::vector<hipEvent_t> events;
     std::vector<uint8_t> kind;

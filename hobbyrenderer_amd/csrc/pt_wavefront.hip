@@ -197,22 +197,20 @@ hipError_t device_cus(WavefrontState& st, uint32_t& cus, std::string& error)
     return hipSuccess;
 }
 
-// Grows `buf` (of `have` bytes) to at least `bytes`. Work in flight on the context's streams may still use the old allocation, so both are
-// waited for before it goes. After a failure the buffer is empty and `have` 0.
-hipError_t grow_buffer(WavefrontState& st, hipStream_t stream, DeviceBuffer<void>& buf, size_t& have, size_t bytes)
+// Grows `buf` to at least `bytes`. Work in flight on the context's streams may still use the old allocation, so both are waited for before
+// it goes. After a failure the buffer is empty.
+hipError_t grow_buffer(WavefrontState& st, hipStream_t stream, DeviceBuffer<void>& buf, size_t bytes)
 {
-    if (bytes <= have) return hipSuccess;
+    if (bytes <= buf.bytes()) return hipSuccess;
     if (buf) { (void)hipStreamSynchronize(stream); if (st.auxStream) (void)hipStreamSynchronize(st.auxStream); }
-    const hipError_t e = buf.alloc(bytes);
-    have = e == hipSuccess ? bytes : 0;
-    return e;
+    return buf.alloc(bytes);
 }
 // The traversal-stack overflow columns of a render or G-buffer plan: two sets (wf_extend and wf_shadow run concurrently) of `entries` ints
 // each (threads x entries per thread; 0 = the tree fits the LDS stack). A G-buffer call sizes them as a render does: the next render keeps the buffer.
 hipError_t reserve_spill(WavefrontState& st, hipStream_t stream, size_t entries, WfArgs& a, std::string& error)
 {
     if (!entries) return hipSuccess;
-    const hipError_t e = grow_buffer(st, stream, st.spill, st.spillBytes, 2 * entries * 4);
+    const hipError_t e = grow_buffer(st, stream, st.spill, 2 * entries * 4);
     if (e != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
     a.spill[0] = static_cast<int32_t*>(st.spill.get()); a.spill[1] = a.spill[0] + entries;
     return hipSuccess;
@@ -232,7 +230,7 @@ hipError_t wavefront_trace_rays(WavefrontState& st, const SceneView& scene, cons
     a.refillMin = p.refillMin; a.nodeLoopMin = p.nodeLoopMin; a.quantised = p.v.quantised;
     if (p.spillEntries) {
         // own overflow columns (a render may be in flight on the context's buffers only in stream order, but sizes differ)
-        if ((e = grow_buffer(st, stream, st.traceSpill, st.traceSpillBytes, p.spillThreads * p.spillEntries * 4)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
+        if ((e = grow_buffer(st, stream, st.traceSpill, p.spillThreads * p.spillEntries * 4)) != hipSuccess) { error = "hipMalloc(traversal stack overflow)"; return e; }
         a.spill = static_cast<int32_t*>(st.traceSpill.get());
     }
     launch_wf_trace_rays(p.v, cus, dim3(p.grid), stream, a, shadow);
@@ -248,11 +246,7 @@ bool wavefront_supports(const SceneView& scene, const HrptPathTracerConstants& c
 
 void wavefront_release(WavefrontState& st)
 {
-    st.pool.reset(); st.poolBytes = 0;
-    st.spill.reset(); st.spillBytes = 0;
-    st.traceSpill.reset(); st.traceSpillBytes = 0;
-    st.gbPool.reset(); st.gbPoolBytes = 0;
-    st.radPool.reset(); st.radPoolBytes = 0;
+    st.pool.reset(); st.spill.reset(); st.traceSpill.reset(); st.gbPool.reset(); st.radPool.reset();
     for (auto* events : { &st.events, &st.forkEvents, &st.joinEvents }) { for (hipEvent_t e : *events) (void)hipEventDestroy(e); events->clear(); }
     st.eventsUsed = 0;
     if (st.auxStream) (void)hipStreamDestroy(st.auxStream);
@@ -393,11 +387,11 @@ hipError_t size_batch_and_pool(WavefrontState& st, const RenderPlan& plan, const
 {
     sppPerBatch = accumCount < kMaxSppPerBatch ? accumCount : kMaxSppPerBatch;
     uint64_t maxSamples = 64ull << 20;
-    if (pixelsPadded * sppPerBatch * plan.bytesPerSample > st.poolBytes) {
+    if (pixelsPadded * sppPerBatch * plan.bytesPerSample > st.pool.bytes()) {
         // the pool has to grow: keep it within half of what the device has free (other contexts -- a second frame in flight -- need theirs)
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-            const uint64_t budget = (uint64_t)(freeB + st.poolBytes) / 2;
+            const uint64_t budget = (uint64_t)(freeB + st.pool.bytes()) / 2;
             if (budget / plan.bytesPerSample < maxSamples) maxSamples = budget / plan.bytesPerSample;
         }
     }
@@ -407,7 +401,7 @@ hipError_t size_batch_and_pool(WavefrontState& st, const RenderPlan& plan, const
         const uint64_t capacity = ((pixelsPadded * sppPerBatch + kMaxSegment - 1) / kMaxSegment) * kMaxSegment;
         if (capacity >= (1ull << 31)) { error = "tile too large for one batch"; return hipErrorInvalidValue; }
         const size_t bytes = carve_pool(nullptr, a, capacity, plan.maxLights, traits, hasInstances);
-        const hipError_t e = grow_buffer(st, stream, st.pool, st.poolBytes, bytes);
+        const hipError_t e = grow_buffer(st, stream, st.pool, bytes);
         if (e == hipSuccess) { carve_pool(static_cast<char*>(st.pool.get()), a, capacity, plan.maxLights, traits, hasInstances); return hipSuccess; }
         (void)hipGetLastError();
         if (sppPerBatch == 1) {       // nothing left to halve
@@ -556,8 +550,8 @@ hipError_t wavefront_gbuffer(WavefrontState& st, const SceneView& scene, const S
     const GBufferPlan plan = plan_gbuffer(traits, tree_counts(scene), cus, st.knobs, (uint32_t)pixelsPadded);
     const size_t bytes = carve_gbuffer_pool(nullptr, a, capacity, traits.hasMedium, scene.instances != nullptr);
     char* pool = static_cast<char*>(st.pool.get());
-    if (bytes > st.poolBytes) {
-        if ((e = grow_buffer(st, stream, st.gbPool, st.gbPoolBytes, bytes)) != hipSuccess) { error = "hipMalloc(G-buffer queue pool, " + std::to_string(bytes >> 20) + " MiB)"; return e; }
+    if (bytes > st.pool.bytes()) {
+        if ((e = grow_buffer(st, stream, st.gbPool, bytes)) != hipSuccess) { error = "hipMalloc(G-buffer queue pool, " + std::to_string(bytes >> 20) + " MiB)"; return e; }
         pool = static_cast<char*>(st.gbPool.get());
     }
     carve_gbuffer_pool(pool, a, capacity, traits.hasMedium, scene.instances != nullptr);
@@ -602,14 +596,14 @@ hipError_t wavefront_radiance(WavefrontState& st, const SceneView& scene, const 
     uint64_t batchRays = radiance_batch_rays(count, plan, 0, st.knobs);
     size_t bytes = carve(nullptr, radiance_capacity(batchRays));
     char* pool = static_cast<char*>(st.pool.get());
-    if (bytes > st.poolBytes) {
-        if (bytes > st.radPoolBytes) {     // the pool has to grow: within half of what the device has free, as a render's
+    if (bytes > st.pool.bytes()) {
+        if (bytes > st.radPool.bytes()) {     // the pool has to grow: within half of what the device has free, as a render's
             size_t freeB = 0, totalB = 0;
-            if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) batchRays = radiance_batch_rays(count, plan, (uint64_t)(freeB + st.radPoolBytes) / 2, st.knobs);
+            if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) batchRays = radiance_batch_rays(count, plan, (uint64_t)(freeB + st.radPool.bytes()) / 2, st.knobs);
         }
         for (;;) {
             bytes = carve(nullptr, radiance_capacity(batchRays));
-            if ((e = grow_buffer(st, stream, st.radPool, st.radPoolBytes, bytes)) == hipSuccess) break;
+            if ((e = grow_buffer(st, stream, st.radPool, bytes)) == hipSuccess) break;
             (void)hipGetLastError();
             if (batchRays <= kMaxSegment) { error = "hipMalloc(radiance queue pool, " + std::to_string(bytes >> 20) + " MiB)"; return e; }
             batchRays = (batchRays + 1) / 2;
