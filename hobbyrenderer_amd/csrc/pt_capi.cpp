@@ -81,6 +81,7 @@ try {
     if (const char* e = getenv("HRPT_RADIANCE_BATCH")) c->wf.knobs.radianceBatch = (uint32_t)atoi(e);
     if (const char* e = getenv("HRPT_BLOOM_FUSED_TAIL")) { const int v = atoi(e); c->bloomTailTexels = v == 1 ? 8192u : (v > 0 ? (uint32_t)v : 0u); }
     if (const char* e = getenv("HRPT_UPSCALE_STAGED")) c->upscaleStaged = atoi(e) != 0;
+    if (const char* e = getenv("HRPT_RESTIR_GLOBAL_LIGHTS")) c->restirGlobalLights = atoi(e) != 0;
     if (const char* e = getenv("HRPT_DEFERRED_LIGHT_BATCH")) { const int v = atoi(e); c->deferredLightBatch = (v >= 1 && v <= 16) ? (uint32_t)v : 0u; }
     *out = c;
     return HRPT_OK;

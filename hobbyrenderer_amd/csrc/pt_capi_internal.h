@@ -72,6 +72,12 @@ struct StageImages {
     // traced indirect lighting (hrpt_indirect_lighting): the two resolved planes ([0] diffuse, [1] specular) and the ray and radiance records of one call
     DeviceBuffer<float4> dIndirect[2];
     DeviceBuffer<HrptRay> dIndirectRays; DeviceBuffer<float4> dIndirectRadiance;
+    // resampled direct lighting (hrpt_restir_lighting): the ping-pong history (final reservoirs and their keys; [restirCur] is what the last
+    // call wrote, read only while restirValid), the plane between the temporal and the spatial pass, and the ray and hit records of one trace
+    DeviceBuffer<HrptRestirReservoir> dRestirReservoirs[2], dRestirScratch;
+    DeviceBuffer<float4> dRestirKeys[2];
+    DeviceBuffer<HrptRay> dRestirRays; DeviceBuffer<HrptRayHit> dRestirHits;
+    int restirCur = 0; bool restirValid = false;
 };
 
 // Images of width * height float4. The members named here are the ones hrpt_resize makes again at the new size, zeroed and without
@@ -119,7 +125,8 @@ struct Context {
     PerContextBuffers perContext;
     uint32_t bloomTailTexels = 0;            // HRPT_BLOOM_FUSED_TAIL: levels of at most this many texels run in one workgroup's LDS (0 = one kernel per pass, the measured-faster default)
     uint32_t deferredLightBatch = 0;         // HRPT_DEFERRED_LIGHT_BATCH: lights per pass of hrpt_deferred_lighting, 1..16 (0 = min(m_LightCount, 4))
-    bool upscaleStaged = false;             // HRPT_UPSCALE_STAGED: the upscale kernel serves its current-frame taps from an LDS-staged window (false = global gathers, the measured-faster default)
+    bool restirGlobalLights = false;        // HRPT_RESTIR_GLOBAL_LIGHTS: restir_initial gathers its candidates' light records from global memory whatever the count (false = from LDS up to HRPT_RESTIR_LDS_MAX_LIGHTS; same bits)
+    bool upscaleStaged = false;            // HRPT_UPSCALE_STAGED: the upscale kernel serves its current-frame taps from an LDS-staged window (false = global gathers, the measured-faster default)
     hipEvent_t evStart = nullptr, evStop = nullptr;
     bool timed = false;
     WavefrontState wf;

@@ -100,7 +100,7 @@ HRT_FN T4 pixel(const Args& a, const float* input, const float* depth, const flo
 
     const T3 centerWorldPos = recon(a.view, u, v, D.y);
     const float dist = length3(sub(centerWorldPos, t3(a.view.cam[0], a.view.cam[1], a.view.cam[2])));
-    const float roughnessRadius = lerp(hrt_sqrt(rough), 1.0f, 0.5f * (1.0f - metal));
+    const float roughnessRadius = img::lerp(hrt_sqrt(rough), 1.0f, 0.5f * (1.0f - metal));
 
     const T2 random = sample_noise(noise, (uint32_t)px, (uint32_t)py, a.frame);          // .x = random.r, .y = random.a
 
@@ -128,10 +128,10 @@ HRT_FN T4 pixel(const Args& a, const float* input, const float* depth, const flo
         const float normalDiff = 1.0f - hrt_max(dot3(N, t3(nN.x, nN.y, nN.z)), 0.0f);
         const float depthDiff = 10.0f * hrt_abs(dot3(sub(centerWorldPos, nWorldPos), N));        // plane distance
         const float roughnessDiff = hrt_abs(rough - nN.w);
-        const float lumaDiff = lerp(hrt_abs(centerLum - nLum), 0.0f, w);
+        const float lumaDiff = img::lerp(hrt_abs(centerLum - nLum), 0.0f, w);
 
         const float wBasic = hrt_exp(((-normalDiff * a.normalPhi) - depthDiff * a.depthPhi) - roughnessDiff * a.roughnessPhi);
-        const float wBasicD = lerp(wBasic, hrt_exp(-normalDiff * kYoungNormalPhi), w);
+        const float wBasicD = img::lerp(wBasic, hrt_exp(-normalDiff * kYoungNormalPhi), w);
         const float wDiff = hrt_min(w * hrt_pow(wBasicD * hrt_exp(-lumaDiff * a.lumaPhi), a.phi / w), 1.0f);
 
         sum = t3(sum.x + wDiff * nC.x, sum.y + wDiff * nC.y, sum.z + wDiff * nC.z);

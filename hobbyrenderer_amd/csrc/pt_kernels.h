@@ -186,6 +186,31 @@ void indirect_resolve_host(const HrptIndirectImages& images, uint32_t width, uin
                            const float* radiance4, int nthreads);
 void indirect_compose_host(const HrptIndirectImages& images, uint32_t width, uint32_t height, const HrptIndirectParams& params, int nthreads);
 
+// Resampled direct lighting (pt_restir.hip; arithmetic in pt_restir.h): the four passes, each over the planes of `images` and the device
+// arrays named after what they hold. initial writes images.reservoirOut (raysOut null = no record); temporal reads `initial`, its hit
+// records (null = visibility 1) and, with `history`, images.reservoirIn / keyIn / motion, and writes images.reservoirOut; spatial reads
+// `temporal` and writes images.reservoirOut, images.keyOut and the final ray records (raysOut null = none); shade reads `final` and its hit
+// records (null = visibility 1) and writes images.colorOut. `lds`: initial stages the light list in LDS when it fits. No output may alias an
+// input of the same pass. restir_*_host (pt_restir_host.cpp): the same arithmetic on host threads, atmosphere terms and visibilities as images.
+namespace restir { struct Args; }
+bool restir_params_valid(const HrptRestirParams& params);
+hipError_t launch_restir_initial(const SceneView& scene, const restir::Args& args, const HrptGPULight* lights, const HrptRestirImages& images, HrptRay* raysOut, bool lds,
+                                 hipStream_t stream);
+hipError_t launch_restir_temporal(const SceneView& scene, const restir::Args& args, const HrptGPULight* lights, const HrptRestirImages& images,
+                                  const HrptRestirReservoir* initial, const HrptRayHit* initialHits, bool history, hipStream_t stream);
+hipError_t launch_restir_spatial(const SceneView& scene, const restir::Args& args, const HrptGPULight* lights, const HrptRestirImages& images,
+                                 const HrptRestirReservoir* temporal, HrptRay* raysOut, hipStream_t stream);
+hipError_t launch_restir_shade(const SceneView& scene, const restir::Args& args, const HrptGPULight* lights, const HrptRestirImages& images,
+                               const HrptRestirReservoir* final, const HrptRayHit* hits, hipStream_t stream);
+void restir_initial_host(const HrptRestirImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptGPULight* lights,
+                         const HrptRestirParams& params, const float* sunRadiance, HrptRay* raysOut, int nthreads);
+void restir_temporal_host(const HrptRestirImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptGPULight* lights,
+                          const HrptRestirParams& params, const float* sunRadiance, const HrptRestirReservoir* initial, const float* initialVisibility, int nthreads);
+void restir_spatial_host(const HrptRestirImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptGPULight* lights,
+                         const HrptRestirParams& params, const float* sunRadiance, const HrptRestirReservoir* temporal, HrptRay* raysOut, int nthreads);
+void restir_shade_host(const HrptRestirImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptGPULight* lights,
+                       const HrptRestirParams& params, const float* sunRadiance, const float* sky, const HrptRestirReservoir* final, const float* visibility, int nthreads);
+
 // Vertex quantiser (pt_deform.hip; arithmetic in pt_deform.h): out[i] = the 24-byte scene-format record of the float vertex in[i], both in
 // device memory (in 16-byte aligned); *flag (device, may be null) is set to 1 when a position is not finite. quantize_vertices_host
 // (pt_deform_host.cpp): the same arithmetic on host threads; returns whether every position is finite.

@@ -71,7 +71,7 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
-_COUNT_WORDS = {2: "two", 4: "four", 5: "five"}
+_COUNT_WORDS = {1: "one", 2: "two", 4: "four", 5: "five"}
 
 
 def _same_shape_images(name, required, **optional):

@@ -310,6 +310,32 @@ class IndirectImages(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "geoNormal", "depth", "diffuse", "specular", "colorInOut")]
 
 
+# resampled direct lighting (hrpt_restir_lighting)
+RESTIR_SHADOWS, RESTIR_SKY, RESTIR_TEMPORAL, RESTIR_SPATIAL, RESTIR_INITIAL_VISIBILITY, RESTIR_RESET = 1, 2, 4, 8, 16, 32
+RESTIR_EMPTY = 0xFFFFFFFF          # HrptRestirReservoir.light of an empty reservoir
+RESTIR_LDS_MAX_LIGHTS = 512
+RestirReservoir = np.dtype([("light", u32), ("W", f32), ("M", f32), ("pHat", f32)])       # HrptRestirReservoir, 16 B
+
+
+class RestirParams(C.Structure):
+    """HrptRestirParams. flags: RESTIR_SHADOWS traces the chosen light's shadow ray, RESTIR_SKY takes the sky at misses and the sun's radiance
+    from the atmosphere, RESTIR_TEMPORAL / RESTIR_SPATIAL switch the two reuse passes on, RESTIR_INITIAL_VISIBILITY adds a shadow ray for the
+    initial sample (biased), RESTIR_RESET drops the history. The defaults are the documented ones."""
+    _fields_ = [("flags", C.c_uint32), ("frameSeed", C.c_uint32), ("candidates", C.c_uint32), ("spatialSamples", C.c_uint32), ("spatialRadius", C.c_float),
+                ("maxHistory", C.c_float), ("depthThreshold", C.c_float), ("normalThreshold", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, flags=RESTIR_SHADOWS | RESTIR_SKY | RESTIR_TEMPORAL | RESTIR_SPATIAL, frameSeed=0, candidates=8, spatialSamples=1, spatialRadius=32.0,
+                 maxHistory=20.0, depthThreshold=0.1, normalThreshold=0.5):
+        super().__init__(flags, frameSeed, candidates, spatialSamples, spatialRadius, maxHistory, depthThreshold, normalThreshold)
+
+
+class RestirImages(C.Structure):
+    """HrptRestirImages: host or device addresses. The five planes and motion are width x height float4 images (motion may be None without
+    RESTIR_TEMPORAL); reservoirIn / keyIn are the history (both None = none); reservoirOut (RestirReservoir records), keyOut and colorOut are
+    written."""
+    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "geoNormal", "emissive", "depth", "motion", "reservoirIn", "keyIn", "reservoirOut", "keyOut", "colorOut")]
+
+
 class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B
     _fields_ = [("requestedBuilder", C.c_uint32), ("usedBuilder", C.c_uint32), ("buildMs", C.c_float), ("deviceBuildMs", C.c_float),
                 ("triangleCount", C.c_uint32), ("nodeCount", C.c_uint32), ("node4Count", C.c_uint32), ("maxDepth", C.c_uint32),

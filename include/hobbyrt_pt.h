@@ -1200,6 +1200,109 @@ int  hrpt_indirect_resolve_host(const HrptIndirectImages* images, uint32_t width
 int  hrpt_indirect_compose_host(const HrptIndirectImages* images, uint32_t width, uint32_t height, const HrptIndirectParams* params,
                                 int nthreads);
 
+/* ---- resampled direct lighting (ReSTIR DI) -------------------------------------------------------------------------------------------
+ * A direct-light stage whose shadow rays do not grow with the light list: one per pixel whatever m_LightCount is (two with
+ * HRPT_RESTIR_INITIAL_VISIBILITY). Candidates are drawn by resampled importance sampling, reused across frames through the motion plane
+ * and across neighbouring pixels (pairwise MIS), and the chosen light is shaded into an image of hrpt_deferred_lighting's form; in
+ * expectation it equals hrpt_deferred_lighting(HRPT_DEFERRED_SHADOWS). Defined by this project after the published algorithm (Bitterli
+ * et al. 2020); parity with the RTXDI SDK is out of scope. Additive; HRPT_ABI_VERSION stays 3.
+ * One source for kernels and host executors: hobbyrenderer_amd/csrc/pt_restir.h; DESIGN.md section 30 has every operation in order.
+ * Surface S(x, y): the primary ray of `constants`, X = o + d * t, the surface terms of deferred lighting. Target pHat(S, i): 0 when light
+ * i is culled at S, else luminance(diffuse + specular) of the unshadowed light, through p > 0 ? p : 0. A reservoir is 16 bytes per pixel;
+ * light == HRPT_RESTIR_EMPTY means empty. RNG: sA = pcg_hash(y * W + x + pcg_hash(frameSeed)), sB = pcg_hash(sA), sC = pcg_hash(sB).
+ * Four passes: initial (`candidates` uniform draws, W = (wSum / M) / pHat), temporal (the record of the previous pixel q = floor(p + 0.5 +
+ * motion.xy), accepted on motion.w == 1, q inside, light < m_LightCount, dot(N, key.xyz) >= normalThreshold and |key.w - (depth.y +
+ * motion.z)| <= depthThreshold * (depth.y + motion.z), its M clamped to maxHistory * M), spatial (`spatialSamples` neighbours in a disc of
+ * spatialRadius pixels, accepted on the same normal and depth rules, combined with pairwise MIS weights) and shade (rgb = (diffuse +
+ * specular) * (W * vis) + E.rgb, alpha = A.a; a miss as in deferred lighting). A pass whose flag is off runs without a partner. The temporal
+ * pass is the published biased form under motion (exact for a static frame without jitter); HRPT_RESTIR_INITIAL_VISIBILITY makes the
+ * spatial pass biased as well. Light indices must name the same lights between calls: a caller who reorders the list passes
+ * HRPT_RESTIR_RESET. */
+#define HRPT_RESTIR_SHADOWS            1u    /* the chosen light's shadow ray through hrpt_trace_rays(HRPT_RAYS_SHADOW) */
+#define HRPT_RESTIR_SKY                2u    /* the atmosphere: sky at misses, sun_radiance(X) for directional lights */
+#define HRPT_RESTIR_TEMPORAL           4u    /* reuse the previous call's reservoirs through the motion plane */
+#define HRPT_RESTIR_SPATIAL            8u    /* reuse `spatialSamples` neighbouring reservoirs */
+#define HRPT_RESTIR_INITIAL_VISIBILITY 16u   /* a second shadow ray for the initial sample; biased, opt-in */
+#define HRPT_RESTIR_RESET              32u   /* ignore (and replace) the history */
+#define HRPT_RESTIR_EMPTY              0xFFFFFFFFu
+#define HRPT_RESTIR_LDS_MAX_LIGHTS     512   /* up to this many lights the initial pass gathers its candidates from LDS (32 KiB) */
+typedef struct HrptRestirParams {
+    uint32_t flags;              /* HRPT_RESTIR_* */
+    uint32_t frameSeed;
+    uint32_t candidates;         /* 1..32; documented default 8 */
+    uint32_t spatialSamples;     /* 0..8; default 1 */
+    float spatialRadius;         /* pixels, finite, in (0, 65535]; default 32 */
+    float maxHistory;            /* finite, > 0; default 20 */
+    float depthThreshold;        /* finite; default 0.1 */
+    float normalThreshold;       /* finite; default 0.5 */
+    uint32_t reserved[4];        /* 0 */
+} HrptRestirParams;
+typedef struct HrptRestirReservoir {
+    uint32_t light;              /* index into the light list, or HRPT_RESTIR_EMPTY */
+    float W;                     /* the unbiased contribution weight */
+    float M;                     /* the number of candidates the record stands for */
+    float pHat;                  /* the target of `light` at the surface that owns the record */
+} HrptRestirReservoir;
+typedef struct HrptRestirImages {
+    const float *albedo, *normal, *geoNormal, *emissive, *depth;
+    const float *motion;                       /* hrpt_render_motion_vectors' plane; NULL unless HRPT_RESTIR_TEMPORAL */
+    const HrptRestirReservoir *reservoirIn;    /* the history: the previous call's reservoirOut, or NULL */
+    const float *keyIn;                        /* ... and its keyOut (N.xyz, view depth), or NULL */
+    HrptRestirReservoir *reservoirOut;         /* width * height records */
+    float *keyOut;                             /* float4 image */
+    float *colorOut;                           /* float4 image; must differ from every other image */
+} HrptRestirImages;
+/* Over the context's own planes into Output: initial -> [trace] -> temporal -> spatial -> [trace] -> shade on the context stream, each
+ * trace one hrpt_trace_rays(HRPT_RAYS_SHADOW | HRPT_RAYS_DEVICE_POINTERS) of width * height records. Reservoirs, keys, ray and hit records
+ * are library-owned (allocated on first use, dropped by hrpt_resize); the history is also dropped by HRPT_RESTIR_RESET. The result equals,
+ * bit for bit, hrpt_restir_initial_host -> hrpt_trace_rays -> hrpt_restir_temporal_host -> hrpt_restir_spatial_host -> hrpt_trace_rays ->
+ * hrpt_restir_shade_host through the public calls. Accumulation, the G-buffer, the motion plane, the other histories, exposure and
+ * HrptStats are untouched. No scene: HRPT_ERR_NO_SCENE. hrpt_resize not called, a plane never requested (the message names it; the motion
+ * plane with HRPT_RESTIR_TEMPORAL), m_LightCount above the scene's light count, candidates or spatialSamples out of range, a radius or
+ * history that is not finite and positive, a threshold that is not finite, unknown flag bits, non-zero reserved:
+ * HRPT_ERR_INVALID_ARGUMENT. An error changes nothing. */
+int  hrpt_restir_lighting(HrptContext* ctx, const HrptPathTracerConstants* constants, const HrptRestirParams* params);
+/* The last call's final reservoirs, width * height records (synchronises); and the device addresses of them and of their key plane (NULL
+ * before the first call, after a resize). */
+int  hrpt_read_restir_reservoirs(HrptContext* ctx, HrptRestirReservoir* dst, size_t bytes);
+int  hrpt_get_restir_device(HrptContext* ctx, void** reservoirs, void** keys);
+/* The same over caller-owned DEVICE images (16-byte aligned), with the scene, lights and ray buffers of `ctx`, every step on `stream` (a
+ * hipStream_t; NULL = the default stream). The history is reservoirIn / keyIn (both NULL = none). Null or aliased images:
+ * HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_restir_lighting_device(HrptContext* ctx, const HrptRestirImages* deviceImages, uint32_t width, uint32_t height,
+                                 const HrptPathTracerConstants* constants, const HrptRestirParams* params, void* stream);
+/* The four kernels on their own, over DEVICE arrays; the lights are the context's. initial: writes images->reservoirOut, and with
+ * HRPT_RESTIR_INITIAL_VISIBILITY one HrptRay per pixel into raysOut (an empty reservoir: origin = NaN, the rest 0). temporal: reads
+ * `initial`, its hit records (NULL unless HRPT_RESTIR_INITIAL_VISIBILITY), the history and images->motion, writes images->reservoirOut.
+ * spatial: reads `temporal`, writes images->reservoirOut, images->keyOut and, when raysOut is not NULL, the chosen light's HrptRay.
+ * shade: reads `final` and the hit records of those rays (NULL = visibility 1), writes images->colorOut. All four need a scene: its light
+ * buffer, and its atmosphere tables with HRPT_RESTIR_SKY. An output must differ from every array the pass reads. */
+int  hrpt_restir_initial_device(HrptContext* ctx, const HrptRestirImages* deviceImages, uint32_t width, uint32_t height,
+                                const HrptPathTracerConstants* constants, const HrptRestirParams* params, HrptRay* raysOut, void* stream);
+int  hrpt_restir_temporal_device(HrptContext* ctx, const HrptRestirImages* deviceImages, uint32_t width, uint32_t height,
+                                 const HrptPathTracerConstants* constants, const HrptRestirParams* params, const HrptRestirReservoir* initial,
+                                 const HrptRayHit* initialHits, void* stream);
+int  hrpt_restir_spatial_device(HrptContext* ctx, const HrptRestirImages* deviceImages, uint32_t width, uint32_t height,
+                                const HrptPathTracerConstants* constants, const HrptRestirParams* params, const HrptRestirReservoir* temporal,
+                                HrptRay* raysOut, void* stream);
+int  hrpt_restir_shade_device(HrptContext* ctx, const HrptRestirImages* deviceImages, uint32_t width, uint32_t height,
+                              const HrptPathTracerConstants* constants, const HrptRestirParams* params, const HrptRestirReservoir* final,
+                              const HrptRayHit* hits, void* stream);
+/* The four passes on the host, with no GPU and no scene; same bits as the kernels. `lights` is a host array of constants->m_LightCount
+ * records. sunRadiance: a float4 image, rgb = the radiance of a directional light at the pixel's X, NULL = m_Color * m_Intensity. sky: a
+ * float4 image whose texel is stored at a miss, NULL = (0, 0, 0, 0). initialVisibility / visibility: float [height][width], NULL = 1. */
+int  hrpt_restir_initial_host(const HrptRestirImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
+                              const HrptGPULight* lights, const HrptRestirParams* params, const float* sunRadiance, HrptRay* raysOut, int nthreads);
+int  hrpt_restir_temporal_host(const HrptRestirImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
+                               const HrptGPULight* lights, const HrptRestirParams* params, const float* sunRadiance,
+                               const HrptRestirReservoir* initial, const float* initialVisibility, int nthreads);
+int  hrpt_restir_spatial_host(const HrptRestirImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
+                              const HrptGPULight* lights, const HrptRestirParams* params, const float* sunRadiance,
+                              const HrptRestirReservoir* temporal, HrptRay* raysOut, int nthreads);
+int  hrpt_restir_shade_host(const HrptRestirImages* images, uint32_t width, uint32_t height, const HrptPathTracerConstants* constants,
+                            const HrptGPULight* lights, const HrptRestirParams* params, const float* sunRadiance, const float* sky,
+                            const HrptRestirReservoir* final, const float* visibility, int nthreads);
+
 /* Intra-frame overlap: by default the shadow stage of bounce b runs on a second, library-owned stream next to the traversal of bounce
  * b + 1 (they share no buffer). That fills the tails of a context that renders one frame at a time (-3 % per frame). A host that keeps
  * two frames in flight on two contexts already fills those tails with the other frame; there the fork / join events only cost
