@@ -1,0 +1,770 @@
+"""One path of the path tracer in float64, written from the shader text -- TEST INFRASTRUCTURE.
+
+A NumPy float64 statement of PathTracer_CSMain from the ray onward (PathTracer.hlsl:74-329) and of what it calls: TraceRayStandard
+(RaytracingCommon.hlsli:138-198), GetFullHitAttributes / GetPBRAttributes (:52-77, :252-296), PrepareLightingByproducts, EvaluateDirectLight,
+CalculateRTShadow<true>, the three stochastic light functions, AccumulateDirectLighting, SampleHemisphereCosine, SampleGGX_VNDF,
+EvalGGX_VNDF_Weight, SampleConeSolidAngle (CommonLighting.hlsli:316-375, :380-496, :716-908, :170-183, :622-655, :671-688, :693-708), the RNG
+(RNG.hlsli:14-38) and the constants of Common.sr:48-50. It shares no code with hobbyrenderer_amd/csrc/pt_path.h or oracle/pt_oracle.c and
+was not written from them, and it takes no arithmetic from deferred_reference, indirect_reference or restir_reference. From pinned test
+infrastructure it takes the quantised geometry (gbuffer_reference.unpacked_vertices / world_triangle), the atmosphere in float64 over the
+scene's own binary16 tables (atmosphere_reference.rt_sky_radiance / rt_sun_radiance) and texels (texture_reference).
+
+What is the project's and not the shader's is taken as defined there: a ray hits a triangle iff tmin < t < tmax, the
+barycentrics are the weights of v1 and v2, and the candidates of a query are visited in increasing t. Hits are brute force: every ray
+against every world triangle, Moeller-Trumbore in float64. The hit position is ray.Origin + ray.Direction * t (RaytracingCommon.hlsli:65),
+which in float64 is the barycentric interpolation of the vertices to 1e-16.
+
+Rules that keep it comparable with a binary32 implementation: every binary32 input (ray records, light, material and frame constants,
+vertex attributes, literals of the shader) enters at its exact value; a draw is the binary32 value float(state) * 2^-32 -- the conversion
+rounds, and the result can be exactly 1.0 -- carried into float64; sin, cos, exp and sqrt are libm's.
+
+Decision margin. A float64 path and a binary32 path part ways where a comparison flips, so every path carries `margin`: the minimum over
+every decision taken of the normalised distance to its threshold -- |u - p| for a compare against a draw, |value| for a sign test over
+unit vectors (and for the sun disk's nu > cos(alpha)), |distSq / range^2 - 1|, |maxcomp / 0.01 - 1|, |transmission / 1e-3 - 1|,
+|sinThetaTSq - 1|, and for every ray query the smallest |c| over the triangles that could change its result, c = the least of the three
+barycentrics and the distances of t to tmin and tmax along the triangle's normal, relative to the coordinates (PathScene.pairs says why
+not relative to tmin; positive: accepted, negative: rejected), plus the relative gap in t between a visited candidate and the next.
+Compares of material constants (roughness against 0.08 and 0.04) are asserted to be far.
+
+MEASURED: DELTA, TAU and CASE_TABLE below, against the CPU oracle only, never a GPU build, on the cases of tests/path_cases.py;
+tests/test_path_reference_cpu.py::test_delta_and_tau_are_what_the_oracle_measures recomputes and prints them.
+"""
+import math
+
+import numpy as np
+
+from hobbyrenderer_amd import structs as S
+import atmosphere_reference as A
+import gbuffer_reference as G
+import texture_reference as T
+
+F = np.float64
+INF = np.inf
+
+
+def c32(x):
+    """A literal of the shader at its binary32 value."""
+    return F(np.float32(x))
+
+
+PI = c32(3.14159265359)                 # Common.sr:48
+K_EPSILON = c32(1e-5)                   # Common.sr:50
+LUMA = np.array([c32(0.2126), c32(0.7152), c32(0.0722)])
+TWO_PI = F(np.float32(2.0) * np.float32(3.14159265359))
+
+# ---- measured against the oracle (see the module docstring); the GPU tests import the same constants
+DELTA_WORST_FLIPPED_MARGIN = 1.667356e-07   # case C, camera index 8, pixel 420: a ray that leaves a block's face at 0.1 degrees (n.d = 1.7e-3) and meets the
+                                            # face again at t > tmin in binary32; the only path of 47 920 that deviates by more than 1e-2
+DELTA = 2.0 ** -19                          # 8 x the figure above (1.33e-6), rounded up to a power of two: 1.91e-6
+TAU_WORST_INCLUDED_ERROR = 6.675e-04        # case C
+TAU = 4.0 * TAU_WORST_INCLUDED_ERROR        # 2.67e-3
+MAX_EXCLUDED_SHARE = 0.05
+# per case: (worst error of an included path over all measured views, share of the paths of the case's own views left out)
+CASE_TABLE = {"A": (9.518e-05, 0.0036), "B": (2.959e-06, 0.0049), "C": (6.675e-04, 0.0072), "D": (6.651e-05, 0.0018), "E": (3.745e-05, 0.0067)}
+
+MUTATIONS = ("g1_ndotv", "spec_weight_without_prob", "diffuse_weight_by_spec_prob", "roulette_from_bounce_1", "specular_direct_kept",
+             "vndf_u_swapped", "fd90_without_half", "fresnel_with_eta_refract", "medium_not_cleared", "shadow_tmax_without_bias",
+             "sun_disk_on_later_misses", "draw_after_culled_light")
+
+BRANCHES = ("specular lobe", "diffuse lobe", "lobe rejected below the horizon", "roulette survive", "roulette kill", "bail-out",
+            "delta transmission", "rough transmission", "medium entered", "medium left", "Beer-Lambert applied",
+            "reflection fallback at a transmissive surface", "BLEND commit", "BLEND reject", "point light lit", "point light range-culled",
+            "spot cone-culled", "spot lit", "sun lit", "sun occluded", "sky miss at bounce 0", "sky miss later", "sun disk seen",
+            "filtered shadow strictly between 0 and 1", "back-face hit", "shadow early commit", "TIR fallback")
+
+
+# ---------------------------------------------------------------------------------------------------------------- small vector helpers
+def dot(a, b):
+    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
+
+
+def cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1],
+                     a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
+
+
+def normalize(a):
+    return a / np.sqrt(dot(a, a))[..., None]
+
+
+def saturate(x):
+    return np.minimum(np.maximum(x, 0.0), 1.0)
+
+
+def lerp(a, b, t):
+    return a + t * (b - a)
+
+
+def pow5(x):
+    return x * x * x * x * x
+
+
+# ---------------------------------------------------------------------------------------------------------------- RNG.hlsli:14-38
+def pcg_hash(seed):
+    s = np.asarray(seed, np.uint32).astype(np.uint64)
+    mask = np.uint64(0xFFFFFFFF)
+    state = (s * np.uint64(747796405) + np.uint64(2891336453)) & mask
+    word = (((state >> ((state >> np.uint64(28)) + np.uint64(4))) ^ state) * np.uint64(277803737)) & mask
+    return ((word >> np.uint64(22)) ^ word).astype(np.uint32)
+
+
+def init_rng(px, py, index):
+    px, py = np.asarray(px, np.uint64), np.asarray(py, np.uint64)
+    seed = (px + py * np.uint64(65536) + np.uint64(index) * np.uint64(6700417)) & np.uint64(0xFFFFFFFF)
+    return pcg_hash(seed.astype(np.uint32))
+
+
+class Rng:
+    """One PCG state per path; next(mask) advances the paths of `mask` only and returns the draw (valid where mask)."""
+
+    def __init__(self, state):
+        self.state = np.array(state, np.uint32)
+
+    def next(self, mask):
+        self.state = np.where(mask, pcg_hash(self.state), self.state)
+        return self.state.astype(np.float32).astype(F) * 2.0 ** -32          # uint32 -> binary32 rounds to nearest even; the scale is exact
+
+
+# ---------------------------------------------------------------------------------------------------------------- the scene in float64
+class PathScene:
+    """World triangles, vertex attributes and material / light constants of a structs.SceneArrays at their exact values."""
+
+    def __init__(self, scene):
+        self.scene = scene
+        verts = G.unpacked_vertices(scene)
+        P, NW, UV, inst_of, prim_of, mat_of = [], [], [], [], [], []
+        for inst in range(len(scene.instances)):
+            rec = scene.instances[inst]
+            mesh = scene.mesh_data[rec["m_MeshDataIndex"]]
+            base, count = int(mesh["m_IndexOffsets"][0]), int(mesh["m_IndexCounts"][0]) // 3
+            w = np.asarray(rec["m_World"], F)
+            adj = np.stack([np.cross(w[1, :3], w[2, :3]), np.cross(w[2, :3], w[0, :3]), np.cross(w[0, :3], w[1, :3])])      # Common.hlsli:33-41
+            for prim in range(count):
+                idx = scene.indices[base + 3 * prim:base + 3 * prim + 3]
+                P.append(G.world_triangle(scene, verts, inst, prim))
+                NW.append(verts[idx, 3:6].astype(F) @ adj)                  # linear, so transformed per vertex; normalised after interpolation
+                UV.append(verts[idx, 6:8].astype(F))
+                inst_of.append(inst); prim_of.append(prim); mat_of.append(int(rec["m_MaterialIndex"]))
+        self.P, self.NW, self.UV = np.array(P), np.array(NW), np.array(UV)
+        self.inst_of, self.prim_of, self.mat_of = np.array(inst_of), np.array(prim_of), np.array(mat_of)
+        self.e1, self.e2 = self.P[:, 1] - self.P[:, 0], self.P[:, 2] - self.P[:, 0]
+        self.area2 = np.sqrt(dot(cross(self.e1, self.e2), cross(self.e1, self.e2)))
+        self.extent = np.abs(self.P).max((1, 2))                         # the largest coordinate of a triangle
+        m = scene.materials
+        self.base = np.asarray(m["m_BaseColor"], F).reshape(-1, 4)
+        self.emissive = np.asarray(m["m_EmissiveFactor"], F).reshape(-1, 4)[:, :3]
+        self.rough, self.metal = np.asarray(m["m_RoughnessMetallic"], F).reshape(-1, 2).T
+        self.flags, self.mode = np.asarray(m["m_TextureFlags"]).astype(int), np.asarray(m["m_AlphaMode"]).astype(int)
+        self.cutoff, self.ior, self.transmission = (np.asarray(m[k], F) for k in ("m_AlphaCutoff", "m_IOR", "m_TransmissionFactor"))
+        self.thin = np.asarray(m["m_IsThinSurface"]) != 0
+        self.sigma_a, self.sigma_s = np.asarray(m["m_SigmaA"], F).reshape(-1, 3), np.asarray(m["m_SigmaS"], F).reshape(-1, 3)
+        assert not (self.flags & S.TEXFLAG_NORMAL).any(), "normal maps are out of scope"
+        assert not ((self.mode == S.ALPHA_MODE_MASK) & ((self.flags & S.TEXFLAG_ALBEDO) != 0)).any(), "MASK with a sampled alpha is out of scope"
+        assert (np.abs(self.base[:, 3] - self.cutoff)[self.mode == S.ALPHA_MODE_MASK] > 1e-3).all()
+        self.t16, self.s16 = A.to_half(scene.lut_transmittance), A.to_half(scene.lut_scattering)
+        self._levels = {}
+
+    # -- textures
+    def sample(self, tex, sampler, uv):
+        if tex not in self._levels:
+            t = self.scene.textures[tex]
+            if isinstance(t, S.Texture):
+                self._levels[tex] = T.decode_levels(t.data, t.width, t.height, t.format, t.mip_count)[0]
+            else:
+                self._levels[tex] = T.decode_levels(t, t.shape[1], t.shape[0], T.FORMAT_RGBA8_UNORM, 1)[0]
+        uv = np.clip(np.nan_to_num(np.asarray(uv, F), nan=0.0, posinf=0.0, neginf=0.0), -1e3, 1e3)      # lanes that are masked out carry anything
+        return T.sample_level(self._levels[tex], sampler, uv.astype(np.float32))[0]
+
+    def _per_material(self, mat, flag, fn):
+        """fn(material index, rows) for every material among `mat` whose texture flag `flag` is set."""
+        for m in np.unique(mat):
+            if self.flags[m] & flag:
+                fn(int(m), np.nonzero(mat == m)[0])
+
+    def alpha(self, mat, uv):
+        """m_BaseColor.w times the albedo texture's alpha where one is bound (RaytracingCommon.hlsli:173-177, CommonLighting.hlsli:436-440)."""
+        a = self.base[mat, 3].copy()
+        ms = self.scene.materials
+
+        def tex(m, rows):
+            a[rows] *= self.sample(int(ms[m]["m_AlbedoTextureIndex"]), int(ms[m]["m_AlbedoSamplerIndex"]), uv[rows])[:, 3]
+        self._per_material(mat, S.TEXFLAG_ALBEDO, tex)
+        return a
+
+    def pbr(self, mat, uv):
+        """GetPBRAttributes (RaytracingCommon.hlsli:252-296) without a normal map: baseColor, alpha, roughness, metallic, emissive."""
+        ms = self.scene.materials
+        base, rough, metal, emissive = self.base[mat].copy(), self.rough[mat].copy(), self.metal[mat].copy(), self.emissive[mat].copy()
+
+        def albedo(m, rows):
+            base[rows] *= self.sample(int(ms[m]["m_AlbedoTextureIndex"]), int(ms[m]["m_AlbedoSamplerIndex"]), uv[rows])
+
+        def rm(m, rows):
+            s = self.sample(int(ms[m]["m_RoughnessMetallicTextureIndex"]), int(ms[m]["m_RoughnessSamplerIndex"]), uv[rows])
+            rough[rows], metal[rows] = s[:, 1], s[:, 2]
+
+        def em(m, rows):
+            emissive[rows] *= self.sample(int(ms[m]["m_EmissiveTextureIndex"]), int(ms[m]["m_EmissiveSamplerIndex"]), uv[rows])[:, :3]
+        self._per_material(mat, S.TEXFLAG_ALBEDO, albedo)
+        self._per_material(mat, S.TEXFLAG_ROUGHNESS_METALLIC, rm)
+        self._per_material(mat, S.TEXFLAG_EMISSIVE, em)
+        assert (np.abs(rough - c32(0.04)) > 1e-3).all() and (np.abs(rough - c32(0.08)) > 1e-3).all(), "roughness next to a threshold"
+        rough = np.maximum(rough, c32(0.04))
+        return base[:, :3], base[:, 3], rough, metal, emissive
+
+    # -- ray queries
+    def pairs(self, o, d, tmin, tmax):
+        """Every ray against every triangle: t, u, v [n, T] and c [n, T], the least of the acceptance conditions. A pair is a hit iff
+        c > 0; |c| is how far it is from changing sides. The conditions are the three barycentrics and the distances of t to tmin and
+        tmax, the latter two measured ALONG THE TRIANGLE'S NORMAL and relative to the coordinates involved: (t - tmin) * |n.d| is how far
+        the plane lies from the point o + tmin * d, and a binary32 implementation knows o and the vertices to a few ulp of their size
+        (the error of t is a few ulp of the triangle's size), whatever the angle. A plain (t - tmin) / tmin calls
+        a ray that leaves its own surface at a grazing angle safe (t = 0, margin 1) when in binary32 the surface re-appears at
+        t = error / |n.d| > tmin: the one flip at a large margin that the first measurement found (case C, index 8, pixel 420)."""
+        with np.errstate(all="ignore"):
+            pvec = cross(d[:, None, :], self.e2[None])
+            det = dot(self.e1[None], pvec)
+            tvec = o[:, None, :] - self.P[None, :, 0]
+            u = dot(tvec, pvec) / det
+            qvec = cross(tvec, self.e1[None])
+            v = dot(d[:, None, :], qvec) / det
+            e2q = dot(self.e2[None], qvec)
+            t = e2q / det
+            nd, tn = det / self.area2[None], e2q / self.area2[None]      # n.d and t * n.d, finite for a grazing ray
+            scale = np.maximum(np.abs(o).max(1)[:, None], self.extent[None])
+            lo = np.sign(nd) * (tn - tmin[:, None] * nd) / scale
+            hi = np.sign(nd) * (tmax[:, None] * nd - tn) / scale
+            c = np.minimum(np.minimum(np.minimum(1.0 - u - v, u), v), np.minimum(lo, hi))
+        c = np.where(np.isfinite(c) & np.isfinite(t), c, -INF)             # a ray parallel to the plane is a miss by any margin
+        return t, u, v, c
+
+    def normal_at(self, tri, u, v):
+        """normalize(TransformNormal(interpolated local normal)), RaytracingCommon.hlsli:62-68 and Common.hlsli:43-47."""
+        nw = self.NW[tri]
+        return normalize(nw[:, 0] * (1.0 - u - v)[:, None] + nw[:, 1] * u[:, None] + nw[:, 2] * v[:, None])
+
+    def uv_at(self, tri, u, v):
+        uv = self.UV[tri]
+        return uv[:, 0] * (1.0 - u - v)[:, None] + uv[:, 1] * u[:, None] + uv[:, 2] * v[:, None]
+
+    def trace_standard(self, o, d, tmin, rng, live, margin, took):
+        """TraceRayStandard (RaytracingCommon.hlsli:138-198) for the paths of `live`, candidates front to back. Returns hit, tri, t, u, v."""
+        n = len(o)
+        tmax = np.full(n, c32(1e10))
+        t, u, v, c = self.pairs(o, d, tmin, tmax)
+        ok = (c > 0) & live[:, None]
+        ts = np.where(ok, t, INF)
+        order = np.argsort(ts, 1)
+        rows = np.arange(n)
+        done = ~live
+        hit, tri_out = np.zeros(n, bool), np.zeros(n, int)
+        for k in range(ts.shape[1]):
+            tri = order[:, k]
+            valid = ok[rows, tri] & ~done
+            if not valid.any():
+                break
+            mat = self.mat_of[tri]
+            mode = self.mode[mat]
+            commit = valid & (mode == S.ALPHA_MODE_OPAQUE)
+            commit |= valid & (mode == S.ALPHA_MODE_MASK) & (self.base[mat, 3] >= self.cutoff[mat])          # AlphaTest, constants only
+            blend = valid & (mode == S.ALPHA_MODE_BLEND)
+            commit |= blend & (self.transmission[mat] > 0.0)
+            draw = blend & ~(self.transmission[mat] > 0.0)
+            if draw.any():
+                alpha = saturate(self.alpha(mat, self.uv_at(tri, u[rows, tri], v[rows, tri])))
+                x = rng.next(draw)
+                margin[:] = np.where(draw, np.minimum(margin, np.abs(x - alpha)), margin)
+                took["BLEND commit"] |= draw & (x < alpha)
+                took["BLEND reject"] |= draw & ~(x < alpha)
+                commit |= draw & (x < alpha)
+            if k + 1 < ts.shape[1]:                                        # the order of this candidate and the next
+                nxt = ts[rows, order[:, k + 1]]
+                with np.errstate(all="ignore"):
+                    gap = np.where(np.isfinite(nxt), (nxt - ts[rows, tri]) / nxt, INF)
+                margin[:] = np.where(valid, np.minimum(margin, gap), margin)
+            hit |= commit
+            tri_out = np.where(commit, tri, tri_out)
+            done |= commit
+        t_commit = np.where(hit, t[rows, tri_out], INF)
+        relevant = (t <= t_commit[:, None]) & live[:, None] & np.isfinite(c)
+        margin[:] = np.minimum(margin, np.where(relevant, np.abs(c), INF).min(1))
+        return hit, tri_out, t[rows, tri_out], u[rows, tri_out], v[rows, tri_out]
+
+    def shadow(self, X, L, max_dist, live, margin, took, mutation=None):
+        """CalculateRTShadow<true> (CommonLighting.hlsli:380-496), candidates in increasing t."""
+        n = len(X)
+        bias = c32(0.01)
+        tmin = np.full(n, bias)
+        tmax = np.maximum(bias, max_dist - bias * 2.0)
+        if mutation == "shadow_tmax_without_bias":
+            tmax = np.maximum(bias, max_dist)
+        t, u, v, c = self.pairs(X, L, tmin, tmax)
+        ok = (c > 0) & live[:, None]
+        mode = self.mode[self.mat_of]
+        blocks = (mode == S.ALPHA_MODE_OPAQUE) | ((mode == S.ALPHA_MODE_MASK) & (self.base[self.mat_of, 3] >= self.cutoff[self.mat_of]))
+        blocked = (ok & blocks[None]).any(1)
+        # a blocked ray stays blocked while one blocker stays hit; an open one changes if any triangle changes sides
+        m_blocked = np.where(ok & blocks[None], c, -INF).max(1)
+        m_open = np.where(np.isfinite(c), np.abs(c), INF).min(1)
+        margin[:] = np.where(live, np.minimum(margin, np.where(blocked, m_blocked, m_open)), margin)
+        walk = live & ~blocked
+        cand = ok & (mode == S.ALPHA_MODE_BLEND)[None] & walk[:, None]
+        ts = np.where(cand, t, INF)
+        order = np.argsort(ts, 1)
+        rows = np.arange(n)
+        transmission = np.ones(n)
+        in_volume, start_t, sigma_t = np.zeros(n, bool), np.zeros(n), np.zeros((n, 3))
+        committed = np.zeros(n, bool)
+        for k in range(ts.shape[1]):
+            tri = order[:, k]
+            valid = cand[rows, tri] & ~committed
+            if not valid.any():
+                break
+            mat = self.mat_of[tri]
+            uu, vv, tt = u[rows, tri], v[rows, tri], t[rows, tri]
+            alpha = self.alpha(mat, self.uv_at(tri, uu, vv))
+            opacity = saturate(alpha * (1.0 - self.transmission[mat]))
+            transmission = np.where(valid, transmission * (1.0 - opacity), transmission)
+            thick = valid & (self.transmission[mat] > 0.0) & ~self.thin[mat]
+            facing = dot(self.normal_at(tri, uu, vv), L)
+            margin[:] = np.where(thick, np.minimum(margin, np.abs(facing)), margin)
+            front = thick & (facing < 0.0)
+            leave = thick & ~front & in_volume
+            with np.errstate(all="ignore"):
+                tr = np.exp(-sigma_t * np.maximum(0.0, tt - start_t)[:, None])
+            transmission = np.where(leave, transmission * (tr @ LUMA), transmission)
+            in_volume = np.where(front, True, np.where(leave, False, in_volume))
+            start_t = np.where(front, tt, start_t)
+            sigma_t = np.where(front[:, None], self.sigma_a[mat] + self.sigma_s[mat], sigma_t)
+            margin[:] = np.where(valid, np.minimum(margin, np.abs(transmission / c32(1e-3) - 1.0)), margin)
+            commit = valid & (transmission <= c32(1e-3))
+            took["shadow early commit"] |= commit
+            committed |= commit
+            if k + 1 < ts.shape[1]:
+                nxt = ts[rows, order[:, k + 1]]
+                with np.errstate(all="ignore"):
+                    gap = np.where(np.isfinite(nxt), (nxt - ts[rows, tri]) / nxt, INF)
+                margin[:] = np.where(valid & ~commit, np.minimum(margin, gap), margin)
+        with np.errstate(all="ignore"):
+            tr = np.exp(-sigma_t * np.maximum(0.0, tmax - start_t)[:, None])
+        tail = walk & ~committed & in_volume
+        transmission = np.where(tail, transmission * (tr @ LUMA), transmission)
+        return np.where(blocked | committed | ~live, 0.0, saturate(transmission))
+
+
+# ---------------------------------------------------------------------------------------------------------------- CommonLighting.hlsli
+def fresnel_dielectric(eta, cos_i):
+    """EvalFresnelDielectric (PathTracer.hlsl:26-43) for cos_i >= 0: (F, cosThetaT, sinThetaTSq)."""
+    s2 = eta * eta * (1.0 - cos_i * cos_i)
+    tir = s2 >= 1.0
+    cos_t = np.sqrt(np.maximum(0.0, 1.0 - s2))
+    with np.errstate(all="ignore"):
+        rs = (eta * cos_i - cos_t) / (eta * cos_i + cos_t)
+        rp = (eta * cos_t - cos_i) / (eta * cos_t + cos_i)
+    return np.where(tir, 1.0, 0.5 * (rs * rs + rp * rp)), np.where(tir, 0.0, cos_t), s2
+
+
+def tangent_frame(n_, margin=None, live=None):
+    """BuildTangentFrame and the frames of SampleHemisphereCosine / SampleConeSolidAngle (CommonLighting.hlsli:610-615, :178-180, :703-705)."""
+    z = np.abs(n_[..., 2])
+    if margin is not None:
+        margin[:] = np.where(live, np.minimum(margin, np.abs(z - c32(0.999))), margin)
+    up = np.where((z < c32(0.999))[..., None], np.array([0.0, 0.0, 1.0]), np.array([1.0, 0.0, 0.0]))
+    t = normalize(cross(up, n_))
+    return t, cross(n_, t)
+
+
+def sample_hemisphere_cosine(ux, uy, n_, margin, live):
+    phi = TWO_PI * ux
+    cos_t = np.sqrt(uy)
+    sin_t = np.sqrt(np.maximum(0.0, 1.0 - cos_t * cos_t))
+    t, b = tangent_frame(n_, margin, live)
+    return t * (sin_t * np.cos(phi))[:, None] + n_ * cos_t[:, None] + b * (sin_t * np.sin(phi))[:, None]
+
+
+def sample_cone(dir_, cos_half, ux, uy, margin, live):
+    cos_t = 1.0 - ux * (1.0 - cos_half)
+    sin_t = np.sqrt(np.maximum(0.0, 1.0 - cos_t * cos_t))
+    phi = TWO_PI * uy
+    t, b = tangent_frame(dir_, margin, live)
+    return t * (sin_t * np.cos(phi))[:, None] + dir_ * cos_t[:, None] + b * (sin_t * np.sin(phi))[:, None]
+
+
+def sample_ggx_vndf(ux, uy, n_, v_, rough, margin, live):
+    alpha = rough * rough
+    t, b = tangent_frame(n_, margin, live)
+    vl = np.stack([dot(v_, t), dot(v_, n_), dot(v_, b)], -1)
+    vh = normalize(np.stack([alpha * vl[:, 0], vl[:, 1], alpha * vl[:, 2]], -1))
+    lensq = vh[:, 0] * vh[:, 0] + vh[:, 2] * vh[:, 2]
+    margin[:] = np.where(live, np.minimum(margin, np.sqrt(lensq)), margin)      # lensq > 0: the frame turns freely where it vanishes
+    with np.errstate(all="ignore"):
+        t1v = np.where((lensq > 0.0)[:, None], np.stack([-vh[:, 2], np.zeros_like(lensq), vh[:, 0]], -1) / np.sqrt(lensq)[:, None],
+                       np.array([1.0, 0.0, 0.0]))
+    t2v = cross(vh, t1v)
+    r = np.sqrt(ux)
+    phi = TWO_PI * uy
+    t1, t2 = r * np.cos(phi), r * np.sin(phi)
+    s = 0.5 * (1.0 + vh[:, 1])
+    t2 = lerp(np.sqrt(np.maximum(0.0, 1.0 - t1 * t1)), t2, s)
+    nh = t1v * t1[:, None] + t2v * t2[:, None] + vh * np.sqrt(np.maximum(0.0, 1.0 - t1 * t1 - t2 * t2))[:, None]
+    ne = normalize(np.stack([alpha * nh[:, 0], np.maximum(0.0, nh[:, 1]), alpha * nh[:, 2]], -1))
+    return t * ne[:, 0:1] + n_ * ne[:, 1:2] + b * ne[:, 2:3]
+
+
+def byproducts(n_, v_, l_, base, metal, ior):
+    """PrepareLightingByproducts (CommonLighting.hlsli:316-334): NdotV NdotL NdotH VdotH LdotH F0 kD F."""
+    n_v, n_l = saturate(dot(n_, v_)), saturate(dot(n_, l_))
+    vpl = v_ + l_
+    ln = dot(vpl, vpl)
+    with np.errstate(all="ignore"):
+        h = np.where((ln > c32(1e-8))[:, None], vpl * (1.0 / np.sqrt(ln))[:, None], n_)
+    n_h, v_h, l_h = saturate(dot(n_, h)), saturate(dot(v_, h)), saturate(dot(l_, h))
+    q = (ior - 1.0) / (ior + 1.0)
+    f0 = lerp((q * q)[:, None], base, metal[:, None])
+    fc = pow5(1.0 - v_h)
+    fr = saturate(50.0 * f0[:, 1])[:, None] * fc[:, None] + (1.0 - fc)[:, None] * f0           # F_Schlick, :123-129
+    return dict(NdotV=n_v, NdotL=n_l, NdotH=n_h, VdotH=v_h, LdotH=l_h, F0=f0, kD=1.0 - metal, F=fr)
+
+
+def direct_light(n_, v_, l_, base, rough, metal, ior, radiance, mutation=None):
+    """PrepareLightingByproducts + EvaluateDirectLight (CommonLighting.hlsli:360-375) before the shadow factor: (diffuse, specular)."""
+    p = byproducts(n_, v_, l_, base, metal, ior)
+    n_l, n_v, l_h, n_h = p["NdotL"], p["NdotV"], p["LdotH"], p["NdotH"]
+    fl, fv = pow5(1.0 - n_l), pow5(1.0 - n_v)
+    fd90 = (0.0 if mutation == "fd90_without_half" else 0.5) + 2.0 * (rough * rough) * l_h * l_h
+    fd = lerp(1.0, fd90, fl) * lerp(1.0, fd90, fv)
+    burley = np.where((n_l <= 0.0) | (n_v <= 0.0), 0.0, fd * n_l / PI)
+    diffuse = (burley * p["kD"])[:, None] * base
+    alpha = rough * rough
+    alpha2 = alpha * alpha
+    denom = n_h * n_h * (alpha2 - 1.0) + 1.0
+    d_ggx = alpha2 / (PI * denom * denom)
+    g1 = n_v * np.sqrt(alpha2 + (1.0 - alpha2) * n_l * n_l)
+    g2 = n_l * np.sqrt(alpha2 + (1.0 - alpha2) * n_v * n_v)
+    g = 0.5 / np.maximum(g1 + g2, c32(1e-6))
+    spec = p["F"] * (d_ggx * g)[:, None]
+    return diffuse * radiance, spec * n_l[:, None] * radiance
+
+
+# ---------------------------------------------------------------------------------------------------------------- the path
+class Paths:
+    """What trace_paths returns: radiance float64 [n, 3], margin float64 [n], took {branch: bool [n]}."""
+
+    def __init__(self, radiance, margin, took):
+        self.radiance, self.margin, self.took = radiance, margin, took
+
+    def included(self, delta=None):
+        return self.margin >= (DELTA if delta is None else delta)
+
+
+def _low(margin, live, value):
+    margin[:] = np.where(live, np.minimum(margin, np.abs(value)), margin)
+
+
+def trace_paths(ps, cb, rays, mutation=None):
+    with np.errstate(all="ignore"):                                        # lanes that are masked out carry anything
+        return _trace_paths(ps, cb, rays, mutation)
+
+
+def _trace_paths(ps, cb, rays, mutation):
+    """The radiance along every record of `rays` (structs.Ray: origin, unit direction, tmin, RNG state) by PathTracer.hlsl:74-329, with
+    the frame constants m_SunDirection, m_CosSunAngularRadius, m_LightCount and m_MaxBounces of `cb`."""
+    assert mutation is None or mutation in MUTATIONS
+    scene = ps.scene
+    n = len(rays)
+    o, d = np.asarray(rays["origin"], F).reshape(n, 3).copy(), np.asarray(rays["direction"], F).reshape(n, 3).copy()
+    tmin = np.asarray(rays["tmin"], F).copy()
+    rng = Rng(rays["rng"])
+    sun_dir = np.asarray(cb["m_SunDirection"], F).reshape(1, 3)
+    cos_sun = F(cb["m_CosSunAngularRadius"])
+    lights = scene.lights[:int(cb["m_LightCount"])]
+    sun_intensity = F(scene.lights[0]["m_Intensity"])                  # g_Lights[0], whatever its type (PathTracer.hlsl:137, :323)
+    thr, rad = np.ones((n, 3)), np.zeros((n, 3))
+    in_vol, int_ior = np.zeros(n, bool), np.ones(n)
+    int_sa, int_ss = np.zeros((n, 3)), np.zeros((n, 3))
+    alive = np.ones(n, bool)
+    margin = np.full(n, INF)
+    took = {b: np.zeros(n, bool) for b in BRANCHES}
+    sun_vec = np.broadcast_to(sun_dir, (n, 3))
+
+    for bounce in range(int(cb["m_MaxBounces"])):
+        if not alive.any():
+            break
+        hit, tri, t, u, v = ps.trace_standard(o, d, tmin, rng, alive, margin, took)
+        # ---- miss (:315-328)
+        miss = alive & ~hit
+        if miss.any():
+            disk = bounce == 0 or mutation == "sun_disk_on_later_misses"
+            sky = A.rt_sky_radiance(ps.t16, ps.s16, o[miss], d[miss], sun_dir, sun_intensity, disk)
+            rad[miss] += thr[miss] * sky
+            took["sky miss at bounce 0" if bounce == 0 else "sky miss later"] |= miss
+            if bounce == 0:
+                nu = dot(d, sun_vec) - math.cos(A.SUN_ANGULAR_RADIUS)
+                _low(margin, miss, nu)
+                took["sun disk seen"] |= miss & (nu > 0.0)
+        alive = alive & hit
+        if not alive.any():
+            break
+        live = alive.copy()
+        mat = ps.mat_of[tri]
+        # ---- Beer-Lambert over the segment (:96-100)
+        seg = live & in_vol
+        with np.errstate(all="ignore"):
+            thr = np.where(seg[:, None], thr * np.exp(-(int_sa + int_ss) * t[:, None]), thr)
+        took["Beer-Lambert applied"] |= seg
+        # ---- attributes (:102-117)
+        X = o + d * t[:, None]
+        uv = ps.uv_at(tri, u, v)
+        base, alpha, rough, metal, emissive = ps.pbr(mat, uv)
+        ng = ps.normal_at(tri, u, v)
+        N, V = ng.copy(), -d
+        facing = dot(ng, d)
+        _low(margin, live, facing)
+        front = facing < 0.0
+        took["back-face hit"] |= live & ~front
+        N = np.where((dot(N, V) < 0.0)[:, None], -N, N)
+        ior = ps.ior[mat]
+        zero = np.zeros((n, 3))
+        pre = byproducts(N, V, zero, base, metal, ior)                  # inputs.L = 0 (:122, :142)
+
+        # ---- transmission (:149-255)
+        tb = live & ((ps.transmission[mat] > 0.0) | (ps.mode[mat] == S.ALPHA_MODE_BLEND))
+        go = np.zeros(n, bool)
+        if tb.any():
+            eff_alpha = np.where(ps.mode[mat] == S.ALPHA_MODE_BLEND, alpha, 1.0)
+            tf = np.maximum(ps.transmission[mat], 1.0 - eff_alpha)
+            mat_ior = np.maximum(ior, c32(1.0001))
+            outside = np.where(in_vol, int_ior, 1.0)
+            eta_f = np.where(front, outside / mat_ior, mat_ior / outside)
+            thin = ps.thin[mat]
+            eta_r = np.where(thin, 1.0, eta_f)
+            cos_i = np.maximum(dot(N, V), 0.0)
+            fres, _, s2 = fresnel_dielectric(eta_r if mutation == "fresnel_with_eta_refract" else eta_f, cos_i)
+            _low(margin, tb, s2 - 1.0)
+            # Total internal reflection at the geometry normal makes F = 1 and probT = 0: the path falls back to reflection. The
+            # `reflect` fallbacks of :180-181 and :204-205 cannot be reached: the delta form refracts about the same N and eta that gave
+            # probT = 0, and the rough form's vector has length eta * sqrt(1 - VdotH^2) >= 1 under TIR, never below 1e-8.
+            took["TIR fallback"] |= tb & (s2 >= 1.0)
+            prob_t = saturate((1.0 - fres) * tf)
+            x = rng.next(tb)
+            _low(margin, tb, x - prob_t)
+            go = tb & (x < prob_t)
+            took["reflection fallback at a transmissive surface"] |= tb & ~go
+            delta = go & (rough <= c32(0.08))
+            rgh = go & ~delta
+            new_d, weight = np.zeros((n, 3)), np.zeros((n, 3))
+            if delta.any():
+                cosn = dot(N, d)                                             # refract(ray.Direction, N, etaRefract), :179
+                k = 1.0 - eta_r * eta_r * (1.0 - cosn * cosn)
+                _low(margin, delta & (eta_r != 1.0), k)
+                with np.errstate(all="ignore"):
+                    refr = np.where((k < 0.0)[:, None], 0.0, eta_r[:, None] * d - (eta_r * cosn + np.sqrt(np.maximum(k, 0.0)))[:, None] * N)
+                tir = dot(refr, refr) < c32(1e-8)
+                took["TIR fallback"] |= delta & tir
+                refr = np.where(tir[:, None], d - 2.0 * cosn[:, None] * N, refr)
+                new_d = np.where(delta[:, None], refr, new_d)
+                weight = np.where(delta[:, None], base, weight)
+                took["delta transmission"] |= delta
+            if rgh.any():
+                ux = rng.next(rgh); uy = rng.next(rgh)
+                H = sample_ggx_vndf(ux, uy, N, V, rough, margin, rgh)
+                v_h = saturate(dot(V, H))
+                f_mf, _, s2m = fresnel_dielectric(eta_f, v_h)
+                _, cos_t_dir, s2d = fresnel_dielectric(eta_r, v_h)
+                _low(margin, rgh, s2m - 1.0)
+                _low(margin, rgh & (eta_r != 1.0), s2d - 1.0)
+                refr = (eta_r * v_h - cos_t_dir)[:, None] * H - eta_r[:, None] * V
+                tir = dot(refr, refr) < c32(1e-8)
+                took["TIR fallback"] |= rgh & (tir | (s2d >= 1.0) | (s2m >= 1.0))
+                refr = np.where(tir[:, None], d - 2.0 * dot(H, d)[:, None] * H, refr)
+                with np.errstate(all="ignore"):
+                    refr = normalize(refr)
+                a_ = rough * rough
+                a2 = a_ * a_
+                n_lt = np.abs(dot(N, refr))
+                with np.errstate(all="ignore"):
+                    g1t = np.where(n_lt > K_EPSILON, 2.0 * n_lt / (n_lt + np.sqrt(a2 + (1.0 - a2) * n_lt * n_lt)), 0.0)
+                new_d = np.where(rgh[:, None], refr, new_d)
+                weight = np.where(rgh[:, None], base * ((1.0 - f_mf) * g1t * n_lt)[:, None], weight)
+                took["rough transmission"] |= rgh
+            thr = np.where(go[:, None], thr * weight, thr)
+            enter, leave = go & ~thin & front, go & ~thin & ~front
+            took["medium entered"] |= enter
+            took["medium left"] |= leave
+            if mutation == "medium_not_cleared":
+                leave = np.zeros(n, bool)
+            in_vol = np.where(enter, True, np.where(leave, False, in_vol))
+            int_ior = np.where(enter, mat_ior, np.where(leave, 1.0, int_ior))
+            int_sa = np.where(enter[:, None], ps.sigma_a[mat], np.where(leave[:, None], 0.0, int_sa))
+            int_ss = np.where(enter[:, None], ps.sigma_s[mat], np.where(leave[:, None], 0.0, int_ss))
+            o = np.where(go[:, None], X - N * c32(0.001), o)
+            with np.errstate(all="ignore"):
+                d = np.where(go[:, None], normalize(new_d), d)
+            tmin = np.where(go, c32(1e-4), tmin)
+            live = live & ~go                                                # `continue`
+
+        # ---- emissive and direct light (:257-261)
+        rad = np.where(live[:, None], rad + thr * emissive, rad)
+        diffuse, specular = np.zeros((n, 3)), np.zeros((n, 3))
+        sun_rad = None
+        for l in lights:
+            kind = int(l["m_Type"])
+            reach = live.copy()
+            if kind == S.LIGHT_DIRECTIONAL:
+                ndl = dot(N, sun_vec)
+                _low(margin, reach, ndl)
+                reach &= ~(ndl <= 0.0)
+                if sun_rad is None:
+                    sun_rad = np.zeros((n, 3))
+                    if live.any():
+                        sun_rad[live] = A.rt_sun_radiance(ps.t16, X[live], sun_dir, sun_intensity)
+                radiance = sun_rad
+                pos_culled = live & ~reach
+                ux = rng.next(reach); uy = rng.next(reach)
+                Ls = sample_cone(sun_vec, cos_sun, ux, uy, margin, reach)
+                max_dist = np.full(n, c32(1e10))
+            elif kind in (S.LIGHT_POINT, S.LIGHT_SPOT):
+                if not F(l["m_Intensity"]) > 0.0:
+                    reach[:] = False
+                to_light = np.asarray(l["m_Position"], F) - X
+                dist_sq = dot(to_light, to_light)
+                range_ = F(l["m_Range"])
+                if range_ > 0.0:
+                    _low(margin, reach, dist_sq / (range_ * range_) - 1.0)
+                    out = reach & (dist_sq > range_ * range_)
+                    if kind == S.LIGHT_POINT:
+                        took["point light range-culled"] |= out
+                    reach &= ~out
+                dist = np.sqrt(dist_sq)
+                att = 1.0 / (dist_sq + 1.0)
+                if range_ > 0.0:
+                    q = dist / range_
+                    sa = saturate(1.0 - q * q * q * q)
+                    att = att * (sa * sa)
+                radiance = np.asarray(l["m_Color"], F) * F(l["m_Intensity"]) * att[:, None]
+                if kind == S.LIGHT_SPOT:
+                    Lc = to_light / dist[:, None]
+                    ndl = dot(N, Lc)
+                    _low(margin, reach, ndl)
+                    reach &= ~(ndl <= 0.0)
+                    light_dir = normalize(np.asarray(l["m_Direction"], F))
+                    cos_theta = dot(-Lc, light_dir[None])
+                    cos_outer, cos_inner = math.cos(float(l["m_SpotOuterConeAngle"])), math.cos(float(l["m_SpotInnerConeAngle"]))
+                    _low(margin, reach, cos_theta - cos_outer)
+                    took["spot cone-culled"] |= reach & (cos_theta < cos_outer)
+                    reach &= ~(cos_theta < cos_outer)
+                    spot = saturate((cos_theta - cos_outer) / (cos_inner - cos_outer))
+                    radiance = np.asarray(l["m_Color"], F) * F(l["m_Intensity"]) * spot[:, None] * att[:, None]
+                pos_culled = live & ~reach
+                ux = rng.next(reach); uy = rng.next(reach)
+                cos_t = 1.0 - 2.0 * ux
+                sin_t = np.sqrt(np.maximum(0.0, 1.0 - cos_t * cos_t))
+                phi = TWO_PI * uy
+                sphere = np.stack([sin_t * np.cos(phi), cos_t, sin_t * np.sin(phi)], -1)
+                to_sample = (np.asarray(l["m_Position"], F) + sphere * F(l["m_Radius"])) - X
+                max_dist = np.sqrt(dot(to_sample, to_sample))
+                Ls = to_sample / max_dist[:, None]
+            else:
+                continue
+            if mutation == "draw_after_culled_light":
+                rng.next(pos_culled)
+            ndl = dot(N, Ls)
+            _low(margin, reach, ndl)
+            reach &= ~(ndl <= 0.0)
+            if not reach.any():
+                continue
+            shadow = ps.shadow(X, Ls, max_dist, reach, margin, took, mutation)
+            dif, spec = direct_light(N, V, Ls, base, rough, metal, ior, radiance, mutation)
+            diffuse = np.where(reach[:, None], diffuse + dif * shadow[:, None], diffuse)
+            specular = np.where(reach[:, None], specular + spec * shadow[:, None], specular)
+            lit = reach & (shadow > 0.0)
+            took["filtered shadow strictly between 0 and 1"] |= lit & (shadow < 1.0)
+            if kind == S.LIGHT_DIRECTIONAL:
+                took["sun lit"] |= lit
+                took["sun occluded"] |= reach & ~lit
+            elif kind == S.LIGHT_POINT:
+                took["point light lit"] |= lit
+            else:
+                took["spot lit"] |= lit
+        keep_spec = bounce == 0 or mutation == "specular_direct_kept"
+        rad = np.where(live[:, None], rad + thr * (diffuse + (specular if keep_spec else 0.0)), rad)
+
+        # ---- Russian roulette (:263-270)
+        if bounce >= (1 if mutation == "roulette_from_bounce_1" else 2):
+            p_go = saturate(thr.max(1))
+            x = rng.next(live)
+            _low(margin, live, x - p_go)
+            kill = live & (x > p_go)
+            took["roulette kill"] |= kill
+            took["roulette survive"] |= live & ~kill
+            live = live & ~kill
+            with np.errstate(all="ignore"):
+                thr = np.where(live[:, None], thr / p_go[:, None], thr)
+
+        # ---- lobe pick and sample (:272-301)
+        spec_prob = np.clip(lerp(pre["F"][:, 0] * 0.5 + 0.5 * metal, 1.0, metal), c32(0.1), c32(0.9))
+        x = rng.next(live)
+        _low(margin, live, x - spec_prob)
+        ls, ld = live & (x < spec_prob), live & ~(x < spec_prob)
+        new_d, weight = np.zeros((n, 3)), np.zeros((n, 3))
+        if ls.any():
+            ux = rng.next(ls); uy = rng.next(ls)
+            if mutation == "vndf_u_swapped":
+                ux, uy = uy, ux
+            H = sample_ggx_vndf(ux, uy, N, V, rough, margin, ls)
+            nd = -V + 2.0 * dot(V, H)[:, None] * H                          # reflect(-V, H)
+            a_ = rough * rough
+            a2 = a_ * a_
+            n_v, n_l, v_h = saturate(dot(N, V)), saturate(dot(N, nd)), saturate(dot(V, H))
+            fc = pow5(1.0 - v_h)
+            fr = saturate(50.0 * pre["F0"][:, 1])[:, None] * fc[:, None] + (1.0 - fc)[:, None] * pre["F0"]
+            g = n_v if mutation == "g1_ndotv" else n_l
+            with np.errstate(all="ignore"):
+                g1l = 2.0 * g / (g + np.sqrt(a2 + (1.0 - a2) * g * g))
+                w = np.where(((n_v <= 0.0) | (n_l <= 0.0))[:, None], 0.0, fr * g1l[:, None])
+                if mutation != "spec_weight_without_prob":
+                    w = w / spec_prob[:, None]
+            new_d = np.where(ls[:, None], nd, new_d)
+            weight = np.where(ls[:, None], w, weight)
+            took["specular lobe"] |= ls
+        if ld.any():
+            ux = rng.next(ld); uy = rng.next(ld)
+            nd = sample_hemisphere_cosine(ux, uy, N, margin, ld)
+            w = base * (1.0 - metal)[:, None] / (spec_prob if mutation == "diffuse_weight_by_spec_prob" else 1.0 - spec_prob)[:, None]
+            new_d = np.where(ld[:, None], nd, new_d)
+            weight = np.where(ld[:, None], w, weight)
+            took["diffuse lobe"] |= ld
+        below = dot(N, new_d)
+        _low(margin, live, below)
+        rejected = live & (below <= 0.0)
+        took["lobe rejected below the horizon"] |= rejected
+        live = live & ~rejected
+        thr = np.where(live[:, None], thr * weight, thr)
+        # ---- bail-out (:305-307)
+        top = thr.max(1)
+        _low(margin, live, top / c32(0.01) - 1.0)
+        bail = live & (top < c32(0.01))
+        took["bail-out"] |= bail
+        live = live & ~bail
+        # ---- advance (:309-313)
+        o = np.where(live[:, None], X, o)
+        d = np.where(live[:, None], new_d, d)
+        tmin = np.where(live, c32(1e-4), tmin)
+        alive = live | go
+    return Paths(rad, margin, took)
+
+
+def concatenate(parts):
+    """Several Paths as one."""
+    return Paths(np.concatenate([p.radiance for p in parts]), np.concatenate([p.margin for p in parts]),
+                 {b: np.concatenate([p.took[b] for p in parts]) for b in BRANCHES})
+
+
+def path_error(got, paths):
+    """max_c |got - ref| / max(|ref|_inf, 1e-3 * Lmax) per path. Lmax is the largest reference radiance of `paths` (all paths of a case)
+    that does not look into the sun's disk: the disk is 2e4 times brighter than anything else, and with it in Lmax the floor of the
+    denominator would sit above every other radiance of the open-sky case. Leaving it out only makes the check stricter."""
+    got, ref = np.asarray(got, F)[:, :3], paths.radiance
+    lmax = np.abs(ref[~paths.took["sun disk seen"]]).max()
+    return np.abs(got - ref).max(1) / np.maximum(np.abs(ref).max(1), 1e-3 * lmax)
