@@ -89,6 +89,9 @@ def test_delta_and_tau_are_what_the_oracle_measures(luts):
         worst = max(worst, float(err[inc].max()))
         recorded = R.CASE_TABLE[name]
         assert err[inc].max() <= 1.05 * recorded[0] and abs((1 - own_inc.mean()) - recorded[1]) < 2e-3, (name, err[inc].max(), 1 - own_inc.mean())
+        # to the printed digits: the numbers were recorded with vertices from the oracle's unpacking and attributes computed here; they
+        # now come from surface_reference.py, and the swap must move nothing
+        assert f"{err[inc].max():.3e}" == f"{recorded[0]:.3e}" and f"{1 - own_inc.mean():.4f}" == f"{recorded[1]:.4f}", (name, err[inc].max(), 1 - own_inc.mean())
     print(f"  largest margin of a deviating path {flip:.6e}; worst included error {worst:.6e}")
     assert flip > 0.0, "no flip observed: the measurement set no longer holds the one that fixed DELTA"
     assert 2.0 ** math.ceil(math.log2(8.0 * flip)) == R.DELTA and abs(flip - R.DELTA_WORST_FLIPPED_MARGIN) <= 1e-3 * flip
@@ -126,9 +129,12 @@ def test_the_sun_is_occluded_everywhere_in_the_closed_room(luts, name):
 def test_material_thresholds_are_far(luts):
     for name in PC.NAMES:
         ps = _measured(luts, name)["ps"]
-        uv = np.zeros((len(ps.rough), 2))
-        rough = ps.pbr(np.arange(len(ps.rough)), uv)[2]                 # asserts by itself; 1 x 1 textures make uv immaterial
+        n = len(ps.rough)
+        axis = lambda k: np.tile(np.eye(3)[k], (n, 1))                   # noqa: E731
+        attr = dict(uv=np.zeros((n, 2)), world_normal=axis(2), world_tangent=axis(0), tangent_sign=np.ones(n))
+        rough, margin = ps.pbr(np.arange(n), attr)[2::4]                # asserts by itself; 1 x 1 textures make uv immaterial
         assert (np.abs(rough - R.c32(0.08)) > 1e-3).all()
+        assert (margin > 1e-3 / 0.04).all()                             # the 0.04 floor, |roughness / 0.04 - 1|
 
 
 # ---------------------------------------------------------------- mutations
