@@ -78,6 +78,10 @@ struct StageImages {
     DeviceBuffer<float4> dRestirKeys[2];
     DeviceBuffer<HrptRay> dRestirRays; DeviceBuffer<HrptRayHit> dRestirHits;
     int restirCur = 0; bool restirValid = false;
+    // radiance cache (hrpt_rcache_indirect): the served plane, and the surface, cached-radiance and voxel-size records of one call (its ray and
+    // radiance records are dIndirectRays / dIndirectRadiance)
+    DeviceBuffer<float4> dRcacheServed, dRcacheCached;
+    DeviceBuffer<HrptRcacheSurface> dRcacheSurfaces; DeviceBuffer<float> dRcacheVoxel;
 };
 
 // Images of width * height float4. The members named here are the ones hrpt_resize makes again at the new size, zeroed and without

@@ -211,6 +211,34 @@ void restir_spatial_host(const HrptRestirImages& images, uint32_t width, uint32_
 void restir_shade_host(const HrptRestirImages& images, uint32_t width, uint32_t height, const HrptPathTracerConstants& constants, const HrptGPULight* lights,
                        const HrptRestirParams& params, const float* sunRadiance, const float* sky, const HrptRestirReservoir* final, const float* visibility, int nthreads);
 
+// Hash-grid radiance cache (pt_rcache.hip; arithmetic in pt_rcache.h): the four table kernels over three device arrays of 2^capacityLog2
+// entries and the drop counter, and the glue of the two frame calls. query reads `count` records of recordBytes (32: HrptRcachePoint, 48:
+// HrptRcacheSurface; position in floats 0..2, normal in floats 4..6). update_rays writes one diffuse record per sparse block, row-major over
+// the blocks; serve writes the served plane and overwrites the records of served pixels; apply copies served texels over the diffuse plane.
+// Every pointer in device memory, 16-byte aligned. rcache_*_host (pt_rcache_host.cpp): the table stages on host threads.
+// launch_surface_rays (pt_megakernel.hip): position, facing geometric normal, t and RNG state at the closest hit of each ray.
+bool rcache_desc_valid(const HrptRcacheDesc& desc);
+hipError_t launch_surface_rays(const SceneView& scene, const HrptRay* rays, HrptRcacheSurface* surfaces, uint64_t count, hipStream_t stream);
+hipError_t launch_rcache_insert(const HrptRcacheDesc& desc, const float* cameraPos, uint64_t* keys, HrptRcacheAccum* accum, uint64_t* drops,
+                                const HrptRcacheSample* samples, uint64_t count, bool waveCombine, hipStream_t stream);
+hipError_t launch_rcache_resolve(const HrptRcacheDesc& desc, uint64_t* keys, HrptRcacheAccum* accum, HrptRcacheEntry* resolved, hipStream_t stream);
+hipError_t launch_rcache_query(const HrptRcacheDesc& desc, const float* cameraPos, const uint64_t* keys, const HrptRcacheEntry* resolved, const void* records,
+                               uint32_t recordBytes, float* out4, float* voxelOut, uint64_t count, hipStream_t stream);
+hipError_t launch_rcache_clear(const HrptRcacheDesc& desc, uint64_t* keys, HrptRcacheAccum* accum, HrptRcacheEntry* resolved, uint64_t* drops, hipStream_t stream);
+hipError_t launch_rcache_update_rays(const indirect::Frame& frame, const HrptRcacheDesc& desc, uint32_t frameIndex, const float* normal, const float* geoNormal,
+                                     const float* depth, HrptRay* rays, hipStream_t stream);
+hipError_t launch_rcache_gather_samples(const HrptRcacheSurface* surfaces, const float4* radiance, HrptRcacheSample* samples, uint64_t count, hipStream_t stream);
+hipError_t launch_rcache_serve(const HrptRcacheSurface* surfaces, const float4* cached, const float* voxel, float4* servedOut, HrptRay* rays, uint64_t count,
+                               hipStream_t stream);
+hipError_t launch_rcache_apply(const float4* servedPlane, float4* diffuse, uint64_t count, hipStream_t stream);
+void rcache_insert_host(const HrptRcacheDesc& desc, const float* cameraPos, uint64_t* keys, HrptRcacheAccum* accum, uint64_t* drops, const HrptRcacheSample* samples,
+                        uint64_t count, int nthreads);
+void rcache_resolve_host(const HrptRcacheDesc& desc, uint64_t* keys, HrptRcacheAccum* accum, HrptRcacheEntry* resolved, int nthreads);
+void rcache_query_host(const HrptRcacheDesc& desc, const float* cameraPos, const uint64_t* keys, const HrptRcacheEntry* resolved, const HrptRcachePoint* points,
+                       float* out4, float* voxelOut, uint64_t count, int nthreads);
+// nullptr when the table keeps the invariant of pt_rcache.h, else what breaks it
+const char* rcache_table_fault(const HrptRcacheDesc& desc, const uint64_t* keys, const HrptRcacheAccum* accum, const HrptRcacheEntry* resolved);
+
 // Vertex quantiser (pt_deform.hip; arithmetic in pt_deform.h): out[i] = the 24-byte scene-format record of the float vertex in[i], both in
 // device memory (in 16-byte aligned); *flag (device, may be null) is set to 1 when a position is not finite. quantize_vertices_host
 // (pt_deform_host.cpp): the same arithmetic on host threads; returns whether every position is finite.

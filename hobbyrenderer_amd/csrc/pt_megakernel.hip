@@ -1,7 +1,8 @@
 // pt_megakernel.hip -- the thread-per-query kernels: one thread walks the tree with a private stack for one pixel or one ray. pt_megakernel
 // runs the whole of PathTracer_CSMain (/root/reference/src/shaders/PathTracer.hlsl:53-340) for one accumulation index, exactly like one
 // dispatch of the reference (8x8 groups -> here 64-lane waves over 8x8 pixel tiles); pt_radiance_kernel runs its bounce loop from a caller's
-// ray, pt_gbuffer_kernel and pt_motion_kernel stop at the first hit, pt_trace_rays_kernel answers stand-alone ray queries. They exist to
+// ray, pt_gbuffer_kernel and pt_motion_kernel stop at the first hit, pt_trace_rays_kernel answers stand-alone ray queries and pt_surface_rays_kernel
+// adds position and geometric normal to them (the radiance cache's surface query). They exist to
 // prove struct layouts, RNG streams, LUT sampling, the BVH and the shading stages bit-for-bit against the CPU
 // oracle; the wavefront pipeline (pt_wavefront.hip) is the production path and reuses the same stages.
 #include <type_traits>
@@ -258,6 +259,44 @@ hipError_t launch_trace_rays(const SceneView& scene, const HrptRay* rays, HrptRa
     with_tree_of(scene, [&](auto tl) {
         if (shadow) hipLaunchKernelGGL((pt_trace_rays_kernel<true, decltype(tl)::value>), grid, dim3(256), 0, stream, scene, rays, hits, count);
         else hipLaunchKernelGGL((pt_trace_rays_kernel<false, decltype(tl)::value>), grid, dim3(256), 0, stream, scene, rays, hits, count);
+    });
+    return hipGetLastError();
+}
+
+// Where rays land, for the radiance cache (hrpt_rcache_surfaces_device): pt_trace_rays_kernel's closest-hit query, then the terms gbuffer_texels
+// forms of the hit (pt_gbuffer.h:36-38): position o + d * t and Ng = normalize(worldNormal), here turned to face the ray. One thread per ray.
+template <bool TL>
+__global__ __launch_bounds__(256) void pt_surface_rays_kernel(SceneView s, const HrptRay* __restrict__ rays, float4* __restrict__ surfaces, uint64_t count)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    HrptRay r = rays[i];
+    float4 row0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), row1 = row0;
+    uint32_t rng = r.rng;
+    Ray ray; load_ray(r, ray); ray.tmax = r.tmax;
+    if (all_finite(ray.o, ray.d)) {
+        const auto bvh = GlobalBvhOf<tree_key<TL>>::make(s);
+        PrivateStack stack;
+        Hit hit;
+        if (trace_standard(s, bvh, ray, rng, stack, hit)) {
+            const TriVerts tv = load_hit_attr(s, hit);
+            const SurfaceAttr attr = full_hit_attributes(s, hit, ray, tv, s.instShade[tv.inst], false);
+            f3 Ng = normalize(attr.worldNormal);
+            if (dot(Ng, ray.d) > 0.0f) Ng = -Ng;
+            const f3 X = ray.o + ray.d * hit.t;
+            row0 = make_float4(X.x, X.y, X.z, hit.t);
+            row1 = make_float4(Ng.x, Ng.y, Ng.z, __uint_as_float(1u));
+        }
+    }
+    surfaces[i * 3] = row0; surfaces[i * 3 + 1] = row1;
+    surfaces[i * 3 + 2] = make_float4(__uint_as_float(rng), 0.0f, 0.0f, 0.0f);
+}
+hipError_t launch_surface_rays(const SceneView& scene, const HrptRay* rays, HrptRcacheSurface* surfaces, uint64_t count, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    dim3 grid((unsigned)((count + 255) / 256));
+    with_tree_of(scene, [&](auto tl) {
+        hipLaunchKernelGGL(pt_surface_rays_kernel<decltype(tl)::value>, grid, dim3(256), 0, stream, scene, rays, reinterpret_cast<float4*>(surfaces), count);
     });
     return hipGetLastError();
 }

@@ -12,4 +12,5 @@ from .lighting import (deferred_rays_host, deferred_shade_host, indirect_compose
 from .post import (bloom_host, bloom_pack_probe, compose_host, demodulate_host, denoise_host, modulation_probe, noise_tile_from_png,  # noqa: F401
                    temporal_host, upscale_host)
 from .probes import ProbeVolume, probe_points, probe_volume, probes_blend_host, probes_query_host, probes_rays_host  # noqa: F401
+from .rcache import RadianceCache, rcache_desc, rcache_insert_host, rcache_query_host, rcache_resolve_host, rcache_table  # noqa: F401
 from .selftest import host_build_bvh  # noqa: F401

@@ -11,6 +11,7 @@ from .lighting import LightingCalls
 from .post import PostCalls
 from .probes import ProbeCalls
 from .queries import QueryCalls
+from .rcache import RcacheCalls
 from .selftest import SelftestCalls
 
 declare("hrpt_create", [C.POINTER(S.DeviceDesc), C.POINTER(C.c_void_p)])
@@ -51,7 +52,7 @@ def allgather(contexts):
         raise HrptError(rc, lib.hrpt_last_error(contexts[0]._h).decode() if contexts else "hrpt_allgather")
 
 
-class PathTracerContext(QueryCalls, GeometryCalls, PostCalls, ProbeCalls, LightingCalls, SelftestCalls):
+class PathTracerContext(QueryCalls, GeometryCalls, PostCalls, ProbeCalls, LightingCalls, RcacheCalls, SelftestCalls):
     """One context = one GPU = one stream (include/hobbyrt_pt.h)."""
 
     def __init__(self, device=0):

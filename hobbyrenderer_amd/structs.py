@@ -336,6 +336,26 @@ class RestirImages(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "geoNormal", "emissive", "depth", "motion", "reservoirIn", "keyIn", "reservoirOut", "keyOut", "colorOut")]
 
 
+# hash-grid radiance cache (hrpt_rcache_*)
+RCACHE_RESET, RCACHE_NO_FALLBACK, RCACHE_NO_WAVE_COMBINE = 1, 2, 4
+RcacheDesc = np.dtype([("capacityLog2", u32), ("sceneScale", f32), ("levelBias", f32), ("radianceScale", f32), ("maxSamples", u32), ("staleFramesMax", u32),
+                       ("sparseBlock", u32), ("roughnessThreshold", f32)])                                                                  # HrptRcacheDesc, 32 B
+RcacheAccum = np.dtype([("r", np.uint64), ("g", np.uint64), ("b", np.uint64), ("count", u32), ("pad", u32)])                               # HrptRcacheAccum, 32 B
+RcacheEntry = np.dtype([("r", f32), ("g", f32), ("b", f32), ("meta", u32)])                                    # HrptRcacheEntry, 16 B; meta = samples | stale << 16
+RcacheSample = np.dtype([("position", f32, 3), ("valid", f32), ("normal", f32, 3), ("pad0", f32), ("radiance", f32, 3), ("pad1", f32)])    # HrptRcacheSample, 48 B
+RcachePoint = np.dtype([("position", f32, 3), ("pad0", f32), ("normal", f32, 3), ("pad1", f32)])                                           # HrptRcachePoint, 32 B
+RcacheSurface = np.dtype([("position", f32, 3), ("t", f32), ("normal", f32, 3), ("hit", u32), ("rng", u32), ("pad", u32, 3)])              # HrptRcacheSurface, 48 B
+assert (RcacheDesc.itemsize, RcacheAccum.itemsize, RcacheEntry.itemsize, RcacheSample.itemsize, RcachePoint.itemsize, RcacheSurface.itemsize) == (32, 32, 16, 48, 32, 48)
+
+
+class RcacheParams(C.Structure):
+    """HrptRcacheParams. flags: RCACHE_NO_FALLBACK leaves pixels the cache does not serve at zero instead of tracing their path."""
+    _fields_ = [("flags", C.c_uint32), ("frameSeed", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, flags=0, frameSeed=0):
+        super().__init__(flags, frameSeed)
+
+
 class BuildInfo(C.Structure):      # HrptBuildInfo, 64 B
     _fields_ = [("requestedBuilder", C.c_uint32), ("usedBuilder", C.c_uint32), ("buildMs", C.c_float), ("deviceBuildMs", C.c_float),
                 ("triangleCount", C.c_uint32), ("nodeCount", C.c_uint32), ("node4Count", C.c_uint32), ("maxDepth", C.c_uint32),

@@ -1303,6 +1303,111 @@ int  hrpt_restir_shade_host(const HrptRestirImages* images, uint32_t width, uint
                             const HrptGPULight* lights, const HrptRestirParams* params, const float* sunRadiance, const float* sky,
                             const HrptRestirReservoir* final, const float* visibility, int nthreads);
 
+/* ---- world-space hash-grid radiance cache ----------------------------------------------------------------------------------------------
+ * Ends the diffuse indirect path after one segment: a sparse set of pixels (one per sparseBlock x sparseBlock block) feeds path-traced
+ * radiance into a spatial hash table each frame, and every pixel then traces one cosine ray and reads the radiance at its hit point from the
+ * table. The counterpart of the reference's SHARCUpdate.hlsl, SharcResolve.hlsl and SHARCQuery.hlsl; the SDK headers behind them are not in
+ * the reference tree, so the stage is DEFINED by this project after the published description. Additive; HRPT_ABI_VERSION stays 3.
+ * One source for kernels and host executors: hobbyrenderer_amd/csrc/pt_rcache.h; DESIGN.md section 32 has every operation in order.
+ * Not here: parity with the SDK's packing and constants, cache resampling and the four-vertex back-propagation (the value stored is the path
+ * tracer's full estimate along the ray, so the cache has no feedback from its own last state and no energy clamp), re-levelling entries when
+ * the camera moves (entries of a changed level go stale and are rebuilt), a specular lookup, sharding the table over several GPUs, the C++
+ * plugin mirror and a wavefront route for the surface query.
+ *
+ * Table. capacity = 2^capacityLog2 entries in three arrays: keys (uint64, 0 = empty), accumulation (HrptRcacheAccum: the integer sums of
+ * one frame) and resolved (HrptRcacheEntry: the running mean; meta = samples | stale << 16). For a point p with normal n and camera c:
+ * level = clamp(floor(0.5 * log2(max(|p - c|^2, FLT_MIN)) + levelBias), 1, 1023), voxel = exp2(level) / (sceneScale * exp2(levelBias)),
+ * grid = floor(p / voxel) per component (17 bits each, two's complement, wrapped), key = gx | gy << 17 | gz << 34 | level << 51 |
+ * octant << 61 with octant bit k = (n[k] >= 0). Its bucket is the 32 consecutive entries at (pcg(lo + pcg(hi)) mod (capacity / 32)) * 32;
+ * the occupied slots of a bucket are always a prefix of it. Valid desc: capacityLog2 10..26; sceneScale and radianceScale finite and > 0;
+ * levelBias in [-64, 64]; maxSamples 1..65535; staleFramesMax <= 65534; sparseBlock 1..16; roughnessThreshold finite. The reference's
+ * constants: 22, 50, 0, 1e3, 60, 64, 5, 0.1. */
+typedef struct HrptRcacheDesc {
+    uint32_t capacityLog2;
+    float sceneScale, levelBias, radianceScale;
+    uint32_t maxSamples, staleFramesMax, sparseBlock;
+    float roughnessThreshold;
+} HrptRcacheDesc;                                                                                                          /* 32 B */
+typedef struct HrptRcacheAccum { uint64_t r, g, b; uint32_t count; uint32_t pad; } HrptRcacheAccum;                       /* 32 B */
+typedef struct HrptRcacheEntry { float r, g, b; uint32_t meta; } HrptRcacheEntry;                                         /* 16 B */
+typedef struct HrptRcacheSample { float position[3]; float valid; float normal[3]; float pad0; float radiance[3]; float pad1; } HrptRcacheSample;   /* 48 B */
+typedef struct HrptRcachePoint { float position[3]; float pad0; float normal[3]; float pad1; } HrptRcachePoint;           /* 32 B */
+typedef struct HrptRcacheSurface { float position[3]; float t; float normal[3]; uint32_t hit; uint32_t rng; uint32_t pad[3]; } HrptRcacheSurface;   /* 48 B */
+typedef struct HrptRcacheParams {
+    uint32_t flags;              /* HRPT_RCACHE_NO_FALLBACK or 0 */
+    uint32_t frameSeed;          /* of the diffuse records, as HrptIndirectParams::frameSeed */
+    uint32_t reserved[2];        /* 0 */
+} HrptRcacheParams;
+typedef struct HrptRcache HrptRcache;
+#define HRPT_RCACHE_RESET           1u   /* update / resolve: empty the table (update: before this frame's samples go in) */
+#define HRPT_RCACHE_NO_FALLBACK     2u   /* indirect: pixels the cache does not serve get zeros instead of a traced path (the reference's behaviour) */
+#define HRPT_RCACHE_NO_WAVE_COMBINE 4u   /* update / insert: one set of atomics per sample instead of per (wave, key); same table, the cross-check */
+/* A cache on `ctx` with an empty table. Destroy it before its context. hrpt_rcache_destroy(NULL) is allowed. */
+int  hrpt_rcache_create(HrptContext* ctx, const HrptRcacheDesc* desc, HrptRcache** out);
+void hrpt_rcache_destroy(HrptRcache* cache);
+/* One frame of filling. Per block (bx, by) of sparseBlock^2 pixels the pixel (bx * B + pcg(bx ^ by << 16 ^ frameIndex) % B, by * B +
+ * pcg(by ^ bx << 16 ^ (frameIndex + 1)) % B), when inside the image, gets the diffuse record of hrpt_indirect_lighting with frameSeed =
+ * frameIndex over the context's G-buffer planes (ALBEDO, NORMAL, GEO_NORMAL, DEPTH, as rendered with `constants`); it is untraced as there
+ * (a miss, !(1 - metallic > 0), a direction below the surface) and also when roughness < roughnessThreshold. On those records, in order:
+ * hrpt_rcache_surfaces_device, hrpt_trace_radiance(DEVICE_POINTERS | SECONDARY), the insert of (surface, L) where the ray hit and the
+ * radiance has w == 1, and the resolve. The camera position of the keys is constants->m_CameraPos. Asynchronous on the context stream;
+ * Accumulation, Output, every plane and history, exposure and HrptStats stay as they were. No scene: HRPT_ERR_NO_SCENE. hrpt_resize not
+ * called, a plane never requested (the message names it), unknown flag bits, a camera position that is not finite, the argument errors of
+ * hrpt_trace_radiance: HRPT_ERR_INVALID_ARGUMENT. An error leaves the table as it was. */
+int  hrpt_rcache_update(HrptRcache* cache, const HrptPathTracerConstants* constants, uint32_t frameIndex, uint32_t flags);
+/* Writes the context's indirect DIFFUSE plane (the plane and the demodulated form of hrpt_indirect_lighting(HRPT_INDIRECT_DIFFUSE), so
+ * hrpt_indirect_compose, the temporal, denoise and upscale stages work on it unchanged; the specular plane is left as it is; planes that
+ * do not exist at this size are allocated zeroed). In order: the full-resolution diffuse records of hrpt_indirect_rays_device for
+ * params->frameSeed, hrpt_rcache_surfaces_device, the query at every hit; a pixel is SERVED when its ray hit, the key was found with
+ * samples > 0 and t >= voxel (the segment spans the voxel, so no surface reads its own voxel); a served pixel's record is overwritten with
+ * the untraced record and the pixel gets (cached.rgb, 1); every other record goes through hrpt_trace_radiance(SECONDARY) and the diffuse
+ * resolve as in hrpt_indirect_lighting (skipped with HRPT_RCACHE_NO_FALLBACK: zeros). A second library-owned plane receives (cached.rgb, 1)
+ * at served pixels and zeros elsewhere. The table is not changed. Errors as hrpt_indirect_lighting; an error changes nothing. */
+int  hrpt_rcache_indirect(HrptRcache* cache, const HrptPathTracerConstants* constants, const HrptRcacheParams* params);
+/* Host read-back of the served plane (synchronises; bytes = width * height * 16; before the first hrpt_rcache_indirect at this size:
+ * HRPT_ERR_INVALID_ARGUMENT). */
+int  hrpt_read_rcache_served(HrptContext* ctx, float* dst, size_t bytes);
+/* Empties the table and zeroes the drop counter; asynchronous on the context stream. */
+int  hrpt_rcache_clear(HrptRcache* cache);
+/* The table: host read-back (synchronises), device pointers (valid until hrpt_rcache_destroy; dropsOut: one uint64, the samples lost to
+ * full buckets since creation / clear) and hrpt_rcache_write, which installs a table (tests, baked caches; synchronises). `entries` must
+ * equal the capacity; any pointer may be NULL (skipped), but write takes keys, accumulation and resolved together and refuses, with
+ * HRPT_ERR_INVALID_ARGUMENT, a table in which a key sits outside its bucket or twice, an empty slot precedes an occupied one or an empty
+ * slot's records are not zero. */
+int  hrpt_rcache_read(HrptRcache* cache, uint64_t* keys, HrptRcacheAccum* accumulation, HrptRcacheEntry* resolved, uint64_t entries, uint64_t* dropsOut);
+int  hrpt_rcache_write(HrptRcache* cache, const uint64_t* keys, const HrptRcacheAccum* accumulation, const HrptRcacheEntry* resolved, uint64_t entries);
+int  hrpt_rcache_get_device(HrptRcache* cache, void** keys, void** accumulation, void** resolved, void** drops);
+/* Position and geometric normal where rays land: surfacesOut[i] = (o + d * t, t, Ng facing the ray, hit 1, the advanced RNG state) for the
+ * closest hit of rays[i] under the rules of hrpt_trace_rays(HRPT_RAYS_CLOSEST) (same t and rng, bit for bit), zeros with hit 0 and the
+ * ray's rng at a miss or a ray that is not finite. Ng = normalize(the interpolated world normal), negated when dot(Ng, d) > 0. DEVICE arrays,
+ * 16-byte aligned; asynchronous on `stream`. No scene: HRPT_ERR_NO_SCENE; more than 2^31 rays or a two-level structure deeper than the
+ * thread-per-query kernels' stack: HRPT_ERR_INVALID_ARGUMENT. */
+int  hrpt_rcache_surfaces_device(HrptContext* ctx, const HrptRay* rays, HrptRcacheSurface* surfacesOut, uint64_t count, void* stream);
+/* The table stages alone over caller-owned arrays of 2^capacityLog2 entries: with no context (_host: host threads, nthreads <= 0 = one per
+ * hardware thread up to 16) or on device memory (_device: asynchronous on `stream`). cameraPos: three finite floats in HOST memory, read before the call returns.
+ * insert: per used sample (valid == 1, position and normal finite; any other sample is skipped and not counted) the bucket is walked from
+ * slot 0 with a compare-and-swap on the key and stops at the first slot that was empty or holds the key; that slot's sums get
+ * (uint64)min(max(L, 0) * radianceScale, 4294967040) per channel (a NaN adds 0) and its count 1. A sample that finds its bucket full adds
+ * 1 to *drops and is lost. Which slot of a bucket a key lands in depends on the order of arrival; the sums do not.
+ * resolve (no insert may run concurrently): per occupied entry with n = count > 0: No = min(samples, maxSamples), mean = (old * No + sum /
+ * radianceScale) / (No + n), samples = min(No + n, maxSamples), stale = 0; with n == 0: stale += 1, above staleFramesMax the entry is
+ * evicted. The survivors of a bucket move to its front in their old order, the accumulation is zeroed and freed slots are zeroed.
+ * HRPT_RCACHE_RESET empties the table instead.
+ * query: out4[i] = (resolved.rgb, 1) when the key of points[i] is present with samples > 0, else zeros; the walk ends at the first empty
+ * slot; voxelOut (may be NULL) receives the voxel size at the point (0 for a point or normal that is not finite). */
+int  hrpt_rcache_insert_host(const HrptRcacheDesc* desc, const float* cameraPos, uint64_t* keys, HrptRcacheAccum* accumulation, uint64_t* drops,
+                             const HrptRcacheSample* samples, uint64_t count, int nthreads);
+int  hrpt_rcache_insert_device(HrptContext* ctx, const HrptRcacheDesc* desc, const float* cameraPos, uint64_t* keys, HrptRcacheAccum* accumulation,
+                               uint64_t* drops, const HrptRcacheSample* samples, uint64_t count, uint32_t flags, void* stream);
+int  hrpt_rcache_resolve_host(const HrptRcacheDesc* desc, uint64_t* keys, HrptRcacheAccum* accumulation, HrptRcacheEntry* resolved, uint32_t flags,
+                              int nthreads);
+int  hrpt_rcache_resolve_device(HrptContext* ctx, const HrptRcacheDesc* desc, uint64_t* keys, HrptRcacheAccum* accumulation, HrptRcacheEntry* resolved,
+                                uint32_t flags, void* stream);
+int  hrpt_rcache_query_host(const HrptRcacheDesc* desc, const float* cameraPos, const uint64_t* keys, const HrptRcacheEntry* resolved,
+                            const HrptRcachePoint* points, float* out4, float* voxelOut, uint64_t count, int nthreads);
+int  hrpt_rcache_query_device(HrptContext* ctx, const HrptRcacheDesc* desc, const float* cameraPos, const uint64_t* keys, const HrptRcacheEntry* resolved,
+                              const HrptRcachePoint* points, float* out4, float* voxelOut, uint64_t count, void* stream);
+
 /* Intra-frame overlap: by default the shadow stage of bounce b runs on a second, library-owned stream next to the traversal of bounce
  * b + 1 (they share no buffer). That fills the tails of a context that renders one frame at a time (-3 % per frame). A host that keeps
  * two frames in flight on two contexts already fills those tails with the other frame; there the fork / join events only cost
